@@ -14,7 +14,13 @@ g[r*2^20 .. (r+1)*2^20) of a (N*2^20)-point MSM (point-range sharding, SURVEY 8e
 each rank reduces its slice, the partial sums are all-gathered (N x 72 bytes) and folded on
 every rank (N group additions on the host, kh_points_sum).  Weak scaling.
 
-Extra objects on the JSON line:
+A plain run does only what the headline needs: set-up, the warm-up (the synchronous steps, then the timed loop once
+untimed), ONE timed region of exactly --steps MSMs, the outputs (--dump-outputs DIR: the affine point the last timed step
+handed back, see dump_outputs) and the line.  --full adds everything below: three timed regions (`value` = the median),
+the synchronous steps after them (latency, per-phase timings, roofline), the host-scalar pipeline, the CPU baseline and the
+oracle parity, the transform and prover blocks, and at N > 1 the strong-scaling run and the check through the other collective.
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel (k_accumulate): algorithmic bytes (96 B per point-scalar pair,
                 SURVEY 8d) / its HIP-event duration, against the 8 TB/s HBM peak
   cpu_baseline  the oracle's C Pippenger (oracle/pasta_ref.c, "port") on this box's host cores,
@@ -525,6 +531,17 @@ def source_hash():
     return h.hexdigest()
 
 
+def dump_outputs(d, result):
+    """--dump-outputs: the MSM result the timed path handed its caller in the last timed step (combined over the ranks at N > 1).
+    DIR/msm_point.npy = [x, y]: each coordinate's four 64-bit limbs as kh_msm_wait returns them, split into eight little-endian 32-bit
+    words, float64 (exact); DIR/msm_point_is_infinity.npy = [1.0] for the point at infinity, else [0.0]."""
+    os.makedirs(d, exist_ok=True)
+    xy = np.asarray(result[0], dtype=np.uint64).reshape(2, 4)
+    words = np.stack([(xy >> np.uint64(s)) & np.uint64(0xffffffff) for s in (0, 32)], axis=2).reshape(2, 8)
+    np.save(os.path.join(d, "msm_point.npy"), words.astype(np.float64))
+    np.save(os.path.join(d, "msm_point_is_infinity.npy"), np.array([1.0 if result[1] else 0.0]))
+
+
 def load_profile(name):
     p = os.path.join(ROOT, "profiles", name)
     try:
@@ -791,7 +808,10 @@ def _main(base):
     ap.add_argument("--curve", choices=["vesta", "pallas"], default="vesta")
     ap.add_argument("--no-pipeline", action="store_true", help="time synchronous MSMs (one in flight); used for the rocprofv3 kernel-stats profile so kernels do not overlap")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--single-region", action="store_true", help="time the region once instead of three times (profiling runs)")
+    ap.add_argument("--single-region", action="store_true", help="with --full: time the region once instead of three times (profiling runs)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure (module docstring): three timed regions, latency, per-phase "
+                    "timings and roofline, host-scalar pipeline, CPU baseline and oracle parity, transform and prover blocks, strong scaling and the other collective")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result of the last timed step to DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: launcher, rank set-up, process group (KH_BENCH_BACKEND=gloo), sharding, the timed loop's submit / wait / combine "
                     "logic and the line, with a stand-in shard whose every MSM 'result' is the SRS blinding base h (host code of the library); value is meaningless (CPU test tier)")
     ap.add_argument("--no-oplist", "--no-prover", dest="no_oplist", action="store_true", help="skip the ProverProof::create block")
@@ -817,7 +837,6 @@ def _main(base):
     wd = Watchdog(rank, world, base)
     wd.phase("process group", 300)
 
-    import torch
     dist = None
     coll_dev = "cpu"
     backend = None
@@ -825,6 +844,9 @@ def _main(base):
     # KH_BENCH_FORCE_COLLECTIVE=1: form the process group and run the combine's collective even in a world of ONE -- how the 1-GPU box
     # exercises the RCCL call paths (torch's `nccl` all-gather of device tensors, and the in-library kh_comm_* one) that N > 1 uses
     force_coll = os.environ.get("KH_BENCH_FORCE_COLLECTIVE", "0") not in ("", "0")
+    torch = None
+    if world > 1 or force_coll or args.full:               # a plain run on one GPU has no use for torch (its import is seconds of set-up)
+        import torch
     if world > 1 or force_coll:
         import torch.distributed as dist_mod
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -865,7 +887,7 @@ def _main(base):
     lib_comm, lib_note = None, None
     want_lib = os.environ.get("KH_BENCH_COMM", "lib" if backend == "nccl" else "torch") == "lib"
     affinity = {"pci": None, "numa_node": None, "cpus_bound": None}
-    if not args.dry_run:
+    if torch is not None and not args.dry_run:
         affinity = bind_rank_to_gpu(torch, dev, world)
     if want_lib and dist is not None and not args.dry_run:
         wd.phase("in-library communicator", 240)
@@ -920,14 +942,15 @@ def _main(base):
     def fence():
         if not args.dry_run:
             khip.sync()
-            torch.cuda.synchronize()
+            if torch is not None:
+                torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
             if not args.dry_run:
                 torch.cuda.synchronize()
 
     def measure(sm_, srs_, d_sc_, n_, nregions, label):
-        """warm-up (synchronous steps: the latency), then `nregions` timed regions of EXACTLY args.steps MSMs each over the shard `srs_` of `sm_`; returns
+        """warm-up (synchronous steps: the latency; then the loop once, untimed), then `nregions` timed regions of EXACTLY args.steps MSMs each over the shard `srs_` of `sm_`; returns
         (region wall times -- max over ranks --, last combined result, last local partial, synchronous step times).  Timed region: `depth` MSMs in flight
         (kh_msm_submit / kh_msm_wait; two by default): the sort of step i+1 and the bucket-reduction tail of step i-1 run underneath the accumulation of
         step i.  Every step is a full MSM whose affine result is fetched and (N>1) combined across ranks INSIDE the region -- on the combiner thread, in
@@ -986,10 +1009,14 @@ def _main(base):
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 el = float(t.item())
             return el
-        # The region runs THREE times back to back (single-region numbers moved 3-5 % box to box and run to run); `value` is the MEDIAN
-        # region, all three are on the line (`value_runs`); ms_per_step x steps is that one region's wall time.
+        # With --full the region runs THREE times back to back (single-region numbers moved 3-5 % machine to machine and run to run); `value` is the
+        # MEDIAN region, all three are on the line (`value_runs`); ms_per_step x steps is that one region's wall time.  A plain run times one region.
         if not args.dry_run:
             khip.set_phase_timers(False)                   # no per-phase HIP events inside the timed regions (the library's default; khip.init switches them on for tools)
+        # The loop runs once untimed before the regions: after the synchronous warm-up (one pipeline slot in use, the GPU idle between MSMs) the first
+        # pipelined region of 20 steps read 0.92-0.94 of the two after it (957 / 1030 / 1042 Mscalar/s).
+        wd.phase(label + ": untimed region", 180)
+        timed_region()
         runs_ = []
         for r_ in range(nregions):
             wd.phase("%s: timed region %d" % (label, r_), 180)
@@ -1000,16 +1027,18 @@ def _main(base):
             combiner.close()
         return runs_, state["result"], state["partial"], sync_ms_, combine_now
 
-    nreg = 1 if args.single_region else 3
+    nreg = 3 if args.full and not args.single_region else 1
     runs, result, last_p, sync_ms, combine = measure(sm, srs, d_sc, n, nreg, "strong" if args.strong else "weak")
     last_partial = [last_p]
     elapsed = sorted(runs)[len(runs) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
 
-    # BOTH scalings from one invocation (round 6): at N > 1 the weak run above is followed by BASELINE config 4 -- ONE 2^22-point MSM whose point range is cut
+    # BOTH scalings from one --full invocation (round 6): at N > 1 the weak run above is followed by BASELINE config 4 -- ONE 2^22-point MSM whose point range is cut
     # over the ranks (2^22 / N points each) -- with its own shard tables, warm-up and timed regions; it rides in the line as `strong` (KH_BENCH_NO_STRONG=1
     # skips it; `--strong` alone still makes config 4 the line's own workload).
     strong_block = None
-    if world > 1 and not args.strong and os.environ.get("KH_BENCH_NO_STRONG", "0") in ("", "0"):
+    if args.full and world > 1 and not args.strong and os.environ.get("KH_BENCH_NO_STRONG", "0") in ("", "0"):
         wd.phase("strong: shard tables", 300)
         s_total = 1 << int(os.environ.get("KH_BENCH_STRONG_LOG_N", "22"))
         sm2 = sharded.RankShardedMsm(CID, s_total, dist=dist, coll_device=coll_dev, engine=sm.engine, rank=rank, world=world, comm=lib_comm, always_collective=force_coll)
@@ -1065,51 +1094,50 @@ def _main(base):
         if dist is not None:
             dist.destroy_process_group()
         return
-    # Per-phase HIP events and the dominant kernel's own start/stop events (hipExtLaunchKernelGGL, on the stream the kernel
-    # is launched on): synchronous steps right AFTER the timed loop, i.e. at the clocks the loop ran at, one MSM in flight
-    # so that kernels do not overlap.  Median of the samples.  The same steps give the single-MSM latency.
-    phase_ms, lat_ms = {}, []
-    for _ in range(5):
-        ts = time.perf_counter()
-        result = combine(*srs.msm_batch_dev(d_sc.ptr, n, 1))
-        lat_ms.append(1e3 * (time.perf_counter() - ts))
-        for name, ms in khip.last_timings():
-            phase_ms.setdefault(name, []).append(ms)
-    phase_avg = {k: float(np.median(v)) for k, v in phase_ms.items()}
-    kname = "k_acc_wide29" if "k_acc_wide29" in phase_avg else ("k_accumulate29" if "k_accumulate29" in phase_avg else "k_accumulate")
-    acc = phase_avg.get(kname, phase_avg.get("accumulate"))
-    latency = float(np.median(lat_ms))
-
     line = {
         "metric": "MSM Mscalar/s at 2^%d (%s)" % (args.log_n, args.curve.capitalize()), "value": value, "unit": "Mscalar/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
         "higher_is_better": True, "scaling": "strong" if args.strong else "weak", "vs_baseline": None, "dtype": "u29x9 / u32x8 (255-bit Montgomery integers)",
-        "data": "synthetic",
+        "data": "synthetic", "full": args.full,
         "config": {"workload": ("msm_2^%d_%s_srs" % (args.log_n, args.curve)) + ("_sharded" if args.strong else ""), "points_per_gpu": n, "points_total": total,
                    "bases": "SRS::<%s>::create" % args.curve.capitalize(),
                    "scalars": "uniform 254-bit, seed 1234+rank", "parallelism": "point-range x%d" % world,
                    "collective_backend": sm.collective_backend, "process_group_backend": backend, "world_size_seen": world,
                    "partials_per_collective": (combine_every if sm.collective_backend else None)},
         "value_runs": [total / (r / args.steps) / 1e6 for r in runs], "value_note": "median of %d back-to-back timed regions of %d MSMs each; ms_per_step x steps = that region" % (len(runs), args.steps),
-        "ranks_reported": world,
-        "latency_value": total / (latency * 1e-3) / 1e6, "latency_note": "one MSM at a time (submit -> wait -> combine): `value` keeps %d in flight" % depth,
-        "ms_per_step_synchronous": latency, "msm_in_flight": depth,
-        "roofline": roofline_block(kname, acc, n, args.log_n) if not args.strong else roofline_block(kname, acc, n, -1),
-        "phases_ms": phase_avg, "srs_create_device_s": t_gen,
+        "ranks_reported": world, "msm_in_flight": depth, "srs_create_device_s": t_gen,
         "combine_thread": bool(dist is not None and (world > 1 or force_coll) and os.environ.get("KH_BENCH_INLINE_COMBINE", "0") in ("", "0")),
-        "rank0_locality": affinity,
     }
+    if args.full:
+        # Per-phase HIP events and the dominant kernel's own start/stop events (hipExtLaunchKernelGGL, on the stream the kernel
+        # is launched on): synchronous steps right AFTER the timed loop, i.e. at the clocks the loop ran at, one MSM in flight
+        # so that kernels do not overlap.  Median of the samples.  The same steps give the single-MSM latency.
+        phase_ms, lat_ms = {}, []
+        for _ in range(5):
+            ts = time.perf_counter()
+            result = combine(*srs.msm_batch_dev(d_sc.ptr, n, 1))
+            lat_ms.append(1e3 * (time.perf_counter() - ts))
+            for name, ms in khip.last_timings():
+                phase_ms.setdefault(name, []).append(ms)
+        phase_avg = {k: float(np.median(v)) for k, v in phase_ms.items()}
+        kname = "k_acc_wide29" if "k_acc_wide29" in phase_avg else ("k_accumulate29" if "k_accumulate29" in phase_avg else "k_accumulate")
+        acc = phase_avg.get(kname, phase_avg.get("accumulate"))
+        latency = float(np.median(lat_ms))
+        line.update({"latency_value": total / (latency * 1e-3) / 1e6, "latency_note": "one MSM at a time (submit -> wait -> combine): `value` keeps %d in flight" % depth,
+                     "ms_per_step_synchronous": latency,
+                     "roofline": roofline_block(kname, acc, n, args.log_n) if not args.strong else roofline_block(kname, acc, n, -1),
+                     "phases_ms": phase_avg, "rank0_locality": affinity})
     if lib_note:
         line["collective_note"] = lib_note
     if strong_block is not None:
         line["strong"] = strong_block
-    if world == 1 and not args.strong:
+    if args.full and world == 1 and not args.strong:
         wd.phase("host-scalar pipeline", 300)
         line.update(host_scalars_block(khip, srs, sc, n, args.steps, int(os.environ.get("KH_BENCH_HOST_DEPTH", "3")), result))     # 2 / 3 in flight: 798-849 / 901-933 Mscalar/s (profiles/r06_host_msm.txt)
 
     # parity at full size, every rank: its partial against the oracle on its own slice; rank 0 then folds the oracle's
     # partials with the oracle's group law and compares with the combined GPU result
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         wd.phase("parity against the oracle / cpu baseline", 900)
         from oracle import cref          # cpu_baseline / checker leg only
         g = srs.get_g()
@@ -1138,18 +1166,18 @@ def _main(base):
             line["parity_error"] = "GPU result differs from the CPU oracle"
 
     wd.phase("transform and prover blocks", 1800)
-    if rank == 0 and world == 1 and not args.no_oplist and args.curve == "vesta" and not args.strong:
+    if args.full and rank == 0 and world == 1 and not args.no_oplist and args.curve == "vesta" and not args.strong:
         line["ntt_kernels"] = ntt_block(khip)
         line["prover"] = prover_block(khip, srs, check_with_oracle=not args.no_cpu_baseline)
         if not args.no_pair:
             line["prover"]["pair"] = pair_block(khip, check_with_oracle=not args.no_cpu_baseline)
 
-    # Both collectives in ONE run: whichever did not carry the timed loop repeats the last step's combine afterwards (never timed into `value`) and
+    # Both collectives in ONE --full run: whichever did not carry the timed loop repeats the last step's combine afterwards (never timed into `value`) and
     # must land on the same point -- the driver's N > 1 runs thereby execute the in-library RCCL path too.  Guarded by a watchdog: a collective
     # that hangs costs the check, not the line.
     hung = False
     wd.phase("the other collective", 240)
-    if dist is not None and backend == "nccl" and last_partial[0] is not None:
+    if args.full and dist is not None and backend == "nccl" and last_partial[0] is not None:
         line["other_collective"], hung = other_collective_check(khip, dist, sm, lib_comm, last_partial[0], result, rank, world, coll_dev)
     wd.phase("teardown", 120)
     # LAST on the line (the driver's record keeps the tail of the output): both halves of BASELINE's metric and what pins them

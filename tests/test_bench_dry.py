@@ -10,17 +10,17 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _launch(gpus, extra_env=None):
+def _launch(gpus, extra_env=None, args=("--full",)):
     env = dict(os.environ, KH_BENCH_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "1", "--dry-run"],
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "1", "--dry-run"] + list(args),
                           env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
 
 
-def _run(gpus, extra_env=None):
-    r = _launch(gpus, extra_env)
+def _run(gpus, extra_env=None, args=("--full",)):
+    r = _launch(gpus, extra_env, args)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout.decode()
@@ -61,6 +61,23 @@ def test_bench_dry_combine_runs_off_the_submit_thread():
     assert line["combine_thread"] is False and line["combined_result_is_world_times_h"] is True
     line, _ = _run(2, {"KH_BENCH_COMBINE_EVERY": "2"})              # two partial sums per collective
     assert line["combined_result_is_world_times_h"] is True and line["config"]["partials_per_collective"] == 2
+
+
+def test_bench_dry_plain_run_times_one_region_and_dumps_the_last_result(tmp_path):
+    """Without --full: one timed region of exactly --steps MSMs, no strong-scaling run; --dump-outputs writes the combined result of the last
+    timed step (here world x h) as 32-bit words in float64."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import proof_systems_amd.khip as khip
+    h = khip.srs_h(khip.VESTA)
+    want, _ = khip.points_sum(khip.VESTA, np.stack([h, h]), np.zeros(2, np.uint8))
+    want = np.asarray(want, dtype=np.uint64).reshape(8)
+    line, _ = _run(2, args=("--dump-outputs", str(tmp_path)))
+    assert line["steps"] == 5 and len(line["value_runs"]) == 1 and line["strong"] is None and line["combined_result_is_world_times_h"] is True
+    pt, inf = np.load(tmp_path / "msm_point.npy"), np.load(tmp_path / "msm_point_is_infinity.npy")
+    assert pt.dtype == np.float64 and pt.shape == (2, 8) and inf.tolist() == [0.0]
+    words = pt.astype(np.uint64).reshape(8, 2)
+    assert np.array_equal(words[:, 0] | (words[:, 1] << np.uint64(32)), want)
 
 
 def test_bench_dry_failed_rank_ends_the_run_with_an_error_line():

@@ -62,7 +62,7 @@ def test_world_of_one_nccl_and_library_collectives(tmp_path):
 
 @pytest.mark.parametrize("comm,timed,other", [("torch", "nccl-torch", "rccl-lib"), ("lib", "rccl-lib", "nccl-torch")])
 def test_bench_line_names_the_collective_that_ran(comm, timed, other):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--log-n", "14", "--no-oplist"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--log-n", "14", "--no-oplist", "--full"]
     p = subprocess.run(cmd, env=_env(KH_BENCH_FORCE_COLLECTIVE="1", KH_BENCH_COMM=comm, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_PORT="29717"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
