@@ -472,9 +472,9 @@ int kh_sync(void);
  * capacity cap; returns the number of phases written. */
 int kh_last_timings(const char **names, float *ms, int cap);
 /* Process-wide event counters (how often a path ran): "spread_retry" (an opening round's MSM met a hot bucket and was re-run with the hot-bucket
- * kernels), "fused_retry" (the one-launch sort gave up), "graph_replay" / "graph_capture" (replayed / captured launch sequences), "rebase_launch" /
- * "rebase_switch" / "rebase_abandon" (openings that started materialising the folded basis of their late rounds, switched over to it, gave it up),
- * "rebased_rounds" (rounds that ran over a materialised basis).  Unknown names read 0. */
+ * kernels), "fused_retry" (the one-launch sort gave up), "rebase_launch" / "rebase_switch" / "rebase_abandon" (openings that started
+ * materialising the folded basis of their late rounds, switched over to it, gave it up), "rebased_rounds" (rounds that ran over a materialised
+ * basis).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,

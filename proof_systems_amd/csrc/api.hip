@@ -36,7 +36,7 @@ static thread_local Context* tl_private[KH_MAX_DEVICES];
 static std::vector<Context*> g_private_pool[KH_MAX_DEVICES];           // idle private contexts (guarded by g_ctx_mu)
 static std::atomic<int> g_private_made[KH_MAX_DEVICES];                 // private contexts ever created per device (they are never destroyed)
 static int g_private_active[KH_MAX_DEVICES];                             // threads between kh_private_context_begin and _end per device (guarded by g_ctx_mu)
-// a thread keeps the context it used last (its workspaces, captured graphs and staging ring stay warm for its next proof) and hands it to the pool when it
+// a thread keeps the context it used last (its workspaces and staging ring stay warm for its next proof) and hands it to the pool when it
 // exits -- no HIP call in the destructor, only the list
 struct ThreadContextCache {
     Context* c[KH_MAX_DEVICES] = {nullptr};
@@ -318,7 +318,7 @@ DevPool& dev_pool() { static DevPool p; return p; }
 size_t pool_limit() { static const size_t lim = (getenv("KH_POOL_MAX_MB") ? (size_t)atol(getenv("KH_POOL_MAX_MB")) : 2048) << 20; return lim; }
 }  // namespace
 // transfer buffers of the host-pointer transforms (kh_ntt / kh_lde: host_transform below)
-struct XferPair { DevBuf in, out; bool busy = false, owned = false; XferPair() { in.graph_keyed = false; out.graph_keyed = false; } };
+struct XferPair { DevBuf in, out; bool busy = false, owned = false; };
 static std::mutex g_xfer_mu;
 static std::vector<std::unique_ptr<XferPair>>& xfer_registry(int d) {     // (never destroyed: no hipFree from a static destructor after the runtime has gone)
     static auto* r = new std::vector<std::unique_ptr<XferPair>>[KH_MAX_DEVICES];
@@ -386,7 +386,6 @@ int kh_trim(void) {
     }
     for (int i = 0; i < MSM_SLOTS; i++) {
         MsmSlot& S = C.slot[i];
-        if (S.gexec) { (void)hipGraphExecDestroy(S.gexec); S.gexec = nullptr; S.gkey = 0; S.gseen = 0; }
         for (DevBuf* b : {&S.ws_scalars, &S.ws_digits, &S.ws_hist, &S.ws_cnt, &S.ws_off, &S.ws_ntask, &S.ws_toff, &S.ws_entries, &S.ws_partial, &S.ws_buckets,
                           &S.ws_seg, &S.ws_out, &S.ws_scan_tmp, &S.ws_biglist, &S.ws_points, &S.ws_order, &S.ws_chunks, &S.ws_handed, &S.ws_sync, &S.ws_mid,
                           &S.ws_b29, &S.ws_a1, &S.ws_a2, &S.ws_xlist}) b->release();
@@ -705,8 +704,8 @@ static int free_slot(Context& C) {
 // a caller may wait for a slot that another thread is blocked on (it will be released) or that holds ANOTHER thread's un-waited
 // kh_msm_submit ticket (more provers than slots: that thread is on its way to kh_msm_wait) -- the latter for two seconds at most, in case
 // the tickets' owners are themselves waiting here; with only the caller's own un-waited tickets busy the answer is -1 at once
-// side_first: take a slot other than the main stream's when one is free -- a job that may CAPTURE its launch sequence into a hipGraph
-// must not do so on the stream other host threads synchronise and launch on (a capture is invalidated by, and invalidates, such calls)
+// side_first: take a slot other than the main stream's when one is free (the opening rounds: their MSM then runs beside, not behind,
+// the work other host threads queue on the main stream)
 // Back-pressure, not a time-out: the caller blocks until a slot is released (an oversubscribed rayon pool must see a slow call, not
 // a spurious error).  The one case that can never resolve is refused at once: every busy slot holds an un-waited ticket whose owner
 // is itself blocked in here (or is the caller) -- nobody is left to call kh_msm_wait.
@@ -797,7 +796,7 @@ static thread_local double tl_last_wait_us = 0;           // spin / block part o
 static int wait_then_finish(std::unique_lock<std::mutex>& lk, Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf) {
     hipEvent_t ev = S.done;
     // completion by flag (MsmSlot::done_flag): what the job's last kernel will store, read while the context is still locked
-    const bool by_flag = S.done_by_flag && S.done_flag;
+    const bool by_flag = S.job.done_by_flag && S.done_flag;
     const uint32_t expect = S.done_expect;
     C.sync_inflight++;
     lk.unlock();
@@ -1632,7 +1631,7 @@ struct kh_ipa {
     std::vector<uint64_t> tab;            // H / U window multiples staged for the asynchronous upload of kh_ipa_begin
     int sg_slot = -1;                     // pipeline slot holding the two half-sums of sg launched during the last round (kh_ipa_open), -1: none
     bool sg_want = false;                 // kh_ipa_open asks the last kh_ipa_round_lr to launch them
-    std::vector<hipGraphExec_t> retired;  // the previous opening's executable graphs: destroyed underneath the first round's GPU time
+    bool spread_broken = false;           // a round's MSM disproved MSM_SPREAD_SCALARS (MsmJob::spread_rerun): the later rounds run without the hint
     bool rb_glv = false;                          // the folded basis's tables are GLV tables (half the doubling chain; MsmBasis::glv)
     void* round_tab = nullptr; int round_c = 0;   // table set the round MSMs run over (the SRS's own, or its narrower-window second set)
     size_t tab_stride = 0;                        // points per window table of that set (the SRS's g_stride; N + 2 after the rebase)
@@ -1669,22 +1668,7 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     } claim{srs};
     Context& C = ctx();
     std::unique_lock<std::mutex> lk(C.mu);
-    C.spread_suspended = false;                         // a new opening has new scalars: its rounds run under MSM_SPREAD_SCALARS again until one of them disproves it
-    // A graph of the round MSM is captured and replayed WITHIN one opening only (nothing allocates or frees device memory
-    // between the rounds of an opening); replaying it after the caller has freed and allocated buffers in between faulted
-    // on ROCm 7.2 when another HIP user (PyTorch) shared the process.  Re-capturing costs one extra un-graphed round.
-    static const bool graph_reset = !(getenv("KH_GRAPH_KEEP") && atoi(getenv("KH_GRAPH_KEEP")) != 0);
     static const bool begin_timing = getenv("KH_IPA_TIMING") != nullptr;
-    std::vector<hipGraphExec_t> retired;
-    const auto b0_ = std::chrono::steady_clock::now();
-    if (graph_reset)
-        for (int i = 0; i < MSM_SLOTS; i++) {
-            MsmSlot& S = C.slot[i];
-            if (S.busy) continue;
-            if (S.gexec && S.gscalars != srs->ipa_sc.p) continue;                // another handle's opening, between two of its rounds: not ours to retire
-            if (S.gexec) { retired.push_back(S.gexec); S.gexec = nullptr; }      // destroyed while the first round runs (~0.2 ms of host time each)
-            S.gkey = 0; S.gseen = 0; S.gscalars = nullptr;
-        }
     const auto b1_ = std::chrono::steady_clock::now();
     std::unique_ptr<kh_ipa> st(new kh_ipa);
     st->srs = srs; st->curve = srs->curve; st->field = khost::scalar_field_id(srs->curve); st->n = n; st->cur = n;
@@ -1787,10 +1771,9 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     KH_HIP(hipEventRecord(st->ev, s));
     if (begin_timing) {
         auto us = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
-        fprintf(stderr, "kh_ipa_begin: graph reset %.0f us, workspace %.0f, U multiples %.0f, uploads + copies %.0f\n", us(b0_, b1_), us(b1_, b2_), us(b2_, b3_), us(b3_, std::chrono::steady_clock::now()));
+        fprintf(stderr, "kh_ipa_begin: workspace %.0f us, U multiples %.0f, uploads + copies %.0f\n", us(b1_, b2_), us(b2_, b3_), us(b3_, std::chrono::steady_clock::now()));
     }
     claim.keep = true;
-    st->retired = std::move(retired);
     *out = st.release();
     return KH_OK;
 }
@@ -1807,7 +1790,7 @@ int kh_ipa_rounds_left(const kh_ipa_t* st) {
 }
 // During the LAST round of an opening: the two halves of sg (ipa.hip: k_sg_split) as one batch of two MSMs on a side slot.  They need only the
 // challenges of the earlier rounds, so they run underneath the last round instead of after it (0.39 ms of every opening); queued right
-// behind the round's own launches, so that their ~15 un-graphed launches overlap its execution.  `p` / `had_fold`: the challenge tensor as it
+// behind the round's own launches, so that their ~15 launches overlap its execution.  `p` / `had_fold`: the challenge tensor as it
 // was BEFORE the round's step kernel (which only reads it).  Quietly does nothing when no other slot is free: kh_ipa_open then computes
 // sg the plain way.  Called with the library lock held.
 static void ipa_sg_prelaunch_locked(kh_ipa_t* st, Context& C, int p, bool had_fold) {
@@ -1892,20 +1875,14 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
         else { (void)hipGetLastError(); (void)hipStreamSynchronize(rs); st->rb_state = -1; counter(CNT_REBASE_ABANDON)++; }
     }
     MsmBasis bs; bs.pts = st->round_tab; bs.inf = nullptr; bs.n = st->tab_stride; bs.stride = st->tab_stride; bs.precomp_c = st->round_c; bs.glv = st->rb_state == 3 && st->rb_glv;
-    // Plain launches by default since round 5: the round's MSM is down to six launches (digits, one-launch sort, accumulation, bucket sums, two reduction
-    // kernels) which the host queues in ~25 us while the step kernel runs; replaying a captured graph (KH_IPA_GRAPH=1, rounds 2-4's way: every opening
-    // captures afresh in its second round) measured 5.58 / 5.53 / 5.65 ms per opening against 5.49 / 5.47 / 5.51 plain, alternated on one box.
-    static const int round_flags = ((getenv("KH_IPA_GRAPH") && atoi(getenv("KH_IPA_GRAPH")) != 0) ? MSM_REPEATS : 0) | MSM_SPREAD_SCALARS | MSM_LATENCY;
+    // The round's MSM is six launches (digits, one-launch sort, accumulation, bucket sums, two reduction kernels) which the host queues in ~25 us while
+    // the step kernel runs.  Its scalars are products with Fiat-Shamir challenges (MSM_SPREAD_SCALARS) until a round of this opening proves otherwise.
+    const int round_flags = (st->spread_broken ? 0 : MSM_SPREAD_SCALARS) | MSM_LATENCY;
     if ((rc = msm_enqueue(C, S, st->curve, bs, 0, st->sc->as<uint64_t>(), st->n + 2, 2, 1, round_flags))) return rc;
     if (st->sg_want && st->cur == 2) { st->sg_want = false; ipa_sg_prelaunch_locked(st, C, p, had_fold); }
-    if (!st->retired.empty()) {                           // the GPU is busy with this round for the next ~0.3 ms; other callers are not held up:
-        std::vector<hipGraphExec_t> gone; gone.swap(st->retired);
-        lk.unlock();                                      // the slot stays busy (ours), so nothing of this opening can be touched meanwhile
-        for (hipGraphExec_t g : gone) (void)hipGraphExecDestroy(g);
-        lk.lock();
-    }
     const auto pt3 = std::chrono::steady_clock::now();
     if ((rc = wait_then_finish(lk, C, S, lr_xy, lr_inf))) return rc;
+    if (S.job.spread_rerun) st->spread_broken = true;     // (the lock is held again: the slot's job is still this round's)
     if (prof) {
         IpaRoundProf& P = tl_round_prof;
         const double total_wait_finish = us_since(pt3);
@@ -2025,8 +2002,6 @@ void kh_ipa_free(kh_ipa_t* st) {
     if (!st) return;
     kh::DeviceScope dev_scope_(st->srs ? st->srs->device : -1);
     Context& C = ctx();
-    for (hipGraphExec_t g : st->retired) (void)hipGraphExecDestroy(g);
-    st->retired.clear();
     if (st->sg_slot >= 0) {                                // an opening that failed after launching the halves of sg: release their slot
         uint64_t ab[16]; uint8_t abi[2];
         std::unique_lock<std::mutex> ul(C.mu);
@@ -2216,7 +2191,6 @@ struct HostXferEvents {
 // afresh: 16 concurrent extensions took 11.6 ms inside bench.py's process against 5.2 ms in a fresh one.  The buffers live in a per-device REGISTRY, not in
 // thread-local storage: a thread holds a pair while it exists (a rayon worker lives as long as its pool) and hands it back at exit without
 // freeing anything (no hipFree from a TLS destructor); the next new thread adopts it; kh_trim frees every pair that is not inside a call at that moment.
-// They are not part of the hipGraph key (no captured launch sequence reads them): growing or freeing one does not retire the MSM graphs.
 static size_t xfer_keep_bytes() {          // per buffer, per thread; KH_XFER_KEEP_MB overrides.  64 MB holds what the reference's callers hand over one column at
     static const size_t v = getenv("KH_XFER_KEEP_MB") ? (size_t)atol(getenv("KH_XFER_KEEP_MB")) << 20 : (size_t)64 << 20;   // a time (2 MB in, 16 MB out at 2^16 -> 2^19) and a
     return v;                              // few columns batched; a 16-column batched extension (268 MB out) pays its allocation each time (~5 ms of PCIe beside it)
@@ -2329,7 +2303,7 @@ int kh_dev_alloc(void** ptr, size_t bytes) {
                 if (!hand_over[d]) e = hipEventCreateWithFlags(&hand_over[d], hipEventDisableTiming);
                 if (e == hipSuccess) {
                     std::lock_guard<std::mutex> g(me->mu);
-                    e = hipEventRecord(hand_over[d], prev->stream);         // (main streams are never captured into a graph: recording from here is fine)
+                    e = hipEventRecord(hand_over[d], prev->stream);
                     if (e == hipSuccess) e = hipStreamWaitEvent(me->stream, hand_over[d], 0);
                     if (e == hipSuccess) me->mark_async();                  // ... and this context's side slots behind its main stream
                 }
@@ -2409,8 +2383,7 @@ int kh_dev_fill_elements(uint64_t* dst_dev, const uint64_t value[4], size_t coun
 // The library's streams are non-blocking (they do not synchronise with the null stream hipMemcpy uses), so both copies
 // first wait for the main stream: an asynchronous kh_ntt_dev / kh_lde_dev on this buffer is complete before it is read
 // or overwritten.
-// The copies themselves run on a per-thread non-blocking stream, not on the legacy stream: a legacy-stream operation is refused ("would
-// make the legacy stream depend on a capturing ... stream") while ANOTHER host thread captures an opening round's MSM into a hipGraph.
+// The copies themselves run on a per-thread non-blocking stream, not on the legacy stream.
 int kh_dev_upload(void* dst_dev, const void* src_host, size_t bytes) {
     int rc = ensure_init(); if (rc) return rc;
     if (bytes == 0) return KH_OK;

@@ -50,14 +50,8 @@ struct DevBuf {
     DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
     ~DevBuf() { release(); }
-    // bumped by every (re)allocation / release of any workspace buffer: part of the hipGraph key, so that a captured launch sequence can
-    // never be replayed across a reallocation -- not even one that hands the same address back (defence in depth: every pointer the
-    // launches bake in is in the key as well)
-    static std::atomic<uint64_t>& generation() { static std::atomic<uint64_t> g{1}; return g; }
-    bool graph_keyed = true;                  // false: a buffer no captured launch sequence ever reads (the host-pointer transforms' transfer buffers)
     int reserve(size_t bytes) {
         if (bytes <= cap) return KH_OK;
-        if (graph_keyed) generation()++;
         if (p) { hipError_t e = hipFree(p); (void)e; p = nullptr; cap = 0; }
         size_t want = bytes + bytes / 8;
         hipError_t e = hipMalloc(&p, want);
@@ -65,7 +59,7 @@ struct DevBuf {
         cap = want;
         return KH_OK;
     }
-    void release() { if (p) { hipError_t e = hipFree(p); (void)e; if (graph_keyed) generation()++; } p = nullptr; cap = 0; }
+    void release() { if (p) { hipError_t e = hipFree(p); (void)e; } p = nullptr; cap = 0; }
     template <class T> T* as() const { return (T*)p; }
 };
 
@@ -93,8 +87,37 @@ struct PhaseTimer {
     }
 };
 
+struct MsmBasis {
+    const void* pts = nullptr;       // device, n x 64 B affine x||y (Montgomery); with precomp: W tables of n points
+    const uint8_t* inf = nullptr;    // device, nullable per-point infinity flags
+    size_t n = 0;                    // points per table
+    int precomp_c = 0;               // 0: plain basis; else window width of the precomputed tables
+    size_t stride = 0;               // points between consecutive window tables (0: = n)
+    size_t batch_stride = 0;         // >0: MSM j of a batch uses points [j*batch_stride, ...) (independent bases)
+    const void* wide_pts = nullptr;  // a second table set of the SAME basis with wide windows (same stride), used for big single MSMs
+    int wide_c = 0;
+    bool glv = false;                // the tables hold 2^(c w) P for the lower 128 bits and phi(2^(c w) P) behind them: scalars are split k = k1 + k2 lambda (rebase.hip)
+};
+
+// The job a slot has in flight: assigned once by msm_enqueue, read by msm_finish
+struct MsmJob {
+    // the inputs (msm_finish re-runs the job from them when the fused sort gave up or the spread hint did not hold)
+    MsmBasis basis;
+    size_t offset = 0;
+    const uint64_t* scalars = nullptr;
+    size_t n = 0, k = 0;
+    int mont = 0, curve = 0;
+    // what msm_finish folds and how the job ends
+    int W = 0, c = 0, precomp = 0, planes = 0, plane_shift[2] = {0, 0};
+    int wide_lo = 0;                   // wide windows: bits of the low bucket digit (0: the narrow path); msm_finish folds two marginal groups per MSM
+    size_t ngroups = 0;                // 0: nothing was launched (n == 0 or k == 0), the results are k identities
+    bool done_by_flag = false;         // the last kernel stores the slot's launch count into done_flag (MsmSlot)
+    bool fused = false, spread = false;    // ran the one-launch sort / under MSM_SPREAD_SCALARS
+    bool spread_rerun = false;         // set by msm_finish: the spread hint did not hold and the job was re-run without it
+};
+
 // One MSM pipeline slot: its own stream, workspace and result staging, so that several MSMs can be in
-// flight (kh_msm_submit / kh_msm_wait).  k_accumulate is held to 112 VGPRs so that the sort kernels
+// flight (kh_msm_submit / kh_msm_wait).  k_accumulate29 is held to 112 VGPRs so that the sort kernels
 // (4-16 VGPRs) of the NEXT job fit beside its 4 waves per SIMD: with three slots the sort of job i+2
 // and the latency-bound tail of job i both run underneath the accumulation of job i+1.
 struct MsmSlot {
@@ -105,29 +128,17 @@ struct MsmSlot {
         ws_b29, ws_a1, ws_a2, ws_xlist;                              // wide windows (c = 20): lazy buckets, first-level chunk sums, the 2 x 2^lo marginals
     void* pinned = nullptr; size_t pinned_cap = 0;      // host staging of the group sums (XYZZ)
     hipEvent_t done = nullptr;
-    // pending job (set by enqueue, consumed by finish)
-    bool busy = false;
+    bool busy = false;                 // a job is pending (set by enqueue, cleared by finish)
     std::thread::id owner;             // the host thread that queued the pending job (acquire_slot: another thread's ticket will be waited for)
     uint64_t ticket = 0;
-    int curve = 0, W = 0, c = 0, precomp = 0, planes = 0, plane_shift[2] = {0, 0};
-    int wide_lo = 0, g_wide_lo = 0;    // wide windows: bits of the low bucket digit (0: the narrow path); msm_finish folds two marginal groups per MSM
-    size_t k = 0, ngroups = 0;
-    // hipGraph of one MSM's launch sequence (the opening rounds repeat the same MSM -- same basis, scalar buffer, sizes --
-    // 16 times: ~22 launches per round replayed as one graph).  Keyed by every pointer and size the launches bake in.
-    hipGraphExec_t gexec = nullptr;
-    uint64_t gkey = 0, gseen = 0;
-    const void* gscalars = nullptr;   // the scalar buffer the captured launch sequence reads (an opening's: its SRS handle's ipa_sc)
-    size_t gnout = 0;
-    int g_W = 0, g_c = 0, g_precomp = 0, g_planes = 0, g_shift[2] = {0, 0};
-    size_t g_ngroups = 0;
+    MsmJob job;
     // the one-launch sort (k_sort_fused) spins on grid barriers and needs all its blocks resident at once; if another PROCESS shares the
     // GPU they may never be -- its barriers then give up after a bounded spin, set this host-visible word, and msm_finish re-runs the job
-    // with the multi-launch sort (the arguments of the pending job are kept for that) and disables the fused path for the process
+    // with the multi-launch sort and disables the fused path for the process
     volatile uint32_t* host_abort = nullptr;          // pinned host memory, written by the kernel
     // MSM_SPREAD_SCALARS was a wrong promise: k_bucket_sum_q met a bucket with more task partials than a quad may sum in sequence, stored this word
-    // (pinned) and left the bucket empty; msm_finish re-runs the job with the hot-bucket kernels and suspends the hint (Context::spread_suspended)
+    // (pinned) and left the bucket empty; msm_finish re-runs the job with the hot-bucket kernels (and reports it: MsmJob::spread_rerun)
     volatile uint32_t* spread_abort = nullptr;
-    bool spread_used = false, g_spread = false;
     bool flag_unavailable = false;                     // no coherent host allocation for done_flag / pinned: completion by event
     bool pinned_coherent = false;
     // Completion by flag (round 5): when a job's LAST kernel is k_marginal_fin_q (it writes the result into `pinned` itself), the last block of that
@@ -136,9 +147,6 @@ struct MsmSlot {
     volatile uint32_t* done_flag = nullptr;           // pinned host memory
     DevBuf ws_done;                                    // [0] blocks finished in the running launch, [1] launches finished
     uint32_t done_expect = 0;                          // launches enqueued with the flag so far (what done_flag shows when the newest one has ended)
-    bool done_by_flag = false, g_done_by_flag = false; // the job in flight (the captured graph) ends with the flag store
-    bool fused_used = false, g_fused = false;
-    struct { const void* pts; const uint8_t* inf; size_t bn, stride, batch_stride; int precomp_c; size_t offset; const uint64_t* scalars; size_t n, k; int mont, curve; bool glv; } retry{};
 };
 static constexpr int MSM_SLOTS = 4;
 
@@ -154,7 +162,6 @@ struct Context {
     hipEvent_t order_ev = nullptr;     // orders device-resident producers on the main stream before an MSM on another slot's stream
     int num_cus = 256;
     size_t lds_per_cu = (size_t)160 << 10, lds_per_block = (size_t)64 << 10;    // hipDeviceProp: what holds k_acc_wide29 to a block count per CU
-    bool spread_suspended = false;     // an MSM under MSM_SPREAD_SCALARS met a hot bucket: the hint is ignored until the caller's next opening (kh_ipa_begin)
     bool fused_disabled = false;       // a k_sort_fused launch could not get all its blocks resident (shared GPU): multi-launch sort from then on
     PhaseTimer timer;                  // NTT / LDE phases (MSM phases are per slot)
     // last timings (filled after a sync)
@@ -199,8 +206,8 @@ struct DeviceScope {               // run the rest of this scope on `device` (no
 };
 void collect_timings(Context& c, PhaseTimer& t);
 // process-wide event counters behind kh_counter (tests and tools read them: how often a rare path ran).  `name` must be one of COUNTER_NAMES.
-enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_GRAPH_REPLAY, CNT_GRAPH_CAPTURE, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_COUNT };
-static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "graph_replay", "graph_capture", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds"};
+enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_COUNT };
+static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds"};
 std::atomic<uint64_t>& counter(CounterId id);
 
 // device exclusive scan of n u32 values (in may alias out); tmp is workspace

@@ -998,51 +998,11 @@ k_wide_fixup(u32* __restrict__ toff, const u32* __restrict__ ptot, u32 nparts, u
     if (key == 0) handed[0] = 0;                           // (big[0], the hot-bucket count, belongs to pass B on this path)
 }
 // ------------------------------------------------------------------------------------ 5 accumulate
-template <class BF>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(112)))
-k_accumulate(const u32* __restrict__ entries, const u32* __restrict__ off, const u32* __restrict__ toff,
-             const u32* __restrict__ roff, const u32* __restrict__ order,
-             size_t nkeys, const uint8_t* __restrict__ pts, uint8_t* __restrict__ partial, const u32* __restrict__ only, const u32* __restrict__ abort_dev) {
-    KH_HIGH_PRIO();
-    if (sort_gave_up(abort_dev)) return;
-  // `only` = the hand-over list of k_accumulate29 ([0] = count, then task ids): a small persistent grid walks it (almost always
-  // empty -- a full-size grid of early-exit blocks took 0.6 ms to drain underneath the next job's accumulation)
-  const size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = only ? (size_t)gridDim.x * blockDim.x : 0;
-  const size_t count = only ? only[0] : 1;
-  for (size_t it = only ? first : 0; it < count; it += stride ? stride : 1) {
-    size_t t = only ? only[1 + it] : first;
-    u32 NT = roff[nkeys];
-    if (t >= NT) return;
-    // binary search over the length-ranked keys: largest rank with roff[rank] <= t
-    size_t lo = 0, hi = nkeys;           // invariant roff[lo] <= t < roff[hi]
-    while (hi - lo > 1) {
-        size_t mid = (lo + hi) >> 1;
-        if (roff[mid] <= (u32)t) lo = mid; else hi = mid;
-    }
-    size_t key = order ? order[lo] : lo;
-    u32 jt = (u32)t - roff[lo];
-    t = (size_t)toff[key] + jt;          // the partial's slot stays in key order (k_bucket_sum)
-    // balanced split of the bucket's entries over its nt = ceil(cnt / K) tasks: the lanes of a wave
-    // run (almost) equally long chains instead of nt-1 full tasks + a short remainder
-    u32 o0 = off[key], cnt = off[key + 1] - o0, nt = toff[key + 1] - toff[key];
-    u32 start = o0 + (u32)(((u64)jt * cnt) / nt);
-    u32 end = o0 + (u32)(((u64)(jt + 1) * cnt) / nt);
-    u32 e = entries[start];
-    Aff<BF> p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
-    if (e >> 31) p.y = neg<BF>(p.y);
-    Xyzz<BF> acc = Xyzz<BF>::from_affine(p);
-    for (u32 k = start + 1; k < end; k++) {
-        e = entries[k];
-        p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
-        acc = madd<BF>(acc, p, (e >> 31) != 0);
-    }
-    acc.store(partial + t * 128);
-  }
-}
-// The same task in the lazy 29-bit-limb arithmetic of field29.cuh (186 instead of 254 instructions per product, no
-// carry chains in the subtractions).  Its values are not canonical, so it cannot decide the exceptional cases of the
-// group law; it only notices that one cannot be excluded (probability ~2^-25 per addition on random inputs), abandons
-// the lazy state and redoes the task on the spot with the exact formulas of curve.cuh.  Finished
+// One thread per task: the task's share of its bucket's entries (the gathered table points) summed into one XYZZ partial, in the
+// lazy 29-bit-limb arithmetic of field29.cuh (186 instead of 254 instructions per product, no carry chains in the subtractions).
+// Its values are not canonical, so it cannot decide the exceptional cases of the group law; it only notices that one cannot be
+// excluded (probability ~2^-25 per addition on random inputs), abandons the lazy state and redoes the task on the spot with the
+// exact formulas of curve.cuh.  Finished
 // tasks are converted to the canonical wire form, so everything downstream is unchanged and the result stays bit-exact.
 // Occupancy is CAPPED at 4 waves per SIMD although 92 VGPRs would allow 5: the sort kernels of the next job (k_hist / k_scatter:
 // 1024-thread blocks = 4 waves per SIMD, 128 KB of LDS) must find four free wave slots on every CU to run underneath this kernel;
@@ -1824,10 +1784,6 @@ int msm_pick_window(size_t n) {
     return c;
 }
 
-struct CaptureGuard {              // never leave a stream in capture mode on an error path
-    hipStream_t s; bool active = false;
-    ~CaptureGuard() { if (active) { hipGraph_t g = nullptr; (void)hipStreamEndCapture(s, &g); if (g) (void)hipGraphDestroy(g); } }
-};
 // the task-length table of pick_K for a launch with `nkeys` buckets on `cus` compute units (cached per bucket count)
 static KTab task_length_table(size_t nkeys, u32 cus) {
     static std::mutex mu;
@@ -1855,11 +1811,10 @@ static KTab task_length_table(size_t nkeys, u32 cus) {
     cache[{nkeys, cus}] = t;
     return t;
 }
-static inline uint64_t fnv(uint64_t h, uint64_t v) { for (int i = 0; i < 8; i++) { h ^= (v >> (8 * i)) & 0xff; h *= 0x100000001b3ull; } return h; }
 
 template <class CFG>
 static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t offset, const u64* scalars_dev, size_t n, size_t k,
-                         int mont, int curve, int use_graph, const MsmHostScalars* hs) {
+                         int mont, int curve, int flags, const MsmHostScalars* hs) {
     typedef typename CFG::Base BF; typedef typename CFG::Scalar SF;
     hipStream_t s = C.stream;
     // wide windows (a second table set, c = 20: msm.hpp) for big single MSMs: 13 instead of 16 additions per scalar.  Needs the wide sort's
@@ -1871,10 +1826,8 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     // the ~340 us of an opening round) and a bucket's quad sums however many task partials it finds -- correct for any input, slow for a skewed one.
     // The promise is checked, not trusted: a bucket with more than SPREAD_MAX_NT task partials (a constant or sparse polynomial from a
     // degenerate or adversarial witness puts n / K of them into one bucket per window) is left empty and reported through a pinned word; msm_finish re-runs
-    // the job with the hot-bucket kernels and suspends the hint for the rest of the opening (Context::spread_suspended, reset by kh_ipa_begin).
-    static const bool spread_on = !(getenv("KH_NO_SPREAD_HINT") && atoi(getenv("KH_NO_SPREAD_HINT")) != 0);
-    static const u32 SPREAD_MAX_NT = getenv("KH_SPREAD_MAX_NT") ? (u32)atoi(getenv("KH_SPREAD_MAX_NT")) : 256u;
-    const bool spread = spread_on && (use_graph & MSM_SPREAD_SCALARS) != 0 && !Ctx.spread_suspended;
+    // the job with the hot-bucket kernels and reports it (MsmJob::spread_rerun): the opening passes the hint no more.
+    static constexpr u32 SPREAD_MAX_NT = 256;
     const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
     const int c = wide ? basis.wide_c : (basis.precomp_c ? basis.precomp_c : msm_pick_window(n));
     const bool glv = basis.glv && !wide && basis.precomp_c != 0;      // rows 0 .. W/2-1: 2^(c w) P, rows W/2 .. W-1: phi of them (csrc/rebase.hip)
@@ -1883,12 +1836,15 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     const int precomp = (wide || basis.precomp_c) ? 1 : 0;
     // slices per (window, msm): enough blocks to fill the chip (~512), no more -- the per-slice histograms
     // cost nkeys x W x S words of traffic in k_key_totals, which dominates the sort of a batch
-    static const size_t slice_div = getenv("KH_SLICE_DIV") ? (size_t)atol(getenv("KH_SLICE_DIV")) : 32768;
-    int S = (int)(n / slice_div); if (S < 1) S = 1; if (S > 16) S = 16;
+    int S = (int)(n / 32768); if (S < 1) S = 1; if (S > 16) S = 16;
     { int want = (int)(512 / ((size_t)W * k)); if (want < 1) want = 1; if (S > want) S = want; }
     const size_t tab_stride = basis.stride ? basis.stride : basis.n;
     SortGeom g{n, nb, S, W, precomp, tab_stride, offset, basis.batch_stride};
     const size_t ngroups = precomp ? k : k * (size_t)W;
+    // few groups: the latency path of the bucket sums and marginals, lane-cooperative additions (coop.cuh)
+    const bool few_groups = ngroups <= 8;                   // 5 / 7 / 8 MSMs of 2^16: 0.94 / 1.09 / 1.14 -> 0.85 / 1.05 / 1.09 ms against 4
+    const bool quad_sum = !wide && precomp && few_groups;   // k_bucket_sum_q, the only bucket-sum kernel that takes the spread hint
+    const bool spread = quad_sum && (flags & MSM_SPREAD_SCALARS) != 0;
     const int Sq = precomp ? W * S : S;
     const size_t nkeys = ngroups * nb;
     const size_t M = n * (size_t)W * k;                 // upper bound on entries
@@ -1896,15 +1852,13 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     // 1.1 "rounds" of resident threads pays a whole extra chain at 10 % occupancy (measured: 1.80 ms
     // instead of 1.72 ms at 2^20).  Size K so that all tasks are resident at once (4 waves/SIMD =
     // 1024 threads per CU) whenever the bucket count allows it.
-    static const size_t room_waves = getenv("KH_ROOM_WAVES") ? (size_t)atoi(getenv("KH_ROOM_WAVES")) : 4;     // waves per SIMD the task count is sized for
-    const size_t cap = (size_t)Ctx.num_cus * 256 * room_waves;
+    const size_t cap = (size_t)Ctx.num_cus * 256 * 4;
     size_t room_sz = cap / 4;                              // many buckets: about one task per bucket anyway
     if (nkeys < cap / 2) room_sz = cap - cap / 16 - nkeys / 2;   // ~ half of the buckets add a remainder task
     const u32 room = (u32)room_sz;                          // K = clamp(ceil(entries / room), 8, MAX_K), on the device
-    static const u32 kmin = getenv("KH_KMIN") ? (u32)atoi(getenv("KH_KMIN")) : 8u;
-    static const bool ktab_on = !getenv("KH_KMIN") && !(getenv("KH_KTAB") && atoi(getenv("KH_KTAB")) == 0);
-    const KTab ktab = ktab_on && precomp ? task_length_table(nkeys, (u32)Ctx.num_cus) : KTab{};
-    const size_t max_tasks = M / (kmin < 4 ? kmin : 4) + nkeys + 1;          // bound for the smallest K (the table's entries are >= 4)
+    const u32 kmin = 8;
+    const KTab ktab = precomp ? task_length_table(nkeys, (u32)Ctx.num_cus) : KTab{};
+    const size_t max_tasks = M / 4 + nkeys + 1;          // bound for the smallest K (the table's entries are >= 4)
     KH_REQUIRE(M < ((size_t)1 << 31) && (tab_stride * (size_t)(precomp ? W : 1) + basis.batch_stride * k) < ((size_t)1 << 31), "MSM too large for 31-bit entry indices (n=%zu k=%zu)", n, k);
 
     int rc;
@@ -1923,24 +1877,17 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     if ((rc = C.ws_chunks.reserve(bigcap * 128))) return rc;
     if ((rc = C.ws_order.reserve((2 * (MAX_K + 1) + 3 * (nkeys + 2)) * sizeof(u32)))) return rc;
     WideGeom wg{};
-    // wide-path knobs (defaults = measured best, tools/wide_sweep.py): ranks of one partition side by side in the accumulation order; blocks of the
+    // wide-path constants (measured best, tools/wide_sweep.py): ranks of one partition side by side in the accumulation order; blocks of the
     // accumulation per CU (held down with dynamic LDS); log2 of the chunk length of the first reduction level
-    static const u32 wide_og = getenv("KH_WIDE_OG") ? (u32)std::max(1, atoi(getenv("KH_WIDE_OG"))) : 16u;
-    static const u32 wide_acc_blocks = getenv("KH_WIDE_ACC_BLOCKS") ? (u32)std::max(1, atoi(getenv("KH_WIDE_ACC_BLOCKS"))) : 3u;
-    static const u32 wide_rlog = getenv("KH_WIDE_RLOG") ? (u32)atoi(getenv("KH_WIDE_RLOG")) : 4u;
+    static constexpr u32 wide_og = 16, wide_acc_blocks = 3, wide_rlog = 4;
+    // k_part2_sort interleaves `og` consecutive ranks of a partition: og must divide the 2^(c - 9) buckets of a partition; k_wide_a1 / _a2 cut both digit
+    // planes into chunks of 2^rlog buckets: rlog <= min(lo, hi) -- for every wide c (> 16)
+    static_assert((wide_og & (wide_og - 1)) == 0 && wide_og <= (1u << (17 - 9)) && wide_rlog >= 1 && wide_rlog <= 17 / 2, "wide-path constants");
     // dynamic LDS that leaves room for exactly wide_acc_blocks blocks on a CU, from the device's own LDS size (160 KB on gfx950), never more than one block
     // may ask for: where the request cannot hold the count down the kernel simply runs at its register-limited occupancy
-    size_t wide_acc_lds = wide_acc_blocks >= 4 ? 0 : (Ctx.lds_per_cu / (wide_acc_blocks + 1) + 1024) & ~(size_t)1023;
+    size_t wide_acc_lds = (Ctx.lds_per_cu / (wide_acc_blocks + 1) + 1024) & ~(size_t)1023;
     if (wide_acc_lds > Ctx.lds_per_block) wide_acc_lds = Ctx.lds_per_block & ~(size_t)1023;
-    // the narrow accumulation held to fewer blocks per CU the same way (KH_ACC_BLOCKS, experiment: room for the latency kernels of OTHER provers' chains; 0 = no limit)
-    static const unsigned acc_blocks = getenv("KH_ACC_BLOCKS") ? (unsigned)atoi(getenv("KH_ACC_BLOCKS")) : 0u;
-    size_t acc_lds = (acc_blocks == 0 || acc_blocks >= 4) ? 0 : (Ctx.lds_per_cu / (acc_blocks + 1) + 1024) & ~(size_t)1023;
-    if (acc_lds > 65536) acc_lds = 65536;
-    if (wide) {
-        // k_part2_sort interleaves `og` consecutive ranks of a partition: og must divide the 2^low buckets of a partition; k_wide_a1 / _a2 cut both digit
-        // planes into chunks of 2^rlog buckets: rlog <= min(lo, hi)
-        KH_REQUIRE(wide_og >= 1 && (wide_og & (wide_og - 1)) == 0 && wide_og <= (1u << ((u32)c - 9)), "KH_WIDE_OG = %u must be a power of two <= %u", wide_og, 1u << ((u32)c - 9));
-        KH_REQUIRE(wide_rlog >= 1 && wide_rlog <= std::min((u32)c / 2, (u32)(c - 1) - (u32)c / 2), "KH_WIDE_RLOG = %u must be in 1..%u", wide_rlog, std::min((u32)c / 2, (u32)(c - 1) - (u32)c / 2));                                            // bucket = (hi digit, lo digit); chunks of 2^rlog buckets in the first reduction level
+    if (wide) {                                                                         // bucket = (hi digit, lo digit)
         if ((rc = C.ws_xlist.reserve((3 * max_tasks + 8) * sizeof(u32)))) return rc;       // (key, chunk) pairs of the extra chunks, then the split buckets' keys
         if ((rc = C.ws_handed.reserve((2 * max_tasks + 4) * sizeof(u32)))) return rc;
         wg.nb = nb; wg.lo = (u32)c / 2; wg.hi = (u32)(c - 1) - wg.lo; wg.rlog = wide_rlog;
@@ -1959,8 +1906,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     const u32 nseg = nb / m;
     const u32 nblk1 = (nseg + SUM_BLK - 1) / SUM_BLK;
     // one to four MSMs over the tables: digit marginals instead (k_marginals), three fields of <= 5 bits
-    static const size_t marg_max = getenv("KH_MARG_MAX") ? (size_t)atol(getenv("KH_MARG_MAX")) : 4096;
-    const u32 planes = wide ? 3u : ((precomp && ngroups <= marg_max && c >= 7 && c <= 16 && !getenv("KH_NO_PLANES")) ? 3u : 0u);
+    const u32 planes = wide ? 3u : ((precomp && ngroups <= 4096 && c >= 7 && c <= 16) ? 3u : 0u);
     MargGeom mg{};
     if (planes) {                                          // (wide: the tail runs over the two marginal groups of 2^lo slots each, k_wide_a2)
         const u32 bits = wide ? wg.lo : (u32)c - 1, f0 = (bits + 2) / 3, f1 = (bits - f0 + 1) / 2, f2 = bits - f0 - f1;
@@ -1985,12 +1931,11 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     }
     // small jobs over the tables: the whole sort in one launch (k_sort_fused)
     static const bool fused_off = getenv("KH_NO_FUSED_SORT") != nullptr;
-    static const size_t fused_max = getenv("KH_FUSED_MAX") ? (size_t)atol(getenv("KH_FUSED_MAX")) : ((size_t)1 << 22);
     // bounded spin of its grid barriers: 20 ms of the 100 MHz wall clock by default (a barrier normally waits < 50 us)
     static const unsigned long long fused_spin_ticks = 100ull * (getenv("KH_FUSED_SPIN_US") ? (unsigned long long)atoll(getenv("KH_FUSED_SPIN_US")) : 20000ull);
     FusedGeom fg{};
     // (co-residency of the spinning blocks is what makes the grid barriers safe: 64 blocks x 4 jobs in flight need 128 CUs -- not in a partitioned mode)
-    bool fused = precomp && !wide && !fused_off && !Ctx.fused_disabled && k <= 4 && M < fused_max && nb >= 2048 && Ctx.num_cus >= 128;
+    bool fused = precomp && !wide && !fused_off && !Ctx.fused_disabled && k <= 4 && M < ((size_t)1 << 22) && nb >= 2048 && Ctx.num_cus >= 128;
     if (fused) {
         fg.n = (u32)n; fg.nb = nb; fg.W = (u32)W; fg.k = (u32)k; fg.bpg = (u32)std::min<size_t>(FUSED_G, FUSED_B / (2 * k)); fg.nkeys = (u32)nkeys;
         fg.split = 2; fg.sub = nb / fg.split;              // 64 blocks of 64 KB LDS: two per CU, so four (even eight) jobs in flight stay co-resident
@@ -2001,8 +1946,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         if (fg.kpt > (u32)FUSED_KPT || n < 4 || ((size_t)W * n) % 4 || chunk4 > (size_t)FUSED_V * FUSED_T || fg.sub > (u32)FUSED_C * FUSED_T) fused = false;
     }
     // large jobs over the tables: the two-pass partitioned sort (k_part_*)
-    static const bool part_off = getenv("KH_NO_PART_SORT") != nullptr;
-    const bool part = wide || (precomp && !fused && !part_off && nb == ((u32)PART_P << PART_LOW) && n <= ((size_t)1 << 20) && W <= 16 && M >= ((size_t)1 << 21));
+    const bool part = wide || (precomp && !fused && nb == ((u32)PART_P << PART_LOW) && n <= ((size_t)1 << 20) && W <= 16 && M >= ((size_t)1 << 21));
     const u32 part_low = wide ? (u32)c - 9 : (u32)PART_LOW;
     const u32 part_nblk = wide ? (u32)std::max<size_t>(std::max<size_t>(1, std::min<size_t>(256, 512 / k)), ((size_t)W * n + 65535) / 65536)
                                : (part ? (u32)std::max<size_t>(1, std::min<size_t>(256, 512 / k)) : 0);
@@ -2042,52 +1986,9 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
             KH_HIP(hipMemsetAsync(C.ws_done.p, 0, 64, s));           // ordered in front of the slot's first launch that counts in it
         }
     }
-    // hipGraph replay / capture (opt-in by the caller; the key covers everything the launches bake in)
-    static const bool graphs_off = getenv("KH_NO_GRAPH") != nullptr;
-    uint64_t key = 0;
-    CaptureGuard gcap{s};
-    const bool timers_were = C.timer.enabled;
-    if ((use_graph & MSM_REPEATS) && !graphs_off && s != Ctx.stream) {       // never capture on the main stream: other host threads synchronise and launch on it
-        key = 0xcbf29ce484222325ull;
-        const uint64_t parts[] = {(uint64_t)(uintptr_t)basis.pts, (uint64_t)(uintptr_t)basis.inf, basis.n, basis.stride, basis.batch_stride, (uint64_t)basis.precomp_c,
-                                  offset, (uint64_t)(uintptr_t)scalars_dev, n, k, (uint64_t)mont, (uint64_t)curve, (uint64_t)(uintptr_t)C.pinned,
-                                  (uint64_t)(uintptr_t)C.ws_digits.p, (uint64_t)(uintptr_t)C.ws_hist.p, (uint64_t)(uintptr_t)C.ws_cnt.p, (uint64_t)(uintptr_t)C.ws_off.p,
-                                  (uint64_t)(uintptr_t)C.ws_ntask.p, (uint64_t)(uintptr_t)C.ws_toff.p, (uint64_t)(uintptr_t)C.ws_entries.p, (uint64_t)(uintptr_t)C.ws_partial.p,
-                                  (uint64_t)(uintptr_t)C.ws_buckets.p, (uint64_t)(uintptr_t)C.ws_seg.p, (uint64_t)(uintptr_t)C.ws_out.p, (uint64_t)(uintptr_t)C.ws_scan_tmp.p,
-                                  (uint64_t)(uintptr_t)C.ws_biglist.p, (uint64_t)(uintptr_t)C.ws_order.p, (uint64_t)(uintptr_t)C.ws_chunks.p,
-                                  (uint64_t)(uintptr_t)C.ws_handed.p, (uint64_t)(uintptr_t)C.ws_sync.p, (uint64_t)fused, (uint64_t)(uintptr_t)C.ws_mid.p, (uint64_t)part,
-                                  (uint64_t)(uintptr_t)tab_pts, (uint64_t)wide, (uint64_t)spread, (uint64_t)(uintptr_t)C.ws_xlist.p, (uint64_t)(uintptr_t)C.ws_b29.p, (uint64_t)(uintptr_t)C.ws_a1.p, (uint64_t)(uintptr_t)C.ws_a2.p, (uint64_t)(uintptr_t)C.ws_done.p, (uint64_t)flag_on, (uint64_t)(use_graph & MSM_LATENCY), (uint64_t)glv,
-                                  ((uint64_t)sort_staging_cell(0).load() << 8) | sort_staging_cell(1).load(), DevBuf::generation().load()};
-        for (uint64_t v : parts) key = fnv(key, v);
-        if (C.gexec && C.gkey == key) {                    // replay
-            C.fused_used = C.g_fused;
-            C.retry = {basis.pts, basis.inf, basis.n, basis.stride, basis.batch_stride, basis.precomp_c, offset, scalars_dev, n, k, mont, curve, basis.glv};
-            // (the host's launch count moves BEFORE the launch that will move the device's: whatever fails in between, the host is never
-            // behind -- a stale equality would end a later wait early -- and a host that is ahead only falls back to the event, then resyncs)
-            C.spread_used = C.g_spread;
-            C.done_by_flag = C.g_done_by_flag; if (C.done_by_flag) C.done_expect++;
-            KH_HIP(hipGraphLaunch(C.gexec, s));
-            counter(CNT_GRAPH_REPLAY)++;
-            KH_HIP(hipEventRecord(C.done, s));
-            C.busy = true; C.owner = std::this_thread::get_id(); C.ticket = Ctx.next_ticket++;
-            C.curve = curve; C.W = C.g_W; C.c = C.g_c; C.precomp = C.g_precomp; C.k = k; C.ngroups = C.g_ngroups; C.planes = C.g_planes;
-            C.plane_shift[0] = C.g_shift[0]; C.plane_shift[1] = C.g_shift[1]; C.wide_lo = C.g_wide_lo;
-            C.timer.n = 0;                                 // no per-phase events inside a graph
-            return KH_OK;
-        }
-        if (C.gseen == key) {                              // second time: every workspace is sized, capture this one
-            if (C.gexec) { (void)hipGraphExecDestroy(C.gexec); C.gexec = nullptr; }
-            C.timer.enabled = false;
-            if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) gcap.active = true;
-            else { (void)hipGetLastError(); C.timer.enabled = timers_were; }
-        } else {
-            C.gseen = key;
-        }
-    }
-
     C.timer.begin(s);
     // 1 digits
-    if (hs && hs->nev > 0 && k == 1 && !gcap.active) {    // upload and digit pass chunk by chunk (MsmHostScalars)
+    if (hs && hs->nev > 0 && k == 1) {    // upload and digit pass chunk by chunk (MsmHostScalars)
         for (int ch = 0; ch < hs->nev; ch++) {
             const size_t c0 = n * (size_t)ch / hs->nev, c1 = n * (size_t)(ch + 1) / hs->nev;
             if (c1 == c0) continue;
@@ -2170,8 +2071,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         // (1024-thread blocks: the per-(block, length) global atomics of k_ntask / k_len_rank serialise on ~40 hot addresses -- 25 us each at 256 threads per block)
         hipLaunchKernelGGL(k_ntask, dim3((unsigned)((nkeys + 1 + 1023) / 1024)), dim3(1024), 0, s, C.ws_off.as<u32>(), nkeys, room, kmin, ktab, C.ws_ntask.as<u32>(), len_hist, C.ws_handed.as<u32>());
         if ((rc = exclusive_scan_u32(C.ws_ntask.as<u32>(), C.ws_toff.as<u32>(), nkeys + 1, C.ws_scan_tmp, s))) return rc;
-        static const int rank_min_log = getenv("KH_RANK_MIN_LOG") ? atoi(getenv("KH_RANK_MIN_LOG")) : 22;   // below ~4M entries the three extra launches cost more than the ordering saves
-        if (M >= ((size_t)1 << rank_min_log)) {
+        if (M >= ((size_t)1 << 22)) {      // below ~4M entries the three extra launches cost more than the ordering saves
             hipLaunchKernelGGL(k_len_starts, dim3(1), dim3(320), 0, s, len_hist, cursor);
             hipLaunchKernelGGL(k_len_rank, dim3((unsigned)((nkeys + 1 + 1023) / 1024)), dim3(1024), 0, s, C.ws_off.as<u32>(), C.ws_ntask.as<u32>(), nkeys, cursor, order, rnt);
             if ((rc = exclusive_scan_u32(rnt, roff, nkeys + 1, C.ws_scan_tmp, s))) return rc;
@@ -2181,16 +2081,14 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         C.timer.mark("tasks", s);
     }
     // 5 accumulate: the lazy 29-bit-limb kernel, then the exact kernel over the (almost always zero) tasks it handed over
-    static const bool acc29 = !(getenv("KH_ACC29") && atoi(getenv("KH_ACC29")) == 0);
     const u32* abort_dev = fused ? C.ws_sync.as<u32>() + 2 + 2 * FUSED_B + 32 : nullptr;     // the fused sort's give-up word (sort_gave_up)
-    const u32* handed = acc29 ? C.ws_handed.as<u32>() : nullptr;
     const dim3 agrid((unsigned)((max_tasks + 255) / 256));
-    const u32 acc_prio = (use_graph & MSM_LATENCY) ? 1u : 0u;
+    const u32 acc_prio = (flags & MSM_LATENCY) ? 1u : 0u;
     uint8_t* const b29 = wide ? C.ws_b29.as<uint8_t>() : nullptr;
     if (wide) {                                            // thread per bucket in pass B's interleaved length order (+ the listed extra chunks), then the exact redos
         const dim3 wgrid((unsigned)(nkeys / 256));
         auto kern = k_acc_wide29<BF>;
-        if (C.timer.enabled && C.timer.created && !gcap.active) {
+        if (C.timer.enabled && C.timer.created) {
             hipExtLaunchKernelGGL(kern, wgrid, dim3(256), wide_acc_lds, s, C.timer.k0, C.timer.k1, 0, C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), order, (u32)nkeys,
                                   (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, part_low, C.ws_handed.as<u32>());
             C.timer.kname = "k_acc_wide29";
@@ -2202,35 +2100,24 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         const unsigned xgrid = M / nkeys >= 64 ? 2048u : WIDE_XB;
         hipLaunchKernelGGL((k_acc_wide_rest<BF>), dim3(xgrid), dim3(256), 0, s, C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(),
                            C.ws_handed.as<u32>(), (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, part_low);
-    } else
-    if (acc29) {
+    } else {
         auto kern = k_accumulate29<BF>;
-        if (C.timer.enabled && C.timer.created && !gcap.active) {     // the dominant kernel's own start / stop timestamps (bench.py roofline)
-            hipExtLaunchKernelGGL(kern, agrid, dim3(256), acc_lds, s, C.timer.k0, C.timer.k1, 0,
+        if (C.timer.enabled && C.timer.created) {     // the dominant kernel's own start / stop timestamps (bench.py roofline)
+            hipExtLaunchKernelGGL(kern, agrid, dim3(256), 0, s, C.timer.k0, C.timer.k1, 0,
                                   C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
                                   (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), C.ws_handed.as<u32>(), abort_dev, acc_prio);
             C.timer.kname = "k_accumulate29";
         } else
-        hipLaunchKernelGGL(kern, agrid, dim3(256), acc_lds, s,
+        hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s,
                            C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
                            (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), C.ws_handed.as<u32>(), abort_dev, acc_prio);
-    } else if (C.timer.enabled && C.timer.created && !gcap.active) {
-        hipExtLaunchKernelGGL((k_accumulate<BF>), agrid, dim3(256), 0, s, C.timer.k0, C.timer.k1, 0,
-                              C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
-                              (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), handed, abort_dev);
-        C.timer.kname = "k_accumulate";
-    } else
-    hipLaunchKernelGGL((k_accumulate<BF>), agrid, dim3(256), 0, s,
-                       C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
-                       (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), handed, abort_dev);
+    }
     C.timer.mark("accumulate", s);
     // 6 bucket sums
-    static const bool bsum_quad = !getenv("KH_NO_BSUM_QUAD");
-    static const size_t bsum_maxg = getenv("KH_QUAD_MAXG") ? (size_t)atol(getenv("KH_QUAD_MAXG")) : 8;     // 5 / 7 / 8 MSMs of 2^16: 0.94 / 1.09 / 1.14 -> 0.85 / 1.05 / 1.09 ms against 4
     if (wide)                                              // (the split buckets' sums, hot ones included: one launch; 2^22: 16 K split buckets of two partials)
         hipLaunchKernelGGL((k_bucket_sum_wide<BF>), dim3(256), dim3(256), 0, s, C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(), C.ws_xlist.as<u32>() + 2 + 2 * max_tasks,
                            C.ws_partial.as<uint8_t>(), b29, part_low, WIDE_HOT_NT, C.ws_biglist.as<u32>(), (u32)bigcap, C.ws_chunks.as<uint8_t>());
-    else if (precomp && ngroups <= bsum_maxg && bsum_quad)
+    else if (quad_sum)
         hipLaunchKernelGGL((k_bucket_sum_q<BF>), dim3((unsigned)((4 * nkeys + 255) / 256)), dim3(256), 0, s,
                            C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
                            bigcap, spread ? SPREAD_MAX_NT : 16u, abort_dev, spread ? (u32*)C.spread_abort : nullptr);
@@ -2238,7 +2125,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     hipLaunchKernelGGL((k_bucket_sum<BF>), dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s,
                        C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
                        bigcap, nkeys <= 16384 ? 4u : 16u, abort_dev);
-    if (!wide && !(spread && precomp && ngroups <= bsum_maxg && bsum_quad)) {     // (the quad kernel took every bucket: nothing was listed; the wide path's kernel sums its hot buckets itself)
+    if (!wide && !spread) {     // (the quad kernel took every bucket: nothing was listed; the wide path's kernel sums its hot buckets itself)
     hipLaunchKernelGGL((k_bucket_chunk<BF>), dim3(2048), dim3(64), 0, s,
                        C.ws_toff.as<u32>(), C.ws_partial.as<uint8_t>(), C.ws_biglist.as<u32>(), bigcap, C.ws_chunks.as<uint8_t>(), abort_dev);
     hipLaunchKernelGGL((k_bucket_big<BF>), dim3(1024), dim3(256), 0, s,
@@ -2247,7 +2134,9 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     C.timer.mark("bucket_sum", s);
     // 7 reduce
     u32* const done_ws = flag_on ? C.ws_done.as<u32>() : nullptr; u32* const done_flag = flag_on ? (u32*)C.done_flag : nullptr;
-    if (flag_on) C.done_expect++;                        // before the launch that stores it (see the replay branch); every flag_on job ends in k_marginal_fin_q
+    // (the host's launch count moves BEFORE the launch that will move the device's: whatever fails in between, the host is never behind -- a stale
+    // equality would end a later wait early -- and a host that is ahead only falls back to the event, then resyncs)
+    if (flag_on) C.done_expect++;                        // every flag_on job ends in k_marginal_fin_q
     bool direct_out = false;                              // latency path: the last kernel writes the (768-byte) result to host memory itself -- no copy node
     if (wide) {
         const u32 items = 2u * (nb >> wg.rlog) * (u32)ngroups;
@@ -2258,31 +2147,23 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)tail_groups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
         direct_out = true;
     } else if (planes) {
-        // few groups: 256 threads per marginal (4 sequential additions + the tree: shortest chain); batches: one wave
-        // per marginal (16 + 6 additions deep, but 2.2x less issue work -- batches are throughput-bound)
-        static const int quad_threads = getenv("KH_QUAD") ? atoi(getenv("KH_QUAD")) : 256;   // 0: scalar additions
-        static const size_t quad_maxg = getenv("KH_QUAD_MAXG") ? (size_t)atol(getenv("KH_QUAD_MAXG")) : 8;
-        static const bool marg_hybrid = !(getenv("KH_MARG_HYBRID") && atoi(getenv("KH_MARG_HYBRID")) == 0) && !getenv("KH_QUAD");
-        if (ngroups <= quad_maxg && quad_threads > 0) {    // latency path: lane-cooperative additions (coop.cuh)
-            if (marg_hybrid && (mg.nb >> mg.wd[0]) >= 256)  // ... for the tree; one lane per addition where every lane has its own buckets (k_marginals_h)
-                hipLaunchKernelGGL((k_marginals_h<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-            else
-            hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)ngroups), dim3(quad_threads), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-            hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);   // straight into the pinned host staging
-            direct_out = true;
-        } else {
-        static const bool marg_h_batch = !(getenv("KH_MARG_H_BATCH") && atoi(getenv("KH_MARG_H_BATCH")) == 0);
-        if (marg_h_batch && marg_hybrid && (mg.nb >> mg.wd[0]) >= 256)      // batches too: the same sums, the 6-level lane tree replaced by the quads' 4 + 4 steps
+        // few groups: 256 threads per marginal (4 sequential additions + the tree: shortest chain); batches: one wave per marginal (16 + 6 additions
+        // deep, but 2.2x less issue work -- batches are throughput-bound).  Either way, where every lane has its own buckets, k_marginals_h: one lane
+        // per addition, the 6-level lane tree replaced by the quads' 4 + 4 steps
+        if ((mg.nb >> mg.wd[0]) >= 256)
             hipLaunchKernelGGL((k_marginals_h<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
+        else if (few_groups)
+            hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         else
-        hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, (unsigned)ngroups), dim3(ngroups <= 4 ? 256 : 64), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
+            hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, (unsigned)ngroups), dim3(64), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         // the weighted tail is 3 x ngroups blocks however many MSMs there are: a pure latency chain (10 additions deep), so it takes the
         // lane-cooperative kernel for batches too (15 witness columns: 96 -> 35 us); the records have the same 128-byte layout
         static const bool fin_quad = !getenv("KH_NO_FIN_QUAD");
-        if (fin_quad) { hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag); direct_out = true; }
-        else
-        hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, (unsigned)ngroups), dim3(64), 0, s, C.ws_seg.as<uint8_t>(), mg, C.ws_out.as<uint8_t>());
-        }
+        if (few_groups || fin_quad) {                      // straight into the pinned host staging
+            hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
+            direct_out = true;
+        } else
+            hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, (unsigned)ngroups), dim3(64), 0, s, C.ws_seg.as<uint8_t>(), mg, C.ws_out.as<uint8_t>());
     } else {
     hipLaunchKernelGGL((k_reduce_seg<BF>), dim3((unsigned)((ngroups * nseg + 127) / 128)), dim3(128), 0, s,
                        C.ws_buckets.as<uint8_t>(), nb, m, ngroups, C.ws_seg.as<uint8_t>());
@@ -2296,45 +2177,41 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     KH_HIP(hipGetLastError());
     // group sums -> pinned host staging
     if (!direct_out) KH_HIP(hipMemcpyAsync(C.pinned, C.ws_out.p, nout * 128, hipMemcpyDeviceToHost, s));
-    if (gcap.active) {
-        hipGraph_t g = nullptr;
-        gcap.active = false;
-        C.timer.enabled = timers_were; C.timer.n = 0;
-        hipError_t e = hipStreamEndCapture(s, &g);
-        if (e == hipSuccess && g) e = hipGraphInstantiate(&C.gexec, g, nullptr, nullptr, 0);
-        if (g) (void)hipGraphDestroy(g);
-        if (e != hipSuccess) { C.gexec = nullptr; set_error("hipGraph capture of the MSM launch sequence failed: %s", hipGetErrorString(e)); return KH_E_DEVICE; }
-        C.gkey = key; C.gnout = nout; C.gscalars = scalars_dev; C.g_fused = fused; C.g_spread = spread && !wide && precomp && ngroups <= bsum_maxg && bsum_quad;
-        C.g_W = W; C.g_c = c; C.g_precomp = precomp; C.g_planes = (int)planes; C.g_shift[0] = (int)mg.wd[0]; C.g_shift[1] = (int)mg.wd[1]; C.g_ngroups = ngroups; C.g_wide_lo = wide ? (int)wg.lo : 0; C.g_done_by_flag = direct_out && flag_on;
-        KH_HIP(hipGraphLaunch(C.gexec, s));
-    }
     KH_HIP(hipEventRecord(C.done, s));
-    C.done_by_flag = direct_out && flag_on;
     C.busy = true; C.owner = std::this_thread::get_id(); C.ticket = Ctx.next_ticket++;
-    C.curve = curve; C.W = W; C.c = c; C.precomp = precomp; C.k = k; C.ngroups = ngroups; C.planes = (int)planes; C.plane_shift[0] = (int)mg.wd[0]; C.plane_shift[1] = (int)mg.wd[1]; C.wide_lo = wide ? (int)wg.lo : 0;
-    C.fused_used = fused;
-    C.spread_used = spread && !wide && precomp && ngroups <= bsum_maxg && bsum_quad;
-    C.retry = {basis.pts, basis.inf, basis.n, basis.stride, basis.batch_stride, basis.precomp_c, offset, scalars_dev, n, k, mont, curve, basis.glv};
+    C.job = {basis, offset, scalars_dev, n, k, mont, curve, W, c, precomp, (int)planes, {(int)mg.wd[0], (int)mg.wd[1]}, wide ? (int)wg.lo : 0, ngroups,
+             direct_out && flag_on, fused, spread};
     return KH_OK;
 }
 
 int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t offset, const uint64_t* scalars_dev, size_t n, size_t k, int mont,
-                int use_graph, const MsmHostScalars* hs) {
-    if (n == 0 || k == 0) {          // nothing to launch: finish() emits k identities
-        S.busy = true; S.owner = std::this_thread::get_id(); S.ticket = C.next_ticket++; S.curve = curve; S.k = k; S.ngroups = 0; S.W = 0; S.c = 0; S.precomp = 1; S.planes = 0; S.done_by_flag = false; S.fused_used = false; S.spread_used = false;
+                int flags, const MsmHostScalars* hs) {
+    if (n == 0 || k == 0) {          // nothing to launch (MsmJob::ngroups = 0): finish() emits k identities
+        S.busy = true; S.owner = std::this_thread::get_id(); S.ticket = C.next_ticket++;
+        S.job = {basis, offset, scalars_dev, n, k, mont, curve};
         KH_HIP(hipEventRecord(S.done, S.stream));
         return KH_OK;
     }
-    if (hs) use_graph &= ~MSM_REPEATS;                     // (a captured launch sequence cannot contain the host's staging)
-    if (curve == KH_CURVE_VESTA) return msm_enqueue_t<VestaCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, use_graph, hs);
-    return msm_enqueue_t<PallasCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, use_graph, hs);
+    if (curve == KH_CURVE_VESTA) return msm_enqueue_t<VestaCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags, hs);
+    return msm_enqueue_t<PallasCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags, hs);
+}
+
+// an aborted job again, from its inputs and without the caller's flags, under the same ticket; waits for it
+static int msm_rerun(Context& C, MsmSlot& S) {
+    const MsmJob j = S.job;
+    const uint64_t ticket = S.ticket; const auto owner = S.owner;
+    int rc = msm_enqueue(C, S, j.curve, j.basis, j.offset, j.scalars, j.n, j.k, j.mont);
+    S.ticket = ticket; S.owner = owner; C.next_ticket--;
+    if (rc) { S.busy = false; return rc; }
+    KH_HIP(hipEventSynchronize(S.done));
+    return KH_OK;
 }
 
 // 8 finish on the host: wait for the slot, Horner over the window sums (plain path), XYZZ -> affine
 int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool flag_seen) {
     // (the per-phase events of a job -- tools only -- are read below: they need the event wait)
-    if (!(flag_seen && S.done_by_flag && S.timer.n == 0)) KH_HIP(hipEventSynchronize(S.done));
-    if (S.fused_used && S.host_abort && *S.host_abort) {
+    if (!(flag_seen && S.job.done_by_flag && S.timer.n == 0)) KH_HIP(hipEventSynchronize(S.done));
+    if (S.job.fused && S.host_abort && *S.host_abort) {
         // the one-launch sort gave up at a grid barrier (its blocks were not all resident: the GPU is shared with another process):
         // everything behind it ran on garbage.  Re-run this job with the multi-launch sort and stay on it.
         *S.host_abort = 0;
@@ -2342,25 +2219,15 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
         C.fused_disabled = true;
         counter(CNT_FUSED_RETRY)++;
         KH_HIP(hipMemsetAsync(S.ws_sync.p, 0, (2 + 2 * FUSED_B + 32 + 2) * sizeof(u32), S.stream));
-        const uint64_t ticket = S.ticket; const auto owner = S.owner;
-        MsmBasis b; b.pts = S.retry.pts; b.inf = S.retry.inf; b.n = S.retry.bn; b.stride = S.retry.stride; b.batch_stride = S.retry.batch_stride; b.precomp_c = S.retry.precomp_c; b.glv = S.retry.glv;
-        int rc = msm_enqueue(C, S, S.retry.curve, b, S.retry.offset, S.retry.scalars, S.retry.n, S.retry.k, S.retry.mont, 0);
-        S.ticket = ticket; S.owner = owner; C.next_ticket--;
-        if (rc) { S.busy = false; return rc; }
-        KH_HIP(hipEventSynchronize(S.done));
+        if (int rc = msm_rerun(C, S)) return rc;
     }
-    if (S.spread_used && S.spread_abort && *S.spread_abort) {
+    if (S.job.spread && S.spread_abort && *S.spread_abort) {
         // MSM_SPREAD_SCALARS did not hold (a bucket with more task partials than a quad may sum in sequence): the buckets that said so were left empty.
-        // Re-run this job with the hot-bucket kernels; the hint stays off until the caller begins its next opening.
+        // Re-run this job with the hot-bucket kernels, and say so: the caller's opening passes the hint no more.
         *S.spread_abort = 0;
-        C.spread_suspended = true;
         counter(CNT_SPREAD_RETRY)++;
-        const uint64_t ticket = S.ticket; const auto owner = S.owner;
-        MsmBasis b; b.pts = S.retry.pts; b.inf = S.retry.inf; b.n = S.retry.bn; b.stride = S.retry.stride; b.batch_stride = S.retry.batch_stride; b.precomp_c = S.retry.precomp_c; b.glv = S.retry.glv;
-        int rc = msm_enqueue(C, S, S.retry.curve, b, S.retry.offset, S.retry.scalars, S.retry.n, S.retry.k, S.retry.mont, 0);
-        S.ticket = ticket; S.owner = owner; C.next_ticket--;
-        if (rc) { S.busy = false; return rc; }
-        KH_HIP(hipEventSynchronize(S.done));
+        if (int rc = msm_rerun(C, S)) return rc;
+        S.job.spread_rerun = true;
     }
     S.busy = false;
     static const bool fused_dbg = getenv("KH_FUSED_DEBUG") != nullptr;
@@ -2370,14 +2237,15 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
         fprintf(stderr, " | p3: %.1f %.1f %.1f %.1f\n", (double)(ts[9] - ts[4]) / 100.0, (double)(ts[10] - ts[9]) / 100.0, (double)(ts[11] - ts[10]) / 100.0, (double)(ts[5] - ts[11]) / 100.0);
     }
     collect_timings(C, S.timer);
-    if (S.ngroups == 0) {
-        for (size_t j = 0; j < S.k; j++) { memset(out_xy + 8 * j, 0, 64); out_inf[j] = 1; }
+    const MsmJob& J = S.job;
+    if (J.ngroups == 0) {
+        for (size_t j = 0; j < J.k; j++) { memset(out_xy + 8 * j, 0, 64); out_inf[j] = 1; }
         return KH_OK;
     }
     const khost::xyzz* res = (const khost::xyzz*)S.pinned;
-    const MsmSlot* Sp = &S;
+    const MsmJob* Sp = &J;
     static thread_local std::vector<khost::xyzz> totals;
-    totals.resize(S.k);
+    totals.resize(J.k);
     khost::xyzz* tot = totals.data();
     auto finish_one = [res, Sp, tot](size_t j) {
         khost::Crv crv(Sp->curve);
@@ -2408,24 +2276,24 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
             }
         }
     };
-    if ((!S.precomp && S.k >= 2) || (S.planes && S.k >= 16)) {      // split the Horner folds with the helper thread (a hand-over costs ~10 us: not for a few doublings)
-        const size_t half = S.k / 2, kk = S.k;
+    if ((!J.precomp && J.k >= 2) || (J.planes && J.k >= 16)) {      // split the Horner folds with the helper thread (a hand-over costs ~10 us: not for a few doublings)
+        const size_t half = J.k / 2, kk = J.k;
         HostHelper& hh = host_helper(&C);
         hh.run([finish_one, half, kk] { for (size_t j = half; j < kk; j++) finish_one(j); });
         for (size_t j = 0; j < half; j++) finish_one(j);
         hh.wait();
     } else {
-        for (size_t j = 0; j < S.k; j++) finish_one(j);
+        for (size_t j = 0; j < J.k; j++) finish_one(j);
     }
     // XYZZ -> affine for all k results with ONE field inversion (Montgomery's trick over the ZZZ's): an inversion is
     // ~13 us on the host, 0.3 ms for a batch of 23 commitments
-    khost::Crv crv(S.curve); const khost::Fld& F = crv.F;
+    khost::Crv crv(J.curve); const khost::Fld& F = crv.F;
     static thread_local std::vector<khost::fe> pre;
-    pre.resize(S.k + 1);
+    pre.resize(J.k + 1);
     pre[0] = F.f.one;
-    for (size_t j = 0; j < S.k; j++) pre[j + 1] = crv.is_identity(tot[j]) ? pre[j] : F.mul(pre[j], tot[j].zzz);
-    khost::fe inv = F.inv(pre[S.k]);
-    for (size_t j = S.k; j-- > 0;) {
+    for (size_t j = 0; j < J.k; j++) pre[j + 1] = crv.is_identity(tot[j]) ? pre[j] : F.mul(pre[j], tot[j].zzz);
+    khost::fe inv = F.inv(pre[J.k]);
+    for (size_t j = J.k; j-- > 0;) {
         if (crv.is_identity(tot[j])) { memset(out_xy + 8 * j, 0, 64); out_inf[j] = 1; continue; }
         const khost::fe izzz = F.mul(inv, pre[j]);
         inv = F.mul(inv, tot[j].zzz);

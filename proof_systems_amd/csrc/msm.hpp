@@ -5,18 +5,6 @@
 
 namespace kh {
 
-struct MsmBasis {
-    const void* pts = nullptr;       // device, n x 64 B affine x||y (Montgomery); with precomp: W tables of n points
-    const uint8_t* inf = nullptr;    // device, nullable per-point infinity flags
-    size_t n = 0;                    // points per table
-    int precomp_c = 0;               // 0: plain basis; else window width of the precomputed tables
-    size_t stride = 0;               // points between consecutive window tables (0: = n)
-    size_t batch_stride = 0;         // >0: MSM j of a batch uses points [j*batch_stride, ...) (independent bases)
-    const void* wide_pts = nullptr;  // a second table set of the SAME basis with wide windows (same stride), used for big single MSMs
-    int wide_c = 0;
-    bool glv = false;                // the tables hold 2^(c w) P for the lower 128 bits and phi(2^(c w) P) behind them: scalars are split k = k1 + k2 lambda (rebase.hip)
-};
-
 int msm_pick_window(size_t n);
 // builds the window tables 2^(c*w) * P_i in place: `tables` holds W x n x 64 B with table 0 = the basis
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c);
@@ -42,9 +30,8 @@ size_t msm_wide_min_n();                          // MSMs of at least this many 
 static constexpr size_t MSM_PRECOMP_MIN_N = 1024; // smaller bases keep the plain per-window path
 static constexpr int IPA_ROUND_C = 16;            // window width of the opening rounds' table set (KH_IPA_C overrides; < 16: a second, narrower set)
 // enqueue all device work of k MSMs on slot S (returns immediately); msm_finish waits for it and does the host part
-// use_graph: flags.  MSM_REPEATS: the caller repeats this exact MSM (same buffers and sizes): from the second call on the launch sequence is
-// captured once into a hipGraph and replayed
-static constexpr int MSM_REPEATS = 1, MSM_SPREAD_SCALARS = 2;      // (MSM_SPREAD_SCALARS: msm.hip, "the caller vouches ...")
+// flags: MSM_SPREAD_SCALARS (msm.hip, "the caller vouches ..."), MSM_LATENCY
+static constexpr int MSM_SPREAD_SCALARS = 2;
 static constexpr int MSM_LATENCY = 4;                              // the caller's critical path: the accumulation runs above the default wave priority too
 // Host scalars of ONE MSM (k == 1) that are still on their way: msm_enqueue uploads them to scalars_dev itself, in `nev` chunks on the copy stream `cs`
 // (pageable memory: the runtime stages each chunk while the previous one's k_digits already runs on the slot's stream), each chunk's digits launched
@@ -52,7 +39,7 @@ static constexpr int MSM_LATENCY = 4;                              // the caller
 // job's accumulation (kh_msm_submit_host).
 struct MsmHostScalars { const uint64_t* host; hipStream_t cs; hipEvent_t* ev; int nev; };
 int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t offset, const uint64_t* scalars_dev, size_t n, size_t k, int mont,
-                int use_graph = 0, const MsmHostScalars* hs = nullptr);
+                int flags = 0, const MsmHostScalars* hs = nullptr);
 // flag_seen: the caller has read the job's launch count from S.done_flag (the result is in S.pinned): no wait on the event
 int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool flag_seen = false);
 int debug_field_op(Context& C, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);

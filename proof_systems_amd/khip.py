@@ -494,7 +494,7 @@ def msm_points_batch(curve: int, xy, scalars, inf=None, mont: bool = True):
 
 
 def counter(name: str) -> int:
-    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, graph_replay, graph_capture, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds."""
+    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds."""
     return int(_lib.kh_counter(name.encode()))
 
 

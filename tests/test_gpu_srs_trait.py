@@ -395,6 +395,48 @@ def test_spread_hint_is_checked_not_trusted(khip):
     srs.close()
 
 
+def test_spread_hint_suspension_is_per_opening(khip):
+    """The hint an opening has disproved stays off for THAT opening: beginning another opening (on another SRS handle) between two of its rounds
+    does not give it back.  A constant polynomial at 2^16 breaks the hint in the first round and would break it again in the second (2^14 equal
+    scalars per window: at least 512 task partials in one bucket against the cap of 256); opening B (random) begins right after A's first round."""
+    cid, logn = 0, 16
+    F = P.CURVES[cid].scalar
+    n, n_b = 1 << logn, 1 << 10
+    rnd = np.random.default_rng(516)
+    ri = lambda: int.from_bytes(rnd.bytes(40), "little") % F.p
+    srs_a = khip.Srs.create(cid, n)
+    srs_b = khip.Srs.create(cid, n_b, start=n)
+    U_l = khip.srs_generate(cid, 1 << 20, 1)[0]
+    x = ri()
+    b = [1]
+    for _ in range(n - 1):
+        b.append(b[-1] * x % F.p)
+    a_l, b_l = _limbs(F, [ri()] * n), _limbs(F, b)
+    rands = [(_limbs(F, [ri()])[0], _limbs(F, [ri()])[0]) for _ in range(logn)]
+    chals = [int.from_bytes(rnd.bytes(16), "little") for _ in range(logn)]
+    a_b, b_b = _limbs(F, [ri() for _ in range(n_b)]), _limbs(F, [ri() for _ in range(n_b)])
+    rands_b = [(_limbs(F, [ri()])[0], _limbs(F, [ri()])[0]) for _ in range(10)]
+    chals_b = [int.from_bytes(rnd.bytes(16), "little") for _ in range(10)]
+    ref, *_ = _run_opening(khip, srs_a, cid, a_l, b_l, U_l, rands, chals)       # A alone
+    before = khip.counter("spread_retry")
+    op_a = khip.IpaOpening(srs_a, a_l, b_l, U_l)
+    lr = []
+    for j, ((rl, rr), ch) in enumerate(zip(rands, chals)):
+        xy, inf = op_a.round_lr(rl, rr)
+        op_a.round_fold(ch)
+        lr.append((xy.copy(), inf.copy()))
+        if j == 0:
+            op_b = khip.IpaOpening(srs_b, a_b, b_b, U_l)
+    op_a.finish(); op_a.free()
+    for (rl, rr), ch in zip(rands_b, chals_b):
+        op_b.round_lr(rl, rr)
+        op_b.round_fold(ch)
+    op_b.finish(); op_b.free()
+    assert khip.counter("spread_retry") == before + 1, "only A's first round re-runs: B's begin must not give A the hint back"
+    assert all(np.array_equal(p[0], q[0]) and np.array_equal(p[1], q[1]) for p, q in zip(lr, ref))
+    srs_a.close(); srs_b.close()
+
+
 def test_two_openings_side_by_side(khip):
     """Two provers on two SRS handles run their opening rounds from two host threads at once (the library lock is
     released while a round's MSM runs): same L, R, a0, b0, sg as when run alone."""

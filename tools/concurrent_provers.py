@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of T independent provers (one host thread, one SRS handle, one library context each) on one GPU through kh_prove -- bench.py's
 `prover.concurrent` with more proofs per thread.  Usage: tools/concurrent_provers.py [threads=4] [proofs_per_thread=20]
-Environment switches worth alternating: KH_IPA_GRAPH=1 (opening rounds replay a captured graph), KH_NO_DONE_FLAG=1 (completion by event only)."""
+Environment switch worth alternating: KH_NO_DONE_FLAG=1 (completion by event only)."""
 import os
 import sys
 import threading
