@@ -590,6 +590,48 @@ int kh_prover_index_attach_lookup(kh_prover_index_t *index, const int *patterns,
  * randomness grows by zk_rows + num_chunks right after the witness blinders. */
 int kh_prover_index_attach_runtime_tables(kh_prover_index_t *index, const uint64_t *selector_d1, const uint64_t *selector_c, const uint64_t *selector_d8,
                                           size_t offset, size_t length);
+/* ---- the index from a gate list: ConstraintSystem::create(gates).public(k).build() + ProverIndex::verifier_index() (constraints.rs, prover_index.rs,
+ * verifier_index.rs:175-300, 405-540) as one call, for circuits WITHOUT a lookup argument ----
+ * kh_permutation_shifts: Shifts::new (permutation.rs:140-199) for the domain of 2^log2_n rows: shift_0 = 1, then six quadratic non-residues r with
+ *   r^n != 1, no repeats, each the first 248 bits (little-endian, 31 bytes) of Blake2b-512(big-endian u32 counter), counter 8, 9, ...
+ *   out: 7 x 4 Montgomery limbs.  Host code; needs no device.
+ * kh_prover_index_create: n_gates records, one per row, as CircuitGate (gate.rs): gate_types[i] = a kh_gate_name id or KH_GATE_ZERO (a row without gate
+ *   constraints); wires[14 i .. 14 i + 13] = the 7 (row, col) pairs the row's cells are wired to (identity: (i, c)); coeffs[60 i .. 60 i + 59] = 15
+ *   Montgomery elements, zero-padded.  The domain is the smallest 2^k with n_gates + zk_rows <= 2^k, where zk_rows and the number of chunks follow
+ *   each other with the SRS size as max_poly_size (constraints.rs:769-771, 946-999); rows n_gates .. n - 1 are Zero rows wired to themselves.  The
+ *   Lagrange basis of the domain is computed on `srs` if it is not registered yet.  The call builds on the device of `srs`: the d1 columns in the
+ *   layout of kh_prover_index_new (coefficients, generic selector, sid, sigma with sigma_c[r] = shift[col] omega^row for the cell (row, col) that
+ *   cell (r, c) is wired to -- zero on rows n + 2 - zk_rows .. n - 2 --, the five library selectors, then ForeignFieldAdd's when the circuit has
+ *   such rows), their coefficient forms and d8 evaluations, x and the permutation vanishing polynomial; then the verifier index: every column
+ *   committed over the Lagrange basis, the generic and the five library selector commitments masked with blinder 1 (an absent gate type gives h
+ *   per chunk), the optional selectors non-hiding, and the digest (the base-field sponge over sigma, coefficients, generic, the five selectors, the
+ *   optional ones).  The result is a kh_prover_index_t for kh_prove / kh_prove_recursive / kh_prove_full that OWNS its device columns
+ *   (kh_prover_index_free releases them); the caller's arrays are not kept.  public_inputs: the number of public inputs (the first rows of
+ *   witness column 0).
+ *   Refused with KH_E_INVALID before any device work: a gate type with a lookup pattern (Xor16, RangeCheck0, RangeCheck1, Rot64, ForeignFieldMul --
+ *   their digest covers the lookup index: kh_prover_index_new + kh_prover_index_attach_lookup is their path), Permutation, an unknown id, a wire
+ *   with row >= n or col >= 7, a coefficient >= p, n_gates < 2, public_inputs >= n - zk_rows.  kh_prover_index_attach_lookup and
+ *   kh_prover_index_attach_runtime_tables refuse a created index.
+ * kh_prover_index_shape: the domain (log2_n), zk_rows and num_chunks of any index (NULL outputs are skipped).
+ * kh_verifier_index_section: a view into the verifier index of a created index (valid until kh_prover_index_free), laid out as kh_proof_section:
+ *   point sections give limbs = count x 8 (affine x | y) and flags = count infinity flags, element sections limbs = count x 4 and flags = NULL.
+ *   An index from kh_prover_index_new gives its shifts and digest; its commitment sections are KH_E_NOTFOUND. */
+#define KH_GATE_ZERO (-1)                  /* a row without gate constraints (GateType::Zero) */
+#define KH_VINDEX_SIGMA_COMM 0             /* 7 x num_chunks points */
+#define KH_VINDEX_COEFFICIENTS_COMM 1      /* 15 x num_chunks points */
+#define KH_VINDEX_GENERIC_COMM 2           /* num_chunks points */
+#define KH_VINDEX_SELECTOR_COMM 3          /* Poseidon (psm), CompleteAdd, VarBaseMul (mul), EndoMul (emul), EndoMulScalar: 5 x num_chunks points */
+#define KH_VINDEX_OPTIONAL_COMM 4          /* num_chunks points per optional gate present, in column order (here: ForeignFieldAdd or nothing) */
+#define KH_VINDEX_SHIFTS 5                 /* 7 elements */
+#define KH_VINDEX_DIGEST 6                 /* 1 base-field element: VerifierIndex::digest */
+int kh_permutation_shifts(int field, unsigned log2_n, uint64_t *out);
+int kh_prover_index_create(kh_srs_t *srs, size_t n_gates, const int *gate_types, const uint32_t *wires, const uint64_t *coeffs,
+                           unsigned public_inputs, kh_prover_index_t **out);
+int kh_prover_index_shape(const kh_prover_index_t *index, unsigned *log2_n, unsigned *zk_rows, size_t *num_chunks);
+int kh_verifier_index_section(const kh_prover_index_t *index, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
+/* wall-clock seconds of kh_prover_index_create's phases, each ended by a device synchronisation: validation + upload + column kernel, transforms
+ * (coefficient forms, d8), commitments, masking + digest; zeros for an index from kh_prover_index_new.  Returns the number of phases (4). */
+int kh_prover_index_phase_seconds(const kh_prover_index_t *index, double *seconds, size_t cap);
 void kh_prover_index_free(kh_prover_index_t *index);
 size_t kh_prove_randomness_count(const kh_prover_index_t *index, int witness_on_host);
 int kh_prove(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, const uint64_t *randomness,

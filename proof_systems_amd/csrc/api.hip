@@ -2529,3 +2529,18 @@ int kh_debug_point_op(int curve, int op, const uint64_t* p_xy, const uint8_t* p_
 }
 
 }  // extern "C"
+
+namespace kh {
+// the column pass of kh_prover_index_create (csrc/prover.cpp; kernel in poly.hip): queued on the main stream like kh_ntt_dev
+int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
+                      size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(d1_dev && shifts && (n_gates == 0 || (selcol_dev && wires_dev && coeffs_dev)), "index_columns_dev: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_index_columns(C, field, selcol_dev, wires_dev, coeffs_dev, n_gates, n, zk_rows, shifts, ncol, d1_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+}  // namespace kh

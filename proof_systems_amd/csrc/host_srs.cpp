@@ -232,4 +232,46 @@ int kh_srs_h(int curve, uint64_t out_xy[8]) {
     group_map(curve).point_of_random_bytes(dig, out_xy);
     return KH_OK;
 }
+// Shifts::new (permutation.rs:140-199): shift_0 = 1, then quadratic non-residues outside the domain, sampled from Blake2b512(counter), no repeats
+int kh_permutation_shifts(int field, unsigned log2_n, uint64_t* out) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(out && log2_n <= 32, "kh_permutation_shifts: null output or log2_n > 32");
+    const Fld F(field);
+    fe half = F.f.p;                                          // (p - 1) / 2 = p >> 1 (p odd)
+    for (int i = 0; i < 4; i++) half.l[i] = (half.l[i] >> 1) | (i < 3 ? half.l[i + 1] << 63 : 0);
+    const fe minus_one = F.neg(F.f.one);
+    auto is_sample = [&](const fe& s) {                       // s^((p-1)/2) = -1 and s^n != 1
+        fe acc = F.f.one, base = s;
+        for (int i = 0; i < 254; i++) {
+            if ((half.l[i >> 6] >> (i & 63)) & 1) acc = F.mul(acc, base);
+            base = F.sqr(base);
+        }
+        if (!khost::eq(acc, minus_one)) return false;
+        fe sn = s;
+        for (unsigned k = 0; k < log2_n; k++) sn = F.sqr(sn);
+        return !khost::eq(sn, F.f.one);
+    };
+    uint32_t counter = 7;
+    auto sample = [&]() {
+        for (;;) {
+            counter++;
+            const uint8_t msg[4] = {(uint8_t)(counter >> 24), (uint8_t)(counter >> 16), (uint8_t)(counter >> 8), (uint8_t)counter};
+            uint8_t dig[64]; blake2b512(msg, 4, dig);
+            fe s = {{0, 0, 0, 0}}; memcpy(&s, dig, 31);       // F::from_random_bytes(&h[..31]): below 2^248 < p
+            s = F.to_mont(s);
+            if (is_sample(s)) return s;
+        }
+    };
+    fe sh[7]; sh[0] = F.f.one;
+    for (int i = 1; i < 7; i++) {
+        bool seen;
+        do {
+            sh[i] = sample();
+            seen = false;
+            for (int j = 0; j < i; j++) seen |= khost::eq(sh[i], sh[j]);
+        } while (seen);
+    }
+    memcpy(out, sh, sizeof(sh));
+    return KH_OK;
+}
 }  // extern "C"

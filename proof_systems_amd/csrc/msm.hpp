@@ -72,6 +72,8 @@ int poly_scan(Context& C, int field, int op, int rev, uint64_t* data_dev, size_t
 int poly_batch_inversion(Context& C, int field, uint64_t* v_dev, size_t n);
 int poly_divide_by_linear(Context& C, int field, const uint64_t* f_dev, size_t len, const uint64_t a[4], uint64_t* q_dev, uint64_t rem[4], uint64_t* rem_dev = nullptr);
 int poly_check_equal(Context& C, const uint64_t* v_dev, size_t n, const uint64_t* expect, uint32_t* flags_dev, unsigned bit);
+int poly_index_columns(Context& C, int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates,
+                       size_t n, size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);
 // expr.hip
 // the gate library as compiled kernels (gates.hip; generated from the same expression DAGs as the token programs)
 int gate_count();

@@ -235,6 +235,42 @@ __global__ void k_linear_quotient(const u64* __restrict__ S, Fe4p a_inv, size_t 
     mul<F>(Fe<F>::load(S + 4 * (i + 1)), pow_u64<F>(Fe<F>::load(a_inv.l), i + 1)).store(q + 4 * i);
 }
 
+// ---------------------------------------------------------------- index columns from gate records (kh_prover_index_create)
+// The d1 columns of ConstraintSystem::build (constraints.rs:596-731) in one pass, one thread per row: the row's 15 coefficients transposed into
+// their columns, the one-hot selectors (Montgomery one in the column `selcol` names, zero in the others) and sigma_c[r] = shift[col] * sid[row]
+// for the cell (row, col) that cell (r, c) is wired to.  Rows from n_gates on are Zero rows wired to themselves.  Every store is a 32-byte
+// element as two 16-byte stores with consecutive rows in consecutive lanes: a wavefront writes 2 KiB of one column per store pair.  sid (column
+// 16) is read, not written; the host validated every wire (row < n, col < 7) and every selector column before the launch.
+struct IndexShifts { Fe4p s[7]; };
+static constexpr int IDX_COLUMNS = 15, IDX_GENERIC = 15, IDX_SID = 16, IDX_SIGMA0 = 17, IDX_SEL0 = 24;
+template <class F>
+__global__ void __launch_bounds__(256)
+k_index_columns(const uint8_t* __restrict__ selcol, const u32* __restrict__ wires, const u64* __restrict__ coeffs, size_t n_gates, size_t n,
+                size_t zk_lo, size_t zk_hi, IndexShifts sh, u32 ncol, u64* __restrict__ d1) {
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const bool gate = r < n_gates;
+    for (int c = 0; c < IDX_COLUMNS; c++)
+        (gate ? Fe<F>::load(coeffs + 4 * (IDX_COLUMNS * r + c)) : Fe<F>::zero()).store(d1 + 4 * (c * n + r));
+    const u32 sc = gate ? selcol[r] : 0u;                     // 0: no selector (Zero rows)
+    (sc == IDX_GENERIC ? Fe<F>::one() : Fe<F>::zero()).store(d1 + 4 * (IDX_GENERIC * n + r));
+    for (u32 k = IDX_SEL0; k < ncol; k++) (sc == k ? Fe<F>::one() : Fe<F>::zero()).store(d1 + 4 * (k * n + r));
+    const u64* sid = d1 + 4 * IDX_SID * n;
+    const bool zk_row = r >= zk_lo && r < zk_hi;              // constraints.rs:523-530
+    for (u32 c = 0; c < 7; c++) {
+        size_t wr = r; u32 wc = c;
+        if (gate) { wr = wires[2 * (7 * r + c)]; wc = wires[2 * (7 * r + c) + 1]; }
+        Fe<F> s = Fe<F>::zero();
+        if (!zk_row) {
+            Fe<F> shift = Fe<F>::load(sh.s[0].l);
+#pragma unroll
+            for (u32 k = 1; k < 7; k++) if (wc == k) shift = Fe<F>::load(sh.s[k].l);
+            s = mul<F>(shift, Fe<F>::load(sid + 4 * wr));
+        }
+        s.store(d1 + 4 * ((IDX_SIGMA0 + c) * n + r));
+    }
+}
+
 #define KH_FIELD_DISPATCH(KERNEL, grid, block, stream, ...)                                             \
     do {                                                                                                \
         if (field == KH_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), grid, block, 0, stream, __VA_ARGS__); \
@@ -323,6 +359,14 @@ int poly_eval_chunks(Context& C, int field, const uint64_t* const* polys_dev, co
 int poly_div_vanishing(Context& C, int field, const uint64_t* f_dev, size_t len, size_t n, uint64_t* q_dev, uint64_t* r_dev) {
     hipStream_t s = C.stream;
     KH_FIELD_DISPATCH(k_div_vanishing, dim3((unsigned)((n + 255) / 256)), dim3(256), s, f_dev, len, n, q_dev, r_dev);
+    return KH_OK;
+}
+int poly_index_columns(Context& C, int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates,
+                       size_t n, size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev) {
+    KH_REQUIRE(n_gates <= n && zk_rows >= 3 && zk_rows < n && ncol >= (size_t)IDX_SEL0 + 5 && ncol < 256, "poly_index_columns: bad shape");
+    IndexShifts sh; memcpy(sh.s, shifts, sizeof(sh.s));
+    KH_FIELD_DISPATCH(k_index_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), C.stream, selcol_dev, wires_dev, coeffs_dev, n_gates, n,
+                      n + 2 - zk_rows, n - 1, sh, (u32)ncol, d1_dev);
     return KH_OK;
 }
 

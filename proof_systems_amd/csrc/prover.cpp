@@ -22,7 +22,11 @@
 #include "../../include/kimchi_hip.h"
 #include "host_ec.hpp"
 
-namespace kh { void set_error(const char* fmt, ...); }
+namespace kh {
+void set_error(const char* fmt, ...);
+int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
+                      size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);     // api.hip / poly.hip: the column pass of kh_prover_index_create
+}
 
 namespace {
 using khost::fe;
@@ -154,6 +158,12 @@ struct kh_prover_index {
     uint64_t* zero_poly = nullptr;                   // n zeros on the device: the public polynomial of a circuit without public inputs
     std::vector<uint64_t> zsel_xy; std::vector<uint8_t> zsel_inf;   // commitment to the zero polynomial masked with 1 (= h per chunk)
     kh_lookup_index* lk = nullptr;                   // kh_prover_index_attach_lookup
+    // kh_prover_index_create: the index owns its columns and carries its verifier index (kh_verifier_index_section) and build phases
+    bool created = false;
+    uint64_t *own_d1 = nullptr, *own_dc = nullptr, *own_d8 = nullptr;
+    struct VSec { std::vector<uint64_t> limbs; std::vector<uint8_t> flags; size_t count = 0; };
+    VSec vsec[KH_VINDEX_OPTIONAL_COMM + 1];
+    double phase[4] = {0, 0, 0, 0};
     const uint64_t* col1(size_t k) const { return d1 + 4 * k * n; }
     const uint64_t* colc(size_t k) const { return dc + 4 * k * n; }
     const uint64_t* col8(size_t k) const { return d8 + 4 * k * 8 * n; }
@@ -232,6 +242,7 @@ int kh_prover_index_new(kh_srs_t* srs, unsigned log2_n, unsigned zk_rows, unsign
 void kh_prover_index_free(kh_prover_index_t* ix) {
     if (!ix) return;
     if (ix->zero_poly) (void)kh_dev_free(ix->zero_poly);
+    for (uint64_t* p : {ix->own_d1, ix->own_dc, ix->own_d8}) if (p) (void)kh_dev_free(p);
     delete ix->lk;
     delete ix;
 }
@@ -241,6 +252,7 @@ int kh_prover_index_attach_lookup(kh_prover_index_t* ix, const int* patterns, si
     if (!ix || !patterns || !n_patterns || n_patterns > 4 || !selectors_d1 || !selectors_c || !selectors_d8 || !table_cols_d1 || !n_table_cols || !atoms_d8) {
         kh::set_error("kh_prover_index_attach_lookup: bad argument"); return KH_E_INVALID;
     }
+    if (ix->created) { kh::set_error("kh_prover_index_attach_lookup: the index comes from kh_prover_index_create, whose digest covers no lookup index"); return KH_E_INVALID; }
     kh_lookup_index* lk = new (std::nothrow) kh_lookup_index();
     if (!lk) { kh::set_error("out of memory"); return KH_E_NOMEM; }
     for (size_t k = 0; k < n_patterns; k++) {
@@ -262,13 +274,189 @@ int kh_prover_index_attach_lookup(kh_prover_index_t* ix, const int* patterns, si
 }
 int kh_prover_index_attach_runtime_tables(kh_prover_index_t* ix, const uint64_t* selector_d1, const uint64_t* selector_c, const uint64_t* selector_d8, size_t offset,
                                           size_t length) {
-    if (!ix || !ix->lk || !selector_d1 || !selector_c || !selector_d8 || !length || offset + length + ix->zk >= ix->n || ix->lk->tcols.size() < 2) {
+    if (ix && ix->created) { kh::set_error("kh_prover_index_attach_runtime_tables: the index comes from kh_prover_index_create (no lookup index)"); return KH_E_INVALID; }
+    if (!ix || !ix->lk || !selector_d1 ||!selector_c || !selector_d8 || !length || offset + length + ix->zk >= ix->n || ix->lk->tcols.size() < 2) {
         kh::set_error("kh_prover_index_attach_runtime_tables: attach the lookup index first; %zu runtime rows at %zu must fit the table (two columns at least)", length, offset);
         return KH_E_INVALID;
     }
     ix->lk->rtsel1 = selector_d1; ix->lk->rtselc = selector_c; ix->lk->rtsel8 = selector_d8;
     ix->lk->rt_offset = offset; ix->lk->rt_len = length;
     return KH_OK;
+}
+
+// ConstraintSystem::create(gates).public(k).build() + ProverIndex::verifier_index() (constraints.rs, prover_index.rs, verifier_index.rs:175-300,
+// 405-540) for circuits without a lookup argument: the same columns, commitments and digest as proof_systems_amd/prover.py::ProverIndex +
+// set_wiring, built from the gate records by one kernel pass (poly.hip: k_index_columns) and the library's own transforms and MSMs.
+int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types, const uint32_t* wires, const uint64_t* coeffs, unsigned public_inputs,
+                           kh_prover_index_t** out) {
+    if (out) *out = nullptr;
+    if (!srs || !out || !gate_types || !wires || !coeffs) { kh::set_error("kh_prover_index_create: null argument"); return KH_E_INVALID; }
+    if (n_gates < 2) { kh::set_error("kh_prover_index_create: %zu gates, a circuit has at least 2 (constraints.rs)", n_gates); return KH_E_INVALID; }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int curve = kh_srs_curve(srs), fid = curve == KH_CURVE_VESTA ? KH_FIELD_FP : KH_FIELD_FQ;
+    const size_t size = kh_srs_size(srs);
+    // ---- the domain: zk_rows and the number of chunks follow each other, with the SRS size as max_poly_size (constraints.rs:769-771, 946-999);
+    //      lower bound max(gates, lookup domain + 1) with the lookup domain = the dummy table row alone
+    const size_t lower = n_gates;
+    size_t zk = 3, bound = lower + zk, nch = 1;
+    for (;;) {
+        size_t sz = 1; while (sz < bound) sz <<= 1;
+        nch = sz < size ? 1 : sz / size;
+        zk = (2 * (PERMUTS + 1) * nch - 2) / PERMUTS + 1;
+        bound = lower + zk;
+        if (sz >= bound) break;
+    }
+    unsigned logn = 0; while (((size_t)1 << logn) < bound) logn++;
+    const size_t n = (size_t)1 << logn;
+    if (logn > 26 || (n >= size && n % size)) { kh::set_error("kh_prover_index_create: a domain of 2^%u rows over an SRS of %zu points is not supported", logn, size); return KH_E_INVALID; }
+    if (public_inputs >= n - zk) { kh::set_error("kh_prover_index_create: %u public inputs, the domain has %zu rows before the %zu zero-knowledge rows", public_inputs, n - zk, zk); return KH_E_INVALID; }
+    // ---- the gate types: selector column per kh gate id (0 = none), refusals with their reason
+    const int ngates = kh_gate_count();
+    std::vector<int> col_of(ngates, -1);             // -1: refused
+    int gid_ffadd = -1;
+    for (int g = 0; g < ngates; g++) {
+        const char* nm = kh_gate_name(g);
+        if (!strcmp(nm, "Generic")) col_of[g] = (int)COLUMNS;
+        for (int k = 0; k < 5; k++) if (!strcmp(nm, LIB_GATES[k])) col_of[g] = (int)SEL0 + k;
+        if (!strcmp(nm, "ForeignFieldAdd")) { col_of[g] = (int)OPT0; gid_ffadd = g; }
+    }
+    std::vector<uint8_t> selcol(n_gates);
+    unsigned live = 0;
+    bool ffadd = false;
+    for (size_t i = 0; i < n_gates; i++) {
+        const int t = gate_types[i];
+        if (t == KH_GATE_ZERO) { selcol[i] = 0; continue; }
+        if (t < 0 || t >= ngates) { kh::set_error("kh_prover_index_create: unknown gate type id %d at row %zu", t, i); return KH_E_INVALID; }
+        if (col_of[t] < 0) {
+            const char* nm = kh_gate_name(t);
+            if (!strcmp(nm, "Permutation")) kh::set_error("kh_prover_index_create: row %zu: Permutation is not a gate type of a circuit", i);
+            else kh::set_error("kh_prover_index_create: row %zu: %s has a lookup pattern; its index needs the lookup index (kh_prover_index_new + "
+                               "kh_prover_index_attach_lookup)", i, nm);
+            return KH_E_INVALID;
+        }
+        selcol[i] = (uint8_t)col_of[t];
+        if (col_of[t] >= (int)SEL0 && col_of[t] < (int)OPT0) live |= 1u << (col_of[t] - (int)SEL0);
+        ffadd |= t == gid_ffadd;
+    }
+    for (size_t i = 0; i < 7 * n_gates; i++)         // the kernel gathers sid[row]: nothing outside the domain may reach it
+        if (wires[2 * i] >= n || wires[2 * i + 1] >= PERMUTS) {
+            kh::set_error("kh_prover_index_create: row %zu, cell %zu is wired to (%u, %u), outside %zu rows x %zu columns", i / 7, i % 7, wires[2 * i], wires[2 * i + 1], n, PERMUTS);
+            return KH_E_INVALID;
+        }
+    const khost::Fld F(fid);
+    for (size_t i = 0; i < COLUMNS * n_gates; i++)
+        if (khost::geq(load(coeffs + 4 * i), F.f.p)) {
+            kh::set_error("kh_prover_index_create: row %zu, coefficient %zu is not a canonical field element (>= p)", i / COLUMNS, i % COLUMNS);
+            return KH_E_INVALID;
+        }
+    // ---- device work, on the SRS's device
+    struct DeviceRestore { int prev; ~DeviceRestore() { if (prev >= 0) (void)kh_set_device(prev); } } device_restore{kh_get_device()};
+    KP(kh_set_device(kh_srs_device(srs)));
+    if (kh_srs_lagrange_chunks(srs, logn) == 0) KP(kh_srs_compute_lagrange(srs, logn));      // SRS::lagrange_basis (index time)
+    fe shifts[7];
+    KP(kh_permutation_shifts(fid, logn, shifts[0].l));
+    const size_t nopt = ffadd ? 1 : 0, ncol = OPT0 + nopt;
+    Dev d1, dc, d8, g_sel, g_wires, g_coeffs;
+    KP(d1.alloc(ncol * n)); KP(dc.alloc((ncol + 2) * n)); KP(d8.alloc((ncol + 2) * 8 * n));
+    KP(kh_dev_alloc((void**)&g_sel.p, n_gates)); KP(kh_dev_alloc((void**)&g_wires.p, 56 * n_gates)); KP(g_coeffs.alloc(COLUMNS * n_gates));
+    KP(kh_dev_upload(g_sel.p, selcol.data(), n_gates));
+    KP(kh_dev_upload(g_wires.p, wires, 56 * n_gates));
+    KP(kh_dev_upload(g_coeffs.p, coeffs, 32 * COLUMNS * n_gates));
+    const fe one = F.f.one;
+    uint64_t* sid = d1.at((COLUMNS + 1) * n);
+    KP(kh_dev_memset_zero(sid, 32 * n));                               // the polynomial x: its evaluations are sid[j] = omega^j
+    KP(kh_dev_upload(sid + 4, one.l, 32));
+    KP(kh_ntt_dev(fid, sid, logn, 0, 1));
+    KP(kh::index_columns_dev(fid, (const uint8_t*)g_sel.p, (const uint32_t*)g_wires.p, g_coeffs.p, n_gates, n, zk, shifts[0].l, ncol, d1.p));
+    KP(kh_sync());
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- coefficient forms, x and the permutation vanishing polynomial (x - w^(n-zk))(x - w^(n-zk+1))(x - w^(n-1)) (permutation.rs:107-118), d8
+    KP(kh_dev_copy(dc.p, d1.p, 32 * ncol * n));
+    KP(kh_ntt_dev(fid, dc.p, logn, 1, ncol));
+    uint64_t w[4];
+    KP(kh_domain_generator(fid, logn, w));
+    const fe omega = load(w);
+    const fe a = fpow(F, omega, n - zk), b = F.mul(a, omega), c = fpow(F, omega, n - 1);
+    const fe ab = F.mul(a, b), zkpm[4] = {F.neg(F.mul(ab, c)), F.add(F.add(ab, F.mul(a, c)), F.mul(b, c)), F.neg(F.add(F.add(a, b), c)), one};
+    KP(kh_dev_memset_zero(dc.at(ncol * n), 32 * 2 * n));
+    KP(kh_dev_upload(dc.at(ncol * n + 1), one.l, 32));
+    KP(kh_dev_upload(dc.at((ncol + 1) * n), zkpm, sizeof(zkpm)));
+    KP(kh_lde_dev(fid, dc.p, logn, 3, d8.p, ncol + 2));
+    KP(kh_sync());
+    const auto t2 = std::chrono::steady_clock::now();
+    // ---- commitments over the Lagrange basis: [coefficients | generic] and [sigma | five selectors | optional], one batched MSM per chunk each
+    const size_t k1 = COLUMNS + 1, k2 = PERMUTS + 5 + nopt;
+    std::vector<uint64_t> xy1(8 * k1 * nch), xy2(8 * k2 * nch), o(8 * (k1 > k2 ? k1 : k2));
+    std::vector<uint8_t> inf1(k1 * nch), inf2(k2 * nch), oi(k1 > k2 ? k1 : k2);
+    for (size_t ch = 0; ch < nch; ch++) {            // chunk lists flat, commitment after commitment
+        KP(kh_msm_batch_dev(srs, (int)logn, (unsigned)ch, 0, d1.p, n, k1, 1, o.data(), oi.data()));
+        for (size_t i = 0; i < k1; i++) { memcpy(&xy1[8 * (i * nch + ch)], &o[8 * i], 64); inf1[i * nch + ch] = oi[i]; }
+        KP(kh_msm_batch_dev(srs, (int)logn, (unsigned)ch, 0, d1.at((COLUMNS + 2) * n), n, k2, 1, o.data(), oi.data()));
+        for (size_t i = 0; i < k2; i++) { memcpy(&xy2[8 * (i * nch + ch)], &o[8 * i], 64); inf2[i * nch + ch] = oi[i]; }
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    // ---- the generic and the five library selectors masked with blinder 1 (verifier_index.rs:255-300), the digest (verifier_index.rs:405-540)
+    std::vector<uint64_t> mxy(8 * 6 * nch), mout(8 * 6 * nch), ones(4 * 6 * nch);
+    std::vector<uint8_t> minf(6 * nch), moinf(6 * nch);
+    memcpy(mxy.data(), &xy1[8 * COLUMNS * nch], 64 * nch); memcpy(minf.data(), &inf1[COLUMNS * nch], nch);
+    memcpy(&mxy[8 * nch], &xy2[8 * PERMUTS * nch], 64 * 5 * nch); memcpy(&minf[nch], &inf2[PERMUTS * nch], 5 * nch);
+    for (size_t i = 0; i < 6 * nch; i++) memcpy(&ones[4 * i], one.l, 32);
+    KP(kh_mask_custom(srs, mxy.data(), minf.data(), 6 * nch, ones.data(), 6 * nch, mout.data(), moinf.data()));
+    SpongeH sp;
+    KP(kh_sponge_new(KH_SPONGE_FQ, curve, &sp.s));
+    KP(kh_sponge_absorb_g(sp.s, xy2.data(), inf2.data(), PERMUTS * nch));                          // sigma
+    KP(kh_sponge_absorb_g(sp.s, xy1.data(), inf1.data(), COLUMNS * nch));                          // coefficients
+    KP(kh_sponge_absorb_g(sp.s, mout.data(), moinf.data(), 6 * nch));                              // generic, psm, complete_add, mul, emul, endomul_scalar
+    if (nopt) KP(kh_sponge_absorb_g(sp.s, xy2.data() + 8 * (PERMUTS + 5) * nch, inf2.data() + (PERMUTS + 5) * nch, nopt * nch));   // foreign_field_add
+    fe digest;
+    KP(kh_sponge_squeeze_field(sp.s, digest.l));
+    // ---- the prover index over the columns (kh_prover_index_new's body), which now owns them
+    std::vector<int> optional;
+    if (ffadd) optional.push_back(gid_ffadd);
+    kh_prover_index* ix = nullptr;
+    KP(kh_prover_index_new(srs, logn, (unsigned)zk, public_inputs, d1.p, dc.p, d8.p, optional.data(), optional.size(), live, shifts[0].l, digest.l, &ix));
+    ix->created = true;
+    ix->own_d1 = d1.p; ix->own_dc = dc.p; ix->own_d8 = d8.p;
+    d1.p = dc.p = d8.p = nullptr;
+    auto points = [&](int s, const uint64_t* pxy, const uint8_t* pinf, size_t cnt) {
+        ix->vsec[s].limbs.assign(pxy, pxy + 8 * cnt); ix->vsec[s].flags.assign(pinf, pinf + cnt); ix->vsec[s].count = cnt;
+    };
+    points(KH_VINDEX_SIGMA_COMM, xy2.data(), inf2.data(), PERMUTS * nch);
+    points(KH_VINDEX_COEFFICIENTS_COMM, xy1.data(), inf1.data(), COLUMNS * nch);
+    points(KH_VINDEX_GENERIC_COMM, mout.data(), moinf.data(), nch);
+    points(KH_VINDEX_SELECTOR_COMM, &mout[8 * nch], &moinf[nch], 5 * nch);
+    points(KH_VINDEX_OPTIONAL_COMM, xy2.data() + 8 * (PERMUTS + 5) * nch, inf2.data() + (PERMUTS + 5) * nch, nopt * nch);
+    const auto t4 = std::chrono::steady_clock::now();
+    const std::chrono::steady_clock::time_point ts[5] = {t0, t1, t2, t3, t4};
+    for (int i = 0; i < 4; i++) ix->phase[i] = std::chrono::duration<double>(ts[i + 1] - ts[i]).count();
+    *out = ix;
+    return KH_OK;
+}
+int kh_prover_index_shape(const kh_prover_index_t* ix, unsigned* log2_n, unsigned* zk_rows, size_t* num_chunks) {
+    if (!ix) { kh::set_error("kh_prover_index_shape: null index"); return KH_E_INVALID; }
+    if (log2_n) *log2_n = ix->logn;
+    if (zk_rows) *zk_rows = (unsigned)ix->zk;
+    if (num_chunks) *num_chunks = ix->nch;
+    return KH_OK;
+}
+int kh_verifier_index_section(const kh_prover_index_t* ix, int section, const uint64_t** limbs, const uint8_t** flags, size_t* count) {
+    if (!ix || section < 0 || section > KH_VINDEX_DIGEST || !limbs || !count) { kh::set_error("kh_verifier_index_section: bad argument"); return KH_E_INVALID; }
+    if (section == KH_VINDEX_SHIFTS || section == KH_VINDEX_DIGEST) {
+        *limbs = section == KH_VINDEX_SHIFTS ? ix->shifts[0].l : ix->digest.l;
+        *count = section == KH_VINDEX_SHIFTS ? 7 : 1;
+        if (flags) *flags = nullptr;
+        return KH_OK;
+    }
+    if (!ix->created) { kh::set_error("kh_verifier_index_section: the index comes from kh_prover_index_new, whose commitments are the caller's"); return KH_E_NOTFOUND; }
+    const kh_prover_index::VSec& s = ix->vsec[section];
+    *limbs = s.limbs.data(); *count = s.count;
+    if (flags) *flags = s.flags.data();
+    return KH_OK;
+}
+int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, size_t cap) {
+    if (!ix || !seconds) { kh::set_error("kh_prover_index_phase_seconds: null argument"); return KH_E_INVALID; }
+    for (size_t i = 0; i < cap && i < 4; i++) seconds[i] = ix->phase[i];
+    return 4;
 }
 
 size_t kh_prove_randomness_count(const kh_prover_index_t* ix, int witness_on_host) {

@@ -40,6 +40,7 @@ SYMBOLS = [
     "kh_msm_sharded", "kh_msm_sharded_dev", "kh_gate_count", "kh_gate_name", "kh_gate_num_constants", "kh_gate_evaluations_dev", "kh_gate_constants", "kh_srs_curve", "kh_lookup_sorted", "kh_private_context_begin", "kh_private_context_end", "kh_private_context_active", "kh_comm_unique_id", "kh_comm_init", "kh_comm_free", "kh_comm_world_size", "kh_comm_rank", "kh_comm_allgather_points",
     "kh_msm_allreduce",
     "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
+    "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
     "kh_commit_non_hiding", "kh_commit_evaluations_non_hiding", "kh_srs_set_blinding_base",
     "kh_srs_get_blinding_base", "kh_mask_custom", "kh_domain_generator", "kh_msm_points_batch", "kh_msm_submit", "kh_msm_wait",
     "kh_ipa_fold_scalars", "kh_inner_product", "kh_ipa_fold_points", "kh_ipa_fold_points_endo", "kh_endos", "kh_scalar_challenge_to_field",
@@ -96,6 +97,11 @@ _lib.kh_batch_inversion_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
 _lib.kh_divide_by_linear_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, U64P]
 _lib.kh_divide_by_linear_async_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_void_p]
 _lib.kh_check_equal_dev.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_uint]
+_lib.kh_permutation_shifts.argtypes = [C.c_int, C.c_uint, U64P]
+_lib.kh_prover_index_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(C.c_void_p)]
+_lib.kh_prover_index_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
+_lib.kh_verifier_index_section.argtypes = [C.c_void_p, C.c_int, C.POINTER(U64P), C.POINTER(U8P), C.POINTER(C.c_size_t)]
+_lib.kh_prover_index_phase_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
 _lib.kh_polycomm_multi_scalar_mul.argtypes = [C.c_int, U64P, U8P, C.POINTER(C.c_size_t), C.c_size_t, U64P, U64P, U8P, C.POINTER(C.c_size_t)]
 _lib.kh_b_poly_coefficients.argtypes = [C.c_int, U64P, C.c_uint, C.c_size_t, U64P]
 _lib.kh_batch_dlog_accumulator_generate.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_size_t, U64P, U8P]
@@ -802,10 +808,14 @@ PROOF_SECTIONS = {"w_comm": 0, "z_comm": 1, "t_comm": 2, "public_comm": 3, "eval
                   "challenges": 11, "lookup_sorted_comm": 12, "lookup_aggreg_comm": 13, "lookup_runtime_comm": 14}
 LOOKUP_PATTERN_IDS = {"Xor": 0, "Lookup": 1, "RangeCheck": 2, "ForeignFieldMul": 3}
 PROOF_PHASES = ("witness_upload", "witness_commit", "z", "quotient", "evaluations", "opening")
+GATE_ZERO = -1                                      # KH_GATE_ZERO: a row without gate constraints
+VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "selector_comm": 3, "optional_comm": 4, "shifts": 5, "digest": 6}
+INDEX_PHASES = ("columns", "transforms", "commitments", "digest")
 
 
 class NativeProverIndex:
-    """kh_prover_index_new: the C++ prover's view of device-resident index columns (they must outlive the handle)."""
+    """kh_prover_index_new: the C++ prover's view of device-resident index columns (they must outlive the handle); or, NativeProverIndex.create,
+    kh_prover_index_create: an index built from gate records that owns its columns."""
 
     def __init__(self, srs, log2_n: int, zk_rows: int, public: int, d1, dc, d8, optional_gate_ids, live_mask: int, shifts, digest):
         self._h = C.c_void_p()
@@ -814,6 +824,49 @@ class NativeProverIndex:
         _check(_lib.kh_prover_index_new(srs._h, C.c_uint(log2_n), C.c_uint(zk_rows), C.c_uint(public), C.c_void_p(d1.ptr), C.c_void_p(dc.ptr), C.c_void_p(d8.ptr),
                                         opt, C.c_size_t(len(optional_gate_ids)), C.c_uint(live_mask), _p64(sh), _p64(dg), C.byref(self._h)))
         self._keep = (srs, d1, dc, d8)
+
+    @classmethod
+    def create(cls, srs, gate_types, wires, coeffs, public: int = 0):
+        """kh_prover_index_create: the index (columns owned by the handle) and its verifier index from gate records -- gate_types: one kh gate id
+        per row (GATE_ZERO: no constraints); wires: (rows, 7, 2) (row, col) pairs; coeffs: (rows, 15, 4) Montgomery limbs."""
+        self = cls.__new__(cls)
+        types = np.ascontiguousarray(gate_types, dtype=np.int32).reshape(-1)
+        rows = types.shape[0]
+        w = np.ascontiguousarray(wires, dtype=np.uint32).reshape(rows, 7, 2)
+        co = _c64(coeffs, (rows, 15, 4))
+        self._h = C.c_void_p()
+        _check(_lib.kh_prover_index_create(srs._h, C.c_size_t(rows), types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           _p64(co), C.c_uint(public), C.byref(self._h)))
+        self._keep = (srs,)
+        return self
+
+    def shape(self):
+        """(log2_n, zk_rows, num_chunks)"""
+        ln, zk, nch = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
+        _check(_lib.kh_prover_index_shape(self._h, C.byref(ln), C.byref(zk), C.byref(nch)))
+        return ln.value, zk.value, nch.value
+
+    def verifier_index(self):
+        """kh_verifier_index_section for every section: {name: (xy (k, 8), inf (k,))} for commitments, {name: (k, 4) limbs} for shifts / digest."""
+        out = {}
+        for name, sid in VINDEX_SECTIONS.items():
+            lp = C.POINTER(C.c_uint64)(); fp = C.POINTER(C.c_uint8)(); cnt = C.c_size_t(0)
+            _check(_lib.kh_verifier_index_section(self._h, C.c_int(sid), C.byref(lp), C.byref(fp), C.byref(cnt)))
+            k = cnt.value
+            if fp:
+                out[name] = (np.ctypeslib.as_array(lp, shape=(k, 8)).copy() if k else np.zeros((0, 8), np.uint64),
+                             np.ctypeslib.as_array(fp, shape=(k,)).copy() if k else np.zeros(0, np.uint8))
+            elif name in ("shifts", "digest"):
+                out[name] = np.ctypeslib.as_array(lp, shape=(k, 4)).copy()
+            else:                                     # a commitment section with no entries (no optional gate)
+                out[name] = (np.zeros((0, 8), np.uint64), np.zeros(0, np.uint8))
+        return out
+
+    def phase_seconds(self):
+        """kh_prover_index_phase_seconds: {phase: seconds} of kh_prover_index_create"""
+        ph = (C.c_double * 4)()
+        _check(min(0, _lib.kh_prover_index_phase_seconds(self._h, ph, C.c_size_t(4))))
+        return dict(zip(INDEX_PHASES, list(ph)))
 
     def attach_lookup(self, patterns, sel_d1, sel_c, sel_d8, table_cols, table_ids, atoms8):
         """kh_prover_index_attach_lookup: patterns = names in the reference's order; per pattern three DevBufs; table columns / ids / atoms: DevBufs."""
@@ -1049,6 +1102,13 @@ def endos(curve: int):
 def domain_generator(field: int, log2_n: int):
     out = np.zeros(4, dtype=np.uint64)
     _check(_lib.kh_domain_generator(field, log2_n, _p64(out)))
+    return out
+
+
+def permutation_shifts(field: int, log2_n: int):
+    """kh_permutation_shifts: Shifts::new for 2^log2_n rows, (7, 4) Montgomery limbs (host code, no device)."""
+    out = np.zeros((7, 4), dtype=np.uint64)
+    _check(_lib.kh_permutation_shifts(C.c_int(field), C.c_uint(log2_n), _p64(out)))
     return out
 
 

@@ -322,6 +322,41 @@ def bench_circuit_index(curve: int, log2_n: int, srs=None) -> ProverIndex:
     return ProverIndex(curve, log2_n, co, srs)
 
 
+class CreatedIndex:
+    """An index built natively from a gate list (kh_prover_index_create: ConstraintSystem::create(gates).public(k).build() + the verifier index, no
+    lookup argument).  The handle owns the device columns; this object carries what create_proof_native and the verifier side read."""
+
+    GATE_TYPES = ProverIndex.GATE_TYPES
+
+    def __init__(self, srs, gate_types, wires, coeffs, public: int = 0):
+        """gate_types: one per row, a name ("Generic", a library gate, "ForeignFieldAdd", "Zero") or a kh gate id; wires: per row 7 (row, col)
+        pairs; coeffs: (rows, 15, 4) Montgomery limbs."""
+        gids = khip.gate_ids()
+        ids = [t if isinstance(t, (int, np.integer)) else (khip.GATE_ZERO if t == "Zero" else gids[t]) for t in gate_types]
+        names = {g: t for t, g in gids.items()}
+        self.srs, self.curve, self.public = srs, srs.curve, public
+        self.fid = khip.FP if self.curve == khip.VESTA else khip.FQ
+        F = self.F = Fld(self.fid)
+        self.native = khip.NativeProverIndex.create(srs, ids, wires, coeffs, public)
+        self.log2_n, self.zk_rows, self.num_chunks = self.native.shape()
+        self.n, self.size = 1 << self.log2_n, srs.n
+        self.live_gate_types = {names[g] for g in set(ids) if g != khip.GATE_ZERO}
+        self.optional = [t for t in OPTIONAL_GATES if t in self.live_gate_types]
+        self.omega = F.value(khip.domain_generator(self.fid, self.log2_n))
+        self.h = khip.srs_h(self.curve)
+        vi = self.vindex = self.native.verifier_index()
+        nch = self.num_chunks
+        comms = lambda key: [(vi[key][0][i * nch:(i + 1) * nch], vi[key][1][i * nch:(i + 1) * nch]) for i in range(vi[key][1].shape[0] // nch)]
+        self.sigma_comm, self.coefficients_comm = comms("sigma_comm"), comms("coefficients_comm")
+        self.generic_comm, self.selector_comms = comms("generic_comm")[0], comms("selector_comm")
+        self.optional_comms = dict(zip(self.optional, comms("optional_comm")))
+        self.shifts = F.values(vi["shifts"])
+        self.digest = vi["digest"][0]
+
+    def free(self):
+        self.native.free()
+
+
 def _horner(p: int, coeffs, x: int) -> int:
     acc = 0
     for c in reversed(coeffs):
@@ -331,6 +366,8 @@ def _horner(p: int, coeffs, x: int) -> int:
 
 def native_index(ix: "ProverIndex"):
     """The C++ prover's handle on this index (kh_prover_index_new + the lookup / runtime-table attachments), made once."""
+    if isinstance(ix, CreatedIndex):
+        return ix.native
     LI = getattr(ix, "lookup", None)
     h = getattr(ix, "_native", None)
     if h is None or h[1] is not ix.d8:
