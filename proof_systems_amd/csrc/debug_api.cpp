@@ -1,0 +1,92 @@
+// debug_api.cpp -- test hooks (kh_debug_*).
+#include "api_internal.hpp"
+
+using namespace kh;
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------- test hooks
+// test hook of csrc/rebase.hip: g'[i] = sum_{q < Q} coef[q] * g[q N + i], i < N = n / Q, from the handle's c = 16 window tables (affine out)
+int kh_debug_rebase_points(kh_srs_t* srs, const uint64_t* coef, size_t Q, uint64_t* out_xy, uint32_t* out_fail) {
+    KH_ON_DEVICE_OF(srs);
+    KH_REQUIRE(srs && coef && out_xy && out_fail, "kh_debug_rebase_points: null argument");
+    KH_REQUIRE(srs->g_precomp_c == 16, "the handle has no c = 16 window tables");
+    KH_REQUIRE(Q >= 1 && srs->n % Q == 0 && (srs->n / Q) % 64 == 0, "Q = %zu must divide the SRS size %zu into a multiple of 64", Q, srs->n);
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    const size_t N = srs->n / Q;
+    DevBuf B, part, lists, out, dcoef, fail, scratch;
+    if ((rc = B.reserve(rebase_bucket_bytes(N))) || (rc = part.reserve(rebase_part_bytes(N))) || (rc = lists.reserve(rebase_list_bytes(Q))) || (rc = out.reserve(N * 64)) ||
+        (rc = dcoef.reserve(Q * 32)) || (rc = fail.reserve(64)) || (rc = scratch.reserve(N * 128))) return rc;
+    KH_HIP(hipMemcpyAsync(dcoef.p, coef, Q * 32, hipMemcpyHostToDevice, C.stream));
+    KH_HIP(hipMemsetAsync(fail.p, 0, 64, C.stream));
+    if ((rc = rebase_points(C.stream, srs->curve, dcoef.as<uint64_t>(), Q, srs->g.p, srs->g_stride, N, B.p, part.p, lists.p))) return rc;
+    if ((rc = rebase_tables(C.stream, srs->curve, part.p, N, nullptr, 0, 256, scratch.p, out.p, fail.as<uint32_t>()))) return rc;      // (c = 256: one level = the points themselves, affine)
+    KH_HIP(hipMemcpyAsync(out_xy, out.p, N * 64, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipMemcpyAsync(out_fail, fail.p, 4, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipStreamSynchronize(C.stream));
+    return KH_OK;
+}
+int kh_debug_glv_split(int scalar_field, const uint64_t* scalars, size_t n, uint32_t* out) {
+    KH_REQUIRE(scalar_field == KH_FIELD_FP || scalar_field == KH_FIELD_FQ, "unknown field id %d", scalar_field);
+    KH_REQUIRE(scalars && out, "kh_debug_glv_split: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    DevBuf din, dout;
+    if ((rc = din.reserve(n * 32)) || (rc = dout.reserve(n * 40))) return rc;
+    KH_HIP(hipMemcpyAsync(din.p, scalars, n * 32, hipMemcpyHostToDevice, C.stream));
+    if ((rc = msm_debug_glv_split(C.stream, scalar_field, din.as<uint64_t>(), n, dout.as<uint32_t>()))) return rc;
+    KH_HIP(hipMemcpyAsync(out, dout.p, n * 40, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipStreamSynchronize(C.stream));
+    return KH_OK;
+}
+int kh_debug_field_op(int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
+    KH_REQUIRE(a && out, "null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    void *da = nullptr, *db = nullptr, *dout = nullptr;
+    KH_HIP(hipMalloc(&da, n * 32)); KH_HIP(hipMalloc(&dout, n * 32));
+    KH_HIP(hipMemcpy(da, a, n * 32, hipMemcpyHostToDevice));
+    if (b) { KH_HIP(hipMalloc(&db, n * 32)); KH_HIP(hipMemcpy(db, b, n * 32, hipMemcpyHostToDevice)); }
+    rc = debug_field_op(C, field, op, (const uint64_t*)da, (const uint64_t*)db, (uint64_t*)dout, n);
+    if (rc == KH_OK) { KH_HIP(hipStreamSynchronize(C.stream)); KH_HIP(hipMemcpy(out, dout, n * 32, hipMemcpyDeviceToHost)); }
+    (void)hipFree(da); (void)hipFree(dout); if (db) (void)hipFree(db);
+    return rc;
+}
+int kh_debug_point_op(int curve, int op, const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
+                      uint64_t* out_xy, uint8_t* out_inf, size_t n) {
+    KH_REQUIRE(p_xy && q_xy && out_xy && out_inf, "null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    void *dp, *dq, *dpi = nullptr, *dqi = nullptr, *dout;
+    KH_HIP(hipMalloc(&dp, n * 64)); KH_HIP(hipMalloc(&dq, n * 64)); KH_HIP(hipMalloc(&dout, n * 128));
+    KH_HIP(hipMemcpy(dp, p_xy, n * 64, hipMemcpyHostToDevice)); KH_HIP(hipMemcpy(dq, q_xy, n * 64, hipMemcpyHostToDevice));
+    if (p_inf) { KH_HIP(hipMalloc(&dpi, n)); KH_HIP(hipMemcpy(dpi, p_inf, n, hipMemcpyHostToDevice)); }
+    if (q_inf) { KH_HIP(hipMalloc(&dqi, n)); KH_HIP(hipMemcpy(dqi, q_inf, n, hipMemcpyHostToDevice)); }
+    rc = debug_point_op(C, curve, op, (const uint64_t*)dp, (const uint8_t*)dpi, (const uint64_t*)dq, (const uint8_t*)dqi, (uint8_t*)dout, n);
+    if (rc == KH_OK) {
+        std::vector<khost::xyzz> res(n);
+        KH_HIP(hipStreamSynchronize(C.stream));
+        KH_HIP(hipMemcpy(res.data(), dout, n * 128, hipMemcpyDeviceToHost));
+        khost::Crv crv(curve);
+        for (size_t i = 0; i < n; i++) {
+            const unsigned char* raw = (const unsigned char*)&res[i];
+            bool handed = true;                                   // op 6: a record of 0xff bytes = madd29 declined (exceptional case possible)
+            for (int k = 0; k < 128; k++) handed &= raw[k] == 0xff;
+            if (handed) { memset(out_xy + 8 * i, 0, 64); out_inf[i] = 2; continue; }
+            khost::aff a; bool inf = crv.to_affine(res[i], a);
+            memcpy(out_xy + 8 * i, &a, 64); out_inf[i] = inf ? 1 : 0;
+        }
+    }
+    (void)hipFree(dp); (void)hipFree(dq); (void)hipFree(dout); if (dpi) (void)hipFree(dpi); if (dqi) (void)hipFree(dqi);
+    return rc;
+}
+
+}  // extern "C"

@@ -136,9 +136,8 @@ static int lagrange_t(Context& C, int sfield, const void* g_dev, size_t srs_size
     KH_HIP(hipMemcpyAsync(ninv_dev, &ninv, 32, hipMemcpyHostToDevice, s));
     KH_HIP(hipStreamSynchronize(s));
     hipLaunchKernelGGL((k_lag_init<BF>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint8_t*)g_dev, start, num_terms, log_n, A.as<uint8_t>());
-    static const bool lag_quad = !(getenv("KH_LAG_QUAD") && atoi(getenv("KH_LAG_QUAD")) == 0);      // 0: one lane per butterfly (round 1's kernel)
     for (unsigned lm = 0; lm < log_n; lm++) {
-        if (lag_quad && n >= 8)
+        if (n >= 8)
             hipLaunchKernelGGL((k_lag_stage_q<BF>), dim3((unsigned)((4 * (n / 2) + 255) / 256)), dim3(256), 0, s, A.as<uint8_t>(), tw_plain, log_n, lm);
         else
             hipLaunchKernelGGL((k_lag_stage<BF>), dim3((unsigned)((n / 2 + 127) / 128)), dim3(128), 0, s, A.as<uint8_t>(), tw_plain, log_n, lm);

@@ -1820,7 +1820,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     // wide windows (a second table set, c = 20: msm.hpp) for big single MSMs: 13 instead of 16 additions per scalar.  Needs the wide sort's
     // record (<= 65,536 digits per pass-A block, <= 1024 blocks).
     const bool wide = basis.wide_pts && basis.wide_c > 16 && basis.wide_c - 9 <= (int)PART2_MAXLOW && n >= msm_wide_min_n() && k <= 4 &&
-                      (size_t)((256 + basis.wide_c - 1) / basis.wide_c) * n <= ((size_t)1 << 26);
+                      (size_t)windows_of(basis.wide_c) * n <= ((size_t)1 << 26);
     // MSM_SPREAD_SCALARS: the caller vouches that the scalars are spread like random ones (the opening rounds: products with Fiat-Shamir challenges), so
     // no bucket collects a large share of the entries: the two-phase hot-bucket kernels are not launched (two empty dependent launches per MSM, ~20 us of
     // the ~340 us of an opening round) and a bucket's quad sums however many task partials it finds -- correct for any input, slow for a skewed one.
@@ -1831,7 +1831,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
     const int c = wide ? basis.wide_c : (basis.precomp_c ? basis.precomp_c : msm_pick_window(n));
     const bool glv = basis.glv && !wide && basis.precomp_c != 0;      // rows 0 .. W/2-1: 2^(c w) P, rows W/2 .. W-1: phi of them (csrc/rebase.hip)
-    const int W = glv ? 2 * ((128 + c - 1) / c) : (256 + c - 1) / c;
+    const int W = glv ? 2 * ((128 + c - 1) / c) : windows_of(c);
     const u32 nb = 1u << (c - 1);
     const int precomp = (wide || basis.precomp_c) ? 1 : 0;
     // slices per (window, msm): enough blocks to fill the chip (~512), no more -- the per-slice histograms
@@ -2307,7 +2307,7 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
 
 // the same on a caller's stream, with a caller's scratch buffer ((W - 1) x n x 128 bytes), no synchronisation: the opening's rebased tables (rebase.hip)
 int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, void* scratch) {
-    const int W = (256 + c - 1) / c;
+    const int W = windows_of(c);
     dim3 grid((unsigned)((n + 63) / 64));                  // small blocks: the chain of 255 doublings per point is pure latency, one wave per SIMD is the fastest
     if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_precompute<FqParams>), grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
     else hipLaunchKernelGGL((k_precompute<FpParams>), grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
@@ -2315,7 +2315,7 @@ int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, v
     return KH_OK;
 }
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c) {
-    const int W = (256 + c - 1) / c;
+    const int W = windows_of(c);
     DevBuf& scratch = C.scratch("precompute");
     int rc = scratch.reserve((size_t)(W - 1) * n * 128); if (rc) return rc;
     dim3 grid((unsigned)((n + 255) / 256));

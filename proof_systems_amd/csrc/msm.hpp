@@ -1,4 +1,4 @@
-// msm.hpp -- internal interface between api.hip and msm.hip
+// msm.hpp -- internal interface between the extern "C" boundary (context.hip, srs.cpp, msm_api.cpp, opening.cpp, vector_api.cpp, debug_api.cpp) and the kernel files
 #pragma once
 #include "common.hpp"
 #include "host_ec.hpp"
@@ -21,6 +21,7 @@ size_t rebase_bucket_bytes(size_t N);
 size_t rebase_part_bytes(size_t N);
 size_t rebase_list_bytes(size_t Q);
 static constexpr int MSM_PRECOMP_C = 16;          // window width of the precomputed tables
+constexpr int windows_of(int c) { return (256 + c - 1) / c; }      // windows of c bits that cover a 256-bit scalar = tables of a set
 static constexpr int MSM_WIDE_C = 20;             // ... of the second table set big bases get: 13 windows, 2^19 buckets (msm.hip, "wide windows")
 void msm_set_wide_min_n(size_t n);
 void msm_set_sort_staging(unsigned entries, unsigned max_passes);   // k_part2_sort's staged scatter (kh_msm_set_sort_staging)
@@ -28,7 +29,6 @@ size_t msm_wide_min_n();                          // MSMs of at least this many 
                                                   // measured (tools/wide_ab.py, pipelined Mscalar/s narrow -> wide): 2^17 537 -> 400, 2^18 655 -> 685, 2^19 746 -> 815,
                                                   // 2^20 896 -> 960..1000, 2^21 770 -> 976, 2^22 861 -> 992
 static constexpr size_t MSM_PRECOMP_MIN_N = 1024; // smaller bases keep the plain per-window path
-static constexpr int IPA_ROUND_C = 16;            // window width of the opening rounds' table set (KH_IPA_C overrides; < 16: a second, narrower set)
 // enqueue all device work of k MSMs on slot S (returns immediately); msm_finish waits for it and does the host part
 // flags: MSM_SPREAD_SCALARS (msm.hip, "the caller vouches ..."), MSM_LATENCY
 static constexpr int MSM_SPREAD_SCALARS = 2;

@@ -398,8 +398,7 @@ static std::vector<unsigned> split_passes(unsigned log_n) {
 // 0.808 against 0.750 ms, profiles/r04_ntt29_* -- live in tools/ntt29/ with their limb model; DESIGN.md section 4 has the analysis.)
 template <class F>
 static int launch_pass(Context& C, const PassArgs& A, u64 tiles) {
-    static const size_t lds_pad = getenv("KH_NTT_LDS_PAD") ? (size_t)atol(getenv("KH_NTT_LDS_PAD")) : 0;      // (occupancy experiments: extra dynamic LDS per workgroup)
-    size_t lds = ((size_t)4 << (A.log_R + A.log_T)) * 8 + ((size_t)4 << (A.log_R ? A.log_R - 1 : 0)) * 8 + lds_pad;
+    size_t lds = ((size_t)4 << (A.log_R + A.log_T)) * 8 + ((size_t)4 << (A.log_R ? A.log_R - 1 : 0)) * 8;
     hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS>), dim3((unsigned)tiles), dim3(NTT_THREADS), lds, C.stream, A);
     KH_HIP(hipGetLastError());
     return KH_OK;

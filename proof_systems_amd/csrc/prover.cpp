@@ -25,7 +25,7 @@
 namespace kh {
 void set_error(const char* fmt, ...);
 int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
-                      size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);     // api.hip / poly.hip: the column pass of kh_prover_index_create
+                      size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);     // vector_api.cpp / poly.hip: the column pass of kh_prover_index_create
 }
 
 namespace {
@@ -584,15 +584,14 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     Dev e8; KP(e8.alloc(16 * N8));
     const bool any_lib = (ix->live != 0) || nopt > 0;
     const size_t w8 = (!any_lib && !all_gates) ? PERMUTS : COLUMNS;     // generic + permutation read w0..w6 only
-    // The witness extension (0.35 ms of throughput work) either right behind the interpolation -- it then runs underneath the transfer / the witness commitment, and the
-    // small kernels of the permutation aggregation queue behind it -- or (KH_LDE_LATE=1) behind the aggregation, underneath the z commitment.
-    static const bool lde_late = getenv("KH_LDE_LATE") && atoi(getenv("KH_LDE_LATE")) != 0;
+    // The witness extension (0.35 ms of throughput work) goes right behind the interpolation: it then runs underneath the transfer / the witness commitment, and the
+    // small kernels of the permutation aggregation queue behind it.
     auto interpolate_extend = [&](size_t c0, size_t c1) -> int {       // columns c0 .. c1-1: evaluations -> coefficients -> d8
         if (c1 <= c0) return KH_OK;
         int rc_ = kh_dev_copy(cf.at(c0 * NB), ev.at(c0 * NB), (c1 - c0) * NB * 32); if (rc_) return rc_;
         rc_ = kh_ntt_dev(fid, cf.at(c0 * NB), logn, 1, c1 - c0); if (rc_) return rc_;
         const size_t e1 = c1 < w8 ? c1 : w8;
-        if (!lde_late && e1 > c0) rc_ = kh_lde_dev(fid, cf.at(c0 * NB), logn, 3, e8.at(c0 * N8), e1 - c0);
+        if (e1 > c0) rc_ = kh_lde_dev(fid, cf.at(c0 * NB), logn, 3, e8.at(c0 * N8), e1 - c0);
         return rc_;
     };
     size_t cols_pending = 0;                           // first column whose interpolation / extension is not queued yet
@@ -840,7 +839,6 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     KP(kh_dev_copy(zc, zcol, NB * 32));
     KP(kh_ntt_dev(fid, zc, logn, 1, 1));
     if (nch == 1 && size == n) { KP(kh_msm_submit(srs, KH_BASIS_G, 0, 0, zc, n, 1, 1, &tk)); have_tk = true; }   // ... while z is extended to d8
-    if (lde_late) KP(kh_lde_dev(fid, cf.p, logn, 3, e8.p, w8));
     KP(kh_lde_dev(fid, zc, logn, 3, e8.at(COLUMNS * N8), 1));
     std::vector<uint64_t> zxy, zbx; std::vector<uint8_t> zinf, zbi;
     const fe* z_blind = draw(nch);

@@ -245,13 +245,8 @@ static int rebase_t(hipStream_t s, const u64* coef, size_t Q, const void* tables
     uint8_t* outs = part + (size_t)RB_CHUNKS * 2 * N * 128;
     hipLaunchKernelGGL((k_rb_plan<SF>), dim3(1), dim3(1024), 0, s, coef, (u32)Q, off, list, dig);
     if (after_plan) KH_HIP(hipEventRecord(after_plan, s));   // `coef` is the caller's again once this event has passed
-    // The two kernels with thousands of waves are held to a few waves per CU (dynamic LDS they do not use, as k_acc_wide29 is held): resident all at once they
-    // took the wave slots and registers of every CU for ~0.3 ms, and the round in flight -- whose kernels outrank them in issue priority but have to be PLACED
-    // first -- stalled for that long (a 5 us k_digits took 73, the round 1.2-1.36 ms instead of 0.35).  KH_IPA_REBASE_WAVES_PER_CU (experiment, default 0 = no limit: 2 / 4 / 8 waves per CU measured 5.28 / 5.20 / 5.06 ms per opening against 4.97-5.01 -- the stall was the host's, see RbExtra).
-    static const unsigned rb_waves = getenv("KH_IPA_REBASE_WAVES_PER_CU") ? (unsigned)atoi(getenv("KH_IPA_REBASE_WAVES_PER_CU")) : 0u;
-    const size_t hold = (rb_waves == 0 || rb_waves >= 32) ? 0 : std::min<size_t>(65536, (((size_t)160 << 10) / (rb_waves + 1) + 1024) & ~(size_t)1023);
-    hipLaunchKernelGGL((k_rb_acc<BF>), dim3(RB_BUCKETS, (unsigned)(N / 64)), dim3(64), hold, s, off, list, (const uint8_t*)tables, stride, (u32)N, B);
-    hipLaunchKernelGGL((k_rb_reduce1<BF>), dim3(RB_CHUNKS, (unsigned)(N / 16)), dim3(64), hold, s, B, (u32)N, part);
+    hipLaunchKernelGGL((k_rb_acc<BF>), dim3(RB_BUCKETS, (unsigned)(N / 64)), dim3(64), 0, s, off, list, (const uint8_t*)tables, stride, (u32)N, B);
+    hipLaunchKernelGGL((k_rb_reduce1<BF>), dim3(RB_CHUNKS, (unsigned)(N / 16)), dim3(64), 0, s, B, (u32)N, part);
     hipLaunchKernelGGL((k_rb_reduce2<BF>), dim3((unsigned)((N + 3) / 4)), dim3(64), 0, s, part, (u32)N, outs);
     KH_HIP(hipGetLastError());
     return KH_OK;
@@ -274,7 +269,7 @@ int rebase_tables(hipStream_t s, int curve, const void* part, size_t N, const vo
     KH_REQUIRE(extra <= 2 && (extra == 0 || extra_affine_host), "rebase_tables: at most two extra points");
     // glv_beta: W = the levels built by doubling (the lower 128 bits: HALF the chain); the kernel that normalises them writes phi of every level W levels further up
     const int glv = glv_beta ? 1 : 0;
-    const int W = glv ? (128 + c - 1) / c : (256 + c - 1) / c;
+    const int W = glv ? (128 + c - 1) / c : windows_of(c);
     RbBeta beta; memset(&beta, 0, sizeof beta);
     if (glv) memcpy(beta.l, glv_beta, 32);
     const u32 npts = (u32)(N + extra);

@@ -1,0 +1,369 @@
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+#include <stdlib.h>
+
+#include "api_internal.hpp"
+
+using namespace kh;
+
+// transfer buffers of the host-pointer transforms (kh_ntt / kh_lde: host_transform below)
+struct XferPair { DevBuf in, out; bool busy = false, owned = false; };
+static std::mutex g_xfer_mu;
+static std::vector<std::unique_ptr<XferPair>>& xfer_registry(int d) {     // (never destroyed: no hipFree from a static destructor after the runtime has gone)
+    static auto* r = new std::vector<std::unique_ptr<XferPair>>[KH_MAX_DEVICES];
+    return r[d];
+}
+struct ThreadXfer {
+    XferPair* p[KH_MAX_DEVICES] = {nullptr};
+    ~ThreadXfer() { std::lock_guard<std::mutex> lk(g_xfer_mu); for (XferPair* q : p) if (q) { q->owned = false; q->busy = false; } }
+};
+static XferPair* xfer_acquire(int d) {
+    static thread_local ThreadXfer tl;
+    std::lock_guard<std::mutex> lk(g_xfer_mu);
+    if (!tl.p[d]) {
+        for (auto& q : xfer_registry(d)) if (!q->owned) { tl.p[d] = q.get(); break; }
+        if (!tl.p[d]) { xfer_registry(d).emplace_back(new XferPair); tl.p[d] = xfer_registry(d).back().get(); }
+        tl.p[d]->owned = true;
+    }
+    tl.p[d]->busy = true;
+    return tl.p[d];
+}
+static void xfer_release(XferPair* q) { std::lock_guard<std::mutex> lk(g_xfer_mu); q->busy = false; }
+struct XferGuard { XferPair* q; ~XferGuard() { xfer_release(q); } };
+void kh::xfer_trim(int d) {              // kh_trim: every pair that is not inside a call right now gives its memory back
+    if (d < 0 || d >= KH_MAX_DEVICES) return;
+    std::lock_guard<std::mutex> lk(g_xfer_mu);
+    for (auto& q : xfer_registry(d)) if (!q->busy) { q->in.release(); q->out.release(); }
+}
+
+extern "C" {
+
+// ---------------------------------------------------------------------------------- coefficient-vector operations around the opening
+int kh_combine_polys_dev(int field, const uint64_t* const* polys_dev, const size_t* lens, const size_t* num_chunks, size_t m,
+                         const uint64_t polyscale[4], size_t srs_length, uint64_t* out_dev, size_t* out_len) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(out_dev && polyscale && srs_length > 0 && (m == 0 || (polys_dev && lens && num_chunks)), "kh_combine_polys_dev: bad argument");
+    int rc = ensure_init(); if (rc) return rc;
+    khost::Fld F(field);
+    khost::fe ps; memcpy(&ps, polyscale, 32);
+    khost::fe scale = F.f.one;
+    std::vector<const uint64_t*> segs; std::vector<size_t> slen; std::vector<khost::fe> scales;
+    size_t longest = 0;
+    for (size_t i = 0; i < m; i++) {                                  // utils.rs:164-176
+        size_t offset = 0;
+        for (size_t c = 0; c < num_chunks[i]; c++) {
+            const size_t lo = std::min(offset, lens[i]), hi = std::min(offset + srs_length, lens[i]);
+            if (hi > lo) { segs.push_back(polys_dev[i] + 4 * lo); slen.push_back(hi - lo); scales.push_back(scale); longest = std::max(longest, hi - lo); }
+            scale = F.mul(scale, ps);
+            offset += srs_length;
+        }
+    }
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    if ((rc = poly_lincomb(C, field, segs.data(), slen.data(), (const uint64_t*)scales.data(), segs.size(), out_dev, srs_length))) return rc;
+    C.mark_async();
+    if (out_len) *out_len = longest;
+    return KH_OK;
+}
+int kh_poly_lincomb_dev(int field, const uint64_t* const* polys_dev, const size_t* lens, const uint64_t* scalars, size_t m,
+                        uint64_t* out_dev, size_t out_len) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE((out_dev || out_len == 0) && (m == 0 || (polys_dev && lens && scalars)), "kh_poly_lincomb_dev: null argument");
+    for (size_t i = 0; i < m; i++) KH_REQUIRE(lens[i] <= out_len, "polynomial %zu has %zu coefficients, the output %zu", i, lens[i], out_len);
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_lincomb(C, field, polys_dev, lens, scalars, m, out_dev, out_len);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_b_init_dev(int field, const uint64_t* elm, size_t k, const uint64_t evalscale[4], size_t padded_len, uint64_t* out_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(out_dev && evalscale && (elm || k == 0), "kh_b_init_dev: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    khost::Fld F(field);
+    khost::fe es; memcpy(&es, evalscale, 32);
+    std::vector<khost::fe> scales(k);
+    khost::fe sc = F.f.one;
+    for (size_t i = 0; i < k; i++) { scales[i] = sc; sc = F.mul(sc, es); }
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_b_init(C, field, elm, (const uint64_t*)scales.data(), k, padded_len, out_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_evaluate_chunks_batch_dev(int field, const uint64_t* const* polys_dev, const size_t* lens, const size_t* num_chunks, size_t m,
+                                 size_t chunk_size, const uint64_t* points, size_t npts, uint64_t* out) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(chunk_size > 0 && (m == 0 || (polys_dev && lens && num_chunks)) && (points || npts == 0), "kh_evaluate_chunks_batch_dev: bad argument");
+    size_t total = 0;
+    for (size_t j = 0; j < m; j++) {
+        KH_REQUIRE(polys_dev[j] || lens[j] == 0, "polynomial %zu: null pointer", j);
+        KH_REQUIRE((lens[j] + chunk_size - 1) / chunk_size <= num_chunks[j], "polynomial %zu: %zu coefficients need more than %zu chunks of %zu (assert_eq at utils/src/dense_polynomial.rs:63)", j, lens[j], num_chunks[j], chunk_size);
+        total += num_chunks[j];
+    }
+    KH_REQUIRE(out || total * npts == 0, "null output");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    return poly_eval_chunks(C, field, polys_dev, lens, num_chunks, m, chunk_size, points, npts, out);
+}
+int kh_evaluate_chunks_dev(int field, const uint64_t* coeffs_dev, size_t len, size_t chunk_size, size_t num_chunks,
+                           const uint64_t* points, size_t npts, uint64_t* out) {
+    return kh_evaluate_chunks_batch_dev(field, &coeffs_dev, &len, &num_chunks, 1, chunk_size, points, npts, out);
+}
+int kh_divide_by_vanishing_poly_dev(int field, const uint64_t* f_dev, size_t len, unsigned log2_n, uint64_t* q_dev, uint64_t* r_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n <= 32 && r_dev && (f_dev || len == 0), "kh_divide_by_vanishing_poly_dev: bad argument");
+    const size_t n = (size_t)1 << log2_n;
+    KH_REQUIRE(q_dev || len <= n, "null quotient buffer");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_div_vanishing(C, field, f_dev, len, n, q_dev, r_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+
+int kh_field_scan_dev(int field, int op, int reverse, uint64_t* data_dev, size_t n) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE((op == KH_SCAN_ADD || op == KH_SCAN_MUL) && (data_dev || n == 0), "kh_field_scan_dev: bad argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_scan(C, field, op, reverse ? 1 : 0, data_dev, n);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_batch_inversion_dev(int field, uint64_t* v_dev, size_t n) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(v_dev || n == 0, "null vector");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_batch_inversion(C, field, v_dev, n);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_divide_by_linear_dev(int field, const uint64_t* f_dev, size_t len, const uint64_t a[4], uint64_t* q_dev, uint64_t rem[4]) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(a && rem && (f_dev || len == 0) && (q_dev || len <= 1), "kh_divide_by_linear_dev: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    return poly_divide_by_linear(C, field, f_dev, len, a, q_dev, rem);
+}
+int kh_divide_by_linear_async_dev(int field, const uint64_t* f_dev, size_t len, const uint64_t a[4], uint64_t* q_dev, uint64_t* rem_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(a && (f_dev || len == 0) && (q_dev || len <= 1), "kh_divide_by_linear_async_dev: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_divide_by_linear(C, field, f_dev, len, a, q_dev, nullptr, rem_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_check_equal_dev(const uint64_t* v_dev, size_t n, const uint64_t* expect, uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE((v_dev || n == 0) && flags_dev && bit < 32, "kh_check_equal_dev: bad argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_check_equal(C, v_dev, n, expect, flags_dev, bit);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_expr_evaluations_dev(int field, const uint32_t* tokens, size_t ntok, const uint64_t* const* cols_dev, const size_t* col_len, size_t ncols,
+                            const uint64_t* constants, size_t nconsts, size_t rows, unsigned stride, unsigned next_shift, int accumulate,
+                            uint64_t* out_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(tokens && ntok > 0 && (out_dev || rows == 0) && stride > 0, "kh_expr_evaluations_dev: bad argument");
+    KH_REQUIRE((ncols == 0 || (cols_dev && col_len)) && (nconsts == 0 || constants), "kh_expr_evaluations_dev: null table");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = expr_run(C, field, tokens, ntok, cols_dev, col_len, ncols, constants, nconsts, rows, stride, next_shift, accumulate, out_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+
+int kh_gate_count(void) { return gate_count(); }
+const char* kh_gate_name(int gate) { return gate_name(gate); }
+int kh_gate_num_constants(int gate) { return gate_num_constants(gate); }
+int kh_gate_constants(int field, int gate, const uint64_t alpha[4], const uint64_t endo[4], const uint64_t* params, size_t nparams, uint64_t* out) {
+    KH_REQUIRE(out, "kh_gate_constants: null output");
+    return gate_constants(field, gate, alpha, endo, params, nparams, out);
+}
+int kh_gate_evaluations_dev(int field, int gate, const uint64_t* const* cols_dev, size_t col_len, const uint64_t* constants, size_t nconsts, size_t rows,
+                            unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(cols_dev && constants && (out_dev || rows == 0) && stride > 0, "kh_gate_evaluations_dev: bad argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = gate_run(C, field, gate, cols_dev, col_len, constants, nconsts, rows, stride, next_shift, accumulate, out_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------- NTT
+int kh_domain_generator(int field, unsigned log2_n, uint64_t out[4]) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n <= 32 && out, "log2_n must be <= 32 (two-adicity of the Pasta fields)");
+    khost::fe w = kh::ntt_host_root(field, log2_n, 0);
+    memcpy(out, &w, 32);
+    return KH_OK;
+}
+int kh_ntt_dev(int field, uint64_t* data_dev, unsigned log2_n, int inverse, size_t batch) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n <= 28, "log2_n = %u too large", log2_n);
+    KH_REQUIRE(data_dev || batch == 0, "null data");
+    int rc = ensure_init(); if (rc) return rc;
+    if (batch == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = ntt_run(C, field, data_dev, log2_n, inverse, batch);
+    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;   // a later MSM on another slot waits for this point
+    return rc;
+}
+int kh_lde_dev(int field, const uint64_t* coeffs_dev, unsigned log2_n, unsigned log2_blowup, uint64_t* out_dev, size_t batch) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n + log2_blowup <= 28, "log2 size %u too large", log2_n + log2_blowup);
+    KH_REQUIRE((coeffs_dev && out_dev) || batch == 0, "null data");
+    int rc = ensure_init(); if (rc) return rc;
+    if (batch == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = lde_run(C, field, coeffs_dev, log2_n, log2_blowup, out_dev, batch);
+    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;
+    return rc;
+}
+int kh_coset_ntt_dev(int field, const uint64_t* coeffs_dev, unsigned log2_n, const uint64_t shift[4], uint64_t* out_dev, size_t batch) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n <= 28 && shift, "kh_coset_ntt_dev: bad argument");
+    KH_REQUIRE((coeffs_dev && out_dev) || batch == 0, "null data");
+    int rc = ensure_init(); if (rc) return rc;
+    if (batch == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_coset_ntt(C, field, coeffs_dev, log2_n, shift, out_dev, batch);
+    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;
+    return rc;
+}
+// Host-pointer transforms (what the ark-poly patch calls: interpolate -> kh_ntt, evaluate_over_domain_by_ref -> kh_lde).  The reference calls them from
+// 15 / 16 rayon workers at once (prover.rs:370-381, constraints.rs:488-494), one column each, and each call moves 2 + 2 (or 2 + 16) MB over PCIe around
+// ~10-50 us of kernels.  Until round 4 a call held the library lock across upload, transform, download and a stream synchronisation on the one shared
+// workspace: sixteen callers ran strictly one after the other at ~27 GB/s (profiles/r04_pcie_inclusive.txt).  Now a call uses the calling thread's own device buffers, moves its data
+// on the calling thread's own copy stream WITHOUT the lock (uploads, downloads and their pageable-memory staging of different callers overlap, and PCIe
+// runs both directions at once), and takes the lock only to queue its kernels on the main stream, ordered by events.  (A call owns the calling thread's
+// transfer buffers, not blocks of the shared pool.)  A batched call is cut into column
+// groups that go through the same three stages, so that group i's download runs under group i + 1's transform.
+}  // extern "C"
+namespace {
+struct HostXferEvents {
+    hipEvent_t up[KH_MAX_DEVICES] = {nullptr}, done[KH_MAX_DEVICES] = {nullptr};
+    ~HostXferEvents() { for (int d = 0; d < KH_MAX_DEVICES; d++) { if (up[d]) (void)hipEventDestroy(up[d]); if (done[d]) (void)hipEventDestroy(done[d]); } }
+};
+// The calling thread's own device buffers for these transfers, per device, grown on demand: the shared block pool is the wrong place for them -- once a
+// prover's buffers have filled it to its limit, a freed 16 MB block went back to the driver (hipFree synchronises the device) and the next call allocated
+// afresh: 16 concurrent extensions took 11.6 ms inside bench.py's process against 5.2 ms in a fresh one.  The buffers live in a per-device REGISTRY, not in
+// thread-local storage: a thread holds a pair while it exists (a rayon worker lives as long as its pool) and hands it back at exit without
+// freeing anything (no hipFree from a TLS destructor); the next new thread adopts it; kh_trim frees every pair that is not inside a call at that moment.
+static size_t xfer_keep_bytes() {          // per buffer, per thread; KH_XFER_KEEP_MB overrides.  64 MB holds what the reference's callers hand over one column at
+    static const size_t v = getenv("KH_XFER_KEEP_MB") ? (size_t)atol(getenv("KH_XFER_KEEP_MB")) << 20 : (size_t)64 << 20;   // a time (2 MB in, 16 MB out at 2^16 -> 2^19) and a
+    return v;                              // few columns batched; a 16-column batched extension (268 MB out) pays its allocation each time (~5 ms of PCIe beside it)
+}
+// in -> [upload] -> din -> run(din, dout, columns) -> dout -> [download] -> out, `batch` columns of in_col / out_col bytes, in groups
+template <class Run>
+int host_transform(const uint64_t* in, size_t in_col, uint64_t* out, size_t out_col, size_t batch, bool in_place, Run run) {
+    static thread_local HostXferEvents ev;
+    Context& C = ctx();
+    const int d = C.device >= 0 && C.device < KH_MAX_DEVICES ? C.device : 0;
+    hipStream_t cs = thread_copy_stream(); if (!cs) return KH_E_DEVICE;
+    if (!ev.up[d]) { KH_HIP(hipEventCreateWithFlags(&ev.up[d], hipEventDisableTiming)); KH_HIP(hipEventCreateWithFlags(&ev.done[d], hipEventDisableTiming)); }
+    // column groups: at most four, at least ~4 MB of output each (a group costs three stream hand-overs)
+    size_t groups = batch < 4 ? batch : 4;
+    while (groups > 1 && (batch / groups) * out_col < ((size_t)4 << 20)) groups--;
+    XferPair* const bufs = xfer_acquire(d);
+    XferGuard guard{bufs};
+    int rc;
+    if ((rc = bufs->in.reserve(batch * in_col))) return rc;
+    if (!in_place && (rc = bufs->out.reserve(batch * out_col))) return rc;
+    char* const di = (char*)bufs->in.p; char* const dst_dev = in_place ? di : (char*)bufs->out.p;
+    // (the queueing in a lambda: whatever fails, the copy stream is drained before this returns -- a caller that sees an error may free `in` / `out`
+    // at once, and a copy queued earlier in the call may still be reading or writing them)
+    auto queue_all = [&]() -> int {
+        size_t c0 = 0;
+        for (size_t g = 0; g < groups; g++) {
+            const size_t c1 = batch * (g + 1) / groups, cols = c1 - c0;
+            KH_HIP(hipMemcpyAsync(di + c0 * in_col, (const char*)in + c0 * in_col, cols * in_col, hipMemcpyHostToDevice, cs));
+            KH_HIP(hipEventRecord(ev.up[d], cs));
+            {
+                std::lock_guard<std::mutex> lk(C.mu);
+                KH_HIP(hipStreamWaitEvent(C.stream, ev.up[d], 0));
+                int rr;
+                if ((rr = run(C, (uint64_t*)(di + c0 * in_col), (uint64_t*)(dst_dev + c0 * out_col), cols))) return rr;
+                KH_HIP(hipEventRecord(ev.done[d], C.stream));
+                C.mark_async();
+            }
+            KH_HIP(hipStreamWaitEvent(cs, ev.done[d], 0));
+            KH_HIP(hipMemcpyAsync((char*)out + c0 * out_col, dst_dev + c0 * out_col, cols * out_col, hipMemcpyDeviceToHost, cs));
+            c0 = c1;
+        }
+        return KH_OK;
+    };
+    rc = queue_all();
+    const hipError_t drained = hipStreamSynchronize(cs);  // everything this call queued anywhere has finished: the buffers are free for the thread's next call
+    if (rc == KH_OK && drained != hipSuccess) { set_error("hipStreamSynchronize (transfer stream): %s", hipGetErrorString(drained)); rc = KH_E_DEVICE; }
+    if (rc != KH_OK) {                                     // the transform kernels of a failed call may still be queued on the library stream, reading the buffers
+        std::lock_guard<std::mutex> lk(C.mu);
+        (void)hipStreamSynchronize(C.stream);
+    }
+    // a thread keeps its two buffers for its next call -- up to a bound: after a huge batch they go back (the PCIe time of such a call dwarfs an allocation)
+    if (bufs->in.cap > xfer_keep_bytes()) bufs->in.release();
+    if (bufs->out.cap > xfer_keep_bytes()) bufs->out.release();
+    if (rc != KH_OK) return rc;
+    {
+        std::lock_guard<std::mutex> lk(C.mu);
+        collect_timings(C, C.timer);                       // (the phases of the LAST transform queued on this context: exact for a lone caller)
+    }
+    return KH_OK;
+}
+}  // namespace
+extern "C" {
+int kh_ntt_set_max_logr(unsigned max_logr) { return ntt_set_max_logr(max_logr); }
+int kh_ntt(int field, uint64_t* data, unsigned log2_n, int inverse, size_t batch) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n <= 28, "log2_n = %u too large", log2_n);
+    KH_REQUIRE(data || batch == 0, "null data");
+    int rc = ensure_init(); if (rc) return rc;
+    if (batch == 0) return KH_OK;
+    const size_t col = ((size_t)1 << log2_n) * 32;
+    return host_transform(data, col, data, col, batch, true,
+                          [&](Context& C, uint64_t* din, uint64_t*, size_t cols) { return ntt_run(C, field, din, log2_n, inverse, cols); });
+}
+int kh_lde(int field, const uint64_t* coeffs, unsigned log2_n, unsigned log2_blowup, uint64_t* out, size_t batch) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(log2_n + log2_blowup <= 28, "log2 size %u too large", log2_n + log2_blowup);
+    KH_REQUIRE((coeffs && out) || batch == 0, "null data");
+    int rc = ensure_init(); if (rc) return rc;
+    if (batch == 0) return KH_OK;
+    const size_t in_col = ((size_t)1 << log2_n) * 32, out_col = in_col << log2_blowup;
+    return host_transform(coeffs, in_col, out, out_col, batch, false,
+                          [&](Context& C, uint64_t* din, uint64_t* dout, size_t cols) { return lde_run(C, field, din, log2_n, log2_blowup, dout, cols); });
+}
+
+}  // extern "C"
+
+namespace kh {
+// the column pass of kh_prover_index_create (csrc/prover.cpp; kernel in poly.hip): queued on the main stream like kh_ntt_dev
+int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
+                      size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(d1_dev && shifts && (n_gates == 0 || (selcol_dev && wires_dev && coeffs_dev)), "index_columns_dev: null argument");
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poly_index_columns(C, field, selcol_dev, wires_dev, coeffs_dev, n_gates, n, zk_rows, shifts, ncol, d1_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+}  // namespace kh

@@ -83,3 +83,13 @@ def test_header_is_plain_c99(tmp_path):
     src.write_text('#include "kimchi_hip.h"\nint main(void) { return KH_OK + KH_TOK_LOAD - KH_TOK_LOAD + KH_SCAN_ADD; }\n')
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(root, "include"), "-fsyntax-only", str(src)])
+
+
+def test_integration_build_line_names_every_source():
+    """INTEGRATION.md spells the manual build out as csrc/{...}.hip csrc/{...}.cpp: the two lists are exactly __graft_entry__.SOURCES."""
+    import __graft_entry__ as ge
+    txt = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    named = []
+    for stems, ext in re.findall(r"csrc/\{([a-z_0-9,]+)\}\.(hip|cpp)", txt):
+        named += [s + "." + ext for s in stems.split(",")]
+    assert sorted(named) == sorted(ge.SOURCES)

@@ -388,7 +388,7 @@ def test_verifier_accepts_reference_proof(golden):
     assert not P.ipa_verify(c, g, h, [bad], rng)
 
 
-# ---- the identities kh_ipa_open's split of sg relies on (csrc/api.hip: ipa_sg_collect, csrc/ipa.hip: k_sg_split), against the literal definitions
+# ---- the identities kh_ipa_open's split of sg relies on (csrc/opening.cpp: ipa_sg_collect, csrc/ipa.hip: k_sg_split), against the literal definitions
 
 def test_sg_splits_on_the_last_challenge():
     """sg = <b_poly_coefficients(chals), G> (ipa.rs:452-470) = A + [u_last] B with A / B the sums over the even / odd points weighted by the
