@@ -609,7 +609,7 @@ int kh_prover_index_attach_runtime_tables(kh_prover_index_t *index, const uint64
  *   (kh_prover_index_free releases them); the caller's arrays are not kept.  public_inputs: the number of public inputs (the first rows of
  *   witness column 0).
  *   Refused with KH_E_INVALID before any device work: a gate type with a lookup pattern (Xor16, RangeCheck0, RangeCheck1, Rot64, ForeignFieldMul --
- *   their digest covers the lookup index: kh_prover_index_new + kh_prover_index_attach_lookup is their path), Permutation, an unknown id, a wire
+ *   their digest covers the lookup index: kh_prover_index_create_lookup below, or kh_prover_index_new + kh_prover_index_attach_lookup, is their path), Permutation, an unknown id, a wire
  *   with row >= n or col >= 7, a coefficient >= p, n_gates < 2, public_inputs >= n - zk_rows.  kh_prover_index_attach_lookup and
  *   kh_prover_index_attach_runtime_tables refuse a created index.
  * kh_prover_index_shape: the domain (log2_n), zk_rows and num_chunks of any index (NULL outputs are skipped).
@@ -627,9 +627,59 @@ int kh_prover_index_attach_runtime_tables(kh_prover_index_t *index, const uint64
 int kh_permutation_shifts(int field, unsigned log2_n, uint64_t *out);
 int kh_prover_index_create(kh_srs_t *srs, size_t n_gates, const int *gate_types, const uint32_t *wires, const uint64_t *coeffs,
                            unsigned public_inputs, kh_prover_index_t **out);
+/* ---- the same call for circuits WITH a lookup argument: + LookupConstraintSystem::create (lookup/index.rs:188-430, lookups.rs:176-264, 500-513) and the
+ * lookup side of the verifier index (verifier_index.rs:189-216, 482-530) ----
+ * kh_prover_index_create_lookup takes the gate records of kh_prover_index_create, where a gate type may now also be RangeCheck0, RangeCheck1, Rot64,
+ *   ForeignFieldMul, Xor16 or KH_GATE_LOOKUP (GateType::Lookup); the caller's fixed lookup tables (LookupTable: id, `width` columns of `len` entries,
+ *   column-major, Montgomery limbs); and the runtime-table configurations (RuntimeTableCfg: id and first column; the second column arrives with each
+ *   proof, kh_prove_full's runtime_values, all tables concatenated in this order).  n_runtime > 0 is `runtime_tables: Some(..)` of the reference.
+ *   (The reference's `Some(vec![])` -- runtime tables enabled, none configured: a runtime selector and uses_runtime_tables without any runtime row --
+ *   cannot be expressed here: n_runtime = 0 is `None`.)
+ *   Domain: the smallest 2^k with max(n_gates, lookup_domain_size + 1) + zk_rows <= 2^k, lookup_domain_size = the fixed tables' entries + the runtime
+ *   tables' + 4096 if a gate has the RangeCheck or ForeignFieldMul pattern + 256 if one has the Xor pattern + 1 if no fixed table has id 0
+ *   (constraints.rs:883-945); zk_rows and the chunks as for kh_prover_index_create.
+ *   Patterns (LookupPattern::from_gate): Xor16 -> Xor on its row; KH_GATE_LOOKUP -> Lookup on its row; RangeCheck0, Rot64 -> RangeCheck on their
+ *   row; RangeCheck1 -> RangeCheck on its row and the next; ForeignFieldMul -> ForeignFieldMul on its row and the next.
+ *   Optional gate selector columns 29..: RangeCheck0, RangeCheck1, ForeignFieldAdd, ForeignFieldMul, Xor16, Rot64, those the circuit has, in that order.
+ *   The combined table: the caller's tables in their order, then the gate tables the patterns need (the 12-bit range-check table, id 1, before the
+ *   4-bit XOR table, id 0), then the runtime tables (first column fixed, second zero); max(table widths, largest joint lookup) columns, zero rows up
+ *   to n; a table-id column when some id is not 0; with runtime tables the runtime selector (1 outside the runtime rows, 0 on them and on the
+ *   zero-knowledge rows).  All of these, the pattern selectors and the three row-set atoms of the lookup constraints are produced on the device from
+ *   the gate types and the raw table data (csrc/lookup_index.hip); table columns and ids are committed and masked with blinder 1, the pattern
+ *   selectors and the runtime selector committed non-hiding, and the digest absorbs, after the optional gates (in verifier_index.rs's order:
+ *   range_check0, range_check1, foreign_field_mul, foreign_field_add, xor, rot): tables, ids, runtime selector, pattern selectors.
+ *   The result is a created index like kh_prover_index_create's (it owns its columns; kh_prover_index_attach_* refuse it); kh_prove* run the lookup
+ *   argument on it as after kh_prover_index_attach_lookup / _attach_runtime_tables.  Without any lookup pattern the call gives what
+ *   kh_prover_index_create gives (tables, if any, still count for the domain, as in the reference).
+ *   Refused with KH_E_INVALID before any device work, besides kh_prover_index_create's refusals: two tables (fixed, gate or runtime) with the same id,
+ *   a runtime id configured twice, a table with id 0 without an all-zero entry, entries >= n - zk_rows - 1, a table value >= p, a table without
+ *   columns (or more than 128), runtime tables for a circuit without a lookup pattern.
+ * KH_VINDEX_LOOKUP_*: the lookup sections of kh_verifier_index_section; empty (count 0) for an index without a lookup argument. */
+#define KH_GATE_LOOKUP (-2)                /* GateType::Lookup: a row without gate constraints that carries the Lookup pattern */
+#define KH_VINDEX_LOOKUP_TABLE_COMM 7      /* one commitment per table column: width x num_chunks points */
+#define KH_VINDEX_LOOKUP_TABLE_IDS_COMM 8  /* num_chunks points, or none when every table id is 0 */
+#define KH_VINDEX_LOOKUP_SELECTOR_COMM 9   /* num_chunks points per pattern present, in the order xor, lookup, range_check, foreign_field_mul */
+#define KH_VINDEX_LOOKUP_RUNTIME_SELECTOR_COMM 10   /* num_chunks points, or none without runtime tables */
+#define KH_VINDEX_LOOKUP_INFO 11           /* NOT field elements: 2 records of 4 plain 64-bit words, flags = NULL: max_per_row, max_joint_size, joint_lookup_used,
+                                              uses_runtime_tables | patterns present (bit k = pattern id k), table columns, first runtime row, runtime rows */
+typedef struct { int id; size_t width, len; const uint64_t *data; } kh_lookup_table_t;
+typedef struct { int id; size_t len; const uint64_t *first_column; } kh_runtime_table_cfg_t;
+int kh_prover_index_create_lookup(kh_srs_t *srs, size_t n_gates, const int *gate_types, const uint32_t *wires, const uint64_t *coeffs,
+                                  unsigned public_inputs, const kh_lookup_table_t *tables, size_t n_tables,
+                                  const kh_runtime_table_cfg_t *runtime, size_t n_runtime, kh_prover_index_t **out);
+/* Debug view of the lookup columns an index carries (built by kh_prover_index_create_lookup or attached): the device address and the element count
+ * (n, or 8n for d8 columns) of column k of a block; KH_E_NOTFOUND where the index has none.  The memory belongs to the index (or its caller). */
+#define KH_LOOKUP_COL_SELECTOR_D1 0        /* k-th pattern selector: evaluations on the domain */
+#define KH_LOOKUP_COL_SELECTOR_C 1         /* ... its coefficient form */
+#define KH_LOOKUP_COL_SELECTOR_D8 2        /* ... its evaluations on d8 */
+#define KH_LOOKUP_COL_TABLE_D1 3           /* k-th column of the combined table */
+#define KH_LOOKUP_COL_TABLE_IDS_D1 4       /* the table-id column (k = 0) */
+#define KH_LOOKUP_COL_ATOM_D8 5            /* k = 0 VanishesOnZeroKnowledgeAndPreviousRows, 1 UnnormalizedLagrangeBasis(0), 2 UnnormalizedLagrangeBasis(-zk_rows - 1) */
+#define KH_LOOKUP_COL_RUNTIME_SELECTOR 6   /* the runtime-table selector: k = 0 evaluations, 1 coefficient form, 2 d8 */
+int kh_debug_lookup_column(const kh_prover_index_t *index, int block, size_t k, const uint64_t **dev, size_t *elems);
 int kh_prover_index_shape(const kh_prover_index_t *index, unsigned *log2_n, unsigned *zk_rows, size_t *num_chunks);
 int kh_verifier_index_section(const kh_prover_index_t *index, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
-/* wall-clock seconds of kh_prover_index_create's phases, each ended by a device synchronisation: validation + upload + column kernel, transforms
+/* wall-clock seconds of kh_prover_index_create(_lookup)'s phases (the lookup columns count under the first, their transforms and atoms under the second), each ended by a device synchronisation: validation + upload + column kernel, transforms
  * (coefficient forms, d8), commitments, masking + digest; zeros for an index from kh_prover_index_new.  Returns the number of phases (4). */
 int kh_prover_index_phase_seconds(const kh_prover_index_t *index, double *seconds, size_t cap);
 void kh_prover_index_free(kh_prover_index_t *index);

@@ -74,6 +74,14 @@ int poly_divide_by_linear(Context& C, int field, const uint64_t* f_dev, size_t l
 int poly_check_equal(Context& C, const uint64_t* v_dev, size_t n, const uint64_t* expect, uint32_t* flags_dev, unsigned bit);
 int poly_index_columns(Context& C, int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates,
                        size_t n, size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);
+// lookup_index.hip: the lookup index's columns and row-set atoms (kh_prover_index_create_lookup)
+int lookup_selector_columns(Context& C, int field, const uint8_t* code_dev, size_t n_gates, size_t n, const int* patterns, size_t npat, uint64_t* out_dev);
+int lookup_table_columns(Context& C, int field, const uint64_t* segs_dev, const uint64_t* seg_starts /* host: first row per segment */, size_t nseg, const uint64_t* data_dev, size_t n, size_t width,
+                         uint64_t* tcols_dev, uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows);
+int lookup_atom_denominators(Context& C, int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4],
+                             uint64_t* atoms_dev);
+int lookup_atom_finish(Context& C, int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4],
+                       uint64_t* atoms_dev);
 // expr.hip
 // the gate library as compiled kernels (gates.hip; generated from the same expression DAGs as the token programs)
 int gate_count();

@@ -26,6 +26,12 @@ namespace kh {
 void set_error(const char* fmt, ...);
 int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
                       size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);     // vector_api.cpp / poly.hip: the column pass of kh_prover_index_create
+// vector_api.cpp / lookup_index.hip: the lookup passes of kh_prover_index_create_lookup
+int lookup_selectors_dev(int field, const uint8_t* code_dev, size_t n_gates, size_t n, const int* patterns, size_t npat, uint64_t* out_dev);
+int lookup_tables_dev(int field, const uint64_t* segs_dev, const uint64_t* seg_starts, size_t nseg, const uint64_t* data_dev, size_t n, size_t width, uint64_t* tcols_dev,
+                      uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows);
+int lookup_atom_denominators_dev(int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4], uint64_t* atoms_dev);
+int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4], uint64_t* atoms_dev);
 }
 
 namespace {
@@ -157,12 +163,13 @@ struct kh_prover_index {
     fe shifts[7], digest, omega, endo;
     uint64_t* zero_poly = nullptr;                   // n zeros on the device: the public polynomial of a circuit without public inputs
     std::vector<uint64_t> zsel_xy; std::vector<uint8_t> zsel_inf;   // commitment to the zero polynomial masked with 1 (= h per chunk)
-    kh_lookup_index* lk = nullptr;                   // kh_prover_index_attach_lookup
-    // kh_prover_index_create: the index owns its columns and carries its verifier index (kh_verifier_index_section) and build phases
+    kh_lookup_index* lk = nullptr;                   // kh_prover_index_attach_lookup, or built by kh_prover_index_create_lookup
+    // kh_prover_index_create(_lookup): the index owns its columns and carries its verifier index (kh_verifier_index_section) and build phases
     bool created = false;
     uint64_t *own_d1 = nullptr, *own_dc = nullptr, *own_d8 = nullptr;
+    uint64_t *own_l1 = nullptr, *own_lc = nullptr, *own_l8 = nullptr;      // the lookup columns: d1, coefficient forms of the selectors, their d8 + the atoms
     struct VSec { std::vector<uint64_t> limbs; std::vector<uint8_t> flags; size_t count = 0; };
-    VSec vsec[KH_VINDEX_OPTIONAL_COMM + 1];
+    VSec vsec[KH_VINDEX_LOOKUP_INFO + 1];
     double phase[4] = {0, 0, 0, 0};
     const uint64_t* col1(size_t k) const { return d1 + 4 * k * n; }
     const uint64_t* colc(size_t k) const { return dc + 4 * k * n; }
@@ -242,7 +249,7 @@ int kh_prover_index_new(kh_srs_t* srs, unsigned log2_n, unsigned zk_rows, unsign
 void kh_prover_index_free(kh_prover_index_t* ix) {
     if (!ix) return;
     if (ix->zero_poly) (void)kh_dev_free(ix->zero_poly);
-    for (uint64_t* p : {ix->own_d1, ix->own_dc, ix->own_d8}) if (p) (void)kh_dev_free(p);
+    for (uint64_t* p : {ix->own_d1, ix->own_dc, ix->own_d8, ix->own_l1, ix->own_lc, ix->own_l8}) if (p) (void)kh_dev_free(p);
     delete ix->lk;
     delete ix;
 }
@@ -252,7 +259,11 @@ int kh_prover_index_attach_lookup(kh_prover_index_t* ix, const int* patterns, si
     if (!ix || !patterns || !n_patterns || n_patterns > 4 || !selectors_d1 || !selectors_c || !selectors_d8 || !table_cols_d1 || !n_table_cols || !atoms_d8) {
         kh::set_error("kh_prover_index_attach_lookup: bad argument"); return KH_E_INVALID;
     }
-    if (ix->created) { kh::set_error("kh_prover_index_attach_lookup: the index comes from kh_prover_index_create, whose digest covers no lookup index"); return KH_E_INVALID; }
+    if (ix->created) {
+        kh::set_error(ix->lk ? "kh_prover_index_attach_lookup: the index comes from kh_prover_index_create_lookup and carries its own lookup index"
+                             : "kh_prover_index_attach_lookup: the index comes from kh_prover_index_create, whose digest covers no lookup index");
+        return KH_E_INVALID;
+    }
     kh_lookup_index* lk = new (std::nothrow) kh_lookup_index();
     if (!lk) { kh::set_error("out of memory"); return KH_E_NOMEM; }
     for (size_t k = 0; k < n_patterns; k++) {
@@ -274,7 +285,11 @@ int kh_prover_index_attach_lookup(kh_prover_index_t* ix, const int* patterns, si
 }
 int kh_prover_index_attach_runtime_tables(kh_prover_index_t* ix, const uint64_t* selector_d1, const uint64_t* selector_c, const uint64_t* selector_d8, size_t offset,
                                           size_t length) {
-    if (ix && ix->created) { kh::set_error("kh_prover_index_attach_runtime_tables: the index comes from kh_prover_index_create (no lookup index)"); return KH_E_INVALID; }
+    if (ix && ix->created) {
+        kh::set_error(ix->lk ? "kh_prover_index_attach_runtime_tables: the index comes from kh_prover_index_create_lookup, which configures its runtime tables itself"
+                             : "kh_prover_index_attach_runtime_tables: the index comes from kh_prover_index_create (no lookup index)");
+        return KH_E_INVALID;
+    }
     if (!ix || !ix->lk || !selector_d1 ||!selector_c || !selector_d8 || !length || offset + length + ix->zk >= ix->n || ix->lk->tcols.size() < 2) {
         kh::set_error("kh_prover_index_attach_runtime_tables: attach the lookup index first; %zu runtime rows at %zu must fit the table (two columns at least)", length, offset);
         return KH_E_INVALID;
@@ -285,19 +300,100 @@ int kh_prover_index_attach_runtime_tables(kh_prover_index_t* ix, const uint64_t*
 }
 
 // ConstraintSystem::create(gates).public(k).build() + ProverIndex::verifier_index() (constraints.rs, prover_index.rs, verifier_index.rs:175-300,
-// 405-540) for circuits without a lookup argument: the same columns, commitments and digest as proof_systems_amd/prover.py::ProverIndex +
-// set_wiring, built from the gate records by one kernel pass (poly.hip: k_index_columns) and the library's own transforms and MSMs.
-int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types, const uint32_t* wires, const uint64_t* coeffs, unsigned public_inputs,
-                           kh_prover_index_t** out) {
+// 405-540): the same columns, commitments and digest as proof_systems_amd/prover.py::ProverIndex + set_wiring (+ lookup.py::LookupIndex +
+// attach_lookup), built from the gate records by one kernel pass (poly.hip: k_index_columns), the lookup passes of lookup_index.hip and the
+// library's own transforms and MSMs.  One builder serves both entry points: kh_prover_index_create is the builder with lookups disallowed.
+namespace {
+struct LookupInput { const kh_lookup_table_t* tables; size_t n_tables; const kh_runtime_table_cfg_t* runtime; size_t n_runtime; };
+constexpr int XOR_TABLE_ID = 0, RANGE_CHECK_TABLE_ID = 1;      // tables/mod.rs:13,16
+constexpr size_t XOR_TABLE_LEN = 256, RANGE_CHECK_TABLE_LEN = 4096;
+// the optional gates in the column order kh_prover_index_new documents (proof.rs:95-106) ...
+const char* const OPTIONAL_GATE_NAMES[6] = {"RangeCheck0", "RangeCheck1", "ForeignFieldAdd", "ForeignFieldMul", "Xor16", "Rot64"};
+// ... their position in VerifierIndex::digest (verifier_index.rs:405-540): range_check0, range_check1, foreign_field_mul, foreign_field_add, xor, rot
+const int OPTIONAL_DIGEST_ORDER[6] = {0, 1, 3, 2, 4, 5};
+// LookupPattern::from_gate (lookups.rs:500-513) per optional gate: 1 + pattern id on CURR | (1 + pattern id on NEXT) << 4
+const uint8_t OPTIONAL_LOOKUP_CODE[6] = {3, 3 | (3 << 4), 0, 4 | (4 << 4), 1, 3};
+constexpr uint8_t LOOKUP_GATE_CODE = 2;                         // GateType::Lookup: the Lookup pattern on CURR
+
+int index_build(const char* who, kh_srs_t* srs, size_t n_gates, const int* gate_types, const uint32_t* wires, const uint64_t* coeffs, unsigned public_inputs,
+                const LookupInput* lin, kh_prover_index_t** out) {
     if (out) *out = nullptr;
-    if (!srs || !out || !gate_types || !wires || !coeffs) { kh::set_error("kh_prover_index_create: null argument"); return KH_E_INVALID; }
-    if (n_gates < 2) { kh::set_error("kh_prover_index_create: %zu gates, a circuit has at least 2 (constraints.rs)", n_gates); return KH_E_INVALID; }
+    if (!srs || !out || !gate_types || !wires || !coeffs) { kh::set_error("%s: null argument", who); return KH_E_INVALID; }
+    if (lin && ((lin->n_tables && !lin->tables) || (lin->n_runtime && !lin->runtime))) { kh::set_error("%s: null table list", who); return KH_E_INVALID; }
+    if (n_gates < 2) { kh::set_error("%s: %zu gates, a circuit has at least 2 (constraints.rs)", who, n_gates); return KH_E_INVALID; }
     const auto t0 = std::chrono::steady_clock::now();
     const int curve = kh_srs_curve(srs), fid = curve == KH_CURVE_VESTA ? KH_FIELD_FP : KH_FIELD_FQ;
     const size_t size = kh_srs_size(srs);
-    // ---- the domain: zk_rows and the number of chunks follow each other, with the SRS size as max_poly_size (constraints.rs:769-771, 946-999);
-    //      lower bound max(gates, lookup domain + 1) with the lookup domain = the dummy table row alone
-    const size_t lower = n_gates;
+    const khost::Fld F(fid);
+    // ---- the gate types: which optional gates and lookup patterns the circuit has; refusals with their reason
+    const int ngates = kh_gate_count();
+    std::vector<int> base_col(ngates, -1), opt_of(ngates, -1);       // base_col: the selector column of an always-present gate; opt_of: index into OPTIONAL_GATE_NAMES
+    for (int g = 0; g < ngates; g++) {
+        const char* nm = kh_gate_name(g);
+        if (!strcmp(nm, "Generic")) base_col[g] = (int)COLUMNS;
+        for (int k = 0; k < 5; k++) if (!strcmp(nm, LIB_GATES[k])) base_col[g] = (int)SEL0 + k;
+        for (int k = 0; k < 6; k++) if (!strcmp(nm, OPTIONAL_GATE_NAMES[k])) opt_of[g] = k;
+    }
+    bool opt_present[6] = {false, false, false, false, false, false}, pat_used[4] = {false, false, false, false};
+    unsigned live = 0;
+    char gate_error[320] = "";                       // the first refused row: reported after the domain's own refusals, as kh_prover_index_create always has
+    for (size_t i = 0; i < n_gates; i++) {
+        const int t = gate_types[i];
+        if (t == KH_GATE_ZERO) continue;
+        if (lin && t == KH_GATE_LOOKUP) { pat_used[LOOKUP_GATE_CODE - 1] = true; continue; }
+        if (t < 0 || t >= ngates) {
+            if (!gate_error[0]) snprintf(gate_error, sizeof(gate_error), "%s: unknown gate type id %d at row %zu", who, t, i);
+            continue;
+        }
+        if (base_col[t] >= 0) {
+            if (base_col[t] >= (int)SEL0) live |= 1u << (base_col[t] - (int)SEL0);
+            continue;
+        }
+        const int o = opt_of[t];
+        const uint8_t code = o >= 0 ? OPTIONAL_LOOKUP_CODE[o] : 0;
+        if (o < 0 || (code && !lin)) {
+            const char* nm = kh_gate_name(t);
+            if (gate_error[0]) continue;
+            if (!strcmp(nm, "Permutation")) snprintf(gate_error, sizeof(gate_error), "%s: row %zu: Permutation is not a gate type of a circuit", who, i);
+            else snprintf(gate_error, sizeof(gate_error), "%s: row %zu: %s has a lookup pattern; its index needs the lookup index (kh_prover_index_new + "
+                          "kh_prover_index_attach_lookup)", who, i, nm);
+            continue;
+        }
+        opt_present[o] = true;
+        if (code & 15) pat_used[(code & 15) - 1] = true;
+        if (code >> 4) pat_used[(code >> 4) - 1] = true;
+    }
+    std::vector<int> pats;                           // LookupPatterns::into_iter: xor, lookup, range_check, foreign_field_mul
+    for (int q = 0; q < 4; q++) if (pat_used[q]) pats.push_back(q);
+    const size_t npat = pats.size();
+    // ---- the lookup tables: lengths for the domain; values, ids and the dummy entry checked on the host
+    struct Table { int id; size_t width, len; int kind; const uint64_t* data; };      // kind as in lookup_index.hip: 0 data, 1 range check, 2 xor
+    std::vector<Table> tabs;
+    size_t rt_offset = 0, rt_len = 0, lookup_domain = 0;
+    bool fixed_zero_id = false;
+    if (lin) {
+        for (size_t k = 0; k < lin->n_tables; k++) {
+            const kh_lookup_table_t& t = lin->tables[k];
+            if (!t.width || t.width > 128 || (t.len && !t.data)) { kh::set_error("%s: lookup table %zu: %zu columns of %zu entries, data %s", who, k, t.width, t.len, t.data ? "given" : "NULL"); return KH_E_INVALID; }
+            tabs.push_back(Table{t.id, t.width, t.len, 0, t.data});
+            lookup_domain += t.len;
+            fixed_zero_id |= t.id == 0;
+        }
+        if (pat_used[2] || pat_used[3]) { tabs.push_back(Table{RANGE_CHECK_TABLE_ID, 1, RANGE_CHECK_TABLE_LEN, 1, nullptr}); lookup_domain += RANGE_CHECK_TABLE_LEN; }
+        if (pat_used[0]) { tabs.push_back(Table{XOR_TABLE_ID, 3, XOR_TABLE_LEN, 2, nullptr}); lookup_domain += XOR_TABLE_LEN; }
+        for (const Table& t : tabs) rt_offset += t.len;
+        for (size_t k = 0; k < lin->n_runtime; k++) {
+            const kh_runtime_table_cfg_t& t = lin->runtime[k];
+            if (t.len && !t.first_column) { kh::set_error("%s: runtime table %zu: NULL first column", who, k); return KH_E_INVALID; }
+            for (size_t j = 0; j < k; j++) if (lin->runtime[j].id == t.id) { kh::set_error("%s: runtime table id %d is configured twice", who, t.id); return KH_E_INVALID; }
+            tabs.push_back(Table{t.id, 1, t.len, 0, t.first_column});
+            rt_len += t.len; lookup_domain += t.len;
+        }
+    }
+    const bool has_rt = lin && lin->n_runtime;
+    if (!fixed_zero_id) lookup_domain += 1;          // the dummy entry (constraints.rs:883-945)
+    // ---- the domain: zk_rows and the number of chunks follow each other, with the SRS size as max_poly_size (constraints.rs:769-771, 946-999)
+    const size_t lower = n_gates > lookup_domain + 1 ? n_gates : lookup_domain + 1;
     size_t zk = 3, bound = lower + zk, nch = 1;
     for (;;) {
         size_t sz = 1; while (sz < bound) sz <<= 1;
@@ -308,45 +404,73 @@ int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types,
     }
     unsigned logn = 0; while (((size_t)1 << logn) < bound) logn++;
     const size_t n = (size_t)1 << logn;
-    if (logn > 26 || (n >= size && n % size)) { kh::set_error("kh_prover_index_create: a domain of 2^%u rows over an SRS of %zu points is not supported", logn, size); return KH_E_INVALID; }
-    if (public_inputs >= n - zk) { kh::set_error("kh_prover_index_create: %u public inputs, the domain has %zu rows before the %zu zero-knowledge rows", public_inputs, n - zk, zk); return KH_E_INVALID; }
-    // ---- the gate types: selector column per kh gate id (0 = none), refusals with their reason
-    const int ngates = kh_gate_count();
-    std::vector<int> col_of(ngates, -1);             // -1: refused
-    int gid_ffadd = -1;
-    for (int g = 0; g < ngates; g++) {
-        const char* nm = kh_gate_name(g);
-        if (!strcmp(nm, "Generic")) col_of[g] = (int)COLUMNS;
-        for (int k = 0; k < 5; k++) if (!strcmp(nm, LIB_GATES[k])) col_of[g] = (int)SEL0 + k;
-        if (!strcmp(nm, "ForeignFieldAdd")) { col_of[g] = (int)OPT0; gid_ffadd = g; }
+    if (logn > 26 || (n >= size && n % size)) { kh::set_error("%s: a domain of 2^%u rows over an SRS of %zu points is not supported", who, logn, size); return KH_E_INVALID; }
+    if (public_inputs >= n - zk) { kh::set_error("%s: %u public inputs, the domain has %zu rows before the %zu zero-knowledge rows", who, public_inputs, n - zk, zk); return KH_E_INVALID; }
+    if (gate_error[0]) { kh::set_error("%s", gate_error); return KH_E_INVALID; }
+    if (lin && lin->n_runtime && !npat) { kh::set_error("%s: runtime tables are configured, but no gate of the circuit has a lookup pattern", who); return KH_E_INVALID; }
+    // ---- the lookup constraint system (lookup/index.rs:188-430), when a gate has a pattern: the refusals of LookupConstraintSystem::create
+    size_t mpr = 0, mjs = 0, width = 0, entries = 0, data_elems = 0;
+    bool has_ids = false;
+    if (npat) {
+        for (int q : pats) {
+            const Pattern& P = PATTERNS[q];
+            if ((size_t)P.n > mpr) mpr = (size_t)P.n;
+            for (int i = 0; i < P.n; i++) if ((size_t)P.l[i].ncell > mjs) mjs = (size_t)P.l[i].ncell;
+        }
+        width = mjs;
+        for (size_t k = 0; k < tabs.size(); k++) {
+            const Table& t = tabs[k];
+            const bool runtime = k >= tabs.size() - (lin ? lin->n_runtime : 0);
+            for (size_t j = 0; j < k; j++) if (tabs[j].id == t.id) { kh::set_error("%s: lookup table id collision: two tables have id %d", who, t.id); return KH_E_INVALID; }
+            const size_t w = runtime ? 2 : t.width;  // a runtime table's second column comes with each proof (index.rs:241-311)
+            if (w > width) width = w;
+            has_ids |= t.id != 0;
+            entries += t.len;
+            if (t.kind == 0) {
+                for (size_t e = 0; e < t.width * t.len; e++)
+                    if (khost::geq(load(t.data + 4 * e), F.f.p)) { kh::set_error("%s: lookup table with id %d: value %zu is not a canonical field element (>= p)", who, t.id, e); return KH_E_INVALID; }
+                if (t.id == 0) {                     // the dummy lookup (0, ..., 0) with table id 0 must be in the table (index.rs:330-346)
+                    bool zero_row = false;
+                    for (size_t r = 0; r < t.len && !zero_row; r++) {
+                        zero_row = true;
+                        for (size_t c = 0; c < t.width && zero_row; c++) { const fe v = load(t.data + 4 * (c * t.len + r)); zero_row = !(v.l[0] | v.l[1] | v.l[2] | v.l[3]); }
+                    }
+                    if (!zero_row) { kh::set_error("%s: the lookup table with id 0 has no all-zero entry (TableIDZeroMustHaveZeroEntry)", who); return KH_E_INVALID; }
+                }
+                data_elems += t.width * t.len;
+            }
+        }
+        if (entries >= n - zk - 1) { kh::set_error("%s: %zu lookup table entries, the domain of %zu rows has room for fewer than %zu (LookupTableTooLong)", who, entries, n, n - zk - 1); return KH_E_INVALID; }
+    } else if (lin) {                                // tables of a circuit without lookups only size the domain; their values are still the caller's claim
+        for (const Table& t : tabs)
+            for (size_t e = 0; t.kind == 0 && e < t.width * t.len; e++)
+                if (khost::geq(load(t.data + 4 * e), F.f.p)) { kh::set_error("%s: lookup table with id %d: value %zu is not a canonical field element (>= p)", who, t.id, e); return KH_E_INVALID; }
     }
-    std::vector<uint8_t> selcol(n_gates);
-    unsigned live = 0;
-    bool ffadd = false;
+    // ---- the selector column of every row and its lookup code
+    size_t nopt = 0;
+    int opt_col[6];
+    for (int k = 0; k < 6; k++) opt_col[k] = opt_present[k] ? (int)(OPT0 + nopt++) : -1;
+    const size_t ncol = OPT0 + nopt;
+    std::vector<uint8_t> selcol(n_gates), lkcode(npat ? n_gates : 0);
     for (size_t i = 0; i < n_gates; i++) {
         const int t = gate_types[i];
-        if (t == KH_GATE_ZERO) { selcol[i] = 0; continue; }
-        if (t < 0 || t >= ngates) { kh::set_error("kh_prover_index_create: unknown gate type id %d at row %zu", t, i); return KH_E_INVALID; }
-        if (col_of[t] < 0) {
-            const char* nm = kh_gate_name(t);
-            if (!strcmp(nm, "Permutation")) kh::set_error("kh_prover_index_create: row %zu: Permutation is not a gate type of a circuit", i);
-            else kh::set_error("kh_prover_index_create: row %zu: %s has a lookup pattern; its index needs the lookup index (kh_prover_index_new + "
-                               "kh_prover_index_attach_lookup)", i, nm);
-            return KH_E_INVALID;
+        uint8_t col = 0, code = 0;
+        if (t == KH_GATE_LOOKUP) code = LOOKUP_GATE_CODE;
+        else if (t != KH_GATE_ZERO) {
+            if (base_col[t] >= 0) col = (uint8_t)base_col[t];
+            else { col = (uint8_t)opt_col[opt_of[t]]; code = OPTIONAL_LOOKUP_CODE[opt_of[t]]; }
         }
-        selcol[i] = (uint8_t)col_of[t];
-        if (col_of[t] >= (int)SEL0 && col_of[t] < (int)OPT0) live |= 1u << (col_of[t] - (int)SEL0);
-        ffadd |= t == gid_ffadd;
+        selcol[i] = col;
+        if (npat) lkcode[i] = code;
     }
     for (size_t i = 0; i < 7 * n_gates; i++)         // the kernel gathers sid[row]: nothing outside the domain may reach it
         if (wires[2 * i] >= n || wires[2 * i + 1] >= PERMUTS) {
-            kh::set_error("kh_prover_index_create: row %zu, cell %zu is wired to (%u, %u), outside %zu rows x %zu columns", i / 7, i % 7, wires[2 * i], wires[2 * i + 1], n, PERMUTS);
+            kh::set_error("%s: row %zu, cell %zu is wired to (%u, %u), outside %zu rows x %zu columns", who, i / 7, i % 7, wires[2 * i], wires[2 * i + 1], n, PERMUTS);
             return KH_E_INVALID;
         }
-    const khost::Fld F(fid);
     for (size_t i = 0; i < COLUMNS * n_gates; i++)
         if (khost::geq(load(coeffs + 4 * i), F.f.p)) {
-            kh::set_error("kh_prover_index_create: row %zu, coefficient %zu is not a canonical field element (>= p)", i / COLUMNS, i % COLUMNS);
+            kh::set_error("%s: row %zu, coefficient %zu is not a canonical field element (>= p)", who, i / COLUMNS, i % COLUMNS);
             return KH_E_INVALID;
         }
     // ---- device work, on the SRS's device
@@ -355,7 +479,6 @@ int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types,
     if (kh_srs_lagrange_chunks(srs, logn) == 0) KP(kh_srs_compute_lagrange(srs, logn));      // SRS::lagrange_basis (index time)
     fe shifts[7];
     KP(kh_permutation_shifts(fid, logn, shifts[0].l));
-    const size_t nopt = ffadd ? 1 : 0, ncol = OPT0 + nopt;
     Dev d1, dc, d8, g_sel, g_wires, g_coeffs;
     KP(d1.alloc(ncol * n)); KP(dc.alloc((ncol + 2) * n)); KP(d8.alloc((ncol + 2) * 8 * n));
     KP(kh_dev_alloc((void**)&g_sel.p, n_gates)); KP(kh_dev_alloc((void**)&g_wires.p, 56 * n_gates)); KP(g_coeffs.alloc(COLUMNS * n_gates));
@@ -368,6 +491,33 @@ int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types,
     KP(kh_dev_upload(sid + 4, one.l, 32));
     KP(kh_ntt_dev(fid, sid, logn, 0, 1));
     KP(kh::index_columns_dev(fid, (const uint8_t*)g_sel.p, (const uint32_t*)g_wires.p, g_coeffs.p, n_gates, n, zk, shifts[0].l, ncol, d1.p));
+    // the lookup columns, d1: [pattern selectors | runtime selector | table columns | table ids]; coefficient forms and d8 of the selectors; the atoms on d8
+    const size_t nsel = npat + (has_rt ? 1 : 0), nlk = npat ? nsel + width + (has_ids ? 1 : 0) : 0;
+    Dev l1, lc, l8, g_code, g_segs, g_data;
+    std::vector<uint64_t> segs;
+    if (npat) {
+        KP(l1.alloc(nlk * n)); KP(lc.alloc(nsel * n)); KP(l8.alloc((nsel + 3) * 8 * n));
+        KP(kh_dev_alloc((void**)&g_code.p, n_gates)); KP(g_data.alloc(data_elems ? data_elems : 1));
+        KP(kh_dev_upload(g_code.p, lkcode.data(), n_gates));
+        size_t row = 0, off = 0;
+        for (const Table& t : tabs) {                // segment records of k_lookup_tables (lookup_index.hip)
+            fe idv = {{(uint64_t)(t.id < 0 ? -(int64_t)t.id : (int64_t)t.id), 0, 0, 0}};
+            idv = F.to_mont(idv);
+            if (t.id < 0) idv = F.neg(idv);
+            const uint64_t rec[8] = {row, t.len, off, (uint64_t)t.kind | ((uint64_t)t.width << 32), idv.l[0], idv.l[1], idv.l[2], idv.l[3]};
+            segs.insert(segs.end(), rec, rec + 8);
+            if (t.kind == 0 && t.len) { KP(kh_dev_upload(g_data.at(off), t.data, 32 * t.width * t.len)); off += t.width * t.len; }
+            row += t.len;
+        }
+        if (segs.empty()) segs.assign(8, 0);         // no table at all: every row is padding
+        KP(kh_dev_alloc((void**)&g_segs.p, 8 * segs.size()));
+        KP(kh_dev_upload(g_segs.p, segs.data(), 8 * segs.size()));
+        KP(kh::lookup_selectors_dev(fid, (const uint8_t*)g_code.p, n_gates, n, pats.data(), npat, l1.p));
+        std::vector<uint64_t> seg_starts(segs.size() / 8);           // the prefix offsets, for the kernel's arguments
+        for (size_t k = 0; k < seg_starts.size(); k++) seg_starts[k] = segs[8 * k];
+        KP(kh::lookup_tables_dev(fid, g_segs.p, seg_starts.data(), segs.size() / 8, g_data.p, n, width, l1.at(nsel * n), has_ids ? l1.at((nsel + width) * n) : nullptr,
+                                 has_rt ? l1.at(npat * n) : nullptr, rt_offset, has_rt ? rt_len : 0, zk));
+    }
     KP(kh_sync());
     const auto t1 = std::chrono::steady_clock::now();
     // ---- coefficient forms, x and the permutation vanishing polynomial (x - w^(n-zk))(x - w^(n-zk+1))(x - w^(n-1)) (permutation.rs:107-118), d8
@@ -382,37 +532,68 @@ int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types,
     KP(kh_dev_upload(dc.at(ncol * n + 1), one.l, 32));
     KP(kh_dev_upload(dc.at((ncol + 1) * n), zkpm, sizeof(zkpm)));
     KP(kh_lde_dev(fid, dc.p, logn, 3, d8.p, ncol + 2));
+    if (npat) {
+        KP(kh_dev_copy(lc.p, l1.p, 32 * nsel * n));
+        KP(kh_ntt_dev(fid, lc.p, logn, 1, nsel));
+        KP(kh_lde_dev(fid, lc.p, logn, 3, l8.p, nsel));
+        // the row-set atoms (expr.rs:883-893) from x on d8: x^n - 1 takes the eight values w8^j - 1 there, w8 = g^n for the generator g of d8
+        uint64_t g8[4];
+        KP(kh_domain_generator(fid, logn + 3, g8));
+        const fe w8 = fpow(F, load(g8), n), af = fpow(F, omega, n - zk - 1);
+        fe zh8[8], pw = one;
+        for (int j = 0; j < 8; j++) { zh8[j] = F.sub(pw, one); pw = F.mul(pw, w8); }
+        const fe nf = F.to_mont(fe{{(uint64_t)n, 0, 0, 0}}), limf = F.mul(nf, F.inv(af));
+        uint64_t* atoms = l8.at(nsel * 8 * n);
+        KP(kh::lookup_atom_denominators_dev(fid, d8.at(ncol * 8 * n), n, zk, af.l, omega.l, atoms));
+        KP(kh_batch_inversion_dev(fid, atoms + 4 * 8 * n, 2 * 8 * n));
+        KP(kh::lookup_atom_finish_dev(fid, n, zk, zh8[0].l, nf.l, limf.l, atoms));
+    }
     KP(kh_sync());
     const auto t2 = std::chrono::steady_clock::now();
-    // ---- commitments over the Lagrange basis: [coefficients | generic] and [sigma | five selectors | optional], one batched MSM per chunk each
+    // ---- commitments over the Lagrange basis: [coefficients | generic], [sigma | five selectors | optional] and the lookup columns, batched MSMs per chunk
     const size_t k1 = COLUMNS + 1, k2 = PERMUTS + 5 + nopt;
-    std::vector<uint64_t> xy1(8 * k1 * nch), xy2(8 * k2 * nch), o(8 * (k1 > k2 ? k1 : k2));
-    std::vector<uint8_t> inf1(k1 * nch), inf2(k2 * nch), oi(k1 > k2 ? k1 : k2);
+    const size_t kmax = 16;
+    std::vector<uint64_t> xy1(8 * k1 * nch), xy2(8 * k2 * nch), xyl(8 * nlk * nch), o(8 * (k2 > kmax ? k2 : kmax));
+    std::vector<uint8_t> inf1(k1 * nch), inf2(k2 * nch), infl(nlk * nch), oi(k2 > kmax ? k2 : kmax);
     for (size_t ch = 0; ch < nch; ch++) {            // chunk lists flat, commitment after commitment
         KP(kh_msm_batch_dev(srs, (int)logn, (unsigned)ch, 0, d1.p, n, k1, 1, o.data(), oi.data()));
         for (size_t i = 0; i < k1; i++) { memcpy(&xy1[8 * (i * nch + ch)], &o[8 * i], 64); inf1[i * nch + ch] = oi[i]; }
         KP(kh_msm_batch_dev(srs, (int)logn, (unsigned)ch, 0, d1.at((COLUMNS + 2) * n), n, k2, 1, o.data(), oi.data()));
         for (size_t i = 0; i < k2; i++) { memcpy(&xy2[8 * (i * nch + ch)], &o[8 * i], 64); inf2[i * nch + ch] = oi[i]; }
+        for (size_t i0 = 0; i0 < nlk; i0 += kmax) {
+            const size_t k = nlk - i0 < kmax ? nlk - i0 : kmax;
+            KP(kh_msm_batch_dev(srs, (int)logn, (unsigned)ch, 0, l1.at(i0 * n), n, k, 1, o.data(), oi.data()));
+            for (size_t i = 0; i < k; i++) { memcpy(&xyl[8 * ((i0 + i) * nch + ch)], &o[8 * i], 64); infl[(i0 + i) * nch + ch] = oi[i]; }
+        }
     }
     const auto t3 = std::chrono::steady_clock::now();
-    // ---- the generic and the five library selectors masked with blinder 1 (verifier_index.rs:255-300), the digest (verifier_index.rs:405-540)
-    std::vector<uint64_t> mxy(8 * 6 * nch), mout(8 * 6 * nch), ones(4 * 6 * nch);
-    std::vector<uint8_t> minf(6 * nch), moinf(6 * nch);
+    // ---- the generic and the five library selectors, the table columns and the table ids masked with blinder 1 (verifier_index.rs:189-216, 255-300),
+    //      the digest (verifier_index.rs:405-540)
+    const size_t ntab = npat ? width + (has_ids ? 1 : 0) : 0, nm = 6 + ntab;
+    std::vector<uint64_t> mxy(8 * nm * nch), mout(8 * nm * nch), ones(4 * nm * nch);
+    std::vector<uint8_t> minf(nm * nch), moinf(nm * nch);
     memcpy(mxy.data(), &xy1[8 * COLUMNS * nch], 64 * nch); memcpy(minf.data(), &inf1[COLUMNS * nch], nch);
     memcpy(&mxy[8 * nch], &xy2[8 * PERMUTS * nch], 64 * 5 * nch); memcpy(&minf[nch], &inf2[PERMUTS * nch], 5 * nch);
-    for (size_t i = 0; i < 6 * nch; i++) memcpy(&ones[4 * i], one.l, 32);
-    KP(kh_mask_custom(srs, mxy.data(), minf.data(), 6 * nch, ones.data(), 6 * nch, mout.data(), moinf.data()));
+    if (ntab) { memcpy(mxy.data() + 8 * 6 * nch, xyl.data() + 8 * nsel * nch, 64 * ntab * nch); memcpy(minf.data() + 6 * nch, infl.data() + nsel * nch, ntab * nch); }
+    for (size_t i = 0; i < nm * nch; i++) memcpy(&ones[4 * i], one.l, 32);
+    KP(kh_mask_custom(srs, mxy.data(), minf.data(), nm * nch, ones.data(), nm * nch, mout.data(), moinf.data()));
     SpongeH sp;
     KP(kh_sponge_new(KH_SPONGE_FQ, curve, &sp.s));
     KP(kh_sponge_absorb_g(sp.s, xy2.data(), inf2.data(), PERMUTS * nch));                          // sigma
     KP(kh_sponge_absorb_g(sp.s, xy1.data(), inf1.data(), COLUMNS * nch));                          // coefficients
     KP(kh_sponge_absorb_g(sp.s, mout.data(), moinf.data(), 6 * nch));                              // generic, psm, complete_add, mul, emul, endomul_scalar
-    if (nopt) KP(kh_sponge_absorb_g(sp.s, xy2.data() + 8 * (PERMUTS + 5) * nch, inf2.data() + (PERMUTS + 5) * nch, nopt * nch));   // foreign_field_add
+    for (int k : OPTIONAL_DIGEST_ORDER)
+        if (opt_present[k]) { const size_t j = PERMUTS + 5 + (size_t)(opt_col[k] - (int)OPT0); KP(kh_sponge_absorb_g(sp.s, xy2.data() + 8 * j * nch, inf2.data() + j * nch, nch)); }
+    if (npat) {                                      // the lookup index (verifier_index.rs:482-530): tables, ids, runtime selector, pattern selectors
+        KP(kh_sponge_absorb_g(sp.s, mout.data() + 8 * 6 * nch, moinf.data() + 6 * nch, ntab * nch));
+        if (has_rt) KP(kh_sponge_absorb_g(sp.s, xyl.data() + 8 * npat * nch, infl.data() + npat * nch, nch));
+        KP(kh_sponge_absorb_g(sp.s, xyl.data(), infl.data(), npat * nch));
+    }
     fe digest;
     KP(kh_sponge_squeeze_field(sp.s, digest.l));
     // ---- the prover index over the columns (kh_prover_index_new's body), which now owns them
     std::vector<int> optional;
-    if (ffadd) optional.push_back(gid_ffadd);
+    for (int k = 0; k < 6; k++) if (opt_present[k]) for (int g = 0; g < ngates; g++) if (opt_of[g] == k) optional.push_back(g);
     kh_prover_index* ix = nullptr;
     KP(kh_prover_index_new(srs, logn, (unsigned)zk, public_inputs, d1.p, dc.p, d8.p, optional.data(), optional.size(), live, shifts[0].l, digest.l, &ix));
     ix->created = true;
@@ -426,11 +607,44 @@ int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types,
     points(KH_VINDEX_GENERIC_COMM, mout.data(), moinf.data(), nch);
     points(KH_VINDEX_SELECTOR_COMM, &mout[8 * nch], &moinf[nch], 5 * nch);
     points(KH_VINDEX_OPTIONAL_COMM, xy2.data() + 8 * (PERMUTS + 5) * nch, inf2.data() + (PERMUTS + 5) * nch, nopt * nch);
+    if (npat) {
+        kh_lookup_index* lk = new (std::nothrow) kh_lookup_index();
+        if (!lk) { kh_prover_index_free(ix); kh::set_error("out of memory"); return KH_E_NOMEM; }
+        lk->pats = pats; lk->mpr = mpr; lk->mjs = mjs;
+        for (size_t k = 0; k < npat; k++) { lk->sel1.push_back(l1.at(k * n)); lk->selc.push_back(lc.at(k * n)); lk->sel8.push_back(l8.at(k * 8 * n)); }
+        for (size_t k = 0; k < width; k++) lk->tcols.push_back(l1.at((nsel + k) * n));
+        if (has_ids) lk->tids = l1.at((nsel + width) * n);
+        for (int k = 0; k < 3; k++) lk->atoms8[k] = l8.at((nsel + (size_t)k) * 8 * n);
+        if (has_rt) { lk->rtsel1 = l1.at(npat * n); lk->rtselc = lc.at(npat * n); lk->rtsel8 = l8.at(npat * 8 * n); lk->rt_offset = rt_offset; lk->rt_len = rt_len; }
+        ix->lk = lk;
+        ix->own_l1 = l1.p; ix->own_lc = lc.p; ix->own_l8 = l8.p;
+        l1.p = lc.p = l8.p = nullptr;
+        points(KH_VINDEX_LOOKUP_TABLE_COMM, mout.data() + 8 * 6 * nch, moinf.data() + 6 * nch, width * nch);
+        points(KH_VINDEX_LOOKUP_TABLE_IDS_COMM, mout.data() + 8 * (6 + width) * nch, moinf.data() + (6 + width) * nch, has_ids ? nch : 0);
+        points(KH_VINDEX_LOOKUP_SELECTOR_COMM, xyl.data(), infl.data(), npat * nch);
+        points(KH_VINDEX_LOOKUP_RUNTIME_SELECTOR_COMM, xyl.data() + 8 * npat * nch, infl.data() + npat * nch, has_rt ? nch : 0);
+        unsigned mask = 0;
+        for (int q : pats) mask |= 1u << q;
+        ix->vsec[KH_VINDEX_LOOKUP_INFO].limbs = {mpr, mjs, mjs > 1 ? 1u : 0u, has_rt ? 1u : 0u, mask, width, has_rt ? rt_offset : 0, has_rt ? rt_len : 0};
+        ix->vsec[KH_VINDEX_LOOKUP_INFO].count = 2;
+    }
     const auto t4 = std::chrono::steady_clock::now();
     const std::chrono::steady_clock::time_point ts[5] = {t0, t1, t2, t3, t4};
     for (int i = 0; i < 4; i++) ix->phase[i] = std::chrono::duration<double>(ts[i + 1] - ts[i]).count();
     *out = ix;
     return KH_OK;
+}
+}  // namespace
+
+int kh_prover_index_create(kh_srs_t* srs, size_t n_gates, const int* gate_types, const uint32_t* wires, const uint64_t* coeffs, unsigned public_inputs,
+                           kh_prover_index_t** out) {
+    return index_build("kh_prover_index_create", srs, n_gates, gate_types, wires, coeffs, public_inputs, nullptr, out);
+}
+int kh_prover_index_create_lookup(kh_srs_t* srs, size_t n_gates, const int* gate_types, const uint32_t* wires, const uint64_t* coeffs, unsigned public_inputs,
+                                  const kh_lookup_table_t* tables, size_t n_tables, const kh_runtime_table_cfg_t* runtime, size_t n_runtime,
+                                  kh_prover_index_t** out) {
+    const LookupInput lin{tables, n_tables, runtime, n_runtime};
+    return index_build("kh_prover_index_create_lookup", srs, n_gates, gate_types, wires, coeffs, public_inputs, &lin, out);
 }
 int kh_prover_index_shape(const kh_prover_index_t* ix, unsigned* log2_n, unsigned* zk_rows, size_t* num_chunks) {
     if (!ix) { kh::set_error("kh_prover_index_shape: null index"); return KH_E_INVALID; }
@@ -440,7 +654,7 @@ int kh_prover_index_shape(const kh_prover_index_t* ix, unsigned* log2_n, unsigne
     return KH_OK;
 }
 int kh_verifier_index_section(const kh_prover_index_t* ix, int section, const uint64_t** limbs, const uint8_t** flags, size_t* count) {
-    if (!ix || section < 0 || section > KH_VINDEX_DIGEST || !limbs || !count) { kh::set_error("kh_verifier_index_section: bad argument"); return KH_E_INVALID; }
+    if (!ix || section < 0 || section > KH_VINDEX_LOOKUP_INFO || !limbs || !count) { kh::set_error("kh_verifier_index_section: bad argument"); return KH_E_INVALID; }
     if (section == KH_VINDEX_SHIFTS || section == KH_VINDEX_DIGEST) {
         *limbs = section == KH_VINDEX_SHIFTS ? ix->shifts[0].l : ix->digest.l;
         *count = section == KH_VINDEX_SHIFTS ? 7 : 1;
@@ -450,7 +664,27 @@ int kh_verifier_index_section(const kh_prover_index_t* ix, int section, const ui
     if (!ix->created) { kh::set_error("kh_verifier_index_section: the index comes from kh_prover_index_new, whose commitments are the caller's"); return KH_E_NOTFOUND; }
     const kh_prover_index::VSec& s = ix->vsec[section];
     *limbs = s.limbs.data(); *count = s.count;
-    if (flags) *flags = s.flags.data();
+    if (flags) *flags = section == KH_VINDEX_LOOKUP_INFO ? nullptr : s.flags.data();
+    return KH_OK;
+}
+int kh_debug_lookup_column(const kh_prover_index_t* ix, int block, size_t k, const uint64_t** dev, size_t* elems) {
+    if (!ix || !dev || !elems) { kh::set_error("kh_debug_lookup_column: null argument"); return KH_E_INVALID; }
+    const kh_lookup_index* lk = ix->lk;
+    if (!lk) { kh::set_error("kh_debug_lookup_column: the index has no lookup index"); return KH_E_NOTFOUND; }
+    const uint64_t* p = nullptr;
+    size_t len = ix->n;
+    switch (block) {
+        case KH_LOOKUP_COL_SELECTOR_D1: if (k < lk->sel1.size()) p = lk->sel1[k]; break;
+        case KH_LOOKUP_COL_SELECTOR_C: if (k < lk->selc.size()) p = lk->selc[k]; break;
+        case KH_LOOKUP_COL_SELECTOR_D8: if (k < lk->sel8.size()) p = lk->sel8[k]; len = 8 * ix->n; break;
+        case KH_LOOKUP_COL_TABLE_D1: if (k < lk->tcols.size()) p = lk->tcols[k]; break;
+        case KH_LOOKUP_COL_TABLE_IDS_D1: if (k == 0) p = lk->tids; break;
+        case KH_LOOKUP_COL_ATOM_D8: if (k < 3) p = lk->atoms8[k]; len = 8 * ix->n; break;
+        case KH_LOOKUP_COL_RUNTIME_SELECTOR: if (k < 3) p = k == 0 ? lk->rtsel1 : k == 1 ? lk->rtselc : lk->rtsel8; if (k == 2) len = 8 * ix->n; break;
+        default: break;
+    }
+    if (!p) { kh::set_error("kh_debug_lookup_column: the index has no column %zu in block %d", k, block); return KH_E_NOTFOUND; }
+    *dev = p; *elems = len;
     return KH_OK;
 }
 int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, size_t cap) {

@@ -366,4 +366,31 @@ int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wire
     if (rc == KH_OK) C.mark_async();
     return rc;
 }
+// the lookup passes of kh_prover_index_create_lookup (kernels in lookup_index.hip), queued on the main stream
+#define KH_LOOKUP_STEP(call)                                                                     \
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);     \
+    int rc = ensure_init(); if (rc) return rc;                                                  \
+    Context& C = ctx();                                                                         \
+    std::lock_guard<std::mutex> lk(C.mu);                                                       \
+    rc = call;                                                                                  \
+    if (rc == KH_OK) C.mark_async();                                                            \
+    return rc
+int lookup_selectors_dev(int field, const uint8_t* code_dev, size_t n_gates, size_t n, const int* patterns, size_t npat, uint64_t* out_dev) {
+    KH_REQUIRE(code_dev && patterns && out_dev, "lookup_selectors_dev: null argument");
+    KH_LOOKUP_STEP(lookup_selector_columns(C, field, code_dev, n_gates, n, patterns, npat, out_dev));
+}
+int lookup_tables_dev(int field, const uint64_t* segs_dev, const uint64_t* seg_starts, size_t nseg, const uint64_t* data_dev, size_t n, size_t width, uint64_t* tcols_dev,
+                      uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows) {
+    KH_REQUIRE(segs_dev && seg_starts && tcols_dev, "lookup_tables_dev: null argument");
+    KH_LOOKUP_STEP(lookup_table_columns(C, field, segs_dev, seg_starts, nseg, data_dev, n, width, tcols_dev, ids_dev, rtsel_dev, rt_offset, rt_len, zk_rows));
+}
+int lookup_atom_denominators_dev(int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4], uint64_t* atoms_dev) {
+    KH_REQUIRE(x8_dev && a && omega && atoms_dev, "lookup_atom_denominators_dev: null argument");
+    KH_LOOKUP_STEP(lookup_atom_denominators(C, field, x8_dev, n, zk_rows, a, omega, atoms_dev));
+}
+int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4], uint64_t* atoms_dev) {
+    KH_REQUIRE(zh8 && lim0 && limf && atoms_dev, "lookup_atom_finish_dev: null argument");
+    KH_LOOKUP_STEP(lookup_atom_finish(C, field, n, zk_rows, zh8, lim0, limf, atoms_dev));
+}
+#undef KH_LOOKUP_STEP
 }  // namespace kh

@@ -40,13 +40,24 @@ SYMBOLS = [
     "kh_msm_sharded", "kh_msm_sharded_dev", "kh_gate_count", "kh_gate_name", "kh_gate_num_constants", "kh_gate_evaluations_dev", "kh_gate_constants", "kh_srs_curve", "kh_lookup_sorted", "kh_private_context_begin", "kh_private_context_end", "kh_private_context_active", "kh_comm_unique_id", "kh_comm_init", "kh_comm_free", "kh_comm_world_size", "kh_comm_rank", "kh_comm_allgather_points",
     "kh_msm_allreduce",
     "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
-    "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
+    "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_create_lookup", "kh_debug_lookup_column", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
     "kh_commit_non_hiding", "kh_commit_evaluations_non_hiding", "kh_srs_set_blinding_base",
     "kh_srs_get_blinding_base", "kh_mask_custom", "kh_domain_generator", "kh_msm_points_batch", "kh_msm_submit", "kh_msm_wait",
     "kh_ipa_fold_scalars", "kh_inner_product", "kh_ipa_fold_points", "kh_ipa_fold_points_endo", "kh_endos", "kh_scalar_challenge_to_field",
     "kh_polycomm_multi_scalar_mul", "kh_expr_evaluations_dev", "kh_field_scan_dev", "kh_batch_inversion_dev", "kh_divide_by_linear_dev", "kh_divide_by_linear_async_dev", "kh_check_equal_dev", "kh_b_poly_coefficients", "kh_batch_dlog_accumulator_generate", "kh_batch_dlog_accumulator_check", "kh_ipa_verify_msm",
     "kh_ipa_begin", "kh_ipa_begin_dev", "kh_combine_polys_dev", "kh_poly_lincomb_dev", "kh_b_init_dev", "kh_evaluate_chunks_dev", "kh_evaluate_chunks_batch_dev", "kh_divide_by_vanishing_poly_dev", "kh_ipa_rounds_left", "kh_ipa_round_lr", "kh_ipa_round_fold", "kh_ipa_finish", "kh_ipa_free", "kh_points_sum", "kh_points_add", "kh_srs_create_device", "kh_srs_create_device_range", "kh_srs_get_g",
 ]
+
+
+class LookupTableC(C.Structure):
+    """kh_lookup_table_t"""
+    _fields_ = [("id", C.c_int), ("width", C.c_size_t), ("len", C.c_size_t), ("data", C.POINTER(C.c_uint64))]
+
+
+class RuntimeTableCfgC(C.Structure):
+    """kh_runtime_table_cfg_t"""
+    _fields_ = [("id", C.c_int), ("len", C.c_size_t), ("first_column", C.POINTER(C.c_uint64))]
+
 
 _lib.kh_last_error.restype = C.c_char_p
 _lib.kh_set_device.argtypes = [C.c_int]
@@ -99,6 +110,9 @@ _lib.kh_divide_by_linear_async_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, 
 _lib.kh_check_equal_dev.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_uint]
 _lib.kh_permutation_shifts.argtypes = [C.c_int, C.c_uint, U64P]
 _lib.kh_prover_index_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(C.c_void_p)]
+_lib.kh_prover_index_create_lookup.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(LookupTableC), C.c_size_t,
+                                               C.POINTER(RuntimeTableCfgC), C.c_size_t, C.POINTER(C.c_void_p)]
+_lib.kh_debug_lookup_column.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(U64P), C.POINTER(C.c_size_t)]
 _lib.kh_prover_index_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
 _lib.kh_verifier_index_section.argtypes = [C.c_void_p, C.c_int, C.POINTER(U64P), C.POINTER(U8P), C.POINTER(C.c_size_t)]
 _lib.kh_prover_index_phase_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
@@ -809,7 +823,11 @@ PROOF_SECTIONS = {"w_comm": 0, "z_comm": 1, "t_comm": 2, "public_comm": 3, "eval
 LOOKUP_PATTERN_IDS = {"Xor": 0, "Lookup": 1, "RangeCheck": 2, "ForeignFieldMul": 3}
 PROOF_PHASES = ("witness_upload", "witness_commit", "z", "quotient", "evaluations", "opening")
 GATE_ZERO = -1                                      # KH_GATE_ZERO: a row without gate constraints
-VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "selector_comm": 3, "optional_comm": 4, "shifts": 5, "digest": 6}
+GATE_LOOKUP = -2                                    # KH_GATE_LOOKUP: GateType::Lookup, a row without gate constraints that carries the Lookup pattern
+VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "selector_comm": 3, "optional_comm": 4, "shifts": 5, "digest": 6,
+                   "lookup_table_comm": 7, "lookup_table_ids_comm": 8, "lookup_selector_comm": 9, "lookup_runtime_selector_comm": 10, "lookup_info": 11}
+LOOKUP_COLUMN_BLOCKS = {"selector_d1": 0, "selector_c": 1, "selector_d8": 2, "table_d1": 3, "table_ids_d1": 4, "atom_d8": 5, "runtime_selector": 6}
+LOOKUP_INFO_FIELDS = ("max_per_row", "max_joint_size", "joint_lookup_used", "uses_runtime_tables", "pattern_mask", "table_columns", "runtime_offset", "runtime_len")
 INDEX_PHASES = ("columns", "transforms", "commitments", "digest")
 
 
@@ -840,6 +858,26 @@ class NativeProverIndex:
         self._keep = (srs,)
         return self
 
+    @classmethod
+    def create_lookup(cls, srs, gate_types, wires, coeffs, public: int = 0, tables=(), runtime_tables=()):
+        """kh_prover_index_create_lookup: as `create`, for circuits with a lookup argument (gate_types may hold the lookup gates and GATE_LOOKUP).
+        tables: [(id, data (width, len, 4) Montgomery limbs)]; runtime_tables: [(id, first column (len, 4) limbs)] (RuntimeTableCfg)."""
+        self = cls.__new__(cls)
+        types = np.ascontiguousarray(gate_types, dtype=np.int32).reshape(-1)
+        rows = types.shape[0]
+        w = np.ascontiguousarray(wires, dtype=np.uint32).reshape(rows, 7, 2)
+        co = _c64(coeffs, (rows, 15, 4))
+        tdata = [np.ascontiguousarray(d, dtype=np.uint64) for _i, d in tables]
+        assert all(d.ndim == 3 and d.shape[2] == 4 for d in tdata), "table data: (width, len, 4) limbs"
+        rdata = [_c64(d, (-1, 4)) for _i, d in runtime_tables]
+        tc = (LookupTableC * max(len(tdata), 1))(*[LookupTableC(int(i), d.shape[0], d.shape[1], _p64(d)) for (i, _d), d in zip(tables, tdata)])
+        rc = (RuntimeTableCfgC * max(len(rdata), 1))(*[RuntimeTableCfgC(int(i), d.shape[0], _p64(d)) for (i, _d), d in zip(runtime_tables, rdata)])
+        self._h = C.c_void_p()
+        _check(_lib.kh_prover_index_create_lookup(srs._h, C.c_size_t(rows), types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  _p64(co), C.c_uint(public), tc, C.c_size_t(len(tdata)), rc, C.c_size_t(len(rdata)), C.byref(self._h)))
+        self._keep = (srs,)
+        return self
+
     def shape(self):
         """(log2_n, zk_rows, num_chunks)"""
         ln, zk, nch = C.c_uint(0), C.c_uint(0), C.c_size_t(0)
@@ -858,8 +896,20 @@ class NativeProverIndex:
                              np.ctypeslib.as_array(fp, shape=(k,)).copy() if k else np.zeros(0, np.uint8))
             elif name in ("shifts", "digest"):
                 out[name] = np.ctypeslib.as_array(lp, shape=(k, 4)).copy()
+            elif name == "lookup_info":               # plain integers, None for an index without a lookup argument
+                out[name] = dict(zip(LOOKUP_INFO_FIELDS, (int(x) for x in np.ctypeslib.as_array(lp, shape=(4 * k,))))) if k else None
             else:                                     # a commitment section with no entries (no optional gate)
                 out[name] = (np.zeros((0, 8), np.uint64), np.zeros(0, np.uint8))
+        return out
+
+    def lookup_column(self, block: str, k: int = 0):
+        """kh_debug_lookup_column, downloaded: (elems, 4) limbs of column k of a block of LOOKUP_COLUMN_BLOCKS, or None where the index has none."""
+        dev = U64P(); cnt = C.c_size_t(0)
+        if _lib.kh_debug_lookup_column(self._h, C.c_int(LOOKUP_COLUMN_BLOCKS[block]), C.c_size_t(k), C.byref(dev), C.byref(cnt)) != 0:
+            return None
+        out = np.zeros((cnt.value, 4), dtype=np.uint64)
+        sync()
+        _check(_lib.kh_dev_download(_p64(out), C.cast(dev, C.c_void_p), C.c_size_t(out.nbytes)))
         return out
 
     def phase_seconds(self):

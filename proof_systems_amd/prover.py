@@ -305,6 +305,19 @@ class ProverIndex:
                      [LI.selector_comm[q] for q in LI.patterns])
         khip.sync()
 
+    def free_lookup(self):
+        """Releases the attached lookup index: what attach_lookup allocated (coefficient forms and d8 of the selectors, the atoms) and the LookupIndex's own columns."""
+        LI = getattr(self, "lookup", None)
+        if LI is None:
+            return
+        if getattr(self, "_native", None) is not None:       # the native handle keeps pointers into these columns
+            self._native[0].free(); self._native = None
+        for b in list(LI.sel_c.values()) + list(LI.sel8.values()) + list(LI.atoms8) + [LI.rtsel_c, LI.rtsel8]:
+            if b is not None:
+                b.free()
+        LI.free()
+        self.lookup = None
+
     def free(self):
         if getattr(self, "_native", None) is not None:
             self._native[0].free(); self._native = None
@@ -322,25 +335,58 @@ def bench_circuit_index(curve: int, log2_n: int, srs=None) -> ProverIndex:
     return ProverIndex(curve, log2_n, co, srs)
 
 
+class CreatedLookup:
+    """What create_proof_native and the verifier side read of the lookup index a created index carries (the columns stay in the native handle):
+    the fields of proof_systems_amd.lookup.LookupIndex + ProverIndex.attach_lookup they use, from the KH_VINDEX_LOOKUP_* sections."""
+
+    def __init__(self, vi, nch: int, runtime_tables):
+        info = vi["lookup_info"]
+        comms = lambda key: [(vi[key][0][i * nch:(i + 1) * nch], vi[key][1][i * nch:(i + 1) * nch]) for i in range(vi[key][1].shape[0] // nch)]
+        self.patterns = [q for q, k in sorted(khip.LOOKUP_PATTERN_IDS.items(), key=lambda t: t[1]) if info["pattern_mask"] >> k & 1]
+        self.max_per_row, self.max_joint_size = info["max_per_row"], info["max_joint_size"]
+        self.joint_lookup_used = bool(info["joint_lookup_used"])
+        self.table_comm = comms("lookup_table_comm")
+        self.table_ids_comm = (comms("lookup_table_ids_comm") or [None])[0]
+        self.selector_comm = dict(zip(self.patterns, comms("lookup_selector_comm")))
+        self.runtime_selector_comm = (comms("lookup_runtime_selector_comm") or [None])[0]
+        uses = bool(info["uses_runtime_tables"])
+        self.runtime_selector = True if uses else None           # the column itself is on the device; callers only ask whether there is one
+        self.runtime_tables = [(rt["id"], len(rt["first_column"])) for rt in runtime_tables] if uses else None
+        self.runtime_offset = info["runtime_offset"] if uses else None
+        self.runtime_len = info["runtime_len"] if uses else 0
+
+
 class CreatedIndex:
-    """An index built natively from a gate list (kh_prover_index_create: ConstraintSystem::create(gates).public(k).build() + the verifier index, no
-    lookup argument).  The handle owns the device columns; this object carries what create_proof_native and the verifier side read."""
+    """An index built natively from a gate list (kh_prover_index_create / kh_prover_index_create_lookup: ConstraintSystem::create(gates)
+    .lookup(tables).runtime(cfgs).public(k).build() + the verifier index).  The handle owns the device columns; this object carries what
+    create_proof_native and the verifier side read."""
 
     GATE_TYPES = ProverIndex.GATE_TYPES
+    LOOKUP_GATES = ("Lookup", "Xor16", "RangeCheck0", "RangeCheck1", "Rot64", "ForeignFieldMul")
 
-    def __init__(self, srs, gate_types, wires, coeffs, public: int = 0):
-        """gate_types: one per row, a name ("Generic", a library gate, "ForeignFieldAdd", "Zero") or a kh gate id; wires: per row 7 (row, col)
-        pairs; coeffs: (rows, 15, 4) Montgomery limbs."""
+    def __init__(self, srs, gate_types, wires, coeffs, public: int = 0, tables=None, runtime_tables=None):
+        """gate_types: one per row, a name ("Generic", a library or optional gate, "Lookup", "Zero") or a kh gate id; wires: per row 7 (row, col)
+        pairs; coeffs: (rows, 15, 4) Montgomery limbs.  tables: [{"id", "data": columns}] (LookupTable; a column = integers or (len, 4) limbs);
+        runtime_tables: [{"id", "first_column"}] (RuntimeTableCfg).  The lookup entry point is taken when a gate has a lookup pattern or
+        tables are given."""
         gids = khip.gate_ids()
-        ids = [t if isinstance(t, (int, np.integer)) else (khip.GATE_ZERO if t == "Zero" else gids[t]) for t in gate_types]
+        special = {"Zero": khip.GATE_ZERO, "Lookup": khip.GATE_LOOKUP}
+        ids = [t if isinstance(t, (int, np.integer)) else special[t] if t in special else gids[t] for t in gate_types]
         names = {g: t for t, g in gids.items()}
         self.srs, self.curve, self.public = srs, srs.curve, public
         self.fid = khip.FP if self.curve == khip.VESTA else khip.FQ
         F = self.F = Fld(self.fid)
-        self.native = khip.NativeProverIndex.create(srs, ids, wires, coeffs, public)
+        lookup_ids = {khip.GATE_LOOKUP} | {gids[t] for t in self.LOOKUP_GATES if t in gids}
+        if tables or runtime_tables or lookup_ids & set(ids):
+            col = lambda c: np.asarray(c, dtype=np.uint64).reshape(-1, 4) if isinstance(c, np.ndarray) else F.limbs_many([int(v) % F.p for v in c]).reshape(-1, 4)
+            tl = [(t["id"], np.stack([col(c) for c in t["data"]])) for t in (tables or ())]
+            rl = [(rt["id"], col(rt["first_column"])) for rt in (runtime_tables or ())]
+            self.native = khip.NativeProverIndex.create_lookup(srs, ids, wires, coeffs, public, tl, rl)
+        else:
+            self.native = khip.NativeProverIndex.create(srs, ids, wires, coeffs, public)
         self.log2_n, self.zk_rows, self.num_chunks = self.native.shape()
         self.n, self.size = 1 << self.log2_n, srs.n
-        self.live_gate_types = {names[g] for g in set(ids) if g != khip.GATE_ZERO}
+        self.live_gate_types = {names[g] for g in set(ids) if g not in (khip.GATE_ZERO, khip.GATE_LOOKUP)}
         self.optional = [t for t in OPTIONAL_GATES if t in self.live_gate_types]
         self.omega = F.value(khip.domain_generator(self.fid, self.log2_n))
         self.h = khip.srs_h(self.curve)
@@ -352,6 +398,8 @@ class CreatedIndex:
         self.optional_comms = dict(zip(self.optional, comms("optional_comm")))
         self.shifts = F.values(vi["shifts"])
         self.digest = vi["digest"][0]
+        if vi["lookup_info"] is not None:
+            self.lookup = CreatedLookup(vi, nch, runtime_tables or ())
 
     def free(self):
         self.native.free()

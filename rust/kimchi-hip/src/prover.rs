@@ -174,6 +174,91 @@ where
         GpuProver { index, optional, num_chunks: if n < max_poly_size { 1 } else { n / max_poly_size }, lookup, prev_challenges: cs.prev_challenges, _cols: cols, _srs: srs }
     }
 
+    /// The whole index from the gate list as ONE native call (`kh_prover_index_create_lookup`): what
+    /// `ConstraintSystem::create(gates).lookup(tables).runtime(cfgs).public(public).build()` + `ProverIndex::verifier_index()` compute, on the device --
+    /// domain, columns, the lookup constraint system (selectors, combined table, table ids, runtime selector, row-set atoms), commitments and digest.
+    /// `cs` supplies the gates only (type, wires, coefficients; trailing `Zero` padding rows are dropped); `lookup_tables`: `(id, columns)` of each
+    /// `LookupTable`; `runtime_tables`: `(id, first_column)` of each `RuntimeTableCfg` (empty: none configured).  The digest is the library's own
+    /// (`kh_verifier_index_section(KH_VINDEX_DIGEST)`); the verifier index's commitments are the other `KH_VINDEX_*` sections of `index_handle()`.
+    pub fn from_gates(
+        cs: &ConstraintSystem<G::ScalarField>,
+        lookup_tables: &[(i32, Vec<Vec<G::ScalarField>>)],
+        runtime_tables: &[(i32, Vec<G::ScalarField>)],
+        srs: GpuSrs<G>,
+    ) -> Self {
+        let rows = cs.gates.iter().rposition(|g| g.typ != GateType::Zero).map_or(0, |r| r + 1);
+        let gates = &cs.gates[..rows];
+        let types: Vec<i32> = gates
+            .iter()
+            .map(|g| match g.typ {
+                GateType::Zero => sys::KH_GATE_ZERO,
+                GateType::Lookup => sys::KH_GATE_LOOKUP,
+                GateType::Generic => gate_id("Generic"),
+                t => LIB
+                    .iter()
+                    .position(|l| *l == t)
+                    .map(|k| gate_id(["Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar"][k]))
+                    .or_else(|| OPTIONAL.iter().find(|o| o.0 == t).map(|o| gate_id(o.1)))
+                    .expect("gate type without a kernel in libkimchi_hip"),
+            })
+            .collect();
+        let wires: Vec<u32> = gates.iter().flat_map(|g| g.wires.iter().flat_map(|w| [w.row as u32, w.col as u32])).collect();
+        let mut coeffs = vec![G::ScalarField::zero(); COLUMNS * rows];
+        for (r, g) in gates.iter().enumerate() {
+            for (c, v) in g.coeffs.iter().take(COLUMNS).enumerate() {
+                coeffs[COLUMNS * r + c] = *v;
+            }
+        }
+        // column-major copies of the tables: the library keeps nothing of them after the call
+        let flat: Vec<Vec<G::ScalarField>> = lookup_tables.iter().map(|(_, cols)| cols.iter().flat_map(|c| c.iter().copied()).collect()).collect();
+        let tabs: Vec<sys::kh_lookup_table_t> = lookup_tables
+            .iter()
+            .zip(&flat)
+            .map(|((id, cols), data)| sys::kh_lookup_table_t { id: *id, width: cols.len(), len: cols.first().map_or(0, |c| c.len()), data: limbs(data) })
+            .collect();
+        let cfgs: Vec<sys::kh_runtime_table_cfg_t> =
+            runtime_tables.iter().map(|(id, first)| sys::kh_runtime_table_cfg_t { id: *id, len: first.len(), first_column: limbs(first) }).collect();
+        let mut index = core::ptr::null_mut();
+        ok(unsafe {
+            sys::kh_prover_index_create_lookup(
+                srs.handle(),
+                rows,
+                types.as_ptr(),
+                wires.as_ptr(),
+                limbs(&coeffs),
+                cs.public as u32,
+                tabs.as_ptr(),
+                tabs.len(),
+                cfgs.as_ptr(),
+                cfgs.len(),
+                &mut index,
+            )
+        });
+        let (mut log2_n, mut zk, mut num_chunks) = (0u32, 0u32, 0usize);
+        ok(unsafe { sys::kh_prover_index_shape(index, &mut log2_n, &mut zk, &mut num_chunks) });
+        // the lookup shape from the index itself: KH_VINDEX_LOOKUP_INFO = max_per_row, max_joint_size, joint_lookup_used, uses_runtime_tables | pattern mask, ...
+        let (mut info, mut flags, mut count) = (core::ptr::null(), core::ptr::null(), 0usize);
+        ok(unsafe { sys::kh_verifier_index_section(index, sys::KH_VINDEX_LOOKUP_INFO, &mut info, &mut flags, &mut count) });
+        let lookup = if count == 0 {
+            None
+        } else {
+            let words = unsafe { core::slice::from_raw_parts(info, 4 * count) };
+            let mut patterns = [false; 4];
+            for (k, p) in patterns.iter_mut().enumerate() {
+                *p = (words[4] >> k) & 1 == 1;
+            }
+            let runtime = if words[3] != 0 { Some(runtime_tables.iter().map(|(id, first)| (*id, first.len())).collect()) } else { None };
+            Some(LookupShape { patterns, max_per_row: words[0] as usize, runtime })
+        };
+        let optional: Vec<usize> = (0..6).filter(|&k| gates.iter().any(|g| g.typ == OPTIONAL[k].0)).collect();
+        GpuProver { index, optional, num_chunks, lookup, prev_challenges: cs.prev_challenges, _cols: Vec::new(), _srs: srs }
+    }
+
+    /// The native handle, for `kh_verifier_index_section` / `kh_prover_index_shape`.
+    pub fn index_handle(&self) -> *const sys::kh_prover_index_t {
+        self.index
+    }
+
     /// `kh_prover_index_attach_lookup` (+ `_attach_runtime_tables`) from the reference's `LookupConstraintSystem`: it keeps the pattern selectors,
     /// the table columns and the table ids as evaluations over d8 (lookup/index.rs:159-194) -- every 8th value is the d1 column; coefficient forms
     /// and the library's own d8 copies are made on the device.  The three row-set atoms of the lookup constraints (expr.rs:883-893) are evaluated
