@@ -44,3 +44,22 @@ def test_spread_constants_dominate_their_subtrahends():
             assert all(c[i] >= J * gen.MASK for i in range(8))
             top = int(bound * p) >> 232                      # largest top limb of a NORMALISED value below bound * p
             assert c[8] >= top + (J - 1), (K, J)             # (+ J - 1: the top limb of a J-term limb-wise sum is not normalised)
+
+
+def test_directed_operands_reach_the_extreme_reduction_digits():
+    """Carry sites of the 29-bit streams: a v_mad_u64_u32 is the only VCC writer and nothing reads VCC, so all of them are
+    unreachable -- by the accumulator bound that simulate() asserts on every vector, checked here through trace (VCC = 0 only).
+    What uniform operands miss instead (2^-29 per column) is m_k = 0 and m_k = MASK: gen.directed29 solves for both in every
+    column of the middle product of the three device pipelines, and the pipelines equal big integers on those operands."""
+    for p in (gen.P_FP, gen.P_FQ):
+        Rinv = pow(1 << 256, -1, p)
+        for kind in ("mul", "sqr", "mul32x"):
+            vecs = gen.directed29(p, kind)
+            assert vecs == gen.directed29(p, kind)                      # deterministic
+            want = {(k, t) for k in range(9) for t in (0, gen.MASK)} - ({(0, gen.MASK)} if kind == "mul32x" else set())
+            assert {(k, t) for _, _, k, t in vecs} == want
+            for x, y, k, t in vecs:
+                assert x < p and y < p
+                assert gen.pipeline29(p, kind, x, y) == x * y * Rinv % p, (kind, k, t)
+    for lines in (gen.gen_mul(), gen.gen_sqr(), gen.gen_muladd(), gen.gen_mul(False)):
+        assert not any(ln.split(",")[-1].strip() == "vcc" for ln in lines)          # no instruction reads VCC

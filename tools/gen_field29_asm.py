@@ -110,8 +110,11 @@ def _gen(r, prods, P, mask, pairk, pre, shift64):
 
 
 # ------------------------------------------------------------------------------------------- interpreter
-def simulate(lines, regs):
-    """regs: dict name -> int (32-bit values; the accumulator is two entries '<acc>_lo' / '<acc>_hi')."""
+def simulate(lines, regs, trace=None):
+    """regs: dict name -> int (32-bit values; the accumulator is two entries '<acc>_lo' / '<acc>_hi').
+    trace: dict instruction index -> set, updated: the VCC values of every v_mad_u64_u32 (its only carry site: the stream has
+    no instruction that reads VCC, and the assertion below is the bound that keeps every one of them at 0) and the values of
+    every m_k (v_bfi_b32)."""
     def val(tok):
         tok = tok.strip()
         if tok in regs:
@@ -129,17 +132,21 @@ def simulate(lines, regs):
         assert tok == ACC
         return regs[LO] | (regs[HI] << 32)
 
-    for ln in lines:
+    for idx, ln in enumerate(lines):
         op, rest = ln.split(None, 1)
         args = [x.strip() for x in rest.split(",")]
         if op == "v_mad_u64_u32":
             d, _vcc, x, y, c = args
             v = val(x) * val(y) + val64(c)
             assert v < (1 << 64), "64-bit accumulator overflow in: " + ln
+            if trace is not None:
+                trace.setdefault(idx, set()).add(v >> 64)
             regs[LO], regs[HI] = v & 0xffffffff, v >> 32
         elif op == "v_bfi_b32":
             d, s0, s1, s2 = args
             regs[d] = (val(s0) & val(s1)) | (~val(s0) & val(s2) & 0xffffffff)
+            if trace is not None:
+                trace.setdefault(idx, set()).add(regs[d])
         elif op == "v_and_b32":
             d, x, y = args
             regs[d] = val(x) & val(y)
@@ -465,6 +472,106 @@ def check_add(p, name, trees=6, leaves=24):
     neg = (b2[0], limbs29((5 * p - val29(b2[1])) % (8 * p)), b2[2], b2[3])
     assert M.add(a2, neg) is None
     print(f"{name}: add29 limb model OK over {trees} trees of {leaves} leaves; max value / p = " + ", ".join(f"{m:.2f}" for m in maxv))
+
+
+# ------------------------------------------------------------------------------------------- directed operands
+# The 29-bit streams have no carry chain: a v_mad_u64_u32 is their only VCC writer and nothing reads VCC, so every carry site is
+# unreachable by the accumulator bound that simulate() asserts (A + B <= 60.7, see the header).  What a uniform operand meets with
+# probability 2^-29 per column instead is an extreme reduction digit: m_k = 0 (the offset column ends in 29 one bits) and
+# m_k = MASK (it ends in 29 zero bits).  directed29 reaches both for every column k of the MIDDLE product of the three device
+# pipelines (khip.debug_field_op mul29 / sqr29 / mul29_32x), by solving for limb k of the second operand: it enters column k through
+# the one product with a_0 and no earlier column.
+def m_sites(lines):
+    return [i for i, ln in enumerate(lines) if ln.startswith("v_bfi_b32")]
+
+
+def directed29(p, kind):
+    """kind 'mul', 'sqr', 'mul32x'.  Returns [(x, y, k, target)]: canonical wire-form operands (integers < p; y = x for sqr) for
+    which the middle product has m_k = target (every k = 0..8 and target 0, MASK; not m_0 = MASK for mul32x).  Deterministic."""
+    rnd = random.Random(f"directed29/{kind}/{p & 0xffff}")
+    M = Madd29Model(p)
+    R, R29 = 1 << 256, 1 << 261
+    to_wire = R * pow(R29, -1, p) % p                    # to29(x) = x R' / R (mod p)
+    lines = M.sqr_l if kind == "sqr" else M.mul_l
+    sites = m_sites(lines)
+
+    def middle(al, bl):
+        tr = {}
+        regs = {f"%{i}": 0 for i in range(9)}
+        pl = M.pl
+        if kind == "sqr":
+            regs.update({f"%{17 + i}": al[i] for i in range(9)})
+            regs.update({"%26": pl[1], "%27": pl[2], "%28": pl[3], "%29": pl[4], "%30": 1 << 22, "%31": MASK, "%32": (1 << 29) + 1, LO: 0, HI: 0})
+            regs.update({f"%{8 + j}": 0 for j in range(1, 9)})
+        else:
+            regs.update({f"%{9 + i}": al[i] for i in range(9)}); regs.update({f"%{18 + i}": bl[i] for i in range(9)})
+            regs.update({"%27": pl[1], "%28": pl[2], "%29": pl[3], "%30": pl[4], "%31": 1 << 22, "%32": MASK, "%33": (1 << 29) + 1, LO: 0, HI: 0})
+        simulate(lines, regs, tr)
+        assert all(tr[i] == {0} for i in tr if i not in sites)
+        return [next(iter(tr[i])) for i in sites]
+
+    def wire(limbs_):                                      # the canonical x with to29(x) == limbs_, or None
+        x = val29(limbs_) * to_wire % p
+        return x if M.mul(limbs29(x), M.c["KIN"]) == list(limbs_) else None
+
+    out = []
+    for k in range(9):
+        for target in (0, MASK):
+            if kind == "mul32x" and k == 0 and target == MASK:
+                continue                                   # needs a_0 b_0 = 1 (mod 2^29), and a_0 = 32 X mod 2^29 is even
+            for _ in range(4000):
+                if kind == "mul32x":
+                    x = rnd.randrange(p); al = limbs29(x << 5)
+                else:
+                    al = limbs29(rnd.randrange(p)); al[0] |= 1
+                if kind == "sqr" and k == 0:
+                    al[0] = 0 if target == 0 else 1        # the column is a_0^2 + MASK
+                    bl = al
+                elif kind == "sqr":
+                    lo = [middle(al[:k] + [v] + al[k + 1:], None)[k] for v in (0, 1)]
+                else:
+                    bl = limbs29(rnd.randrange(p))
+                    lo = [middle(al, bl[:k] + [v] + bl[k + 1:])[k] for v in (0, 1)]
+                if not (kind == "sqr" and k == 0):
+                    g = (lo[0] - lo[1]) % (1 << 29)        # m_k = ~low & MASK falls by g when the limb rises by one
+                    need = (lo[0] - target) % (1 << 29)
+                    d = 1
+                    while g % (2 * d) == 0 and d < (1 << 29):
+                        d *= 2
+                    if g == 0 or need % d:
+                        continue
+                    v = (need // d) * pow(g // d, -1, (1 << 29) // d) % ((1 << 29) // d)
+                    if v > ((1 << 22) - 1 if k == 8 else MASK):
+                        continue
+                    if kind == "sqr":
+                        al = al[:k] + [v] + al[k + 1:]; bl = al
+                    else:
+                        bl = bl[:k] + [v] + bl[k + 1:]
+                if val29(al) >= (32 * p if kind == "mul32x" else p) or val29(bl) >= p or middle(al, bl)[k] != target:
+                    continue
+                xw = x if kind == "mul32x" else wire(al)
+                yw = xw if kind == "sqr" else wire(bl)
+                if xw is None or yw is None:
+                    continue
+                out.append((xw, yw, k, target))
+                break
+            else:
+                raise AssertionError(f"directed29 {kind}: no operand for m_{k} = {target}")
+    return out
+
+
+def pipeline29(p, kind, x, y, trace=None):
+    """The device pipeline of debug_field_op mul29 / sqr29 / mul29_32x on wire-form integers, through the model: to29 (or the
+    free 32 X packing), the product, from29.  Returns the canonical wire-form result."""
+    M = Madd29Model(p)
+    a = limbs29(x << 5) if kind == "mul32x" else M.mul(limbs29(x), M.c["KIN"])
+    if kind == "sqr":
+        t = M.sqr(a)
+    else:
+        t = M.mul(a, M.mul(limbs29(y), M.c["KIN"]))
+    w = val29(M.mul(t, M.c["KOUT"]))
+    assert w < 2 * p
+    return w - p if w >= p else w
 
 
 def emit_consts():

@@ -186,19 +186,32 @@ def gen_add():
     return L
 
 
-out = ["// GENERATED by tools/gen_field_asm.py -- do not edit.  See that file for the schedule.",
-       f"// {len(gen_mul())} instructions per Montgomery product.",
-       emit("KH_MONT_MUL_ASM", gen_mul()),
-       '#define KH_MONT_MUL_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13"',
-       f"// Montgomery squaring: {len(gen_sqr())} instructions (36 limb products instead of 64)",
-       emit("KH_MONT_SQR_ASM", gen_sqr()),
-       '#define KH_MONT_SQR_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20"',
-       f"// modular subtraction ({len(gen_sub())} instructions) and addition ({len(gen_add())} instructions)",
-       emit("KH_FE_SUB_ASM", gen_sub()),
-       '#define KH_FE_SUB_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7"',
-       emit("KH_FE_ADD_ASM", gen_add()),
-       '#define KH_FE_ADD_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9"',
-       ""]
-path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "proof_systems_amd", "csrc", "field_mulasm.inc")
-open(path, "w").write("\n".join(out))
-print(len(gen_mul()), "instructions")
+INC_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "proof_systems_amd", "csrc", "field_mulasm.inc")
+
+
+def render():
+    out = ["// GENERATED by tools/gen_field_asm.py -- do not edit.  See that file for the schedule.",
+           f"// {len(gen_mul())} instructions per Montgomery product.",
+           emit("KH_MONT_MUL_ASM", gen_mul()),
+           '#define KH_MONT_MUL_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13"',
+           f"// Montgomery squaring: {len(gen_sqr())} instructions (36 limb products instead of 64)",
+           emit("KH_MONT_SQR_ASM", gen_sqr()),
+           '#define KH_MONT_SQR_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16", "v17", "v18", "v19", "v20"',
+           f"// modular subtraction ({len(gen_sub())} instructions) and addition ({len(gen_add())} instructions)",
+           emit("KH_FE_SUB_ASM", gen_sub()),
+           '#define KH_FE_SUB_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7"',
+           emit("KH_FE_ADD_ASM", gen_add()),
+           '#define KH_FE_ADD_CLOBBERS "vcc", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9"',
+           ""]
+    return "\n".join(out)
+
+
+def main():
+    text = render()
+    if not os.path.exists(INC_PATH) or open(INC_PATH).read() != text:      # leave the mtime alone when nothing changed
+        open(INC_PATH, "w").write(text)
+    print(len(gen_mul()), "instructions")
+
+
+if __name__ == "__main__":
+    main()
