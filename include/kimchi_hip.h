@@ -474,7 +474,7 @@ int kh_last_timings(const char **names, float *ms, int cap);
 /* Process-wide event counters (how often a path ran): "spread_retry" (an opening round's MSM met a hot bucket and was re-run with the hot-bucket
  * kernels), "fused_retry" (the one-launch sort gave up), "rebase_launch" / "rebase_switch" / "rebase_abandon" (openings that started
  * materialising the folded basis of their late rounds, switched over to it, gave it up), "rebased_rounds" (rounds that ran over a materialised
- * basis).  Unknown names read 0. */
+ * basis), "lookup_sorted_dev" (successful kh_lookup_sorted_dev calls; kh_prove makes one per proof with lookups).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,
@@ -512,13 +512,29 @@ int kh_comm_allgather_points(kh_comm_t *comm, const uint64_t *xy, const uint8_t 
 int kh_msm_allreduce(kh_comm_t *comm, kh_srs_t *shard, const uint64_t *scalars, size_t n, int scalars_are_montgomery, uint64_t out_xy[8],
                      uint8_t *out_is_inf);
 
-/* ---- the lookup argument's `sorted` step (kimchi/src/circuits/lookup/constraints.rs:90-194), host code as in the reference ----
+/* ---- the lookup argument's `sorted` step (kimchi/src/circuits/lookup/constraints.rs:90-194) ----
+ * Two entry points with one result.  kh_lookup_sorted is the host one: host vectors in, host vectors out, one thread, a HashMap walk as in the
+ * reference; it serves callers whose columns live on the host and is the reference the device path is tested against.  kh_lookup_sorted_dev runs the
+ * same hash join and the expansion on the device (csrc/lookup_sorted.hip) over device-resident columns: it is the path kh_prove takes -- the
+ * looked-up values and the combined table never leave the card -- and the one for any device-resident caller.
+ *
  * table: the first lookup_rows = n - zk_rows - 1 entries of the combined table (4 limbs each, host memory); values: max_per_row columns of looked-up
  * joint values, column s at values + 4 s value_stride, lookup_rows entries each (a row with fewer lookups than max_per_row holds the dummy value 0 in
  * the remaining slots).  out: max_per_row + 1 columns of lookup_rows + 1 values: every table entry repeated (times looked up + 1), in table order,
  * snake layout (consecutive columns share one element, odd columns reversed).  A value that is not in the table: KH_E_INVALID and *bad_row = its row. */
 int kh_lookup_sorted(const uint64_t *table, size_t lookup_rows, const uint64_t *values, size_t value_stride, size_t max_per_row, uint64_t *out,
                      size_t *bad_row);
+/* The same on the device, queued on the main stream of the calling thread's current context.  table_dev / values_dev as above, in device memory (rows
+ * from lookup_rows on are not looked at); column k of the result starts at out_dev + 4 k out_stride and exactly lookup_rows + 1 elements of it are
+ * written: every other element of out_dev is left untouched (a prover points it at its padded n-element columns, out_stride = n, and fills the
+ * zero-knowledge rows itself).  The same 32-byte values as kh_lookup_sorted, position for position.  A value that is not in the table: KH_E_INVALID,
+ * *bad_row = the row the host function would report (lowest slot, then lowest row), the same text in kh_last_error, out_dev untouched.  The call waits
+ * once, for one status word; on KH_OK out_dev is ordered on the main stream like the results of the other vector steps (no kh_sync before a consumer on
+ * the library's stream).  KH_E_INVALID before anything is launched: a null pointer (bad_row may be null), pointers that are not 16-byte aligned,
+ * lookup_rows == 0, max_per_row == 0, value_stride < lookup_rows, out_stride < lookup_rows + 1, (max_per_row + 1) lookup_rows >= 2^31.
+ * Scratch (hash slots, counts, offsets) comes from the kh_dev_alloc pool. */
+int kh_lookup_sorted_dev(const uint64_t *table_dev, size_t lookup_rows, const uint64_t *values_dev, size_t value_stride, size_t max_per_row,
+                         uint64_t *out_dev, size_t out_stride, size_t *bad_row);
 
 /* ---- ProverProof::create as ONE native call (kimchi/src/prover.rs:187-1515, the part this library accelerates end to end) ----
  * The host loop of the prover -- witness columns -> commitments -> z -> quotient -> evaluations -> opening, with the transcript -- written
@@ -577,7 +593,7 @@ int kh_prover_index_new(kh_srs_t *srs, unsigned log2_n, unsigned zk_rows, unsign
  * d1 evaluations, coefficient form and d8 evaluations; the concatenated table columns and (nullable) the table-id column as d1 evaluations; and the d8
  * evaluations of the three row-set atoms the constraints use (expr.rs:883-893): VanishesOnZeroKnowledgeAndPreviousRows, UnnormalizedLagrangeBasis(0),
  * UnnormalizedLagrangeBasis(-zk_rows - 1).  The digest given to kh_prover_index_new must cover the lookup index.  kh_prove then runs the lookup argument
- * (joint combiner, combined table, sorted columns via kh_lookup_sorted, aggregation, the lookup constraints on d8, the extra evaluations and openings);
+ * (joint combiner, combined table, sorted columns on the device via kh_lookup_sorted_dev, aggregation, the lookup constraints on d8, the extra evaluations and openings);
  * KH_PROOF_EVALS carries, after the polynomials listed above: sorted x (max_per_row + 1), aggregation, combined table, one selector per pattern;
  * the randomness grows by (max_per_row + 1) (zk_rows + num_chunks) after the witness blinders and zk_rows + num_chunks before z's two rows. */
 int kh_prover_index_attach_lookup(kh_prover_index_t *index, const int *patterns, size_t n_patterns, const uint64_t *const *selectors_d1,

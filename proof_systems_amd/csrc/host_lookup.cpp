@@ -2,10 +2,12 @@
 //
 // The reference counts, with a HashMap over field elements, how often every entry of the combined table is looked up, repeats each entry
 // (count + 1) times in table order and lays the result out as max_per_row + 1 "snake" columns (consecutive columns share one element, every
-// second column is reversed).  That is a hash join between two host-sized vectors -- it stays host code here too, but native: the Python loop
-// that used to do it cost 0.36 s of a 0.38 s proof at 2^16 rows.  The looked-up values themselves are computed on the device (one expression
-// per lookup slot over the resident witness columns and pattern selectors, proof_systems_amd/lookup.py::lookup_values_dev) and come down as
-// limbs; nothing here does field arithmetic: values are compared as 32-byte strings (canonical Montgomery limbs are unique).
+// second column is reversed).  That is a hash join between two vectors.  This file is the host entry point, kh_lookup_sorted: host vectors in, host
+// vectors out, one thread (the Python loop it replaced cost 0.36 s of a 0.38 s proof at 2^16 rows).  kh_prove and the Python prover no longer come
+// through here: their values and table are device-resident and csrc/lookup_sorted.hip (kh_lookup_sorted_dev) runs the same join there, without the
+// two transfers.  This function stays for callers with host-side columns and as the reference the device path is tested against, position for
+// position (tests/test_gpu_lookup_sorted_dev.py); the hash and the first-occurrence rule below are the ones the kernels use.
+// Nothing here does field arithmetic: values are compared as 32-byte strings (canonical Montgomery limbs are unique).
 #include <stdint.h>
 #include <string.h>
 #include <vector>

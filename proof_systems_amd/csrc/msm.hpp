@@ -82,6 +82,12 @@ int lookup_atom_denominators(Context& C, int field, const uint64_t* x8_dev, size
                              uint64_t* atoms_dev);
 int lookup_atom_finish(Context& C, int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4],
                        uint64_t* atoms_dev);
+// lookup_sorted.hip: the `sorted` step of the lookup argument (kh_lookup_sorted_dev).  scratch_dev: lookup_sorted_scratch_words(L) 32-bit words, of which
+// the two at lookup_sorted_status_offset(L) end up as [lowest s * L + r of a value that is not in the table, or 0xffffffff | size of the sorted multiset]
+size_t lookup_sorted_scratch_words(size_t L);
+size_t lookup_sorted_status_offset(size_t L);
+int lookup_sorted_run(Context& C, const uint64_t* table_dev, size_t L, const uint64_t* values_dev, size_t value_stride, size_t mpr, uint64_t* out_dev,
+                      size_t out_stride, uint32_t* scratch_dev);
 // expr.hip
 // the gate library as compiled kernels (gates.hip; generated from the same expression DAGs as the token programs)
 int gate_count();

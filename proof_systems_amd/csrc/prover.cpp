@@ -956,7 +956,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
             KP(d_table.alloc(NB));
             KP(p.run(fid, cols, lens, n, 1, 1, 0, d_table.p));
         }
-        std::vector<fe> vals(lk->mpr * n), table(n);
+        KP(d_sorted.alloc(ns * NB));
         {                                                           // the looked-up joint values, one column per lookup slot (0 = the dummy entry's value)
             Dev d_vals; KP(d_vals.alloc(lk->mpr * NB));
             LookupChallenges ch{}; ch.jc = jc; ch.tic = tic_t;
@@ -975,17 +975,16 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
                 }
                 KP(p.run(fid, cols, lens, n, 1, 1, 0, d_vals.at(sl * NB)));
             }
-            KP(kh_dev_download(vals.data(), d_vals.p, lk->mpr * NB * 32));
-            KP(kh_dev_download(table.data(), d_table.p, NB * 32));
+            // the sorted columns (constraints.rs:90-194) on the device: hash join + snake layout straight into rows 0 .. n - zk - 1 of the padded columns;
+            // values and table stay on the card, the one wait is the join's status word (a value that is not in the table fails here, with its row)
+            size_t bad = 0;
+            KP(kh_lookup_sorted_dev(d_table.p, lookup_rows, d_vals.p, n, lk->mpr, d_sorted.p, n, &bad));
         }
-        std::vector<fe> srt(ns * (lookup_rows + 1)), full(ns * n, zero);
-        size_t bad = 0;
-        KP(kh_lookup_sorted((const uint64_t*)table.data(), lookup_rows, (const uint64_t*)vals.data(), n, lk->mpr, (uint64_t*)srt.data(), &bad));
-        for (size_t k = 0; k < ns; k++) {                           // zk_patch (constraints.rs:35-48): the last zk_rows random, column by column
-            memcpy(&full[k * n], &srt[k * (lookup_rows + 1)], (lookup_rows + 1) * 32);
-            memcpy(&full[k * n + (n - zk)], draw(zk), zk * 32);
+        {                                                           // zk_patch (constraints.rs:35-48): the last zk_rows random, column by column
+            std::vector<fe> zkr(ns * zk);
+            for (size_t k = 0; k < ns; k++) memcpy(&zkr[k * zk], draw(zk), zk * 32);
+            KP(kh_dev_upload_2d(d_sorted.at(n - zk), NB * 32, zkr.data(), zk * 32, zk * 32, ns));
         }
-        KP(d_sorted.alloc(ns * NB)); KP(kh_dev_upload(d_sorted.p, full.data(), ns * NB * 32));
         std::vector<uint64_t> sxy, scx; std::vector<uint8_t> sinf, sci;
         KP(commit_evals(d_sorted.p, ns, sxy, sinf));
         s_blind = draw(ns * nch);

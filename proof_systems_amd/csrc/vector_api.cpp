@@ -185,6 +185,39 @@ int kh_expr_evaluations_dev(int field, const uint32_t* tokens, size_t ntok, cons
     return rc;
 }
 
+// The `sorted` step of the lookup argument on the device (kernels in lookup_sorted.hip).  The scratch block comes from the kh_dev_alloc pool (taken before the
+// context's lock: the pool may order this context behind a block's previous owner); the one wait is the read-back of the status words, outside the lock.
+int kh_lookup_sorted_dev(const uint64_t* table_dev, size_t lookup_rows, const uint64_t* values_dev, size_t value_stride, size_t max_per_row, uint64_t* out_dev,
+                         size_t out_stride, size_t* bad_row) {
+    KH_REQUIRE(table_dev && values_dev && out_dev && lookup_rows > 0 && max_per_row > 0 && value_stride >= lookup_rows && out_stride >= lookup_rows + 1,
+               "kh_lookup_sorted_dev: bad argument");
+    KH_REQUIRE((((uintptr_t)table_dev | (uintptr_t)values_dev | (uintptr_t)out_dev) & 15) == 0, "kh_lookup_sorted_dev: pointers must be 16-byte aligned");
+    KH_REQUIRE(max_per_row < ((size_t)1 << 31) && lookup_rows < ((size_t)1 << 31) && (max_per_row + 1) * lookup_rows < ((size_t)1 << 31),
+               "kh_lookup_sorted_dev: (max_per_row + 1) * lookup_rows = (%zu + 1) * %zu does not fit 31 bits", max_per_row, lookup_rows);
+    int rc = ensure_init(); if (rc) return rc;
+    if (bad_row) *bad_row = (size_t)-1;
+    struct Scratch { uint32_t* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } scratch;
+    if ((rc = kh_dev_alloc((void**)&scratch.p, lookup_sorted_scratch_words(lookup_rows) * sizeof(uint32_t)))) return rc;
+    {
+        Context& C = ctx();
+        std::lock_guard<std::mutex> lk(C.mu);
+        rc = lookup_sorted_run(C, table_dev, lookup_rows, values_dev, value_stride, max_per_row, out_dev, out_stride, scratch.p);
+        C.mark_async();
+        if (rc) return rc;
+    }
+    uint32_t status[2] = {0, 0};
+    if ((rc = kh_dev_download(status, scratch.p + lookup_sorted_status_offset(lookup_rows), sizeof(status)))) return rc;
+    if (status[0] != 0xffffffffu) {                         // a looked-up value that is not in the table (constraints.rs:137-141)
+        const size_t s = status[0] / lookup_rows, r = status[0] % lookup_rows;
+        if (bad_row) *bad_row = r;
+        set_error("lookup in row %zu (slot %zu): the value is not in the table", r, s);
+        return KH_E_INVALID;
+    }
+    KH_REQUIRE(status[1] == (max_per_row + 1) * lookup_rows, "kh_lookup_sorted_dev: %u values for %zu places", status[1], (max_per_row + 1) * lookup_rows);
+    counter(CNT_LOOKUP_SORTED_DEV)++;
+    return KH_OK;
+}
+
 int kh_gate_count(void) { return gate_count(); }
 const char* kh_gate_name(int gate) { return gate_name(gate); }
 int kh_gate_num_constants(int gate) { return gate_num_constants(gate); }

@@ -37,7 +37,7 @@ SYMBOLS = [
     "kh_dev_alloc", "kh_dev_free", "kh_dev_upload", "kh_dev_download", "kh_dev_upload_2d", "kh_dev_upload_2d_unordered",
     "kh_msm_batch_dev", "kh_ntt_dev", "kh_lde_dev", "kh_coset_ntt_dev", "kh_sync", "kh_last_timings",
     "kh_debug_field_op", "kh_debug_point_op", "kh_srs_generate", "kh_srs_h",
-    "kh_msm_sharded", "kh_msm_sharded_dev", "kh_gate_count", "kh_gate_name", "kh_gate_num_constants", "kh_gate_evaluations_dev", "kh_gate_constants", "kh_srs_curve", "kh_lookup_sorted", "kh_private_context_begin", "kh_private_context_end", "kh_private_context_active", "kh_comm_unique_id", "kh_comm_init", "kh_comm_free", "kh_comm_world_size", "kh_comm_rank", "kh_comm_allgather_points",
+    "kh_msm_sharded", "kh_msm_sharded_dev", "kh_gate_count", "kh_gate_name", "kh_gate_num_constants", "kh_gate_evaluations_dev", "kh_gate_constants", "kh_srs_curve", "kh_lookup_sorted", "kh_lookup_sorted_dev", "kh_private_context_begin", "kh_private_context_end", "kh_private_context_active", "kh_comm_unique_id", "kh_comm_init", "kh_comm_free", "kh_comm_world_size", "kh_comm_rank", "kh_comm_allgather_points",
     "kh_msm_allreduce",
     "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
     "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_create_lookup", "kh_debug_lookup_column", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
@@ -108,6 +108,7 @@ _lib.kh_batch_inversion_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
 _lib.kh_divide_by_linear_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, U64P]
 _lib.kh_divide_by_linear_async_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_void_p]
 _lib.kh_check_equal_dev.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_uint]
+_lib.kh_lookup_sorted_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
 _lib.kh_permutation_shifts.argtypes = [C.c_int, C.c_uint, U64P]
 _lib.kh_prover_index_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(C.c_void_p)]
 _lib.kh_prover_index_create_lookup.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(LookupTableC), C.c_size_t,
@@ -514,7 +515,7 @@ def msm_points_batch(curve: int, xy, scalars, inf=None, mont: bool = True):
 
 
 def counter(name: str) -> int:
-    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds."""
+    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds, lookup_sorted_dev."""
     return int(_lib.kh_counter(name.encode()))
 
 
@@ -781,6 +782,18 @@ def lookup_sorted(table, lookup_rows: int, values, max_per_row: int):
         raise ValueError(bad.value)
     _check(rc)
     return out
+
+
+def lookup_sorted_dev(table, lookup_rows: int, values, value_stride: int, max_per_row: int, out, out_stride: int):
+    """kh_lookup_sorted_dev: the same over device buffers (anything with a .ptr), queued on the main stream.  table: >= lookup_rows elements; values:
+    max_per_row columns, value_stride elements apart; out: max_per_row + 1 columns, out_stride elements apart, of which elements 0 .. lookup_rows are
+    written and nothing else.  Raises ValueError(row) for a value that is not in the table (out is then untouched)."""
+    bad = C.c_size_t(0)
+    rc = _lib.kh_lookup_sorted_dev(C.c_void_p(table.ptr), C.c_size_t(lookup_rows), C.c_void_p(values.ptr), C.c_size_t(value_stride), C.c_size_t(max_per_row),
+                                   C.c_void_p(out.ptr), C.c_size_t(out_stride), C.byref(bad))
+    if rc != 0 and bad.value != C.c_size_t(-1).value:
+        raise ValueError(bad.value)
+    _check(rc)
 
 
 class Comm:

@@ -6,8 +6,10 @@ Reference (kimchi/src/): prover.rs:383-673 (the lookup part of ProverProof::crea
 (constraints), circuits/lookup/lookups.rs:222-280 (selectors, by_row).
 
 What runs where
-  * `sorted`       the reference counts multiplicities in a HashMap and walks the table once (constraints.rs:108-171):
-                   sequential host work, stays on the host here as well (numpy / dict over the values' limbs).
+  * `sorted`       the reference counts multiplicities in a HashMap and walks the table once (constraints.rs:108-171).
+                   Here: the looked-up values by kh_expr_evaluations_dev, the hash join and the snake layout by
+                   kh_lookup_sorted_dev (sorted_columns_dev) -- nothing leaves the device; sorted_columns_host goes
+                   through the host entry point kh_lookup_sorted, sorted_columns is the restatement on Python integers.
   * `aggregation`  per-row numerators f_chunk * t_chunk and denominators s_chunk: two token programs run by
                    kh_expr_evaluations_dev over the device-resident witness / table / sorted columns, one
                    kh_batch_inversion_dev, one running product kh_field_scan_dev -- the same three vector steps as the
@@ -219,9 +221,27 @@ def lookup_values_dev(ix: LookupIndex, d_witness, joint_combiner: int) -> "khip.
     return out
 
 
-def sorted_columns_dev(ix: LookupIndex, d_witness, d_table, joint_combiner: int):
-    """`sorted` (constraints.rs:90-194) without Python integers: looked-up values by the device, the hash join natively on the host
-    (kh_lookup_sorted).  Returns (max_per_row + 1, n - zk_rows, 4) limbs; ValueError(row) for a value that is not in the table."""
+def sorted_columns_dev(ix: LookupIndex, d_witness, d_table, joint_combiner: int, out=None):
+    """`sorted` (constraints.rs:90-194) without Python integers and without leaving the device: looked-up values by the expression kernels, hash join
+    and snake layout by kh_lookup_sorted_dev.  With `out` (a device buffer of max_per_row + 1 columns of n elements) rows 0 .. n - zk_rows - 1 of every
+    column are written there, the rest is left to the caller, and nothing is returned; without it the columns come back as
+    (max_per_row + 1, n - zk_rows, 4) limbs.  ValueError(row) for a value that is not in the table."""
+    n, lookup_rows = ix.n, ix.n - ix.zk_rows - 1
+    d_vals = lookup_values_dev(ix, d_witness, joint_combiner)
+    d_out = out if out is not None else khip.DevBuf((ix.max_per_row + 1) * n * 32)
+    try:
+        khip.lookup_sorted_dev(d_table, lookup_rows, d_vals, n, ix.max_per_row, d_out, n)
+        if out is None:
+            return np.ascontiguousarray(d_out.download((ix.max_per_row + 1, n, 4))[:, :lookup_rows + 1])
+    finally:
+        d_vals.free()
+        if out is None:
+            d_out.free()
+
+
+def sorted_columns_host(ix: LookupIndex, d_witness, d_table, joint_combiner: int):
+    """The same through the host entry point (kh_lookup_sorted): values and table come down, the hash join runs on one host thread.  For callers
+    whose columns are host-side anyway, and the device path's reference."""
     n = ix.n
     d_vals = lookup_values_dev(ix, d_witness, joint_combiner)
     vals = d_vals.download((ix.max_per_row, n, 4))

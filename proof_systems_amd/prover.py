@@ -36,7 +36,7 @@ MOD = {khip.FP: 0x40000000000000000000000000000000224698fc094cf91b992d30ed000000
        khip.FQ: 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001}
 R256 = 1 << 256
 import os as _os
-_PY_LOOKUP_SORT = bool(_os.environ.get("KH_PY_LOOKUP_SORT"))   # A/B: the lookup argument's sorted columns in Python instead of kh_lookup_sorted
+_PY_LOOKUP_SORT = bool(_os.environ.get("KH_PY_LOOKUP_SORT"))   # A/B: the lookup argument's sorted columns in Python instead of kh_lookup_sorted_dev
 _TOKEN_GATES = bool(_os.environ.get("KH_TOKEN_GATES"))     # A/B: run the gate library through the token machine instead of the compiled kernels
 
 
@@ -583,14 +583,18 @@ def create_proof(ix: ProverIndex, witness, rng, timings=None, check: bool = True
             wit_ints = [F.values(wcols[c]) if c in used else None for c in range(COLUMNS)]
             srt = [LK.zk_patch(F, c, n, zk, rng) for c in LK.sorted_columns(LI, wit_ints, table_ints, jc)]    # ValueError(row): value not in the table
             full = np.stack([F.limbs_many(c) for c in srt])
-        else:                                               # looked-up values on the device, hash join natively on the host (kh_lookup_sorted)
-            sl = LK.sorted_columns_dev(LI, [ev.view(i * NB) for i in range(COLUMNS)], d_table, jc)
-            full = np.zeros((sl.shape[0], n, 4), dtype=np.uint64)
-            full[:, :n - zk] = sl
-            for k_ in range(sl.shape[0]):                   # zk_patch (constraints.rs:35-48): the last zk_rows of every column random, column by column
-                full[k_, n - zk:] = F.limbs_many(F.rand_many(rng, zk))
-        d_sorted_base = khip.DevBuf(full.shape[0] * NB).upload(full)
-        d_sorted = [d_sorted_base.view(k_ * NB) for k_ in range(full.shape[0])]
+            d_sorted_base = khip.DevBuf(full.shape[0] * NB).upload(full)
+        else:                                               # looked-up values, hash join and snake layout on the device (kh_lookup_sorted_dev): nothing comes down
+            ns_ = LI.max_per_row + 1
+            d_sorted_base = khip.DevBuf(ns_ * NB)
+            try:                                            # rows 0 .. n - zk - 1 of every column; ValueError(row): value not in the table
+                LK.sorted_columns_dev(LI, [ev.view(i * NB) for i in range(COLUMNS)], d_table, jc, out=d_sorted_base)
+            except ValueError:
+                d_sorted_base.free()
+                raise
+            # zk_patch (constraints.rs:35-48): the last zk_rows of every column random, column by column
+            d_sorted_base.upload_2d((n - zk) * 32, NB, np.stack([F.limbs_many(F.rand_many(rng, zk)) for _ in range(ns_)]))
+        d_sorted = [d_sorted_base.view(k_ * NB) for k_ in range(d_sorted_base.nbytes // NB)]
         scom = ix.commit_evals(d_sorted_base.ptr, len(d_sorted))    # commit_evaluations(d1, v, rng): non-hiding (one batched MSM), then one blinder per chunk
         s_blind = [F.rand_many(rng, nch) for _ in d_sorted]
         s_comm = ix.mask(scom, [x for bl_ in s_blind for x in bl_])
