@@ -712,6 +712,48 @@ int kh_prove_recursive(kh_prover_index_t *index, const uint64_t *witness, size_t
 int kh_prove_full(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, const uint64_t *randomness, size_t n_random,
                   unsigned flags, const uint64_t *prev_chals, const unsigned *prev_rounds, const uint64_t *prev_comm_xy, const uint8_t *prev_comm_inf,
                   const size_t *prev_comm_chunks, size_t n_prev, const uint64_t *runtime_values, size_t n_runtime, kh_proof_t **out);
+/* ---- the witness against the circuit, row by row: ProverIndex::verify / ConstraintSystem::verify (kimchi/src/circuits/constraints.rs) ----
+ * kh_prove with KH_PROVE_CHECK runs the whole proof before it says that the witness does not satisfy the constraints, and names no row.
+ * kh_witness_check says which row and why, in tens of microseconds of kernels (csrc/witness_check.hip) over what is resident already: the index's d1
+ * columns (coefficients, selectors), the wires of the gate list, the witness.  It is a deterministic check: every constraint of every row is evaluated
+ * on its own and compared with zero exactly -- no alpha, no random combination.
+ *   The witness is given as to kh_prove: witness = 15 columns x rows x 4 Montgomery limbs on the host (rows + zk_rows <= n; padded with zeros to n
+ *   on the device -- no zero-knowledge rows and no randomness are drawn, the call is deterministic), or witness_dev = the padded 15 x n columns on the
+ *   device, checked as given (`rows` is not read).
+ *   flags: KH_WITNESS_GATES -- the constraints of every row's gate: the double generic gate (2 constraints; on rows r < public_inputs the public
+ *   input, by definition the witness's own cell w[0][r], is subtracted from the first), the five library gates, the optional gates.  `next` of row
+ *   n - 1 is row 0.  Works on every index (one from kh_prover_index_new has the selector columns too; its library gates are those of live_mask).
+ *   KH_WITNESS_WIRES -- the copy constraints: every cell (r, c < 7) of the gate list holds the value of the cell it is wired to.  Needs the gate
+ *   list: an index from kh_prover_index_create(_lookup), which keeps its wires on the device; any other index: KH_E_INVALID with a message.
+ *   Returns KH_OK for a satisfied AND for a violated witness; out->kind says which.  Errors are for bad arguments only -- a null pointer, both or
+ *   neither witness pointer, rows + zk_rows > n, flags == 0 or an unknown flag, KH_WITNESS_WIRES without wires -- and leave *out untouched.
+ *   The report names the FIRST violation in the reference's order: every violation has the key row * 64 + sub, sub = 0..6 for a disconnected cell of
+ *   that column, 7 for the row's gate, and the lowest key is reported -- the lowest row, within a row the wires by column before the gate.
+ *     KH_WITNESS_DISCONNECTED (GateError::DisconnectedWires): (row, col) and the cell (wired_row, wired_col) it is wired to hold different values.
+ *     KH_WITNESS_GATE (GateError::Custom { row, .. }): gate = the kh_gate_name id of the row's gate, constraints = bit i set iff constraint i of that
+ *     row is not zero; constraint i is the one that carries alpha^i in the gate's combined expression (Argument::constraint_checks's order).
+ *     gate_rows_violated, cells_disconnected: how many rows have a violated gate / how many (row, column) cells are disconnected, over the whole circuit.
+ *   Not checked: lookups (kh_prove reports a looked-up value that is not in the table with its row), and the reference's index-side condition
+ *   IncorrectPublic (a public row that is not a Generic gate with coefficients 1, 0, 0, ...), a property of the gate list, not of the witness.
+ * kh_witness_report_message: the report as one line ("row 37: gate Poseidon, constraints 3, 4 of 15 are not zero (412 rows violated)", "row 12, column
+ *   0 is wired to (12, 4) but holds a different value (3 cells disconnected)", "the witness satisfies the circuit"), NUL-terminated and cut at cap;
+ *   returns the length of the whole line (as snprintf), or KH_E_INVALID. */
+#define KH_WITNESS_GATES 1
+#define KH_WITNESS_WIRES 2
+#define KH_WITNESS_OK 0
+#define KH_WITNESS_DISCONNECTED 1   /* GateError::DisconnectedWires */
+#define KH_WITNESS_GATE 2           /* GateError::Custom { row, .. } */
+typedef struct {
+    int kind;                 /* KH_WITNESS_* */
+    int gate;                 /* KH_WITNESS_GATE: kh_gate_name id of the row's gate */
+    uint32_t constraints;     /* KH_WITNESS_GATE: bit i = constraint i of that row is non-zero */
+    int col, wired_col;       /* KH_WITNESS_DISCONNECTED: the cell and the cell it is wired to */
+    size_t row, wired_row;
+    size_t gate_rows_violated, cells_disconnected;   /* over the whole circuit */
+} kh_witness_report_t;
+int kh_witness_check(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, unsigned flags,
+                     kh_witness_report_t *out);
+int kh_witness_report_message(const kh_witness_report_t *r, char *buf, size_t cap);
 int kh_proof_section(const kh_proof_t *proof, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
 int kh_proof_phase_seconds(const kh_proof_t *proof, double *seconds, size_t cap);   /* witness_upload, witness_commit, z, quotient, evaluations, opening */
 void kh_proof_free(kh_proof_t *proof);

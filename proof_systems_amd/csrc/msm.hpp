@@ -96,6 +96,12 @@ int gate_num_constants(int gate);
 int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* endo, const uint64_t* params, size_t nparams, uint64_t* out);
 int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, size_t len, const uint64_t* consts, size_t nconsts, size_t rows,
              unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
+// witness_check.hip: the gate constraints of every row one by one and the copy constraints (kh_witness_check).  scratch_dev: witness_check_scratch_bytes(),
+// whose first three 64-bit words end up as [lowest (row * 64 + sub) << 32 | detail, or ~0 | rows with a violated gate | disconnected cells]
+size_t witness_check_scratch_bytes();
+int witness_check_num_constraints(int gate);
+int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids,
+                      size_t public_inputs, const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, void* scratch_dev);
 int expr_run(Context& C, int field, const uint32_t* prog, size_t ntok, const uint64_t* const* cols_dev, const size_t* col_len, size_t ncols,
              const uint64_t* consts, size_t nconsts, size_t rows, unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
 // host_srs.cpp

@@ -32,6 +32,10 @@ int lookup_tables_dev(int field, const uint64_t* segs_dev, const uint64_t* seg_s
                       uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows);
 int lookup_atom_denominators_dev(int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4], uint64_t* atoms_dev);
 int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4], uint64_t* atoms_dev);
+// vector_api.cpp / witness_check.hip: the kernels of kh_witness_check and the read-back of their status words
+int witness_check_dev(int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids, size_t public_inputs,
+                      const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, uint64_t status[3]);
+int witness_check_num_constraints(int gate);         // of a gate id the check evaluates, else 0
 }
 
 namespace {
@@ -168,6 +172,7 @@ struct kh_prover_index {
     bool created = false;
     uint64_t *own_d1 = nullptr, *own_dc = nullptr, *own_d8 = nullptr;
     uint64_t *own_l1 = nullptr, *own_lc = nullptr, *own_l8 = nullptr;      // the lookup columns: d1, coefficient forms of the selectors, their d8 + the atoms
+    uint32_t* own_wires = nullptr; size_t n_gates = 0;                    // the gate list's wires, 7 (row, column) pairs per recorded row: kh_witness_check's copy constraints
     struct VSec { std::vector<uint64_t> limbs; std::vector<uint8_t> flags; size_t count = 0; };
     VSec vsec[KH_VINDEX_LOOKUP_INFO + 1];
     double phase[4] = {0, 0, 0, 0};
@@ -250,6 +255,7 @@ void kh_prover_index_free(kh_prover_index_t* ix) {
     if (!ix) return;
     if (ix->zero_poly) (void)kh_dev_free(ix->zero_poly);
     for (uint64_t* p : {ix->own_d1, ix->own_dc, ix->own_d8, ix->own_l1, ix->own_lc, ix->own_l8}) if (p) (void)kh_dev_free(p);
+    if (ix->own_wires) (void)kh_dev_free(ix->own_wires);
     delete ix->lk;
     delete ix;
 }
@@ -599,6 +605,8 @@ int index_build(const char* who, kh_srs_t* srs, size_t n_gates, const int* gate_
     ix->created = true;
     ix->own_d1 = d1.p; ix->own_dc = dc.p; ix->own_d8 = d8.p;
     d1.p = dc.p = d8.p = nullptr;
+    ix->own_wires = (uint32_t*)g_wires.p; ix->n_gates = n_gates;
+    g_wires.p = nullptr;
     auto points = [&](int s, const uint64_t* pxy, const uint8_t* pinf, size_t cnt) {
         ix->vsec[s].limbs.assign(pxy, pxy + 8 * cnt); ix->vsec[s].flags.assign(pinf, pinf + cnt); ix->vsec[s].count = cnt;
     };
@@ -691,6 +699,71 @@ int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, 
     if (!ix || !seconds) { kh::set_error("kh_prover_index_phase_seconds: null argument"); return KH_E_INVALID; }
     for (size_t i = 0; i < cap && i < 4; i++) seconds[i] = ix->phase[i];
     return 4;
+}
+
+// ProverIndex::verify (constraints.rs): the first row of the witness that violates its gate or a copy constraint.  Kernels in witness_check.hip.
+int kh_witness_check(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, unsigned flags, kh_witness_report_t* out) {
+    if (!ix || !out) { kh::set_error("kh_witness_check: null argument"); return KH_E_INVALID; }
+    if (!witness == !witness_dev) { kh::set_error("kh_witness_check: give the witness either on the host or on the device"); return KH_E_INVALID; }
+    if (!flags || (flags & ~(unsigned)(KH_WITNESS_GATES | KH_WITNESS_WIRES))) { kh::set_error("kh_witness_check: flags %u: KH_WITNESS_GATES, KH_WITNESS_WIRES or both", flags); return KH_E_INVALID; }
+    const size_t n = ix->n;
+    if (witness && (rows > n || rows + ix->zk > n)) { kh::set_error("kh_witness_check: %zu witness rows + %zu zero-knowledge rows do not fit the domain of %zu rows", rows, ix->zk, n); return KH_E_INVALID; }
+    if ((flags & KH_WITNESS_WIRES) && !ix->own_wires) {
+        kh::set_error("kh_witness_check: KH_WITNESS_WIRES needs the gate list's wires, which only an index from kh_prover_index_create(_lookup) keeps; this one comes from "
+                      "kh_prover_index_new (sigma columns only)");
+        return KH_E_INVALID;
+    }
+    struct DeviceRestore { int prev; ~DeviceRestore() { if (prev >= 0) (void)kh_set_device(prev); } } device_restore{kh_get_device()};
+    KP(kh_set_device(kh_srs_device(ix->srs)));
+    Dev wbuf;
+    if (witness) {                                   // padded with zeros: no zero-knowledge rows, no randomness
+        KP(wbuf.alloc(COLUMNS * n));
+        if (rows < n) KP(kh_dev_memset_zero(wbuf.p, COLUMNS * n * 32));
+        if (rows) KP(kh_dev_upload_2d(wbuf.p, n * 32, witness, rows * 32, rows * 32, COLUMNS));
+    }
+    // the selector column of every gate id: none = no launch.  Generic and the optional gates always, the library gates by live_mask
+    std::vector<int> sel_col((size_t)kh_gate_count(), -1);
+    if (flags & KH_WITNESS_GATES) {
+        sel_col[(size_t)ix->gid_generic] = (int)COLUMNS;
+        for (int k = 0; k < 5; k++) if (ix->live >> k & 1) sel_col[(size_t)ix->lib_gate[k]] = (int)SEL0 + k;
+        for (size_t j = 0; j < ix->optional.size(); j++) sel_col[(size_t)ix->optional[j]] = (int)(OPT0 + j);
+    }
+    uint64_t st[3] = {0, 0, 0};
+    KP(kh::witness_check_dev(ix->fid, witness ? wbuf.p : witness_dev, ix->d1, n, sel_col.data(), sel_col.size(), ix->pub, ix->endo.l,
+                             (flags & KH_WITNESS_WIRES) ? ix->own_wires : nullptr, ix->n_gates, st));
+    kh_witness_report_t r;
+    memset(&r, 0, sizeof(r));
+    r.gate = -1;
+    r.gate_rows_violated = (size_t)st[1]; r.cells_disconnected = (size_t)st[2];
+    if (st[0] != ~(uint64_t)0) {                     // (key << 32) | detail, key = row * 64 + sub (witness_check.hip)
+        const uint64_t key = st[0] >> 32; const uint32_t detail = (uint32_t)st[0];
+        r.row = (size_t)(key >> 6);
+        if ((key & 63) == 7) { r.kind = KH_WITNESS_GATE; r.gate = (int)(detail >> 24 & 15); r.constraints = detail & 0xffffffu; }
+        else { r.kind = KH_WITNESS_DISCONNECTED; r.col = (int)(key & 63); r.wired_col = (int)(detail >> 28 & 7); r.wired_row = (size_t)(detail & 0x0fffffffu); }
+    }
+    *out = r;
+    return KH_OK;
+}
+int kh_witness_report_message(const kh_witness_report_t* r, char* buf, size_t cap) {
+    if (!r || (!buf && cap)) { kh::set_error("kh_witness_report_message: null argument"); return KH_E_INVALID; }
+    char line[512];
+    int len = 0;
+    if (r->kind == KH_WITNESS_OK) len = snprintf(line, sizeof(line), "the witness satisfies the circuit");
+    else if (r->kind == KH_WITNESS_DISCONNECTED)
+        len = snprintf(line, sizeof(line), "row %zu, column %d is wired to (%zu, %d) but holds a different value (%zu cells disconnected)", r->row, r->col, r->wired_row, r->wired_col,
+                       r->cells_disconnected);
+    else if (r->kind == KH_WITNESS_GATE) {
+        const char* nm = kh_gate_name(r->gate);
+        char list[160]; size_t pos = 0; int total;
+        list[0] = 0;
+        for (int i = 0; i < 32; i++)
+            if (r->constraints >> i & 1) { const int k = snprintf(list + pos, sizeof(list) - pos, pos ? ", %d" : "%d", i); if (k > 0 && pos + (size_t)k < sizeof(list)) pos += (size_t)k; }
+        total = kh::witness_check_num_constraints(r->gate);
+        len = snprintf(line, sizeof(line), "row %zu: gate %s, constraint%s %s of %d %s not zero (%zu rows violated)", r->row, nm ? nm : "?", (r->constraints & (r->constraints - 1)) ? "s" : "",
+                       list, total, (r->constraints & (r->constraints - 1)) ? "are" : "is", r->gate_rows_violated);
+    } else { kh::set_error("kh_witness_report_message: unknown kind %d", r->kind); return KH_E_INVALID; }
+    if (cap) { snprintf(buf, cap, "%s", line); }
+    return len;
 }
 
 size_t kh_prove_randomness_count(const kh_prover_index_t* ix, int witness_on_host) {

@@ -41,6 +41,7 @@ SYMBOLS = [
     "kh_msm_allreduce",
     "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
     "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_create_lookup", "kh_debug_lookup_column", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
+    "kh_witness_check", "kh_witness_report_message",
     "kh_commit_non_hiding", "kh_commit_evaluations_non_hiding", "kh_srs_set_blinding_base",
     "kh_srs_get_blinding_base", "kh_mask_custom", "kh_domain_generator", "kh_msm_points_batch", "kh_msm_submit", "kh_msm_wait",
     "kh_ipa_fold_scalars", "kh_inner_product", "kh_ipa_fold_points", "kh_ipa_fold_points_endo", "kh_endos", "kh_scalar_challenge_to_field",
@@ -52,6 +53,12 @@ SYMBOLS = [
 class LookupTableC(C.Structure):
     """kh_lookup_table_t"""
     _fields_ = [("id", C.c_int), ("width", C.c_size_t), ("len", C.c_size_t), ("data", C.POINTER(C.c_uint64))]
+
+
+class WitnessReportC(C.Structure):
+    """kh_witness_report_t"""
+    _fields_ = [("kind", C.c_int), ("gate", C.c_int), ("constraints", C.c_uint32), ("col", C.c_int), ("wired_col", C.c_int), ("row", C.c_size_t), ("wired_row", C.c_size_t),
+                ("gate_rows_violated", C.c_size_t), ("cells_disconnected", C.c_size_t)]
 
 
 class RuntimeTableCfgC(C.Structure):
@@ -113,6 +120,8 @@ _lib.kh_permutation_shifts.argtypes = [C.c_int, C.c_uint, U64P]
 _lib.kh_prover_index_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(C.c_void_p)]
 _lib.kh_prover_index_create_lookup.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(LookupTableC), C.c_size_t,
                                                C.POINTER(RuntimeTableCfgC), C.c_size_t, C.POINTER(C.c_void_p)]
+_lib.kh_witness_check.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_void_p, C.c_uint, C.POINTER(WitnessReportC)]
+_lib.kh_witness_report_message.argtypes = [C.POINTER(WitnessReportC), C.c_char_p, C.c_size_t]
 _lib.kh_debug_lookup_column.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(U64P), C.POINTER(C.c_size_t)]
 _lib.kh_prover_index_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
 _lib.kh_verifier_index_section.argtypes = [C.c_void_p, C.c_int, C.POINTER(U64P), C.POINTER(U8P), C.POINTER(C.c_size_t)]
@@ -842,6 +851,27 @@ VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "
 LOOKUP_COLUMN_BLOCKS = {"selector_d1": 0, "selector_c": 1, "selector_d8": 2, "table_d1": 3, "table_ids_d1": 4, "atom_d8": 5, "runtime_selector": 6}
 LOOKUP_INFO_FIELDS = ("max_per_row", "max_joint_size", "joint_lookup_used", "uses_runtime_tables", "pattern_mask", "table_columns", "runtime_offset", "runtime_len")
 INDEX_PHASES = ("columns", "transforms", "commitments", "digest")
+WITNESS_GATES, WITNESS_WIRES = 1, 2                 # KH_WITNESS_*: flags of kh_witness_check
+WITNESS_OK, WITNESS_DISCONNECTED, WITNESS_GATE = 0, 1, 2
+
+
+def witness_report_message(report: "WitnessReportC", cap: int = 512) -> str:
+    """kh_witness_report_message: the report as one line, cut at cap - 1 characters."""
+    buf = C.create_string_buffer(max(cap, 1))
+    rc = _lib.kh_witness_report_message(C.byref(report), buf, C.c_size_t(cap))
+    if rc < 0:
+        _check(rc)
+    return buf.value.decode()
+
+
+def witness_check(index, witness=None, witness_dev=None, flags: int = WITNESS_GATES | WITNESS_WIRES) -> "WitnessReportC":
+    """kh_witness_check on a NativeProverIndex: witness (15, rows, 4) Montgomery limbs on the host, or witness_dev: a DevBuf with the padded 15 x n
+    columns.  Returns the filled kh_witness_report_t (kind WITNESS_OK / WITNESS_DISCONNECTED / WITNESS_GATE); bad arguments raise KhError."""
+    w = _c64(witness, (15, -1, 4)) if witness is not None else None
+    rep = WitnessReportC()
+    _check(_lib.kh_witness_check(index._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
+                                 C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, C.c_uint(flags), C.byref(rep)))
+    return rep
 
 
 class NativeProverIndex:
@@ -943,6 +973,10 @@ class NativeProverIndex:
     def attach_runtime_tables(self, sel_d1, sel_c, sel_d8, offset: int, length: int):
         _check(_lib.kh_prover_index_attach_runtime_tables(self._h, C.c_void_p(sel_d1.ptr), C.c_void_p(sel_c.ptr), C.c_void_p(sel_d8.ptr), C.c_size_t(offset), C.c_size_t(length)))
         self._keep += (sel_d1, sel_c, sel_d8)
+
+    def witness_check(self, witness=None, witness_dev=None, flags: int = WITNESS_GATES | WITNESS_WIRES):
+        """kh_witness_check (see witness_check)"""
+        return witness_check(self, witness, witness_dev, flags)
 
     def randomness_count(self, witness_on_host: bool) -> int:
         _lib.kh_prove_randomness_count.restype = C.c_size_t

@@ -423,6 +423,17 @@ def generic_expression(env: Env, alpha: int = 0):
     return env.column(30) * acc
 
 
+def generic_constraints(env: Env):
+    """The two constraints of the double generic gate as separate expressions, without alpha and selector (generic.rs:100-131):
+    c = q_l l + q_r r + q_o o + q_m l r + q_c on either half.  What the witness check (csrc/witness_check.hip) evaluates row by row."""
+    out = []
+    for g in range(2):
+        w = [env.witness_curr(3 * g + i) for i in range(3)]
+        c = [env.coeff(5 * g + i) for i in range(5)]
+        out.append(c[0] * w[0] + c[1] * w[1] + c[2] * w[2] + c[3] * w[0] * w[1] + c[4])
+    return out
+
+
 PERM_Z_COL, PERM_X_COL, PERM_ZKPM_COL = 22, 23, 24
 
 

@@ -62,6 +62,15 @@ struct LookupShape {
     max_per_row: usize,                 // sorted columns = max_per_row + 1
     runtime: Option<Vec<(i32, usize)>>, // (id, len) of the configured runtime tables, in order (runtime_tables.rs:15-20)
 }
+/// What `GpuProver::verify_witness` found: the two witness-side variants of the reference's `GateError` (gate.rs), with what the device adds --
+/// which constraints of the row are not zero (bit order of `Argument::constraint_checks`) and the counts over the whole circuit.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub enum WitnessError {
+    /// `GateError::DisconnectedWires`: `cell` = (row, column) holds another value than the cell it is wired to.
+    DisconnectedWires { cell: (usize, usize), wired_to: (usize, usize), cells_disconnected: usize },
+    /// `GateError::Custom { row, err }`: the row's gate has constraints that are not zero.
+    Custom { row: usize, gate: String, constraints: Vec<usize>, rows_violated: usize },
+}
 
 pub struct GpuProver<G: HipCurve> {
     index: *mut sys::kh_prover_index_t,
@@ -361,6 +370,34 @@ where
             present[k as usize] = true;
         }
         LookupShape { patterns: present, max_per_row: lcs.configuration.lookup_info.max_per_row, runtime }
+    }
+
+    /// `ProverIndex::verify` / `ConstraintSystem::verify` (constraints.rs) on the device (`kh_witness_check`): the gate constraints of every row,
+    /// each compared with zero exactly, and -- for an index built by `from_gates`, which keeps the gate list's wires -- the copy constraints.
+    /// The error is the FIRST violation in the reference's order (rows upwards; within a row the wires by column, then the gate).  Lookups are
+    /// not checked here, nor is the index-side condition `GateError::IncorrectPublic`.  Tens of microseconds of kernels: call it before
+    /// `create`, whose own check runs the whole proof and names no row.
+    pub fn verify_witness(&self, witness: &[Vec<G::ScalarField>; COLUMNS], wires: bool) -> Result<(), WitnessError> {
+        let rows = witness[0].len();
+        let flat: Vec<G::ScalarField> = witness.iter().flat_map(|c| c.iter().copied()).collect();
+        let flags = sys::KH_WITNESS_GATES as u32 | if wires { sys::KH_WITNESS_WIRES as u32 } else { 0 };
+        let mut r = core::mem::MaybeUninit::<sys::kh_witness_report_t>::zeroed();
+        ok(unsafe { sys::kh_witness_check(self.index, flat.as_ptr() as *const u64, rows, core::ptr::null(), flags, r.as_mut_ptr()) });
+        let r = unsafe { r.assume_init() };
+        match r.kind {
+            k if k == sys::KH_WITNESS_OK => Ok(()),
+            k if k == sys::KH_WITNESS_DISCONNECTED => Err(WitnessError::DisconnectedWires {
+                cell: (r.row, r.col as usize),
+                wired_to: (r.wired_row, r.wired_col as usize),
+                cells_disconnected: r.cells_disconnected,
+            }),
+            _ => Err(WitnessError::Custom {
+                row: r.row,
+                gate: unsafe { std::ffi::CStr::from_ptr(sys::kh_gate_name(r.gate)) }.to_string_lossy().into_owned(),
+                constraints: (0..32usize).filter(|&i| r.constraints >> i & 1 == 1).collect(),
+                rows_violated: r.gate_rows_violated,
+            }),
+        }
     }
 
     /// `ProverProof::create::<EFqSponge, EFrSponge, _>(group_map, witness, &[], index, rng)`.

@@ -9,6 +9,10 @@ the same expression DAGs proof_systems_amd/polish.py lowers to tokens (same buil
 sqr / sqr / mul / mul.  csrc/gates.hip wraps them in kernels (`kh_gate_evaluations_dev`).  The constants table a kernel reads is exactly
 `polish.gate_program(name, ...)[1]` (literals, MDS entries, the endo coefficient, powers of alpha), so the caller computes it as before.
 
+A second output, csrc/gates_check_gen.inc (render_check), holds the same gates' constraints ONE BY ONE for the witness check
+(csrc/witness_check.hip): `gate_check_<Name><F>(ctx)` returns a bit mask of the constraints of a row that are not zero -- no alpha, no selector
+product, constants = literals and the endo coefficient only; tests/test_witness_check_gen.py checks that it is current.
+
 Like the asm generators, the output is committed; tests/test_gates.py checks that it is current and tests/test_gpu_gates.py that the kernels
 equal the token machine and the oracle's row machines.  Usage: python tools/gen_gate_kernels.py [--check]"""
 import os
@@ -19,12 +23,14 @@ sys.path.insert(0, ROOT)
 from proof_systems_amd import polish as OP  # noqa: E402
 
 OUT = os.path.join(ROOT, "proof_systems_amd", "csrc", "gates_gen.inc")
+OUT_CHECK = os.path.join(ROOT, "proof_systems_amd", "csrc", "gates_check_gen.inc")
 P_FP = 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001
 P_FQ = 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001
 ALPHA = 0x1d2c3b4a59687796a5b4c3d2e1f00112233445566778899aabbccddeeff00123      # placeholder: only the LAYOUT of the constants table matters
 ENDO = 0x2d33357cb532458ed3552a23a8554e5005270d29d19fc7d27b7fd22f0201b547       # (any value different from every literal)
 RECIPES = {}
 GATE_IDS = list(OP.GATES) + list(OP.COMPILED_EXTRA)       # the library, then the two arguments every circuit has (generic, permutation)
+CHECK_IDS = list(OP.GATES) + ["Generic"]                  # the gates whose rows the witness check evaluates, in gate-id order
 
 
 def build(name, p, fid):
@@ -40,10 +46,8 @@ def build(name, p, fid):
     return env, expr, toks
 
 
-def emit(name):
-    env, expr, toks = build(name, P_FP, 0)
-    env_q, _, toks_q = build(name, P_FQ, 1)
-    assert toks == toks_q and len(env.consts) == len(env_q.consts), "the constants layout must not depend on the field"
+def lowering(env):
+    """(lines, go): go(node) appends the SSA statements of a node's sub-DAG to `lines` (shared sub-expressions once) and returns its variable"""
     lines, memo, counter = [], {}, [0]
 
     def var():
@@ -89,6 +93,14 @@ def emit(name):
             v = var(); lines.append("const Fe<F> %s = %s<F>(%s, %s);" % (v, f, a, b))
         memo[key] = v
         return v
+    return lines, go
+
+
+def emit(name):
+    env, expr, toks = build(name, P_FP, 0)
+    env_q, _, toks_q = build(name, P_FQ, 1)
+    assert toks == toks_q and len(env.consts) == len(env_q.consts), "the constants layout must not depend on the field"
+    lines, go = lowering(env)
     sys.setrecursionlimit(100000)
     root = go(expr)
     nmul = sum(1 for l in lines if "mul<F>" in l or "sqr<F>" in l)
@@ -135,9 +147,70 @@ def render():
     return "\n".join(out) + "\n"
 
 
+def check_constraints(name, p, fid):
+    """(env, the gate's constraints one by one): what build() combines with powers of alpha, before the combination"""
+    env = OP.Env(p, w0=0, c0=15, mds=OP.POSEIDON_MDS[fid], endo=ENDO)
+    if name == "Generic":
+        return env, OP.generic_constraints(env)
+    fn, count = OP.GATES[name]
+    cs = fn(env)
+    assert len(cs) == count
+    return env, cs
+
+
+def emit_check(name):
+    """gate_check_<Name>: bit i of the result = constraint i of the row is not zero.  Constraint i is compared as soon as its last node is there, so
+    that its value dies at once; sub-expressions shared between constraints are computed once, as in emit()."""
+    env, cs = check_constraints(name, P_FP, 0)
+    env_q, cs_q = check_constraints(name, P_FQ, 1)
+    lines, go = lowering(env)
+    lines_q, go_q = lowering(env_q)
+    sys.setrecursionlimit(100000)
+    for i, (c, cq) in enumerate(zip(cs, cs_q)):
+        for ls, v in ((lines, go(c)), (lines_q, go_q(cq))):
+            if name == "Generic" and i == 0:             # the public input of the row (zero past the public rows) belongs to the first constraint
+                ls.append("const Fe<F> pub = sub<F>(%s, g.public_input());" % v); v = "pub"
+            ls.append("m |= (%s.is_zero() ? 0u : 1u) << %d;" % (v, i))
+    assert lines == lines_q and len(env.consts) == len(env_q.consts), "the code and the constants layout must not depend on the field"
+    recipe = []
+    for a, b in zip(env.consts, env_q.consts):           # no alpha, no per-proof value: literals of the protocol (kind 0) and the endo coefficient (kind 2)
+        recipe.append((2, 0, 0, 0) if a == ENDO % P_FP and b == ENDO % P_FQ else (0, 0, a, b))
+    nmul = sum(1 for l in lines if "mul<F>" in l or "sqr<F>" in l)
+    body = "\n".join("    " + l for l in lines)
+    return ("// %s: %d constraints, %d products, %d constants\ntemplate <class F>\n__device__ __forceinline__ uint32_t gate_check_%s(const GateCtx<F>& g) {\n    uint32_t m = 0;\n%s\n    return m;\n}\n"
+            % (name, len(cs), nmul, len(env.consts), name, body)), len(cs), recipe
+
+
+def render_check():
+    out = ["// GENERATED by tools/gen_gate_kernels.py from proof_systems_amd/polish.py -- do not edit.",
+           "// One straight-line function per gate type a row can have: the row's constraints one by one, each compared with zero exactly (no alpha, no",
+           "// selector product); bit i of the result = constraint i is not zero, i as in polish.GATES / oracle/gates.py (the constraint that carries alpha^i).",
+           "// Column numbering as in gates_gen.inc: witness 0..14, coefficients 15..29.  Constants: literals of the protocol and the endo coefficient.", ""]
+    counts, recipes = [], {}
+    for name in CHECK_IDS:
+        src, n, recipes[name] = emit_check(name)
+        out.append(src); counts.append(n)
+    ids = [GATE_IDS.index(n) for n in CHECK_IDS]
+    out.append("#define KH_FOR_EACH_CHECKED_GATE(X) " + " ".join("X(%d, %s)" % (k, n) for k, n in zip(ids, CHECK_IDS)))
+    out.append("static constexpr int GATE_CHECK_COUNT = %d;" % len(CHECK_IDS))
+    out.append("static const char* const GATE_CHECK_NAMES[GATE_CHECK_COUNT] = {%s};" % ", ".join('"%s"' % n for n in CHECK_IDS))
+    out.append("static constexpr int GATE_CHECK_NCONSTRAINTS[GATE_CHECK_COUNT] = {%s};" % ", ".join(map(str, counts)))
+    out.append("static constexpr int GATE_CHECK_NCONST[GATE_CHECK_COUNT] = {%s};" % ", ".join(str(len(recipes[n])) for n in CHECK_IDS))
+    limbs = lambda v: ", ".join("0x%016xULL" % ((v >> (64 * i)) & 0xffffffffffffffff) for i in range(4))
+    out.append("struct GateConst { int kind, arg; unsigned long long lit[2][4]; };      // as in gates_gen.inc: kind 0 = a literal per field, 2 = the endo coefficient")
+    for name in CHECK_IDS:
+        rows = ["    {%d, %d, {{%s}, {%s}}}," % (k, a, limbs(x), limbs(y)) for k, a, x, y in recipes[name]] or ["    {0, 0, {{0, 0, 0, 0}, {0, 0, 0, 0}}},"]
+        out.append("static const GateConst GATE_CHECK_CONSTS_%s[] = {\n%s\n};" % (name, "\n".join(rows)))
+    out.append("static const GateConst* const GATE_CHECK_CONST_TABLE[GATE_CHECK_COUNT] = {%s};" % ", ".join("GATE_CHECK_CONSTS_" + n for n in CHECK_IDS))
+    return "\n".join(out) + "\n"
+
+
 if __name__ == "__main__":
     text = render()
     if "--check" in sys.argv:
         sys.exit(0 if os.path.exists(OUT) and open(OUT).read() == text else 1)
     open(OUT, "w").write(text)
     print("wrote", OUT, len(text.splitlines()), "lines")
+    text = render_check()
+    open(OUT_CHECK, "w").write(text)
+    print("wrote", OUT_CHECK, len(text.splitlines()), "lines")
