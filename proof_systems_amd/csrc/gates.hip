@@ -3,9 +3,11 @@
 // prover.rs:824-868 evaluates, for every gate type, index(gate) * sum_i alpha^i constraint_i over the d8 columns.  csrc/expr.hip can run any
 // such expression as a token program, but its operand stack and Store / Load slots live in LDS, which caps the Poseidon / VarBaseMul / EndoMulScalar
 // programs at one wave per SIMD (16-30 G products/s).  The gate library is protocol data fixed at build time, so tools/gen_gate_kernels.py lowers
-// the SAME expression DAGs (proof_systems_amd/polish.py) to straight-line functions (gates_gen.inc): every intermediate value a register-resident
-// field element, common sub-expressions once, no interpreter.  One kernel per (gate, field); thread per row; columns 0..14 = witness, 15..29 =
-// coefficients, 30 = the gate's selector; the constants table is the one polish.gate_program returns (literals, MDS, endo, powers of alpha).
+// the SAME expression DAGs (proof_systems_amd/polish.py) to straight-line functions (gates_gen.inc: gate_constraints_<Name>): every intermediate
+// value a register-resident field element, common sub-expressions once, no interpreter.  Those functions hand each finished constraint to a sink;
+// the one here (QuotientSink) sums multiplier_i * constraint_i, and the kernel multiplies by the selector -- csrc/witness_check.hip runs the same
+// functions with a sink that compares.  One kernel per (gate, field); thread per row; columns 0..14 = witness, 15..29 = coefficients, 30 = the
+// gate's selector; the constants table is the one polish.gate_program returns (literals, MDS, endo, powers of alpha).
 // Bound: VALU issue (products of 254 instructions), as everywhere in this library.
 #include "common.hpp"
 #include "field.cuh"
@@ -32,6 +34,26 @@ struct GateCtx {
 
 #include "gates_gen.inc"
 
+// acc = sum_i cst(SLOT[i]) * constraint_i: SLOT = the gate's GATE_MULT_SLOT, the table slots of alpha^i (of the two per-proof values for Generic)
+template <class F, const int* SLOT>
+struct QuotientSink {
+    const GateCtx<F>& g;
+    Fe<F> acc;
+    template <int I>
+    __device__ __forceinline__ void constraint(const Fe<F>& v) {
+        const Fe<F> t = mul<F>(g.cst(SLOT[I]), v);
+        if constexpr (I == 0) acc = t; else acc = add<F>(acc, t);
+    }
+};
+#define KH_GATE_VALUE(ID, NAME)                                                                               \
+    template <class F>                                                                                        \
+    __device__ __forceinline__ Fe<F> gate_##NAME(const GateCtx<F>& g) {                                       \
+        QuotientSink<F, GATE_MULT_SLOT_##NAME> s{g, {}};                                                      \
+        gate_constraints_##NAME<F>(g, s);                                                                     \
+        return mul<F>(g.cell(30, 0), s.acc);                                                                  \
+    }
+KH_FOR_EACH_CHECKED_GATE(KH_GATE_VALUE)
+
 #define KH_GATE_KERNEL(ID, NAME)                                                                              \
     template <class F>                                                                                        \
     __global__ void __launch_bounds__(128) k_gate_##NAME(GateArgs a) {                                        \
@@ -53,8 +75,9 @@ const char* gate_name(int gate) { return gate >= 0 && gate < GATE_COUNT ? GATE_N
 int gate_num_constants(int gate) { return gate >= 0 && gate < GATE_COUNT ? GATE_NCONST[gate] : -1; }
 
 // the constants table of one gate for one proof, on the host (gates_gen.inc: GATE_CONST_TABLE): literals of the protocol, powers of alpha, the endo
-// coefficient, the caller's per-proof values -- so that a caller needs no copy of the expression builder to drive kh_gate_evaluations_dev
-int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* endo, const uint64_t* params, size_t nparams, uint64_t* out) {
+// coefficient, the caller's per-proof values -- so that a caller needs no copy of the expression builder to drive kh_gate_evaluations_dev.
+// fixed_only: the literals and the endo coefficient alone, the other slots of `out` left as they are (all that the constraints themselves read)
+static int fill_constants(int field, int gate, bool fixed_only, const uint64_t* alpha, const uint64_t* endo, const uint64_t* params, size_t nparams, uint64_t* out) {
     KH_REQUIRE(gate >= 0 && gate < GATE_COUNT, "unknown gate id %d", gate);
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field %d", field);
     const khost::Fld F(field == KH_FIELD_FP ? 0 : 1);
@@ -62,6 +85,7 @@ int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* e
     khost::fe apow[64]; int have = 0;                     // alpha^1 .. alpha^have
     for (int k = 0; k < GATE_NCONST[gate]; k++) {
         khost::fe v;
+        if (fixed_only && rc[k].kind != 0 && rc[k].kind != 2) continue;
         switch (rc[k].kind) {
             case 0: { khost::fe c; for (int i = 0; i < 4; i++) c.l[i] = rc[k].lit[field == KH_FIELD_FP ? 0 : 1][i]; v = F.to_mont(c); break; }
             case 1: {
@@ -80,6 +104,10 @@ int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* e
     }
     return KH_OK;
 }
+int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* endo, const uint64_t* params, size_t nparams, uint64_t* out) {
+    return fill_constants(field, gate, false, alpha, endo, params, nparams, out);
+}
+int gate_fixed_constants(int field, int gate, const uint64_t* endo, uint64_t* out) { return fill_constants(field, gate, true, nullptr, endo, nullptr, 0, out); }
 
 #define g_gate_consts (kh::ctx().scratch("gate_consts"))
 

@@ -94,6 +94,7 @@ int gate_count();
 const char* gate_name(int gate);
 int gate_num_constants(int gate);
 int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* endo, const uint64_t* params, size_t nparams, uint64_t* out);
+int gate_fixed_constants(int field, int gate, const uint64_t* endo, uint64_t* out);      // the literal and endo slots of that table alone
 int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, size_t len, const uint64_t* consts, size_t nconsts, size_t rows,
              unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
 // witness_check.hip: the gate constraints of every row one by one and the copy constraints (kh_witness_check).  scratch_dev: witness_check_scratch_bytes(),

@@ -7,10 +7,10 @@
 //
 //   k_witness_gate_<Name>   one kernel per (gate type, field); thread per row, stride 1 over the d1 columns: witness 0..14, coefficients 15..29.  A wave
 //                           none of whose rows has the gate's selector set leaves after that one 32-byte load per lane -- a Kimchi row has ONE gate
-//                           type, so that is most waves of every kernel but one.  The live rows run gates_check_gen.inc's gate_check_<Name>
-//                           (tools/gen_gate_kernels.py: the constraints of polish.py one by one, shared sub-expressions once): bit i of the result =
-//                           constraint i is not zero.  `next` of row n - 1 is row 0.  Generic subtracts the row's public input, which is by
-//                           definition the witness's own cell w[0][r] for r < public_inputs, from its first constraint.
+//                           type, so that is most waves of every kernel but one.  The live rows run gates_gen.inc's gate_constraints_<Name>, the
+//                           same function the quotient kernels of csrc/gates.hip run, with a sink (CheckSink) that compares instead of summing:
+//                           bit i of the result = constraint i is not zero.  `next` of row n - 1 is row 0.  Generic subtracts the row's public
+//                           input, which is by definition the witness's own cell w[0][r] for r < public_inputs, from its first constraint.
 //   k_witness_wires         thread per (row, column < 7) of the n_gates recorded rows: the cell's 32 bytes against those of the cell it is wired to
 //                           (padding rows are wired to themselves and need no thread; nor does a recorded cell wired to itself).
 //
@@ -23,7 +23,6 @@
 #include "common.hpp"
 #include "field.cuh"
 #include "msm.hpp"
-#include "host_ec.hpp"
 
 namespace kh {
 
@@ -32,7 +31,7 @@ struct WitnessCheckArgs {
     const u64* w;                                        // 15 witness columns of n elements
     const u64* coeffs;                                   // the index's 15 coefficient columns (d1)
     const u64* sel;                                      // the gate's selector column (d1)
-    const u64* consts;                                   // the gate's constants (GATE_CHECK_CONST_TABLE), Montgomery limbs
+    const u64* consts;                                   // the gate's constants table (as kh_gate_constants lays it out; literals and endo filled in), Montgomery limbs
     u64* status;                                         // [0] the lowest (key << 32 | detail), [1] rows with a violated gate, [2] disconnected cells
     u32 n, pub, gate;
 };
@@ -48,7 +47,19 @@ struct GateCtx {
     __device__ __forceinline__ Fe<F> public_input() const { return r0 < a.pub ? Fe<F>::load(a.w + 4 * (size_t)r0) : Fe<F>::zero(); }
 };
 
-#include "gates_check_gen.inc"
+#include "gates_gen.inc"
+
+// bit i of m = constraint i is not zero.  GENERIC: the public input of the row (zero past the public rows) belongs to the first constraint
+template <class F, bool GENERIC>
+struct CheckSink {
+    const GateCtx<F>& g;
+    u32 m;
+    template <int I>
+    __device__ __forceinline__ void constraint(const Fe<F>& v) {
+        if constexpr (GENERIC && I == 0) m |= (sub<F>(v, g.public_input()).is_zero() ? 0u : 1u) << I;
+        else m |= (v.is_zero() ? 0u : 1u) << I;
+    }
+};
 
 constexpr u32 SUB_GATE = 7;
 constexpr int ST_WORD = 0, ST_GATE_ROWS = 1, ST_CELLS = 2;
@@ -76,12 +87,10 @@ __device__ __forceinline__ void report(u64* status, bool bad, u64 word, int coun
         const u32 i = blockIdx.x * 128 + threadIdx.x;                                                           \
         const bool live = i < a.n && !Fe<F>::load(a.sel + 4 * (size_t)i).is_zero();                             \
         if (!__ballot(live)) return;                                                                            \
-        u32 m = 0;                                                                                              \
-        if (live) {                                                                                             \
-            const GateCtx<F> g{a, i, i + 1 < a.n ? i + 1 : 0};                                                  \
-            m = gate_check_##NAME<F>(g);                                                                        \
-        }                                                                                                       \
-        report(a.status, m != 0, ((((u64)i << 6) | SUB_GATE) << 32) | ((u64)a.gate << 24) | m, ST_GATE_ROWS);   \
+        const GateCtx<F> g{a, i, i + 1 < a.n ? i + 1 : 0};                                                      \
+        CheckSink<F, ID == GATE_ID_GENERIC> s{g, 0};                                                            \
+        if (live) gate_constraints_##NAME<F>(g, s);                                                             \
+        report(a.status, s.m != 0, ((((u64)i << 6) | SUB_GATE) << 32) | ((u64)a.gate << 24) | s.m, ST_GATE_ROWS); \
     }
 KH_FOR_EACH_CHECKED_GATE(KH_WITNESS_GATE_KERNEL)
 
@@ -106,17 +115,13 @@ k_witness_wires(const u64* __restrict__ w, const u32* __restrict__ wires, u32 n,
 }
 }  // namespace
 
-// scratch: the status block (4 words of 64 bits; the caller reads the first three back) followed by one constants table of 32 elements per checked gate
-static constexpr size_t WC_STATUS_WORDS = 4, WC_CONST_SLOT = 32;
-size_t witness_check_scratch_bytes() { return WC_STATUS_WORDS * 8 + (size_t)GATE_CHECK_COUNT * WC_CONST_SLOT * 32; }
+// scratch: the status block (4 words of 64 bits; the caller reads the first three back) followed by the checked gates' constants tables, one after
+// the other: wc_const_words(gate) = the 64-bit words before that gate's table
+static constexpr size_t WC_STATUS_WORDS = 4;
+static constexpr size_t wc_const_words(int gate) { size_t n = WC_STATUS_WORDS; for (int k = 0; k < gate; k++) n += 4 * (size_t)GATE_NCONST[k]; return n; }
+size_t witness_check_scratch_bytes() { return 8 * wc_const_words(GATE_CHECKED_COUNT); }
 
-int witness_check_num_constraints(int gate) {
-    int k = 0;
-#define KH_WITNESS_GATE_COUNT(ID, NAME) if (gate == ID) return GATE_CHECK_NCONSTRAINTS[k]; k++;
-    KH_FOR_EACH_CHECKED_GATE(KH_WITNESS_GATE_COUNT)
-#undef KH_WITNESS_GATE_COUNT
-    return 0;
-}
+int witness_check_num_constraints(int gate) { return gate >= 0 && gate < GATE_CHECKED_COUNT ? GATE_NCONSTRAINTS[gate] : 0; }
 
 // sel_col[gate id] = the d1 column of that gate's selector, or -1: no launch (a gate type the circuit has no rows of).  wires_dev may be NULL (no
 // wiring check).  Queues everything on C.stream; the status block is then [lowest word or ~0 | rows with a violated gate | disconnected cells].
@@ -124,24 +129,13 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
                       size_t public_inputs, const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, void* scratch_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field %d", field);
     KH_REQUIRE(witness_dev && d1_dev && sel_col && endo && scratch_dev && n >= 2 && n <= ((size_t)1 << 26) && n_gates <= n, "witness_check_run: bad argument");
-    static_assert(GATE_CHECK_COUNT <= 16, "the gate id takes four bits of the status word");
-    const int fi = field == KH_FIELD_FP ? 0 : 1;
-    const khost::Fld F(fi);
-    // one upload: the cleared status block and every gate's constants
+    static_assert(GATE_CHECKED_COUNT <= 16, "the gate id takes four bits of the status word");
+    // one upload: the cleared status block and every gate's constants (the multiplier slots, which the sink here never reads, stay zero)
     std::vector<uint64_t> host(witness_check_scratch_bytes() / 8, 0);
     host[ST_WORD] = ~0ull;
-    for (int k = 0; k < GATE_CHECK_COUNT; k++) {
-        static_assert(sizeof(khost::fe) == 32, "limbs");
-        KH_REQUIRE(GATE_CHECK_NCONST[k] <= (int)WC_CONST_SLOT, "constants of %s do not fit their slot", GATE_CHECK_NAMES[k]);
-        for (int j = 0; j < GATE_CHECK_NCONST[k]; j++) {
-            const GateConst& rc = GATE_CHECK_CONST_TABLE[k][j];
-            khost::fe v;
-            if (rc.kind == 2) memcpy(&v, endo, 32);
-            else { khost::fe c; for (int i = 0; i < 4; i++) c.l[i] = rc.lit[fi][i]; v = F.to_mont(c); }
-            memcpy(&host[WC_STATUS_WORDS + 4 * ((size_t)k * WC_CONST_SLOT + j)], &v, 32);
-        }
-    }
     int rc;
+    for (int k = 0; k < GATE_CHECKED_COUNT; k++)
+        if ((rc = gate_fixed_constants(field, k, endo, &host[wc_const_words(k)]))) return rc;
     if ((rc = C.stage_upload(scratch_dev, {{host.data(), host.size() * 8}}))) return rc;
     u64* const status = (u64*)scratch_dev;
     WitnessCheckArgs a{};
@@ -149,15 +143,13 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
     hipStream_t s = C.stream;
     const dim3 grid((unsigned)((n + 127) / 128));
     C.timer.begin(s);
-    int k = 0;
 #define KH_WITNESS_GATE_LAUNCH(ID, NAME)                                                                                          \
     if ((size_t)ID < ngate_ids && sel_col[ID] >= 0) {                                                                             \
-        a.sel = d1_dev + 4 * (size_t)sel_col[ID] * n; a.consts = status + WC_STATUS_WORDS + 4 * (size_t)k * WC_CONST_SLOT; a.gate = ID;  \
+        a.sel = d1_dev + 4 * (size_t)sel_col[ID] * n; a.consts = status + wc_const_words(ID); a.gate = ID;                      \
         if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_witness_gate_##NAME<FpParams>), grid, dim3(128), 0, s, a);                \
         else hipLaunchKernelGGL((k_witness_gate_##NAME<FqParams>), grid, dim3(128), 0, s, a);                                     \
         C.timer.mark("check_" #NAME, s);                                                                                          \
-    }                                                                                                                             \
-    k++;
+    }
     KH_FOR_EACH_CHECKED_GATE(KH_WITNESS_GATE_LAUNCH)
 #undef KH_WITNESS_GATE_LAUNCH
     if (wires_dev && n_gates) {

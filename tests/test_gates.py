@@ -170,13 +170,60 @@ def test_every_constrained_cell_matters(name):
         assert any(vals), (name, c)
 
 
+GATES_GEN = os.path.join(ROOT, "proof_systems_amd", "csrc", "gates_gen.inc")
+
+
 def test_generated_gate_kernels_are_current():
     """csrc/gates_gen.inc is the output of tools/gen_gate_kernels.py for the expressions of proof_systems_amd/polish.py as they are now."""
-    import os
     import subprocess
     import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert subprocess.run([sys.executable, os.path.join(root, "tools", "gen_gate_kernels.py"), "--check"], cwd=root).returncode == 0
+    assert subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_gate_kernels.py"), "--check"], cwd=ROOT).returncode == 0
+
+
+def test_the_committed_file_is_what_render_returns():
+    """The same in process: render() is the one output there is, and the committed file is it, byte for byte."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_gate_kernels as GK
+    assert open(GATES_GEN).read() == GK.render()
+    assert not os.path.exists(os.path.join(os.path.dirname(GATES_GEN), "gates_check_gen.inc")) and not hasattr(GK, "render_check")
+
+
+def test_every_gate_declares_its_constraints():
+    """One generated body per gate serves the quotient and the witness check: it hands exactly the gate's constraints, in order, to its sink."""
+    import re
+    src = open(GATES_GEN).read()
+    want = {name: count for name, (_fn, count) in OP.GATES.items()}
+    assert want == G.ROW_MACHINES
+    want["Generic"] = 2
+    checked = list(OP.GATES) + ["Generic"]
+    declared = {m.group(1): int(m.group(2)) for m in re.finditer(r"^// (\w+): (\d+) constraints", src, flags=re.M)}
+    assert declared == dict(want, Permutation=1)
+    for name, count in want.items():
+        body = src[src.index("void gate_constraints_%s(" % name):]
+        body = body[:body.index("\n}\n")]
+        assert re.findall(r"s\.template constraint<(\d+)>\(", body) == [str(i) for i in range(count)], name      # one call per constraint, in order
+        assert "g.cell(30" not in body                                # no selector in the body: the quotient kernel's business
+    assert "gate_constraints_Permutation" not in src
+    counts = re.search(r"GATE_NCONSTRAINTS\[GATE_COUNT\] = \{([^}]*)\}", src).group(1)
+    assert [int(x) for x in counts.split(",")] == [want[n] for n in checked] + [1]
+    listed = re.search(r"^#define KH_FOR_EACH_CHECKED_GATE\(X\) (.*)$", src, flags=re.M).group(1)
+    assert re.findall(r"X\((\d+), (\w+)\)", listed) == [(str(k), n) for k, n in enumerate(checked)]
+    # the check path: no alpha, no per-proof value -- the constants its bodies read are literals (kind 0) and the endo coefficient (kind 2) only
+    for name in checked:
+        body = src[src.index("void gate_constraints_%s(" % name):]
+        read = {int(k) for k in re.findall(r"g\.cst\((\d+)\)", body[:body.index("\n}\n")])}
+        table = src[src.index("GATE_CONSTS_%s[] = {" % name):]
+        kinds = re.findall(r"^    \{(\d), ", table[:table.index("\n};")], flags=re.M)
+        assert {kinds[k] for k in read} <= {"0", "2"}, name
+
+
+def test_the_constants_layout_is_the_one_callers_know():
+    """GATE_NCONST and the GATE_CONSTS_<Name> recipes (what kh_gate_constants builds, = polish.gate_program(name, ...)[1]) are, to the letter, the block
+    the generator emitted before the constraint bodies were shared with the witness check (tests/golden/gate_constants_layout.txt)."""
+    golden = open(os.path.join(ROOT, "tests", "golden", "gate_constants_layout.txt")).read()
+    assert golden.startswith("static constexpr int GATE_NCONST[") and golden.count("GATE_CONSTS_") == 2 * 13
+    assert golden in open(GATES_GEN).read()
 
 
 def test_compiled_expressions_keep_the_constants_layout():

@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Generates proof_systems_amd/csrc/gates_gen.inc: the gate library's combined constraints as STRAIGHT-LINE device code.
+"""Generates proof_systems_amd/csrc/gates_gen.inc: the gate library's constraints as STRAIGHT-LINE device code.
 
 The token machine of csrc/expr.hip runs any caller-supplied expression, but its operand stack and Store / Load slots live in LDS (4 KB per slot
 per block): the Poseidon program needs ~20 slots, which leaves one wave per SIMD and 27 G products/s of the 139 G/s the product allows
 (tools/gate_expr_time.py).  The gate library is fixed protocol data, so its expressions are compiled ahead of time instead: this script builds
 the same expression DAGs proof_systems_amd/polish.py lowers to tokens (same builder functions, same constants table), and emits one
-`gate_<Name><F>(ctx)` function per gate in SSA form -- every node a register-resident Fe<F>, shared sub-expressions computed once, x^7 as
-sqr / sqr / mul / mul.  csrc/gates.hip wraps them in kernels (`kh_gate_evaluations_dev`).  The constants table a kernel reads is exactly
-`polish.gate_program(name, ...)[1]` (literals, MDS entries, the endo coefficient, powers of alpha), so the caller computes it as before.
-
-A second output, csrc/gates_check_gen.inc (render_check), holds the same gates' constraints ONE BY ONE for the witness check
-(csrc/witness_check.hip): `gate_check_<Name><F>(ctx)` returns a bit mask of the constraints of a row that are not zero -- no alpha, no selector
-product, constants = literals and the endo coefficient only; tests/test_witness_check_gen.py checks that it is current.
+`gate_constraints_<Name><F>(ctx, sink)` per gate in SSA form -- every node a register-resident Fe<F>, shared sub-expressions computed once, x^7 as
+sqr / sqr / mul / mul -- which hands constraint i to `sink.constraint<i>(value)` as soon as its last node is there.  The body holds no selector
+and no multiplier: csrc/gates.hip's sink sums cst(GATE_MULT_SLOT_<Name>[i]) * constraint_i and multiplies by the selector (`kh_gate_evaluations_dev`),
+csrc/witness_check.hip's compares each constraint with zero (`kh_witness_check`).  The constants table both read is laid out from the COMBINED
+expression, exactly as `polish.gate_program(name, ...)[1]` (literals, MDS entries, the endo coefficient, powers of alpha), so the caller computes it
+as before; the check fills in the literals and the endo coefficient only.  Permutation is one expression nobody checks row by row: `gate_Permutation`
+returns its value.
 
 Like the asm generators, the output is committed; tests/test_gates.py checks that it is current and tests/test_gpu_gates.py that the kernels
 equal the token machine and the oracle's row machines.  Usage: python tools/gen_gate_kernels.py [--check]"""
@@ -23,7 +23,6 @@ sys.path.insert(0, ROOT)
 from proof_systems_amd import polish as OP  # noqa: E402
 
 OUT = os.path.join(ROOT, "proof_systems_amd", "csrc", "gates_gen.inc")
-OUT_CHECK = os.path.join(ROOT, "proof_systems_amd", "csrc", "gates_check_gen.inc")
 P_FP = 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001
 P_FQ = 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001
 ALPHA = 0x1d2c3b4a59687796a5b4c3d2e1f00112233445566778899aabbccddeeff00123      # placeholder: only the LAYOUT of the constants table matters
@@ -96,13 +95,33 @@ def lowering(env):
     return lines, go
 
 
+def constraints(expr):
+    """The combined expression taken apart again: selector * ((m_0 * c_0 + m_1 * c_1) + ...) -> [(constants slot of the multiplier m_i, c_i)].  The
+    c_i are the very nodes compile_tokens walked, so the bodies below number their constants as the caller's table does."""
+    assert expr.op == OP.TOK_MUL and (expr.a.op, expr.a.arg) == (OP.TOK_CELL, 2 * 30)
+    terms, acc = [], expr.b
+    while acc.op == OP.TOK_ADD:
+        terms.append(acc.b); acc = acc.a
+    terms = [acc] + terms[::-1]
+    assert all(t.op == OP.TOK_MUL and t.a.op == OP.TOK_CONST for t in terms)
+    return [(t.a.arg, t.b) for t in terms]
+
+
 def emit(name):
     env, expr, toks = build(name, P_FP, 0)
     env_q, _, toks_q = build(name, P_FQ, 1)
-    assert toks == toks_q and len(env.consts) == len(env_q.consts), "the constants layout must not depend on the field"
+    assert toks == toks_q and len(env.consts) == len(env_q.consts), "the code and the constants layout must not depend on the field"
     lines, go = lowering(env)
     sys.setrecursionlimit(100000)
-    root = go(expr)
+    if name == "Permutation":                            # one expression, never checked row by row: the value itself
+        count, slots = 1, None
+        lines.append("return %s;" % go(expr))
+    else:                                                # constraint i goes to the sink as soon as its last node is there, so that its value dies at once
+        cs = constraints(expr)
+        count, slots = len(cs), [slot for slot, _ in cs]
+        assert count == (OP.GATES[name][1] if name in OP.GATES else 2)
+        for i, (_, c) in enumerate(cs):
+            lines.append("s.template constraint<%d>(%s);" % (i, go(c)))
     nmul = sum(1 for l in lines if "mul<F>" in l or "sqr<F>" in l)
     body = "\n".join("    " + l for l in lines)
     recipe = []
@@ -120,21 +139,33 @@ def emit(name):
         else:
             recipe.append((0, 0, a, b))
     RECIPES[name] = recipe
-    return ("// %s: %d constraints, %d products, %d constants\ntemplate <class F>\n__device__ __forceinline__ Fe<F> gate_%s(const GateCtx<F>& g) {\n%s\n    return %s;\n}\n"
-            % (name, OP.GATES[name][1] if name in OP.GATES else {"Generic": 2, "Permutation": 1}[name], nmul, len(env.consts), name, body, root)), len(env.consts)
+    src = "// %s: %d constraints, %d products, %d constants\n" % (name, count, nmul, len(env.consts))
+    if slots is None:
+        src += "template <class F, class G>\n__device__ __forceinline__ Fe<F> gate_%s(const G& g) {\n%s\n}\n" % (name, body)
+    else:
+        src += "template <class F, class G, class Sink>\n__device__ __forceinline__ void gate_constraints_%s(const G& g, Sink& s) {\n%s\n}\n" % (name, body)
+        src += "static constexpr int GATE_MULT_SLOT_%s[%d] = {%s};\n" % (name, count, ", ".join(map(str, slots)))
+    return src, count, len(env.consts)
 
 
 def render():
     out = ["// GENERATED by tools/gen_gate_kernels.py from proof_systems_amd/polish.py -- do not edit.",
-           "// One straight-line function per gate of the library: index(gate) * sum_i alpha^i constraint_i on one row (column numbering: witness 0..14,",
-           "// coefficients 15..29, the gate's selector 30; constants table = polish.gate_program(name, ...)[1]).", ""]
-    counts = []
+           "// One straight-line function per gate of the library: the constraints of one row, each handed to the sink `s` as s.constraint<i>(value), i as in",
+           "// polish.GATES / oracle/gates.py (the constraint that carries alpha^i).  What becomes of a constraint is the sink's business: gates.hip sums",
+           "// cst(GATE_MULT_SLOT_<Name>[i]) * constraint_i for the quotient, witness_check.hip compares each with zero.  `g` gives the cells (column numbering:",
+           "// witness 0..14, coefficients 15..29) and the constants (g.cst(k): slot k of the table polish.gate_program(name, ...)[1] lays out).", ""]
+    counts, nconstraints = [], []
     for name in GATE_IDS:
-        src, nc = emit(name)
-        out.append(src); counts.append(nc)
-    out.append("#define KH_FOR_EACH_GATE(X) " + " ".join("X(%d, %s)" % (k, n) for k, n in enumerate(GATE_IDS)))
-    out.append("static constexpr int GATE_COUNT = %d;" % len(GATE_IDS))
+        src, n, nc = emit(name)
+        out.append(src); nconstraints.append(n); counts.append(nc)
+    assert GATE_IDS[:len(CHECK_IDS)] == CHECK_IDS
+    gates = ["X(%d, %s)" % (k, n) for k, n in enumerate(GATE_IDS)]
+    out.append("// the gates with a gate_constraints_<Name>, which are those the witness check evaluates: ids 0 .. GATE_CHECKED_COUNT - 1")
+    out.append("#define KH_FOR_EACH_CHECKED_GATE(X) " + " ".join(gates[:len(CHECK_IDS)]))
+    out.append("#define KH_FOR_EACH_GATE(X) KH_FOR_EACH_CHECKED_GATE(X) " + " ".join(gates[len(CHECK_IDS):]))
+    out.append("static constexpr int GATE_COUNT = %d, GATE_CHECKED_COUNT = %d, GATE_ID_GENERIC = %d;" % (len(GATE_IDS), len(CHECK_IDS), GATE_IDS.index("Generic")))
     out.append("static const char* const GATE_NAMES[GATE_COUNT] = {%s};" % ", ".join('"%s"' % n for n in GATE_IDS))
+    out.append("static constexpr int GATE_NCONSTRAINTS[GATE_COUNT] = {%s};" % ", ".join(map(str, nconstraints)))
     out.append("static constexpr int GATE_NCONST[GATE_COUNT] = {%s};" % ", ".join(map(str, counts)))
     # how the caller's constants table is made (kh_gate_constants): kind 0 = a literal of the protocol (canonical value per field: small integers, 2^k,
     # the Poseidon MDS), 1 = alpha^arg, 2 = the endo coefficient, 3 = the caller's arg-th per-proof value (challenges)
@@ -147,70 +178,9 @@ def render():
     return "\n".join(out) + "\n"
 
 
-def check_constraints(name, p, fid):
-    """(env, the gate's constraints one by one): what build() combines with powers of alpha, before the combination"""
-    env = OP.Env(p, w0=0, c0=15, mds=OP.POSEIDON_MDS[fid], endo=ENDO)
-    if name == "Generic":
-        return env, OP.generic_constraints(env)
-    fn, count = OP.GATES[name]
-    cs = fn(env)
-    assert len(cs) == count
-    return env, cs
-
-
-def emit_check(name):
-    """gate_check_<Name>: bit i of the result = constraint i of the row is not zero.  Constraint i is compared as soon as its last node is there, so
-    that its value dies at once; sub-expressions shared between constraints are computed once, as in emit()."""
-    env, cs = check_constraints(name, P_FP, 0)
-    env_q, cs_q = check_constraints(name, P_FQ, 1)
-    lines, go = lowering(env)
-    lines_q, go_q = lowering(env_q)
-    sys.setrecursionlimit(100000)
-    for i, (c, cq) in enumerate(zip(cs, cs_q)):
-        for ls, v in ((lines, go(c)), (lines_q, go_q(cq))):
-            if name == "Generic" and i == 0:             # the public input of the row (zero past the public rows) belongs to the first constraint
-                ls.append("const Fe<F> pub = sub<F>(%s, g.public_input());" % v); v = "pub"
-            ls.append("m |= (%s.is_zero() ? 0u : 1u) << %d;" % (v, i))
-    assert lines == lines_q and len(env.consts) == len(env_q.consts), "the code and the constants layout must not depend on the field"
-    recipe = []
-    for a, b in zip(env.consts, env_q.consts):           # no alpha, no per-proof value: literals of the protocol (kind 0) and the endo coefficient (kind 2)
-        recipe.append((2, 0, 0, 0) if a == ENDO % P_FP and b == ENDO % P_FQ else (0, 0, a, b))
-    nmul = sum(1 for l in lines if "mul<F>" in l or "sqr<F>" in l)
-    body = "\n".join("    " + l for l in lines)
-    return ("// %s: %d constraints, %d products, %d constants\ntemplate <class F>\n__device__ __forceinline__ uint32_t gate_check_%s(const GateCtx<F>& g) {\n    uint32_t m = 0;\n%s\n    return m;\n}\n"
-            % (name, len(cs), nmul, len(env.consts), name, body)), len(cs), recipe
-
-
-def render_check():
-    out = ["// GENERATED by tools/gen_gate_kernels.py from proof_systems_amd/polish.py -- do not edit.",
-           "// One straight-line function per gate type a row can have: the row's constraints one by one, each compared with zero exactly (no alpha, no",
-           "// selector product); bit i of the result = constraint i is not zero, i as in polish.GATES / oracle/gates.py (the constraint that carries alpha^i).",
-           "// Column numbering as in gates_gen.inc: witness 0..14, coefficients 15..29.  Constants: literals of the protocol and the endo coefficient.", ""]
-    counts, recipes = [], {}
-    for name in CHECK_IDS:
-        src, n, recipes[name] = emit_check(name)
-        out.append(src); counts.append(n)
-    ids = [GATE_IDS.index(n) for n in CHECK_IDS]
-    out.append("#define KH_FOR_EACH_CHECKED_GATE(X) " + " ".join("X(%d, %s)" % (k, n) for k, n in zip(ids, CHECK_IDS)))
-    out.append("static constexpr int GATE_CHECK_COUNT = %d;" % len(CHECK_IDS))
-    out.append("static const char* const GATE_CHECK_NAMES[GATE_CHECK_COUNT] = {%s};" % ", ".join('"%s"' % n for n in CHECK_IDS))
-    out.append("static constexpr int GATE_CHECK_NCONSTRAINTS[GATE_CHECK_COUNT] = {%s};" % ", ".join(map(str, counts)))
-    out.append("static constexpr int GATE_CHECK_NCONST[GATE_CHECK_COUNT] = {%s};" % ", ".join(str(len(recipes[n])) for n in CHECK_IDS))
-    limbs = lambda v: ", ".join("0x%016xULL" % ((v >> (64 * i)) & 0xffffffffffffffff) for i in range(4))
-    out.append("struct GateConst { int kind, arg; unsigned long long lit[2][4]; };      // as in gates_gen.inc: kind 0 = a literal per field, 2 = the endo coefficient")
-    for name in CHECK_IDS:
-        rows = ["    {%d, %d, {{%s}, {%s}}}," % (k, a, limbs(x), limbs(y)) for k, a, x, y in recipes[name]] or ["    {0, 0, {{0, 0, 0, 0}, {0, 0, 0, 0}}},"]
-        out.append("static const GateConst GATE_CHECK_CONSTS_%s[] = {\n%s\n};" % (name, "\n".join(rows)))
-    out.append("static const GateConst* const GATE_CHECK_CONST_TABLE[GATE_CHECK_COUNT] = {%s};" % ", ".join("GATE_CHECK_CONSTS_" + n for n in CHECK_IDS))
-    return "\n".join(out) + "\n"
-
-
 if __name__ == "__main__":
     text = render()
     if "--check" in sys.argv:
         sys.exit(0 if os.path.exists(OUT) and open(OUT).read() == text else 1)
     open(OUT, "w").write(text)
     print("wrote", OUT, len(text.splitlines()), "lines")
-    text = render_check()
-    open(OUT_CHECK, "w").write(text)
-    print("wrote", OUT_CHECK, len(text.splitlines()), "lines")
