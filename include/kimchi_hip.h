@@ -733,16 +733,45 @@ int kh_prove_full(kh_prover_index_t *index, const uint64_t *witness, size_t rows
  *     KH_WITNESS_GATE (GateError::Custom { row, .. }): gate = the kh_gate_name id of the row's gate, constraints = bit i set iff constraint i of that
  *     row is not zero; constraint i is the one that carries alpha^i in the gate's combined expression (Argument::constraint_checks's order).
  *     gate_rows_violated, cells_disconnected: how many rows have a violated gate / how many (row, column) cells are disconnected, over the whole circuit.
- *   Not checked: lookups (kh_prove reports a looked-up value that is not in the table with its row), and the reference's index-side condition
- *   IncorrectPublic (a public row that is not a Generic gate with coefficients 1, 0, 0, ...), a property of the gate list, not of the witness.
+ *   Not checked: the reference's index-side condition IncorrectPublic (a public row that is not a Generic gate with coefficients 1, 0, 0, ...), a
+ *   property of the gate list, not of the witness.  Lookups are checked by kh_witness_check_full with KH_WITNESS_LOOKUPS (kh_witness_check refuses
+ *   that flag):
+ * kh_witness_check_full: kh_witness_check + the lookups.  With KH_WITNESS_GATES / KH_WITNESS_WIRES alone it is kh_witness_check (the runtime arguments
+ *   are not read; lookup_out, if given, gets an empty record).  KH_WITNESS_LOOKUPS -- exact, without a joint combiner:
+ *     The table is a set of tuples.  With L = n - zk_rows - 1, every row t < L of the index's combined table gives (id_t, c_0[t], .., c_{W-1}[t]): its W
+ *     columns on the domain and the table-id column, id_t = 0 when the index has no id column.  On the runtime rows column 1 is the call's
+ *     runtime_values (all runtime tables' second columns concatenated in the index's order, as for kh_prove_full; the fixed second column is zero there).
+ *     Only rows r < L are checked.  For every lookup-pattern selector that is 1 on row r (the `next` rows of RangeCheck1 / ForeignFieldMul are in
+ *     the selector columns), each joint lookup s of the pattern (LookupPattern::lookups, lookups.rs:417-487) gives the tuple (id, w[cells[0]][r], ..,
+ *     w[cells[ncell - 1]][r], 0, .., 0) padded with zeros to W entries, id = the pattern's constant table id or w[0][r] (Lookup), and that tuple must
+ *     equal a table tuple in all W + 1 components (compared as 32-byte strings: canonical Montgomery limbs are unique).
+ *     This is the statement the lookup constraints enforce, and it is strictly tighter than the sorted step of kh_prove in one case: when the index
+ *     has no table-id column the prover multiplies the looked-up id by 0, so a Lookup row whose w[0] names a table that does not exist passes there;
+ *     here it is reported.  Rows with fewer lookups than max_per_row and the dummy entry are properties of the index and are not checked.
+ *     A miss has the key row * 64 + 8 + s, after the wires (0..6) and the gate (7) of its row: the report is the lowest key over everything that was
+ *     asked for, kind KH_WITNESS_LOOKUP with out->row set (kh_prove names the first miss in slot-major order instead, under its random combiner).
+ *     lookup_out is always filled: lookups_missing = the (row, pattern, joint lookup) triples over the whole circuit whose tuple is in no table; for kind
+ *     KH_WITNESS_LOOKUP also the pattern, the joint lookup, its witness columns and what the row looked up (read back from the witness at that row);
+ *     otherwise pattern = slot = -1 and the rest is zero.
+ *     Works on created and on attached indexes.  KH_E_INVALID with a message, *out and *lookup_out untouched: kh_witness_check's refusals, and with
+ *     KH_WITNESS_LOOKUPS an index without a lookup index, lookup_out NULL, n_runtime different from the index's runtime rows (or runtime_values NULL
+ *     with runtime rows), runtime values given for an index without runtime tables, a runtime value >= p.
+ * kh_witness_lookup_message: report + lookup record as one line, "row 37: lookup 2 of pattern RangeCheck (column 5), table id 1: the value is not in
+ *   the table (3 lookups missing)" ("columns 1, 2", "1 lookup missing"); for every other kind the line of kh_witness_report_message.  The record does
+ *   not say which field its limbs belong to, so the table id is printed by a heuristic: the limbs are taken out of Montgomery form under Fp, then Fq, and
+ *   the first result below 2^32 is the id (a table id is a small number; the other field's reading is a 255-bit value except by a 2^-220 accident);
+ *   if neither is, the limbs are printed in hexadecimal.  NUL-terminated and cut at cap; returns the length of the whole line.
  * kh_witness_report_message: the report as one line ("row 37: gate Poseidon, constraints 3, 4 of 15 are not zero (412 rows violated)", "row 12, column
- *   0 is wired to (12, 4) but holds a different value (3 cells disconnected)", "the witness satisfies the circuit"), NUL-terminated and cut at cap;
+ *   0 is wired to (12, 4) but holds a different value (3 cells disconnected)", "the witness satisfies the circuit"; for KH_WITNESS_LOOKUP the short
+ *   "row 37: a looked-up value is in no table (kh_witness_lookup_message names it)"), NUL-terminated and cut at cap;
  *   returns the length of the whole line (as snprintf), or KH_E_INVALID. */
 #define KH_WITNESS_GATES 1
 #define KH_WITNESS_WIRES 2
+#define KH_WITNESS_LOOKUPS 4        /* kh_witness_check_full only */
 #define KH_WITNESS_OK 0
 #define KH_WITNESS_DISCONNECTED 1   /* GateError::DisconnectedWires */
 #define KH_WITNESS_GATE 2           /* GateError::Custom { row, .. } */
+#define KH_WITNESS_LOOKUP 3         /* report kind: a looked-up tuple is in no table */
 typedef struct {
     int kind;                 /* KH_WITNESS_* */
     int gate;                 /* KH_WITNESS_GATE: kh_gate_name id of the row's gate */
@@ -754,6 +783,16 @@ typedef struct {
 int kh_witness_check(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, unsigned flags,
                      kh_witness_report_t *out);
 int kh_witness_report_message(const kh_witness_report_t *r, char *buf, size_t cap);
+typedef struct {
+    int pattern, slot, ncells;       /* 0 Xor, 1 Lookup, 2 RangeCheck, 3 ForeignFieldMul; joint lookup 0..3 of the row; 1..3 */
+    int cols[3];                     /* the witness columns of the tuple */
+    uint64_t table_id[4], entry[3][4];   /* Montgomery limbs of what the row looked up */
+    size_t lookups_missing;          /* over the whole circuit */
+} kh_witness_lookup_t;
+int kh_witness_check_full(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev,
+                          const uint64_t *runtime_values, size_t n_runtime, unsigned flags, kh_witness_report_t *out,
+                          kh_witness_lookup_t *lookup_out);
+int kh_witness_lookup_message(const kh_witness_report_t *r, const kh_witness_lookup_t *l, char *buf, size_t cap);
 int kh_proof_section(const kh_proof_t *proof, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
 int kh_proof_phase_seconds(const kh_proof_t *proof, double *seconds, size_t cap);   /* witness_upload, witness_commit, z, quotient, evaluations, opening */
 void kh_proof_free(kh_proof_t *proof);

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "host_ec.hpp"
+#include "witness_lookup.hpp"
 
 namespace kh {
 
@@ -97,12 +98,14 @@ int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* e
 int gate_fixed_constants(int field, int gate, const uint64_t* endo, uint64_t* out);      // the literal and endo slots of that table alone
 int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, size_t len, const uint64_t* consts, size_t nconsts, size_t rows,
              unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
-// witness_check.hip: the gate constraints of every row one by one and the copy constraints (kh_witness_check).  scratch_dev: witness_check_scratch_bytes(),
-// whose first three 64-bit words end up as [lowest (row * 64 + sub) << 32 | detail, or ~0 | rows with a violated gate | disconnected cells]
+// witness_check.hip: the gate constraints of every row one by one, the copy constraints and (lk != NULL) the lookups (kh_witness_check,
+// kh_witness_check_full).  scratch_dev: witness_check_scratch_bytes() (+ witness_check_lookup_scratch_bytes with lookups), whose first four 64-bit words
+// end up as [lowest (row * 64 + sub) << 32 | detail, or ~0 | rows with a violated gate | disconnected cells | lookups that are in no table]
 size_t witness_check_scratch_bytes();
+size_t witness_check_lookup_scratch_bytes(size_t L, size_t W, size_t rt_len);
 int witness_check_num_constraints(int gate);
 int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids,
-                      size_t public_inputs, const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, void* scratch_dev);
+                      size_t public_inputs, const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, const WitnessLookups* lk, void* scratch_dev);
 int expr_run(Context& C, int field, const uint32_t* prog, size_t ntok, const uint64_t* const* cols_dev, const size_t* col_len, size_t ncols,
              const uint64_t* consts, size_t nconsts, size_t rows, unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
 // host_srs.cpp

@@ -21,6 +21,7 @@
 
 #include "../../include/kimchi_hip.h"
 #include "host_ec.hpp"
+#include "witness_lookup.hpp"
 
 namespace kh {
 void set_error(const char* fmt, ...);
@@ -32,9 +33,9 @@ int lookup_tables_dev(int field, const uint64_t* segs_dev, const uint64_t* seg_s
                       uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows);
 int lookup_atom_denominators_dev(int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4], uint64_t* atoms_dev);
 int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4], uint64_t* atoms_dev);
-// vector_api.cpp / witness_check.hip: the kernels of kh_witness_check and the read-back of their status words
+// vector_api.cpp / witness_check.hip: the kernels of kh_witness_check(_full) and the read-back of their status words
 int witness_check_dev(int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids, size_t public_inputs,
-                      const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, uint64_t status[3]);
+                      const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, const WitnessLookups* lk, uint64_t status[4]);
 int witness_check_num_constraints(int gate);         // of a gate id the check evaluates, else 0
 }
 
@@ -87,6 +88,7 @@ int os_random(int fid, size_t k, fe* out) {          // uniform elements of the 
 // witness columns of the entry.  Pattern ids: 0 Xor, 1 Lookup, 2 RangeCheck, 3 ForeignFieldMul (the reference's order).
 struct JointLookup { int tid_is_column, tid, ncell, cells[3]; };
 struct Pattern { int n; JointLookup l[4]; };
+const char* const PATTERN_NAMES[4] = {"Xor", "Lookup", "RangeCheck", "ForeignFieldMul"};
 const Pattern PATTERNS[4] = {
     {4, {{0, 0, 3, {3, 7, 11}}, {0, 0, 3, {4, 8, 12}}, {0, 0, 3, {5, 9, 13}}, {0, 0, 3, {6, 10, 14}}}},
     {3, {{1, 0, 2, {1, 2, 0}}, {1, 0, 2, {3, 4, 0}}, {1, 0, 2, {5, 6, 0}}, {0, 0, 0, {0, 0, 0}}}},
@@ -701,17 +703,53 @@ int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, 
     return 4;
 }
 
-// ProverIndex::verify (constraints.rs): the first row of the witness that violates its gate or a copy constraint.  Kernels in witness_check.hip.
-int kh_witness_check(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, unsigned flags, kh_witness_report_t* out) {
-    if (!ix || !out) { kh::set_error("kh_witness_check: null argument"); return KH_E_INVALID; }
-    if (!witness == !witness_dev) { kh::set_error("kh_witness_check: give the witness either on the host or on the device"); return KH_E_INVALID; }
-    if (!flags || (flags & ~(unsigned)(KH_WITNESS_GATES | KH_WITNESS_WIRES))) { kh::set_error("kh_witness_check: flags %u: KH_WITNESS_GATES, KH_WITNESS_WIRES or both", flags); return KH_E_INVALID; }
-    const size_t n = ix->n;
-    if (witness && (rows > n || rows + ix->zk > n)) { kh::set_error("kh_witness_check: %zu witness rows + %zu zero-knowledge rows do not fit the domain of %zu rows", rows, ix->zk, n); return KH_E_INVALID; }
-    if ((flags & KH_WITNESS_WIRES) && !ix->own_wires) {
-        kh::set_error("kh_witness_check: KH_WITNESS_WIRES needs the gate list's wires, which only an index from kh_prover_index_create(_lookup) keeps; this one comes from "
-                      "kh_prover_index_new (sigma columns only)");
+// ProverIndex::verify (constraints.rs): the first row of the witness that violates its gate or a copy constraint -- or, kh_witness_check_full with
+// KH_WITNESS_LOOKUPS, looks up a tuple that is in no table.  Kernels in witness_check.hip.  `allowed`: the flags the entry point `who` takes.
+static int witness_check_impl(const char* who, unsigned allowed, kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev,
+                              const uint64_t* runtime_values, size_t n_runtime, unsigned flags, kh_witness_report_t* out, kh_witness_lookup_t* lookup_out) {
+    if (!ix || !out) { kh::set_error("%s: null argument", who); return KH_E_INVALID; }
+    if (!witness == !witness_dev) { kh::set_error("%s: give the witness either on the host or on the device", who); return KH_E_INVALID; }
+    if (!flags || (flags & ~allowed)) {
+        kh::set_error(allowed & KH_WITNESS_LOOKUPS ? "%s: flags %u: a combination of KH_WITNESS_GATES, KH_WITNESS_WIRES and KH_WITNESS_LOOKUPS" : "%s: flags %u: KH_WITNESS_GATES, KH_WITNESS_WIRES or both", who, flags);
         return KH_E_INVALID;
+    }
+    const size_t n = ix->n;
+    if (witness && (rows > n || rows + ix->zk > n)) { kh::set_error("%s: %zu witness rows + %zu zero-knowledge rows do not fit the domain of %zu rows", who, rows, ix->zk, n); return KH_E_INVALID; }
+    if ((flags & KH_WITNESS_WIRES) && !ix->own_wires) {
+        kh::set_error("%s: KH_WITNESS_WIRES needs the gate list's wires, which only an index from kh_prover_index_create(_lookup) keeps; this one comes from "
+                      "kh_prover_index_new (sigma columns only)", who);
+        return KH_E_INVALID;
+    }
+    const khost::Fld F(ix->fid);
+    const kh_lookup_index* lk = ix->lk;
+    kh::WitnessLookups wl{};
+    if (flags & KH_WITNESS_LOOKUPS) {
+        if (!lk) { kh::set_error("%s: KH_WITNESS_LOOKUPS on an index without a lookup index (kh_prover_index_create_lookup, or kh_prover_index_attach_lookup)", who); return KH_E_INVALID; }
+        if (!lookup_out) { kh::set_error("%s: KH_WITNESS_LOOKUPS needs lookup_out", who); return KH_E_INVALID; }
+        const size_t rt_len = lk->rtsel1 ? lk->rt_len : 0;
+        if (!rt_len && (runtime_values || n_runtime)) { kh::set_error("%s: runtime values for an index without runtime tables", who); return KH_E_INVALID; }
+        if (n_runtime != rt_len || (rt_len && !runtime_values)) {
+            kh::set_error("%s: RuntimeTablesInconsistent: the index has %zu runtime table rows, the call brings %zu", who, rt_len, runtime_values ? n_runtime : (size_t)0);
+            return KH_E_INVALID;
+        }
+        for (size_t i = 0; i < rt_len; i++)
+            if (khost::geq(load(runtime_values + 4 * i), F.f.p)) { kh::set_error("%s: runtime value %zu is not below the field's modulus", who, i); return KH_E_INVALID; }
+        if (n <= ix->zk + 1 || lk->tcols.empty() || lk->pats.empty()) { kh::set_error("%s: the lookup index is empty", who); return KH_E_INVALID; }
+        wl.npat = lk->pats.size();
+        for (size_t k = 0; k < wl.npat; k++) {
+            const Pattern& P = PATTERNS[lk->pats[k]];
+            kh::WitnessLookupPattern& q = wl.pat[k];
+            q.pattern = lk->pats[k]; q.n = P.n; q.sel = lk->sel1[k];
+            for (int i = 0; i < P.n; i++) {
+                const JointLookup& J = P.l[i];
+                q.l[i].tid_is_column = J.tid_is_column; q.l[i].tid_column = J.tid_is_column ? J.tid : 0; q.l[i].ncell = J.ncell;
+                for (int c = 0; c < 3; c++) q.l[i].cells[c] = J.cells[c];
+                const fe id = J.tid_is_column ? fe{{0, 0, 0, 0}} : F.to_mont(fe{{(uint64_t)J.tid, 0, 0, 0}});
+                memcpy(q.l[i].id, id.l, 32);
+            }
+        }
+        wl.L = n - ix->zk - 1; wl.W = lk->tcols.size(); wl.tcols = lk->tcols.data(); wl.tids = lk->tids;
+        wl.rt_offset = rt_len ? lk->rt_offset : 0; wl.rt_len = rt_len; wl.runtime = rt_len ? runtime_values : nullptr;
     }
     struct DeviceRestore { int prev; ~DeviceRestore() { if (prev >= 0) (void)kh_set_device(prev); } } device_restore{kh_get_device()};
     KP(kh_set_device(kh_srs_device(ix->srs)));
@@ -728,21 +766,48 @@ int kh_witness_check(kh_prover_index_t* ix, const uint64_t* witness, size_t rows
         for (int k = 0; k < 5; k++) if (ix->live >> k & 1) sel_col[(size_t)ix->lib_gate[k]] = (int)SEL0 + k;
         for (size_t j = 0; j < ix->optional.size(); j++) sel_col[(size_t)ix->optional[j]] = (int)(OPT0 + j);
     }
-    uint64_t st[3] = {0, 0, 0};
+    uint64_t st[4] = {0, 0, 0, 0};
     KP(kh::witness_check_dev(ix->fid, witness ? wbuf.p : witness_dev, ix->d1, n, sel_col.data(), sel_col.size(), ix->pub, ix->endo.l,
-                             (flags & KH_WITNESS_WIRES) ? ix->own_wires : nullptr, ix->n_gates, st));
+                             (flags & KH_WITNESS_WIRES) ? ix->own_wires : nullptr, ix->n_gates, (flags & KH_WITNESS_LOOKUPS) ? &wl : nullptr, st));
     kh_witness_report_t r;
     memset(&r, 0, sizeof(r));
     r.gate = -1;
     r.gate_rows_violated = (size_t)st[1]; r.cells_disconnected = (size_t)st[2];
+    kh_witness_lookup_t l;
+    memset(&l, 0, sizeof(l));
+    l.pattern = -1; l.slot = -1;
+    l.lookups_missing = (size_t)st[3];
     if (st[0] != ~(uint64_t)0) {                     // (key << 32) | detail, key = row * 64 + sub (witness_check.hip)
         const uint64_t key = st[0] >> 32; const uint32_t detail = (uint32_t)st[0];
         r.row = (size_t)(key >> 6);
-        if ((key & 63) == 7) { r.kind = KH_WITNESS_GATE; r.gate = (int)(detail >> 24 & 15); r.constraints = detail & 0xffffffu; }
+        if ((key & 63) >= 8) {                       // the tuple the row looked up: read back from the witness, a few cells
+            r.kind = KH_WITNESS_LOOKUP;
+            l.pattern = (int)(detail & 3); l.slot = (int)(key & 63) - 8;
+            KP_REQUIRE(l.slot < PATTERNS[l.pattern].n, "%s: status word names lookup %d of pattern %d", who, l.slot, l.pattern);
+            const JointLookup& J = PATTERNS[l.pattern].l[l.slot];
+            auto cell = [&](int c, uint64_t* dst) -> int {
+                if (witness_dev) return kh_dev_download(dst, witness_dev + 4 * ((size_t)c * n + r.row), 32);
+                if (r.row < rows) memcpy(dst, witness + 4 * ((size_t)c * rows + r.row), 32); else memset(dst, 0, 32);
+                return KH_OK;
+            };
+            l.ncells = J.ncell;
+            for (int c = 0; c < J.ncell; c++) { l.cols[c] = J.cells[c]; KP(cell(J.cells[c], l.entry[c])); }
+            if (J.tid_is_column) KP(cell(J.tid, l.table_id));
+            else { const fe id = F.to_mont(fe{{(uint64_t)J.tid, 0, 0, 0}}); memcpy(l.table_id, id.l, 32); }
+        } else if ((key & 63) == 7) { r.kind = KH_WITNESS_GATE; r.gate = (int)(detail >> 24 & 15); r.constraints = detail & 0xffffffu; }
         else { r.kind = KH_WITNESS_DISCONNECTED; r.col = (int)(key & 63); r.wired_col = (int)(detail >> 28 & 7); r.wired_row = (size_t)(detail & 0x0fffffffu); }
     }
     *out = r;
+    if (lookup_out) *lookup_out = l;
     return KH_OK;
+}
+int kh_witness_check(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, unsigned flags, kh_witness_report_t* out) {
+    return witness_check_impl("kh_witness_check", KH_WITNESS_GATES | KH_WITNESS_WIRES, ix, witness, rows, witness_dev, nullptr, 0, flags, out, nullptr);
+}
+int kh_witness_check_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* runtime_values, size_t n_runtime,
+                          unsigned flags, kh_witness_report_t* out, kh_witness_lookup_t* lookup_out) {
+    return witness_check_impl("kh_witness_check_full", KH_WITNESS_GATES | KH_WITNESS_WIRES | KH_WITNESS_LOOKUPS, ix, witness, rows, witness_dev, runtime_values, n_runtime,
+                              flags, out, lookup_out);
 }
 int kh_witness_report_message(const kh_witness_report_t* r, char* buf, size_t cap) {
     if (!r || (!buf && cap)) { kh::set_error("kh_witness_report_message: null argument"); return KH_E_INVALID; }
@@ -761,7 +826,30 @@ int kh_witness_report_message(const kh_witness_report_t* r, char* buf, size_t ca
         total = kh::witness_check_num_constraints(r->gate);
         len = snprintf(line, sizeof(line), "row %zu: gate %s, constraint%s %s of %d %s not zero (%zu rows violated)", r->row, nm ? nm : "?", (r->constraints & (r->constraints - 1)) ? "s" : "",
                        list, total, (r->constraints & (r->constraints - 1)) ? "are" : "is", r->gate_rows_violated);
-    } else { kh::set_error("kh_witness_report_message: unknown kind %d", r->kind); return KH_E_INVALID; }
+    } else if (r->kind == KH_WITNESS_LOOKUP) len = snprintf(line, sizeof(line), "row %zu: a looked-up value is in no table (kh_witness_lookup_message names it)", r->row);
+    else { kh::set_error("kh_witness_report_message: unknown kind %d", r->kind); return KH_E_INVALID; }
+    if (cap) { snprintf(buf, cap, "%s", line); }
+    return len;
+}
+int kh_witness_lookup_message(const kh_witness_report_t* r, const kh_witness_lookup_t* l, char* buf, size_t cap) {
+    if (!r || !l || (!buf && cap)) { kh::set_error("kh_witness_lookup_message: null argument"); return KH_E_INVALID; }
+    if (r->kind != KH_WITNESS_LOOKUP) return kh_witness_report_message(r, buf, cap);
+    if (l->pattern < 0 || l->pattern > 3 || l->slot < 0 || l->slot > 3 || l->ncells < 0 || l->ncells > 3) { kh::set_error("kh_witness_lookup_message: the lookup record names no lookup"); return KH_E_INVALID; }
+    // the id as a number: the record does not say which field its limbs belong to, and a table id is small -- the field under which it is below 2^32
+    char id[96];
+    id[0] = 0;
+    for (int fid = 0; fid < 2 && !id[0]; fid++) {
+        const fe v = khost::Fld(fid).from_mont(load(l->table_id));
+        if (!(v.l[1] | v.l[2] | v.l[3]) && v.l[0] < ((uint64_t)1 << 32)) snprintf(id, sizeof(id), "%llu", (unsigned long long)v.l[0]);
+    }
+    if (!id[0]) snprintf(id, sizeof(id), "0x%016llx%016llx%016llx%016llx (Montgomery limbs)", (unsigned long long)l->table_id[3], (unsigned long long)l->table_id[2],
+                         (unsigned long long)l->table_id[1], (unsigned long long)l->table_id[0]);
+    char cols[48]; size_t pos = 0;
+    cols[0] = 0;
+    for (int c = 0; c < l->ncells; c++) { const int k = snprintf(cols + pos, sizeof(cols) - pos, pos ? ", %d" : "%d", l->cols[c]); if (k > 0 && pos + (size_t)k < sizeof(cols)) pos += (size_t)k; }
+    char line[512];
+    const int len = snprintf(line, sizeof(line), "row %zu: lookup %d of pattern %s (column%s %s), table id %s: the value is not in the table (%zu lookup%s missing)", r->row, l->slot,
+                             PATTERN_NAMES[l->pattern], l->ncells == 1 ? "" : "s", cols, id, l->lookups_missing, l->lookups_missing == 1 ? "" : "s");
     if (cap) { snprintf(buf, cap, "%s", line); }
     return len;
 }

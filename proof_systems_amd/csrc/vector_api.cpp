@@ -427,20 +427,20 @@ int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t z
 }
 #undef KH_LOOKUP_STEP
 // the kernels of kh_witness_check (csrc/prover.cpp; witness_check.hip).  The scratch block comes from the kh_dev_alloc pool, taken before the context's lock like
-// kh_lookup_sorted_dev's; the read-back of the three status words, outside the lock, is the call's only wait.
+// kh_lookup_sorted_dev's; the read-back of the four status words, outside the lock, is the call's only wait.  lookups: what to check of them, or NULL.
 int witness_check_dev(int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids, size_t public_inputs,
-                      const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, uint64_t status[3]) {
+                      const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, const WitnessLookups* lookups, uint64_t status[4]) {
     KH_REQUIRE(status, "witness_check_dev: null argument");
     int rc = ensure_init(); if (rc) return rc;
     struct Scratch { void* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } scratch;
-    if ((rc = kh_dev_alloc(&scratch.p, witness_check_scratch_bytes()))) return rc;
+    if ((rc = kh_dev_alloc(&scratch.p, witness_check_scratch_bytes() + (lookups ? witness_check_lookup_scratch_bytes(lookups->L, lookups->W, lookups->rt_len) : 0)))) return rc;
     {
         Context& C = ctx();
         std::lock_guard<std::mutex> lk(C.mu);
-        rc = witness_check_run(C, field, witness_dev, d1_dev, n, sel_col, ngate_ids, public_inputs, endo, wires_dev, n_gates, scratch.p);
+        rc = witness_check_run(C, field, witness_dev, d1_dev, n, sel_col, ngate_ids, public_inputs, endo, wires_dev, n_gates, lookups, scratch.p);
         C.mark_async();
         if (rc) return rc;
     }
-    return kh_dev_download(status, scratch.p, 3 * sizeof(uint64_t));
+    return kh_dev_download(status, scratch.p, 4 * sizeof(uint64_t));
 }
 }  // namespace kh

@@ -41,7 +41,7 @@ SYMBOLS = [
     "kh_msm_allreduce",
     "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
     "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_create_lookup", "kh_debug_lookup_column", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
-    "kh_witness_check", "kh_witness_report_message",
+    "kh_witness_check", "kh_witness_report_message", "kh_witness_check_full", "kh_witness_lookup_message",
     "kh_commit_non_hiding", "kh_commit_evaluations_non_hiding", "kh_srs_set_blinding_base",
     "kh_srs_get_blinding_base", "kh_mask_custom", "kh_domain_generator", "kh_msm_points_batch", "kh_msm_submit", "kh_msm_wait",
     "kh_ipa_fold_scalars", "kh_inner_product", "kh_ipa_fold_points", "kh_ipa_fold_points_endo", "kh_endos", "kh_scalar_challenge_to_field",
@@ -59,6 +59,12 @@ class WitnessReportC(C.Structure):
     """kh_witness_report_t"""
     _fields_ = [("kind", C.c_int), ("gate", C.c_int), ("constraints", C.c_uint32), ("col", C.c_int), ("wired_col", C.c_int), ("row", C.c_size_t), ("wired_row", C.c_size_t),
                 ("gate_rows_violated", C.c_size_t), ("cells_disconnected", C.c_size_t)]
+
+
+class WitnessLookupC(C.Structure):
+    """kh_witness_lookup_t"""
+    _fields_ = [("pattern", C.c_int), ("slot", C.c_int), ("ncells", C.c_int), ("cols", C.c_int * 3), ("table_id", C.c_uint64 * 4), ("entry", (C.c_uint64 * 4) * 3),
+                ("lookups_missing", C.c_size_t)]
 
 
 class RuntimeTableCfgC(C.Structure):
@@ -122,6 +128,8 @@ _lib.kh_prover_index_create_lookup.argtypes = [C.c_void_p, C.c_size_t, C.POINTER
                                                C.POINTER(RuntimeTableCfgC), C.c_size_t, C.POINTER(C.c_void_p)]
 _lib.kh_witness_check.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_void_p, C.c_uint, C.POINTER(WitnessReportC)]
 _lib.kh_witness_report_message.argtypes = [C.POINTER(WitnessReportC), C.c_char_p, C.c_size_t]
+_lib.kh_witness_check_full.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_void_p, U64P, C.c_size_t, C.c_uint, C.POINTER(WitnessReportC), C.POINTER(WitnessLookupC)]
+_lib.kh_witness_lookup_message.argtypes = [C.POINTER(WitnessReportC), C.POINTER(WitnessLookupC), C.c_char_p, C.c_size_t]
 _lib.kh_debug_lookup_column.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(U64P), C.POINTER(C.c_size_t)]
 _lib.kh_prover_index_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
 _lib.kh_verifier_index_section.argtypes = [C.c_void_p, C.c_int, C.POINTER(U64P), C.POINTER(U8P), C.POINTER(C.c_size_t)]
@@ -851,8 +859,8 @@ VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "
 LOOKUP_COLUMN_BLOCKS = {"selector_d1": 0, "selector_c": 1, "selector_d8": 2, "table_d1": 3, "table_ids_d1": 4, "atom_d8": 5, "runtime_selector": 6}
 LOOKUP_INFO_FIELDS = ("max_per_row", "max_joint_size", "joint_lookup_used", "uses_runtime_tables", "pattern_mask", "table_columns", "runtime_offset", "runtime_len")
 INDEX_PHASES = ("columns", "transforms", "commitments", "digest")
-WITNESS_GATES, WITNESS_WIRES = 1, 2                 # KH_WITNESS_*: flags of kh_witness_check
-WITNESS_OK, WITNESS_DISCONNECTED, WITNESS_GATE = 0, 1, 2
+WITNESS_GATES, WITNESS_WIRES, WITNESS_LOOKUPS = 1, 2, 4      # KH_WITNESS_*: flags of kh_witness_check (the first two) and kh_witness_check_full
+WITNESS_OK, WITNESS_DISCONNECTED, WITNESS_GATE, WITNESS_LOOKUP = 0, 1, 2, 3
 
 
 def witness_report_message(report: "WitnessReportC", cap: int = 512) -> str:
@@ -872,6 +880,27 @@ def witness_check(index, witness=None, witness_dev=None, flags: int = WITNESS_GA
     _check(_lib.kh_witness_check(index._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
                                  C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, C.c_uint(flags), C.byref(rep)))
     return rep
+
+
+def witness_check_full(index, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS):
+    """kh_witness_check_full on a NativeProverIndex: as witness_check, + the lookups (WITNESS_LOOKUPS; runtime: (k, 4) limbs, the runtime tables' second
+    column, as for prove).  Returns (kh_witness_report_t, kh_witness_lookup_t), both filled; bad arguments raise KhError."""
+    w = _c64(witness, (15, -1, 4)) if witness is not None else None
+    rtv = _c64(runtime, (-1, 4)) if runtime is not None else None
+    rep, lk = WitnessReportC(), WitnessLookupC()
+    _check(_lib.kh_witness_check_full(index._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
+                                      C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rtv) if rtv is not None else None,
+                                      C.c_size_t(rtv.shape[0] if rtv is not None else 0), C.c_uint(flags), C.byref(rep), C.byref(lk)))
+    return rep, lk
+
+
+def witness_lookup_message(report: "WitnessReportC", lookup: "WitnessLookupC", cap: int = 512) -> str:
+    """kh_witness_lookup_message: report and lookup record as one line, cut at cap - 1 characters."""
+    buf = C.create_string_buffer(max(cap, 1))
+    rc = _lib.kh_witness_lookup_message(C.byref(report), C.byref(lookup), buf, C.c_size_t(cap))
+    if rc < 0:
+        _check(rc)
+    return buf.value.decode()
 
 
 class NativeProverIndex:
@@ -977,6 +1006,10 @@ class NativeProverIndex:
     def witness_check(self, witness=None, witness_dev=None, flags: int = WITNESS_GATES | WITNESS_WIRES):
         """kh_witness_check (see witness_check)"""
         return witness_check(self, witness, witness_dev, flags)
+
+    def witness_check_full(self, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS):
+        """kh_witness_check_full (see witness_check_full)"""
+        return witness_check_full(self, witness, witness_dev, runtime, flags)
 
     def randomness_count(self, witness_on_host: bool) -> int:
         _lib.kh_prove_randomness_count.restype = C.c_size_t

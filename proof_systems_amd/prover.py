@@ -306,9 +306,9 @@ class ProverIndex:
                      [LI.selector_comm[q] for q in LI.patterns])
         khip.sync()
 
-    def check_witness(self, witness=None, witness_on_device=None) -> "WitnessReport":
-        """kh_witness_check, the gates only: this index holds sigma columns, not the gate list's wires (see check_witness)"""
-        return check_witness(self, witness, witness_on_device, True, False)
+    def check_witness(self, witness=None, witness_on_device=None, lookups: bool = False, runtime=None) -> "WitnessReport":
+        """kh_witness_check(_full), the gates (and the lookups) only: this index holds sigma columns, not the gate list's wires (see check_witness)"""
+        return check_witness(self, witness, witness_on_device, True, False, lookups, runtime)
 
     def free_lookup(self):
         """Releases the attached lookup index: what attach_lookup allocated (coefficient forms and d8 of the selectors, the atoms) and the LookupIndex's own columns."""
@@ -406,38 +406,52 @@ class CreatedIndex:
         if vi["lookup_info"] is not None:
             self.lookup = CreatedLookup(vi, nch, runtime_tables or ())
 
-    def check_witness(self, witness=None, witness_on_device=None, gates: bool = True, wires: bool = True) -> "WitnessReport":
-        """kh_witness_check: gates and copy constraints (see check_witness)"""
-        return check_witness(self, witness, witness_on_device, gates, wires)
+    def check_witness(self, witness=None, witness_on_device=None, gates: bool = True, wires: bool = True, lookups: bool = False, runtime=None) -> "WitnessReport":
+        """kh_witness_check(_full): gates, copy constraints and (lookups=True) the lookups (see check_witness)"""
+        return check_witness(self, witness, witness_on_device, gates, wires, lookups, runtime)
 
     def free(self):
         self.native.free()
 
 
-class WitnessReport(collections.namedtuple("WitnessReport", "ok kind row gate constraints col wired gate_rows_violated cells_disconnected message")):
-    """What kh_witness_check found (ProverIndex::verify of the reference): kind "ok" | "gate" (GateError::Custom: `row`, the name of its `gate`, the
+class WitnessReport(collections.namedtuple("WitnessReport", "ok kind row gate constraints col wired gate_rows_violated cells_disconnected message lookup lookups_missing",
+                                          defaults=(None, 0))):
+    """What kh_witness_check(_full) found (ProverIndex::verify of the reference): kind "ok" | "gate" (GateError::Custom: `row`, the name of its `gate`, the
     indices of the `constraints` that are not zero) | "disconnected" (GateError::DisconnectedWires: cell (row, col) and the cell `wired` = (row, col) it
-    is wired to); the two counts are over the whole circuit; `message` is the library's one line."""
+    is wired to) | "lookup" (a looked-up tuple that is in no table: `lookup` = {"pattern", "slot", "cols", "table_id", "entry"}, limbs as integers
+    Montgomery form); the counts are over the whole circuit; `message` is the library's one line."""
     __slots__ = ()
 
     def __bool__(self):
         return self.ok
 
 
-def check_witness(ix, witness=None, witness_on_device=None, gates: bool = True, wires: bool = None) -> WitnessReport:
+def check_witness(ix, witness=None, witness_on_device=None, gates: bool = True, wires: bool = None, lookups: bool = False, runtime=None) -> WitnessReport:
     """The first row of the witness that violates its gate or a copy constraint, found on the device (kh_witness_check) -- call it before proving, or
     when kh_prove's check refuses a witness without saying where.  witness: (15, rows, 4) Montgomery limbs, or witness_on_device: the padded columns.
-    wires: the copy constraints need the gate list, which only a CreatedIndex carries (default: checked there, not on a ProverIndex)."""
+    wires: the copy constraints need the gate list, which only a CreatedIndex carries (default: checked there, not on a ProverIndex).
+    lookups: also every looked-up tuple against the tables (kh_witness_check_full; the index must carry a lookup index); runtime: the runtime
+    tables' second column as for create_proof_native's kh_prove_full call, (k, 4) Montgomery limbs."""
     created = isinstance(ix, CreatedIndex)
     if wires is None:
         wires = created
-    flags = (khip.WITNESS_GATES if gates else 0) | (khip.WITNESS_WIRES if wires else 0)
-    r = khip.witness_check(native_index(ix), None if witness is None else np.asarray(witness, dtype=np.uint64).reshape(COLUMNS, -1, 4), witness_on_device, flags)
-    kind = {khip.WITNESS_OK: "ok", khip.WITNESS_GATE: "gate", khip.WITNESS_DISCONNECTED: "disconnected"}[r.kind]
+    flags = (khip.WITNESS_GATES if gates else 0) | (khip.WITNESS_WIRES if wires else 0) | (khip.WITNESS_LOOKUPS if lookups else 0)
+    w = None if witness is None else np.asarray(witness, dtype=np.uint64).reshape(COLUMNS, -1, 4)
+    if lookups:
+        r, lk = khip.witness_check_full(native_index(ix), w, witness_on_device, runtime, flags)
+        message, missing = khip.witness_lookup_message(r, lk), lk.lookups_missing
+    else:
+        r, lk = khip.witness_check(native_index(ix), w, witness_on_device, flags), None
+        message, missing = khip.witness_report_message(r), 0
+    kind = {khip.WITNESS_OK: "ok", khip.WITNESS_GATE: "gate", khip.WITNESS_DISCONNECTED: "disconnected", khip.WITNESS_LOOKUP: "lookup"}[r.kind]
     names = {g: t for t, g in khip.gate_ids().items()}
+    lookup = None
+    if kind == "lookup":
+        pname = {k: q for q, k in khip.LOOKUP_PATTERN_IDS.items()}[lk.pattern]
+        lookup = {"pattern": pname, "slot": lk.slot, "cols": list(lk.cols)[:lk.ncells], "table_id": list(lk.table_id), "entry": [list(lk.entry[c]) for c in range(lk.ncells)]}
     return WitnessReport(kind == "ok", kind, r.row if kind != "ok" else None, names[r.gate] if kind == "gate" else None,
                          [i for i in range(32) if r.constraints >> i & 1] if kind == "gate" else None, r.col if kind == "disconnected" else None,
-                         (r.wired_row, r.wired_col) if kind == "disconnected" else None, r.gate_rows_violated, r.cells_disconnected, khip.witness_report_message(r))
+                         (r.wired_row, r.wired_col) if kind == "disconnected" else None, r.gate_rows_violated, r.cells_disconnected, message, lookup, missing)
 
 
 def _horner(p: int, coeffs, x: int) -> int:

@@ -70,6 +70,9 @@ pub enum WitnessError {
     DisconnectedWires { cell: (usize, usize), wired_to: (usize, usize), cells_disconnected: usize },
     /// `GateError::Custom { row, err }`: the row's gate has constraints that are not zero.
     Custom { row: usize, gate: String, constraints: Vec<usize>, rows_violated: usize },
+    /// `ProverError::ValueNotInTable` with what the device adds (`verify_witness_full`): joint lookup `slot` of the row's `pattern` (0 Xor, 1 Lookup,
+    /// 2 RangeCheck, 3 ForeignFieldMul) reads the witness columns `cols` and, with the table id, forms a tuple that is in no table.
+    ValueNotInTable { row: usize, pattern: usize, slot: usize, cols: Vec<usize>, lookups_missing: usize, message: String },
 }
 
 pub struct GpuProver<G: HipCurve> {
@@ -375,7 +378,7 @@ where
     /// `ProverIndex::verify` / `ConstraintSystem::verify` (constraints.rs) on the device (`kh_witness_check`): the gate constraints of every row,
     /// each compared with zero exactly, and -- for an index built by `from_gates`, which keeps the gate list's wires -- the copy constraints.
     /// The error is the FIRST violation in the reference's order (rows upwards; within a row the wires by column, then the gate).  Lookups are
-    /// not checked here, nor is the index-side condition `GateError::IncorrectPublic`.  Tens of microseconds of kernels: call it before
+    /// checked by `verify_witness_full`, not here, nor is the index-side condition `GateError::IncorrectPublic`.  Tens of microseconds of kernels: call it before
     /// `create`, whose own check runs the whole proof and names no row.
     pub fn verify_witness(&self, witness: &[Vec<G::ScalarField>; COLUMNS], wires: bool) -> Result<(), WitnessError> {
         let rows = witness[0].len();
@@ -383,7 +386,32 @@ where
         let flags = sys::KH_WITNESS_GATES as u32 | if wires { sys::KH_WITNESS_WIRES as u32 } else { 0 };
         let mut r = core::mem::MaybeUninit::<sys::kh_witness_report_t>::zeroed();
         ok(unsafe { sys::kh_witness_check(self.index, flat.as_ptr() as *const u64, rows, core::ptr::null(), flags, r.as_mut_ptr()) });
-        let r = unsafe { r.assume_init() };
+        Self::witness_result(unsafe { r.assume_init() }, None)
+    }
+
+    /// `verify_witness` + the lookups (`kh_witness_check_full` with `KH_WITNESS_LOOKUPS`): every joint lookup of every row below
+    /// `n - zk_rows - 1` against the set of table tuples (id, columns), exactly and without a joint combiner -- the statement the lookup
+    /// constraints enforce.  `runtime_tables` as for `create_recursive`.  A miss on a row comes after that row's wires and gate.
+    pub fn verify_witness_full(
+        &self,
+        witness: &[Vec<G::ScalarField>; COLUMNS],
+        wires: bool,
+        runtime_tables: &[RuntimeTable<G::ScalarField>],
+    ) -> Result<(), WitnessError> {
+        let rows = witness[0].len();
+        let flat: Vec<G::ScalarField> = witness.iter().flat_map(|c| c.iter().copied()).collect();
+        let runtime_values: Vec<G::ScalarField> = runtime_tables.iter().flat_map(|t| t.data.iter().copied()).collect();
+        let runtime_ptr = if runtime_values.is_empty() { core::ptr::null() } else { runtime_values.as_ptr() as *const u64 };
+        let flags = sys::KH_WITNESS_GATES as u32 | sys::KH_WITNESS_LOOKUPS as u32 | if wires { sys::KH_WITNESS_WIRES as u32 } else { 0 };
+        let mut r = core::mem::MaybeUninit::<sys::kh_witness_report_t>::zeroed();
+        let mut l = core::mem::MaybeUninit::<sys::kh_witness_lookup_t>::zeroed();
+        ok(unsafe {
+            sys::kh_witness_check_full(self.index, flat.as_ptr() as *const u64, rows, core::ptr::null(), runtime_ptr, runtime_values.len(), flags, r.as_mut_ptr(), l.as_mut_ptr())
+        });
+        Self::witness_result(unsafe { r.assume_init() }, Some(unsafe { l.assume_init() }))
+    }
+
+    fn witness_result(r: sys::kh_witness_report_t, l: Option<sys::kh_witness_lookup_t>) -> Result<(), WitnessError> {
         match r.kind {
             k if k == sys::KH_WITNESS_OK => Ok(()),
             k if k == sys::KH_WITNESS_DISCONNECTED => Err(WitnessError::DisconnectedWires {
@@ -391,6 +419,20 @@ where
                 wired_to: (r.wired_row, r.wired_col as usize),
                 cells_disconnected: r.cells_disconnected,
             }),
+            k if k == sys::KH_WITNESS_LOOKUP => {
+                let l = l.expect("a lookup report comes with its record");
+                let mut buf = [0u8; 512];
+                let len = unsafe { sys::kh_witness_lookup_message(&r, &l, buf.as_mut_ptr() as *mut core::ffi::c_char, buf.len()) };
+                let len = (len.max(0) as usize).min(buf.len() - 1);
+                Err(WitnessError::ValueNotInTable {
+                    row: r.row,
+                    pattern: l.pattern as usize,
+                    slot: l.slot as usize,
+                    cols: l.cols[..l.ncells as usize].iter().map(|&c| c as usize).collect(),
+                    lookups_missing: l.lookups_missing,
+                    message: String::from_utf8_lossy(&buf[..len]).into_owned(),
+                })
+            }
             _ => Err(WitnessError::Custom {
                 row: r.row,
                 gate: unsafe { std::ffi::CStr::from_ptr(sys::kh_gate_name(r.gate)) }.to_string_lossy().into_owned(),
