@@ -596,16 +596,17 @@ int kh_prover_index_new(kh_srs_t *srs, unsigned log2_n, unsigned zk_rows, unsign
  * (joint combiner, combined table, sorted columns on the device via kh_lookup_sorted_dev, aggregation, the lookup constraints on d8, the extra evaluations and openings);
  * KH_PROOF_EVALS carries, after the polynomials listed above: sorted x (max_per_row + 1), aggregation, combined table, one selector per pattern;
  * the randomness grows by (max_per_row + 1) (zk_rows + num_chunks) after the witness blinders and zk_rows + num_chunks before z's two rows. */
-int kh_prover_index_attach_lookup(kh_prover_index_t *index, const int *patterns, size_t n_patterns, const uint64_t *const *selectors_d1,
-                                  const uint64_t *const *selectors_c, const uint64_t *const *selectors_d8, const uint64_t *const *table_cols_d1,
-                                  size_t n_table_cols, const uint64_t *table_ids_d1, const uint64_t *const *atoms_d8);
+int kh_prover_index_attach_lookup(kh_prover_index_t *index, const int *patterns, size_t n_patterns, const uint64_t *const *selectors_d1_dev,
+                                  const uint64_t *const *selectors_c_dev, const uint64_t *const *selectors_d8_dev,
+                                  const uint64_t *const *table_cols_d1_dev, size_t n_table_cols, const uint64_t *table_ids_d1_dev,
+                                  const uint64_t *const *atoms_d8_dev);
 /* Runtime tables (lookup/runtime_tables.rs, index.rs:241-311): `length` rows of the combined table, starting at row `offset`, whose second column arrives
  * with each proof (kh_prove_full: runtime_values, all runtime tables' data concatenated in the index's order); selector = the runtime-table selector column
  * (1 outside the runtime rows, 0 on them and on the zero-knowledge rows) as d1 evaluations, coefficient form, d8 evaluations.  After
  * kh_prover_index_attach_lookup.  KH_PROOF_EVALS then carries runtime table + runtime selector between the combined table and the pattern selectors; the
  * randomness grows by zk_rows + num_chunks right after the witness blinders. */
-int kh_prover_index_attach_runtime_tables(kh_prover_index_t *index, const uint64_t *selector_d1, const uint64_t *selector_c, const uint64_t *selector_d8,
-                                          size_t offset, size_t length);
+int kh_prover_index_attach_runtime_tables(kh_prover_index_t *index, const uint64_t *selector_d1_dev, const uint64_t *selector_c_dev,
+                                          const uint64_t *selector_d8_dev, size_t offset, size_t length);
 /* ---- the index from a gate list: ConstraintSystem::create(gates).public(k).build() + ProverIndex::verifier_index() (constraints.rs, prover_index.rs,
  * verifier_index.rs:175-300, 405-540) as one call, for circuits WITHOUT a lookup argument ----
  * kh_permutation_shifts: Shifts::new (permutation.rs:140-199) for the domain of 2^log2_n rows: shift_0 = 1, then six quadratic non-residues r with

@@ -1,5 +1,9 @@
 """ctypes binding of include/kimchi_hip.h (numpy uint64 limb arrays in, numpy out).
 
+The header is the only description of the ABI: at import it is parsed (_abi.py) and every function the library exports gets its
+argtypes and restype from its prototype, the caller-filled structs become ctypes Structures and every KH_* constant a module
+attribute (`_ctype` below is the whole mapping).  A new entry point needs its prototype in the header and its wrapper here.
+
 No fallback: if libkimchi_hip.so has not been built this module raises ImportError, and
 every call raises KhError when the library reports a failure (e.g. no GPU).
 """
@@ -10,221 +14,94 @@ import os
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KH_LIB") or os.path.join(_HERE, "libkimchi_hip.so")      # KH_LIB: another build of the library (same-box A/B of two builds)
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                       "(hipcc --offload-arch=gfx950); there is no CPU fallback")
+try:
+    _PROTOTYPES, _STRUCTS, _CONSTANTS = _abi.parse()
+except OSError as e:
+    raise ImportError(f"{_abi.HEADER} is missing: the binding is declared from it ({e})") from e
 
 _lib = C.CDLL(LIB_PATH)
 
+SYMBOLS = list(_PROTOTYPES)          # every function include/kimchi_hip.h declares
+
+def __getattr__(name: str):
+    """Every constant of the header is an attribute of this module under its name without the KH_ prefix (khip.TOK_CONST, khip.SCAN_MUL, khip.E_BLINDERS,
+    khip.MSM_SLOTS, khip.GATE_ZERO, khip.GATE_LOOKUP, ...).  The ones this module uses itself, and the short names, are spelled out below."""
+    try:
+        return _CONSTANTS["KH_" + name]
+    except KeyError:
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}") from None
+
+
+VESTA, PALLAS = _CONSTANTS["KH_CURVE_VESTA"], _CONSTANTS["KH_CURVE_PALLAS"]
+FP, FQ = _CONSTANTS["KH_FIELD_FP"], _CONSTANTS["KH_FIELD_FQ"]
+BASIS_G = _CONSTANTS["KH_BASIS_G"]
+PROVE_CHECK = _CONSTANTS["KH_PROVE_CHECK"]
+WITNESS_GATES, WITNESS_WIRES, WITNESS_LOOKUPS = _CONSTANTS["KH_WITNESS_GATES"], _CONSTANTS["KH_WITNESS_WIRES"], _CONSTANTS["KH_WITNESS_LOOKUPS"]
+
+
+def _sections(prefix: str):
+    """{"w_comm": KH_PROOF_W_COMM, ...}: the constants of one prefix, in the header's order"""
+    return {name[len(prefix):].lower(): value for name, value in _CONSTANTS.items() if name.startswith(prefix)}
+
+
+_BY_VALUE = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8,
+             "double": C.c_double, "float": C.c_float}
+_STRUCTURES = {}                     # kh_lookup_table_t -> LookupTableC, ...
+
+
+def _ctype(ctype: str, name: str = ""):
+    """The ctypes type of a C type of the header.  By value: the matching ctypes (void: None).  A device address (a parameter named *_dev), an opaque
+    handle (kh_srs_t *) and void * are c_void_p -- callers pass integers --, char * is c_char_p; one more level of either is a POINTER to that.  Every
+    other T * (arrays arrive as T *) is POINTER(T), so a numpy array of the wrong element type is refused before the call."""
+    toks = ctype.replace("*", " * ").split()
+    depth = toks.count("*")
+    base, = [t for t in toks if t not in ("const", "*")]
+    if depth and (name.endswith("_dev") or base == "void" or (base.startswith("kh_") and base not in _STRUCTURES)):
+        t, depth = C.c_void_p, depth - 1
+    elif depth and base == "char":
+        t, depth = C.c_char_p, depth - 1
+    else:
+        t = None if base == "void" else _STRUCTURES.get(base) or _BY_VALUE[base]
+    for _ in range(depth):
+        t = C.POINTER(t)
+    return t
+
+
+def _structure(name: str, fields):
+    """kh_lookup_table_t -> class LookupTableC(ctypes.Structure) with the typedef's fields.  A pointer field keeps its pointee type (`data` takes
+    arr.ctypes.data_as(U64P)): no name is given to _ctype, its *_dev rule is for parameters."""
+    members = []
+    for field, ctype, dims in fields:
+        t = _ctype(ctype)
+        for d in reversed(dims):               # entry[3][4] -> (c_uint64 * 4) * 3
+            t = t * d
+        members.append((field, t))
+    return type("".join(w.capitalize() for w in name[3:-2].split("_")) + "C", (C.Structure,), {"__doc__": name, "_fields_": members})
+
+
+for _name, _fields in _STRUCTS.items():
+    _STRUCTURES[_name] = _structure(_name, _fields)
+LookupTableC, RuntimeTableCfgC = _STRUCTURES["kh_lookup_table_t"], _STRUCTURES["kh_runtime_table_cfg_t"]
+WitnessReportC, WitnessLookupC = _STRUCTURES["kh_witness_report_t"], _STRUCTURES["kh_witness_lookup_t"]
+
+# ctypes passes an undeclared Python int as a 32-bit C int (round 6: kh_msm_submit_host, called with a bare int for its size_t n, asked hipMalloc for
+# 6.6 EB), so nothing is left undeclared.  A function an older build (KH_LIB) lacks is skipped; tests/test_abi.py holds the in-tree build to all of them.
+for _name, (_ret, _params) in _PROTOTYPES.items():
+    _fn = getattr(_lib, _name, None)
+    if _fn is not None:
+        _fn.restype = _ctype(_ret)
+        _fn.argtypes = [_ctype(_t, _p) for _t, _p in _params]
+
 U64P = C.POINTER(C.c_uint64)
 U8P = C.POINTER(C.c_uint8)
-VESTA, PALLAS = 0, 1
-FP, FQ = 0, 1
-BASIS_G = -1
-MSM_SLOTS = 4          # KH_MSM_SLOTS: jobs kh_msm_submit accepts before kh_msm_wait
-
-# every symbol include/kimchi_hip.h declares
-SYMBOLS = [
-    "kh_sponge_new", "kh_sponge_clone", "kh_sponge_free", "kh_sponge_absorb_g", "kh_sponge_absorb", "kh_sponge_absorb_fr", "kh_sponge_challenge",
-    "kh_sponge_challenge_field", "kh_sponge_squeeze_field", "kh_sponge_digest",
-    "kh_group_map_to_group", "kh_dev_copy", "kh_dev_memset_zero", "kh_dev_fill_elements", "kh_set_phase_timers", "kh_ipa_open",
-    "kh_device_count", "kh_init", "kh_set_device", "kh_get_device", "kh_trim", "kh_srs_device", "kh_last_error", "kh_srs_create", "kh_msm_set_wide_min_n", "kh_msm_set_sort_staging", "kh_ntt_set_max_logr", "kh_debug_rebase_points", "kh_debug_glv_split", "kh_msm_submit_host", "kh_counter", "kh_srs_set_wide_tables", "kh_srs_has_wide_tables", "kh_srs_free", "kh_srs_size",
-    "kh_srs_set_lagrange", "kh_srs_compute_lagrange", "kh_srs_get_lagrange", "kh_srs_lagrange_chunks",
-    "kh_msm", "kh_msm_batch", "kh_msm_points", "kh_ntt", "kh_lde",
-    "kh_dev_alloc", "kh_dev_free", "kh_dev_upload", "kh_dev_download", "kh_dev_upload_2d", "kh_dev_upload_2d_unordered",
-    "kh_msm_batch_dev", "kh_ntt_dev", "kh_lde_dev", "kh_coset_ntt_dev", "kh_sync", "kh_last_timings",
-    "kh_debug_field_op", "kh_debug_point_op", "kh_srs_generate", "kh_srs_h",
-    "kh_msm_sharded", "kh_msm_sharded_dev", "kh_gate_count", "kh_gate_name", "kh_gate_num_constants", "kh_gate_evaluations_dev", "kh_gate_constants", "kh_srs_curve", "kh_lookup_sorted", "kh_lookup_sorted_dev", "kh_private_context_begin", "kh_private_context_end", "kh_private_context_active", "kh_comm_unique_id", "kh_comm_init", "kh_comm_free", "kh_comm_world_size", "kh_comm_rank", "kh_comm_allgather_points",
-    "kh_msm_allreduce",
-    "kh_prover_index_new", "kh_prover_index_attach_lookup", "kh_prover_index_free", "kh_prove_randomness_count", "kh_prove", "kh_prove_recursive", "kh_prove_full", "kh_prover_index_attach_runtime_tables", "kh_proof_section", "kh_proof_phase_seconds", "kh_proof_free",
-    "kh_permutation_shifts", "kh_prover_index_create", "kh_prover_index_create_lookup", "kh_debug_lookup_column", "kh_prover_index_shape", "kh_verifier_index_section", "kh_prover_index_phase_seconds",
-    "kh_witness_check", "kh_witness_report_message", "kh_witness_check_full", "kh_witness_lookup_message",
-    "kh_commit_non_hiding", "kh_commit_evaluations_non_hiding", "kh_srs_set_blinding_base",
-    "kh_srs_get_blinding_base", "kh_mask_custom", "kh_domain_generator", "kh_msm_points_batch", "kh_msm_submit", "kh_msm_wait",
-    "kh_ipa_fold_scalars", "kh_inner_product", "kh_ipa_fold_points", "kh_ipa_fold_points_endo", "kh_endos", "kh_scalar_challenge_to_field",
-    "kh_polycomm_multi_scalar_mul", "kh_expr_evaluations_dev", "kh_field_scan_dev", "kh_batch_inversion_dev", "kh_divide_by_linear_dev", "kh_divide_by_linear_async_dev", "kh_check_equal_dev", "kh_b_poly_coefficients", "kh_batch_dlog_accumulator_generate", "kh_batch_dlog_accumulator_check", "kh_ipa_verify_msm",
-    "kh_ipa_begin", "kh_ipa_begin_dev", "kh_combine_polys_dev", "kh_poly_lincomb_dev", "kh_b_init_dev", "kh_evaluate_chunks_dev", "kh_evaluate_chunks_batch_dev", "kh_divide_by_vanishing_poly_dev", "kh_ipa_rounds_left", "kh_ipa_round_lr", "kh_ipa_round_fold", "kh_ipa_finish", "kh_ipa_free", "kh_points_sum", "kh_points_add", "kh_srs_create_device", "kh_srs_create_device_range", "kh_srs_get_g",
-]
-
-
-class LookupTableC(C.Structure):
-    """kh_lookup_table_t"""
-    _fields_ = [("id", C.c_int), ("width", C.c_size_t), ("len", C.c_size_t), ("data", C.POINTER(C.c_uint64))]
-
-
-class WitnessReportC(C.Structure):
-    """kh_witness_report_t"""
-    _fields_ = [("kind", C.c_int), ("gate", C.c_int), ("constraints", C.c_uint32), ("col", C.c_int), ("wired_col", C.c_int), ("row", C.c_size_t), ("wired_row", C.c_size_t),
-                ("gate_rows_violated", C.c_size_t), ("cells_disconnected", C.c_size_t)]
-
-
-class WitnessLookupC(C.Structure):
-    """kh_witness_lookup_t"""
-    _fields_ = [("pattern", C.c_int), ("slot", C.c_int), ("ncells", C.c_int), ("cols", C.c_int * 3), ("table_id", C.c_uint64 * 4), ("entry", (C.c_uint64 * 4) * 3),
-                ("lookups_missing", C.c_size_t)]
-
-
-class RuntimeTableCfgC(C.Structure):
-    """kh_runtime_table_cfg_t"""
-    _fields_ = [("id", C.c_int), ("len", C.c_size_t), ("first_column", C.POINTER(C.c_uint64))]
-
-
-_lib.kh_last_error.restype = C.c_char_p
-_lib.kh_set_device.argtypes = [C.c_int]
-_lib.kh_ipa_open.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, U64P, U64P, C.c_void_p, U64P, C.c_size_t, U64P, U8P, U64P, U8P, U64P, U64P, U64P, U8P]
-_lib.kh_sponge_new.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-_lib.kh_sponge_clone.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-_lib.kh_sponge_free.argtypes = [C.c_void_p]
-_lib.kh_sponge_free.restype = None
-_lib.kh_sponge_absorb_g.argtypes = [C.c_void_p, U64P, U8P, C.c_size_t]
-_lib.kh_sponge_absorb.argtypes = [C.c_void_p, U64P, C.c_size_t]
-_lib.kh_sponge_absorb_fr.argtypes = [C.c_void_p, U64P, C.c_size_t]
-_lib.kh_sponge_challenge.argtypes = [C.c_void_p, U64P]
-_lib.kh_sponge_challenge_field.argtypes = [C.c_void_p, U64P]
-_lib.kh_sponge_squeeze_field.argtypes = [C.c_void_p, U64P]
-_lib.kh_sponge_digest.argtypes = [C.c_void_p, U64P]
-_lib.kh_srs_device.argtypes = [C.c_void_p]
-_lib.kh_srs_size.restype = C.c_size_t
-_lib.kh_srs_size.argtypes = [C.c_void_p]
-_lib.kh_srs_free.restype = None
-_lib.kh_srs_free.argtypes = [C.c_void_p]
-_lib.kh_srs_create.argtypes = [C.c_int, U64P, C.c_size_t, C.POINTER(C.c_void_p)]
-_lib.kh_msm_set_wide_min_n.argtypes = [C.c_size_t]
-_lib.kh_msm_set_sort_staging.argtypes = [C.c_uint, C.c_uint]
-_lib.kh_ntt_set_max_logr.argtypes = [C.c_uint]
-_lib.kh_counter.argtypes = [C.c_char_p]
-_lib.kh_counter.restype = C.c_uint64
-_lib.kh_srs_set_wide_tables.argtypes = [C.c_void_p, C.c_int]
-_lib.kh_srs_has_wide_tables.argtypes = [C.c_void_p]
-_lib.kh_dev_fill_elements.argtypes = [C.c_void_p, U64P, C.c_size_t]
-_lib.kh_srs_set_lagrange.argtypes = [C.c_void_p, C.c_uint, C.c_uint, U64P, U8P, C.c_size_t]
-_lib.kh_srs_compute_lagrange.argtypes = [C.c_void_p, C.c_uint]
-_lib.kh_srs_get_lagrange.argtypes = [C.c_void_p, C.c_uint, C.c_uint, U64P, U8P]
-_lib.kh_srs_lagrange_chunks.argtypes = [C.c_void_p, C.c_uint]
-_lib.kh_msm.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_size_t, U64P, C.c_size_t, C.c_int, U64P, U8P]
-_lib.kh_msm_batch.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_size_t, U64P, C.c_size_t, C.c_size_t, C.c_int, U64P, U8P]
-_lib.kh_msm_batch_dev.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, U64P, U8P]
-_lib.kh_msm_points.argtypes = [C.c_int, U64P, U8P, U64P, C.c_size_t, C.c_int, U64P, U8P]
-_lib.kh_ipa_fold_scalars.argtypes = [C.c_int, U64P, U64P, U64P, C.c_size_t, U64P]
-_lib.kh_inner_product.argtypes = [C.c_int, U64P, U64P, C.c_size_t, U64P]
-_lib.kh_ipa_fold_points.argtypes = [C.c_int, U64P, U64P, U64P, C.c_size_t, U64P, U8P]
-_lib.kh_ipa_fold_points_endo.argtypes = [C.c_int, U64P, U64P, U64P, C.c_size_t, U64P, U8P]
-_lib.kh_endos.argtypes = [C.c_int, U64P, U64P]
-_lib.kh_scalar_challenge_to_field.argtypes = [C.c_int, U64P, U64P]
-_lib.kh_expr_evaluations_dev.argtypes = [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
-                                         U64P, C.c_size_t, C.c_size_t, C.c_uint, C.c_uint, C.c_int, C.c_void_p]
-_lib.kh_field_scan_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-_lib.kh_batch_inversion_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
-_lib.kh_divide_by_linear_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, U64P]
-_lib.kh_divide_by_linear_async_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_void_p]
-_lib.kh_check_equal_dev.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_void_p, C.c_uint]
-_lib.kh_lookup_sorted_dev.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
-_lib.kh_permutation_shifts.argtypes = [C.c_int, C.c_uint, U64P]
-_lib.kh_prover_index_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(C.c_void_p)]
-_lib.kh_prover_index_create_lookup.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_uint32), U64P, C.c_uint, C.POINTER(LookupTableC), C.c_size_t,
-                                               C.POINTER(RuntimeTableCfgC), C.c_size_t, C.POINTER(C.c_void_p)]
-_lib.kh_witness_check.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_void_p, C.c_uint, C.POINTER(WitnessReportC)]
-_lib.kh_witness_report_message.argtypes = [C.POINTER(WitnessReportC), C.c_char_p, C.c_size_t]
-_lib.kh_witness_check_full.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_void_p, U64P, C.c_size_t, C.c_uint, C.POINTER(WitnessReportC), C.POINTER(WitnessLookupC)]
-_lib.kh_witness_lookup_message.argtypes = [C.POINTER(WitnessReportC), C.POINTER(WitnessLookupC), C.c_char_p, C.c_size_t]
-_lib.kh_debug_lookup_column.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(U64P), C.POINTER(C.c_size_t)]
-_lib.kh_prover_index_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]
-_lib.kh_verifier_index_section.argtypes = [C.c_void_p, C.c_int, C.POINTER(U64P), C.POINTER(U8P), C.POINTER(C.c_size_t)]
-_lib.kh_prover_index_phase_seconds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_size_t]
-_lib.kh_polycomm_multi_scalar_mul.argtypes = [C.c_int, U64P, U8P, C.POINTER(C.c_size_t), C.c_size_t, U64P, U64P, U8P, C.POINTER(C.c_size_t)]
-_lib.kh_b_poly_coefficients.argtypes = [C.c_int, U64P, C.c_uint, C.c_size_t, U64P]
-_lib.kh_batch_dlog_accumulator_generate.argtypes = [C.c_void_p, C.c_size_t, U64P, C.c_size_t, U64P, U8P]
-_lib.kh_batch_dlog_accumulator_check.argtypes = [C.c_void_p, U64P, U8P, C.c_size_t, U64P, C.c_size_t, U64P, C.POINTER(C.c_int)]
-_lib.kh_ipa_verify_msm.argtypes = [C.c_void_p, U64P, C.c_size_t, U64P, C.c_size_t, U64P, U8P, U64P, C.c_size_t, C.POINTER(C.c_int)]
-_lib.kh_ipa_begin.argtypes = [C.c_void_p, U64P, C.c_size_t, U64P, C.c_size_t, U64P, C.POINTER(C.c_void_p)]
-_lib.kh_ipa_begin_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, U64P, C.POINTER(C.c_void_p)]
-_lib.kh_combine_polys_dev.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, U64P, C.c_size_t,
-                                      C.c_void_p, C.POINTER(C.c_size_t)]
-_lib.kh_poly_lincomb_dev.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), U64P, C.c_size_t, C.c_void_p, C.c_size_t]
-_lib.kh_b_init_dev.argtypes = [C.c_int, U64P, C.c_size_t, U64P, C.c_size_t, C.c_void_p]
-_lib.kh_evaluate_chunks_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, U64P, C.c_size_t, U64P]
-_lib.kh_evaluate_chunks_batch_dev.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t,
-                                              U64P, C.c_size_t, U64P]
-_lib.kh_divide_by_vanishing_poly_dev.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p]
-_lib.kh_ipa_rounds_left.argtypes = [C.c_void_p]
-_lib.kh_ipa_round_lr.argtypes = [C.c_void_p, U64P, U64P, U64P, U8P]
-_lib.kh_ipa_round_fold.argtypes = [C.c_void_p, U64P, U64P, U64P]
-_lib.kh_ipa_finish.argtypes = [C.c_void_p, U64P, U64P, U64P, U8P]
-_lib.kh_ipa_free.argtypes = [C.c_void_p]
-_lib.kh_ipa_free.restype = None
-_lib.kh_srs_create_device.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-_lib.kh_srs_create_device_range.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]
-_lib.kh_srs_get_g.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, U64P]
-_lib.kh_points_sum.argtypes = [C.c_int, U64P, U8P, C.c_size_t, U64P, U8P]
-_lib.kh_points_add.argtypes = [C.c_int, U64P, U8P, U64P, U8P, C.c_size_t, U64P, U8P]
-_lib.kh_msm_submit.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
-_lib.kh_msm_wait.argtypes = [C.c_uint64, U64P, U8P]
-_lib.kh_msm_submit_host.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_size_t, U64P, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
-_lib.kh_msm_points_batch.argtypes = [C.c_int, U64P, U8P, U64P, C.c_size_t, C.c_size_t, C.c_int, U64P, U8P]
-_lib.kh_ntt.argtypes = [C.c_int, U64P, C.c_uint, C.c_int, C.c_size_t]
-_lib.kh_lde.argtypes = [C.c_int, U64P, C.c_uint, C.c_uint, U64P, C.c_size_t]
-_lib.kh_ntt_dev.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_int, C.c_size_t]
-_lib.kh_lde_dev.argtypes = [C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t]
-_lib.kh_coset_ntt_dev.argtypes = [C.c_int, C.c_void_p, C.c_uint, U64P, C.c_void_p, C.c_size_t]
-_lib.kh_dev_alloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-_lib.kh_dev_free.argtypes = [C.c_void_p]
-_lib.kh_dev_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-_lib.kh_dev_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-_lib.kh_dev_upload_2d.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]
-_lib.kh_dev_upload_2d_unordered.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]
-_lib.kh_last_timings.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
-_lib.kh_debug_field_op.argtypes = [C.c_int, C.c_int, U64P, U64P, U64P, C.c_size_t]
-_lib.kh_debug_point_op.argtypes = [C.c_int, C.c_int, U64P, U8P, U64P, U8P, U64P, U8P, C.c_size_t]
-
-
-_lib.kh_srs_generate.argtypes = [C.c_int, C.c_size_t, C.c_size_t, U64P, C.c_int]
-_lib.kh_srs_h.argtypes = [C.c_int, U64P]
-
-
-_lib.kh_commit_non_hiding.argtypes = [C.c_void_p, U64P, C.c_size_t, C.c_size_t, U64P, U8P, C.POINTER(C.c_size_t)]
-_lib.kh_commit_evaluations_non_hiding.argtypes = [C.c_void_p, C.c_uint, U64P, C.c_size_t, U64P, U8P, C.POINTER(C.c_size_t)]
-_lib.kh_srs_set_blinding_base.argtypes = [C.c_void_p, U64P]
-_lib.kh_srs_get_blinding_base.argtypes = [C.c_void_p, U64P]
-_lib.kh_mask_custom.argtypes = [C.c_void_p, U64P, U8P, C.c_size_t, U64P, C.c_size_t, U64P, U8P]
-_lib.kh_domain_generator.argtypes = [C.c_int, C.c_uint, U64P]
-E_BLINDERS = -5
-
-
-def _declare_remaining_argtypes():
-    """ctypes passes an undeclared Python int as a 32-bit C int: every function whose argument list is not declared above gets it from the header's own
-    prototype (include/kimchi_hip.h): int / unsigned / size_t / uint64_t by value, every pointer or array as void* (which takes ctypes pointers, byref(),
-    arrays, addresses and None alike).  Round 6: kh_msm_submit_host, called with a bare Python int for its size_t n, asked hipMalloc for 6.6 EB."""
-    import re
-    hdr = os.path.join(os.path.dirname(_HERE), "include", "kimchi_hip.h")
-    try:
-        src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
-    except OSError:
-        return
-    by_value = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32, "double": C.c_double, "float": C.c_float}
-    for m in re.finditer(r"\b(kh_[a-z_0-9]+)\s*\(([^;{}]*?)\)\s*;", src):
-        name, args = m.group(1), " ".join(m.group(2).split())
-        fn = getattr(_lib, name, None)
-        if fn is None or fn.argtypes is not None or args in ("", "void"):
-            continue
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            if "*" in a or "[" in a:
-                types.append(C.c_void_p)
-                continue
-            base = [t for t in a.split()[:-1] if t != "const"]
-            if len(base) != 1 or base[0] not in by_value:
-                types = None
-                break
-            types.append(by_value[base[0]])
-        if types is not None:
-            fn.argtypes = types
-
-
-_declare_remaining_argtypes()
 
 
 class KhError(RuntimeError):
@@ -295,7 +172,6 @@ def glv_split(scalar_field: int, scalars):
     a = np.ascontiguousarray(scalars, dtype=np.uint64)
     n = a.shape[0]
     out = np.zeros((n, 10), np.uint32)
-    _lib.kh_debug_glv_split.argtypes = [C.c_int, U64P, C.c_size_t, C.POINTER(C.c_uint32)]
     _check(_lib.kh_debug_glv_split(scalar_field, _p64(a), n, out.ctypes.data_as(C.POINTER(C.c_uint32))))
     res = []
     for row in out:
@@ -633,7 +509,7 @@ def dev_copy(dst_ptr: int, src_ptr: int, nbytes: int):
 
 
 def dev_memset_zero(dst_ptr: int, nbytes: int):
-    _check(_lib.kh_dev_memset_zero(C.c_void_p(dst_ptr), C.c_size_t(nbytes)))
+    _check(_lib.kh_dev_memset_zero(C.c_void_p(dst_ptr), nbytes))
 
 
 def group_map_to_group(curve: int, t):
@@ -705,9 +581,6 @@ def ipa_fold_points_endo(curve: int, g_lo, g_hi, chal: int):
     return out, inf
 
 
-SCAN_ADD, SCAN_MUL = 0, 1
-
-
 def field_scan_dev(field: int, op: int, buf, n: int, reverse: bool = False, offset: int = 0):
     """In-place inclusive scan of n elements starting `offset` elements into the DevBuf."""
     _check(_lib.kh_field_scan_dev(field, op, int(reverse), C.c_void_p(buf.ptr + 32 * offset), n))
@@ -735,9 +608,6 @@ def check_equal_dev(v, n: int, expect, flags, bit: int, offset: int = 0):
     _check(_lib.kh_check_equal_dev(C.c_void_p(v.ptr + 32 * offset), n, _p64(e) if e is not None else None, C.c_void_p(flags.ptr), bit))
 
 
-TOK_CONST, TOK_CELL, TOK_DUP, TOK_POW, TOK_ADD, TOK_MUL, TOK_SUB, TOK_STORE, TOK_LOAD = range(9)
-
-
 def expr_evaluations_dev(field: int, tokens, cols, col_len, constants, rows: int, out, stride: int = 1, next_shift: int = 8, accumulate: bool = False,
                          out_offset: int = 0):
     """tokens: list of (opcode, arg); cols: list of DevBuf; constants: (k, 4) Montgomery limbs; out: DevBuf receiving `rows`
@@ -757,13 +627,12 @@ _GATE_IDS = {}
 def gate_ids():
     """{name: id} of the compiled kernels (kh_gate_evaluations_dev): the gate library's GateType names, "Generic", "Permutation"."""
     if not _GATE_IDS:
-        _lib.kh_gate_name.restype = C.c_char_p
         _GATE_IDS.update({_lib.kh_gate_name(g).decode(): g for g in range(_lib.kh_gate_count())})
     return _GATE_IDS
 
 
 def gate_num_constants(gate: int) -> int:
-    return _lib.kh_gate_num_constants(C.c_int(gate))
+    return _lib.kh_gate_num_constants(gate)
 
 
 def gate_constants(field: int, gate: int, alpha=None, endo=None, params=None):
@@ -773,8 +642,8 @@ def gate_constants(field: int, gate: int, alpha=None, endo=None, params=None):
     a = _c64(alpha, (4,)) if alpha is not None else None
     e = _c64(endo, (4,)) if endo is not None else None
     ps = _c64(params, (-1, 4)) if params is not None else None
-    _check(_lib.kh_gate_constants(C.c_int(field), C.c_int(gate), _p64(a) if a is not None else None, _p64(e) if e is not None else None,
-                                  _p64(ps) if ps is not None else None, C.c_size_t(ps.shape[0] if ps is not None else 0), _p64(out)))
+    _check(_lib.kh_gate_constants(field, gate, _p64(a) if a is not None else None, _p64(e) if e is not None else None,
+                                  _p64(ps) if ps is not None else None, ps.shape[0] if ps is not None else 0, _p64(out)))
     return out
 
 
@@ -784,8 +653,8 @@ def gate_evaluations_dev(field: int, gate: int, cols, col_len: int, constants, r
     assert len(cols) == 31
     ptrs = (C.c_void_p * 31)(*[C.c_void_p(c.ptr) for c in cols])
     cs = _c64(constants, (-1, 4))
-    _check(_lib.kh_gate_evaluations_dev(C.c_int(field), C.c_int(gate), ptrs, C.c_size_t(col_len), _p64(cs), C.c_size_t(cs.shape[0]), C.c_size_t(rows),
-                                        C.c_uint(stride), C.c_uint(next_shift), C.c_int(int(accumulate)), C.c_void_p(out.ptr + 32 * out_offset)))
+    _check(_lib.kh_gate_evaluations_dev(field, gate, ptrs, col_len, _p64(cs), cs.shape[0], rows,
+                                        stride, next_shift, int(accumulate), C.c_void_p(out.ptr + 32 * out_offset)))
 
 
 def lookup_sorted(table, lookup_rows: int, values, max_per_row: int):
@@ -794,7 +663,7 @@ def lookup_sorted(table, lookup_rows: int, values, max_per_row: int):
     t = _c64(table, (-1, 4)); v = _c64(values, (max_per_row, -1, 4))
     out = np.zeros((max_per_row + 1, lookup_rows + 1, 4), dtype=np.uint64)
     bad = C.c_size_t(0)
-    rc = _lib.kh_lookup_sorted(_p64(t), C.c_size_t(lookup_rows), _p64(v), C.c_size_t(v.shape[1]), C.c_size_t(max_per_row), _p64(out), C.byref(bad))
+    rc = _lib.kh_lookup_sorted(_p64(t), lookup_rows, _p64(v), v.shape[1], max_per_row, _p64(out), C.byref(bad))
     if rc != 0 and bad.value != C.c_size_t(-1).value:
         raise ValueError(bad.value)
     _check(rc)
@@ -806,8 +675,8 @@ def lookup_sorted_dev(table, lookup_rows: int, values, value_stride: int, max_pe
     max_per_row columns, value_stride elements apart; out: max_per_row + 1 columns, out_stride elements apart, of which elements 0 .. lookup_rows are
     written and nothing else.  Raises ValueError(row) for a value that is not in the table (out is then untouched)."""
     bad = C.c_size_t(0)
-    rc = _lib.kh_lookup_sorted_dev(C.c_void_p(table.ptr), C.c_size_t(lookup_rows), C.c_void_p(values.ptr), C.c_size_t(value_stride), C.c_size_t(max_per_row),
-                                   C.c_void_p(out.ptr), C.c_size_t(out_stride), C.byref(bad))
+    rc = _lib.kh_lookup_sorted_dev(C.c_void_p(table.ptr), lookup_rows, C.c_void_p(values.ptr), value_stride, max_per_row,
+                                   C.c_void_p(out.ptr), out_stride, C.byref(bad))
     if rc != 0 and bad.value != C.c_size_t(-1).value:
         raise ValueError(bad.value)
     _check(rc)
@@ -826,20 +695,20 @@ class Comm:
     def __init__(self, world: int, rank: int, uid: bytes):
         self._h = C.c_void_p()
         buf = (C.c_uint8 * 128)(*uid)
-        _check(_lib.kh_comm_init(C.c_int(world), C.c_int(rank), buf, C.byref(self._h)))
+        _check(_lib.kh_comm_init(world, rank, buf, C.byref(self._h)))
         self.world, self.rank = world, rank
 
     def allgather_points(self, xy, inf):
         xy = _c64(xy, (-1, 8)); i8 = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
         k = xy.shape[0]
         out = np.zeros((self.world * k, 8), dtype=np.uint64); oinf = np.zeros(self.world * k, dtype=np.uint8)
-        _check(_lib.kh_comm_allgather_points(self._h, _p64(xy), _p8(i8), C.c_size_t(k), _p64(out), _p8(oinf)))
+        _check(_lib.kh_comm_allgather_points(self._h, _p64(xy), _p8(i8), k, _p64(out), _p8(oinf)))
         return out, oinf
 
     def msm_allreduce(self, shard, scalars, mont: bool = True):
         sc = _c64(scalars, (-1, 4))
         out = np.zeros(8, dtype=np.uint64); inf = np.zeros(1, dtype=np.uint8)
-        _check(_lib.kh_msm_allreduce(self._h, shard._h, _p64(sc), C.c_size_t(sc.shape[0]), C.c_int(int(mont)), _p64(out), _p8(inf)))
+        _check(_lib.kh_msm_allreduce(self._h, shard._h, _p64(sc), sc.shape[0], int(mont), _p64(out), _p8(inf)))
         return out, bool(inf[0])
 
     def free(self):
@@ -847,26 +716,19 @@ class Comm:
             _lib.kh_comm_free(self._h); self._h = C.c_void_p()
 
 
-PROVE_CHECK, PROVE_ALL_GATES, PROVE_SHARED_CONTEXT, PROVE_EAGER_CHECK = 1, 2, 4, 8
-PROOF_SECTIONS = {"w_comm": 0, "z_comm": 1, "t_comm": 2, "public_comm": 3, "evals": 4, "public_evals": 5, "ft_eval1": 6, "lr": 7, "delta": 8, "z1_z2": 9, "sg": 10,
-                  "challenges": 11, "lookup_sorted_comm": 12, "lookup_aggreg_comm": 13, "lookup_runtime_comm": 14}
+PROOF_SECTIONS = _sections("KH_PROOF_")
 LOOKUP_PATTERN_IDS = {"Xor": 0, "Lookup": 1, "RangeCheck": 2, "ForeignFieldMul": 3}
 PROOF_PHASES = ("witness_upload", "witness_commit", "z", "quotient", "evaluations", "opening")
-GATE_ZERO = -1                                      # KH_GATE_ZERO: a row without gate constraints
-GATE_LOOKUP = -2                                    # KH_GATE_LOOKUP: GateType::Lookup, a row without gate constraints that carries the Lookup pattern
-VINDEX_SECTIONS = {"sigma_comm": 0, "coefficients_comm": 1, "generic_comm": 2, "selector_comm": 3, "optional_comm": 4, "shifts": 5, "digest": 6,
-                   "lookup_table_comm": 7, "lookup_table_ids_comm": 8, "lookup_selector_comm": 9, "lookup_runtime_selector_comm": 10, "lookup_info": 11}
-LOOKUP_COLUMN_BLOCKS = {"selector_d1": 0, "selector_c": 1, "selector_d8": 2, "table_d1": 3, "table_ids_d1": 4, "atom_d8": 5, "runtime_selector": 6}
+VINDEX_SECTIONS = _sections("KH_VINDEX_")
+LOOKUP_COLUMN_BLOCKS = _sections("KH_LOOKUP_COL_")
 LOOKUP_INFO_FIELDS = ("max_per_row", "max_joint_size", "joint_lookup_used", "uses_runtime_tables", "pattern_mask", "table_columns", "runtime_offset", "runtime_len")
 INDEX_PHASES = ("columns", "transforms", "commitments", "digest")
-WITNESS_GATES, WITNESS_WIRES, WITNESS_LOOKUPS = 1, 2, 4      # KH_WITNESS_*: flags of kh_witness_check (the first two) and kh_witness_check_full
-WITNESS_OK, WITNESS_DISCONNECTED, WITNESS_GATE, WITNESS_LOOKUP = 0, 1, 2, 3
 
 
 def witness_report_message(report: "WitnessReportC", cap: int = 512) -> str:
     """kh_witness_report_message: the report as one line, cut at cap - 1 characters."""
     buf = C.create_string_buffer(max(cap, 1))
-    rc = _lib.kh_witness_report_message(C.byref(report), buf, C.c_size_t(cap))
+    rc = _lib.kh_witness_report_message(C.byref(report), buf, cap)
     if rc < 0:
         _check(rc)
     return buf.value.decode()
@@ -877,8 +739,8 @@ def witness_check(index, witness=None, witness_dev=None, flags: int = WITNESS_GA
     columns.  Returns the filled kh_witness_report_t (kind WITNESS_OK / WITNESS_DISCONNECTED / WITNESS_GATE); bad arguments raise KhError."""
     w = _c64(witness, (15, -1, 4)) if witness is not None else None
     rep = WitnessReportC()
-    _check(_lib.kh_witness_check(index._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
-                                 C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, C.c_uint(flags), C.byref(rep)))
+    _check(_lib.kh_witness_check(index._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
+                                 C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, flags, C.byref(rep)))
     return rep
 
 
@@ -888,16 +750,16 @@ def witness_check_full(index, witness=None, witness_dev=None, runtime=None, flag
     w = _c64(witness, (15, -1, 4)) if witness is not None else None
     rtv = _c64(runtime, (-1, 4)) if runtime is not None else None
     rep, lk = WitnessReportC(), WitnessLookupC()
-    _check(_lib.kh_witness_check_full(index._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
+    _check(_lib.kh_witness_check_full(index._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
                                       C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rtv) if rtv is not None else None,
-                                      C.c_size_t(rtv.shape[0] if rtv is not None else 0), C.c_uint(flags), C.byref(rep), C.byref(lk)))
+                                      rtv.shape[0] if rtv is not None else 0, flags, C.byref(rep), C.byref(lk)))
     return rep, lk
 
 
 def witness_lookup_message(report: "WitnessReportC", lookup: "WitnessLookupC", cap: int = 512) -> str:
     """kh_witness_lookup_message: report and lookup record as one line, cut at cap - 1 characters."""
     buf = C.create_string_buffer(max(cap, 1))
-    rc = _lib.kh_witness_lookup_message(C.byref(report), C.byref(lookup), buf, C.c_size_t(cap))
+    rc = _lib.kh_witness_lookup_message(C.byref(report), C.byref(lookup), buf, cap)
     if rc < 0:
         _check(rc)
     return buf.value.decode()
@@ -911,8 +773,8 @@ class NativeProverIndex:
         self._h = C.c_void_p()
         opt = (C.c_int * max(len(optional_gate_ids), 1))(*optional_gate_ids)
         sh = _c64(shifts, (7, 4)); dg = _c64(digest, (4,))
-        _check(_lib.kh_prover_index_new(srs._h, C.c_uint(log2_n), C.c_uint(zk_rows), C.c_uint(public), C.c_void_p(d1.ptr), C.c_void_p(dc.ptr), C.c_void_p(d8.ptr),
-                                        opt, C.c_size_t(len(optional_gate_ids)), C.c_uint(live_mask), _p64(sh), _p64(dg), C.byref(self._h)))
+        _check(_lib.kh_prover_index_new(srs._h, log2_n, zk_rows, public, C.c_void_p(d1.ptr), C.c_void_p(dc.ptr), C.c_void_p(d8.ptr),
+                                        opt, len(optional_gate_ids), live_mask, _p64(sh), _p64(dg), C.byref(self._h)))
         self._keep = (srs, d1, dc, d8)
 
     @classmethod
@@ -925,8 +787,8 @@ class NativeProverIndex:
         w = np.ascontiguousarray(wires, dtype=np.uint32).reshape(rows, 7, 2)
         co = _c64(coeffs, (rows, 15, 4))
         self._h = C.c_void_p()
-        _check(_lib.kh_prover_index_create(srs._h, C.c_size_t(rows), types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                           _p64(co), C.c_uint(public), C.byref(self._h)))
+        _check(_lib.kh_prover_index_create(srs._h, rows, types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                           _p64(co), public, C.byref(self._h)))
         self._keep = (srs,)
         return self
 
@@ -945,8 +807,8 @@ class NativeProverIndex:
         tc = (LookupTableC * max(len(tdata), 1))(*[LookupTableC(int(i), d.shape[0], d.shape[1], _p64(d)) for (i, _d), d in zip(tables, tdata)])
         rc = (RuntimeTableCfgC * max(len(rdata), 1))(*[RuntimeTableCfgC(int(i), d.shape[0], _p64(d)) for (i, _d), d in zip(runtime_tables, rdata)])
         self._h = C.c_void_p()
-        _check(_lib.kh_prover_index_create_lookup(srs._h, C.c_size_t(rows), types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  _p64(co), C.c_uint(public), tc, C.c_size_t(len(tdata)), rc, C.c_size_t(len(rdata)), C.byref(self._h)))
+        _check(_lib.kh_prover_index_create_lookup(srs._h, rows, types.ctypes.data_as(C.POINTER(C.c_int)), w.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  _p64(co), public, tc, len(tdata), rc, len(rdata), C.byref(self._h)))
         self._keep = (srs,)
         return self
 
@@ -961,7 +823,7 @@ class NativeProverIndex:
         out = {}
         for name, sid in VINDEX_SECTIONS.items():
             lp = C.POINTER(C.c_uint64)(); fp = C.POINTER(C.c_uint8)(); cnt = C.c_size_t(0)
-            _check(_lib.kh_verifier_index_section(self._h, C.c_int(sid), C.byref(lp), C.byref(fp), C.byref(cnt)))
+            _check(_lib.kh_verifier_index_section(self._h, sid, C.byref(lp), C.byref(fp), C.byref(cnt)))
             k = cnt.value
             if fp:
                 out[name] = (np.ctypeslib.as_array(lp, shape=(k, 8)).copy() if k else np.zeros((0, 8), np.uint64),
@@ -977,17 +839,17 @@ class NativeProverIndex:
     def lookup_column(self, block: str, k: int = 0):
         """kh_debug_lookup_column, downloaded: (elems, 4) limbs of column k of a block of LOOKUP_COLUMN_BLOCKS, or None where the index has none."""
         dev = U64P(); cnt = C.c_size_t(0)
-        if _lib.kh_debug_lookup_column(self._h, C.c_int(LOOKUP_COLUMN_BLOCKS[block]), C.c_size_t(k), C.byref(dev), C.byref(cnt)) != 0:
+        if _lib.kh_debug_lookup_column(self._h, LOOKUP_COLUMN_BLOCKS[block], k, C.byref(dev), C.byref(cnt)) != 0:
             return None
         out = np.zeros((cnt.value, 4), dtype=np.uint64)
         sync()
-        _check(_lib.kh_dev_download(_p64(out), C.cast(dev, C.c_void_p), C.c_size_t(out.nbytes)))
+        _check(_lib.kh_dev_download(_p64(out), C.cast(dev, C.c_void_p), out.nbytes))
         return out
 
     def phase_seconds(self):
         """kh_prover_index_phase_seconds: {phase: seconds} of kh_prover_index_create"""
         ph = (C.c_double * 4)()
-        _check(min(0, _lib.kh_prover_index_phase_seconds(self._h, ph, C.c_size_t(4))))
+        _check(min(0, _lib.kh_prover_index_phase_seconds(self._h, ph, 4)))
         return dict(zip(INDEX_PHASES, list(ph)))
 
     def attach_lookup(self, patterns, sel_d1, sel_c, sel_d8, table_cols, table_ids, atoms8):
@@ -995,12 +857,12 @@ class NativeProverIndex:
         m = len(patterns)
         arr = lambda bufs: (C.c_void_p * max(len(bufs), 1))(*[C.c_void_p(b.ptr) for b in bufs])
         ids = (C.c_int * m)(*[LOOKUP_PATTERN_IDS[q] for q in patterns])
-        _check(_lib.kh_prover_index_attach_lookup(self._h, ids, C.c_size_t(m), arr(sel_d1), arr(sel_c), arr(sel_d8), arr(table_cols), C.c_size_t(len(table_cols)),
+        _check(_lib.kh_prover_index_attach_lookup(self._h, ids, m, arr(sel_d1), arr(sel_c), arr(sel_d8), arr(table_cols), len(table_cols),
                                                   C.c_void_p(table_ids.ptr) if table_ids is not None else None, arr(atoms8)))
         self._keep += (sel_d1, sel_c, sel_d8, table_cols, table_ids, atoms8)
 
     def attach_runtime_tables(self, sel_d1, sel_c, sel_d8, offset: int, length: int):
-        _check(_lib.kh_prover_index_attach_runtime_tables(self._h, C.c_void_p(sel_d1.ptr), C.c_void_p(sel_c.ptr), C.c_void_p(sel_d8.ptr), C.c_size_t(offset), C.c_size_t(length)))
+        _check(_lib.kh_prover_index_attach_runtime_tables(self._h, C.c_void_p(sel_d1.ptr), C.c_void_p(sel_c.ptr), C.c_void_p(sel_d8.ptr), offset, length))
         self._keep += (sel_d1, sel_c, sel_d8)
 
     def witness_check(self, witness=None, witness_dev=None, flags: int = WITNESS_GATES | WITNESS_WIRES):
@@ -1012,8 +874,7 @@ class NativeProverIndex:
         return witness_check_full(self, witness, witness_dev, runtime, flags)
 
     def randomness_count(self, witness_on_host: bool) -> int:
-        _lib.kh_prove_randomness_count.restype = C.c_size_t
-        return _lib.kh_prove_randomness_count(self._h, C.c_int(int(witness_on_host)))
+        return _lib.kh_prove_randomness_count(self._h, int(witness_on_host))
 
     def prove(self, witness=None, witness_dev=None, randomness=None, flags: int = PROVE_CHECK, prev=(), runtime=None):
         """kh_prove_full (runtime: (k, 4) limbs, the runtime tables' second column).  witness: (15, rows, 4) limbs on the host, or witness_dev: DevBuf with the padded columns.  randomness:
@@ -1029,16 +890,16 @@ class NativeProverIndex:
         cinf = np.ascontiguousarray(np.concatenate([np.asarray(cm[1], dtype=np.uint8).reshape(-1) for _, cm in prev])) if m else None
         cch = (C.c_size_t * max(m, 1))(*[np.asarray(cm[1]).reshape(-1).shape[0] for _, cm in prev])
         rtv = _c64(runtime, (-1, 4)) if runtime is not None else None
-        _check(_lib.kh_prove_full(self._h, _p64(w) if w is not None else None, C.c_size_t(w.shape[1] if w is not None else 0),
+        _check(_lib.kh_prove_full(self._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
                                        C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rnd) if rnd is not None else None,
-                                       C.c_size_t(rnd.shape[0] if rnd is not None else 0), C.c_uint(flags), _p64(chals) if m else None, rounds,
-                                       _p64(cxy) if m else None, _p8(cinf) if m else None, cch, C.c_size_t(m), _p64(rtv) if rtv is not None else None,
-                                       C.c_size_t(rtv.shape[0] if rtv is not None else 0), C.byref(pr)))
+                                       rnd.shape[0] if rnd is not None else 0, flags, _p64(chals) if m else None, rounds,
+                                       _p64(cxy) if m else None, _p8(cinf) if m else None, cch, m, _p64(rtv) if rtv is not None else None,
+                                       rtv.shape[0] if rtv is not None else 0, C.byref(pr)))
         try:
             out = {}
             for name, sid in PROOF_SECTIONS.items():
                 lp = C.POINTER(C.c_uint64)(); fp = C.POINTER(C.c_uint8)(); cnt = C.c_size_t(0)
-                _check(_lib.kh_proof_section(pr, C.c_int(sid), C.byref(lp), C.byref(fp), C.byref(cnt)))
+                _check(_lib.kh_proof_section(pr, sid, C.byref(lp), C.byref(fp), C.byref(cnt)))
                 k = cnt.value
                 if fp:                                    # points
                     out[name] = (np.ctypeslib.as_array(lp, shape=(k, 8)).copy() if k else np.zeros((0, 8), np.uint64),
@@ -1046,7 +907,7 @@ class NativeProverIndex:
                 else:
                     out[name] = np.ctypeslib.as_array(lp, shape=(k, 4)).copy() if k else np.zeros((0, 4), np.uint64)
             ph = (C.c_double * 6)()
-            _lib.kh_proof_phase_seconds(pr, ph, C.c_size_t(6))
+            _lib.kh_proof_phase_seconds(pr, ph, 6)
             return out, dict(zip(PROOF_PHASES, list(ph)))
         finally:
             _lib.kh_proof_free(pr)
@@ -1238,13 +1099,13 @@ def domain_generator(field: int, log2_n: int):
 def permutation_shifts(field: int, log2_n: int):
     """kh_permutation_shifts: Shifts::new for 2^log2_n rows, (7, 4) Montgomery limbs (host code, no device)."""
     out = np.zeros((7, 4), dtype=np.uint64)
-    _check(_lib.kh_permutation_shifts(C.c_int(field), C.c_uint(log2_n), _p64(out)))
+    _check(_lib.kh_permutation_shifts(field, log2_n, _p64(out)))
     return out
 
 
 class Sponge:
     """kh_sponge_*: the host-side Fiat-Shamir sponges (FQ: DefaultFqSponge of `curve`, FR: DefaultFrSponge of `curve`)."""
-    FQ, FR = 0, 1
+    FQ, FR = _CONSTANTS["KH_SPONGE_FQ"], _CONSTANTS["KH_SPONGE_FR"]
 
     def __init__(self, kind: int, curve: int, _h=None):
         self.kind, self.curve = kind, curve
