@@ -59,8 +59,7 @@ int resolve_basis(kh_srs_t* srs, int basis, unsigned chunk, MsmBasis& out);
 void xyzz_to_affine_batch(const khost::Crv& crv, const std::vector<khost::xyzz>& acc, uint64_t* out_xy, uint8_t* out_inf);
 // context.hip: per (host thread, device)
 hipStream_t thread_copy_stream();
-static constexpr int UPLOAD_CHUNKS = 8;
-hipEvent_t* thread_upload_events();
+hipEvent_t thread_upload_event();          // kh_msm_submit_host: orders the job's first kernel behind the upload on the copy stream
 // msm_api.cpp
 int acquire_slot(std::unique_lock<std::mutex>* lk, Context& C, bool side_first = false);
 const char* slot_error(int si);

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "api_internal.hpp"
+#include "env.hpp"
 
 namespace kh {
 
@@ -83,7 +84,7 @@ int Context::stage_upload(void* dst_dev, std::initializer_list<std::pair<const v
     size_t total = 0;
     for (const auto& pr : parts) total += pr.second;
     if (total == 0) return KH_OK;
-    static const bool put_kernel = !(getenv("KH_STAGE_PUT") && atoi(getenv("KH_STAGE_PUT")) == 0);
+    static const bool put_kernel = env_flag("KH_STAGE_PUT", true);
     if (put_kernel && total <= sizeof(StageBlob) && total % 4 == 0 && ((uintptr_t)dst_dev & 3) == 0) {
         StageBlob b;
         size_t o = 0;
@@ -205,16 +206,15 @@ hipStream_t kh::thread_copy_stream() {
     return tl.s[d];
 }
 
-// events of the chunked scalar upload (MsmHostScalars), per (host thread, device)
+// the event behind the scalar upload of kh_msm_submit_host, per (host thread, device)
 struct ThreadUploadEvents {
-    hipEvent_t e[KH_MAX_DEVICES][UPLOAD_CHUNKS] = {{nullptr}};
-    ~ThreadUploadEvents() { for (auto& row : e) for (hipEvent_t x : row) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t e[KH_MAX_DEVICES] = {nullptr};
+    ~ThreadUploadEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
-hipEvent_t* kh::thread_upload_events() {
+hipEvent_t kh::thread_upload_event() {
     static thread_local ThreadUploadEvents tl;
     const int d = kh::ctx().device >= 0 && kh::ctx().device < KH_MAX_DEVICES ? kh::ctx().device : 0;
-    for (int i = 0; i < UPLOAD_CHUNKS; i++)
-        if (!tl.e[d][i] && hipEventCreateWithFlags(&tl.e[d][i], hipEventDisableTiming) != hipSuccess) { kh::set_error("hipEventCreate for an upload event failed"); return nullptr; }
+    if (!tl.e[d] && hipEventCreateWithFlags(&tl.e[d], hipEventDisableTiming) != hipSuccess) { kh::set_error("hipEventCreate for an upload event failed"); return nullptr; }
     return tl.e[d];
 }
 
@@ -238,7 +238,7 @@ struct DevPool {
     size_t cached[KH_MAX_DEVICES] = {0};
 };
 DevPool& dev_pool() { static DevPool p; return p; }
-size_t pool_limit() { static const size_t lim = (getenv("KH_POOL_MAX_MB") ? (size_t)atol(getenv("KH_POOL_MAX_MB")) : 2048) << 20; return lim; }
+size_t pool_limit() { static const size_t lim = (size_t)env_int("KH_POOL_MAX_MB", 2048) << 20; return lim; }
 }  // namespace
 static void dev_pool_trim(int device) {
     DevPool& P = dev_pool();

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/kimchi_hip.h"
+#include "env.hpp"
 #include "host_ec.hpp"
 
 namespace kh { void set_error(const char* fmt, ...); }
@@ -297,7 +298,7 @@ template <int FID> struct IfmaPerm {
 #undef KH_IFMA
 static bool ifma_usable() {
     static const bool ok = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma") && __builtin_cpu_supports("avx512vl") &&
-                           __builtin_cpu_supports("avx512dq") && !(getenv("KH_NO_IFMA") && atoi(getenv("KH_NO_IFMA")) != 0);
+                           __builtin_cpu_supports("avx512dq") && !kh::env_flag("KH_NO_IFMA", false);
     return ok;
 }
 #else

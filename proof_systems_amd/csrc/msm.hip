@@ -29,6 +29,7 @@
 #include <hip/hip_ext.h>
 #include <math.h>
 #include "common.hpp"
+#include "env.hpp"
 #include "curve.cuh"
 #include "coop.cuh"
 #include "field29.cuh"
@@ -1765,12 +1766,12 @@ struct VestaCfg { typedef FqParams Base; typedef FpParams Scalar; };
 struct PallasCfg { typedef FpParams Base; typedef FqParams Scalar; };
 
 static std::atomic<size_t>& wide_min_n_cell() {
-    static std::atomic<size_t> v{getenv("KH_WIDE_MIN_N") ? (size_t)strtoull(getenv("KH_WIDE_MIN_N"), nullptr, 0) : ((size_t)1 << 19)};
+    static std::atomic<size_t> v{(size_t)env_int("KH_WIDE_MIN_N", 1 << 19)};
     return v;
 }
 // the staged scatter of k_part2_sort: [0] entries per pass in LDS (KH_PART2_STAGE, 0 = the direct scatter), [1] the most passes a partition may take (KH_PART2_MAXPASS)
 static std::atomic<u32>& sort_staging_cell(int i) {
-    static std::atomic<u32> v[2] = {{getenv("KH_PART2_STAGE") ? (u32)atoi(getenv("KH_PART2_STAGE")) : 28672u}, {getenv("KH_PART2_MAXPASS") ? (u32)atoi(getenv("KH_PART2_MAXPASS")) : 2u}};
+    static std::atomic<u32> v[2] = {{(u32)env_int("KH_PART2_STAGE", 28672)}, {(u32)env_int("KH_PART2_MAXPASS", 2)}};
     return v[i];
 }
 void msm_set_sort_staging(unsigned entries, unsigned max_passes) { sort_staging_cell(0).store(entries); sort_staging_cell(1).store(max_passes); }
@@ -1814,7 +1815,7 @@ static KTab task_length_table(size_t nkeys, u32 cus) {
 
 template <class CFG>
 static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t offset, const u64* scalars_dev, size_t n, size_t k,
-                         int mont, int curve, int flags, const MsmHostScalars* hs) {
+                         int mont, int curve, int flags) {
     typedef typename CFG::Base BF; typedef typename CFG::Scalar SF;
     hipStream_t s = C.stream;
     // wide windows (a second table set, c = 20: msm.hpp) for big single MSMs: 13 instead of 16 additions per scalar.  Needs the wide sort's
@@ -1930,9 +1931,9 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         KH_HIP(hipFuncSetAttribute((const void*)k_sort_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
     }
     // small jobs over the tables: the whole sort in one launch (k_sort_fused)
-    static const bool fused_off = getenv("KH_NO_FUSED_SORT") != nullptr;
+    static const bool fused_off = env_flag("KH_NO_FUSED_SORT", false);
     // bounded spin of its grid barriers: 20 ms of the 100 MHz wall clock by default (a barrier normally waits < 50 us)
-    static const unsigned long long fused_spin_ticks = 100ull * (getenv("KH_FUSED_SPIN_US") ? (unsigned long long)atoll(getenv("KH_FUSED_SPIN_US")) : 20000ull);
+    static const unsigned long long fused_spin_ticks = 100ull * (unsigned long long)env_int("KH_FUSED_SPIN_US", 20000);
     FusedGeom fg{};
     // (co-residency of the spinning blocks is what makes the grid barriers safe: 64 blocks x 4 jobs in flight need 128 CUs -- not in a partitioned mode)
     bool fused = precomp && !wide && !fused_off && !Ctx.fused_disabled && k <= 4 && M < ((size_t)1 << 22) && nb >= 2048 && Ctx.num_cus >= 128;
@@ -1974,7 +1975,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         C.spread_abort = (volatile uint32_t*)hp; *C.spread_abort = 0;
     }
     // completion by flag (MsmSlot::done_flag): pinned word + two device words, once per slot
-    static const bool flag_off = getenv("KH_NO_DONE_FLAG") != nullptr;
+    static const bool flag_off = env_flag("KH_NO_DONE_FLAG", false);
     bool flag_on = !flag_off && (wide || planes) && !C.flag_unavailable && C.pinned_coherent;
     if (flag_on && !C.done_flag) {
         void* hp = nullptr;
@@ -1988,17 +1989,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     }
     C.timer.begin(s);
     // 1 digits
-    if (hs && hs->nev > 0 && k == 1) {    // upload and digit pass chunk by chunk (MsmHostScalars)
-        for (int ch = 0; ch < hs->nev; ch++) {
-            const size_t c0 = n * (size_t)ch / hs->nev, c1 = n * (size_t)(ch + 1) / hs->nev;
-            if (c1 == c0) continue;
-            KH_HIP(hipMemcpyAsync((char*)scalars_dev + c0 * 32, (const char*)hs->host + c0 * 32, (c1 - c0) * 32, hipMemcpyHostToDevice, hs->cs));
-            KH_HIP(hipEventRecord(hs->ev[ch], hs->cs));
-            KH_HIP(hipStreamWaitEvent(s, hs->ev[ch], 0));
-            hipLaunchKernelGGL((k_digits<SF>), dim3((unsigned)((c1 - c0 + 255) / 256), 1u), dim3(256), 0, s,
-                               scalars_dev, basis.inf, offset, basis.batch_stride, n, mont, c, W, C.ws_digits.as<int32_t>(), c0, c1);
-        }
-    } else if (glv)
+    if (glv)
     hipLaunchKernelGGL((k_digits_glv<SF>), dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s,
                        scalars_dev, basis.inf, offset, basis.batch_stride, n, mont, c, W, C.ws_digits.as<int32_t>());
     else
@@ -2158,7 +2149,7 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
             hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, (unsigned)ngroups), dim3(64), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         // the weighted tail is 3 x ngroups blocks however many MSMs there are: a pure latency chain (10 additions deep), so it takes the
         // lane-cooperative kernel for batches too (15 witness columns: 96 -> 35 us); the records have the same 128-byte layout
-        static const bool fin_quad = !getenv("KH_NO_FIN_QUAD");
+        static const bool fin_quad = !env_flag("KH_NO_FIN_QUAD", false);
         if (few_groups || fin_quad) {                      // straight into the pinned host staging
             hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
             direct_out = true;
@@ -2185,15 +2176,15 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
 }
 
 int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t offset, const uint64_t* scalars_dev, size_t n, size_t k, int mont,
-                int flags, const MsmHostScalars* hs) {
+                int flags) {
     if (n == 0 || k == 0) {          // nothing to launch (MsmJob::ngroups = 0): finish() emits k identities
         S.busy = true; S.owner = std::this_thread::get_id(); S.ticket = C.next_ticket++;
         S.job = {basis, offset, scalars_dev, n, k, mont, curve};
         KH_HIP(hipEventRecord(S.done, S.stream));
         return KH_OK;
     }
-    if (curve == KH_CURVE_VESTA) return msm_enqueue_t<VestaCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags, hs);
-    return msm_enqueue_t<PallasCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags, hs);
+    if (curve == KH_CURVE_VESTA) return msm_enqueue_t<VestaCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags);
+    return msm_enqueue_t<PallasCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags);
 }
 
 // an aborted job again, from its inputs and without the caller's flags, under the same ticket; waits for it
@@ -2230,7 +2221,7 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
         S.job.spread_rerun = true;
     }
     S.busy = false;
-    static const bool fused_dbg = getenv("KH_FUSED_DEBUG") != nullptr;
+    static const bool fused_dbg = env_flag("KH_FUSED_DEBUG", false);
     if (fused_dbg && S.ws_sync.p) {                       // phase timestamps of the last k_sort_fused on this slot (block 0)
         unsigned long long ts[12]; (void)hipMemcpy(ts, S.ws_sync.as<u32>() + 2 + 2 * FUSED_B, sizeof(ts), hipMemcpyDeviceToHost);
         fprintf(stderr, "k_sort_fused phases (us):"); for (int i = 1; i < 9; i++) fprintf(stderr, " %.1f", (double)(ts[i] - ts[i - 1]) / 100.0);

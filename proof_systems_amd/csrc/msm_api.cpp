@@ -4,6 +4,7 @@
 #include <chrono>
 
 #include "api_internal.hpp"
+#include "env.hpp"
 
 using namespace kh;
 
@@ -40,7 +41,7 @@ int kh::acquire_slot(std::unique_lock<std::mutex>* lk, Context& C, bool side_fir
         }
         // A slot whose owner leaked its ticket (an exception between kh_msm_submit and kh_msm_wait, a thread that exited) never frees: after a
         // long deadline -- far beyond any MSM, KH_SLOT_WAIT_S, default 30 s -- give up with an error instead of hanging every later caller.
-        static const long slot_wait_s = getenv("KH_SLOT_WAIT_S") ? atol(getenv("KH_SLOT_WAIT_S")) : 30;
+        static const long slot_wait_s = (long)env_int("KH_SLOT_WAIT_S", 30);
         if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(slot_wait_s)) return -2;
         C.blocked_owners.insert(me);
         C.cv.wait_for(*lk, std::chrono::milliseconds(50));  // (the time-out re-evaluates the deadlock test and the deadline)
@@ -63,28 +64,15 @@ static int msm_submit_locked(Context& C, kh_srs_t* srs, int basis, unsigned chun
     if (lk && (rc = resolve_basis(srs, basis, chunk, b))) return rc;     // acquire_slot may have dropped the lock: the basis map can have changed
     MsmSlot& S = C.slot[si];
     const uint64_t* sdev = scalars;
-    // a big single MSM from host scalars: upload and digit pass in chunks on the calling thread's copy stream (MsmHostScalars) -- the other slots' jobs keep
-    // the GPU busy meanwhile (kh_msm_submit_host: two in flight hide the whole upload), and a lone MSM hides its digit pass
-    // (KH_HOST_CHUNK_MIN=n switches it on for MSMs of >= n scalars; off by default: at 2^20 the chunked upload measured level with the single copy -- what
-    // pipelines the PCIe transfer under the neighbouring job's accumulation is kh_msm_submit_host itself, not the chunking: profiles/r06_host_msm*.txt)
-    static const size_t chunked_min = getenv("KH_HOST_CHUNK_MIN") ? (size_t)atol(getenv("KH_HOST_CHUNK_MIN")) : 0;     // scalars; 0 = never
-    MsmHostScalars hs{}; const MsmHostScalars* hsp = nullptr;
-    if (!scalars_on_device && k == 1 && chunked_min && use >= chunked_min) {
-        if ((rc = S.ws_scalars.reserve(use * 32))) return rc;
-        hs.host = scalars; hs.cs = thread_copy_stream(); hs.ev = thread_upload_events();
-        if (!hs.cs || !hs.ev) return KH_E_DEVICE;
-        hs.nev = (int)std::min<size_t>(UPLOAD_CHUNKS, std::max<size_t>(1, use >> 16));       // >= 2 MB per chunk
-        hsp = &hs; sdev = S.ws_scalars.as<uint64_t>();
-    } else
     if (!scalars_on_device && use > 0 && k > 0) {
         if ((rc = S.ws_scalars.reserve(k * use * 32))) return rc;
         // (host_async: kh_msm_submit_host returns while the job runs -- its copies go on the calling thread's copy stream, which that call waits for)
-        hipStream_t up = S.stream; hipEvent_t* uev = nullptr;
-        if (host_async) { up = thread_copy_stream(); uev = thread_upload_events(); if (!up || !uev) return KH_E_DEVICE; }
+        hipStream_t up = S.stream; hipEvent_t uev = nullptr;
+        if (host_async) { up = thread_copy_stream(); uev = thread_upload_event(); if (!up || !uev) return KH_E_DEVICE; }
         if (use == n) KH_HIP(hipMemcpyAsync(S.ws_scalars.p, scalars, k * n * 32, hipMemcpyHostToDevice, up));
         else for (size_t j = 0; j < k; j++)
             KH_HIP(hipMemcpyAsync((char*)S.ws_scalars.p + j * use * 32, scalars + j * n * 4, use * 32, hipMemcpyHostToDevice, up));
-        if (host_async) { KH_HIP(hipEventRecord(uev[0], up)); KH_HIP(hipStreamWaitEvent(S.stream, uev[0], 0)); }
+        if (host_async) { KH_HIP(hipEventRecord(uev, up)); KH_HIP(hipStreamWaitEvent(S.stream, uev, 0)); }
         sdev = S.ws_scalars.as<uint64_t>();
     } else if (scalars_on_device) {
         KH_REQUIRE(use == n || k == 1, "device-resident batched scalars must not exceed the basis window");
@@ -92,11 +80,7 @@ static int msm_submit_locked(Context& C, kh_srs_t* srs, int basis, unsigned chun
         // the event recorded right behind the last such producer (NOT for whatever else slot 0's stream has queued since)
         if (C.main_dirty && S.stream != C.stream) KH_HIP(hipStreamWaitEvent(S.stream, C.order_ev, 0));
     }
-    rc = msm_enqueue(C, S, srs->curve, b, offset, sdev, use, k, mont, 0, hsp);
-    if (rc) {
-        if (hsp) (void)hipStreamSynchronize(hs.cs);      // a caller that sees an error may free its scalars at once: no copy may still be reading them
-        return rc;
-    }
+    if ((rc = msm_enqueue(C, S, srs->curve, b, offset, sdev, use, k, mont))) return rc;
     *slot_out = si;
     return KH_OK;
 }
@@ -115,7 +99,7 @@ int kh::wait_then_finish(std::unique_lock<std::mutex>& lk, Context& C, MsmSlot& 
     const auto tw0 = std::chrono::steady_clock::now();
     // a synchronous caller is latency-bound (an opening round is ~0.4 ms of GPU time, then ~40 us of transcript on this thread):
     // poll for up to a millisecond before blocking -- the blocking wait's wake-up alone costs 10-20 us
-    static const long spin_us = getenv("KH_SPIN_US") ? atol(getenv("KH_SPIN_US")) : 1000;
+    static const long spin_us = (long)env_int("KH_SPIN_US", 1000);
     hipError_t e = hipErrorNotReady;
     bool flag_seen = false;
     if (spin_us > 0) {
@@ -175,34 +159,11 @@ static int msm_common(kh_srs_t* srs, int basis, unsigned chunk, size_t offset, c
     int rc = ensure_init(); if (rc) return rc;
     Context& C = ctx();
     std::unique_lock<std::mutex> lk(C.mu);
-    static const bool coalesce_on = !(getenv("KH_NO_COALESCE") && atoi(getenv("KH_NO_COALESCE")) != 0);
+    static const bool coalesce_on = !env_flag("KH_NO_COALESCE", false);
     const auto now = std::chrono::steady_clock::now();
     const bool burst = C.last_sync_msm_arrival.time_since_epoch().count() != 0 &&
                        std::chrono::duration_cast<std::chrono::microseconds>(now - C.last_sync_msm_arrival).count() < 200;
     C.last_sync_msm_arrival = now;
-    // KH_HOST_SPLIT_MIN=n (experiment, off by default): a lone host-scalar MSM of >= n scalars as TWO half-range MSMs on two slots, each with its own upload.
-    // Measured (round 6, profiles/r06_host_msm*.txt): no gain -- 1.91-1.98 ms either way at 2^20.  The host thread stages the two uploads one after the
-    // other (~0.45 ms each incl. the pinning of the pageable pages), so the second half's kernels cannot start before ~1.2 ms and then need 0.75 ms: the
-    // bound is (all uploads) + (the last piece's whole pipeline), and an uneven cut would reach ~1.75 ms at best.
-    static const size_t split_min = getenv("KH_HOST_SPLIT_MIN") ? (size_t)atol(getenv("KH_HOST_SPLIT_MIN")) : 0;
-    if (!scalars_on_device && k == 1 && srs != nullptr && !burst && split_min && n >= split_min) {
-        MsmBasis b;
-        if (resolve_basis(srs, basis, chunk, b) == KH_OK && offset <= b.n && b.precomp_c) {
-            const size_t use = n < b.n - offset ? n : b.n - offset, h = use / 2;
-            if (h >= MSM_PRECOMP_MIN_N) {
-                int s0 = -1, s1 = -1;
-                if ((rc = msm_submit_locked(C, srs, basis, chunk, offset, scalars, false, h, 1, mont, &s0, &lk))) return rc;
-                uint64_t xy[16]; uint8_t inf[2] = {1, 1};
-                rc = msm_submit_locked(C, srs, basis, chunk, offset + h, scalars + 4 * h, false, use - h, 1, mont, &s1, &lk);
-                const int rc0 = wait_then_finish(lk, C, C.slot[s0], xy, inf);          // (whatever the second submit said: the first job is in flight)
-                if (rc) return rc;
-                if ((rc = wait_then_finish(lk, C, C.slot[s1], xy + 8, inf + 1))) return rc;
-                if (rc0) return rc0;
-                lk.unlock();
-                return kh_points_sum(srs->curve, xy, inf, 2, out_xy, out_inf);
-            }
-        }
-    }
     bool eligible = coalesce_on && !scalars_on_device && k == 1 && n >= MSM_PRECOMP_MIN_N && srs != nullptr;
     if (eligible) {                                       // whole-window MSMs only (the ragged tail of a chunked polynomial goes alone)
         MsmBasis b; if (resolve_basis(srs, basis, chunk, b) != KH_OK || offset > b.n || n > b.n - offset) eligible = false;

@@ -26,6 +26,7 @@
 #include <tuple>
 
 #include "common.hpp"
+#include "env.hpp"
 #include "field.cuh"
 #include "host_ec.hpp"
 #include "msm.hpp"
@@ -372,7 +373,7 @@ static int get_twiddles(Context& C, int field, unsigned logn, int inverse, TwEnt
 // Largest sub-transform of a pass: KH_NTT_MAX_LOGR at start-up, kh_ntt_set_max_logr afterwards (4..10; 0 = back to the default).  The twiddle tables hold every
 // power of the root, so they do not depend on the split and a change takes effect with the next transform.
 static std::atomic<unsigned>& max_logr_cell() {
-    static std::atomic<unsigned> v(getenv("KH_NTT_MAX_LOGR") ? (unsigned)std::min(10, std::max(4, atoi(getenv("KH_NTT_MAX_LOGR")))) : (unsigned)NTT_MAX_LOGR);
+    static std::atomic<unsigned> v((unsigned)std::min(10ll, std::max(4ll, env_int("KH_NTT_MAX_LOGR", NTT_MAX_LOGR))));
     return v;
 }
 unsigned ntt_max_logr() { return max_logr_cell().load(std::memory_order_relaxed); }

@@ -4,8 +4,12 @@
 #include <chrono>
 
 #include "api_internal.hpp"
+#include "env.hpp"
 
 using namespace kh;
+
+// KH_IPA_TIMING: the phase split of every opening on stderr
+static bool ipa_timing() { static const bool v = env_flag("KH_IPA_TIMING", false); return v; }
 
 struct EndoPair { uint64_t q[4], r[4]; };
 static const EndoPair& cached_endos(int curve) {
@@ -271,7 +275,6 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     } claim{srs};
     Context& C = ctx();
     std::unique_lock<std::mutex> lk(C.mu);
-    static const bool begin_timing = getenv("KH_IPA_TIMING") != nullptr;
     const auto b1_ = std::chrono::steady_clock::now();
     std::unique_ptr<kh_ipa> st(new kh_ipa);
     st->srs = srs; st->curve = srs->curve; st->field = khost::scalar_field_id(srs->curve); st->n = n; st->cur = n;
@@ -296,15 +299,15 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     // Plan the rebase (csrc/rebase.hip): the folded basis of N = 2^KH_IPA_REBASE_LOGN points (default 2^11; at least three rounds folded into it, at least 64
     // points) with window tables of KH_IPA_REBASE_C bits (default 13: 20 windows, 2^12 buckets), materialised from the c = 16 tables.  KH_IPA_REBASE=0: never.
     {
-        static const bool rb_on = !(getenv("KH_IPA_REBASE") && atoi(getenv("KH_IPA_REBASE")) == 0);
-        static const unsigned rb_logn = getenv("KH_IPA_REBASE_LOGN") ? (unsigned)atoi(getenv("KH_IPA_REBASE_LOGN")) : 11u;     // 2^16 proof, opening: 5.39 (off) / 5.26 (2^9) / 5.17 (2^10) / 5.11 (2^11) / 5.34 (2^12) ms: profiles/r06_rebase_sweep.txt
-        static const int rb_c = getenv("KH_IPA_REBASE_C") ? std::min(16, std::max(7, atoi(getenv("KH_IPA_REBASE_C")))) : 13;     // 13: 20 windows, the top one still 8 bits wide (12, 14: a 3-bit top window = hot buckets)
+        static const bool rb_on = env_flag("KH_IPA_REBASE", true);
+        static const unsigned rb_logn = (unsigned)env_int("KH_IPA_REBASE_LOGN", 11);     // 2^16 proof, opening: 5.39 (off) / 5.26 (2^9) / 5.17 (2^10) / 5.11 (2^11) / 5.34 (2^12) ms: profiles/r06_rebase_sweep.txt
+        static const int rb_c = (int)std::min(16ll, std::max(7ll, env_int("KH_IPA_REBASE_C", 13)));     // 13: 20 windows, the top one still 8 bits wide (12, 14: a 3-bit top window = hot buckets)
         unsigned logn = 0; while (((size_t)1 << logn) < n) logn++;
         if (rb_on && srs->g_precomp_c == 16 && logn >= 9) {
             const unsigned ln = std::max(6u, std::min(rb_logn, logn - 3));
             const size_t N = (size_t)1 << ln, Q = n >> ln;
             // KH_IPA_REBASE_GLV (default on): tables for the lower 128 bits and phi of them; off when the generated constants' eigenvalue is not this curve's endo_r
-            static const bool glv_env = !(getenv("KH_IPA_REBASE_GLV") && atoi(getenv("KH_IPA_REBASE_GLV")) == 0);
+            static const bool glv_env = env_flag("KH_IPA_REBASE_GLV", true);
             bool glv_ok = glv_env;
             if (glv_ok) {
                 khost::Fld SFc(khost::scalar_field_id(srs->curve));
@@ -351,7 +354,7 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     KH_HIP(hipMemcpyAsync(st->coef[0].p, &ones[st->field & 1], 32, hipMemcpyHostToDevice, s));
     if (kind != hipMemcpyDeviceToDevice) KH_HIP(hipStreamSynchronize(s));      // host inputs may be the caller's temporaries
     KH_HIP(hipEventRecord(st->ev, s));
-    if (begin_timing) {
+    if (ipa_timing()) {
         auto us = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
         fprintf(stderr, "kh_ipa_begin: workspace %.0f us, U multiples %.0f, uploads + copies %.0f\n", us(b1_, b2_), us(b2_, b3_), us(b3_, std::chrono::steady_clock::now()));
     }
@@ -396,7 +399,7 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
     KH_REQUIRE(st && rand_l && rand_r && lr_xy && lr_inf, "kh_ipa_round_lr: null argument");
     KH_REQUIRE(st->cur > 1, "no round left: the vectors are folded to length 1");
     KH_REQUIRE(!st->lr_done, "kh_ipa_round_fold must follow kh_ipa_round_lr");
-    static const bool prof = getenv("KH_IPA_TIMING") != nullptr;
+    const bool prof = ipa_timing();
     const auto pt0 = std::chrono::steady_clock::now();
     auto us_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); };
     Context& C = ctx();
@@ -409,7 +412,7 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
     st->round_no++;
     // the rebase (csrc/rebase.hip): switch to the materialised folded basis as soon as its tables are complete
     if (st->rb_state == 2) {
-        static const bool rb_wait = getenv("KH_IPA_REBASE_WAIT") && atoi(getenv("KH_IPA_REBASE_WAIT")) != 0;      // tests: the earliest possible switch, deterministically
+        static const bool rb_wait = env_flag("KH_IPA_REBASE_WAIT", false);      // tests: the earliest possible switch, deterministically
         if (rb_wait) KH_HIP(hipEventSynchronize(srs->ipa_rb_done));
         const hipError_t qe = hipEventQuery(srs->ipa_rb_done);
         if (qe == hipSuccess) {
@@ -419,8 +422,7 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
                 st->n = st->rb_N; st->ncoef >>= st->rb_j0;
                 st->round_tab = srs->ipa_rb_tab.p; st->round_c = st->rb_c; st->tab_stride = st->rb_N + 2;
                 st->rb_state = 3; counter(CNT_REBASE_SWITCH)++;
-                static const bool rb_say = getenv("KH_IPA_TIMING") != nullptr;
-                if (rb_say) fprintf(stderr, "kh_ipa: round %u runs over the rebased tables (%zu points, c = %d, %u rounds folded in)\n", st->round_no, st->rb_N, st->rb_c, st->rb_j0);
+                if (ipa_timing()) fprintf(stderr, "kh_ipa: round %u runs over the rebased tables (%zu points, c = %d, %u rounds folded in)\n", st->round_no, st->rb_N, st->rb_c, st->rb_j0);
             }
         } else if (qe != hipErrorNotReady) { KH_HIP(qe); }
         else (void)hipGetLastError();
@@ -630,7 +632,6 @@ int kh_ipa_open(kh_srs_t* srs, const uint64_t* a_dev, size_t a_len, const uint64
         else sh = SF.sub(cip, acc);
         int rc = kh_sponge_absorb_fr(sponge, sh.l, 1); if (rc) return rc;
     }
-    static const bool ipa_timing = getenv("KH_IPA_TIMING") != nullptr;      // phase split of one opening on stderr
     const auto tp0 = std::chrono::steady_clock::now();
     uint64_t t[4], u_base[8];
     int rc = kh_sponge_squeeze_field(sponge, t); if (rc) return rc;
@@ -655,7 +656,7 @@ int kh_ipa_open(kh_srs_t* srs, const uint64_t* a_dev, size_t a_len, const uint64
         const auto q2 = std::chrono::steady_clock::now();
         if ((rc = kh_ipa_round_fold(st, chal, u, ui))) return rc;
         memcpy(u_last, u, 32); chal_last[0] = chal[0]; chal_last[1] = chal[1];
-        if (ipa_timing) {
+        if (ipa_timing()) {
             const auto q3 = std::chrono::steady_clock::now();
             if (r < 32) per_round_us[r] = std::chrono::duration<double, std::micro>(q1 - q0).count();
             t_lr += std::chrono::duration<double, std::micro>(q1 - q0).count(); t_sponge += std::chrono::duration<double, std::micro>(q2 - q1).count();
@@ -696,7 +697,7 @@ int kh_ipa_open(kh_srs_t* srs, const uint64_t* a_dev, size_t a_len, const uint64
     scalar_challenge_to_field(sfield, cc, cached_endos(curve).r, c);
     const khost::fe z1v = SF.add(SF.mul(fe_of(a0), fe_of(c)), d), z2v = SF.add(SF.mul(r_prime, fe_of(c)), r_delta);
     memcpy(z1, &z1v, 32); memcpy(z2, &z2v, 32);
-    if (ipa_timing) {
+    if (ipa_timing()) {
         auto us = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
         { const IpaRoundProf P = tl_round_prof; tl_round_prof = IpaRoundProf();
           fprintf(stderr, "kh_ipa_open: per round inside launch + wait + finish: slot %.1f us, step kernel launch %.1f, MSM enqueue %.1f, wait %.1f, finish %.1f\n",

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/kimchi_hip.h"
+#include "env.hpp"
 #include "host_ec.hpp"
 #include "witness_lookup.hpp"
 
@@ -883,7 +884,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     if (!ix || !out || (!witness == !witness_dev)) { kh::set_error("kh_prove: give the witness either on the host or on the device"); return KH_E_INVALID; }
     if (n_prev && (!prev_chals || !prev_rounds || !prev_comm_xy || !prev_comm_inf || !prev_comm_chunks)) { kh::set_error("kh_prove_recursive: null previous-challenge argument"); return KH_E_INVALID; }
     const bool check = flags & KH_PROVE_CHECK, all_gates = flags & KH_PROVE_ALL_GATES;
-    static const bool eager_env = getenv("KH_PROVE_EAGER_CHECK") && atoi(getenv("KH_PROVE_EAGER_CHECK")) != 0;
+    static const bool eager_env = kh::env_flag("KH_PROVE_EAGER_CHECK", false);
     const bool eager = check && ((flags & KH_PROVE_EAGER_CHECK) || eager_env);       // fail at the phase the reference fails at (a stream stall per check)
     const int fid = ix->fid, curve = ix->curve;
     const unsigned logn = ix->logn;
@@ -900,7 +901,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     } private_context;
     if (!(flags & KH_PROVE_SHARED_CONTEXT) && !kh_private_context_active()) {
         KP(kh_private_context_begin()); private_context.mine = true;
-        static const bool keep_timers = getenv("KH_PROVE_TIMERS") && atoi(getenv("KH_PROVE_TIMERS")) != 0;
+        static const bool keep_timers = kh::env_flag("KH_PROVE_TIMERS", false);
         KP(kh_set_phase_timers(keep_timers ? 1 : 0));    // (this context is ours for the call: no per-phase events between the kernels of the proof; a pooled context may come with them on)
     }
     // ---- the randomness of the whole proof, in the reference's draw order
@@ -965,11 +966,11 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     };
     // ---- witness on the device: [w 0..14 | z] in evaluation form
     Dev ev; KP(ev.alloc(16 * NB));
-    struct Tickets {                                  // un-waited MSM tickets: an error on the way out must not leave their pipeline slots taken
-        uint64_t t[4] = {0, 0, 0, 0}; bool live[4] = {false, false, false, false};
-        ~Tickets() { for (int i = 0; i < 4; i++) if (live[i]) { uint64_t xy[8 * COLUMNS]; uint8_t inf[COLUMNS]; (void)kh_msm_wait(t[i], xy, inf); } }
-        int wait(int i, uint64_t* xy, uint8_t* inf) { live[i] = false; return kh_msm_wait(t[i], xy, inf); }
-    } tickets;
+    struct Ticket {                                   // the un-waited MSM ticket (one at a time): an error on the way out must not leave its pipeline slot taken
+        uint64_t t = 0; bool live = false;
+        ~Ticket() { if (live) { uint64_t xy[8 * COLUMNS]; uint8_t inf[COLUMNS]; (void)kh_msm_wait(t, xy, inf); } }
+        int wait(uint64_t* xy, uint8_t* inf) { live = false; return kh_msm_wait(t, xy, inf); }
+    } ticket;
     // The witness arrives over PCIe in 0.6 ms at 2^16 rows (31 MB), and nothing of the proof can start without it -- except the columns' own interpolation and
     // extension, which need one column each.  So the columns travel in groups (KH_PROVE_UPLOAD_GROUPS, default 3; 1 = one transfer as before) and every group but
     // the last has its copy -> iNTT -> LDE queued behind its transfer: that work (2/3 of 0.37 ms) runs underneath the next group's transfer instead of underneath
@@ -990,8 +991,6 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
         return rc_;
     };
     size_t cols_pending = 0;                           // first column whose interpolation / extension is not queued yet
-    static const bool commit_per_group = getenv("KH_PROVE_COMMIT_PER_GROUP") && atoi(getenv("KH_PROVE_COMMIT_PER_GROUP")) != 0;
-    size_t commit_groups = 0, group_c0[4] = {0, 0, 0, 0};
     if (witness) {
         KP_REQUIRE(rows + zk <= n, "NoRoomForZkInWitness: %zu rows + %zu zero-knowledge rows > %zu", rows, zk, n);
         if (rows + zk < n) KP(kh_dev_memset_zero(ev.p, 16 * NB * 32));
@@ -999,7 +998,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
         std::vector<fe> zkr(COLUMNS * zk);
         for (size_t c = 0; c < COLUMNS; c++) for (size_t j = 0; j < zk; j++) zkr[c * zk + j] = z[c * zk + (zk - 1 - j)];
         KP(kh_dev_upload_2d(ev.at(n - zk), NB * 32, zkr.data(), zk * 32, zk * 32, COLUMNS));
-        static const size_t groups_env = getenv("KH_PROVE_UPLOAD_GROUPS") ? (size_t)atoi(getenv("KH_PROVE_UPLOAD_GROUPS")) : 3;
+        static const size_t groups_env = (size_t)kh::env_int("KH_PROVE_UPLOAD_GROUPS", 3);
         const size_t groups = (rows == 0 || groups_env < 1 || nch != 1 || n < 4096) ? 1 : (groups_env > COLUMNS ? COLUMNS : groups_env);
         for (size_t g = 0; g < groups && rows; g++) {
             const size_t c0 = COLUMNS * g / groups, c1 = COLUMNS * (g + 1) / groups;
@@ -1007,10 +1006,6 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
             if (groups > 1) KP(kh_dev_upload_2d_unordered(ev.at(c0 * NB), NB * 32, witness + 4 * c0 * rows, rows * 32, rows * 32, c1 - c0));
             else KP(kh_dev_upload_2d(ev.p, NB * 32, witness, rows * 32, rows * 32, COLUMNS));
             if (g + 1 < groups) { KP(interpolate_extend(c0, c1)); cols_pending = c1; }
-            // KH_PROVE_COMMIT_PER_GROUP=1 (experiment): the group's share of the witness commitment behind its transfer as well (a batch of its own)
-            if (commit_per_group && groups > 1 && groups <= 3) {
-                KP(kh_msm_submit(srs, (int)logn, 0, 0, ev.at(c0 * NB), n, c1 - c0, 1, &tickets.t[g])); tickets.live[g] = true; group_c0[g] = c0; group_c0[g + 1] = c1; commit_groups = g + 1;
-            }
         }
     } else KP(kh_dev_copy(ev.p, witness_dev, COLUMNS * NB * 32));
     mark();
@@ -1056,16 +1051,13 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     };
     auto set_const = [&](uint64_t* dst, const fe& val) { return kh_dev_fill_elements(dst, val.l, 1); };    // *dst = val, queued on the main stream
     // ---- witness commitments: one batched MSM per chunk of the Lagrange basis, queued before the columns are interpolated
-    uint64_t& tk = tickets.t[3]; bool& have_tk = tickets.live[3];
-    if (nch == 1 && !commit_groups) { KP(kh_msm_submit(srs, (int)logn, 0, 0, ev.p, n, COLUMNS, 1, &tk)); have_tk = true; }
+    uint64_t& tk = ticket.t; bool& have_tk = ticket.live;
+    if (nch == 1) { KP(kh_msm_submit(srs, (int)logn, 0, 0, ev.p, n, COLUMNS, 1, &tk)); have_tk = true; }
     KP(interpolate_extend(cols_pending, COLUMNS));
     std::vector<uint64_t> wxy, wbx; std::vector<uint8_t> winf, wbi;
     const fe* w_blind = draw(COLUMNS * nch);          // blinder(num_chunks) per column, column by column (prover.rs:316-327)
     KP(blinding_points(w_blind, COLUMNS * nch, wbx, wbi));              // (underneath the MSM)
-    if (commit_groups) {
-        wxy.resize(8 * COLUMNS); winf.resize(COLUMNS);
-        for (size_t g = 0; g < commit_groups; g++) KP(tickets.wait((int)g, &wxy[8 * group_c0[g]], &winf[group_c0[g]]));
-    } else if (have_tk) { wxy.resize(8 * COLUMNS); winf.resize(COLUMNS); KP(tickets.wait(3, wxy.data(), winf.data())); }
+    if (have_tk) { wxy.resize(8 * COLUMNS); winf.resize(COLUMNS); KP(ticket.wait(wxy.data(), winf.data())); }
     else KP(commit_evals(ev.p, COLUMNS, wxy, winf));
     std::vector<uint64_t> wcx; std::vector<uint8_t> wci;
     KP(mask_with(wxy, winf, wbx, wbi, wcx, wci));
@@ -1237,7 +1229,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     std::vector<uint64_t> zxy, zbx; std::vector<uint8_t> zinf, zbi;
     const fe* z_blind = draw(nch);
     KP(blinding_points(z_blind, nch, zbx, zbi));
-    if (have_tk) { zxy.resize(8); zinf.resize(1); KP(tickets.wait(3, zxy.data(), zinf.data())); }
+    if (have_tk) { zxy.resize(8); zinf.resize(1); KP(ticket.wait(zxy.data(), zinf.data())); }
     else KP(commit_coeffs(zc, n, nch, zxy, zinf));
     const size_t nzb = zinf.size();
     KP_REQUIRE(nzb == nch, "unexpected chunk count of z");
@@ -1356,7 +1348,7 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     const size_t ntb = 7 * nch;
     const fe* t_blind = draw(ntb);
     KP(blinding_points(t_blind, ntb, tbx, tbi));
-    if (have_tk) { txy.resize(8 * 7); tinf.resize(7); KP(tickets.wait(3, txy.data(), tinf.data())); }
+    if (have_tk) { txy.resize(8 * 7); tinf.resize(7); KP(ticket.wait(txy.data(), tinf.data())); }
     else KP(commit_coeffs(quot.p, 7 * n, 7 * nch, txy, tinf));
     KP_REQUIRE(tinf.size() == ntb, "unexpected chunk count of t");
     std::vector<uint64_t> tcx; std::vector<uint8_t> tci;

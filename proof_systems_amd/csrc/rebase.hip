@@ -29,6 +29,7 @@
 // Everything here is throughput work on a side stream; the round in flight keeps the latency path.
 #include <algorithm>
 #include "common.hpp"
+#include "env.hpp"
 #include "curve.cuh"
 #include "coop.cuh"
 #include "field29.cuh"
@@ -273,7 +274,7 @@ int rebase_tables(hipStream_t s, int curve, const void* part, size_t N, const vo
     RbBeta beta; memset(&beta, 0, sizeof beta);
     if (glv) memcpy(beta.l, glv_beta, 32);
     const u32 npts = (u32)(N + extra);
-    static const int rb_prio = getenv("KH_IPA_REBASE_PRIO") ? atoi(getenv("KH_IPA_REBASE_PRIO")) : 0;
+    static const int rb_prio = (int)env_int("KH_IPA_REBASE_PRIO", 0);
     RbExtra hu; memset(&hu, 0, sizeof hu);
     if (extra) memcpy(&hu, extra_affine_host, 64 * extra);
     const uint8_t* outs = (const uint8_t*)rebase_outputs(part, N);

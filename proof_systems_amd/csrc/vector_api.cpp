@@ -2,6 +2,7 @@
 #include <stdlib.h>
 
 #include "api_internal.hpp"
+#include "env.hpp"
 
 using namespace kh;
 
@@ -301,7 +302,7 @@ struct HostXferEvents {
 // thread-local storage: a thread holds a pair while it exists (a rayon worker lives as long as its pool) and hands it back at exit without
 // freeing anything (no hipFree from a TLS destructor); the next new thread adopts it; kh_trim frees every pair that is not inside a call at that moment.
 static size_t xfer_keep_bytes() {          // per buffer, per thread; KH_XFER_KEEP_MB overrides.  64 MB holds what the reference's callers hand over one column at
-    static const size_t v = getenv("KH_XFER_KEEP_MB") ? (size_t)atol(getenv("KH_XFER_KEEP_MB")) << 20 : (size_t)64 << 20;   // a time (2 MB in, 16 MB out at 2^16 -> 2^19) and a
+    static const size_t v = (size_t)env_int("KH_XFER_KEEP_MB", 64) << 20;   // a time (2 MB in, 16 MB out at 2^16 -> 2^19) and a
     return v;                              // few columns batched; a 16-column batched extension (268 MB out) pays its allocation each time (~5 ms of PCIe beside it)
 }
 // in -> [upload] -> din -> run(din, dout, columns) -> dout -> [download] -> out, `batch` columns of in_col / out_col bytes, in groups

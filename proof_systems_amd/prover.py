@@ -36,9 +36,6 @@ ALPHA_PERM0 = 21                    # the gates register 21 powers of alpha firs
 MOD = {khip.FP: 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
        khip.FQ: 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001}
 R256 = 1 << 256
-import os as _os
-_PY_LOOKUP_SORT = bool(_os.environ.get("KH_PY_LOOKUP_SORT"))   # A/B: the lookup argument's sorted columns in Python instead of kh_lookup_sorted_dev
-_TOKEN_GATES = bool(_os.environ.get("KH_TOKEN_GATES"))     # A/B: run the gate library through the token machine instead of the compiled kernels
 
 
 class Fld:
@@ -625,24 +622,16 @@ def create_proof(ix: ProverIndex, witness, rng, timings=None, check: bool = True
             rt = {"d": d_rt, "c": d_rtc, "blind": rt_blind, "comm": rt_comm}
         jc = scalar_challenge(curve, F, fq.challenge() if LI.joint_lookup_used else 0)
         d_table = LI.joint_table_dev(jc, rt["d"] if rt else None)
-        if _PY_LOOKUP_SORT:                                 # A/B: the sorted columns by the Python restatement of constraints.rs:90-194
-            table_ints = F.values(d_table.download((n, 4)))
-            wcols = ev.download((COLUMNS, n, 4))
-            used = sorted({c for q in LI.patterns for tid, entry in OP.LOOKUP_PATTERNS[q] for c in (list(entry) + ([tid[1]] if isinstance(tid, tuple) else []))})
-            wit_ints = [F.values(wcols[c]) if c in used else None for c in range(COLUMNS)]
-            srt = [LK.zk_patch(F, c, n, zk, rng) for c in LK.sorted_columns(LI, wit_ints, table_ints, jc)]    # ValueError(row): value not in the table
-            full = np.stack([F.limbs_many(c) for c in srt])
-            d_sorted_base = khip.DevBuf(full.shape[0] * NB).upload(full)
-        else:                                               # looked-up values, hash join and snake layout on the device (kh_lookup_sorted_dev): nothing comes down
-            ns_ = LI.max_per_row + 1
-            d_sorted_base = khip.DevBuf(ns_ * NB)
-            try:                                            # rows 0 .. n - zk - 1 of every column; ValueError(row): value not in the table
-                LK.sorted_columns_dev(LI, [ev.view(i * NB) for i in range(COLUMNS)], d_table, jc, out=d_sorted_base)
-            except ValueError:
-                d_sorted_base.free()
-                raise
-            # zk_patch (constraints.rs:35-48): the last zk_rows of every column random, column by column
-            d_sorted_base.upload_2d((n - zk) * 32, NB, np.stack([F.limbs_many(F.rand_many(rng, zk)) for _ in range(ns_)]))
+        # looked-up values, hash join and snake layout on the device (kh_lookup_sorted_dev): nothing comes down
+        ns_ = LI.max_per_row + 1
+        d_sorted_base = khip.DevBuf(ns_ * NB)
+        try:                                                # rows 0 .. n - zk - 1 of every column; ValueError(row): value not in the table
+            LK.sorted_columns_dev(LI, [ev.view(i * NB) for i in range(COLUMNS)], d_table, jc, out=d_sorted_base)
+        except ValueError:
+            d_sorted_base.free()
+            raise
+        # zk_patch (constraints.rs:35-48): the last zk_rows of every column random, column by column
+        d_sorted_base.upload_2d((n - zk) * 32, NB, np.stack([F.limbs_many(F.rand_many(rng, zk)) for _ in range(ns_)]))
         d_sorted = [d_sorted_base.view(k_ * NB) for k_ in range(d_sorted_base.nbytes // NB)]
         scom = ix.commit_evals(d_sorted_base.ptr, len(d_sorted))    # commit_evaluations(d1, v, rng): non-hiding (one batched MSM), then one blinder per chunk
         s_blind = [F.rand_many(rng, nch) for _ in d_sorted]
@@ -698,27 +687,20 @@ def create_proof(ix: ProverIndex, witness, rng, timings=None, check: bool = True
     gids = khip.gate_ids()
     # The double generic gate is evaluated on ALL of d8 and accumulated onto the permutation rows: the reference evaluates it on d4 and interpolates it
     # separately (prover.rs:794-822); its degree is below 4n, so the 8n-point interpolation of the sum is the same polynomial -- no t4, no 4n-point iNTT.
-    if _TOKEN_GATES:
-        perm_cols = [e8.view(i * N8) for i in range(PERMUTS)] + [ix.col8(COLUMNS + 2 + i) for i in range(PERMUTS)] + [e8.view(COLUMNS * N8), ix.col8(ix.X8), ix.col8(ix.ZKPM8)]
-        khip.expr_evaluations_dev(fid, OP.perm_quot_tokens(w0=0, s0=7, z=14, x=15, zkpm=16, gamma=0, beta=1, bshift0=3, alpha0=2), perm_cols, [8 * n] * 17, pconsts,
-                                  8 * n, t8, stride=1, next_shift=8)
-        gen_cols = [e8.view(i * N8) for i in range(6)] + [ix.col8(i) for i in range(10)] + [ix.col8(COLUMNS)]
-        khip.expr_evaluations_dev(fid, OP.generic_gate_tokens(0, 6, 16, 0, 1), gen_cols, [8 * n] * 17, F.limbs_many([1, alpha]), 8 * n, t8, stride=1, next_shift=8,
-                                  accumulate=True)
-    else:                                                   # the same two expressions as compiled kernels (csrc/gates.hip: "Permutation", "Generic")
-        wcols = [e8.view(i * N8) for i in range(COLUMNS)]
-        pcols = wcols + [ix.col8(COLUMNS + 2 + i) for i in range(PERMUTS)] + [e8.view(COLUMNS * N8), ix.col8(ix.X8), ix.col8(ix.ZKPM8)]
-        pcols += [wcols[0]] * (31 - len(pcols))             # columns the expression does not read
-        khip.gate_evaluations_dev(fid, gids["Permutation"], pcols, 8 * n, pconsts, 8 * n, t8, stride=1, next_shift=8)
-        khip.gate_evaluations_dev(fid, gids["Generic"], wcols + [ix.col8(i) for i in range(COLUMNS)] + [ix.col8(COLUMNS)], 8 * n, F.limbs_many([1, alpha]), 8 * n, t8,
-                                  stride=1, next_shift=8, accumulate=True)
+    # both as compiled kernels (csrc/gates.hip: "Permutation", "Generic")
+    wcols = [e8.view(i * N8) for i in range(COLUMNS)]
+    pcols = wcols + [ix.col8(COLUMNS + 2 + i) for i in range(PERMUTS)] + [e8.view(COLUMNS * N8), ix.col8(ix.X8), ix.col8(ix.ZKPM8)]
+    pcols += [wcols[0]] * (31 - len(pcols))                 # columns the expression does not read
+    khip.gate_evaluations_dev(fid, gids["Permutation"], pcols, 8 * n, pconsts, 8 * n, t8, stride=1, next_shift=8)
+    khip.gate_evaluations_dev(fid, gids["Generic"], wcols + [ix.col8(i) for i in range(COLUMNS)] + [ix.col8(COLUMNS)], 8 * n, F.limbs_many([1, alpha]), 8 * n, t8,
+                              stride=1, next_shift=8, accumulate=True)
     live_gates = [(k_, name) for k_, name in enumerate(ix.GATE_TYPES + tuple(ix.optional)) if all_gates or name in ix.live_gate_types]
     if live_gates:                                          # the gate library on d8 (prover.rs:824-868): index(gate) * sum_i alpha^i constraint_i
         endo_q = F.value(khip.endos(1 - curve)[0])          # VerifierIndex::endo = endos::<OtherCurve>().0, an element of this scalar field
         gcols = [e8.view(i * N8) for i in range(COLUMNS)] + [ix.col8(i) for i in range(COLUMNS)]
         for k_, name in live_gates:                         # compiled kernels (csrc/gates.hip); the token program of the same expression is the fallback
             gtoks, gconsts = OP.gate_program(name, F.p, alpha, selector_col=30, mds=OP.POSEIDON_MDS[fid], endo=endo_q)
-            if name in gids and not _TOKEN_GATES:
+            if name in gids:
                 khip.gate_evaluations_dev(fid, gids[name], gcols + [ix.col8(ix.SEL0 + k_)], 8 * n, F.limbs_many(gconsts), 8 * n, t8, stride=1, next_shift=8, accumulate=True)
             else:
                 khip.expr_evaluations_dev(fid, gtoks, gcols + [ix.col8(ix.SEL0 + k_)], [8 * n] * 31, F.limbs_many(gconsts), 8 * n, t8, stride=1, next_shift=8, accumulate=True)

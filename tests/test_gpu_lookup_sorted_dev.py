@@ -281,7 +281,7 @@ def test_native_and_python_provers_agree_on_the_device_path(khip, cid):
 
 def test_lookup_py_device_path_equals_its_python_path(khip):
     """proof_systems_amd/lookup.py: sorted_columns_dev (values, join and layout on the device) against sorted_columns (Python integers, the
-    KH_PY_LOOKUP_SORT path of the Python prover) on the two-table circuit; and written in place into padded columns"""
+    restatement of lookup/constraints.rs:90-194) on the two-table circuit; and written in place into padded columns"""
     from proof_systems_amd import lookup as LK
     ix, LI, F, wit, ngen = two_table_circuit(khip, 0)
     n, zk = LI.n, LI.zk_rows

@@ -1,7 +1,6 @@
 """Round-6 entry points on the device against the C oracle: kh_msm_submit_host (the MSM pipeline from HOST scalars -- what
-SRS::commit_non_hiding(&DensePolynomial) hands over, poly-commitment/src/ipa.rs:638-683) in its chunked and un-chunked forms, and the lone big host MSM
-(the chunked upload -- KH_HOST_CHUNK_MIN -- and the two half-range jobs of a lone big MSM -- KH_HOST_SPLIT_MIN -- are
-experiments that measured level and are off by default: the tests below run them in a subprocess)."""
+SRS::commit_non_hiding(&DensePolynomial) hands over, poly-commitment/src/ipa.rs:638-683) from pageable and from pinned memory, and the lone big host MSM through
+the synchronous call and through a submit / wait pair (one upload on the calling thread's copy stream, one job)."""
 import os
 
 import numpy as np
@@ -28,9 +27,8 @@ def _rand_fe(rng, n):
 
 @pytest.mark.parametrize("cid", [0, 1])
 def test_msm_submit_host_pipeline(khip, cid):
-    """Three MSMs in flight from host buffers that are OVERWRITTEN as soon as the submit returns (the contract: the scalars are the caller's again), sizes on
-    both sides of the chunking threshold (2^17 scalars), ragged lengths, an offset window, canonical and Montgomery scalars, and a batch of two (the
-    un-chunked asynchronous upload); every result against the C oracle."""
+    """Three MSMs in flight from host buffers that are OVERWRITTEN as soon as the submit returns (the contract: the scalars are the caller's again), sizes from
+    5000 to 2^18 scalars, ragged lengths, an offset window, canonical and Montgomery scalars, and a batch of two; every result against the C oracle."""
     rng = np.random.default_rng(600 + cid)
     N = 1 << 18
     g = cref.srs_generate(cid, 0, N, threads=THREADS)
@@ -85,28 +83,17 @@ def test_msm_submit_host_from_pinned_memory(khip):
     srs.close()
 
 
-def test_chunked_upload_and_split_experiments_stay_bit_exact():
-    """KH_HOST_CHUNK_MIN / KH_HOST_SPLIT_MIN (off by default) in a fresh process: the same MSMs against the C oracle."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = (
-        "import sys, numpy as np\n"
-        "sys.path.insert(0, %r)\n"
-        "from oracle import cref\n"
-        "import proof_systems_amd.khip as k\n"
-        "k.init(0)\n"
-        "rng = np.random.default_rng(5)\n"
-        "n = 1 << 17\n"
-        "g = cref.srs_generate(0, 0, n, threads=8)\n"
-        "srs = k.Srs(0, g)\n"
-        "for m in (n, n - 77, 1 << 16):\n"
-        "    sc = rng.integers(0, 1 << 64, size=(m, 4), dtype=np.uint64); sc[:, 3] &= np.uint64((1 << 61) - 1)\n"
-        "    w, winf = cref.msm(0, g[:m], sc, threads=8)\n"
-        "    o, i = srs.msm(sc)\n"
-        "    assert not i and np.array_equal(o, w), ('sync', m)\n"
-        "    o, i = k.Srs.msm_wait(srs.msm_submit_host(sc))\n"
-        "    assert not i[0] and np.array_equal(o[0], w), ('submit_host', m)\n"
-        "print('ok')\n" % root)
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, KH_HOST_CHUNK_MIN="4096", KH_HOST_SPLIT_MIN="65536"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
-    assert r.returncode == 0 and b"ok" in r.stdout, r.stderr.decode()[-1500:]
+def test_lone_big_host_msm_sync_and_submit_host_stay_bit_exact(khip):
+    """A lone host-scalar MSM of 2^17, 2^17 - 77 and 2^16 scalars, through kh_msm and through kh_msm_submit_host / kh_msm_wait: both against the C oracle."""
+    rng = np.random.default_rng(5)
+    n = 1 << 17
+    g = cref.srs_generate(0, 0, n, threads=8)
+    srs = khip.Srs(0, g)
+    for m in (n, n - 77, 1 << 16):
+        sc = _rand_fe(rng, m)
+        w, winf = cref.msm(0, g[:m], sc, threads=8)
+        o, i = srs.msm(sc)
+        assert not i and np.array_equal(o, w), ("sync", m)
+        o, i = khip.Srs.msm_wait(srs.msm_submit_host(sc))
+        assert not i[0] and np.array_equal(o[0], w), ("submit_host", m)
+    srs.close()

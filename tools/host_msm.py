@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """The 2^20 MSM from HOST scalars (pageable memory, what SRS::commit_non_hiding(&DensePolynomial) hands over, poly-commitment/src/ipa.rs:638-683):
-one at a time through kh_msm (two half-range jobs with chunked uploads), and pipelined through kh_msm_submit_host / kh_msm_wait with 2 / 3 in flight,
+one at a time through kh_msm, and pipelined through kh_msm_submit_host / kh_msm_wait with 2 / 3 in flight,
 beside the device-resident pipeline of bench.py.  Distinct host buffers per MSM in flight (a caller's polynomials are different Vecs); results checked
-against each other.  KH_HOST_SPLIT_MIN=0 / KH_HOST_CHUNK_MIN=0 in the environment give the round-5 behaviour for an A/B on the same box."""
+against each other."""
 import os
 import sys
 import time
