@@ -798,6 +798,64 @@ int kh_proof_section(const kh_proof_t *proof, int section, const uint64_t **limb
 int kh_proof_phase_seconds(const kh_proof_t *proof, double *seconds, size_t cap);   /* witness_upload, witness_commit, z, quotient, evaluations, opening */
 void kh_proof_free(kh_proof_t *proof);
 
+/* ---- kimchi::verifier::verify / batch_verify as ONE native call (kimchi/src/verifier.rs:126-640, 781-1200, 1275-1373; the scalar side of SRS::verify,
+ * poly-commitment/src/ipa.rs:301-470) ----
+ * The host loop of the verifier (csrc/verifier.cpp), written against the entry points above as kh_prove is: per proof the Fiat-Shamir replay (kh_sponge_*),
+ * the public commitment (kh_msm over the registered Lagrange basis, negated, masked with blinder 1; the basis is computed on first use), ft_eval0, the
+ * evaluation list in opening order with its combined inner product, and the scalars of SRS::verify; for the whole batch ONE evaluation of the
+ * linearisation's constant terms on the device (the compiled gate constraints with one constants table per proof, one launch per gate type present in the
+ * batch; the lookup constraints as a token program per proof that has them) and ONE final MSM (kh_ipa_verify_msm).  f_comm, ft_comm and the combined lookup
+ * table are linear in commitments the final MSM takes anyway: their scalars are multiplied out on the host and no group operation runs there.
+ * Scope: everything kh_prove_full produces and everything the reference's stored proofs contain -- both curves, any num_chunks, public inputs, previous
+ * challenges (one or two chunks), the five library gates, the six optional gates, the lookup argument with table ids and runtime tables.
+ *
+ * kh_verifier_index_of: the verifier index of an index from kh_prover_index_create(_lookup) (KH_E_NOTFOUND for one from kh_prover_index_new, whose
+ *   commitments are the caller's): a copy that outlives the prover index, not the SRS handle.  A prover index carries no number of previous challenges
+ *   (kh_prove_recursive takes any): neither does this verifier index, which accepts any n_prev.
+ * kh_verifier_index_new: from a caller's own data (a deserialised VerifierIndex, verifier_index.rs:59-158): sections[] indexed by KH_VINDEX_*, in exactly
+ *   the layout kh_verifier_index_section gives (missing / count 0 = absent; flags NULL = no point at infinity); optional_gates = the kh_gate ids of
+ *   KH_VINDEX_OPTIONAL_COMM's entries in column order (RangeCheck0, RangeCheck1, ForeignFieldAdd, ForeignFieldMul, Xor16, Rot64, those present); shifts and
+ *   digest are computed when their sections are absent (kh_permutation_shifts; the base-field sponge in verifier_index.rs's order).  A lookup index is
+ *   present iff KH_VINDEX_LOOKUP_TABLE_COMM is; it needs KH_VINDEX_LOOKUP_INFO.  Host code: no device work.  KH_E_INVALID with a message: null pointers, a
+ *   domain that is no multiple of the SRS size, a section with the wrong number of points, a point off the curve, an element >= p, an unknown or
+ *   out-of-order optional gate, inconsistent lookup sections.
+ * kh_verifier_index_digest: VerifierIndex::digest as the index holds it (given or computed), an element of the curve's base field.
+ * kh_proof_from_sections: a proof from a caller's own data: sections[] indexed by KH_PROOF_* in the layout kh_proof_section gives.  KH_PROOF_PUBLIC_COMM and
+ *   KH_PROOF_CHALLENGES are ignored (the verifier derives both); KH_PROOF_PUBLIC_EVALS may be absent for a one-chunk proof (then they are computed from the
+ *   public inputs, verifier.rs:336-386).  The sections are copied; their contents are checked by kh_verify, which knows the curve.
+ * kh_batch_verify / kh_verify: KH_OK with *ok = 1 / 0 for well-formed proofs that are accepted / of which one at least is rejected.  KH_E_INVALID, with a
+ *   kh_last_error text naming the item and the check, BEFORE any device work, for anything malformed: null pointers, k == 0, items over different SRS
+ *   handles, rand containing a zero element, a limb vector that is not a canonical field element (>= p), a point that is not on the curve, and the
+ *   reference's structural errors (verifier.rs:781-830, check_proof_evals_len): a commitment or evaluation with the wrong number of chunks, n_public or
+ *   n_prev different from the index's, an L / R count different from log2(SRS size), lookup sections present without a lookup index or missing with one,
+ *   an optional-gate selector evaluation without its commitment.  *ok and trace are untouched on error.
+ *   rand: rand_base, sg_rand_base (ipa.rs:330-331; the reference draws them inside) as 2 x 4 Montgomery limbs, NULL = from the operating system.
+ *   The call runs on the SRS's device, on a library context of its own like kh_prove (kh_private_context_begin) unless the thread is inside one.
+ * kh_verify_last_phase_seconds: wall-clock seconds of the calling thread's last kh_batch_verify, for tools: transcript (validation, Fiat-Shamir, public
+ *   commitments), constant term (upload, launches, download), scalars (ft_eval0, combined inner products, the terms of SRS::verify), final MSM.  Returns 4. */
+typedef struct kh_verifier_index kh_verifier_index_t;
+typedef struct kh_section { const uint64_t *limbs; const uint8_t *flags; size_t count; } kh_section_t;   /* the layout kh_*_section returns */
+int kh_verifier_index_of(const kh_prover_index_t *index, kh_verifier_index_t **out);
+int kh_verifier_index_new(kh_srs_t *srs, unsigned log2_n, unsigned zk_rows, unsigned public_inputs, unsigned prev_challenges,
+                          const int *optional_gates, size_t n_optional, const kh_section_t *sections, size_t n_sections, kh_verifier_index_t **out);
+int kh_verifier_index_digest(const kh_verifier_index_t *vix, uint64_t out[4]);
+void kh_verifier_index_free(kh_verifier_index_t *vix);
+int kh_proof_from_sections(const kh_section_t *sections, size_t n_sections, kh_proof_t **out);
+typedef struct kh_verify_item {
+    const kh_verifier_index_t *index;               /* the items of one call may use different indexes over ONE SRS handle (batch_verify's rule) */
+    const kh_proof_t *proof;
+    const uint64_t *public_inputs; size_t n_public; /* Montgomery limbs */
+    const uint64_t *prev_chals; const unsigned *prev_rounds; const uint64_t *prev_comm_xy; const uint8_t *prev_comm_inf;
+    const size_t *prev_comm_chunks; size_t n_prev;  /* as for kh_prove_recursive */
+} kh_verify_item_t;
+typedef struct kh_verify_trace {                     /* what the verifier derived for one item: for tests and for a caller hunting a rejection */
+    uint64_t challenges[7][4];                       /* as KH_PROOF_CHALLENGES (the seventh is zero without lookups) */
+    uint64_t constant_term[4], ft_eval0[4], combined_inner_product[4];
+} kh_verify_trace_t;
+int kh_batch_verify(const kh_verify_item_t *items, size_t k, const uint64_t *rand, int *ok, kh_verify_trace_t *trace /* k records, nullable */);
+int kh_verify(const kh_verify_item_t *item, int *ok, kh_verify_trace_t *trace);
+int kh_verify_last_phase_seconds(double *seconds, size_t cap);
+
 /* ---- Fiat-Shamir sponges (host side) --------------------------------------
  * The transcript of kimchi's prover / verifier: Kimchi Poseidon (width 3, rate 2, 55 full rounds, x^7) under
  * DefaultFqSponge (poseidon/src/sponge.rs:228-412) and DefaultFrSponge (kimchi/src/plonk_sponge.rs:36-57).  Host code, no

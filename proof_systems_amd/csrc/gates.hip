@@ -35,9 +35,9 @@ struct GateCtx {
 #include "gates_gen.inc"
 
 // acc = sum_i cst(SLOT[i]) * constraint_i: SLOT = the gate's GATE_MULT_SLOT, the table slots of alpha^i (of the two per-proof values for Generic)
-template <class F, const int* SLOT>
+template <class F, class G, const int* SLOT>
 struct QuotientSink {
-    const GateCtx<F>& g;
+    const G& g;
     Fe<F> acc;
     template <int I>
     __device__ __forceinline__ void constraint(const Fe<F>& v) {
@@ -46,9 +46,9 @@ struct QuotientSink {
     }
 };
 #define KH_GATE_VALUE(ID, NAME)                                                                               \
-    template <class F>                                                                                        \
-    __device__ __forceinline__ Fe<F> gate_##NAME(const GateCtx<F>& g) {                                       \
-        QuotientSink<F, GATE_MULT_SLOT_##NAME> s{g, {}};                                                      \
+    template <class F, class G>                                                                               \
+    __device__ __forceinline__ Fe<F> gate_##NAME(const G& g) {                                                \
+        QuotientSink<F, G, GATE_MULT_SLOT_##NAME> s{g, {}};                                                   \
         gate_constraints_##NAME<F>(g, s);                                                                     \
         return mul<F>(g.cell(30, 0), s.acc);                                                                  \
     }
@@ -69,6 +69,39 @@ KH_FOR_EACH_CHECKED_GATE(KH_GATE_VALUE)
         }                                                                                                     \
     }
 KH_FOR_EACH_GATE(KH_GATE_KERNEL)
+
+// The same bodies with one constants table PER ROW: the verifier's constant term of the linearisation (kimchi/src/verifier.rs:412-490) for a batch of
+// proofs.  Item i of the batch is rows 2i (the proof's evaluations at zeta) and 2i + 1 (at zeta omega) of every column, its table -- alpha differs
+// from proof to proof -- the i-th of `consts`; thread per item, one launch per gate type present in the batch, all accumulating into one k-element
+// output.  No LDS, no atomics.
+struct GateBatchArgs {
+    const u64* cols[31];
+    const u64* consts;                                   // items x nconst x 4 limbs
+    size_t items;
+    int nconst, accumulate;
+    u64* out;
+};
+template <class F>
+struct GateBatchCtx {
+    const GateBatchArgs& a;
+    const u64* tab;                                      // this item's constants table
+    size_t i0, i1;
+    __device__ __forceinline__ Fe<F> cell(int c, int nxt) const { return Fe<F>::load(a.cols[c] + 4 * (nxt ? i1 : i0)); }
+    __device__ __forceinline__ Fe<F> cst(int k) const { return Fe<F>::load(tab + 4 * k); }
+};
+#define KH_GATE_BATCH_KERNEL(ID, NAME)                                                                        \
+    template <class F>                                                                                        \
+    __global__ void __launch_bounds__(128) k_gate_batch_##NAME(GateBatchArgs a) {                             \
+        const size_t t = (size_t)blockIdx.x * 128 + threadIdx.x;                                              \
+        const size_t i = t < a.items ? t : a.items - 1;                                                       \
+        const GateBatchCtx<F> g{a, a.consts + 4 * i * (size_t)a.nconst, 2 * i, 2 * i + 1};                    \
+        Fe<F> v = gate_##NAME<F>(g);                                                                          \
+        if (t < a.items) {                                                                                    \
+            if (a.accumulate) v = add<F>(Fe<F>::load(a.out + 4 * i), v);                                      \
+            v.store(a.out + 4 * i);                                                                           \
+        }                                                                                                     \
+    }
+KH_FOR_EACH_CHECKED_GATE(KH_GATE_BATCH_KERNEL)
 
 int gate_count() { return GATE_COUNT; }
 const char* gate_name(int gate) { return gate >= 0 && gate < GATE_COUNT ? GATE_NAMES[gate] : nullptr; }
@@ -139,6 +172,60 @@ int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, s
     }
     KH_HIP(hipGetLastError());
     C.timer.mark("gate", s);
+    return KH_OK;
+}
+
+#define g_gate_batch (kh::ctx().scratch("gate_batch"))
+
+// cols_host: ncols columns of 2 * items elements (witness 0..14, coefficients 15..29, then the selector columns the launches name); launches: per gate type its
+// selector column and the items' constants tables (items x kh_gate_num_constants x 4 limbs, host).  ONE staged upload of columns + tables, one launch per
+// gate type, all accumulating into out_dev (items elements, on the main stream); the caller downloads it.  *cols_dev: where the columns are on the device
+// (column c at + 8 c items limbs), valid until the context's next gate_batch_run -- the lookup programs of kh_batch_verify read them there.
+int gate_batch_run(Context& C, int field, const uint64_t* cols_host, size_t ncols, size_t items, const GateBatchLaunch* launches, size_t nl, uint64_t* out_dev,
+                   const uint64_t** cols_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field %d", field);
+    KH_REQUIRE(cols_host && launches && out_dev && items > 0 && nl > 0 && ncols > 30, "gate_batch_run: bad argument");
+    const size_t col_bytes = ncols * 2 * items * 32;
+    size_t total = col_bytes;
+    for (size_t l = 0; l < nl; l++) {
+        KH_REQUIRE(launches[l].gate >= 0 && launches[l].gate < GATE_CHECKED_COUNT && launches[l].consts, "gate_batch_run: unknown gate id %d", launches[l].gate);
+        KH_REQUIRE(launches[l].selector_col >= 30 && (size_t)launches[l].selector_col < ncols, "gate_batch_run: selector column %d of %zu", launches[l].selector_col, ncols);
+        total += items * (size_t)GATE_NCONST[launches[l].gate] * 32;
+    }
+    int rc;
+    if ((rc = g_gate_batch.reserve(total))) return rc;
+    u64* base = g_gate_batch.as<u64>();
+    std::vector<u64> blob(total / 8);
+    memcpy(blob.data(), cols_host, col_bytes);
+    size_t off = col_bytes / 8;
+    std::vector<size_t> tab_off(nl);
+    for (size_t l = 0; l < nl; l++) {
+        const size_t words = items * (size_t)GATE_NCONST[launches[l].gate] * 4;
+        memcpy(blob.data() + off, launches[l].consts, words * 8);
+        tab_off[l] = off; off += words;
+    }
+    if ((rc = C.stage_upload(base, {{blob.data(), total}}))) return rc;
+    hipStream_t s = C.stream;
+    dim3 grid((unsigned)((items + 127) / 128));
+    C.timer.begin(s);
+    for (size_t l = 0; l < nl; l++) {
+        GateBatchArgs a{};
+        for (int c = 0; c < 30; c++) a.cols[c] = base + (size_t)c * 2 * items * 4;
+        a.cols[30] = base + (size_t)launches[l].selector_col * 2 * items * 4;
+        a.consts = base + tab_off[l]; a.items = items; a.nconst = GATE_NCONST[launches[l].gate]; a.accumulate = l > 0; a.out = out_dev;
+        switch (launches[l].gate) {
+#define KH_GATE_BATCH_LAUNCH(ID, NAME)                                                                                     \
+            case ID:                                                                                                           \
+                if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_gate_batch_##NAME<FpParams>), grid, dim3(128), 0, s, a);       \
+                else hipLaunchKernelGGL((k_gate_batch_##NAME<FqParams>), grid, dim3(128), 0, s, a);                            \
+                break;
+            KH_FOR_EACH_CHECKED_GATE(KH_GATE_BATCH_LAUNCH)
+            default: break;
+        }
+        KH_HIP(hipGetLastError());
+    }
+    C.timer.mark("gate_batch", s);
+    if (cols_dev) *cols_dev = base;
     return KH_OK;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "host_ec.hpp"
+#include "gate_batch.hpp"
 #include "witness_lookup.hpp"
 
 namespace kh {
@@ -93,6 +94,9 @@ int gate_constants(int field, int gate, const uint64_t* alpha, const uint64_t* e
 int gate_fixed_constants(int field, int gate, const uint64_t* endo, uint64_t* out);      // the literal and endo slots of that table alone
 int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, size_t len, const uint64_t* consts, size_t nconsts, size_t rows,
              unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev);
+// the verifier's constant term for a batch of proofs (kh_batch_verify): the same bodies with one constants table per item (gates.hip)
+int gate_batch_run(Context& C, int field, const uint64_t* cols_host, size_t ncols, size_t items, const GateBatchLaunch* launches, size_t nl, uint64_t* out_dev,
+                   const uint64_t** cols_dev);
 // witness_check.hip: the gate constraints of every row one by one, the copy constraints and (lk != NULL) the lookups (kh_witness_check,
 // kh_witness_check_full).  scratch_dev: witness_check_scratch_bytes() (+ witness_check_lookup_scratch_bytes with lookups), whose first four 64-bit words
 // end up as [lowest (row * 64 + sub) << 32 | detail, or ~0 | rows with a violated gate | disconnected cells | lookups that are in no table]

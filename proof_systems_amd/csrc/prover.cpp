@@ -14,7 +14,6 @@
 //   round 5  prover.rs:1265-1500 SRS::open over (public, ft, z, selectors, w, coefficients, sigma, optional selectors)
 #include <stdint.h>
 #include <string.h>
-#include <sys/random.h>
 #include <chrono>
 #include <new>
 #include <vector>
@@ -22,10 +21,10 @@
 #include "../../include/kimchi_hip.h"
 #include "env.hpp"
 #include "host_ec.hpp"
+#include "protocol_host.hpp"
 #include "witness_lookup.hpp"
 
 namespace kh {
-void set_error(const char* fmt, ...);
 int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates, size_t n,
                       size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev);     // vector_api.cpp / poly.hip: the column pass of kh_prover_index_create
 // vector_api.cpp / lookup_index.hip: the lookup passes of kh_prover_index_create_lookup
@@ -41,111 +40,10 @@ int witness_check_num_constraints(int gate);         // of a gate id the check e
 }
 
 namespace {
-using khost::fe;
-constexpr size_t COLUMNS = 15, PERMUTS = 7, SEL0 = COLUMNS + 2 + PERMUTS, OPT0 = SEL0 + 5;
-constexpr int ALPHA_PERM0 = 21;                      // the gates take the first 21 powers of alpha (linearization.rs:56-58), the permutation the next 3
+using namespace kh_protocol;
+constexpr size_t SEL0 = COLUMNS + 2 + PERMUTS, OPT0 = SEL0 + 5;
 const char* const LIB_GATES[5] = {"Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar"};
 
-struct Dev {                                         // a device allocation that lives as long as the proof is being made
-    uint64_t* p = nullptr;
-    Dev() = default;
-    Dev(const Dev&) = delete;
-    Dev& operator=(const Dev&) = delete;
-    ~Dev() { if (p) (void)kh_dev_free(p); }
-    int alloc(size_t elems) { return kh_dev_alloc((void**)&p, elems * 32); }
-    uint64_t* at(size_t elem) const { return p + 4 * elem; }
-};
-struct SpongeH {
-    kh_sponge_t* s = nullptr;
-    ~SpongeH() { if (s) kh_sponge_free(s); }
-};
-fe load(const uint64_t* l) { fe r; memcpy(&r, l, 32); return r; }
-fe fpow(const khost::Fld& F, fe base, uint64_t e) {
-    fe acc = F.f.one;
-    while (e) { if (e & 1) acc = F.mul(acc, base); base = F.sqr(base); e >>= 1; }
-    return acc;
-}
-// sum_k c[k] x^k over `cnt` consecutive elements (ProofEvaluations::combine: the chunks of one evaluation)
-fe horner(const khost::Fld& F, const fe* c, size_t cnt, const fe& x) {
-    fe acc = {{0, 0, 0, 0}};
-    for (size_t k = cnt; k-- > 0;) acc = F.add(F.mul(acc, x), c[k]);
-    return acc;
-}
-int os_random(int fid, size_t k, fe* out) {          // uniform elements of the field, used as Montgomery limbs
-    const fe& p = khost::field(fid).p;
-    for (size_t i = 0; i < k;) {
-        fe buf[8];
-        if (getrandom(buf, sizeof(buf), 0) != (ssize_t)sizeof(buf)) { kh::set_error("getrandom failed"); return KH_E_DEVICE; }
-        for (int j = 0; j < 8 && i < k; j++) {
-            buf[j].l[3] &= 0x7fffffffffffffffULL;
-            if (!khost::geq(buf[j], p)) out[i++] = buf[j];
-        }
-    }
-    return KH_OK;
-}
-
-// ---- the lookup argument (kimchi/src/circuits/lookup/): protocol data and the expressions of its constraints as token programs ----
-// LookupPattern::lookups (lookups.rs:417-487): per pattern the joint lookups of a row -- table id (a constant, or a witness column) and the
-// witness columns of the entry.  Pattern ids: 0 Xor, 1 Lookup, 2 RangeCheck, 3 ForeignFieldMul (the reference's order).
-struct JointLookup { int tid_is_column, tid, ncell, cells[3]; };
-struct Pattern { int n; JointLookup l[4]; };
-const char* const PATTERN_NAMES[4] = {"Xor", "Lookup", "RangeCheck", "ForeignFieldMul"};
-const Pattern PATTERNS[4] = {
-    {4, {{0, 0, 3, {3, 7, 11}}, {0, 0, 3, {4, 8, 12}}, {0, 0, 3, {5, 9, 13}}, {0, 0, 3, {6, 10, 14}}}},
-    {3, {{1, 0, 2, {1, 2, 0}}, {1, 0, 2, {3, 4, 0}}, {1, 0, 2, {5, 6, 0}}, {0, 0, 0, {0, 0, 0}}}},
-    {4, {{0, 1, 1, {3, 0, 0}}, {0, 1, 1, {4, 0, 0}}, {0, 1, 1, {5, 0, 0}}, {0, 1, 1, {6, 0, 0}}}},
-    {4, {{0, 1, 1, {7, 0, 0}}, {0, 1, 1, {8, 0, 0}}, {0, 1, 1, {9, 0, 0}}, {0, 1, 1, {10, 0, 0}}}},
-};
-// a postfix token program under construction (KH_TOK_*), constants interned by value
-struct Prog {
-    std::vector<uint32_t> t;
-    std::vector<fe> consts;
-    void push(uint32_t op, uint32_t a) { t.push_back(op); t.push_back(a); }
-    void C(const fe& v) {
-        for (size_t i = 0; i < consts.size(); i++) if (khost::eq(consts[i], v)) { push(KH_TOK_CONST, (uint32_t)i); return; }
-        consts.push_back(v); push(KH_TOK_CONST, (uint32_t)(consts.size() - 1));
-    }
-    void cell(uint32_t col, int next = 0) { push(KH_TOK_CELL, 2 * col + (next ? 1u : 0u)); }
-    void add() { push(KH_TOK_ADD, 0); }
-    void sub() { push(KH_TOK_SUB, 0); }
-    void mul() { push(KH_TOK_MUL, 0); }
-    int run(int fid, const std::vector<const uint64_t*>& cols, const std::vector<size_t>& lens, size_t rows, unsigned stride, unsigned next_shift, int accumulate, uint64_t* out) const {
-        return kh_expr_evaluations_dev(fid, t.data(), t.size() / 2, cols.data(), lens.data(), cols.size(), (const uint64_t*)consts.data(), consts.size(), rows, stride,
-                                       next_shift, accumulate, out);
-    }
-};
-struct LookupChallenges { fe jc, tic, beta, gamma, gb1; fe prefactor[5]; };   // prefactor[k] = (gamma + dummy)^k (1 + beta)^max_per_row, dummy = 0
-// combine_table_entry (tables/mod.rs:147-162) of one joint lookup: Horner in the joint combiner from the last cell + table_id_combiner * id
-void emit_joint(Prog& p, const khost::Fld& F, const JointLookup& L, const LookupChallenges& ch) {
-    p.cell((uint32_t)L.cells[L.ncell - 1]);
-    for (int i = L.ncell - 2; i >= 0; i--) { p.C(ch.jc); p.mul(); p.cell((uint32_t)L.cells[i]); p.add(); }
-    if (L.tid_is_column) { p.cell((uint32_t)L.tid); p.C(ch.tic); p.mul(); p.add(); }
-    else if (L.tid) { fe id = {{(uint64_t)L.tid, 0, 0, 0}}; p.C(F.mul(ch.tic, F.to_mont(id))); p.add(); }
-}
-// (1 + beta)^max_per_row (gamma + dummy)^padding prod (gamma + joint value)   (constraints.rs:497-523)
-void emit_fterm(Prog& p, const khost::Fld& F, const Pattern* pat, size_t mpr, const LookupChallenges& ch) {
-    const int n = pat ? pat->n : 0;
-    p.C(ch.prefactor[mpr - (size_t)n]);
-    for (int i = 0; i < n; i++) { p.C(ch.gamma); emit_joint(p, F, pat->l[i], ch); p.add(); p.mul(); }
-}
-// numerator of an aggregation row: f_chunk * t_chunk, with the pattern selectors at columns sel0.., the combined table at column `table`
-void emit_numerator(Prog& p, const khost::Fld& F, const std::vector<int>& pats, size_t mpr, const LookupChallenges& ch, uint32_t sel0, uint32_t table) {
-    p.C(F.f.one);
-    for (size_t k = 0; k < pats.size(); k++) { p.cell(sel0 + (uint32_t)k); if (k) p.add(); }
-    p.sub();                                                            // 1 - sum of the selectors: a row without lookups
-    emit_fterm(p, F, nullptr, mpr, ch); p.mul();
-    for (size_t k = 0; k < pats.size(); k++) { p.cell(sel0 + (uint32_t)k); emit_fterm(p, F, &PATTERNS[pats[k]], mpr, ch); p.mul(); p.add(); }
-    p.C(ch.gb1); p.cell(table); p.add(); p.C(ch.beta); p.cell(table, 1); p.mul(); p.add();      // t_chunk = gamma (1 + beta) + t + beta t'
-    p.mul();
-}
-// denominator: prod_i (gamma (1 + beta) + s_i + beta s_i') with the roles of s_i, s_i' swapped for odd i (the snake)
-void emit_denominator(Prog& p, size_t mpr, const LookupChallenges& ch, uint32_t sorted0) {
-    for (size_t i = 0; i <= mpr; i++) {
-        const int odd = (int)(i & 1);
-        p.C(ch.gb1); p.cell(sorted0 + (uint32_t)i, odd); p.add(); p.C(ch.beta); p.cell(sorted0 + (uint32_t)i, !odd); p.mul(); p.add();
-        if (i) p.mul();
-    }
-}
 }  // namespace
 
 struct kh_lookup_index {
@@ -678,6 +576,14 @@ int kh_verifier_index_section(const kh_prover_index_t* ix, int section, const ui
     if (flags) *flags = section == KH_VINDEX_LOOKUP_INFO ? nullptr : s.flags.data();
     return KH_OK;
 }
+}  // extern "C"
+namespace kh {
+// what kh_verifier_index_of (csrc/verifier.cpp) needs besides kh_verifier_index_section and kh_prover_index_shape
+void prover_index_facts(const kh_prover_index_t* ix, kh_srs_t** srs, unsigned* public_inputs, const int** optional_gates, size_t* n_optional) {
+    *srs = ix->srs; *public_inputs = (unsigned)ix->pub; *optional_gates = ix->optional.data(); *n_optional = ix->optional.size();
+}
+}  // namespace kh
+extern "C" {
 int kh_debug_lookup_column(const kh_prover_index_t* ix, int block, size_t k, const uint64_t** dev, size_t* elems) {
     if (!ix || !dev || !elems) { kh::set_error("kh_debug_lookup_column: null argument"); return KH_E_INVALID; }
     const kh_lookup_index* lk = ix->lk;
@@ -1292,26 +1198,14 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
         const uint32_t c_vanish = (uint32_t)cols.size(), c_l0 = c_vanish + 1, c_lfinal = c_vanish + 2;
         for (int a = 0; a < 3; a++) cols.push_back(lk->atoms8[a]);
         std::vector<size_t> lens(cols.size(), N8);
-        fe ap = fpow(F, alpha, ALPHA_PERM0 + 3);
-        Prog p;
-        // alpha^24 vanish (aggreg' denominator - aggreg numerator)
-        p.C(ap); p.cell(c_vanish);
-        p.cell(c_agg, 1); emit_denominator(p, mpr, cch, c_sorted); p.mul();
-        p.cell(c_agg); emit_numerator(p, F, lk->pats, mpr, cch, c_sel0, c_table); p.mul();
-        p.sub(); p.mul(); p.mul();
-        // alpha^25 l0 (aggreg - 1), alpha^26 lfinal (aggreg - 1)
-        for (int i = 0; i < 2; i++) { ap = F.mul(ap, alpha); p.C(ap); p.cell(i ? c_lfinal : c_l0); p.cell(c_agg); p.C(one); p.sub(); p.mul(); p.mul(); p.add(); }
-        // the snake's shared elements: lfinal (s_i - s_i+1) for even i, l0 (...) for odd i
-        for (size_t i = 0; i < mpr; i++) {
-            ap = F.mul(ap, alpha);
-            p.C(ap); p.cell((i & 1) ? c_l0 : c_lfinal); p.cell(c_sorted + (uint32_t)i); p.cell(c_sorted + (uint32_t)i + 1); p.sub(); p.mul(); p.mul(); p.add();
-        }
-        if (has_rt) {                                 // the constraints are padded to 3 + 4, then RT(x) selector_RT(x) (constraints.rs:658-680, runtime_tables.rs:59-66)
+        LookupColumns lc{c_sorted, c_agg, c_table, c_sel0, c_vanish, c_l0, c_lfinal, 0, 0};
+        if (has_rt) {
             KP(rt8.alloc(N8)); KP(kh_lde_dev(fid, d_rtc.p, logn, 3, rt8.p, 1));
-            const uint32_t c_rt8 = (uint32_t)cols.size(); cols.push_back(rt8.p); cols.push_back(lk->rtsel8);
+            lc.rt = (uint32_t)cols.size(); lc.rtsel = lc.rt + 1; cols.push_back(rt8.p); cols.push_back(lk->rtsel8);
             lens.assign(cols.size(), N8);
-            p.C(fpow(F, alpha, ALPHA_PERM0 + 3 + 7)); p.cell(c_rt8); p.cell(c_rt8 + 1); p.mul(); p.mul(); p.add();
         }
+        Prog p;
+        emit_lookup_constraints(p, F, lk->pats, mpr, cch, alpha, lc, has_rt);
         KP(p.run(fid, cols, lens, N8, 1, 8, 1, t8.p));
     }
     KP(kh_ntt_dev(fid, t8.p, logn + 3, 1, 1));
@@ -1558,6 +1452,26 @@ int kh_proof_section(const kh_proof_t* proof, int section, const uint64_t** limb
     const kh_proof::Sec& s = proof->sec[section];
     *limbs = s.limbs.data(); *count = s.count;
     if (flags) *flags = s.points ? s.flags.data() : nullptr;
+    return KH_OK;
+}
+// a proof from a caller's own data (a deserialised ProverProof), for kh_verify: the sections are copied as given; what they must hold is checked where the
+// curve is known, in kh_batch_verify
+int kh_proof_from_sections(const kh_section_t* sections, size_t n_sections, kh_proof_t** out) {
+    if (!sections || !out || n_sections > KH_PROOF_LOOKUP_RUNTIME_COMM + 1) { kh::set_error("kh_proof_from_sections: bad argument"); return KH_E_INVALID; }
+    for (size_t s = 0; s < n_sections; s++)
+        if (sections[s].count && !sections[s].limbs) { kh::set_error("kh_proof_from_sections: section %zu has %zu entries and no limbs", s, sections[s].count); return KH_E_INVALID; }
+    kh_proof* pr = new (std::nothrow) kh_proof();
+    if (!pr) { kh::set_error("out of memory"); return KH_E_NOMEM; }
+    for (size_t s = 0; s < n_sections; s++) {
+        const kh_section_t& in = sections[s];
+        if (s == KH_PROOF_PUBLIC_COMM || s == KH_PROOF_CHALLENGES || !in.count) continue;      // the verifier derives both
+        const bool points = s <= KH_PROOF_PUBLIC_COMM || s == KH_PROOF_LR || s == KH_PROOF_DELTA || s == KH_PROOF_SG || s >= KH_PROOF_LOOKUP_SORTED_COMM;
+        if (points) {
+            const std::vector<uint8_t> finite(in.count, 0);
+            pr->set_points((int)s, in.limbs, in.flags ? in.flags : finite.data(), in.count);
+        } else pr->set_elems((int)s, (const fe*)in.limbs, in.count);
+    }
+    *out = pr;
     return KH_OK;
 }
 int kh_proof_phase_seconds(const kh_proof_t* proof, double* seconds, size_t cap) {

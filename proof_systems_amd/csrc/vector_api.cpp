@@ -427,6 +427,16 @@ int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t z
     KH_LOOKUP_STEP(lookup_atom_finish(C, field, n, zk_rows, zh8, lim0, limf, atoms_dev));
 }
 #undef KH_LOOKUP_STEP
+// the gate part of the constant term of a batch of proofs (csrc/verifier.cpp; kernels in gates.hip), queued on the main stream
+int verifier_gate_terms_dev(int field, const uint64_t* cols_host, size_t ncols, size_t items, const GateBatchLaunch* launches, size_t nl, uint64_t* out_dev,
+                            const uint64_t** cols_dev) {
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = gate_batch_run(C, field, cols_host, ncols, items, launches, nl, out_dev, cols_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
 // the kernels of kh_witness_check (csrc/prover.cpp; witness_check.hip).  The scratch block comes from the kh_dev_alloc pool, taken before the context's lock like
 // kh_lookup_sorted_dev's; the read-back of the four status words, outside the lock, is the call's only wait.  lookups: what to check of them, or NULL.
 int witness_check_dev(int field, const uint64_t* witness_dev, const uint64_t* d1_dev, size_t n, const int* sel_col, size_t ngate_ids, size_t public_inputs,

@@ -91,6 +91,7 @@ for _name, _fields in _STRUCTS.items():
     _STRUCTURES[_name] = _structure(_name, _fields)
 LookupTableC, RuntimeTableCfgC = _STRUCTURES["kh_lookup_table_t"], _STRUCTURES["kh_runtime_table_cfg_t"]
 WitnessReportC, WitnessLookupC = _STRUCTURES["kh_witness_report_t"], _STRUCTURES["kh_witness_lookup_t"]
+SectionC, VerifyItemC, VerifyTraceC = _STRUCTURES["kh_section_t"], _STRUCTURES["kh_verify_item_t"], _STRUCTURES["kh_verify_trace_t"]
 
 # ctypes passes an undeclared Python int as a 32-bit C int (round 6: kh_msm_submit_host, called with a bare int for its size_t n, asked hipMalloc for
 # 6.6 EB), so nothing is left undeclared.  A function an older build (KH_LIB) lacks is skipped; tests/test_abi.py holds the in-tree build to all of them.
@@ -915,6 +916,141 @@ class NativeProverIndex:
     def free(self):
         if self._h:
             _lib.kh_prover_index_free(self._h); self._h = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------------- the native verifier
+VERIFY_PHASES = ("transcript", "constant_term", "scalars", "final_msm")
+
+
+def _section_array(sections: dict, names: dict):
+    """{name: (xy (k, 8), inf (k,)) | (k, 4) limbs | 8 plain words (lookup_info: a dict or a sequence) | None} -> kh_section_t[len(names)] + what keeps it alive"""
+    arr = (SectionC * len(names))()
+    keep = []
+    for name, sid in names.items():
+        v = sections.get(name)
+        if v is None:
+            continue
+        if name == "lookup_info":
+            w = np.ascontiguousarray([v[f] for f in LOOKUP_INFO_FIELDS] if isinstance(v, dict) else list(v), dtype=np.uint64).reshape(8)
+            keep.append(w)
+            arr[sid] = SectionC(_p64(w), None, 2)
+        elif isinstance(v, tuple):
+            xy = _c64(v[0], (-1, 8)); inf = np.ascontiguousarray(v[1], dtype=np.uint8).reshape(-1) if v[1] is not None else None
+            keep += [xy, inf]
+            if xy.shape[0]:
+                arr[sid] = SectionC(_p64(xy), _p8(inf) if inf is not None else None, xy.shape[0])
+        else:
+            e = _c64(v, (-1, 4))
+            keep.append(e)
+            if e.shape[0]:
+                arr[sid] = SectionC(_p64(e), None, e.shape[0])
+    return arr, keep
+
+
+class VerifierIndex:
+    """kh_verifier_index_new: a verifier index from sections in the layout NativeProverIndex.verifier_index() returns (absent / None = not there; shifts and
+    digest are computed when absent); VerifierIndex.of(native_index): kh_verifier_index_of."""
+
+    def __init__(self, srs, log2_n: int, zk_rows: int, public: int, prev_challenges: int, optional_gate_ids, sections: dict):
+        self._h = C.c_void_p()
+        opt = (C.c_int * max(len(optional_gate_ids), 1))(*optional_gate_ids)
+        arr, _keep = _section_array(sections, VINDEX_SECTIONS)
+        _check(_lib.kh_verifier_index_new(srs._h, log2_n, zk_rows, public, prev_challenges, opt, len(optional_gate_ids), arr, len(arr), C.byref(self._h)))
+        self._keep = (srs,)
+
+    @classmethod
+    def of(cls, index: "NativeProverIndex"):
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(_lib.kh_verifier_index_of(index._h, C.byref(self._h)))
+        self._keep = index._keep[:1]
+        return self
+
+    def digest(self):
+        out = np.zeros(4, dtype=np.uint64)
+        _check(_lib.kh_verifier_index_digest(self._h, _p64(out)))
+        return out
+
+    def free(self):
+        if self._h:
+            _lib.kh_verifier_index_free(self._h); self._h = C.c_void_p()
+
+
+class Proof:
+    """kh_proof_from_sections: a proof handle from the sections NativeProverIndex.prove returns (or a caller's own, same layout)."""
+
+    def __init__(self, sections: dict):
+        self._h = C.c_void_p()
+        arr, _keep = _section_array(sections, PROOF_SECTIONS)
+        _check(_lib.kh_proof_from_sections(arr, len(arr), C.byref(self._h)))
+
+    def free(self):
+        if self._h:
+            _lib.kh_proof_free(self._h); self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _trace(t: "VerifyTraceC"):
+    a = lambda x: np.ctypeslib.as_array(x).copy()
+    return {"challenges": a(t.challenges), "constant_term": a(t.constant_term), "ft_eval0": a(t.ft_eval0), "combined_inner_product": a(t.combined_inner_product)}
+
+
+def batch_verify_raw(items, rand=None, ok_before: int = -1, count=None):
+    """kh_batch_verify without raising: (return code, *ok afterwards (ok_before if the call left it alone), [trace dict per item]).  items: [(VerifierIndex,
+    Proof, public (k, 4) limbs or None, prev)] with prev as for NativeProverIndex.prove; count: the k handed to the library (default: len(items))."""
+    k = len(items)
+    arr = (VerifyItemC * max(k, 1))()
+    keep = []
+    for i, item in enumerate(items):
+        vix, proof = item[0], item[1]
+        public = item[2] if len(item) > 2 else None
+        prev = item[3] if len(item) > 3 else ()
+        arr[i].index = vix._h.value if vix is not None else None
+        arr[i].proof = proof._h.value if proof is not None else None
+        if public is not None and len(public):
+            pub = _c64(public, (-1, 4)); keep.append(pub)
+            arr[i].public_inputs = _p64(pub); arr[i].n_public = pub.shape[0]
+        m = len(prev)
+        if m:
+            chals = _c64(np.concatenate([np.asarray(c, dtype=np.uint64).reshape(-1, 4) for c, _ in prev]), (-1, 4))
+            rounds = (C.c_uint * m)(*[np.asarray(c).reshape(-1, 4).shape[0] for c, _ in prev])
+            cxy = np.ascontiguousarray(np.concatenate([np.asarray(cm[0], dtype=np.uint64).reshape(-1, 8) for _, cm in prev]))
+            cinf = np.ascontiguousarray(np.concatenate([np.asarray(cm[1], dtype=np.uint8).reshape(-1) for _, cm in prev]))
+            cch = (C.c_size_t * m)(*[np.asarray(cm[1]).reshape(-1).shape[0] for _, cm in prev])
+            keep += [chals, rounds, cxy, cinf, cch]
+            arr[i].prev_chals = _p64(chals); arr[i].prev_rounds = rounds; arr[i].prev_comm_xy = _p64(cxy); arr[i].prev_comm_inf = _p8(cinf)
+            arr[i].prev_comm_chunks = cch; arr[i].n_prev = m
+    rnd = _c64(rand, (2, 4)) if rand is not None else None
+    ok = C.c_int(ok_before)
+    tr = (VerifyTraceC * max(k, 1))()
+    rc = _lib.kh_batch_verify(arr, k if count is None else count, _p64(rnd) if rnd is not None else None, C.byref(ok), tr)
+    return rc, ok.value, [_trace(tr[i]) for i in range(k)] if rc == 0 else None
+
+
+def batch_verify(items, rand=None):
+    """kh_batch_verify: (ok, [trace dict per item]); a malformed item raises KhError (code E_INVALID).  rand: (2, 4) limbs (rand_base, sg_rand_base) or
+    None (drawn from the operating system)."""
+    rc, ok, tr = batch_verify_raw(items, rand)
+    _check(rc)
+    return ok == 1, tr
+
+
+def verify(vix, proof, public=None, prev=()):
+    """kh_verify: (ok, trace)"""
+    ok, tr = batch_verify([(vix, proof, public, prev)])
+    return ok, tr[0]
+
+
+def verify_last_phase_seconds():
+    """kh_verify_last_phase_seconds: {phase: seconds} of this thread's last batch_verify"""
+    ph = (C.c_double * 4)()
+    _check(min(0, _lib.kh_verify_last_phase_seconds(ph, 4)))
+    return dict(zip(VERIFY_PHASES, list(ph)))
 
 
 def polycomm_multi_scalar_mul(curve: int, comms, scalars):

@@ -13,6 +13,7 @@
 //!   * `get_lagrange_basis*`                                                -> the CPU cache of the inner SRS (what the verifier
 //!     and the index read); the device computes its own copy of the same basis once (`kh_srs_compute_lagrange`)
 //!   * `OpenProof::open`                                                    -> host transcript, device rounds (`kh_ipa_*`)
+//!   * `verifier::GpuVerifier::verify`                                     -> `kh_batch_verify`: `batch_verify` in one call, over the verifier index the library built with the prover index
 //!   * `prover::GpuProver::create`                                         -> `kh_prove`: the WHOLE of `ProverProof::create` in one call (no lookups / recursion)
 //!   * `OpenProof::verify`                                                  -> `ipa::SRS::verify` of the inner SRS (batch verifier MSM:
 //!     `kh_ipa_verify_msm` is available to a caller that restructures `verify`; not needed for proving)
@@ -41,6 +42,7 @@ use std::{ffi::CStr, sync::Arc};
 
 pub mod ntt;
 pub mod prover;
+pub mod verifier;
 
 /// Non-zero status -> panic with the library's message: the trait methods return values, and the reference itself
 /// unwraps at these sites (poly-commitment/src/ipa.rs:649-659).
