@@ -130,10 +130,19 @@ def fixture_sections(khip, curve, fx):
     return index_args, ps, elems(F, fx["public"]), prev
 
 
-def native_verify(khip, srs, curve, fx):
+def fixture_item(khip, srs, curve, fx):
+    """the live (vix, proof, public, prev) item of a loaded fixture: what kh_verify / kh_batch_verify take; the caller frees item[1] and item[0]"""
     index_args, ps, pub, prev = fixture_sections(khip, curve, fx)
     vix = khip.VerifierIndex(srs, *index_args)
-    proof = khip.Proof(ps)
+    try:
+        return (vix, khip.Proof(ps), pub, prev)
+    except Exception:
+        vix.free()
+        raise
+
+
+def native_verify(khip, srs, curve, fx):
+    vix, proof, pub, prev = fixture_item(khip, srs, curve, fx)
     try:
         ok, trace = khip.verify(vix, proof, pub, prev)
         return ok, trace, vix.digest()
