@@ -125,7 +125,7 @@ struct MsmSlot {
     PhaseTimer timer;
     DevBuf ws_scalars, ws_digits, ws_hist, ws_cnt, ws_off, ws_ntask, ws_toff, ws_entries, ws_partial,
         ws_buckets, ws_seg, ws_out, ws_scan_tmp, ws_biglist, ws_points, ws_order, ws_chunks, ws_handed, ws_sync, ws_mid,
-        ws_b29, ws_a1, ws_a2, ws_xlist;                              // wide windows (c = 20): lazy buckets, first-level chunk sums, the 2 x 2^lo marginals
+        ws_b29, ws_a1, ws_l2, ws_a2, ws_xlist;                       // wide windows (c = 20): lazy buckets, chunk sums (level one), run sums (level two), the 2 x 2^lo marginals
     void* pinned = nullptr; size_t pinned_cap = 0;      // host staging of the group sums (XYZZ)
     hipEvent_t done = nullptr;
     bool busy = false;                 // a job is pending (set by enqueue, cleared by finish)

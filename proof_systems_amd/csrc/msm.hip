@@ -1567,17 +1567,19 @@ k_marginal_fin_q(const uint8_t* __restrict__ marg, MargGeom g, uint8_t* __restri
 // Bucket t = (a, b), a = its top `hi` bits, b = its low `lo` bits, has weight t + 1:
 //     sum_t (t + 1) B_t  =  2^lo  sum_a a H_a  +  sum_b (b + 1) L_b,      H_a = sum_b B_(a,b),   L_b = sum_a B_(a,b)
 // -- every bucket goes into ONE hi-digit and ONE lo-digit marginal: 2 x 2^19 full additions, all of them in the lazy 29-bit arithmetic
-// (add29: ~1.4 mixed additions each), then 2^hi + 2^lo = 1536 marginals take the 5-bit digit-marginal tail of the narrow path.
+// (add29: ~1.4 mixed additions each) in two levels, then 2^hi + 2^lo = 1536 marginals take the 5-bit digit-marginal tail of the narrow path.
 //   k_bucket_sum_wide  the split buckets of pass B's list (exact sum of the wire partials; hot ones by the whole block, lane-cooperatively);
 //                      empty buckets got their identity record from pass B, all others ARE a task's output
-//   k_wide_a1          thread (plane, marginal, chunk): the sum of r = 8 buckets, sequentially, B29 in -> B29 out (2^17 threads; plane 0 reads
-//                      r consecutive records, plane 1 a column: neighbouring lanes read neighbouring records).  A thread whose add29 cannot
-//                      exclude an exceptional case writes a marker record; k_wide_a2 redoes such a chunk with the exact formulas.
-//   k_wide_a2          wave per marginal: its 2^lo / r (or 2^hi / r) chunk sums, converted to the wire form, one or two per lane, then the
-//                      lane-cooperative tree of k_marginals_h.  Output: 2 x 2^lo wire records per MSM laid out as TWO bucket groups of 2^lo
+//   k_wide_a1          level one, thread (plane, marginal, chunk): the sum of the chunk's 2^rlog = 16 buckets, sequentially, B29 in -> B29 out (2^16 threads per
+//                      MSM; plane 0 reads 16 consecutive records, plane 1 a column: neighbouring lanes read neighbouring records).
+//   k_wide_l2          level two, thread per run of 2^flog = 4 consecutive chunk records of a marginal, the same body (wide_sum29): 2^14 threads per MSM,
+//                      B29 in -> B29 out.  Either level writes a marker record where add29 cannot exclude an exceptional case (level two also where
+//                      an input is a marker); k_wide_a2 redoes a marked run exactly from its chunk records, a marked chunk in it from its buckets.
+//   k_wide_a2          wave per 16 run records, i.e. one hi-digit marginal of 16 runs or two lo-digit marginals of 8: converted to the wire form, one
+//                      per lane, then 4 or 3 lane-cooperative additions (coop.cuh).  Output: 2 x 2^lo wire records per MSM laid out as TWO bucket groups of 2^lo
 //                      buckets for k_marginals_q / k_marginal_fin_q -- group 0 holds H_a at slot a - 1 (weight a; H_0 has weight 0 and is
 //                      dropped, slots >= 2^hi - 1 are the identity), group 1 holds L_b at slot b.
-struct WideGeom { u32 nb, lo, hi, rlog; };
+struct WideGeom { u32 nb, lo, hi, rlog, flog; };      // buckets, the two digit widths, log2 of the chunk (level one) and of the run of chunks (level two)
 // split buckets only (slist: pass B's list of buckets with more than one task; count in xlist[1]), ONE launch (round 6; until then this kernel listed the hot
 // buckets for k_bucket_chunk / k_bucket_big and k_big_to29 converted their sums: three more empty dependent launches for unskewed scalars).
 //   (1) a thread sums a bucket of up to SMALL_NT partials by itself (2^22 uniform scalars: 16 K buckets of two partials);
@@ -1644,9 +1646,29 @@ __device__ __forceinline__ void wide_a1_item(const WideGeom& g, u32 out, u32& t0
     const u32 cpm = (1u << g.hi) >> g.rlog, v = out - per, b = v / cpm, s = v - b * cpm;      // chunks per lo-digit marginal
     t0 = ((s << g.rlog) << g.lo) + b; tstride = 1u << g.lo;
 }
-// a record whose zz limb 0 is all ones (no normalised limb is): "this chunk's lazy sum met a possible exceptional case" -- k_wide_a2 redoes the chunk exactly
+// a record whose zz limb 0 is all ones (no normalised limb is): "this lazy sum met a possible exceptional case" -- k_wide_a2 redoes it exactly, from the
+// records one level down
 template <class F>
 __device__ __forceinline__ bool is_marker29(const Acc29<F>& a) { return a.zz.v[0] == 0xffffffffu; }
+// One thread's share of a level of the lazy reduction, the same at both levels: the sum of the n records `stride` bytes apart from `in`, in sequence.
+// Three outcomes: the sum; the identity record when every input is one; a marker when add29 cannot exclude an exceptional case or an input is itself a
+// marker (level two only: no bucket record is one).
+template <class BF>
+__device__ __forceinline__ void wide_sum29(const uint8_t* __restrict__ in, size_t stride, u32 n, uint8_t* __restrict__ o) {
+    Acc29<BF> acc;
+    bool have = false, ok = true;
+#pragma unroll 1
+    for (u32 i = 0; i < n; i++) {
+        const Acc29<BF> b = load_b29<BF>(in + (size_t)i * stride);
+        if (is_identity29<BF>(b)) continue;
+        if (!have) { acc = b; have = true; ok = !is_marker29<BF>(b); }
+        else ok = !is_marker29<BF>(b) && add29<BF>(acc, b);
+        if (!ok) break;
+    }
+    if (!ok) { acc.zz.v[0] = 0xffffffffu; store_b29<BF>(o, acc); return; }      // (the marker's other limbs are not read)
+    if (have) store_b29<BF>(o, acc); else store_b29_identity<BF>(o);
+}
+// level one: 2^rlog bucket records -> the chunk record of (plane, marginal, chunk)
 template <class BF>
 __global__ void __launch_bounds__(256)
 k_wide_a1(const uint8_t* __restrict__ buckets29, WideGeom g, u32 ngroups, uint8_t* __restrict__ out29) {
@@ -1660,21 +1682,18 @@ k_wide_a1(const uint8_t* __restrict__ buckets29, WideGeom g, u32 ngroups, uint8_
     if (u >= per) { const u32 v = u - per, b = v & ((1u << g.lo) - 1u), sc = v >> g.lo; out = per + b * ((1u << g.hi) >> g.rlog) + sc; }
     u32 t0, ts;
     wide_a1_item(g, out, t0, ts);
-    const uint8_t* B = buckets29 + ((size_t)q * g.nb + t0) * B29_BYTES;
-    Acc29<BF> acc;
-    bool have = false, ok = true;
-    const u32 r = 1u << g.rlog;
-#pragma unroll 1
-    for (u32 i = 0; i < r; i++) {
-        const Acc29<BF> b = load_b29<BF>(B + (size_t)i * ts * B29_BYTES);
-        if (is_identity29<BF>(b)) continue;
-        if (!have) { acc = b; have = true; continue; }
-        ok = add29<BF>(acc, b);
-        if (!ok) break;
-    }
-    uint8_t* o = out29 + ((size_t)q * items + out) * B29_BYTES;
-    if (!ok) { acc.zz.v[0] = 0xffffffffu; store_b29<BF>(o, acc); return; }
-    if (have) store_b29<BF>(o, acc); else store_b29_identity<BF>(o);
+    wide_sum29<BF>(buckets29 + ((size_t)q * g.nb + t0) * B29_BYTES, (size_t)ts * B29_BYTES, 1u << g.rlog, out29 + ((size_t)q * items + out) * B29_BYTES);
+}
+// level two: 2^flog consecutive chunk records of one marginal -> a run record.  A marginal's chunk records are consecutive in both planes and 2^flog divides
+// their number, so run record j of the whole batch is the sum of the chunk records j 2^flog .. (j + 1) 2^flog - 1, whatever its plane and its MSM.
+// (Lanes read records 2^flog apart, as in plane 0 of level one; the level reads what k_wide_a1 has just written, 9 MB per MSM.)
+template <class BF>
+__global__ void __launch_bounds__(256)
+k_wide_l2(const uint8_t* __restrict__ in29, u32 flog, u32 nrec, uint8_t* __restrict__ out29) {
+    KH_HIGH_PRIO();
+    const u32 gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= nrec) return;
+    wide_sum29<BF>(in29 + ((size_t)gid << flog) * B29_BYTES, B29_BYTES, 1u << flog, out29 + (size_t)gid * B29_BYTES);
 }
 // the exact sum of one chunk (k_wide_a2's rare path; kept out of line so that its registers do not weigh on the kernel)
 template <class BF>
@@ -1689,41 +1708,53 @@ __device__ __attribute__((noinline)) Xyzz<BF> wide_chunk_exact(const uint8_t* __
     }
     return acc;
 }
+// the exact sum of run `run` of a group from its chunk records, a marked chunk among them from its buckets (rare path, out of line as above)
+template <class BF>
+__device__ __attribute__((noinline)) Xyzz<BF> wide_run_exact(const uint8_t* __restrict__ chunks29g, const uint8_t* __restrict__ buckets29g, WideGeom g, u32 run) {
+    Xyzz<BF> acc = Xyzz<BF>::identity();
+    const u32 f = 1u << g.flog, c0 = run << g.flog;
+    for (u32 i = 0; i < f; i++) {
+        const Acc29<BF> b = load_b29<BF>(chunks29g + (size_t)(c0 + i) * B29_BYTES);
+        if (is_marker29<BF>(b)) acc = add<BF>(acc, wide_chunk_exact<BF>(buckets29g, g, c0 + i));
+        else if (!is_identity29<BF>(b)) acc = add<BF>(acc, xyzz_from29<BF>(b));
+    }
+    return acc;
+}
+// The last records of the marginals, to the wire form: a wave takes 16 consecutive run records of a group, i.e. 16 / s whole marginals of s = 2^(lo or hi) >>
+// (rlog + flog) runs each (the host chooses flog so that s <= 16 in both planes).  Lane l < 16 converts record l (a marker: redone exactly), the 16 quads add
+// the s records of each marginal up in log2 s cooperative steps, and the first quad of each marginal writes its slot.  The wave of plane 0 also writes its
+// share of the identity padding behind H's 2^hi - 1 slots.
 template <class BF>
 __global__ void __launch_bounds__(64)
-k_wide_a2(const uint8_t* __restrict__ in29, const uint8_t* __restrict__ buckets29, WideGeom g, uint8_t* __restrict__ outw) {
+k_wide_a2(const uint8_t* __restrict__ runs29, const uint8_t* __restrict__ chunks29, const uint8_t* __restrict__ buckets29, WideGeom g, uint8_t* __restrict__ outw) {
     KH_HIGH_PRIO();
-    __shared__ u32 stage[32][64];                        // [word of the XYZZ record][lane]
-    const u32 slot = blockIdx.x, q = blockIdx.y, plane = slot >> g.lo, sidx = slot & ((1u << g.lo) - 1u);
-    const u32 per = g.nb >> g.rlog, items = 2u * per;
-    const u32 lane = threadIdx.x, role = lane & 3u, quad = lane >> 2;
-    uint8_t* o = outw + (((size_t)q * 2 + plane) * (1u << g.lo) + sidx) * 128;
-    u32 cnt, first;
-    if (plane == 0) {
-        const u32 a = sidx + 1u;
-        if (a >= (1u << g.hi)) { if (lane < 4) quad_store<BF>(o, Fe<BF>::zero()); return; }
-        cnt = (1u << g.lo) >> g.rlog; first = a * cnt;
-    } else { cnt = (1u << g.hi) >> g.rlog; first = per + sidx * cnt; }
-    const uint8_t* src = in29 + ((size_t)q * items + first) * B29_BYTES;
-    Xyzz<BF> a = Xyzz<BF>::identity();
-    for (u32 k = lane; k < cnt; k += 64) {
-        const Acc29<BF> b = load_b29<BF>(src + (size_t)k * B29_BYTES);
-        if (__builtin_expect(is_marker29<BF>(b), 0)) a = add<BF>(a, wide_chunk_exact<BF>(buckets29 + (size_t)q * g.nb * B29_BYTES, g, first + k));
-        else if (!is_identity29<BF>(b)) a = add<BF>(a, xyzz_from29<BF>(b));
+    __shared__ u32 stage[32][16];                        // [word of the XYZZ record][record of the wave]
+    const u32 q = blockIdx.y, lane = threadIdx.x, role = lane & 3u, quad = lane >> 2;
+    const u32 per = g.nb >> g.rlog, per2 = per >> g.flog;                        // chunk records and run records of a plane
+    const u32 r0 = blockIdx.x * 16u, plane = r0 >= per2 ? 1u : 0u;                // (16 divides per2: a wave stays in one plane)
+    const u32 s = ((1u << (plane ? g.hi : g.lo)) >> g.rlog) >> g.flog;           // runs per marginal, a power of two <= 16
+    uint8_t* const og = outw + ((size_t)q * 2 + plane) * (1u << g.lo) * 128;
+    if (lane < 16) {
+        const u32 run = r0 + lane;
+        const Acc29<BF> b = load_b29<BF>(runs29 + ((size_t)q * 2 * per2 + run) * B29_BYTES);
+        Xyzz<BF> a = Xyzz<BF>::identity();
+        if (__builtin_expect(is_marker29<BF>(b), 0)) a = wide_run_exact<BF>(chunks29 + (size_t)q * 2 * per * B29_BYTES, buckets29 + (size_t)q * g.nb * B29_BYTES, g, run);
+        else if (!is_identity29<BF>(b)) a = xyzz_from29<BF>(b);
+#pragma unroll
+        for (int k = 0; k < 8; k++) { stage[k][lane] = a.x.v[k]; stage[8 + k][lane] = a.y.v[k]; stage[16 + k][lane] = a.zz.v[k]; stage[24 + k][lane] = a.zzz.v[k]; }
     }
-#pragma unroll
-    for (int k = 0; k < 8; k++) { stage[k][lane] = a.x.v[k]; stage[8 + k][lane] = a.y.v[k]; stage[16 + k][lane] = a.zz.v[k]; stage[24 + k][lane] = a.zzz.v[k]; }
     __syncthreads();
-    auto parked = [&](u32 point) {
-        Fe<BF> r;
+    Fe<BF> acc;
 #pragma unroll
-        for (int k = 0; k < 8; k++) r.v[k] = stage[role * 8 + k][point];
-        return r;
-    };
-    Fe<BF> acc = parked(quad);
-    for (u32 k = 1; k < 4; k++) acc = quad_add<BF>(acc, parked(quad + 16 * k));
-    for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
-    if (lane < 4) quad_store<BF>(o, acc);
+    for (int k = 0; k < 8; k++) acc.v[k] = stage[role * 8 + k][quad];
+    // quad j of a marginal <- quads j and j + d: after the last step the marginal's first quad holds its sum (what the other quads hold is not used)
+    for (u32 d = s >> 1; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, (int)d));
+    if ((quad & (s - 1u)) == 0u) {
+        const u32 m = (r0 - plane * per2 + quad) / s;                            // the marginal: hi digit a in plane 0 (slot a - 1; H_0 is dropped), lo digit b in plane 1
+        if (plane || m) quad_store<BF>(og + (size_t)(m - (plane ? 0u : 1u)) * 128, acc);
+    }
+    if (plane == 0 && lane < 4)                            // identity padding: slots 2^hi - 1 .. 2^lo - 1, shared out among plane 0's waves
+        for (u32 p = (1u << g.hi) - 1u + blockIdx.x; p < (1u << g.lo); p += per2 / 16u) quad_store<BF>(og + (size_t)p * 128, Fe<BF>::zero());
 }
 
 // ------------------------------------------------------------------------------------ precomputed window tables
@@ -1881,9 +1912,9 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     // wide-path constants (measured best, tools/wide_sweep.py): ranks of one partition side by side in the accumulation order; blocks of the
     // accumulation per CU (held down with dynamic LDS); log2 of the chunk length of the first reduction level
     static constexpr u32 wide_og = 16, wide_acc_blocks = 3, wide_rlog = 4;
-    // k_part2_sort interleaves `og` consecutive ranks of a partition: og must divide the 2^(c - 9) buckets of a partition; k_wide_a1 / _a2 cut both digit
-    // planes into chunks of 2^rlog buckets: rlog <= min(lo, hi) -- for every wide c (> 16)
-    static_assert((wide_og & (wide_og - 1)) == 0 && wide_og <= (1u << (17 - 9)) && wide_rlog >= 1 && wide_rlog <= 17 / 2, "wide-path constants");
+    // k_part2_sort interleaves `og` consecutive ranks of a partition: og must divide the 2^(c - 9) buckets of a partition; k_wide_a1 cuts both digit
+    // planes into chunks of 2^rlog buckets and k_wide_l2 the chunks of a marginal into runs of 2^flog, flog = max(lo - rlog - 4, 1), which leaves a marginal at most 16 runs -- for every wide c (> 16)
+    static_assert((wide_og & (wide_og - 1)) == 0 && wide_og <= (1u << (17 - 9)) && wide_rlog >= 1 && wide_rlog + 2 <= 17 / 2, "wide-path constants");
     // dynamic LDS that leaves room for exactly wide_acc_blocks blocks on a CU, from the device's own LDS size (160 KB on gfx950), never more than one block
     // may ask for: where the request cannot hold the count down the kernel simply runs at its register-limited occupancy
     size_t wide_acc_lds = (Ctx.lds_per_cu / (wide_acc_blocks + 1) + 1024) & ~(size_t)1023;
@@ -1892,8 +1923,12 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         if ((rc = C.ws_xlist.reserve((3 * max_tasks + 8) * sizeof(u32)))) return rc;       // (key, chunk) pairs of the extra chunks, then the split buckets' keys
         if ((rc = C.ws_handed.reserve((2 * max_tasks + 4) * sizeof(u32)))) return rc;
         wg.nb = nb; wg.lo = (u32)c / 2; wg.hi = (u32)(c - 1) - wg.lo; wg.rlog = wide_rlog;
+        // level two leaves k_wide_a2 sixteen run records per hi-digit marginal (c = 20: runs of 4 chunks, 16 + 8 records).  Runs of 8 halve k_wide_a2's work again,
+        // but their seven additions in sequence made the synchronous MSM 8 us longer than it was with one level; runs of 4 leave it as it was (NOTES 7)
+        wg.flog = wg.lo > wg.rlog + 5 ? wg.lo - wg.rlog - 4 : 1;
         if ((rc = C.ws_b29.reserve(nkeys * B29_BYTES))) return rc;
         if ((rc = C.ws_a1.reserve(ngroups * 2 * (size_t)(nb >> wg.rlog) * B29_BYTES))) return rc;
+        if ((rc = C.ws_l2.reserve(ngroups * 2 * (size_t)(nb >> (wg.rlog + wg.flog)) * B29_BYTES))) return rc;
         if ((rc = C.ws_a2.reserve(ngroups * 2 * ((size_t)1 << wg.lo) * 128))) return rc;
     }
     // segment length of the weighted reduction: one bucket per thread (a 15-bit double-and-add each)
@@ -2133,7 +2168,11 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         const u32 items = 2u * (nb >> wg.rlog) * (u32)ngroups;
         hipLaunchKernelGGL((k_wide_a1<BF>), dim3((items + 255) / 256), dim3(256), 0, s, b29, wg, (u32)ngroups, C.ws_a1.as<uint8_t>());
         C.timer.mark("reduce_a1", s);
-        hipLaunchKernelGGL((k_wide_a2<BF>), dim3(2u << wg.lo, (unsigned)ngroups), dim3(64), 0, s, C.ws_a1.as<uint8_t>(), b29, wg, C.ws_a2.as<uint8_t>());
+        // (one-wave blocks: the 256 waves per MSM each carry a chain of 2^flog - 1 additions, and a wave alone on its SIMD runs it fastest)
+        const u32 runs = 2u * (nb >> (wg.rlog + wg.flog)) * (u32)ngroups;
+        hipLaunchKernelGGL((k_wide_l2<BF>), dim3((runs + 63) / 64), dim3(64), 0, s, C.ws_a1.as<uint8_t>(), wg.flog, runs, C.ws_l2.as<uint8_t>());
+        hipLaunchKernelGGL((k_wide_a2<BF>), dim3(runs / (u32)ngroups / 16u, (unsigned)ngroups), dim3(64), 0, s, C.ws_l2.as<uint8_t>(), C.ws_a1.as<uint8_t>(), b29, wg,
+                           C.ws_a2.as<uint8_t>());
         hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)tail_groups), dim3(256), 0, s, C.ws_a2.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)tail_groups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
         direct_out = true;

@@ -5,7 +5,7 @@ VALU instructions do not all cost the same on gfx950 (tools/microbench.hip, prof
 v_sub_u32 / v_and / v_or / shifts / v_fma_f32 issue in ~2.4 cycles per wave64 instruction per SIMD, everything else the
 kernel uses (v_mad_u64_u32, v_bfi, v_alignbit, v_lshrrev_b64, carry ops, v_add3) in ~4.2-4.4.  The issue-bound time of a
 launch is therefore  sum over opcodes (executed count x measured cycles), with the executed count = SQ_INSTS_VALU (PMC)
-split by the opcode histogram of the loop body's dominant basic block (the mixed addition: ~95 % of the loop).
+split by the opcode histogram of every basic block inside the loop around the mixed addition's products.
 
 Compiles csrc/msm.hip to gfx950 assembly (hipcc cross-compiles without a GPU) and writes
 profiles/<round>_k_accumulate29_valu_mix.json: {"source_sha256", "kernel", "block_instructions", "valu_histogram"}.
@@ -49,19 +49,36 @@ def main():
     kern = NARROW_KERNEL if narrow else KERNEL
     start = next(i for i, l in enumerate(lines) if l.startswith(kern) and l.split(";")[0].strip().endswith(":"))
     end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    blocks, cur = {"entry": []}, "entry"
+    blocks, cur = [["entry", []]], 0                     # basic blocks in layout order: [label, opcodes], and the branch targets of each
+    targets = {}
     for l in lines[start + 1:end]:
         l = l.split(";")[0].strip()
         if not l:
             continue
         if l.endswith(":") and l.startswith(".LBB"):
-            cur = l[:-1]; blocks[cur] = []
+            blocks.append([l[:-1], []])
         elif not l.startswith("."):
-            blocks[cur].append(l.split()[0])
-    name, body = max(blocks.items(), key=lambda kv: sum(op == "v_mad_u64_u32" for op in kv[1]))
+            op = l.split()[0]
+            blocks[-1][1].append(op)
+            if op.startswith(("s_cbranch", "s_branch")):
+                targets.setdefault(len(blocks) - 1, []).append(l.split()[1])
+    index = {b[0]: i for i, b in enumerate(blocks)}
+    mads = [sum(op == "v_mad_u64_u32" for op in b[1]) for b in blocks]
+    dom = max(range(len(blocks)), key=lambda i: mads[i])   # the block of the mixed addition's products
+    # the loop around it: the innermost backward branch whose span (target block .. branching block) holds the dominant block.  Every block of
+    # the span is inside the loop (until this round only the dominant block was counted: 1312 of ~1790 VALU instructions per iteration of
+    # k_acc_wide29 -- the block of the first two products and the conditional negation were left out)
+    spans = [(index[t], i) for i, ts in targets.items() for t in ts if t in index and index[t] <= i and index[t] <= dom <= i]
+    if not spans:
+        raise SystemExit("no loop around the dominant block of " + kern)
+    lo, hi = min(spans, key=lambda sp: sp[1] - sp[0])
+    body = [op for b in blocks[lo:hi + 1] for op in b[1]]
     hist = Counter(op for op in body if op.startswith("v_"))
-    res = {"source_sha256": source_hash(), "kernel": ("k_accumulate29" if narrow else "k_acc_wide29") + "<FqParams>", "block": name, "block_instructions": len(body),
-           "block_valu_instructions": sum(hist.values()), "valu_histogram": dict(sorted(hist.items(), key=lambda kv: -kv[1]))}
+    res = {"source_sha256": source_hash(), "kernel": ("k_accumulate29" if narrow else "k_acc_wide29") + "<FqParams>",
+           "block": "every block of the loop, %s .. %s" % (blocks[lo][0], blocks[hi][0]),
+           "loop_blocks": [{"label": b[0], "instructions": len(b[1]), "valu": sum(op.startswith("v_") for op in b[1]), "v_mad_u64_u32": m}
+                           for b, m in zip(blocks[lo:hi + 1], mads[lo:hi + 1])],
+           "block_instructions": len(body), "block_valu_instructions": sum(hist.values()), "valu_histogram": dict(sorted(hist.items(), key=lambda kv: -kv[1]))}
     json.dump(res, open(out, "w"), indent=1)
     print(json.dumps(res, indent=1))
 
