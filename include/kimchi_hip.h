@@ -65,7 +65,8 @@ int kh_get_device(void);              /* the calling thread's current device (-1
  * main stream, MSM pipeline slots, workspaces and lock -- instead of the device's shared one, so that independent provers neither queue their vector steps
  * on one stream nor serialise their launches on one mutex (measured: four provers 150 -> 165-176 proofs/s; four processes: 177).  Everything the thread
  * queues in between is complete when _end returns; tickets of kh_msm_submit must be waited for before _end; work the thread queued on the shared context
- * before _begin is ordered in front.  SRS handles, device buffers and indexes are process-wide as before (a handle still runs one opening at a time).
+ * before _begin is ordered in front.  SRS handles, device buffers and indexes are process-wide as before: one handle and one index serve every prover thread (up to
+ * KH_IPA_OPENINGS openings run over a handle's tables at once, see kh_ipa_begin).
  * kh_prove* do this themselves.  Contexts are pooled per device and reused. */
 int kh_private_context_begin(void);
 int kh_private_context_end(void);
@@ -90,7 +91,7 @@ int kh_msm_set_wide_min_n(size_t n);
 int kh_msm_set_sort_staging(unsigned entries, unsigned max_passes);
 /* The wide set is OPTIONAL: if it does not fit in device memory when the handle is created, the handle is created without it (the narrow tables serve every
  * MSM, ~8 % slower at 2^20) and no error is reported.  kh_srs_set_wide_tables(srs, 0) gives an existing wide set back (832 MiB at 2^20 points, 3.3 GiB at
- * 2^22) -- no MSM over the handle may be in flight, as for kh_srs_free --, (srs, 1) builds it now whatever the threshold says and fails with KH_E_NOMEM if it
+ * 2^22) -- KH_E_INVALID while an MSM over the handle is in flight, submitted by ANY thread or context (the handle counts them) --, (srs, 1) builds it now whatever the threshold says and fails with KH_E_NOMEM if it
  * does not fit; kh_srs_has_wide_tables tells which state the handle is in. */
 int kh_srs_set_wide_tables(kh_srs_t *srs, int on);
 int kh_srs_has_wide_tables(const kh_srs_t *srs);
@@ -330,8 +331,11 @@ int kh_ipa_verify_msm(kh_srs_t *srs, const uint64_t *chals, size_t chals_len, co
  * L, R and sg are the reference's group elements (bit-identical affine coordinates); the basis is never folded:
  * round j's L / R are MSMs over the SRS's resident window tables with the scalars a (x) (challenge tensor), and
  * sg = <challenge tensor, G>.  The blinding base H is the handle's (kh_srs_set_blinding_base);
- * the SRS size must be a power of two; one opening at a time per SRS handle (KH_E_INVALID otherwise).
+ * the SRS size must be a power of two.  Up to KH_IPA_OPENINGS openings begun by DIFFERENT threads run over one handle's tables at the same time (each has
+ * its own workspace on the handle and its own slot for U in the handle's tables); a further kh_ipa_begin waits until one of them is freed.  A thread
+ * that begins a second opening on a handle before freeing its first gets KH_E_INVALID.
  * All field elements Montgomery limbs; u_pre as in kh_ipa_fold_points_endo. */
+#define KH_IPA_OPENINGS 4          /* = KH_MSM_SLOTS: more openings than pipeline slots could not overlap anyway */
 typedef struct kh_ipa kh_ipa_t;
 int kh_ipa_begin(kh_srs_t *srs, const uint64_t *a, size_t a_len, const uint64_t *b, size_t b_len,
                  const uint64_t u_base_xy[8], kh_ipa_t **out);
@@ -376,7 +380,8 @@ int kh_commit_non_hiding(kh_srs_t *srs, const uint64_t *coeffs, size_t len, size
  * A domain larger than the evaluations' domain is the reference's panic: returns KH_E_INVALID. */
 int kh_commit_evaluations_non_hiding(kh_srs_t *srs, unsigned log2_domain, const uint64_t *evals, size_t evals_len,
                                      uint64_t *out_xy, uint8_t *out_inf, size_t *out_count);
-/* Blinding base h of the SRS (ipa::SRS::h); defaults to SRS::create's h (ipa.rs:765-772). */
+/* Blinding base h of the SRS (ipa::SRS::h); defaults to SRS::create's h (ipa.rs:765-772).  Setting it while an opening is live on the handle
+ * (between kh_ipa_begin and kh_ipa_free, on any thread) is refused with KH_E_INVALID: the openings' rounds read H from the handle's tables. */
 int kh_srs_set_blinding_base(kh_srs_t *srs, const uint64_t h_xy[8]);
 int kh_srs_get_blinding_base(const kh_srs_t *srs, uint64_t h_xy[8]);
 /* kh_mask_custom = SRS::mask_custom (ipa.rs:605-622): out_j = blinders_j * h + com_j on the host
@@ -474,7 +479,9 @@ int kh_last_timings(const char **names, float *ms, int cap);
 /* Process-wide event counters (how often a path ran): "spread_retry" (an opening round's MSM met a hot bucket and was re-run with the hot-bucket
  * kernels), "fused_retry" (the one-launch sort gave up), "rebase_launch" / "rebase_switch" / "rebase_abandon" (openings that started
  * materialising the folded basis of their late rounds, switched over to it, gave it up), "rebased_rounds" (rounds that ran over a materialised
- * basis), "lookup_sorted_dev" (successful kh_lookup_sorted_dev calls; kh_prove makes one per proof with lookups).  Unknown names read 0. */
+ * basis), "lookup_sorted_dev" (successful kh_lookup_sorted_dev calls; kh_prove makes one per proof with lookups), "ipa_concurrent" (kh_ipa_begin calls
+ * that found another opening live on the same handle and went ahead beside it), "ipa_waited" (kh_ipa_begin calls that found every workspace of the handle
+ * claimed; counted before the wait starts).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,

@@ -1,6 +1,7 @@
 // api_internal.hpp -- what crosses a file boundary between the translation units of the extern "C" boundary (context.hip, srs.cpp, msm_api.cpp,
 // opening.cpp, vector_api.cpp, debug_api.cpp).  State stays private to the file that owns it: only types and functions are declared here.
 #pragma once
+#include <atomic>
 #include <map>
 #include <memory>
 
@@ -12,44 +13,60 @@ namespace kh {
 struct LagrangeChunk { DevBuf pts; DevBuf inf; bool has_inf = false; size_t n = 0; int precomp_c = 0; };
 }  // namespace kh
 
+namespace kh {
+// Everything one opening needs besides the handle's tables: a handle owns up to KH_IPA_OPENINGS of them (kh_srs::ipa_ws), each allocated the first time an
+// opening claims it and kept across openings (hipMalloc / hipFree cost ~0.1 ms each: 1 ms per proof).  Workspace j writes U into slot n + 1 + j of the
+// handle's window tables.  `live` / `owner` are guarded by the handle's ipa_mu; the rest belongs to the opening that holds the claim.
+struct IpaWorkspace {
+    int index = 0;            // j: which U slot of the handle's tables is this workspace's
+    bool live = false;        // claimed by an opening (kh_ipa_begin .. kh_ipa_free)
+    std::thread::id owner;    // ... begun by this thread (the SAME thread beginning a second one is a programming error)
+    DevBuf a[2], b[2], coef[2], sc, partial, sg;
+    hipEvent_t ev = nullptr;
+    // the late rounds' materialised folded basis (csrc/rebase.hip): its window tables, the materialisation's workspaces, a low-priority side stream, the
+    // events that order it against the rounds, a pinned "an output was the identity" word
+    DevBuf rb_tab, rb_B, rb_part, rb_lists, rb_scratch;
+    hipStream_t rb_stream = nullptr;
+    hipEvent_t rb_go = nullptr, rb_snap = nullptr, rb_done = nullptr;
+    uint32_t* rb_fail = nullptr;
+    ~IpaWorkspace() {                                               // the DevBufs free themselves
+        if (ev) (void)hipEventDestroy(ev);
+        if (rb_go) (void)hipEventDestroy(rb_go);
+        if (rb_snap) (void)hipEventDestroy(rb_snap);
+        if (rb_done) (void)hipEventDestroy(rb_done);
+        if (rb_stream) { (void)hipStreamSynchronize(rb_stream); (void)hipStreamDestroy(rb_stream); }
+        if (rb_fail) (void)hipHostFree(rb_fail);
+    }
+};
+}  // namespace kh
+
 struct kh_srs {
     int curve = 0;
     int device = -1;          // the device its tables live on: every entry point taking this handle runs there
     size_t n = 0;
-    kh::DevBuf g;                 // window tables of g_stride = n + 2 points: g[0..n), then the slots of H and U
-    size_t g_stride = 0;      // (the two extra bases of the opening rounds, written by kh_ipa_begin)
+    kh::DevBuf g;                 // window tables of g_stride = n + 1 + KH_IPA_OPENINGS points: g[0..n), the slot of H, then one slot of U per opening workspace
+    size_t g_stride = 0;      // (the extra bases of the opening rounds: H written once per handle, U by every kh_ipa_begin into its workspace's slot)
     int g_precomp_c = 0;
     kh::DevBuf g_wide; int g_wide_c = 0;   // second table set with wide windows (MSM_WIDE_C) for bases of >= msm_wide_min_n() points: big single MSMs
-    bool ipa_live = false;    // the U slot belongs to one opening at a time
-    std::thread::id ipa_owner;   // ... begun by this thread (a second opening from ANOTHER thread waits for it: SRS::open is re-entrant on &self)
-    // workspace of the opening rounds, kept across openings (hipMalloc / hipFree cost ~0.1 ms each: 1 ms per proof)
-    kh::DevBuf ipa_a[2], ipa_b[2], ipa_coef[2], ipa_sc, ipa_partial, ipa_sg;
-    hipEvent_t ipa_ev = nullptr;
-    // the late rounds' materialised folded basis (csrc/rebase.hip): its window tables, the materialisation's workspaces, a low-priority side stream, the
-    // events that order it against the rounds, a pinned "an output was the identity" word
-    kh::DevBuf ipa_rb_tab, ipa_rb_B, ipa_rb_part, ipa_rb_lists, ipa_rb_scratch;
-    hipStream_t ipa_rb_stream = nullptr;
-    hipEvent_t ipa_rb_go = nullptr, ipa_rb_snap = nullptr, ipa_rb_done = nullptr;
-    uint32_t* ipa_rb_fail = nullptr;
+    // MSM jobs in flight that were resolved against this handle (kh::resolve_basis: the ones that may read the wide set), whatever context queued them:
+    // counted under wide_mu together with the resolution (msm_api.cpp: resolve_counted), so that kh_srs_set_wide_tables(srs, 0) on another thread never frees tables a job reads.
+    // Shared with the pipeline slots (MsmSlot::handle_jobs): a ticket may be waited for after the handle is gone.
+    std::shared_ptr<std::atomic<int>> jobs = std::make_shared<std::atomic<int>>(0);
+    std::mutex wide_mu;
+    // the openings' workspaces (guarded by ipa_mu; allocated on first need, lowest index first: a handle used by one thread at a time only ever has [0])
+    std::unique_ptr<kh::IpaWorkspace> ipa_ws[KH_IPA_OPENINGS];
     uint64_t h[8];
     // fixed-base table of the blinding base: h_table[i * 255 + (j - 1)] = j * 2^(8 i) * h (XYZZ), built on first use:
     // SRS::mask_custom is one scalar multiplication by h per chunk (ipa.rs:605-622) -- 32 additions instead of 255
     // doublings + ~128 additions (a proof masks 23 commitments: 3.5 ms of host time otherwise)
     std::vector<khost::xyzz> h_table;
-    std::vector<uint64_t> h_multiples;     // 2^(c w) * h for the W windows (affine, 8 words each): slots of the opening's MSMs
-    std::mutex h_mu;
-    // handle-level locks (callers may be on different contexts, kh_private_context_begin): the basis map, and the one opening a handle runs at a time
+    std::vector<uint64_t> h_multiples;     // 2^(c w) * h for the W windows (affine, 8 words each): slot n of the handle's tables
+    bool h_in_tables = false;              // ... and they are there (uploaded by the first opening after creation / kh_srs_set_blinding_base)
+    std::mutex h_mu;                       // h_table, h_multiples, h_in_tables
+    // handle-level locks (callers may be on different contexts, kh_private_context_begin): the basis map, and the claims on the openings' workspaces
     std::mutex map_mu;
     std::mutex ipa_mu; std::condition_variable ipa_cv;
     std::map<unsigned, std::vector<std::unique_ptr<kh::LagrangeChunk>>> lagrange;
-    ~kh_srs() {                                                     // the DevBufs free themselves
-        if (ipa_ev) (void)hipEventDestroy(ipa_ev);
-        if (ipa_rb_go) (void)hipEventDestroy(ipa_rb_go);
-        if (ipa_rb_snap) (void)hipEventDestroy(ipa_rb_snap);
-        if (ipa_rb_done) (void)hipEventDestroy(ipa_rb_done);
-        if (ipa_rb_stream) { (void)hipStreamSynchronize(ipa_rb_stream); (void)hipStreamDestroy(ipa_rb_stream); }
-        if (ipa_rb_fail) (void)hipHostFree(ipa_rb_fail);
-    }
 };
 #define KH_ON_DEVICE_OF(srs) kh::DeviceScope dev_scope_((srs) ? (srs)->device : -1)
 

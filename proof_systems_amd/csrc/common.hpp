@@ -10,6 +10,7 @@
 #include <condition_variable>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <string>
@@ -132,6 +133,7 @@ struct MsmSlot {
     std::thread::id owner;             // the host thread that queued the pending job (acquire_slot: another thread's ticket will be waited for)
     uint64_t ticket = 0;
     MsmJob job;
+    std::shared_ptr<std::atomic<int>> handle_jobs;     // the pending job counts among an SRS handle's jobs in flight (kh_srs::jobs); dropped when the slot is released
     // the one-launch sort (k_sort_fused) spins on grid barriers and needs all its blocks resident at once; if another PROCESS shares the
     // GPU they may never be -- its barriers then give up after a bounded spin, set this host-visible word, and msm_finish re-runs the job
     // with the multi-launch sort and disables the fused path for the process
@@ -206,8 +208,8 @@ struct DeviceScope {               // run the rest of this scope on `device` (no
 };
 void collect_timings(Context& c, PhaseTimer& t);
 // process-wide event counters behind kh_counter (tests and tools read them: how often a rare path ran).  `name` must be one of COUNTER_NAMES.
-enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_LOOKUP_SORTED_DEV, CNT_COUNT };
-static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds", "lookup_sorted_dev"};
+enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_LOOKUP_SORTED_DEV, CNT_IPA_CONCURRENT, CNT_IPA_WAITED, CNT_COUNT };
+static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds", "lookup_sorted_dev", "ipa_concurrent", "ipa_waited"};
 std::atomic<uint64_t>& counter(CounterId id);
 
 // device exclusive scan of n u32 values (in may alias out); tmp is workspace

@@ -28,7 +28,7 @@ static thread_local int tl_hip_dev = -1;       // what this thread last passed t
 // A prover thread may take a context of its OWN for a stretch of work (kh_private_context_begin / _end; kh_prove does): own main stream, pipeline slots,
 // workspaces and lock, so that several provers in one process neither queue their vector steps on one stream nor serialise their launches on one mutex
 // (four single-prover processes: 177 proofs/s, four threads on the shared context: 128).  Private contexts are pooled per device and never destroyed,
-// like the shared ones.  What belongs to an SRS HANDLE (its Lagrange-basis map, the one opening it can run at a time) has its own locks (kh_srs).
+// like the shared ones.  What belongs to an SRS HANDLE (its Lagrange-basis map, the claims on its openings' workspaces) has its own locks (kh_srs).
 static thread_local Context* tl_private[KH_MAX_DEVICES];
 static std::vector<Context*> g_private_pool[KH_MAX_DEVICES];           // idle private contexts (guarded by g_ctx_mu)
 static std::atomic<int> g_private_made[KH_MAX_DEVICES];                 // private contexts ever created per device (they are never destroyed)

@@ -207,11 +207,14 @@ __global__ void k_ipa_fold(const u64* __restrict__ a, const u64* __restrict__ b,
 // Thread t expands point t (recomputing the folded a' it needs: a product, not a dependency on another thread's store); threads
 // below m = N'/2 also materialise a', b' at i and i + m and accumulate <a'_hi, b'_lo> / <a'_lo, b'_hi>; the block sums go to
 // `partial`, and the LAST block to finish (agent-scope counter) adds them up and fills the H / U scalar slots of both sides.
+// `extra`: the slots behind the n points of the table set the round's MSM runs over (1 + KH_IPA_OPENINGS on the handle's tables, 2 on rebased ones) --
+// each side's scalar vector has n + extra entries: the points, H, then the U slots; `uslot`: which of those is this opening's.  The other openings'
+// entries are left alone (zeroed by kh_ipa_begin: a zero digit makes no entry, their points are never fetched).
 // Replaces k_ipa_fold + k_ipa_ip + k_ipa_ip_fin + k_ipa_expand: four dependent launches (~25 us of an opening round) -> one.
 template <class F>
 __global__ void __launch_bounds__(256)
-k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __restrict__ coef, size_t n, size_t cur2, unsigned logN2, size_t ncoef,
-           int has_fold, Fe4 u4, Fe4 ui4, u64* __restrict__ a2, u64* __restrict__ b2, u64* __restrict__ coef2,
+k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __restrict__ coef, size_t n, size_t cur2, unsigned logN2, unsigned extra, size_t ncoef,
+           int has_fold, unsigned uslot, Fe4 u4, Fe4 ui4, u64* __restrict__ a2, u64* __restrict__ b2, u64* __restrict__ coef2,
            Fe4 rand_l, Fe4 rand_r, u64* __restrict__ sc, u64* __restrict__ partial, unsigned* __restrict__ counter) {
     __shared__ u32 sh[8 * 8];
     __shared__ unsigned is_last;
@@ -228,7 +231,7 @@ k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __re
         if (has_fold && (q & 1)) c = mul<F>(c, u);
         const Fe<F> v = mul<F>(a_at(lo ? r + m : r - m), c), z = Fe<F>::zero();
         (lo ? v : z).store(sc + 4 * t);
-        (lo ? z : v).store(sc + 4 * ((n + 2) + t));
+        (lo ? z : v).store(sc + 4 * ((n + extra) + t));
     }
     if (has_fold && t < 2 * ncoef) {                       // coef' = coef (x) (1, u)
         Fe<F> c = Fe<F>::load(coef + 4 * (t >> 1));
@@ -301,10 +304,10 @@ k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __re
 #pragma unroll
             for (int k = 0; k < 8; k++) { o.v[k] = sh[(2 * threadIdx.x) * 8 + k]; r2.v[k] = sh[(2 * threadIdx.x + 1) * 8 + k]; }
             o = add<F>(o, r2);
-            u64* dst = sc + 4 * ((size_t)threadIdx.x * (n + 2) + n);
+            u64* dst = sc + 4 * ((size_t)threadIdx.x * (n + extra) + n);
             const Fe4& r = threadIdx.x == 0 ? rand_l : rand_r;
             dst[0] = r.l[0]; dst[1] = r.l[1]; dst[2] = r.l[2]; dst[3] = r.l[3];
-            o.store(dst + 4);
+            o.store(dst + 4 * (1 + uslot));
         }
     }
     if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // re-armed for the next round
@@ -312,12 +315,12 @@ k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __re
 // cur2 = the vector length AFTER the pending fold (= cur if none); a2 / b2 / coef2 receive the folded vectors
 int ipa_round_step(hipStream_t s, int field, int has_fold, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t n, size_t cur2, size_t ncoef,
                    const uint64_t u[4], const uint64_t uinv[4], uint64_t* a2, uint64_t* b2, uint64_t* coef2,
-                   const uint64_t rand_l[4], const uint64_t rand_r[4], uint64_t* sc, uint64_t* partial, unsigned* counter) {
+                   const uint64_t rand_l[4], const uint64_t rand_r[4], uint64_t* sc, uint64_t* partial, unsigned* counter, unsigned extra, unsigned uslot) {
     unsigned logN2 = 0; while (((size_t)1 << logN2) < cur2) logN2++;
     Fe4 rl, rr, u4, ui4; memcpy(rl.l, rand_l, 32); memcpy(rr.l, rand_r, 32); memcpy(u4.l, u, 32); memcpy(ui4.l, uinv, 32);
     dim3 g((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_ipa_step<FpParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, ncoef, has_fold, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
-    else hipLaunchKernelGGL((k_ipa_step<FqParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, ncoef, has_fold, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
+    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_ipa_step<FpParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, extra, ncoef, has_fold, uslot, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
+    else hipLaunchKernelGGL((k_ipa_step<FqParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, extra, ncoef, has_fold, uslot, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
     KH_HIP(hipGetLastError());
     return KH_OK;
 }

@@ -52,6 +52,19 @@ const char* kh::slot_error(int si) {
     return si == -2 ? "no MSM pipeline slot came free and none changed hands for KH_SLOT_WAIT_S (default 30 s): a kh_msm_submit ticket was leaked (its owner never called kh_msm_wait)"
                     : "every MSM pipeline slot holds an un-waited kh_msm_submit ticket of this thread (or of threads blocked behind it): kh_msm_wait first";
 }
+// The basis a job on slot S will run with, and the job counted among the handle's jobs in flight (kh_srs::jobs) in the same step: kh_srs_set_wide_tables(srs, 0)
+// on another thread -- another context, another lock -- either sees the job or has taken the wide set away before it was resolved.  The count is dropped when
+// the slot is released (wait_then_finish), or by the guard when the job is never enqueued.
+static void uncount_handle_job(MsmSlot& S) { if (S.handle_jobs) { (*S.handle_jobs)--; S.handle_jobs.reset(); } }
+static int resolve_counted(kh_srs_t* srs, int basis, unsigned chunk, MsmBasis& b, MsmSlot& S) {
+    KH_REQUIRE(srs != nullptr, "null SRS handle");
+    std::lock_guard<std::mutex> wl(srs->wide_mu);
+    int rc = resolve_basis(srs, basis, chunk, b); if (rc) return rc;
+    S.handle_jobs = srs->jobs;
+    (*S.handle_jobs)++;
+    return KH_OK;
+}
+struct HandleJobGuard { MsmSlot& S; bool keep = false; ~HandleJobGuard() { if (!keep) uncount_handle_job(S); } };
 // enqueue on a free slot; returns the slot index through *slot_out
 static int msm_submit_locked(Context& C, kh_srs_t* srs, int basis, unsigned chunk, size_t offset, const uint64_t* scalars,
                              bool scalars_on_device, size_t n, size_t k, int mont, int* slot_out, std::unique_lock<std::mutex>* lk = nullptr,
@@ -61,8 +74,9 @@ static int msm_submit_locked(Context& C, kh_srs_t* srs, int basis, unsigned chun
     size_t use = n < b.n - offset ? n : b.n - offset;      // msm_bigint semantics: min(len) pairs
     int si = acquire_slot(lk, C);
     KH_REQUIRE(si >= 0, "%s", slot_error(si));
-    if (lk && (rc = resolve_basis(srs, basis, chunk, b))) return rc;     // acquire_slot may have dropped the lock: the basis map can have changed
     MsmSlot& S = C.slot[si];
+    if ((rc = resolve_counted(srs, basis, chunk, b, S))) return rc;      // (again: acquire_slot may have dropped the lock, the basis map can have changed)
+    HandleJobGuard counted{S};
     const uint64_t* sdev = scalars;
     if (!scalars_on_device && use > 0 && k > 0) {
         if ((rc = S.ws_scalars.reserve(k * use * 32))) return rc;
@@ -81,6 +95,7 @@ static int msm_submit_locked(Context& C, kh_srs_t* srs, int basis, unsigned chun
         if (C.main_dirty && S.stream != C.stream) KH_HIP(hipStreamWaitEvent(S.stream, C.order_ev, 0));
     }
     if ((rc = msm_enqueue(C, S, srs->curve, b, offset, sdev, use, k, mont))) return rc;
+    counted.keep = true;
     *slot_out = si;
     return KH_OK;
 }
@@ -125,6 +140,9 @@ int kh::wait_then_finish(std::unique_lock<std::mutex>& lk, Context& C, MsmSlot& 
     int rc;
     if (e != hipSuccess) { set_error("hipEventSynchronize: %s", hipGetErrorString(e)); S.busy = false; rc = KH_E_DEVICE; }
     else rc = msm_finish(C, S, out_xy, out_inf, flag_seen);
+    // the job (and any re-run of it inside msm_finish) reads its handle's tables no more -- or its wait failed (e != hipSuccess: a device error, after
+    // which it is not known to have ended; the slot is given up all the same, and so is the count: srs.cpp, kh_srs_set_wide_tables)
+    uncount_handle_job(S);
     C.cv.notify_all();
     return rc;
 }
@@ -204,12 +222,14 @@ static int msm_common(kh_srs_t* srs, int basis, unsigned chunk, size_t offset, c
         MsmBasis b; int r;
         int si = acquire_slot(&lk, C);
         KH_REQUIRE(si >= 0, "%s", slot_error(si));
-        if ((r = resolve_basis(srs, basis, chunk, b))) return r;         // after the wait: the lock was dropped meanwhile
         MsmSlot& S = C.slot[si];
+        if ((r = resolve_counted(srs, basis, chunk, b, S))) return r;    // after the wait: the lock was dropped meanwhile
+        HandleJobGuard counted{S};
         if ((r = S.ws_scalars.reserve(kk * n * 32))) return r;
         for (size_t j = 0; j < kk; j++)
             KH_HIP(hipMemcpyAsync((char*)S.ws_scalars.p + j * n * 32, grp->members[j].scalars, n * 32, hipMemcpyHostToDevice, S.stream));
         if ((r = msm_enqueue(C, S, srs->curve, b, offset, S.ws_scalars.as<uint64_t>(), n, kk, mont))) return r;
+        counted.keep = true;
         return wait_then_finish(lk, C, S, res.data(), rinf.data());
     };
     rc = run();

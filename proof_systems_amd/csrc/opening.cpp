@@ -227,21 +227,23 @@ struct kh_ipa {
     kh_srs_t* srs = nullptr;
     int curve = 0, field = 0;
     size_t n = 0, cur = 0, ncoef = 1;     // basis size, current vector length N_j, challenge tensor length 2^j
-    DevBuf *a = nullptr, *b = nullptr, *coef = nullptr;   // the SRS handle's workspace (ping-pong pairs)
-    DevBuf *sc = nullptr, *partial = nullptr;             // srs->ipa_sc / ipa_partial
+    IpaWorkspace* ws = nullptr;           // the workspace this opening claimed on the handle (given back by kh_ipa_free)
+    DevBuf *a = nullptr, *b = nullptr, *coef = nullptr;   // its ping-pong pairs
+    DevBuf *sc = nullptr, *partial = nullptr;             // ws->sc / ws->partial
+    unsigned extra = 0, uslot = 0;        // of the table set the rounds run over: slots behind the n points, and which U slot is this opening's (ipa.hip, k_ipa_step)
     int pp = 0;
     hipEvent_t ev = nullptr;              // orders the fold (library stream) before the next round's MSM (slot stream)
     bool lr_done = false;
     bool pending = false;                 // a recorded, not yet applied fold (kh_ipa_round_fold): the next round's step kernel applies it
     uint64_t u_p[4] = {0, 0, 0, 0}, ui_p[4] = {0, 0, 0, 0};
     size_t partial_words = 0;             // u64 words of `partial` before the step kernel's block counter
-    std::vector<uint64_t> tab;            // H / U window multiples staged for the asynchronous upload of kh_ipa_begin
+    std::vector<uint64_t> tab;            // U's window multiples staged for the asynchronous upload of kh_ipa_begin
     int sg_slot = -1;                     // pipeline slot holding the two half-sums of sg launched during the last round (kh_ipa_open), -1: none
     bool sg_want = false;                 // kh_ipa_open asks the last kh_ipa_round_lr to launch them
     bool spread_broken = false;           // a round's MSM disproved MSM_SPREAD_SCALARS (MsmJob::spread_rerun): the later rounds run without the hint
     bool rb_glv = false;                          // the folded basis's tables are GLV tables (half the doubling chain; MsmBasis::glv)
     void* round_tab = nullptr; int round_c = 0;   // table set the round MSMs run over (the SRS's own, or the rebased one)
-    size_t tab_stride = 0;                        // points per window table of that set (the SRS's g_stride; N + 2 after the rebase)
+    size_t tab_stride = 0;                        // points per window table of that set (the SRS's g_stride; N + 2 after the rebase: the folded basis, H, U)
     // Rebase (csrc/rebase.hip): after rb_j0 rounds the folded basis of rb_N = n / 2^rb_j0 points is materialised on a side stream while the rounds go on
     // over the original tables; the first round that finds it ready switches over (n, ncoef, round_tab, round_c, tab_stride change; a, b, coef do not).
     int rb_state = 0;                             // 0: not planned, 1: planned (launch behind round rb_j0 + 1's step kernel), 2: running, 3: switched, -1: abandoned
@@ -260,40 +262,63 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
     KH_REQUIRE(a_len <= n && a_len > 0, "polynomial of %zu coefficients does not fit the SRS (%zu)", a_len, n);
     KH_REQUIRE(b_len == n, "b must hold padded_length = %zu evaluation-point powers (got %zu)", n, b_len);
     int rc = ensure_init(); if (rc) return rc;
-    // the reference's SRS::open takes &self and is called from several threads on clones of one SRS (GpuSrs is Clone + Sync): a second
-    // opening on the same handle waits for the first to be freed; only the SAME thread beginning twice is a programming error.  The claim is
-    // the HANDLE's (its own lock: the callers may be on different contexts) and is given back by kh_ipa_free -- or here, if beginning fails.
+    // the reference's SRS::open takes &self and is called from several threads on clones of one SRS (GpuSrs is Clone + Sync): every opening claims one of
+    // the handle's KH_IPA_OPENINGS workspaces (its buffers, its U slot in the handle's tables) and runs beside the others; with all of them claimed a further
+    // one waits for a kh_ipa_free; only the SAME thread beginning twice is a programming error.  The claim is the HANDLE's (its own lock: the callers may be
+    // on different contexts) and is given back by kh_ipa_free -- or here, if beginning fails.
+    IpaWorkspace* wsp = nullptr;
     {
         std::unique_lock<std::mutex> hl(srs->ipa_mu);
-        KH_REQUIRE(!(srs->ipa_live && srs->ipa_owner == std::this_thread::get_id()), "another opening is in progress on this SRS in this thread (kh_ipa_free it first)");
-        srs->ipa_cv.wait(hl, [&] { return !srs->ipa_live; });
-        srs->ipa_live = true; srs->ipa_owner = std::this_thread::get_id();
+        const auto me = std::this_thread::get_id();
+        bool others = false;
+        for (auto& w : srs->ipa_ws) if (w && w->live) {
+            KH_REQUIRE(w->owner != me, "another opening is in progress on this SRS in this thread (kh_ipa_free it first)");
+            others = true;
+        }
+        auto find_free = [&]() -> int {                    // a workspace that exists before one that would have to be allocated
+            for (int j = 0; j < KH_IPA_OPENINGS; j++) if (srs->ipa_ws[j] && !srs->ipa_ws[j]->live) return j;
+            for (int j = 0; j < KH_IPA_OPENINGS; j++) if (!srs->ipa_ws[j]) return j;
+            return -1;
+        };
+        int j = find_free();
+        if (j < 0) {
+            counter(CNT_IPA_WAITED)++;                     // (before the wait: a test can see a blocked begin)
+            srs->ipa_cv.wait(hl, [&] { return (j = find_free()) >= 0; });
+        } else if (others) counter(CNT_IPA_CONCURRENT)++;
+        if (!srs->ipa_ws[j]) { srs->ipa_ws[j].reset(new IpaWorkspace); srs->ipa_ws[j]->index = j; }
+        wsp = srs->ipa_ws[j].get();
+        wsp->live = true; wsp->owner = me;
     }
+    IpaWorkspace& ws = *wsp;
     struct Claim {
-        kh_srs_t* s; bool keep = false;
-        ~Claim() { if (!keep) { { std::lock_guard<std::mutex> hl(s->ipa_mu); s->ipa_live = false; } s->ipa_cv.notify_all(); } }
-    } claim{srs};
+        kh_srs_t* s; IpaWorkspace* w; bool keep = false;
+        ~Claim() { if (!keep) { { std::lock_guard<std::mutex> hl(s->ipa_mu); w->live = false; } s->ipa_cv.notify_all(); } }
+    } claim{srs, wsp};
     Context& C = ctx();
     std::unique_lock<std::mutex> lk(C.mu);
     const auto b1_ = std::chrono::steady_clock::now();
     std::unique_ptr<kh_ipa> st(new kh_ipa);
-    st->srs = srs; st->curve = srs->curve; st->field = khost::scalar_field_id(srs->curve); st->n = n; st->cur = n;
+    st->srs = srs; st->ws = wsp; st->curve = srs->curve; st->field = khost::scalar_field_id(srs->curve); st->n = n; st->cur = n;
     for (int i = 0; i < 2; i++) {
-        if ((rc = srs->ipa_a[i].reserve(n * 32))) return rc;
-        if ((rc = srs->ipa_b[i].reserve(n * 32))) return rc;
-        if ((rc = srs->ipa_coef[i].reserve(n * 32))) return rc;
+        if ((rc = ws.a[i].reserve(n * 32))) return rc;
+        if ((rc = ws.b[i].reserve(n * 32))) return rc;
+        if ((rc = ws.coef[i].reserve(n * 32))) return rc;
     }
-    if ((rc = srs->ipa_sc.reserve(2 * (n + 2) * 32))) return rc;
-    if ((rc = srs->ipa_sg.reserve(2 * n * 32))) return rc;             // scalars of the two halves of sg (kh_ipa_open)
+    if ((rc = ws.sc.reserve(2 * srs->g_stride * 32))) return rc;       // two scalar vectors over the handle's tables: the points, H, every workspace's U
+    if ((rc = ws.sg.reserve(2 * n * 32))) return rc;                   // scalars of the two halves of sg (kh_ipa_open)
     const size_t partial_bytes = 2 * (n / 512 + 1) * 32;               // block sums of the two inner products, then the last-block counter
-    if ((rc = srs->ipa_partial.reserve(partial_bytes + 64))) return rc;
-    KH_HIP(hipMemsetAsync((uint8_t*)srs->ipa_partial.p + partial_bytes, 0, 64, C.stream));
-    if (!srs->ipa_ev) KH_HIP(hipEventCreateWithFlags(&srs->ipa_ev, hipEventDisableTiming));
-    st->a = srs->ipa_a; st->b = srs->ipa_b; st->coef = srs->ipa_coef; st->sc = &srs->ipa_sc; st->partial = &srs->ipa_partial; st->ev = srs->ipa_ev; st->partial_words = partial_bytes / 8;
-    // H and U into the two extra slots of every window table of the SRS (the rounds run over them until the rebase switches)
+    if ((rc = ws.partial.reserve(partial_bytes + 64))) return rc;
+    KH_HIP(hipMemsetAsync((uint8_t*)ws.partial.p + partial_bytes, 0, 64, C.stream));
+    // the scalars of the OTHER workspaces' U slots are zero: a zero digit makes no entry in the MSM's sort, so a slot another opening is rewriting is never
+    // fetched.  The step kernel writes only H's and this opening's entries; the rest is zeroed here (a reused buffer may hold a rebased round's scalars).
+    for (int side = 0; side < 2; side++)
+        KH_HIP(hipMemsetAsync(ws.sc.as<uint8_t>() + ((size_t)side * srs->g_stride + n) * 32, 0, (srs->g_stride - n) * 32, C.stream));
+    if (!ws.ev) KH_HIP(hipEventCreateWithFlags(&ws.ev, hipEventDisableTiming));
+    st->a = ws.a; st->b = ws.b; st->coef = ws.coef; st->sc = &ws.sc; st->partial = &ws.partial; st->ev = ws.ev; st->partial_words = partial_bytes / 8;
+    st->extra = (unsigned)(srs->g_stride - n); st->uslot = (unsigned)ws.index;
+    // U into this workspace's slot of every window table of the SRS, H into its slot if it is not there yet (the rounds run over them until the rebase switches)
     const int rc_c = srs->g_precomp_c;                                             // window width of the rounds' tables
     void* const round_tab = srs->g.p;
-    std::vector<uint64_t>& hm = srs->h_multiples;
     st->round_tab = round_tab; st->round_c = rc_c; st->tab_stride = srs->g_stride;
     memcpy(st->u_xy, u_base_xy, 64);
     // Plan the rebase (csrc/rebase.hip): the folded basis of N = 2^KH_IPA_REBASE_LOGN points (default 2^11; at least three rounds folded into it, at least 64
@@ -317,36 +342,42 @@ static int ipa_begin_common(kh_srs_t* srs, const uint64_t* a, size_t a_len, cons
             }
             st->rb_glv = glv_ok;
             const int W2 = std::max(windows_of(rb_c), 2 * ((128 + rb_c - 1) / rb_c));
-            bool ok = srs->ipa_rb_tab.reserve((N + 2) * 64 * (size_t)W2) == KH_OK && srs->ipa_rb_B.reserve(rebase_bucket_bytes(N)) == KH_OK &&
-                      srs->ipa_rb_part.reserve(rebase_part_bytes(N)) == KH_OK && srs->ipa_rb_lists.reserve(rebase_list_bytes(Q) + 256) == KH_OK &&       // (+ H | U, affine)
-                      srs->ipa_rb_scratch.reserve((size_t)W2 * (N + 2) * 128) == KH_OK;
-            if (ok && !srs->ipa_rb_stream) {
+            bool ok = ws.rb_tab.reserve((N + 2) * 64 * (size_t)W2) == KH_OK && ws.rb_B.reserve(rebase_bucket_bytes(N)) == KH_OK &&
+                      ws.rb_part.reserve(rebase_part_bytes(N)) == KH_OK && ws.rb_lists.reserve(rebase_list_bytes(Q) + 256) == KH_OK &&       // (+ H | U, affine)
+                      ws.rb_scratch.reserve((size_t)W2 * (N + 2) * 128) == KH_OK;
+            if (ok && !ws.rb_stream) {
                 int lo = 0, hi = 0;
                 (void)hipDeviceGetStreamPriorityRange(&lo, &hi);                 // lo = the numerically largest = the LEAST urgent
-                ok = hipStreamCreateWithPriority(&srs->ipa_rb_stream, hipStreamNonBlocking, lo) == hipSuccess &&
-                     hipEventCreateWithFlags(&srs->ipa_rb_go, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&srs->ipa_rb_snap, hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&srs->ipa_rb_done, hipEventDisableTiming) == hipSuccess &&
-                     hipHostMalloc((void**)&srs->ipa_rb_fail, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+                ok = hipStreamCreateWithPriority(&ws.rb_stream, hipStreamNonBlocking, lo) == hipSuccess &&
+                     hipEventCreateWithFlags(&ws.rb_go, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&ws.rb_snap, hipEventDisableTiming) == hipSuccess &&
+                     hipEventCreateWithFlags(&ws.rb_done, hipEventDisableTiming) == hipSuccess &&
+                     hipHostMalloc((void**)&ws.rb_fail, 64, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
             }
-            if (ok) { *srs->ipa_rb_fail = 0; st->rb_state = 1; st->rb_j0 = logn - ln; st->rb_N = N; st->rb_c = rb_c; }
+            if (ok) { *ws.rb_fail = 0; st->rb_state = 1; st->rb_j0 = logn - ln; st->rb_N = N; st->rb_c = rb_c; }
             else { (void)hipGetLastError(); set_error(""); }                     // no memory for it: the rounds stay on the original tables
         }
     }
     const int W = rc_c ? windows_of(rc_c) : 1;
     std::vector<uint64_t>& tab = st->tab;                  // lives as long as the opening: no synchronisation before returning
-    std::vector<uint64_t> col((size_t)W * 8);
-    tab.resize((size_t)W * 16);
-    if (hm.size() != (size_t)W * 8) {                      // H is the SRS's: its window multiples are computed once
-        hm.resize((size_t)W * 8);
-        host_window_multiples(srs->curve, srs->h, W, rc_c, hm.data());
-    }
-    for (int w = 0; w < W; w++) memcpy(&tab[16 * w], &hm[8 * w], 64);
-    const auto b2_ = std::chrono::steady_clock::now();
-    host_window_multiples(srs->curve, u_base_xy, W, rc_c, col.data());
-    const auto b3_ = std::chrono::steady_clock::now();
-    for (int w = 0; w < W; w++) memcpy(&tab[16 * w + 8], &col[8 * w], 64);
+    tab.resize((size_t)W * 8);
     hipStream_t s = C.stream;
-    KH_HIP(hipMemcpy2DAsync((char*)round_tab + n * 64, srs->g_stride * 64, tab.data(), 128, 128, W, hipMemcpyHostToDevice, s));
+    {
+        // H is the SRS's: its window multiples are computed and written into slot n once per handle (and again after kh_srs_set_blinding_base, which no
+        // live opening allows).  Openings of other contexts read the slot through streams of their own, so the one upload is complete before h_mu is let go.
+        std::lock_guard<std::mutex> hk(srs->h_mu);
+        std::vector<uint64_t>& hm = srs->h_multiples;
+        if (hm.size() != (size_t)W * 8 || !srs->h_in_tables) {
+            hm.resize((size_t)W * 8);
+            host_window_multiples(srs->curve, srs->h, W, rc_c, hm.data());
+            KH_HIP(hipMemcpy2DAsync((char*)round_tab + n * 64, srs->g_stride * 64, hm.data(), 64, 64, W, hipMemcpyHostToDevice, s));
+            KH_HIP(hipStreamSynchronize(s));
+            srs->h_in_tables = true;
+        }
+    }
+    const auto b2_ = std::chrono::steady_clock::now();
+    host_window_multiples(srs->curve, u_base_xy, W, rc_c, tab.data());
+    const auto b3_ = std::chrono::steady_clock::now();
+    KH_HIP(hipMemcpy2DAsync((char*)round_tab + (n + 1 + st->uslot) * 64, srs->g_stride * 64, tab.data(), 64, 64, W, hipMemcpyHostToDevice, s));
     if (a_len < n) KH_HIP(hipMemsetAsync((char*)st->a[0].p + a_len * 32, 0, (n - a_len) * 32, s));
     KH_HIP(hipMemcpyAsync(st->a[0].p, a, a_len * 32, kind, s));
     KH_HIP(hipMemcpyAsync(st->b[0].p, b, n * 32, kind, s));
@@ -385,10 +416,10 @@ static void ipa_sg_prelaunch_locked(kh_ipa_t* st, Context& C, int p, bool had_fo
     MsmSlot& S = C.slot[si];
     kh_srs_t* srs = st->srs;
     if (hipStreamWaitEvent(S.stream, st->ev, 0) != hipSuccess) return;
-    if (ipa_sg_split(S.stream, st->field, st->coef[p].as<uint64_t>(), st->n, had_fold ? 1 : 0, st->u_p, srs->ipa_sg.as<uint64_t>())) return;
+    if (ipa_sg_split(S.stream, st->field, st->coef[p].as<uint64_t>(), st->n, had_fold ? 1 : 0, st->u_p, st->ws->sg.as<uint64_t>())) return;
     MsmBasis bs; bs.pts = srs->g.p; bs.inf = nullptr; bs.n = srs->n; bs.stride = srs->g_stride; bs.precomp_c = srs->g_precomp_c;
     if (st->rb_state == 3) { bs.pts = st->round_tab; bs.n = st->n; bs.stride = st->tab_stride; bs.precomp_c = st->round_c; bs.glv = st->rb_glv; }     // sg = <coef_rel, g'>
-    if (msm_enqueue(C, S, st->curve, bs, 0, srs->ipa_sg.as<uint64_t>(), st->n, 2, 1)) return;
+    if (msm_enqueue(C, S, st->curve, bs, 0, st->ws->sg.as<uint64_t>(), st->n, 2, 1)) return;
     st->sg_slot = si;
 }
 // KH_IPA_TIMING: where a round's host time goes (accumulated per thread, printed and reset by kh_ipa_open)
@@ -409,25 +440,27 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
     MsmSlot& S = C.slot[si];
     KH_HIP(hipStreamWaitEvent(S.stream, st->ev, 0));
     kh_srs_t* const srs = st->srs;
+    IpaWorkspace& ws = *st->ws;
     st->round_no++;
     // the rebase (csrc/rebase.hip): switch to the materialised folded basis as soon as its tables are complete
     if (st->rb_state == 2) {
         static const bool rb_wait = env_flag("KH_IPA_REBASE_WAIT", false);      // tests: the earliest possible switch, deterministically
-        if (rb_wait) KH_HIP(hipEventSynchronize(srs->ipa_rb_done));
-        const hipError_t qe = hipEventQuery(srs->ipa_rb_done);
+        if (rb_wait) KH_HIP(hipEventSynchronize(ws.rb_done));
+        const hipError_t qe = hipEventQuery(ws.rb_done);
         if (qe == hipSuccess) {
-            if (__atomic_load_n(srs->ipa_rb_fail, __ATOMIC_ACQUIRE) != 0) { st->rb_state = -1; counter(CNT_REBASE_ABANDON)++; }
+            if (__atomic_load_n(ws.rb_fail, __ATOMIC_ACQUIRE) != 0) { st->rb_state = -1; counter(CNT_REBASE_ABANDON)++; }
             else {
-                KH_HIP(hipStreamWaitEvent(S.stream, srs->ipa_rb_done, 0));
+                KH_HIP(hipStreamWaitEvent(S.stream, ws.rb_done, 0));
                 st->n = st->rb_N; st->ncoef >>= st->rb_j0;
-                st->round_tab = srs->ipa_rb_tab.p; st->round_c = st->rb_c; st->tab_stride = st->rb_N + 2;
+                st->round_tab = ws.rb_tab.p; st->round_c = st->rb_c; st->tab_stride = st->rb_N + 2;
+                st->extra = 2; st->uslot = 0;              // the rebased tables are this opening's own: the folded basis, H, U
                 st->rb_state = 3; counter(CNT_REBASE_SWITCH)++;
                 if (ipa_timing()) fprintf(stderr, "kh_ipa: round %u runs over the rebased tables (%zu points, c = %d, %u rounds folded in)\n", st->round_no, st->rb_N, st->rb_c, st->rb_j0);
             }
         } else if (qe != hipErrorNotReady) { KH_HIP(qe); }
         else (void)hipGetLastError();
         // the step kernel of round j0 + 3 is the first to overwrite the challenge tensor the plan kernel reads (ping-pong buffers): order it behind the plan
-        if (st->rb_state == 2 && st->round_no == st->rb_j0 + 3) KH_HIP(hipStreamWaitEvent(S.stream, srs->ipa_rb_snap, 0));
+        if (st->rb_state == 2 && st->round_no == st->rb_j0 + 3) KH_HIP(hipStreamWaitEvent(S.stream, ws.rb_snap, 0));
     }
     if (st->rb_state == 3) counter(CNT_REBASED_ROUNDS)++;
     const int p = st->pp, q = p ^ 1;
@@ -438,7 +471,7 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
     int rc = ipa_round_step(S.stream, st->field, st->pending ? 1 : 0, st->a[p].as<uint64_t>(), st->b[p].as<uint64_t>(), st->coef[p].as<uint64_t>(),
                             st->n, st->cur, st->pending ? st->ncoef / 2 : st->ncoef, st->u_p, st->ui_p,
                             st->a[q].as<uint64_t>(), st->b[q].as<uint64_t>(), st->coef[q].as<uint64_t>(), rand_l, rand_r,
-                            st->sc->as<uint64_t>(), st->partial->as<uint64_t>(), (unsigned*)(st->partial->as<uint64_t>() + st->partial_words));
+                            st->sc->as<uint64_t>(), st->partial->as<uint64_t>(), (unsigned*)(st->partial->as<uint64_t>() + st->partial_words), st->extra, st->uslot);
     if (rc) return rc;
     const auto pt2 = std::chrono::steady_clock::now();
     if (st->pending) { st->pp = q; st->pending = false; }
@@ -446,15 +479,15 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
         // this round's step kernel has just written the tensor of the first j0 challenges (2^j0 entries, st->coef[st->pp]): materialise the folded basis
         // and its window tables behind it on the side stream, H and U in the two extra slots
         const size_t N = st->rb_N, Q = (size_t)1 << st->rb_j0;
-        hipStream_t rs = srs->ipa_rb_stream;
-        bool ok = hipEventRecord(srs->ipa_rb_go, S.stream) == hipSuccess && hipStreamWaitEvent(rs, srs->ipa_rb_go, 0) == hipSuccess;
-        uint32_t* const lists = srs->ipa_rb_lists.as<uint32_t>();
-        if (ok) ok = rebase_points(rs, st->curve, st->coef[st->pp].as<uint64_t>(), Q, srs->g.p, srs->g_stride, N, srs->ipa_rb_B.p, srs->ipa_rb_part.p, lists,
-                                   srs->ipa_rb_snap) == KH_OK;                   // (ipa_rb_snap: behind the plan kernel, the tensor's only reader)
+        hipStream_t rs = ws.rb_stream;
+        bool ok = hipEventRecord(ws.rb_go, S.stream) == hipSuccess && hipStreamWaitEvent(rs, ws.rb_go, 0) == hipSuccess;
+        uint32_t* const lists = ws.rb_lists.as<uint32_t>();
+        if (ok) ok = rebase_points(rs, st->curve, st->coef[st->pp].as<uint64_t>(), Q, srs->g.p, srs->g_stride, N, ws.rb_B.p, ws.rb_part.p, lists,
+                                   ws.rb_snap) == KH_OK;                   // (rb_snap: behind the plan kernel, the tensor's only reader)
         memcpy(st->hu_stage, srs->h, 64); memcpy(st->hu_stage + 8, st->u_xy, 64);       // (H | U travel in the table kernel's arguments: rebase.hip, RbExtra)
-        if (ok) ok = rebase_tables(rs, st->curve, srs->ipa_rb_part.p, N, st->hu_stage, 2, st->rb_c, srs->ipa_rb_scratch.p, srs->ipa_rb_tab.p, srs->ipa_rb_fail,
+        if (ok) ok = rebase_tables(rs, st->curve, ws.rb_part.p, N, st->hu_stage, 2, st->rb_c, ws.rb_scratch.p, ws.rb_tab.p, ws.rb_fail,
                                    st->rb_glv ? cached_endos(st->curve).q : nullptr) == KH_OK;
-        if (ok) ok = hipEventRecord(srs->ipa_rb_done, rs) == hipSuccess;
+        if (ok) ok = hipEventRecord(ws.rb_done, rs) == hipSuccess;
         if (ok) { st->rb_state = 2; counter(CNT_REBASE_LAUNCH)++; }
         else { (void)hipGetLastError(); (void)hipStreamSynchronize(rs); st->rb_state = -1; counter(CNT_REBASE_ABANDON)++; }
     }
@@ -462,7 +495,7 @@ int kh_ipa_round_lr(kh_ipa_t* st, const uint64_t rand_l[4], const uint64_t rand_
     // The round's MSM is six launches (digits, one-launch sort, accumulation, bucket sums, two reduction kernels) which the host queues in ~25 us while
     // the step kernel runs.  Its scalars are products with Fiat-Shamir challenges (MSM_SPREAD_SCALARS) until a round of this opening proves otherwise.
     const int round_flags = (st->spread_broken ? 0 : MSM_SPREAD_SCALARS) | MSM_LATENCY;
-    if ((rc = msm_enqueue(C, S, st->curve, bs, 0, st->sc->as<uint64_t>(), st->n + 2, 2, 1, round_flags))) return rc;
+    if ((rc = msm_enqueue(C, S, st->curve, bs, 0, st->sc->as<uint64_t>(), st->tab_stride, 2, 1, round_flags))) return rc;
     if (st->sg_want && st->cur == 2) { st->sg_want = false; ipa_sg_prelaunch_locked(st, C, p, had_fold); }
     const auto pt3 = std::chrono::steady_clock::now();
     if ((rc = wait_then_finish(lk, C, S, lr_xy, lr_inf))) return rc;
@@ -595,10 +628,11 @@ void kh_ipa_free(kh_ipa_t* st) {
     std::lock_guard<std::mutex> lk(C.mu);
     (void)hipStreamSynchronize(C.stream);                 // a fold may still be in flight on the library stream
     kh_srs_t* const srs = st->srs;
-    if (srs && st->rb_state >= 2 && srs->ipa_rb_stream) (void)hipStreamSynchronize(srs->ipa_rb_stream);      // a materialisation that was never switched to: the handle's next opening reuses its buffers
+    IpaWorkspace* const ws = st->ws;
+    if (ws && st->rb_state >= 2 && ws->rb_stream) (void)hipStreamSynchronize(ws->rb_stream);      // a materialisation that was never switched to: the workspace's next opening reuses its buffers
     delete st;
-    if (srs) {                                            // an opening another thread wants to begin on this handle can start
-        { std::lock_guard<std::mutex> hl(srs->ipa_mu); srs->ipa_live = false; }
+    if (srs && ws) {                                      // the workspace is free again: an opening waiting for one on this handle can start
+        { std::lock_guard<std::mutex> hl(srs->ipa_mu); ws->live = false; }
         srs->ipa_cv.notify_all();
     }
     C.cv.notify_all();

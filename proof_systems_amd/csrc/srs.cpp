@@ -43,7 +43,7 @@ void kh::xyzz_to_affine_batch(const khost::Crv& crv, const std::vector<khost::xy
     }
 }
 
-// the wide-window table set of a big basis (table 0 = a copy of the basis; H / U slots unused).  It is a throughput optimisation on top of the narrow tables
+// the wide-window table set of a big basis (table 0 = a copy of the basis; the slots of H and U unused).  It is a throughput optimisation on top of the narrow tables
 // (+13/16 of their memory: 832 MiB at 2^20 points, 3.3 GiB at 2^22), so a handle whose second set does not fit is still a working handle: `required` = false
 // gives the memory back, clears the error and leaves the narrow tables to serve every MSM.
 static int build_wide_tables(Context& C, kh_srs* s, bool required) {
@@ -66,7 +66,7 @@ static int build_wide_tables(Context& C, kh_srs* s, bool required) {
     s->g_wide_c = MSM_WIDE_C;
     return KH_OK;
 }
-// The narrow window tables of a point buffer of `stride` points per table (the basis of n points and, for an SRS, the two extra slots).
+// The narrow window tables of a point buffer of `stride` points per table (the basis of n points and, for an SRS, the slots of H and U).
 // table_width: the window width a basis of n points gets; 0 = none, smaller bases keep the plain per-window path.  table_bytes: what the buffer must
 // hold before its table 0 is filled.
 static int table_width(size_t n) { return n >= MSM_PRECOMP_MIN_N ? MSM_PRECOMP_C : 0; }
@@ -87,11 +87,11 @@ static int srs_create(int curve, size_t n, kh_srs_t** out, Fill fill) {
     Context& C = ctx();
     s->device = C.device;
     std::lock_guard<std::mutex> lk(C.mu);
-    s->g_stride = n + 2;
+    s->g_stride = n + 1 + KH_IPA_OPENINGS;              // behind the basis: H, then one slot of U per opening workspace (kh_ipa_begin)
     if ((rc = s->g.reserve(table_bytes(n, s->g_stride)))) return rc;
     if ((rc = fill(C, s->g.p))) return rc;
-    KH_HIP(hipMemcpyAsync((char*)s->g.p + n * 64, s->g.p, 64, hipMemcpyDeviceToDevice, C.stream));          // placeholders: valid points
-    KH_HIP(hipMemcpyAsync((char*)s->g.p + (n + 1) * 64, s->g.p, 64, hipMemcpyDeviceToDevice, C.stream));
+    for (size_t i = n; i < s->g_stride; i++)            // placeholders: valid points
+        KH_HIP(hipMemcpyAsync((char*)s->g.p + i * 64, s->g.p, 64, hipMemcpyDeviceToDevice, C.stream));
     if ((rc = build_tables(C, curve, s->g.p, nullptr, n, s->g_stride, &s->g_precomp_c))) return rc;
     if ((rc = build_wide_tables(C, s.get(), false))) return rc;
     // tables are per HANDLE, streams per context: another context (kh_private_context_begin on another thread) may use the handle at once, so it is
@@ -113,14 +113,23 @@ int kh_srs_set_wide_tables(kh_srs_t* srs, int on) {
     std::lock_guard<std::mutex> lk(C.mu);
     if (on) {
         KH_REQUIRE(srs->g_precomp_c, "kh_srs_set_wide_tables: the handle has no window tables (fewer than %d points)", (int)MSM_PRECOMP_MIN_N);
+        // another context may resolve the handle's basis at any time (msm_api.cpp: resolve_counted, under wide_mu): the set is built aside and published --
+        // g_wide_c -- only when it is complete on the device
+        std::lock_guard<std::mutex> wl(srs->wide_mu);
+        if (srs->g_wide_c) return KH_OK;
         if ((rc = build_wide_tables(C, srs, true))) return rc;
-        KH_HIP(hipStreamSynchronize(C.stream));
+        const int built = srs->g_wide_c;
+        srs->g_wide_c = 0;
+        const hipError_t e = hipStreamSynchronize(C.stream);
+        if (e != hipSuccess) { srs->g_wide.release(); KH_HIP(e); }
+        srs->g_wide_c = built;
         return KH_OK;
     }
-    for (int i = 0; i < MSM_SLOTS; i++) {
-        KH_REQUIRE(!C.slot[i].busy, "kh_srs_set_wide_tables: an MSM is in flight (kh_msm_wait first)");
-        if (C.slot[i].stream) KH_HIP(hipStreamSynchronize(C.slot[i].stream));
-    }
+    // the handle is shared between contexts: what counts is the handle's own tally of jobs in flight (kh_srs::jobs), not the calling context's slots.  A job
+    // that was counted has finished on the device by the time it is counted out (wait_then_finish waited for its event), so nothing is left to wait for --
+    // except a job whose wait itself failed (a device error: it is counted out without having been seen to end; every later call on that device fails too).
+    std::lock_guard<std::mutex> wl(srs->wide_mu);
+    KH_REQUIRE(srs->jobs->load() == 0, "kh_srs_set_wide_tables: an MSM is in flight (kh_msm_wait first)");
     srs->g_wide_c = 0;
     srs->g_wide.release();
     return KH_OK;
@@ -245,9 +254,14 @@ int kh_srs_get_lagrange(kh_srs_t* srs, unsigned log2_domain, unsigned chunk, uin
 
 int kh_srs_set_blinding_base(kh_srs_t* srs, const uint64_t h_xy[8]) {
     KH_REQUIRE(srs && h_xy, "null argument");
+    // the rounds of a live opening read H from the handle's tables: no opening may be live, and none may begin before the new H is in place (ipa_mu is held
+    // throughout; kh_ipa_begin takes h_mu only after it has let go of ipa_mu)
+    std::lock_guard<std::mutex> il(srs->ipa_mu);
+    for (auto& w : srs->ipa_ws)
+        KH_REQUIRE(!(w && w->live), "kh_srs_set_blinding_base: an opening is in progress on this SRS (kh_ipa_free it first)");
     std::lock_guard<std::mutex> lk(srs->h_mu);
     memcpy(srs->h, h_xy, 64);
-    srs->h_table.clear(); srs->h_multiples.clear();
+    srs->h_table.clear(); srs->h_multiples.clear(); srs->h_in_tables = false;      // the next opening writes the new H into the tables
     return KH_OK;
 }
 int kh_srs_get_blinding_base(const kh_srs_t* srs, uint64_t h_xy[8]) {
