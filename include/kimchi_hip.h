@@ -277,6 +277,44 @@ int kh_gate_constants(int field, int gate, const uint64_t alpha[4], const uint64
 int kh_gate_evaluations_dev(int field, int gate, const uint64_t *const *cols_dev, size_t col_len, const uint64_t *constants, size_t nconsts,
                             size_t rows, unsigned stride, unsigned next_shift, int accumulate, uint64_t *out_dev);
 
+/* ---- Poseidon on the device (csrc/poseidon.hip) ----
+ * Kimchi Poseidon (PlonkSpongeConstantsKimchi, poseidon/src/constants.rs:29-41: width 3, rate 2, 55 full rounds of x^7, the 3 x 3 MDS, + round constants,
+ * no initial round-constant addition; poseidon/src/permutation.rs full_round) as a batch operation: many permutations, many sponge hashes, and the witness
+ * rows of the Poseidon gadget (11 gate rows + the output row) written straight into the witness_dev columns kh_witness_check and kh_prove consume -- so
+ * that a circuit made of Poseidon gadgets needs neither a host pass over its rows nor their transfer.  One lane per permutation (three for small batches
+ * of gadget rows, kh_poseidon_set_split_max_n); every value is the canonical Montgomery element the reference computes, bit for bit.  Inputs are canonical Montgomery elements (< p); they are not checked.
+ * The three *_dev calls are vector steps like the ones above: queued on the main stream of the calling thread's current context (the private one between
+ * kh_private_context_begin and _end), they return when queued and are ordered against every other call of the library -- a producer followed by a consumer
+ * needs no kh_sync.  n == 0 is KH_OK with nothing launched.  KH_E_INVALID with a kh_last_error text, before anything is launched and with nothing written:
+ * an unknown field, a null pointer with n > 0, a device pointer that is not 16-byte aligned, sizes whose byte counts overflow, and for
+ * kh_poseidon_gate_witness_dev an instance that does not fit (rows[i] + 12 > col_len, naming i; rows == NULL with row_stride < 12 or
+ * row0 + (n - 1) row_stride + 12 > col_len) or col_stride < col_len.  Instances that overlap in `rows` are the caller's responsibility: they are not
+ * checked, and which instance's values the shared cells end up with is undefined. */
+/* host only, no device: the 11 coefficient rows of a Poseidon gadget, out[(15 r + c)] = round constant (5 r + c / 3)[c % 3]
+ * (poseidon.rs:239-290), 11 x 15 x 4 Montgomery limbs -- what a gate list for kh_prover_index_create carries on its Poseidon rows */
+int kh_poseidon_gate_coefficients(int field, uint64_t *out);
+
+/* n permutations in place: states_dev = n x 3 x 4 limbs */
+int kh_poseidon_permute_dev(int field, uint64_t *states_dev, size_t n);
+
+/* n sponge hashes of msg_len elements each (msgs_dev: n x msg_len x 4 limbs, message after message): state = init (3 elements on the
+ * host, NULL = zero), absorb the message, squeeze once (poseidon/src/poseidon.rs:60-175) -> digests_dev: n x 4 limbs.
+ * msg_len == 0 is allowed (msgs_dev may be NULL): max(1, ceil(msg_len / 2)) permutations per hash */
+int kh_poseidon_hash_dev(int field, const uint64_t *msgs_dev, size_t msg_len, size_t n, const uint64_t *init, uint64_t *digests_dev);
+
+/* The witness of n Poseidon gadgets (kimchi/src/circuits/polynomials/poseidon.rs:239-290, state order :65-80): instance i starts at row
+ * rows[i] (host array, copied before the call returns), or at row0 + i * row_stride when rows == NULL (row_stride >= 12).
+ * witness_dev: 15 columns, column c at witness_dev + 4 * c * col_stride, col_len rows each -- the layout kh_prove / kh_witness_check take
+ * with col_stride = n.  Written per instance: all 15 cells of rows r .. r + 10 (round 5 j + t of row r + j in columns
+ * 3 * {0, 2, 3, 4, 1}[t] + k) and cells 0..2 of row r + 11 (the final state).  NOTHING else is written.
+ * out_states_dev (nullable; may equal states_dev): the n final states. */
+int kh_poseidon_gate_witness_dev(int field, const uint64_t *states_dev, size_t n, const uint32_t *rows, size_t row0, size_t row_stride,
+                                 uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_states_dev);
+/* Tuning knob (process-wide): kh_poseidon_gate_witness_dev spreads a permutation over three lanes (7 products in sequence per round instead of 21, three
+ * times the waves) for up to n instances, and takes one lane per permutation above; default 43008 (two three-lane waves per SIMD), 0 = never.  The same
+ * values are written either way; the tests set it to run both kernels at small sizes. */
+int kh_poseidon_set_split_max_n(size_t n);
+
 /* ---- scans, batch inversion, division by a linear factor: the permutation argument's vector steps ----
  * kh_field_scan_dev: in-place inclusive prefix (reverse = 0) or suffix (reverse = 1) scan under + or *
  *   (the running product z[j+1] = z[j] * ..., kimchi/src/circuits/polynomials/permutation.rs:556-563).

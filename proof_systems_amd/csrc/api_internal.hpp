@@ -84,4 +84,11 @@ int wait_then_finish(std::unique_lock<std::mutex>& lk, Context& C, MsmSlot& S, u
 double last_wait_us();           // spin / block part of the last wait_then_finish on this thread
 // vector_api.cpp
 void xfer_trim(int d);
+// poseidon.hip: the launchers of kh_poseidon_*_dev, queued on C.stream (arguments validated by the entry points; n >= 1)
+static constexpr size_t POSEIDON_MAX_N = (size_t)1 << 36;      // one-wave blocks: the grid stays inside 31 bits
+int poseidon_permute(Context& C, int field, uint64_t* states_dev, size_t n);
+int poseidon_hash(Context& C, int field, const uint64_t* msgs_dev, size_t msg_len, size_t n, const uint64_t* init, uint64_t* digests_dev);
+int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride,
+                       uint64_t* witness_dev, size_t col_stride, uint64_t* out_states_dev);
+void poseidon_set_split_max_n(size_t n);
 }  // namespace kh

@@ -1,10 +1,14 @@
-// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
 #include <stdlib.h>
 
 #include "api_internal.hpp"
 #include "env.hpp"
 
 using namespace kh;
+
+namespace {
+#include "poseidon_params.inc"      // the round constants kh_poseidon_gate_coefficients hands out (the host sponge and the device kernels have the same table)
+}
 
 // transfer buffers of the host-pointer transforms (kh_ntt / kh_lde: host_transform below)
 struct XferPair { DevBuf in, out; bool busy = false, owned = false; };
@@ -237,6 +241,78 @@ int kh_gate_evaluations_dev(int field, int gate, const uint64_t* const* cols_dev
     if (rc == KH_OK) C.mark_async();
     return rc;
 }
+
+// ---------------------------------------------------------------------------------- Poseidon on the device (kernels in poseidon.hip)
+int kh_poseidon_gate_coefficients(int field, uint64_t* out) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(out, "kh_poseidon_gate_coefficients: null output");
+    const khost::fe (*rc)[3] = field == KH_FIELD_FP ? POSEIDON_RC_FP : POSEIDON_RC_FQ;
+    for (size_t r = 0; r < 11; r++)
+        for (size_t c = 0; c < 15; c++) memcpy(out + 4 * (15 * r + c), &rc[5 * r + c / 3][c % 3], 32);
+    return KH_OK;
+}
+#define KH_POSEIDON_ALIGNED(p) ((((uintptr_t)(p)) & 15) == 0)
+int kh_poseidon_permute_dev(int field, uint64_t* states_dev, size_t n) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(states_dev || n == 0, "kh_poseidon_permute_dev: null states");
+    KH_REQUIRE(KH_POSEIDON_ALIGNED(states_dev), "kh_poseidon_permute_dev: states_dev must be 16-byte aligned");
+    KH_REQUIRE(n <= POSEIDON_MAX_N, "kh_poseidon_permute_dev: %zu states are more than the %zu one call takes", n, POSEIDON_MAX_N);
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poseidon_permute(C, field, states_dev, n);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_poseidon_hash_dev(int field, const uint64_t* msgs_dev, size_t msg_len, size_t n, const uint64_t* init, uint64_t* digests_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(n == 0 || (digests_dev && (msgs_dev || msg_len == 0)), "kh_poseidon_hash_dev: null %s", digests_dev ? "messages" : "digests");
+    KH_REQUIRE(KH_POSEIDON_ALIGNED(msgs_dev) && KH_POSEIDON_ALIGNED(digests_dev), "kh_poseidon_hash_dev: msgs_dev and digests_dev must be 16-byte aligned");
+    KH_REQUIRE(n <= POSEIDON_MAX_N && (msg_len == 0 || n <= (SIZE_MAX / 32) / msg_len),
+               "kh_poseidon_hash_dev: %zu messages of %zu elements overflow the byte count", n, msg_len);
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = poseidon_hash(C, field, msgs_dev, msg_len, n, init, digests_dev);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_states_dev) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    KH_REQUIRE(n == 0 || (states_dev && witness_dev), "kh_poseidon_gate_witness_dev: null %s", states_dev ? "witness" : "states");
+    KH_REQUIRE(KH_POSEIDON_ALIGNED(states_dev) && KH_POSEIDON_ALIGNED(witness_dev) && KH_POSEIDON_ALIGNED(out_states_dev),
+               "kh_poseidon_gate_witness_dev: states_dev, witness_dev and out_states_dev must be 16-byte aligned");
+    KH_REQUIRE(col_stride >= col_len, "kh_poseidon_gate_witness_dev: col_stride %zu is less than col_len %zu", col_stride, col_len);
+    KH_REQUIRE(n <= POSEIDON_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "kh_poseidon_gate_witness_dev: %zu instances in columns %zu elements apart overflow the byte count",
+               n, col_stride);
+    if (n > 0 && rows) {
+        for (size_t i = 0; i < n; i++)
+            KH_REQUIRE(col_len >= 12 && rows[i] <= col_len - 12, "kh_poseidon_gate_witness_dev: instance %zu at row %u does not fit %zu rows (12 rows each)", i, rows[i], col_len);
+    } else if (n > 0) {
+        KH_REQUIRE(row_stride >= 12, "kh_poseidon_gate_witness_dev: row_stride %zu is less than the 12 rows of an instance", row_stride);
+        KH_REQUIRE(col_len >= 12 && row0 <= col_len - 12 && (n - 1) <= (col_len - 12 - row0) / row_stride,
+                   "kh_poseidon_gate_witness_dev: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", n, row0, row_stride, col_len);
+    }
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    // the start rows travel through the pinned staging ring into a block of the kh_dev_alloc pool (taken before the context's lock, like
+    // kh_lookup_sorted_dev's scratch), in pieces that leave the ring its size: the caller's array is not read after this returns
+    struct Scratch { uint32_t* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } rows_dev;
+    if (rows && (rc = kh_dev_alloc((void**)&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    const size_t piece = (size_t)1 << 15;
+    for (size_t i = 0; rows && i < n; i += piece)
+        if ((rc = C.stage_upload(rows_dev.p + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}}))) return rc;
+    rc = poseidon_gate_rows(C, field, states_dev, n, rows_dev.p, row0, row_stride, witness_dev, col_stride, out_states_dev);
+    C.mark_async();
+    return rc;
+}
+#undef KH_POSEIDON_ALIGNED
+int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return KH_OK; }
 
 // ---------------------------------------------------------------------------------- NTT
 int kh_domain_generator(int field, unsigned log2_n, uint64_t out[4]) {

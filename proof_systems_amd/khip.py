@@ -683,6 +683,40 @@ def lookup_sorted_dev(table, lookup_rows: int, values, value_stride: int, max_pe
     _check(rc)
 
 
+def poseidon_gate_coefficients(field: int):
+    """kh_poseidon_gate_coefficients: the (11, 15, 4) coefficient rows of a Poseidon gadget (host only)."""
+    out = np.zeros((11, 15, 4), dtype=np.uint64)
+    _check(_lib.kh_poseidon_gate_coefficients(field, _p64(out)))
+    return out
+
+
+def poseidon_permute_dev(field: int, states, n: int):
+    """kh_poseidon_permute_dev: n states of 3 elements at `states` (anything with a .ptr) permuted in place, queued on the main stream."""
+    _check(_lib.kh_poseidon_permute_dev(field, C.c_void_p(states.ptr), n))
+
+
+def poseidon_hash_dev(field: int, msgs, msg_len: int, n: int, digests, init=None):
+    """kh_poseidon_hash_dev: n messages of msg_len elements at `msgs` (None when msg_len == 0) -> n digests at `digests`; init: (3, 4) limbs or None (zero)."""
+    st = None if init is None else _c64(init, (3, 4))
+    _check(_lib.kh_poseidon_hash_dev(field, C.c_void_p(msgs.ptr if msgs is not None else 0), msg_len, n, _p64(st) if st is not None else None,
+                                     C.c_void_p(digests.ptr)))
+
+
+def poseidon_gate_witness_dev(field: int, states, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0, row_stride: int = 12,
+                              out_states=None):
+    """kh_poseidon_gate_witness_dev: the witness rows of n Poseidon gadgets into the 15 columns at `witness`, instance i at row rows[i] (a sequence of
+    ints) or row0 + i * row_stride; out_states (nullable, may be `states`): the n final states."""
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+    _check(_lib.kh_poseidon_gate_witness_dev(field, C.c_void_p(states.ptr), n, r.ctypes.data_as(C.POINTER(C.c_uint32)) if r is not None else None, row0,
+                                             row_stride, C.c_void_p(witness.ptr), col_stride, col_len,
+                                             C.c_void_p(out_states.ptr if out_states is not None else 0)))
+
+
+def poseidon_set_split_max_n(n: int = 43008):
+    """kh_poseidon_set_split_max_n: up to n instances poseidon_gate_witness_dev runs its three-lanes-per-permutation kernel (0: never)"""
+    _check(_lib.kh_poseidon_set_split_max_n(n))
+
+
 class Comm:
     """kh_comm_*: the in-library RCCL communicator of the one-process-per-GPU deployment (no torch).  Comm.unique_id() on one rank, the bytes to
     the others, Comm(world, rank, id) on every rank."""

@@ -1,0 +1,396 @@
+"""Poseidon on the device (csrc/poseidon.hip: kh_poseidon_permute_dev, kh_poseidon_hash_dev, kh_poseidon_gate_witness_dev) against the oracle's sponge
+(oracle/poseidon.py, pinned on the reference's poseidon/tests/test_vectors/kimchi.json), the oracle's gadget witness (oracle/gates.py) and the product's
+own constraint check, prover and verifier.  Everything is compared bit for bit: a canonical Montgomery element has one 32-byte form."""
+import ctypes as C
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+from oracle import gates as G
+from oracle import pasta as P
+from oracle import poseidon as S
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIELDS = (P.Fp, P.Fq)
+SENTINEL = np.array([0x0123456789abcdef, 0xfedcba9876543210, 0x0f1e2d3c4b5a6978, 0x1badc0de1badc0de], dtype=np.uint64)     # a canonical element (< 2^253)
+
+
+@pytest.fixture(scope="module")
+def khip():
+    import proof_systems_amd.khip as k
+    k.init(0)
+    return k
+
+
+def limbs(F, vals):
+    """(len(vals), 4) Montgomery limbs"""
+    p, R = F.p, 1 << 256
+    return np.frombuffer(b"".join((v % p * R % p).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def permuted(F, st):
+    sp = S.ArithmeticSponge(F); sp.state = list(st); sp.permute()
+    return sp.state
+
+
+def hashed(F, init, msg):
+    sp = S.ArithmeticSponge(F); sp.state = list(init); sp.absorb(msg)
+    return sp.squeeze()
+
+
+def sentinel_buf(khip, elems):
+    return khip.DevBuf(32 * elems).upload(np.tile(SENTINEL, (elems, 1)))
+
+
+# ---- 1. the permutation
+POOL = 1000
+
+
+@pytest.fixture(scope="module")
+def pools():
+    """per field: 1000 states -- random canonical ones, with the 27 states made of 0, 1, p - 1 on the odd places up to 53 and again on the places next to
+    the wave boundaries and on the last one -- and their permutations by the oracle, computed once"""
+    out = []
+    for fid, F in enumerate(FIELDS):
+        rnd = random.Random(100 + fid)
+        special = [[a, b, c] for a in (0, 1, F.p - 1) for b in (0, 1, F.p - 1) for c in (0, 1, F.p - 1)]
+        st = [[rnd.randrange(F.p) for _ in range(3)] for _ in range(POOL)]
+        for k, s in enumerate(special):
+            st[2 * k + 1] = s
+        for k, i in enumerate((62, 63, 64, 65, 126, 127, 128, 129, POOL - 1)):
+            st[i] = special[(3 * k + 5) % 27]
+        out.append((st, [permuted(F, s) for s in st]))
+    return out
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 127, 128, 129, 1000])
+@pytest.mark.parametrize("fid", [0, 1])
+def test_permutation_equals_the_oracle(khip, pools, fid, n):
+    F = FIELDS[fid]
+    st, want = pools[fid]
+    for lo in sorted({0, 1 if n <= 2 else 0, POOL - n}):            # the head of the pool, its tail, and for n <= 2 a window that starts on a special state
+        buf = khip.DevBuf(96 * n).upload(limbs(F, [x for s in st[lo:lo + n] for x in s]))
+        khip.poseidon_permute_dev(fid, buf, n)
+        got = buf.download((n, 3, 4))
+        assert np.array_equal(got, limbs(F, [x for s in want[lo:lo + n] for x in s]).reshape(n, 3, 4)), (fid, n, lo)
+        buf.free()
+
+
+# ---- 2. the reference's own vectors
+def test_reference_vectors_through_the_device_hash(khip):
+    """every entry of poseidon/tests/test_vectors/kimchi.json (hash over Fp), batched by message length"""
+    kats = json.load(open(os.path.join(ROOT, "tests", "golden", "poseidon_kimchi_params.json")))["kats"]["kimchi_fp_hash"]
+    assert len(kats) >= 5
+    by_len = {}
+    for kat in kats:
+        by_len.setdefault(len(kat["input"]), []).append(kat)
+    assert len(by_len) >= 5
+    for msg_len, group in by_len.items():
+        n = len(group)
+        ins = [int.from_bytes(bytes.fromhex(h), "little") for kat in group for h in kat["input"]]
+        msgs = khip.DevBuf(32 * max(len(ins), 1))
+        if ins:
+            msgs.upload(limbs(P.Fp, ins))
+        dig = sentinel_buf(khip, n)
+        khip.poseidon_hash_dev(khip.FP, msgs, msg_len, n, dig)
+        want = limbs(P.Fp, [int.from_bytes(bytes.fromhex(kat["output"]), "little") for kat in group])
+        assert np.array_equal(dig.download((n, 4)), want), msg_len
+        msgs.free(); dig.free()
+
+
+# ---- 3. the sponge
+@pytest.mark.parametrize("with_init", [False, True])
+@pytest.mark.parametrize("fid", [0, 1])
+def test_hash_equals_the_oracle_sponge(khip, fid, with_init):
+    """msg_len 0..7, n in {1, 65, 300}, from the zero state and from a given one.  The reference is computed once: 300 messages of 7 elements, whose
+    prefixes are the messages of every shorter length (the oracle's sponge absorbs element by element; a copy of it is squeezed after each), and the
+    smaller batches are the first 1 and 65 of them."""
+    F = FIELDS[fid]
+    rnd = random.Random(200 + 2 * fid + with_init)
+    init = [rnd.randrange(F.p), F.p - 1, rnd.randrange(F.p)] if with_init else [0, 0, 0]
+    full = [[rnd.choice((rnd.randrange(F.p), rnd.randrange(F.p), rnd.randrange(F.p), 0, 1, F.p - 1)) for _ in range(7)] for _ in range(300)]
+    digests = [[] for _ in range(8)]
+    for m in full:
+        sp = S.ArithmeticSponge(F); sp.state = list(init)
+        for msg_len in range(8):
+            cp = S.ArithmeticSponge(F); cp.state, cp.mode, cp.n = list(sp.state), sp.mode, sp.n
+            digests[msg_len].append(cp.squeeze())
+            if msg_len < 7:
+                sp.absorb([m[msg_len]])
+    assert digests[3][:2] == [hashed(F, init, m[:3]) for m in full[:2]]
+    for msg_len in range(8):
+        msg = [m[:msg_len] for m in full]
+        want = limbs(F, digests[msg_len])
+        msgs = khip.DevBuf(32 * max(300 * msg_len, 1))
+        if msg_len:
+            msgs.upload(limbs(F, [x for m in msg for x in m]))
+        for n in (1, 65, 300):
+            dig = sentinel_buf(khip, n + 1)
+            khip.poseidon_hash_dev(fid, msgs, msg_len, n, dig, init=limbs(F, init) if with_init else None)
+            got = dig.download((n + 1, 4))
+            assert np.array_equal(got[:n], want[:n]), (fid, with_init, msg_len, n)
+            assert np.array_equal(got[n], SENTINEL)                    # n digests and not one more
+            dig.free()
+        msgs.free()
+
+
+@pytest.mark.parametrize("fid", [0, 1])
+def test_empty_message_without_a_message_buffer(khip, fid):
+    F = FIELDS[fid]
+    init = [5, 0, F.p - 2]
+    for st in (None, init):
+        dig = sentinel_buf(khip, 65)
+        khip.poseidon_hash_dev(fid, None, 0, 65, dig, init=None if st is None else limbs(F, st))
+        want = limbs(F, [hashed(F, st or [0, 0, 0], [])])
+        assert np.array_equal(dig.download((65, 4)), np.tile(want, (65, 1)))
+        dig.free()
+
+
+def test_device_digest_equals_the_host_sponge(khip):
+    """the product's own host code: a fresh Fr-sponge of Vesta (over Fp), two elements absorbed, one squeezed"""
+    rnd = random.Random(7)
+    x = limbs(P.Fp, [rnd.randrange(P.Fp.p), rnd.randrange(P.Fp.p)])
+    sp = khip.Sponge(khip.Sponge.FR, khip.VESTA)
+    sp.absorb(x)
+    want = sp.squeeze_field()
+    msgs = khip.DevBuf(64).upload(x)
+    dig = khip.DevBuf(32)
+    khip.poseidon_hash_dev(khip.FP, msgs, 2, 1, dig)
+    assert np.array_equal(dig.download((4,)), np.asarray(want, dtype=np.uint64).reshape(4))
+    msgs.free(); dig.free()
+
+
+# ---- 4. the gadget's witness rows
+COL_LEN = 256
+
+
+def gadget_cells(F, fid, st):
+    """({(row offset, column): value} of the cells poseidon_witness fills: 11 x 15 + 3, the final state)"""
+    par = S.params(("fp", "fq")[fid])
+    w, _co, out = G.poseidon_witness(F, st, par["mds"], par["rc"], 11)
+    cells = {(j, c): w[j][c] for j in range(11) for c in range(15)}
+    cells.update({(11, c): w[11][c] for c in range(3)})
+    assert [w[11][c] for c in range(3)] == out == permuted(F, st)
+    return cells, out
+
+
+@pytest.fixture(params=["three lanes per permutation", "one lane per permutation"])
+def kernel(khip, request):
+    """kh_poseidon_gate_witness_dev has two kernels and a size threshold between them: every gate-rows test runs under both"""
+    khip.poseidon_set_split_max_n((1 << 40) if request.param.startswith("three") else 0)
+    yield request.param
+    khip.poseidon_set_split_max_n()
+
+
+def run_gate_rows(khip, fid, states, rows=None, row0=0, row_stride=12, col_stride=COL_LEN, alias=False, col_len=COL_LEN):
+    """calls kh_poseidon_gate_witness_dev on a sentinel-filled 15 x col_stride buffer and compares every cell and the final states"""
+    F = FIELDS[fid]
+    n = len(states)
+    start = list(rows) if rows is not None else [row0 + i * row_stride for i in range(n)]
+    want = np.tile(SENTINEL, (15, col_stride, 1))
+    finals = []
+    for r, st in zip(start, states):
+        cells, out = gadget_cells(F, fid, st)
+        keys = sorted(cells)
+        lm = limbs(F, [cells[k] for k in keys])
+        for (j, c), v in zip(keys, lm):
+            want[c, r + j] = v
+        finals += out
+    wit = sentinel_buf(khip, 15 * col_stride)
+    sbuf = khip.DevBuf(96 * n).upload(limbs(F, [x for s in states for x in s]))
+    obuf = sbuf if alias else sentinel_buf(khip, 3 * n + 1)
+    khip.poseidon_gate_witness_dev(fid, sbuf, n, wit, col_stride, col_len, rows=rows, row0=row0, row_stride=row_stride, out_states=obuf)
+    got = wit.download((15, col_stride, 4))
+    bad = np.argwhere((got != want).any(axis=2))
+    assert bad.size == 0, ("cells (column, row) that differ", bad[:8].tolist())
+    assert np.array_equal(obuf.download((3 * n, 4)), limbs(F, finals))
+    if not alias:
+        assert np.array_equal(obuf.download_at(96 * n, (4,)), SENTINEL)
+        assert np.array_equal(sbuf.download((3 * n, 4)), limbs(F, [x for s in states for x in s]))      # the inputs are left alone
+        obuf.free()
+    wit.free(); sbuf.free()
+
+
+def some_states(F, n, seed):
+    rnd = random.Random(seed)
+    st = [[rnd.randrange(F.p) for _ in range(3)] for _ in range(n)]
+    st[0] = [0, 1, F.p - 1]
+    return st
+
+
+@pytest.mark.parametrize("alias", [False, True])
+@pytest.mark.parametrize("fid", [0, 1])
+def test_gate_rows_at_irregular_rows(khip, kernel, fid, alias):
+    """(a) seven instances, in no order, touching row 0 and row col_len - 12, two of them back to back"""
+    rows = [100, 0, COL_LEN - 12, 13, 200, 52, 40]
+    run_gate_rows(khip, fid, some_states(FIELDS[fid], 7, 300 + fid), rows=rows, alias=alias)
+
+
+@pytest.mark.parametrize("n,row0,row_stride", [(21, 4, 12), (19, 10, 13), (1, 7, 12), (1, COL_LEN - 12, 40)])
+@pytest.mark.parametrize("fid", [0, 1])
+def test_gate_rows_at_regular_rows(khip, kernel, fid, n, row0, row_stride):
+    """(b), (c): rows == NULL with strides 12 (a full column: 21 instances end on the last row) and 13, n = 1 and 21"""
+    run_gate_rows(khip, fid, some_states(FIELDS[fid], n, 310 + fid), row0=row0, row_stride=row_stride)
+    if n == 21:
+        run_gate_rows(khip, fid, some_states(FIELDS[fid], n, 320 + fid), rows=[row0 + 12 * i for i in range(n)], alias=True)     # the same places through `rows`
+
+
+def test_gate_rows_with_columns_further_apart_than_their_length(khip, kernel):
+    """col_stride > col_len: the rows between the columns keep the sentinel"""
+    run_gate_rows(khip, 1, some_states(P.Fq, 3, 330), rows=[COL_LEN - 12, 0, 77], col_stride=COL_LEN + 37)
+
+
+@pytest.mark.parametrize("fid", [0, 1])
+def test_gate_rows_over_several_waves(khip, kernel, fid):
+    """a longer column: 64 and 65 instances are one wave (and one lane of a second) with a lane each, three waves of 21 and one or two lanes of a fourth
+    with three lanes each; 43 end one lane behind a full second wave"""
+    for n, seed in ((64, 340), (65, 341), (43, 342)):
+        run_gate_rows(khip, fid, some_states(FIELDS[fid], n, seed + 10 * fid), row0=2, row_stride=13, col_stride=900, col_len=900)
+
+
+def test_the_threshold_chooses_the_kernel(khip):
+    """up to kh_poseidon_set_split_max_n instances (default 43008) the three-lane kernel runs, above it the one-lane kernel: the phase kh_last_timings
+    names after the call says which"""
+    states = khip.DevBuf(96 * 5).upload(limbs(P.Fp, [x for s in some_states(P.Fp, 5, 350) for x in s]))
+    wit = khip.DevBuf(32 * 15 * 64)
+    try:
+        for split_max, phase in ((None, "poseidon_gate_rows3"), (4, "poseidon_gate_rows"), (5, "poseidon_gate_rows3"), (0, "poseidon_gate_rows")):
+            khip.poseidon_set_split_max_n(*(() if split_max is None else (split_max,)))
+            khip.poseidon_gate_witness_dev(0, states, 5, wit, 64, 64)
+            khip.sync()
+            assert [name for name, _ms in khip.last_timings()] == [phase], (split_max, khip.last_timings())
+    finally:
+        khip.poseidon_set_split_max_n()
+    states.free(); wit.free()
+
+
+# ---- 5. through the product: index, constraint check, proof, verification
+def test_gadget_witness_satisfies_the_product(khip):
+    fid, F = khip.FP, P.Fp
+    srs = khip.Srs.create(khip.VESTA, 1 << 7)
+    gids = khip.gate_ids()
+    inst = 5
+    types = ([gids["Poseidon"]] * 11 + [khip.GATE_ZERO]) * inst
+    wires = np.array([[(r, c) for c in range(7)] for r in range(12 * inst)], dtype=np.uint32)
+    coeffs = np.zeros((12 * inst, 15, 4), dtype=np.uint64)
+    for i in range(inst):
+        coeffs[12 * i:12 * i + 11] = khip.poseidon_gate_coefficients(fid)
+    ix = khip.NativeProverIndex.create(srs, types, wires, coeffs)
+    log2_n, _zk, nch = ix.shape()
+    n = 1 << log2_n
+    assert n >= 12 * inst + 3 and nch == 1
+    states = some_states(F, inst, 400)
+    sbuf = khip.DevBuf(96 * inst).upload(limbs(F, [x for s in states for x in s]))
+    wit = khip.DevBuf(32 * 15 * n).zero()
+    khip.poseidon_gate_witness_dev(fid, sbuf, inst, wit, n, n)                       # nothing else fills the witness
+    rep = ix.witness_check(witness_dev=wit, flags=khip.WITNESS_GATES | khip.WITNESS_WIRES)
+    assert rep.kind == khip.WITNESS_OK, khip.witness_report_message(rep)
+    sections, _ph = ix.prove(witness_dev=wit, flags=khip.PROVE_CHECK)
+    vix = khip.VerifierIndex.of(ix)
+    proof = khip.Proof(sections)
+    ok, _trace = khip.verify(vix, proof)
+    assert ok
+    # the check reads these very cells: another input state under instance 2's rows, and its first row is the first that fails
+    wit.upload_at(32 * (1 * n + 24), limbs(F, [states[2][1] + 1]))
+    rep = ix.witness_check(witness_dev=wit, flags=khip.WITNESS_GATES | khip.WITNESS_WIRES)
+    assert (rep.kind, rep.row, rep.gate) == (khip.WITNESS_GATE, 24, gids["Poseidon"]), khip.witness_report_message(rep)
+    assert rep.gate_rows_violated == 1
+    proof.free(); vix.free(); ix.free(); wit.free(); sbuf.free(); srs.close()
+
+
+# ---- 6. ordering: producer -> permutation -> hash -> download without a kh_sync in between
+def test_steps_are_ordered_on_the_main_stream_and_on_a_private_context(khip):
+    fid, F = khip.FQ, P.Fq
+    n = 130
+    vals = [3, F.p - 1, 0x1234567]
+    per = [n // 3, n // 3, n - 2 * (n // 3)]
+
+    def sequence():
+        st = sentinel_buf(khip, 3 * n)
+        dig = sentinel_buf(khip, n)
+        off = 0
+        for v, cnt in zip(vals, per):
+            st.fill_elements(3 * off, limbs(F, [v])[0], 3 * cnt)
+            off += cnt
+        khip.poseidon_permute_dev(fid, st, n)
+        khip.poseidon_hash_dev(fid, st, 3, n, dig)
+        out = dig.download((n, 4))
+        st.free(); dig.free()
+        return out
+
+    want = limbs(F, [hashed(F, [0, 0, 0], permuted(F, [v, v, v])) for v, cnt in zip(vals, per) for _ in range(cnt)])
+    shared = sequence()
+    assert np.array_equal(shared, want)
+    lib = khip.raw()
+    assert lib.kh_private_context_begin() == 0
+    try:
+        private = sequence()
+    finally:
+        assert lib.kh_private_context_end() == 0
+    assert private.tobytes() == shared.tobytes()
+
+
+# ---- 7. refusals: KH_E_INVALID with a text, before anything is launched, nothing written
+def test_refusals_leave_everything_untouched(khip):
+    lib = khip.raw()
+    n = 4
+    states = sentinel_buf(khip, 3 * n)
+    dig = sentinel_buf(khip, n)
+    msgs = sentinel_buf(khip, 2 * n)
+    wit = sentinel_buf(khip, 15 * COL_LEN)
+    out = sentinel_buf(khip, 3 * n)
+    vp = C.c_void_p
+    rows_t = C.c_uint32 * 3
+
+    def permute(field=0, p=states.ptr, k=n):
+        return lib.kh_poseidon_permute_dev(field, vp(p), k)
+
+    def hash_(field=0, m=msgs.ptr, msg_len=2, k=n, d=dig.ptr):
+        return lib.kh_poseidon_hash_dev(field, vp(m), msg_len, k, None, vp(d))
+
+    def gate(field=0, s=states.ptr, k=n, rows=None, row0=0, row_stride=12, w=wit.ptr, col_stride=COL_LEN, col_len=COL_LEN, o=out.ptr):
+        return lib.kh_poseidon_gate_witness_dev(field, vp(s), k, rows, row0, row_stride, vp(w), col_stride, col_len, vp(o))
+
+    refused = {
+        "permute: unknown field": lambda: permute(field=2),
+        "hash: unknown field": lambda: hash_(field=-1),
+        "gate rows: unknown field": lambda: gate(field=7),
+        "permute: null states": lambda: permute(p=None),
+        "hash: null messages": lambda: hash_(m=None),
+        "hash: null digests": lambda: hash_(d=None),
+        "gate rows: null states": lambda: gate(s=None),
+        "gate rows: null witness": lambda: gate(w=None),
+        "permute: unaligned": lambda: permute(p=states.ptr + 8),
+        "hash: unaligned messages": lambda: hash_(m=msgs.ptr + 8, k=n - 1),
+        "hash: unaligned digests": lambda: hash_(d=dig.ptr + 8, k=n - 1),
+        "gate rows: unaligned states": lambda: gate(s=states.ptr + 8, k=n - 1),
+        "gate rows: unaligned witness": lambda: gate(w=wit.ptr + 8, col_len=COL_LEN - 1, col_stride=COL_LEN - 1),
+        "gate rows: unaligned final states": lambda: gate(o=out.ptr + 8, k=n - 1),
+        "gate rows: an instance past the end": lambda: gate(k=3, rows=rows_t(0, 20, COL_LEN - 11)),
+        "gate rows: row_stride < 12": lambda: gate(row_stride=11),
+        "gate rows: the last instance past the end": lambda: gate(row0=COL_LEN - 12 * n + 1),
+        "gate rows: col_len < 12": lambda: gate(k=1, col_len=11, col_stride=11),
+        "gate rows: col_stride < col_len": lambda: gate(col_stride=COL_LEN - 1),
+        "permute: byte count overflows": lambda: permute(k=1 << 60),
+        "hash: byte count overflows": lambda: hash_(k=1 << 35, msg_len=1 << 30),
+        "gate rows: byte count overflows": lambda: gate(col_stride=1 << 62),
+        "gate rows: row count overflows": lambda: gate(k=1 << 36, row_stride=1 << 40),
+    }
+    for what, call in refused.items():
+        assert call() == khip.E_INVALID, what
+        text = lib.kh_last_error().decode()
+        assert text.strip(), what
+        if what == "gate rows: an instance past the end":
+            assert "instance 2" in text, text
+    for buf, elems in ((states, 3 * n), (dig, n), (msgs, 2 * n), (wit, 15 * COL_LEN), (out, 3 * n)):
+        assert np.array_equal(buf.download((elems, 4)), np.tile(SENTINEL, (elems, 1)))
+    # ... and what is allowed: n == 0 with null pointers, nothing launched
+    assert lib.kh_poseidon_permute_dev(0, None, 0) == 0
+    assert lib.kh_poseidon_hash_dev(1, None, 5, 0, None, None) == 0
+    assert lib.kh_poseidon_gate_witness_dev(0, None, 0, None, 0, 0, None, 0, 0, None) == 0
+    for buf in (states, dig, msgs, wit, out):
+        buf.free()
