@@ -315,6 +315,60 @@ int kh_poseidon_gate_witness_dev(int field, const uint64_t *states_dev, size_t n
  * values are written either way; the tests set it to run both kernels at small sizes. */
 int kh_poseidon_set_split_max_n(size_t n);
 
+/* ---- The curve gates' witness on the device (csrc/curve_gadgets.hip) ----
+ * CompleteAdd, VarBaseMul, EndoMul and EndoMulScalar: with kh_poseidon_gate_witness_dev, the witness of every always-present library gate, written in
+ * place from a few inputs per instance.  The conventions are those of the Poseidon block above.  witness_dev: 15 columns, column c at
+ * witness_dev + 4 * c * col_stride, col_len rows each.  Instance i starts at row rows[i] (host array, copied before the call returns), or at
+ * row0 + i * row_stride when rows == NULL.  The calls are vector steps: queued on the main stream of the calling thread's current context (the private
+ * one between kh_private_context_begin and _end) and ordered against every other call of the library -- a producer followed by a consumer needs no
+ * kh_sync.  (kh_varbasemul_witness_dev and kh_endomul_witness_dev wait for the stream once per slice, see below: they invert one element on the host,
+ * like kh_batch_inversion_dev.)  n == 0 is KH_OK with nothing launched.  KH_E_INVALID with a kh_last_error text, before anything is launched and with
+ * nothing written: an unknown field, a null pointer with n > 0, a device pointer that is not 16-byte aligned, byte counts that overflow, an instance
+ * that does not fit col_len (naming it), row_stride smaller than an instance's row count, col_stride < col_len, a bad num_bits.
+ * `field` is the circuit's field; points are affine x || y in that field (8 limbs, Montgomery), as the gates see them, and are not checked to be on a
+ * curve.  Every value is the canonical Montgomery element the reference's generator computes, bit for bit, and each call writes exactly the cells that
+ * generator assigns: NOTHING else (not column 6 of a VarBaseMul base row, columns 12..14 of its bit row, column 3 of an EndoMul row, columns 11..14 of
+ * CompleteAdd).  Overlapping instances are the caller's responsibility. */
+
+/* complete_add.rs witness: one row per instance, cells 0..10 = x1 y1 x2 y2 x3 y3 inf same_x s inf_z x21_inv: the generic sum, the doubling when
+ * p1 == p2, inf = 1 (x3, y3 as the formulas give them) for P + (-P).  out_dev (nullable): n x 8 limbs, (x3, y3) as written. */
+int kh_complete_add_witness_dev(int field, const uint64_t *p1_dev, const uint64_t *p2_dev, size_t n, const uint32_t *rows, size_t row0, size_t row_stride,
+                                uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev);
+
+/* varbasemul.rs witness(): acc <- (acc + Q) + acc for the bits num_bits - 1 .. 0 of scalars_dev[i] (n x 4 canonical little-endian limbs, plain integers;
+ * higher bits are ignored), Q = base if the bit is 1 and -base otherwise, starting from acc0; 5 bits per pair of rows, 2 * num_bits / 5 rows per instance
+ * (num_bits a multiple of 5 from 5 to 255).  out_acc_dev (nullable, n x 8): the final accumulator; out_n_dev (nullable, n x 4, Montgomery): the final
+ * n_acc, the scalar's num_bits bits mod p.
+ * Zero denominators (the reference's generator panics: x_i == x_Q or R == -acc at some bit): flags_dev (nullable) is a caller-zeroed uint32_t on the
+ * device, as for kh_check_equal_dev; bit `bit` (< 32) of it is set when any instance met one, and is not touched otherwise.  Such an instance's own
+ * cells are unspecified (inside its own rows); every other instance of the call is exact.
+ * No lane inverts per bit: one lane per instance walks the accumulator in XYZZ coordinates, one batch inversion over (instance, bit) yields the affine
+ * accumulators and the slopes, one lane per (instance, bit) writes the cells.  Scratch comes from the kh_dev_alloc pool for the time of the call:
+ * 160 bytes per (instance, bit + 1) -- 41 KB per 255-bit instance --, for at most 2^22 / (num_bits + 1) instances at a time (16384 at 255 bits,
+ * 0.67 GB); a larger batch is worked through in slices of that many, so n is bounded only by the grid (2^36). */
+int kh_varbasemul_witness_dev(int field, const uint64_t *base_dev, const uint64_t *acc0_dev, const uint64_t *scalars_dev, unsigned num_bits, size_t n,
+                              const uint32_t *rows, size_t row0, size_t row_stride, uint64_t *witness_dev, size_t col_stride, size_t col_len,
+                              uint64_t *out_acc_dev, uint64_t *out_n_dev, uint32_t *flags_dev, unsigned bit);
+
+/* endosclmul.rs gen_witness: 4 bits of chals_dev[i] (n x 2 canonical limbs) per row, most significant of the num_bits first (a multiple of 4 from 4 to
+ * 128), num_bits / 4 rows + the closing row (cells 0, 1, 4, 5, 6) per instance.  endo: 4 host limbs, VerifierIndex::endo (what kh_gate_constants takes).
+ * out_acc_dev, out_n_dev, flags_dev, bit as above; the zero denominators are the two of each half-step and (x_p - x_r)(x_r - x_s).  Scratch as above
+ * with num_bits / 2 + 1 accumulators and num_bits / 4 more inversions per instance: 11.4 KB per 128-bit instance. */
+int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t *base_dev, const uint64_t *acc0_dev, const uint64_t *chals_dev,
+                           unsigned num_bits, size_t n, const uint32_t *rows, size_t row0, size_t row_stride, uint64_t *witness_dev, size_t col_stride,
+                           size_t col_len, uint64_t *out_acc_dev, uint64_t *out_n_dev, uint32_t *flags_dev, unsigned bit);
+
+/* Tuning knob (process-wide): kh_varbasemul_witness_dev and kh_endomul_witness_dev take as many instances at a time as keep the slice's batch inversion
+ * within `elements` field elements; default and maximum 2^22 (what one scan takes), 0 = the default.  The same values are written either way; the tests
+ * set it to run several slices at small sizes. */
+int kh_curve_witness_set_slice_elements(size_t elements);
+
+/* endomul_scalar.rs gen_witness: 16 bits of chals_dev[i] (n x 2 canonical limbs) per row, most significant of the num_bits first (a multiple of 16 from
+ * 16 to 128), num_bits / 16 rows per instance, cells 0..13 = n0 n8 a0 b0 a8 b8 x0..x7.  out_dev (nullable, n x 4): a * endo_scalar + b, the scalar the
+ * challenge stands for; endo_scalar: 4 host limbs (Montgomery), required with out_dev.  One lane per instance, additions only. */
+int kh_endomul_scalar_witness_dev(int field, const uint64_t *chals_dev, unsigned num_bits, size_t n, const uint32_t *rows, size_t row0, size_t row_stride,
+                                  uint64_t *witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t *out_dev);
+
 /* ---- scans, batch inversion, division by a linear factor: the permutation argument's vector steps ----
  * kh_field_scan_dev: in-place inclusive prefix (reverse = 0) or suffix (reverse = 1) scan under + or *
  *   (the running product z[j+1] = z[j] * ..., kimchi/src/circuits/polynomials/permutation.rs:556-563).

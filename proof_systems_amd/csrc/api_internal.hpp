@@ -91,4 +91,19 @@ int poseidon_hash(Context& C, int field, const uint64_t* msgs_dev, size_t msg_le
 int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride,
                        uint64_t* witness_dev, size_t col_stride, uint64_t* out_states_dev);
 void poseidon_set_split_max_n(size_t n);
+// curve_gadgets.hip: the launchers of kh_complete_add_witness_dev, kh_endomul_scalar_witness_dev, kh_varbasemul_witness_dev and kh_endomul_witness_dev,
+// queued on C.stream (arguments validated by the entry points; n >= 1).  chain_rows (VarBaseMul, or EndoMul with is_endo) works through the batch in
+// slices over a scratch block of chain_scratch_bytes (chain_slice instances; the knob kh_curve_witness_set_slice_elements may move between the
+// entry point's question and the launch, so the launcher is told what it got), which the entry point takes from the kh_dev_alloc pool.
+static constexpr size_t GADGET_MAX_N = (size_t)1 << 36;        // one-wave blocks: the grid stays inside 31 bits
+int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows_dev, size_t row0,
+                      size_t row_stride, uint64_t* witness_dev, size_t col_stride, uint64_t* out_dev);
+int endomul_scalar_rows(Context& C, int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0,
+                        size_t row_stride, uint64_t* witness_dev, size_t col_stride, const uint64_t* endo_scalar, uint64_t* out_dev);
+size_t chain_slice(bool is_endo, unsigned num_bits, size_t n);
+size_t chain_scratch_bytes(bool is_endo, unsigned num_bits, size_t n);
+int chain_rows(Context& C, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev,
+               unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride,
+               uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit, uint64_t* scratch_dev, size_t scratch_bytes);
+void chain_set_slice_elements(size_t elems);
 }  // namespace kh

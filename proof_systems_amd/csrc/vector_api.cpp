@@ -1,4 +1,4 @@
-// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve gates' kh_*_witness_dev, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
 #include <stdlib.h>
 
 #include "api_internal.hpp"
@@ -313,6 +313,118 @@ int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n
 }
 #undef KH_POSEIDON_ALIGNED
 int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return KH_OK; }
+
+// ---------------------------------------------------------------------------------- the curve gates' witness on the device (kernels in curve_gadgets.hip)
+namespace {
+struct GadgetPtr { const char* name; const void* p; bool required; };
+// what the four calls refuse alike: the field, null / misaligned device pointers, sizes that overflow, instances of inst_rows rows that do not fit
+int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                    size_t col_stride, size_t col_len, size_t inst_rows) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
+    for (const GadgetPtr& a : ptrs) {
+        KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
+        KH_REQUIRE((((uintptr_t)a.p) & 15) == 0, "%s: %s must be 16-byte aligned", call, a.name);
+    }
+    KH_REQUIRE(col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, col_stride, col_len);
+    KH_REQUIRE(n <= GADGET_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
+               col_stride);
+    if (n > 0 && rows) {
+        for (size_t i = 0; i < n; i++)
+            KH_REQUIRE(col_len >= inst_rows && rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
+                       rows[i], col_len, inst_rows);
+    } else if (n > 0) {
+        KH_REQUIRE(row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, row_stride, inst_rows);
+        KH_REQUIRE(col_len >= inst_rows && row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - row0) / row_stride,
+                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, row0, row_stride, col_len);
+    }
+    return KH_OK;
+}
+// blocks of the kh_dev_alloc pool that go back to it when the call returns (work queued on the main stream before that precedes their next use)
+struct PoolBlock { void* p = nullptr; ~PoolBlock() { if (p) (void)kh_dev_free(p); } };
+// the start rows through the pinned staging ring into rows_dev, in pieces that leave the ring its size (C.mu held)
+int upload_rows(Context& C, const uint32_t* rows, size_t n, uint32_t* rows_dev) {
+    const size_t piece = (size_t)1 << 15;
+    int rc;
+    for (size_t i = 0; rows && i < n; i += piece)
+        if ((rc = C.stage_upload(rows_dev + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}}))) return rc;
+    return KH_OK;
+}
+}  // namespace
+
+int kh_complete_add_witness_dev(int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                                uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
+    int rc = gadget_validate("kh_complete_add_witness_dev", field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"witness_dev", witness_dev, true},
+                             {"out_dev", out_dev, false}}, n, rows, row0, row_stride, col_stride, col_len, 1);
+    if (rc) return rc;
+    if ((rc = ensure_init())) return rc;
+    if (n == 0) return KH_OK;
+    PoolBlock rows_dev;
+    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
+    rc = complete_add_rows(C, field, p1_dev, p2_dev, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev, col_stride, out_dev);
+    C.mark_async();
+    return rc;
+}
+int kh_endomul_scalar_witness_dev(int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                                  uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t* out_dev) {
+    KH_REQUIRE(num_bits >= 16 && num_bits <= 128 && num_bits % 16 == 0, "kh_endomul_scalar_witness_dev: num_bits %u is not a multiple of 16 from 16 to 128",
+               num_bits);
+    int rc = gadget_validate("kh_endomul_scalar_witness_dev", field, {{"chals_dev", chals_dev, true}, {"witness_dev", witness_dev, true},
+                             {"out_dev", out_dev, false}}, n, rows, row0, row_stride, col_stride, col_len, num_bits / 16);
+    if (rc) return rc;
+    KH_REQUIRE(endo_scalar || !out_dev || n == 0, "kh_endomul_scalar_witness_dev: null endo_scalar with an out_dev");
+    if ((rc = ensure_init())) return rc;
+    if (n == 0) return KH_OK;
+    PoolBlock rows_dev;
+    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
+    rc = endomul_scalar_rows(C, field, chals_dev, num_bits, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev, col_stride, endo_scalar, out_dev);
+    C.mark_async();
+    return rc;
+}
+// VarBaseMul (endo == nullptr, scalars of 4 limbs) and EndoMul (challenges of 2 limbs) share everything but their row counts
+static int chain_witness(const char* call, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev,
+                         const uint64_t* scalars_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev,
+                         size_t col_stride, size_t col_len, uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
+    if (is_endo) KH_REQUIRE(num_bits >= 4 && num_bits <= 128 && num_bits % 4 == 0, "%s: num_bits %u is not a multiple of 4 from 4 to 128", call, num_bits);
+    else KH_REQUIRE(num_bits >= 5 && num_bits <= 255 && num_bits % 5 == 0, "%s: num_bits %u is not a multiple of 5 from 5 to 255", call, num_bits);
+    int rc = gadget_validate(call, field, {{"base_dev", base_dev, true}, {"acc0_dev", acc0_dev, true}, {is_endo ? "chals_dev" : "scalars_dev", scalars_dev, true},
+                             {"witness_dev", witness_dev, true}, {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
+                             n, rows, row0, row_stride, col_stride, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
+    if (rc) return rc;
+    KH_REQUIRE(!is_endo || endo || n == 0, "%s: null endo", call);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (void*)flags_dev);
+    if ((rc = ensure_init())) return rc;
+    if (n == 0) return KH_OK;
+    PoolBlock rows_dev, scratch;
+    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    const size_t scratch_bytes = chain_scratch_bytes(is_endo, num_bits, n);
+    if ((rc = kh_dev_alloc(&scratch.p, scratch_bytes))) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
+    rc = chain_rows(C, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev,
+                    col_stride, out_acc_dev, out_n_dev, flags_dev, bit, (uint64_t*)scratch.p, scratch_bytes);
+    C.mark_async();
+    return rc;
+}
+int kh_varbasemul_witness_dev(int field, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev, unsigned num_bits, size_t n,
+                              const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
+                              uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
+    return chain_witness("kh_varbasemul_witness_dev", field, false, nullptr, base_dev, acc0_dev, scalars_dev, num_bits, n, rows, row0, row_stride, witness_dev,
+                         col_stride, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
+}
+int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* chals_dev, unsigned num_bits,
+                           size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
+                           uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
+    return chain_witness("kh_endomul_witness_dev", field, true, endo, base_dev, acc0_dev, chals_dev, num_bits, n, rows, row0, row_stride, witness_dev,
+                         col_stride, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
+}
+int kh_curve_witness_set_slice_elements(size_t elements) { chain_set_slice_elements(elements); return KH_OK; }
 
 // ---------------------------------------------------------------------------------- NTT
 int kh_domain_generator(int field, unsigned log2_n, uint64_t out[4]) {

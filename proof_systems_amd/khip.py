@@ -717,6 +717,58 @@ def poseidon_set_split_max_n(n: int = 43008):
     _check(_lib.kh_poseidon_set_split_max_n(n))
 
 
+def _rows32(rows):
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.uint32)
+    return r, (r.ctypes.data_as(C.POINTER(C.c_uint32)) if r is not None else None)
+
+
+def _ptr(buf):
+    return C.c_void_p(buf.ptr if buf is not None else 0)
+
+
+def complete_add_witness_dev(field: int, p1, p2, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0, row_stride: int = 1, out=None):
+    """kh_complete_add_witness_dev: the CompleteAdd row of n pairs of affine points (n x 8 limbs at p1, p2) into the 15 columns at `witness`, instance i at
+    row rows[i] or row0 + i * row_stride; out (nullable): the n sums."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_complete_add_witness_dev(field, _ptr(p1), _ptr(p2), n, rp, row0, row_stride, _ptr(witness), col_stride, col_len, _ptr(out)))
+
+
+def varbasemul_witness_dev(field: int, base, acc0, scalars, num_bits: int, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0,
+                           row_stride: int = None, out_acc=None, out_n=None, flags=None, bit: int = 0):
+    """kh_varbasemul_witness_dev: the 2 * num_bits / 5 VarBaseMul rows of n scalar multiplications (base, acc0: n x 8 limbs; scalars: n x 4 canonical
+    limbs, bits num_bits - 1 .. 0); out_acc / out_n (nullable): the final accumulators / n; flags (a DevBuf holding a zeroed uint32) gets bit `bit` set
+    when an instance met a zero denominator."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_varbasemul_witness_dev(field, _ptr(base), _ptr(acc0), _ptr(scalars), num_bits, n, rp, row0,
+                                          2 * num_bits // 5 if row_stride is None else row_stride, _ptr(witness), col_stride, col_len, _ptr(out_acc),
+                                          _ptr(out_n), _ptr(flags), bit))
+
+
+def endomul_witness_dev(field: int, endo, base, acc0, chals, num_bits: int, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0,
+                        row_stride: int = None, out_acc=None, out_n=None, flags=None, bit: int = 0):
+    """kh_endomul_witness_dev: the num_bits / 4 EndoMul rows + the closing row of n endo-scaled multiplications (endo: 4 Montgomery limbs, endos(curve)[0]
+    of the curve whose base field is `field`; chals: n x 2 canonical limbs); outputs and flags as varbasemul_witness_dev."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_endomul_witness_dev(field, _p64(_c64(endo, (4,))), _ptr(base), _ptr(acc0), _ptr(chals), num_bits, n, rp, row0,
+                                       num_bits // 4 + 1 if row_stride is None else row_stride, _ptr(witness), col_stride, col_len, _ptr(out_acc),
+                                       _ptr(out_n), _ptr(flags), bit))
+
+
+def curve_witness_set_slice_elements(elements: int = 0):
+    """kh_curve_witness_set_slice_elements: the batch-inversion length that bounds a slice of varbasemul_witness_dev / endomul_witness_dev (0: the default, 2^22)"""
+    _check(_lib.kh_curve_witness_set_slice_elements(elements))
+
+
+def endomul_scalar_witness_dev(field: int, chals, num_bits: int, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0,
+                               row_stride: int = None, endo_scalar=None, out=None):
+    """kh_endomul_scalar_witness_dev: the num_bits / 16 EndoMulScalar rows of n challenges (n x 2 canonical limbs); out (nullable, needs endo_scalar:
+    4 Montgomery limbs): the n scalars a * endo_scalar + b."""
+    _r, rp = _rows32(rows)
+    es = None if endo_scalar is None else _c64(endo_scalar, (4,))
+    _check(_lib.kh_endomul_scalar_witness_dev(field, _ptr(chals), num_bits, n, rp, row0, num_bits // 16 if row_stride is None else row_stride,
+                                              _ptr(witness), col_stride, col_len, _p64(es) if es is not None else None, _ptr(out)))
+
+
 class Comm:
     """kh_comm_*: the in-library RCCL communicator of the one-process-per-GPU deployment (no torch).  Comm.unique_id() on one rank, the bytes to
     the others, Comm(world, rank, id) on every rank."""
