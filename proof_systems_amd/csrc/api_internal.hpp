@@ -84,26 +84,45 @@ int wait_then_finish(std::unique_lock<std::mutex>& lk, Context& C, MsmSlot& S, u
 double last_wait_us();           // spin / block part of the last wait_then_finish on this thread
 // vector_api.cpp
 void xfer_trim(int d);
+// Blocks of the kh_dev_alloc pool that go back to it when the call returns (work queued on the main stream before that precedes their next use).
+struct PoolBlock {
+    void* p = nullptr;
+    ~PoolBlock() { if (p) (void)kh_dev_free(p); }
+    template <class T> T* as() const { return (T*)p; }
+};
+// Where instance i of a gadget lands in the 15 witness columns (kh_poseidon_gate_witness_dev and the curve gates' kh_*_witness_dev): it starts at row
+// rows[i], or row0 + i row_stride when rows is null; column c of the witness starts at witness + 4 c col_stride.  The entry points validate it against
+// col_len (vector_api.cpp: place_validate) and hand it on with `rows` on the device; the kernels take it by value.
+struct WitnessPlace {
+    const uint32_t* rows;
+    size_t row0, row_stride;
+    uint64_t* witness;
+    size_t col_stride;
+    __host__ __device__ size_t start_row(size_t i) const { return rows ? (size_t)rows[i] : row0 + i * row_stride; }
+    __host__ __device__ size_t offset(size_t r, size_t c) const { return 4 * (c * col_stride + r); }                  // words from a cell to the one r rows down, c columns on
+    __host__ __device__ uint64_t* cell(size_t r, size_t c) const { return witness + offset(r, c); }                  // column c at row r
+};
+// Both files launch one lane per instance in blocks of ONE wave: a circuit's worth of instances is a few waves (5461 Poseidon gadgets in 2^16 rows: 86
+// waves for 1024 SIMDs), which spread over the CUs only in blocks that small.  Up to WAVE_BLOCK_MAX_N instances per call the grid stays inside 31 bits.
+static constexpr int WAVE_BLOCK = 64;
+static constexpr size_t WAVE_BLOCK_MAX_N = (size_t)1 << 36;
+inline dim3 blocks_of(size_t n, size_t per) { return dim3((unsigned)((n + per - 1) / per)); }      // the grid of n lanes in blocks of `per`
 // poseidon.hip: the launchers of kh_poseidon_*_dev, queued on C.stream (arguments validated by the entry points; n >= 1)
-static constexpr size_t POSEIDON_MAX_N = (size_t)1 << 36;      // one-wave blocks: the grid stays inside 31 bits
 int poseidon_permute(Context& C, int field, uint64_t* states_dev, size_t n);
 int poseidon_hash(Context& C, int field, const uint64_t* msgs_dev, size_t msg_len, size_t n, const uint64_t* init, uint64_t* digests_dev);
-int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride,
-                       uint64_t* witness_dev, size_t col_stride, uint64_t* out_states_dev);
+int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const WitnessPlace& at, uint64_t* out_states_dev);
 void poseidon_set_split_max_n(size_t n);
 // curve_gadgets.hip: the launchers of kh_complete_add_witness_dev, kh_endomul_scalar_witness_dev, kh_varbasemul_witness_dev and kh_endomul_witness_dev,
 // queued on C.stream (arguments validated by the entry points; n >= 1).  chain_rows (VarBaseMul, or EndoMul with is_endo) works through the batch in
 // slices over a scratch block of chain_scratch_bytes (chain_slice instances; the knob kh_curve_witness_set_slice_elements may move between the
 // entry point's question and the launch, so the launcher is told what it got), which the entry point takes from the kh_dev_alloc pool.
-static constexpr size_t GADGET_MAX_N = (size_t)1 << 36;        // one-wave blocks: the grid stays inside 31 bits
-int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows_dev, size_t row0,
-                      size_t row_stride, uint64_t* witness_dev, size_t col_stride, uint64_t* out_dev);
-int endomul_scalar_rows(Context& C, int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0,
-                        size_t row_stride, uint64_t* witness_dev, size_t col_stride, const uint64_t* endo_scalar, uint64_t* out_dev);
+int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const WitnessPlace& at, uint64_t* out_dev);
+int endomul_scalar_rows(Context& C, int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const WitnessPlace& at, const uint64_t* endo_scalar,
+                        uint64_t* out_dev);
 size_t chain_slice(bool is_endo, unsigned num_bits, size_t n);
 size_t chain_scratch_bytes(bool is_endo, unsigned num_bits, size_t n);
 int chain_rows(Context& C, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev,
-               unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride,
-               uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit, uint64_t* scratch_dev, size_t scratch_bytes);
+               unsigned num_bits, size_t n, const WitnessPlace& at, uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit,
+               uint64_t* scratch_dev, size_t scratch_bytes);
 void chain_set_slice_elements(size_t elems);
 }  // namespace kh

@@ -216,3 +216,14 @@ std::atomic<uint64_t>& counter(CounterId id);
 int exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, DevBuf& tmp, hipStream_t s);
 
 }  // namespace kh
+
+// How a field id selects a kernel instantiation, for every launch that is keyed by the FIELD (the MSM side is keyed by the curve: msm.hip, rebase.hip,
+// lagrange.hip).  KERNEL names the instantiation with F for the field's parameters, in parentheses when it holds a comma:
+//     KH_FIELD_LAUNCH(field, k_lincomb<F>, grid, block, 0, s, args...);      KH_FIELD_LAUNCH(field, (k_chain<F, true>), ...);
+// The arguments are written once; a launch that fails returns KH_E_DEVICE from the calling function, like KH_HIP.
+#define KH_FIELD_LAUNCH(field, KERNEL, grid, block, lds, stream, ...)                                                        \
+    do {                                                                                                                     \
+        if ((field) == KH_FIELD_FP) { using F = kh::FpParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); } \
+        else { using F = kh::FqParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); }               \
+        KH_HIP(hipGetLastError());                                                                                           \
+    } while (0)

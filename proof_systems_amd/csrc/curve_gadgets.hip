@@ -11,6 +11,7 @@
 //   (poly_batch_inversion over all D and E of the slice: two scans and one inversion on the host; zeros stay zero)
 //   k_varbasemul_cells,
 //   k_endomul_cells       one lane per (step, instance): the affine accumulator, the slope and the bits into their cells
+// The four kernels that write witness cells take where the instances land as one WitnessPlace (api_internal.hpp): at.start_row(i), at.cell(row, column).
 //
 // The reference inverts twice per bit (s1, s2); s2 is never written, and acc' = (acc + Q) + acc does not need it.  No lane of these kernels has a
 // Fermat inversion on its chain but k_complete_add's one: the chain of a 255-bit VarBaseMul is 255 x (madd + add + 2) = 6630 products instead of
@@ -23,7 +24,6 @@
 namespace kh {
 
 struct GadgetConst { u64 l[4]; };
-static constexpr int GADGET_BLOCK = 64;          // one wave per block: a circuit's worth of instances is a few waves, which spread over the CUs only so
 static constexpr int CELLS_BLOCK = 256;
 
 template <class F>
@@ -33,10 +33,6 @@ __device__ __forceinline__ Fe<F> sel(bool c, const Fe<F>& a, const Fe<F>& b) {
     for (int i = 0; i < 8; i++) r.v[i] = c ? a.v[i] : b.v[i];
     return r;
 }
-// column c of row `row`
-__device__ __forceinline__ u64* cell(u64* witness, size_t col_stride, size_t row, size_t c) { return witness + 4 * (c * col_stride + row); }
-__device__ __forceinline__ size_t start_row(const u32* rows, size_t row0, size_t row_stride, size_t i) { return rows ? (size_t)rows[i] : row0 + i * row_stride; }
-
 // bit `pos` of a little-endian scalar of u64 words
 __device__ __forceinline__ bool scalar_bit(const u64* s, unsigned pos) { return (s[pos >> 6] >> (pos & 63)) & 1; }
 // ((s mod 2^num_bits) >> sh) mod p as a Montgomery element: the running n of the gates (NW words, num_bits <= 64 NW, sh <= num_bits <= 255, value < 2^255 < 2 p)
@@ -81,10 +77,9 @@ __device__ __forceinline__ Fe<F> inv_inlined(const Fe<F>& a) {
 // complete_add_witness: cells 0..10 = x1 y1 x2 y2 x3 y3 inf same_x s inf_z x21_inv.  The denominators: x2 - x1 (generic), 2 y1 (same x), and
 // y2 - y1 as well for P + (-P) -- inverted together, 1 / (d1 d2) times the other one.
 template <class F>
-__global__ void __launch_bounds__(GADGET_BLOCK)
-k_complete_add(const u64* __restrict__ p1, const u64* __restrict__ p2, size_t n, const u32* __restrict__ rows, size_t row0, size_t row_stride,
-               u64* __restrict__ witness, size_t col_stride, u64* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * GADGET_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_complete_add(const u64* __restrict__ p1, const u64* __restrict__ p2, size_t n, WitnessPlace at, u64* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= n) return;
     const Aff<F> a = Aff<F>::load(p1 + 8 * i), b = Aff<F>::load(p2 + 8 * i);
     const Fe<F> dx = sub<F>(b.x, a.x), dy = sub<F>(b.y, a.y);
@@ -96,35 +91,34 @@ k_complete_add(const u64* __restrict__ p1, const u64* __restrict__ p2, size_t n,
     const Fe<F> s = mul<F>(sel<F>(same_x, add<F>(dbl<F>(xx), xx), dy), i1);
     const Fe<F> x3 = sub<F>(sub<F>(sqr<F>(s), a.x), b.x);
     const Fe<F> y3 = sub<F>(mul<F>(s, sub<F>(a.x, x3)), a.y);
-    const size_t r = start_row(rows, row0, row_stride, i);
+    const size_t r = at.start_row(i);
     const Fe<F> zero = Fe<F>::zero(), one = Fe<F>::one();
-    a.x.store(cell(witness, col_stride, r, 0)); a.y.store(cell(witness, col_stride, r, 1));
-    b.x.store(cell(witness, col_stride, r, 2)); b.y.store(cell(witness, col_stride, r, 3));
-    x3.store(cell(witness, col_stride, r, 4)); y3.store(cell(witness, col_stride, r, 5));
-    sel<F>(opposite, one, zero).store(cell(witness, col_stride, r, 6));
-    sel<F>(same_x, one, zero).store(cell(witness, col_stride, r, 7));
-    s.store(cell(witness, col_stride, r, 8));
-    sel<F>(opposite, i2, zero).store(cell(witness, col_stride, r, 9));
-    sel<F>(same_x, zero, i1).store(cell(witness, col_stride, r, 10));
+    a.x.store(at.cell(r, 0)); a.y.store(at.cell(r, 1));
+    b.x.store(at.cell(r, 2)); b.y.store(at.cell(r, 3));
+    x3.store(at.cell(r, 4)); y3.store(at.cell(r, 5));
+    sel<F>(opposite, one, zero).store(at.cell(r, 6));
+    sel<F>(same_x, one, zero).store(at.cell(r, 7));
+    s.store(at.cell(r, 8));
+    sel<F>(opposite, i2, zero).store(at.cell(r, 9));
+    sel<F>(same_x, zero, i1).store(at.cell(r, 10));
     if (out) { x3.store(out + 8 * i); y3.store(out + 8 * i + 4); }
 }
 
 // -------------------------------------------------------------------------------------------------------- EndoMulScalar
 // endomul_scalar gen_witness: 8 crumbs per row, most significant first; cells 0..13 = n0 n8 a0 b0 a8 b8 x0..x7
 template <class F>
-__global__ void __launch_bounds__(GADGET_BLOCK)
-k_endomul_scalar(const u64* __restrict__ chals, unsigned num_bits, size_t n, const u32* __restrict__ rows, size_t row0, size_t row_stride,
-                 u64* __restrict__ witness, size_t col_stride, GadgetConst endo_scalar, u64* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * GADGET_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_endomul_scalar(const u64* __restrict__ chals, unsigned num_bits, size_t n, WitnessPlace at, GadgetConst endo_scalar, u64* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= n) return;
     const u64* const sc = chals + 2 * i;
     const Fe<F> zero = Fe<F>::zero(), one = Fe<F>::one(), minus_one = neg<F>(one), two = dbl<F>(one), three = add<F>(two, one);
     Fe<F> a = two, b = two, nacc = zero;
-    size_t r = start_row(rows, row0, row_stride, i);
+    size_t r = at.start_row(i);
     unsigned pos = num_bits;                          // the next bit is pos - 1
 #pragma unroll 1
     for (unsigned row = 0; row < num_bits / 16; row++, r++) {
-        nacc.store(cell(witness, col_stride, r, 0)); a.store(cell(witness, col_stride, r, 2)); b.store(cell(witness, col_stride, r, 3));
+        nacc.store(at.cell(r, 0)); a.store(at.cell(r, 2)); b.store(at.cell(r, 3));
 #pragma unroll 1
         for (unsigned j = 0; j < 8; j++) {
             const bool b1 = scalar_bit(sc, pos - 1), b0 = scalar_bit(sc, pos - 2);
@@ -135,9 +129,9 @@ k_endomul_scalar(const u64* __restrict__ chals, unsigned num_bits, size_t n, con
             const Fe<F> a1 = add<F>(a, sgn), b1v = add<F>(b, sgn);
             a = sel<F>(b1, a1, a); b = sel<F>(b1, b, b1v);
             nacc = add<F>(dbl<F>(dbl<F>(nacc)), crumb);
-            crumb.store(cell(witness, col_stride, r, 6 + j));
+            crumb.store(at.cell(r, 6 + j));
         }
-        nacc.store(cell(witness, col_stride, r, 1)); a.store(cell(witness, col_stride, r, 4)); b.store(cell(witness, col_stride, r, 5));
+        nacc.store(at.cell(r, 1)); a.store(at.cell(r, 4)); b.store(at.cell(r, 5));
     }
     if (out) add<F>(mul<F>(a, Fe<F>::load(endo_scalar.l)), b).store(out + 4 * i);
 }
@@ -153,10 +147,10 @@ struct ChainScratch { u64 *x, *y, *zz, *zzz, *den; };
 // with per-lane selects, and madd always adds (negate = false): no call is divergent.  The exceptional branches of madd / add are taken by degenerate
 // instances only.
 template <class F, bool ENDO>
-__global__ void __launch_bounds__(GADGET_BLOCK)
+__global__ void __launch_bounds__(WAVE_BLOCK)
 k_chain(const u64* __restrict__ base, const u64* __restrict__ acc0, const u64* __restrict__ scalars, unsigned num_bits, size_t m, GadgetConst endo,
         ChainScratch S) {
-    const size_t i = (size_t)blockIdx.x * GADGET_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= m) return;
     constexpr int NW = ENDO ? 4 : 8;                  // 32-bit words of a scalar
     u32 w[8];
@@ -233,8 +227,7 @@ __device__ __forceinline__ Entry<F> entry_values(const ChainScratch& S, size_t a
 template <class F>
 __global__ void __launch_bounds__(CELLS_BLOCK)
 k_varbasemul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __restrict__ scalars, unsigned num_bits, size_t m,
-                   const u32* __restrict__ rows, size_t row0, size_t row_stride, size_t first, u64* __restrict__ witness, size_t col_stride,
-                   u64* __restrict__ out_acc, u64* __restrict__ out_n, u32* __restrict__ flags, u32 bit) {
+                   WitnessPlace at, size_t first, u64* __restrict__ out_acc, u64* __restrict__ out_n, u32* __restrict__ flags, u32 bit) {
     const size_t t = (size_t)blockIdx.x * CELLS_BLOCK + threadIdx.x;
     bool degenerate = false;
     if (t < ((size_t)num_bits + 1) * m) {
@@ -245,19 +238,19 @@ k_varbasemul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __re
         const Aff<F> T = Aff<F>::load(base + 8 * i);
         const Entry<F> e = entry_values<F>(S, 4 * t, last, T.x, sel<F>(b, T.y, neg<F>(T.y)));
         degenerate = e.degenerate;
-        const size_t c = j / 5, k = j - 5 * c, r0 = start_row(rows, row0, row_stride, first + i) + 2 * c;
+        const size_t c = j / 5, k = j - 5 * c, r0 = at.start_row(first + i) + 2 * c;
         if (!last) {
             const size_t xc = k == 0 ? 2 : 5 + 2 * k;
-            e.x.store(cell(witness, col_stride, r0, xc)); e.y.store(cell(witness, col_stride, r0, xc + 1));
-            sel<F>(b, Fe<F>::one(), Fe<F>::zero()).store(cell(witness, col_stride, r0 + 1, 2 + k));
-            e.s.store(cell(witness, col_stride, r0 + 1, 7 + k));
+            e.x.store(at.cell(r0, xc)); e.y.store(at.cell(r0, xc + 1));
+            sel<F>(b, Fe<F>::one(), Fe<F>::zero()).store(at.cell(r0 + 1, 2 + k));
+            e.s.store(at.cell(r0 + 1, 7 + k));
             if (k == 0) {
-                T.x.store(cell(witness, col_stride, r0, 0)); T.y.store(cell(witness, col_stride, r0, 1));
-                scalar_prefix<F, 4>(sc, num_bits, num_bits - (unsigned)j).store(cell(witness, col_stride, r0, 4));
-                scalar_prefix<F, 4>(sc, num_bits, num_bits - (unsigned)j - 5).store(cell(witness, col_stride, r0, 5));
+                T.x.store(at.cell(r0, 0)); T.y.store(at.cell(r0, 1));
+                scalar_prefix<F, 4>(sc, num_bits, num_bits - (unsigned)j).store(at.cell(r0, 4));
+                scalar_prefix<F, 4>(sc, num_bits, num_bits - (unsigned)j - 5).store(at.cell(r0, 5));
             }
         }
-        if (k == 0 && j > 0) { e.x.store(cell(witness, col_stride, r0 - 1, 0)); e.y.store(cell(witness, col_stride, r0 - 1, 1)); }
+        if (k == 0 && j > 0) { e.x.store(at.cell(r0 - 1, 0)); e.y.store(at.cell(r0 - 1, 1)); }
         if (last) {
             if (out_acc) { e.x.store(out_acc + 8 * (first + i)); e.y.store(out_acc + 8 * (first + i) + 4); }
             if (out_n) scalar_prefix<F, 4>(sc, num_bits, 0).store(out_n + 4 * (first + i));
@@ -271,8 +264,7 @@ k_varbasemul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __re
 template <class F>
 __global__ void __launch_bounds__(CELLS_BLOCK)
 k_endomul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __restrict__ chals, unsigned num_bits, size_t m, GadgetConst endo,
-                const u32* __restrict__ rows, size_t row0, size_t row_stride, size_t first, u64* __restrict__ witness, size_t col_stride,
-                u64* __restrict__ out_acc, u64* __restrict__ out_n, u32* __restrict__ flags, u32 bit) {
+                WitnessPlace at, size_t first, u64* __restrict__ out_acc, u64* __restrict__ out_n, u32* __restrict__ flags, u32 bit) {
     const size_t t = (size_t)blockIdx.x * CELLS_BLOCK + threadIdx.x;
     const size_t entries = num_bits / 2 + 1;
     bool degenerate = false;
@@ -286,24 +278,24 @@ k_endomul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __restr
         const Fe<F> qx = bx ? mul<F>(Fe<F>::load(endo.l), T.x) : T.x;
         const Entry<F> e = entry_values<F>(S, 4 * t, last, qx, sel<F>(by, T.y, neg<F>(T.y)));
         degenerate = e.degenerate;
-        const size_t r = start_row(rows, row0, row_stride, first + i) + h / 2;
+        const size_t r = at.start_row(first + i) + h / 2;
         const Fe<F> zero = Fe<F>::zero(), one = Fe<F>::one();
         if (h & 1) {
-            e.x.store(cell(witness, col_stride, r, 7)); e.y.store(cell(witness, col_stride, r, 8)); e.s.store(cell(witness, col_stride, r, 10));
+            e.x.store(at.cell(r, 7)); e.y.store(at.cell(r, 8)); e.s.store(at.cell(r, 10));
             const Fe<F> einv = Fe<F>::load(S.den + 4 * (entries * m + (h / 2) * m + i));
             degenerate |= einv.is_zero();
             const Fe<F> zp = Fe<F>::load(S.zz + 4 * (t - m)), zr = Fe<F>::load(S.zz + 4 * t), zs = Fe<F>::load(S.zz + 4 * (t + m));
-            mul<F>(mul<F>(einv, sqr<F>(zr)), mul<F>(zp, zs)).store(cell(witness, col_stride, r, 2));
+            mul<F>(mul<F>(einv, sqr<F>(zr)), mul<F>(zp, zs)).store(at.cell(r, 2));
         } else {
-            T.x.store(cell(witness, col_stride, r, 0)); T.y.store(cell(witness, col_stride, r, 1));
-            e.x.store(cell(witness, col_stride, r, 4)); e.y.store(cell(witness, col_stride, r, 5));
+            T.x.store(at.cell(r, 0)); T.y.store(at.cell(r, 1));
+            e.x.store(at.cell(r, 4)); e.y.store(at.cell(r, 5));
             const Fe<F> nacc = scalar_prefix<F, 2>(sc, num_bits, num_bits - 2 * (unsigned)h);
-            nacc.store(cell(witness, col_stride, r, 6));
+            nacc.store(at.cell(r, 6));
             if (!last) {
-                e.s.store(cell(witness, col_stride, r, 9));
-                sel<F>(bx, one, zero).store(cell(witness, col_stride, r, 11)); sel<F>(by, one, zero).store(cell(witness, col_stride, r, 12));
-                sel<F>(scalar_bit(sc, top - 2), one, zero).store(cell(witness, col_stride, r, 13));
-                sel<F>(scalar_bit(sc, top - 3), one, zero).store(cell(witness, col_stride, r, 14));
+                e.s.store(at.cell(r, 9));
+                sel<F>(bx, one, zero).store(at.cell(r, 11)); sel<F>(by, one, zero).store(at.cell(r, 12));
+                sel<F>(scalar_bit(sc, top - 2), one, zero).store(at.cell(r, 13));
+                sel<F>(scalar_bit(sc, top - 3), one, zero).store(at.cell(r, 14));
             } else {
                 if (out_acc) { e.x.store(out_acc + 8 * (first + i)); e.y.store(out_acc + 8 * (first + i) + 4); }
                 if (out_n) nacc.store(out_n + 4 * (first + i));
@@ -313,38 +305,20 @@ k_endomul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __restr
     if (flags && __any(degenerate) && (threadIdx.x & 63u) == 0) atomicOr(flags, 1u << bit);
 }
 
-#define KH_GADGET_LAUNCH(KERNEL, grid, block, C, ...)                                                                         \
-    do {                                                                                                                      \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), dim3((unsigned)(grid)), dim3(block), 0, C.stream, __VA_ARGS__);       \
-        else hipLaunchKernelGGL((KERNEL<FqParams>), dim3((unsigned)(grid)), dim3(block), 0, C.stream, __VA_ARGS__);                             \
-        KH_HIP(hipGetLastError());                                                                                            \
-    } while (0)
-#define KH_GADGET_LAUNCH2(KERNEL, FLAG, grid, block, C, ...)                                                                  \
-    do {                                                                                                                      \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams, FLAG>), dim3((unsigned)(grid)), dim3(block), 0, C.stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<FqParams, FLAG>), dim3((unsigned)(grid)), dim3(block), 0, C.stream, __VA_ARGS__);                       \
-        KH_HIP(hipGetLastError());                                                                                            \
-    } while (0)
-
-static size_t blocks_of(size_t n, size_t per) { return (n + per - 1) / per; }
-
-// (the callers in vector_api.cpp have validated pointers and sizes: n <= GADGET_MAX_N keeps the grids inside 31 bits; the phases of kh_last_timings
+// (the callers in vector_api.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grids inside 31 bits; the phases of kh_last_timings
 // are complete_add, endomul_scalar and, per slice, chain, denominators, cells)
-int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows_dev, size_t row0,
-                      size_t row_stride, uint64_t* witness_dev, size_t col_stride, uint64_t* out_dev) {
+int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const WitnessPlace& at, uint64_t* out_dev) {
     C.timer.begin(C.stream);
-    KH_GADGET_LAUNCH(k_complete_add, blocks_of(n, GADGET_BLOCK), GADGET_BLOCK, C, (const u64*)p1_dev, (const u64*)p2_dev, n, rows_dev, row0, row_stride,
-                     (u64*)witness_dev, col_stride, (u64*)out_dev);
+    KH_FIELD_LAUNCH(field, k_complete_add<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, p1_dev, p2_dev, n, at, out_dev);
     C.timer.mark("complete_add", C.stream);
     return KH_OK;
 }
-int endomul_scalar_rows(Context& C, int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0,
-                        size_t row_stride, uint64_t* witness_dev, size_t col_stride, const uint64_t* endo_scalar, uint64_t* out_dev) {
+int endomul_scalar_rows(Context& C, int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const WitnessPlace& at, const uint64_t* endo_scalar,
+                        uint64_t* out_dev) {
     GadgetConst es; memset(&es, 0, sizeof(es));
     if (endo_scalar) memcpy(es.l, endo_scalar, 32);
     C.timer.begin(C.stream);
-    KH_GADGET_LAUNCH(k_endomul_scalar, blocks_of(n, GADGET_BLOCK), GADGET_BLOCK, C, (const u64*)chals_dev, num_bits, n, rows_dev, row0, row_stride,
-                     (u64*)witness_dev, col_stride, es, (u64*)out_dev);
+    KH_FIELD_LAUNCH(field, k_endomul_scalar<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, chals_dev, num_bits, n, at, es, out_dev);
     C.timer.mark("endomul_scalar", C.stream);
     return KH_OK;
 }
@@ -358,15 +332,15 @@ static size_t chain_entries(bool endo, unsigned num_bits) { return endo ? num_bi
 static size_t chain_inversions(bool endo, unsigned num_bits) { return chain_entries(endo, num_bits) + (endo ? num_bits / 4 : 0); }
 size_t chain_slice(bool endo, unsigned num_bits, size_t n) {
     size_t m = g_slice_elems.load(std::memory_order_relaxed) / chain_inversions(endo, num_bits);
-    if (m > GADGET_BLOCK) m -= m % GADGET_BLOCK;
+    if (m > WAVE_BLOCK) m -= m % WAVE_BLOCK;
     return std::min(n, std::max<size_t>(m, 1));
 }
 size_t chain_scratch_bytes(bool endo, unsigned num_bits, size_t n) {
     return 32 * chain_slice(endo, num_bits, n) * (4 * chain_entries(endo, num_bits) + chain_inversions(endo, num_bits));
 }
 int chain_rows(Context& C, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev,
-               unsigned num_bits, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride,
-               uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit, uint64_t* scratch_dev, size_t scratch_bytes) {
+               unsigned num_bits, size_t n, const WitnessPlace& at, uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit,
+               uint64_t* scratch_dev, size_t scratch_bytes) {
     GadgetConst en; memset(&en, 0, sizeof(en));
     if (endo) memcpy(en.l, endo, 32);
     const size_t slice = std::min(chain_slice(is_endo, num_bits, n), scratch_bytes / (32 * (4 * chain_entries(is_endo, num_bits) + chain_inversions(is_endo, num_bits))));
@@ -377,19 +351,20 @@ int chain_rows(Context& C, int field, bool is_endo, const uint64_t* endo, const 
         ChainScratch S;
         S.x = (u64*)scratch_dev; S.y = S.x + plane; S.zz = S.y + plane; S.zzz = S.zz + plane; S.den = S.zzz + plane;
         const u64 *b = (const u64*)base_dev + 8 * first, *a = (const u64*)acc0_dev + 8 * first, *s = (const u64*)scalars_dev + words * first;
-        if (is_endo) KH_GADGET_LAUNCH2(k_chain, true, blocks_of(m, GADGET_BLOCK), GADGET_BLOCK, C, b, a, s, num_bits, m, en, S);
-        else KH_GADGET_LAUNCH2(k_chain, false, blocks_of(m, GADGET_BLOCK), GADGET_BLOCK, C, b, a, s, num_bits, m, en, S);
-        if (is_endo) KH_GADGET_LAUNCH(k_endo_inv_denoms, blocks_of((num_bits / 4) * m, CELLS_BLOCK), CELLS_BLOCK, C, S, m, (size_t)(num_bits / 4), entries);
+        if (is_endo) {
+            KH_FIELD_LAUNCH(field, (k_chain<F, true>), blocks_of(m, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, b, a, s, num_bits, m, en, S);
+            KH_FIELD_LAUNCH(field, k_endo_inv_denoms<F>, blocks_of((num_bits / 4) * m, CELLS_BLOCK), dim3(CELLS_BLOCK), 0, C.stream, S, m, (size_t)(num_bits / 4), entries);
+        } else KH_FIELD_LAUNCH(field, (k_chain<F, false>), blocks_of(m, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, b, a, s, num_bits, m, en, S);
         C.timer.mark("chain", C.stream);
         int rc = poly_batch_inversion(C, field, (uint64_t*)S.den, chain_inversions(is_endo, num_bits) * m);
         if (rc) return rc;
         C.timer.mark("denominators", C.stream);
         if (is_endo)
-            KH_GADGET_LAUNCH(k_endomul_cells, blocks_of(entries * m, CELLS_BLOCK), CELLS_BLOCK, C, S, b, s, num_bits, m, en, rows_dev, row0, row_stride, first,
-                             (u64*)witness_dev, col_stride, (u64*)out_acc_dev, (u64*)out_n_dev, flags_dev, (u32)bit);
+            KH_FIELD_LAUNCH(field, k_endomul_cells<F>, blocks_of(entries * m, CELLS_BLOCK), dim3(CELLS_BLOCK), 0, C.stream, S, b, s, num_bits, m, en, at, first,
+                            out_acc_dev, out_n_dev, flags_dev, (u32)bit);
         else
-            KH_GADGET_LAUNCH(k_varbasemul_cells, blocks_of(entries * m, CELLS_BLOCK), CELLS_BLOCK, C, S, b, s, num_bits, m, rows_dev, row0, row_stride, first,
-                             (u64*)witness_dev, col_stride, (u64*)out_acc_dev, (u64*)out_n_dev, flags_dev, (u32)bit);
+            KH_FIELD_LAUNCH(field, k_varbasemul_cells<F>, blocks_of(entries * m, CELLS_BLOCK), dim3(CELLS_BLOCK), 0, C.stream, S, b, s, num_bits, m, at, first,
+                            out_acc_dev, out_n_dev, flags_dev, (u32)bit);
         C.timer.mark("cells", C.stream);
     }
     return KH_OK;

@@ -136,13 +136,8 @@ int expr_run(Context& C, int field, const uint32_t* prog, size_t ntok, const uin
     }
     dim3 grid((unsigned)((rows + EXPR_T - 1) / EXPR_T));
     C.timer.begin(s);
-    if (field == KH_FIELD_FP)
-        hipLaunchKernelGGL((k_expr<FpParams>), grid, dim3(EXPR_T), lds, s, (const u32*)d_prog, (u32)ntok, (const u64* const*)d_cols, (const u64*)d_len,
-                           (const u64*)d_consts, rows, (u32)stride, (u32)next_shift, slots, accumulate, nowrap, out_dev);
-    else
-        hipLaunchKernelGGL((k_expr<FqParams>), grid, dim3(EXPR_T), lds, s, (const u32*)d_prog, (u32)ntok, (const u64* const*)d_cols, (const u64*)d_len,
-                           (const u64*)d_consts, rows, (u32)stride, (u32)next_shift, slots, accumulate, nowrap, out_dev);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_expr<F>, grid, dim3(EXPR_T), lds, s, (const u32*)d_prog, (u32)ntok, (const u64* const*)d_cols, (const u64*)d_len,
+                    (const u64*)d_consts, rows, (u32)stride, (u32)next_shift, slots, accumulate, nowrap, out_dev);
     C.timer.mark("expr", s);
     return KH_OK;                 // asynchronous on the main stream, like kh_ntt_dev
 }

@@ -162,15 +162,11 @@ int gate_run(Context& C, int field, int gate, const uint64_t* const* cols_dev, s
     dim3 grid((unsigned)((rows + 127) / 128));
     C.timer.begin(s);
     switch (gate) {
-#define KH_GATE_LAUNCH(ID, NAME)                                                                                           \
-        case ID:                                                                                                               \
-            if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_gate_##NAME<FpParams>), grid, dim3(128), 0, s, a);                 \
-            else hipLaunchKernelGGL((k_gate_##NAME<FqParams>), grid, dim3(128), 0, s, a);                                      \
-            break;
-        KH_FOR_EACH_GATE(KH_GATE_LAUNCH)
+#define KH_GATE_CASE(ID, NAME) case ID: KH_FIELD_LAUNCH(field, k_gate_##NAME<F>, grid, dim3(128), 0, s, a); break;
+        KH_FOR_EACH_GATE(KH_GATE_CASE)
+#undef KH_GATE_CASE
         default: break;
     }
-    KH_HIP(hipGetLastError());
     C.timer.mark("gate", s);
     return KH_OK;
 }
@@ -214,15 +210,11 @@ int gate_batch_run(Context& C, int field, const uint64_t* cols_host, size_t ncol
         a.cols[30] = base + (size_t)launches[l].selector_col * 2 * items * 4;
         a.consts = base + tab_off[l]; a.items = items; a.nconst = GATE_NCONST[launches[l].gate]; a.accumulate = l > 0; a.out = out_dev;
         switch (launches[l].gate) {
-#define KH_GATE_BATCH_LAUNCH(ID, NAME)                                                                                     \
-            case ID:                                                                                                           \
-                if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_gate_batch_##NAME<FpParams>), grid, dim3(128), 0, s, a);       \
-                else hipLaunchKernelGGL((k_gate_batch_##NAME<FqParams>), grid, dim3(128), 0, s, a);                            \
-                break;
-            KH_FOR_EACH_CHECKED_GATE(KH_GATE_BATCH_LAUNCH)
+#define KH_GATE_BATCH_CASE(ID, NAME) case ID: KH_FIELD_LAUNCH(field, k_gate_batch_##NAME<F>, grid, dim3(128), 0, s, a); break;
+            KH_FOR_EACH_CHECKED_GATE(KH_GATE_BATCH_CASE)
+#undef KH_GATE_BATCH_CASE
             default: break;
         }
-        KH_HIP(hipGetLastError());
     }
     C.timer.mark("gate_batch", s);
     if (cols_dev) *cols_dev = base;

@@ -319,9 +319,7 @@ int ipa_round_step(hipStream_t s, int field, int has_fold, const uint64_t* a, co
     unsigned logN2 = 0; while (((size_t)1 << logN2) < cur2) logN2++;
     Fe4 rl, rr, u4, ui4; memcpy(rl.l, rand_l, 32); memcpy(rr.l, rand_r, 32); memcpy(u4.l, u, 32); memcpy(ui4.l, uinv, 32);
     dim3 g((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_ipa_step<FpParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, extra, ncoef, has_fold, uslot, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
-    else hipLaunchKernelGGL((k_ipa_step<FqParams>), g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, extra, ncoef, has_fold, uslot, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_ipa_step<F>, g, dim3(256), 0, s, a, b, coef, n, cur2, logN2, extra, ncoef, has_fold, uslot, u4, ui4, a2, b2, coef2, rl, rr, sc, partial, counter);
     return KH_OK;
 }
 
@@ -332,16 +330,9 @@ int ipa_round_prepare(hipStream_t s, int field, const uint64_t* a, const uint64_
     const unsigned nblk = (unsigned)std::min<size_t>(64, (m + 255) / 256);
     Fe4 rl, rr; memcpy(rl.l, rand_l, 32); memcpy(rr.l, rand_r, 32);
     dim3 eg((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) {
-        hipLaunchKernelGGL((k_ipa_ip<FpParams>), dim3(nblk, 2), dim3(256), 0, s, a, b, m, partial);
-        hipLaunchKernelGGL((k_ipa_ip_fin<FpParams>), dim3(2), dim3(64), 0, s, partial, nblk, rl, rr, n, sc);
-        hipLaunchKernelGGL((k_ipa_expand<FpParams>), eg, dim3(256), 0, s, a, coef, n, m, logN, sc);
-    } else {
-        hipLaunchKernelGGL((k_ipa_ip<FqParams>), dim3(nblk, 2), dim3(256), 0, s, a, b, m, partial);
-        hipLaunchKernelGGL((k_ipa_ip_fin<FqParams>), dim3(2), dim3(64), 0, s, partial, nblk, rl, rr, n, sc);
-        hipLaunchKernelGGL((k_ipa_expand<FqParams>), eg, dim3(256), 0, s, a, coef, n, m, logN, sc);
-    }
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_ipa_ip<F>, dim3(nblk, 2), dim3(256), 0, s, a, b, m, partial);
+    KH_FIELD_LAUNCH(field, k_ipa_ip_fin<F>, dim3(2), dim3(64), 0, s, partial, nblk, rl, rr, n, sc);
+    KH_FIELD_LAUNCH(field, k_ipa_expand<F>, eg, dim3(256), 0, s, a, coef, n, m, logN, sc);
     return KH_OK;
 }
 int ipa_round_fold(hipStream_t s, int field, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t Nj, size_t ncoef,
@@ -349,9 +340,7 @@ int ipa_round_fold(hipStream_t s, int field, const uint64_t* a, const uint64_t* 
     const size_t m = Nj / 2, thr = std::max(m, ncoef);
     Fe4 u4, ui4; memcpy(u4.l, u, 32); memcpy(ui4.l, uinv, 32);
     dim3 g((unsigned)((thr + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_ipa_fold<FpParams>), g, dim3(256), 0, s, a, b, coef, m, ncoef, u4, ui4, a2, b2, coef2);
-    else hipLaunchKernelGGL((k_ipa_fold<FqParams>), g, dim3(256), 0, s, a, b, coef, m, ncoef, u4, ui4, a2, b2, coef2);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_ipa_fold<F>, g, dim3(256), 0, s, a, b, coef, m, ncoef, u4, ui4, a2, b2, coef2);
     return KH_OK;
 }
 
@@ -373,9 +362,7 @@ __global__ void k_sg_split(const u64* __restrict__ coef, size_t n, int has_fold,
 int ipa_sg_split(hipStream_t s, int field, const uint64_t* coef, size_t n, int has_fold, const uint64_t u[4], uint64_t* out) {
     Fe4 u4; memcpy(u4.l, u, 32);
     dim3 g((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_sg_split<FpParams>), g, dim3(256), 0, s, coef, n, has_fold, u4, out);
-    else hipLaunchKernelGGL((k_sg_split<FqParams>), g, dim3(256), 0, s, coef, n, has_fold, u4, out);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_sg_split<F>, g, dim3(256), 0, s, coef, n, has_fold, u4, out);
     return KH_OK;
 }
 
@@ -401,9 +388,7 @@ __global__ void k_bpoly(const u64* __restrict__ chals, unsigned rounds, size_t k
 }
 int bpoly_run(hipStream_t s, int field, const uint64_t* chals_dev, unsigned rounds, size_t k, const uint64_t* rs_dev, uint64_t* out_dev) {
     dim3 g((unsigned)((((size_t)1 << rounds) + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_bpoly<FpParams>), g, dim3(256), 0, s, chals_dev, rounds, k, rs_dev, out_dev);
-    else hipLaunchKernelGGL((k_bpoly<FqParams>), g, dim3(256), 0, s, chals_dev, rounds, k, rs_dev, out_dev);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_bpoly<F>, g, dim3(256), 0, s, chals_dev, rounds, k, rs_dev, out_dev);
     return KH_OK;
 }
 
@@ -421,9 +406,7 @@ int ipa_fold_scalars(Context& C, int field, const uint64_t* lo, const uint64_t* 
     KH_HIP(hipMemcpyAsync(dhi, hi, n * 32, hipMemcpyHostToDevice, s));
     KH_HIP(hipMemcpyAsync(du, u, 32, hipMemcpyHostToDevice, s));
     dim3 grid((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_fold_scalars<FpParams>), grid, dim3(256), 0, s, dlo, dhi, du, n, g_ipa_b.as<u64>());
-    else hipLaunchKernelGGL((k_fold_scalars<FqParams>), grid, dim3(256), 0, s, dlo, dhi, du, n, g_ipa_b.as<u64>());
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_fold_scalars<F>, grid, dim3(256), 0, s, dlo, dhi, du, n, g_ipa_b.as<u64>());
     KH_HIP(hipMemcpyAsync(out, g_ipa_b.p, n * 32, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));
     return KH_OK;
@@ -437,9 +420,7 @@ int ipa_inner_product(Context& C, int field, const uint64_t* a, const uint64_t* 
     hipStream_t s = C.stream;
     KH_HIP(hipMemcpyAsync(da, a, n * 32, hipMemcpyHostToDevice, s));
     KH_HIP(hipMemcpyAsync(db, b, n * 32, hipMemcpyHostToDevice, s));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_inner_product<FpParams>), dim3(blocks), dim3(256), 0, s, da, db, n, g_ipa_b.as<u64>());
-    else hipLaunchKernelGGL((k_inner_product<FqParams>), dim3(blocks), dim3(256), 0, s, da, db, n, g_ipa_b.as<u64>());
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_inner_product<F>, dim3(blocks), dim3(256), 0, s, da, db, n, g_ipa_b.as<u64>());
     std::vector<khost::fe> part(blocks);
     KH_HIP(hipMemcpyAsync(part.data(), g_ipa_b.p, (size_t)blocks * 32, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));

@@ -106,19 +106,11 @@ k_lookup_atom_fin(size_t m, AtomZh z, Fe4q lim0, Fe4q limf, size_t kf, u64* __re
     (k == kf ? Fe<F>::load(limf.l) : mul<F>(zh, Fe<F>::load(lf + 4 * k))).store(lf + 4 * k);
 }
 
-#define KH_LK_DISPATCH(KERNEL, rows, stream, ...)                                                                                     \
-    do {                                                                                                                              \
-        const dim3 grid_((unsigned)(((rows) + 255) / 256)), block_(256);                                                              \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), grid_, block_, 0, stream, __VA_ARGS__);                      \
-        else hipLaunchKernelGGL((KERNEL<FqParams>), grid_, block_, 0, stream, __VA_ARGS__);                                           \
-        KH_HIP(hipGetLastError());                                                                                                    \
-    } while (0)
-
 int lookup_selector_columns(Context& C, int field, const uint8_t* code_dev, size_t n_gates, size_t n, const int* patterns, size_t npat, uint64_t* out_dev) {
     KH_REQUIRE(n_gates <= n && npat >= 1 && npat <= 4, "lookup_selector_columns: bad shape");
     LookupPats p; p.npat = (u32)npat;
     for (size_t k = 0; k < 4; k++) p.id[k] = k < npat ? (u32)patterns[k] : 0u;
-    KH_LK_DISPATCH(k_lookup_selectors, n, C.stream, code_dev, n_gates, n, p, out_dev);
+    KH_FIELD_LAUNCH(field, k_lookup_selectors<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, code_dev, n_gates, n, p, out_dev);
     return KH_OK;
 }
 int lookup_table_columns(Context& C, int field, const uint64_t* segs_dev, const uint64_t* seg_starts, size_t nseg, const uint64_t* data_dev, size_t n, size_t width,
@@ -128,7 +120,7 @@ int lookup_table_columns(Context& C, int field, const uint64_t* segs_dev, const 
     st.stride = (u32)((nseg + SEG_STARTS - 1) / SEG_STARTS);
     st.count = (u32)((nseg + st.stride - 1) / st.stride);
     for (u32 k = 0; k < st.count; k++) st.start[k] = seg_starts[(size_t)k * st.stride];
-    KH_LK_DISPATCH(k_lookup_tables, n, C.stream, segs_dev, (u32)nseg, st, data_dev, n, (u32)width, tcols_dev, ids_dev, rtsel_dev, rt_offset,
+    KH_FIELD_LAUNCH(field, k_lookup_tables<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, segs_dev, (u32)nseg, st, data_dev, n, (u32)width, tcols_dev, ids_dev, rtsel_dev, rt_offset,
                    rt_offset + rt_len, n - zk_rows);
     return KH_OK;
 }
@@ -137,7 +129,7 @@ int lookup_atom_denominators(Context& C, int field, const uint64_t* x8_dev, size
     KH_REQUIRE(zk_rows + 1 < n, "lookup_atom_denominators: bad shape");
     const size_t m = 8 * n;
     Fe4q fa, fw; memcpy(fa.l, a, 32); memcpy(fw.l, omega, 32);
-    KH_LK_DISPATCH(k_lookup_atom_den, m, C.stream, x8_dev, m, fa, fw, (u32)(zk_rows + 1), 8 * (n - zk_rows - 1), atoms_dev, atoms_dev + 4 * m,
+    KH_FIELD_LAUNCH(field, k_lookup_atom_den<F>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C.stream, x8_dev, m, fa, fw, (u32)(zk_rows + 1), 8 * (n - zk_rows - 1), atoms_dev, atoms_dev + 4 * m,
                    atoms_dev + 8 * m);
     return KH_OK;
 }
@@ -147,7 +139,7 @@ int lookup_atom_finish(Context& C, int field, size_t n, size_t zk_rows, const ui
     const size_t m = 8 * n;
     AtomZh z; memcpy(z.zh, zh8, sizeof(z.zh));
     Fe4q l0, lf; memcpy(l0.l, lim0, 32); memcpy(lf.l, limf, 32);
-    KH_LK_DISPATCH(k_lookup_atom_fin, m, C.stream, m, z, l0, lf, 8 * (n - zk_rows - 1), atoms_dev + 4 * m, atoms_dev + 8 * m);
+    KH_FIELD_LAUNCH(field, k_lookup_atom_fin<F>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, C.stream, m, z, l0, lf, 8 * (n - zk_rows - 1), atoms_dev + 4 * m, atoms_dev + 8 * m);
     return KH_OK;
 }
 

@@ -345,9 +345,7 @@ int ntt_build_twiddles(Context& C, int field, unsigned logn, int inverse, u64* t
     KH_HIP(hipMemcpyAsync(dpow, pow2, sizeof(pow2), hipMemcpyHostToDevice, C.stream));
     KH_HIP(hipStreamSynchronize(C.stream));       // pow2 is a stack buffer
     dim3 grid((unsigned)((count + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_build_twiddles<FpParams>), grid, dim3(256), 0, C.stream, tab, dpow, count);
-    else hipLaunchKernelGGL((k_build_twiddles<FqParams>), grid, dim3(256), 0, C.stream, tab, dpow, count);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_build_twiddles<F>, grid, dim3(256), 0, C.stream, tab, dpow, count);
     return KH_OK;
 }
 
@@ -413,9 +411,7 @@ static int get_scaled_table(Context& C, int field, unsigned log_ntot, TwEntry* E
         u32* c8 = (u32*)(E->tab_scaled.as<u64>() + count * 4);
         KH_HIP(hipMemcpyAsync(c8, &E->inv_n, 32, hipMemcpyHostToDevice, C.stream));      // inv_n lives in the table entry
         dim3 grid((unsigned)((count + 255) / 256));
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_scale_table<FpParams>), grid, dim3(256), 0, C.stream, E->tab_scaled.as<u64>(), E->tab.as<u64>(), c8, count);
-        else hipLaunchKernelGGL((k_scale_table<FqParams>), grid, dim3(256), 0, C.stream, E->tab_scaled.as<u64>(), E->tab.as<u64>(), c8, count);
-        KH_HIP(hipGetLastError());
+        KH_FIELD_LAUNCH(field, k_scale_table<F>, grid, dim3(256), 0, C.stream, E->tab_scaled.as<u64>(), E->tab.as<u64>(), c8, count);
         KH_HIP(hipStreamSynchronize(C.stream));         // published complete, as the table itself
     }
     *out = E->tab_scaled.as<u64>();

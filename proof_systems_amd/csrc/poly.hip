@@ -271,13 +271,6 @@ k_index_columns(const uint8_t* __restrict__ selcol, const u32* __restrict__ wire
     }
 }
 
-#define KH_FIELD_DISPATCH(KERNEL, grid, block, stream, ...)                                             \
-    do {                                                                                                \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((KERNEL<FpParams>), grid, block, 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<FqParams>), grid, block, 0, stream, __VA_ARGS__);                \
-        KH_HIP(hipGetLastError());                                                                      \
-    } while (0)
-
 #define g_poly_tab (kh::ctx().scratch("poly_tab"))
 
 int poly_lincomb(Context& C, int field, const uint64_t* const* segs_dev, const size_t* lens, const uint64_t* scales, size_t m,
@@ -289,8 +282,8 @@ int poly_lincomb(Context& C, int field, const uint64_t* const* segs_dev, const s
     std::vector<u64> lens64(lens, lens + m);
     hipStream_t s = C.stream;
     if (m && (rc = C.stage_upload(tab, {{segs_dev, m * 8}, {lens64.data(), m * 8}, {scales, m * 32}}))) return rc;
-    KH_FIELD_DISPATCH(k_lincomb, dim3((unsigned)((out_len + 255) / 256)), dim3(256), s,
-                      (const u64* const*)tab, (const u64*)(tab + m * 8), (const u64*)(tab + m * 16), m, out_len, out_dev);
+    KH_FIELD_LAUNCH(field, k_lincomb<F>, dim3((unsigned)((out_len + 255) / 256)), dim3(256), 0, s,
+                    (const u64* const*)tab, (const u64*)(tab + m * 8), (const u64*)(tab + m * 16), m, out_len, out_dev);
     return KH_OK;
 }
 int poly_b_init(Context& C, int field, const uint64_t* elm, const uint64_t* scales, size_t k, size_t n, uint64_t* out_dev) {
@@ -299,8 +292,8 @@ int poly_b_init(Context& C, int field, const uint64_t* elm, const uint64_t* scal
     if ((rc = g_poly_tab.reserve(k * 64 + 64))) return rc;
     hipStream_t s = C.stream;
     if (k && (rc = C.stage_upload(g_poly_tab.p, {{elm, k * 32}, {scales, k * 32}}))) return rc;
-    KH_FIELD_DISPATCH(k_b_init, dim3((unsigned)((n + 255) / 256)), dim3(256), s,
-                      g_poly_tab.as<u64>(), g_poly_tab.as<u64>() + 4 * k, k, n, out_dev);
+    KH_FIELD_LAUNCH(field, k_b_init<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                    g_poly_tab.as<u64>(), g_poly_tab.as<u64>() + 4 * k, k, n, out_dev);
     return KH_OK;
 }
 // polynomial j (polys_dev[j], lens[j] coefficients) is cut into num_chunks[j] chunks of `chunk`; out (host) receives, per
@@ -339,7 +332,7 @@ int poly_eval_chunks(Context& C, int field, const uint64_t* const* polys_dev, co
     char* d_tab = g_poly_tab.as<char>(); u64* d_pw = (u64*)(d_tab + tab_bytes); u64* res = d_pw + pw_bytes / 8;
     std::vector<khost::fe> part(nseg * npts);
     if ((rc = C.stage_upload(d_tab, {{tab.data(), tab_bytes}, {pw.data(), pw_bytes}}))) return rc;
-    KH_FIELD_DISPATCH(k_eval_chunks, dim3((unsigned)nseg, (unsigned)npts), dim3(EVAL_T), s, (const ChunkDesc*)d_tab, (const u64*)d_pw, nseg, res);
+    KH_FIELD_LAUNCH(field, k_eval_chunks<F>, dim3((unsigned)nseg, (unsigned)npts), dim3(EVAL_T), 0, s, (const ChunkDesc*)d_tab, (const u64*)d_pw, nseg, res);
     KH_HIP(hipMemcpyAsync(part.data(), res, res_bytes, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));
     // out_j[p][c] for polynomial j in order: npts x num_chunks[j]
@@ -358,43 +351,39 @@ int poly_eval_chunks(Context& C, int field, const uint64_t* const* polys_dev, co
 }
 int poly_div_vanishing(Context& C, int field, const uint64_t* f_dev, size_t len, size_t n, uint64_t* q_dev, uint64_t* r_dev) {
     hipStream_t s = C.stream;
-    KH_FIELD_DISPATCH(k_div_vanishing, dim3((unsigned)((n + 255) / 256)), dim3(256), s, f_dev, len, n, q_dev, r_dev);
+    KH_FIELD_LAUNCH(field, k_div_vanishing<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f_dev, len, n, q_dev, r_dev);
     return KH_OK;
 }
 int poly_index_columns(Context& C, int field, const uint8_t* selcol_dev, const uint32_t* wires_dev, const uint64_t* coeffs_dev, size_t n_gates,
                        size_t n, size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev) {
     KH_REQUIRE(n_gates <= n && zk_rows >= 3 && zk_rows < n && ncol >= (size_t)IDX_SEL0 + 5 && ncol < 256, "poly_index_columns: bad shape");
     IndexShifts sh; memcpy(sh.s, shifts, sizeof(sh.s));
-    KH_FIELD_DISPATCH(k_index_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), C.stream, selcol_dev, wires_dev, coeffs_dev, n_gates, n,
-                      n + 2 - zk_rows, n - 1, sh, (u32)ncol, d1_dev);
+    KH_FIELD_LAUNCH(field, k_index_columns<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, C.stream, selcol_dev, wires_dev, coeffs_dev, n_gates, n,
+                    n + 2 - zk_rows, n - 1, sh, (u32)ncol, d1_dev);
     return KH_OK;
 }
-
-#define KH_SCAN_DISPATCH(KERNEL, grid, block, stream, ...)                                                              \
-    do {                                                                                                                 \
-        if (field == KH_FIELD_FP) { if (op == 0) hipLaunchKernelGGL((KERNEL<FpParams, 0>), grid, block, 0, stream, __VA_ARGS__); \
-                                    else hipLaunchKernelGGL((KERNEL<FpParams, 1>), grid, block, 0, stream, __VA_ARGS__); }          \
-        else { if (op == 0) hipLaunchKernelGGL((KERNEL<FqParams, 0>), grid, block, 0, stream, __VA_ARGS__);                     \
-               else hipLaunchKernelGGL((KERNEL<FqParams, 1>), grid, block, 0, stream, __VA_ARGS__); }                           \
-        KH_HIP(hipGetLastError());                                                                                       \
-    } while (0)
 
 #define g_scan_tot (kh::ctx().scratch("scan_tot"))
 #define g_scan_a (kh::ctx().scratch("scan_a"))
 #define g_scan_b (kh::ctx().scratch("scan_b"))
 
+template <int OP>
+static int scan_launches(hipStream_t s, int field, int rev, uint64_t* data_dev, size_t n, size_t ntiles, u64* tot) {
+    KH_FIELD_LAUNCH(field, (k_scan_tiles<F, OP>), dim3((unsigned)ntiles), dim3(SCAN_T), 0, s, data_dev, n, rev, tot);
+    if (ntiles > 1) {
+        KH_FIELD_LAUNCH(field, (k_scan_totals<F, OP>), dim3(1), dim3(SCAN_T), 0, s, tot, ntiles);
+        KH_FIELD_LAUNCH(field, (k_scan_fix<F, OP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, data_dev, n, rev, (const u64*)tot);
+    }
+    return KH_OK;
+}
 static int scan_enqueue(hipStream_t s, int field, int op, int rev, uint64_t* data_dev, size_t n) {
     if (n == 0) return KH_OK;
     const size_t ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
     KH_REQUIRE(ntiles <= (size_t)SCAN_TILE, "scan of %zu elements: more than %d tiles", n, SCAN_TILE);
     int rc;
     if ((rc = g_scan_tot.reserve(ntiles * 32))) return rc;
-    KH_SCAN_DISPATCH(k_scan_tiles, dim3((unsigned)ntiles), dim3(SCAN_T), s, data_dev, n, rev, g_scan_tot.as<u64>());
-    if (ntiles > 1) {
-        KH_SCAN_DISPATCH(k_scan_totals, dim3(1), dim3(SCAN_T), s, g_scan_tot.as<u64>(), ntiles);
-        KH_SCAN_DISPATCH(k_scan_fix, dim3((unsigned)((n + 255) / 256)), dim3(256), s, data_dev, n, rev, (const u64*)g_scan_tot.as<u64>());
-    }
-    return KH_OK;
+    return op == 0 ? scan_launches<0>(s, field, rev, data_dev, n, ntiles, g_scan_tot.as<u64>())
+                   : scan_launches<1>(s, field, rev, data_dev, n, ntiles, g_scan_tot.as<u64>());
 }
 // evaluations of `batch` polynomials of n = 2^log2_n coefficients on the coset shift * <w_n> (natural order); asynchronous
 // on the main stream like kh_ntt_dev
@@ -403,7 +392,7 @@ int poly_coset_ntt(Context& C, int field, const uint64_t* coeffs_dev, unsigned l
     if (total == 0) return KH_OK;
     Fe4p a; memcpy(a.l, shift, 32);
     hipStream_t s = C.stream;
-    KH_FIELD_DISPATCH(k_coset_scale, dim3((unsigned)((total + 255) / 256)), dim3(256), s, coeffs_dev, a, n, total, out_dev);
+    KH_FIELD_LAUNCH(field, k_coset_scale<F>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, coeffs_dev, a, n, total, out_dev);
     return ntt_run(C, field, out_dev, log2_n, 0, batch);
 }
 int poly_scan(Context& C, int field, int op, int rev, uint64_t* data_dev, size_t n) {
@@ -417,7 +406,7 @@ int poly_batch_inversion(Context& C, int field, uint64_t* v_dev, size_t n) {
     if ((rc = g_scan_b.reserve(n * 32))) return rc;
     hipStream_t s = C.stream;
     dim3 g((unsigned)((n + 255) / 256));
-    KH_FIELD_DISPATCH(k_zero_to_one, g, dim3(256), s, (const u64*)v_dev, n, g_scan_a.as<u64>());
+    KH_FIELD_LAUNCH(field, k_zero_to_one<F>, g, dim3(256), 0, s, (const u64*)v_dev, n, g_scan_a.as<u64>());
     KH_HIP(hipMemcpyAsync(g_scan_b.p, g_scan_a.p, n * 32, hipMemcpyDeviceToDevice, s));
     if ((rc = scan_enqueue(s, field, 1, 0, g_scan_a.as<u64>(), n))) return rc;        // prefix products
     if ((rc = scan_enqueue(s, field, 1, 1, g_scan_b.as<u64>(), n))) return rc;        // suffix products
@@ -425,7 +414,7 @@ int poly_batch_inversion(Context& C, int field, uint64_t* v_dev, size_t n) {
     KH_HIP(hipMemcpyAsync(&total, g_scan_a.as<char>() + (n - 1) * 32, 32, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));
     Fe4p inv; host_field_inverse(field, total.l, inv.l);   // one inversion, on the host (20 us against ~0.2 ms for a lone GPU thread)
-    KH_FIELD_DISPATCH(k_batch_inv_finish, g, dim3(256), s, v_dev, (const u64*)g_scan_a.as<u64>(), (const u64*)g_scan_b.as<u64>(), inv, n);
+    KH_FIELD_LAUNCH(field, k_batch_inv_finish<F>, g, dim3(256), 0, s, v_dev, (const u64*)g_scan_a.as<u64>(), (const u64*)g_scan_b.as<u64>(), inv, n);
     return KH_OK;
 }
 // f = q (x - a) + rem, rem = f(a): q_i = a^-(i+1) sum_{k > i} c_k a^k
@@ -443,9 +432,9 @@ int poly_divide_by_linear(Context& C, int field, const uint64_t* f_dev, size_t l
     if ((rc = g_scan_a.reserve(len * 32))) return rc;
     Fe4p av, ai; memcpy(av.l, a, 32); host_field_inverse(field, a, ai.l);
     dim3 g((unsigned)((len + 255) / 256));
-    KH_FIELD_DISPATCH(k_scale_powers, g, dim3(256), s, f_dev, av, len, (size_t)0, g_scan_a.as<u64>());
+    KH_FIELD_LAUNCH(field, k_scale_powers<F>, g, dim3(256), 0, s, f_dev, av, len, (size_t)0, g_scan_a.as<u64>());
     if ((rc = scan_enqueue(s, field, 0, 1, g_scan_a.as<u64>(), len))) return rc;      // suffix sums
-    if (len > 1) KH_FIELD_DISPATCH(k_linear_quotient, g, dim3(256), s, (const u64*)g_scan_a.as<u64>(), ai, len, q_dev);
+    if (len > 1) KH_FIELD_LAUNCH(field, k_linear_quotient<F>, g, dim3(256), 0, s, (const u64*)g_scan_a.as<u64>(), ai, len, q_dev);
     if (rem) { KH_HIP(hipMemcpyAsync(rem, g_scan_a.p, 32, hipMemcpyDeviceToHost, s)); KH_HIP(hipStreamSynchronize(s)); }
     else if (rem_dev) KH_HIP(hipMemcpyAsync(rem_dev, g_scan_a.p, 32, hipMemcpyDeviceToDevice, s));
     return KH_OK;

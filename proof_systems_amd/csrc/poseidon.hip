@@ -7,6 +7,7 @@
 //   k_poseidon_gate_rows   the witness of the Poseidon gadget (kimchi/src/circuits/polynomials/poseidon.rs:239-290): the state before each of the 55
 //                          rounds into the cells of 11 rows, the final state into the first three cells of the twelfth
 //   k_poseidon_gate_rows3  the same rows with three lanes per permutation, for batches too small to fill the machine with one lane each (see there)
+// Both gate-rows kernels take where their instances land as one WitnessPlace (api_internal.hpp) and address every cell through its members.
 // One lane per permutation (except in k_poseidon_gate_rows3), blocks of ONE wave: the work is 1155 Montgomery products per lane that touch no memory (VALU issue), and a batch of a few
 // thousand permutations -- one 2^16-row circuit holds 5461 gadgets: 86 waves for 1024 SIMDs -- spreads over the CUs only in blocks that small.
 // The one-lane kernels share one round body: s_k <- s_k^7 as x^2, x^4, x^6 = x^4 x^2, x^7 = x^6 x (2 squarings + 2 products), then s_j <- sum_k mds[j][k] s_k +
@@ -63,12 +64,10 @@ __device__ __forceinline__ void poseidon_permutation(Fe<F>& s0, Fe<F>& s1, Fe<F>
     for (int r = 0; r < POSEIDON_ROUNDS; r++) poseidon_round<F>(s0, s1, s2, r);
 }
 
-static constexpr int POSEIDON_BLOCK = 64;          // one wave per block
-
 template <class F>
-__global__ void __launch_bounds__(POSEIDON_BLOCK)
+__global__ void __launch_bounds__(WAVE_BLOCK)
 k_poseidon_permute(u64* __restrict__ states, size_t n) {
-    const size_t i = (size_t)blockIdx.x * POSEIDON_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= n) return;
     u64* const st = states + 12 * i;
     Fe<F> s0 = Fe<F>::load(st), s1 = Fe<F>::load(st + 4), s2 = Fe<F>::load(st + 8);
@@ -80,9 +79,9 @@ k_poseidon_permute(u64* __restrict__ states, size_t n) {
 // permutation runs before the third, fifth, ... element and once more for the squeeze, which returns s0: max(1, ceil(msg_len / 2)) permutations.
 struct PoseidonInit { u64 s[12]; };
 template <class F>
-__global__ void __launch_bounds__(POSEIDON_BLOCK)
+__global__ void __launch_bounds__(WAVE_BLOCK)
 k_poseidon_hash(const u64* __restrict__ msgs, size_t msg_len, size_t n, PoseidonInit init, u64* __restrict__ digests) {
-    const size_t i = (size_t)blockIdx.x * POSEIDON_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= n) return;
     const u64* const m = msgs + 4 * msg_len * i;
     Fe<F> s0 = Fe<F>::load(init.s), s1 = Fe<F>::load(init.s + 4), s2 = Fe<F>::load(init.s + 8);
@@ -96,27 +95,25 @@ k_poseidon_hash(const u64* __restrict__ msgs, size_t msg_len, size_t n, Poseidon
     s0.store(digests + 4 * i);
 }
 
-// Instance i starts at row rows[i], or row0 + i row_stride when rows is null.  Round 5 j + t reads its state from row + j, columns 3 c .. 3 c + 2 with
-// c = {0, 2, 3, 4, 1}[t] (the gate's state order, poseidon.rs:65-80); column c of the witness starts at witness + 4 c col_stride.
+// Instance i starts at row at.start_row(i) (WitnessPlace, api_internal.hpp).  Round 5 j + t reads its state from row + j, columns 3 c .. 3 c + 2 with
+// c = {0, 2, 3, 4, 1}[t] (the gate's state order, poseidon.rs:65-80).
 template <class F>
-__global__ void __launch_bounds__(POSEIDON_BLOCK)
-k_poseidon_gate_rows(const u64* states, size_t n, const u32* __restrict__ rows, size_t row0, size_t row_stride, u64* __restrict__ witness,
-                     size_t col_stride, u64* out_states) {          // (out_states may be states: a lane reads its state before it writes anything)
-    const size_t i = (size_t)blockIdx.x * POSEIDON_BLOCK + threadIdx.x;
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_poseidon_gate_rows(const u64* states, size_t n, WitnessPlace at, u64* out_states) {          // (out_states may be states: a lane reads its state before it writes anything)
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     if (i >= n) return;
     const u64* const st = states + 12 * i;
     Fe<F> s0 = Fe<F>::load(st), s1 = Fe<F>::load(st + 4), s2 = Fe<F>::load(st + 8);
-    u64* cell = witness + 4 * (rows ? (size_t)rows[i] : row0 + i * row_stride);      // column 0 of the instance's current row
+    u64* cell = at.cell(at.start_row(i), 0);           // column 0 of the instance's current row
     int t = 0;
 #pragma unroll 1
     for (int r = 0; r < POSEIDON_ROUNDS; r++) {
         const size_t c = t == 0 ? 0 : t == 4 ? 1 : (size_t)t + 1;
-        u64* const w = cell + 12 * c * col_stride;
-        s0.store(w); s1.store(w + 4 * col_stride); s2.store(w + 8 * col_stride);
+        s0.store(cell + at.offset(0, 3 * c)); s1.store(cell + at.offset(0, 3 * c + 1)); s2.store(cell + at.offset(0, 3 * c + 2));
         poseidon_round<F>(s0, s1, s2, r);
-        if (++t == 5) { t = 0; cell += 4; }
+        if (++t == 5) { t = 0; cell += at.offset(1, 0); }
     }
-    s0.store(cell); s1.store(cell + 4 * col_stride); s2.store(cell + 8 * col_stride);
+    s0.store(cell); s1.store(cell + at.offset(0, 1)); s2.store(cell + at.offset(0, 2));
     if (out_states) { u64* const o = out_states + 12 * i; s0.store(o); s1.store(o + 4); s2.store(o + 8); }
 }
 
@@ -135,9 +132,8 @@ __device__ __forceinline__ Fe<F> shuffle_elem(const Fe<F>& a, int src) {
     return r;
 }
 template <class F>
-__global__ void __launch_bounds__(POSEIDON_BLOCK)
-k_poseidon_gate_rows3(const u64* states, size_t n, const u32* __restrict__ rows, size_t row0, size_t row_stride, u64* __restrict__ witness,
-                      size_t col_stride, u64* out_states) {
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_poseidon_gate_rows3(const u64* states, size_t n, WitnessPlace at, u64* out_states) {
     const u32 lane = threadIdx.x, q = lane / 3, k = lane - 3 * q;
     size_t i = (size_t)blockIdx.x * POSEIDON_SPLIT + q;
     const bool live = q < POSEIDON_SPLIT && i < n;
@@ -147,18 +143,18 @@ k_poseidon_gate_rows3(const u64* states, size_t n, const u32* __restrict__ rows,
     const PoseidonConsts& K = poseidon_consts<F>();
     const Fe<F> m0 = const_elem<F>(K.mds[k][k]), m1 = const_elem<F>(K.mds[k][k1]), m2 = const_elem<F>(K.mds[k][k2]);
     Fe<F> s = Fe<F>::load(states + 12 * i + 4 * k);
-    u64* cell = witness + 4 * (rows ? (size_t)rows[i] : row0 + i * row_stride) + 4 * k * col_stride;      // column k of the instance's current row
+    u64* cell = at.cell(at.start_row(i), k);           // column k of the instance's current row
     int t = 0;
 #pragma unroll 1
     for (int r = 0; r < POSEIDON_ROUNDS; r++) {
         const size_t c = t == 0 ? 0 : t == 4 ? 1 : (size_t)t + 1;
-        if (live) s.store(cell + 12 * c * col_stride);
+        if (live) s.store(cell + at.offset(0, 3 * c));
         const Fe<F> u0 = sbox7<F>(s), u1 = shuffle_elem<F>(u0, src1), u2 = shuffle_elem<F>(u0, src2);
         Fe<F> a = mul<F>(m0, u0);
         a = add<F>(a, mul<F>(m1, u1));
         a = add<F>(a, mul<F>(m2, u2));
         s = add<F>(a, const_elem<F>(K.rc[r][k]));
-        if (++t == 5) { t = 0; cell += 4; }
+        if (++t == 5) { t = 0; cell += at.offset(1, 0); }
     }
     if (live) {
         s.store(cell);
@@ -167,40 +163,32 @@ k_poseidon_gate_rows3(const u64* states, size_t n, const u32* __restrict__ rows,
 }
 
 // (the phase of kh_last_timings carries the kernel's name without the k_: poseidon_permute, poseidon_hash, poseidon_gate_rows, poseidon_gate_rows3)
-#define KH_POSEIDON_DISPATCH(NAME, per_wave, n, C, ...)                                                                               \
-    do {                                                                                                                              \
-        const dim3 grid_((unsigned)(((n) + (per_wave) - 1) / (per_wave))), block_(POSEIDON_BLOCK);                                    \
-        C.timer.begin(C.stream);                                                                                                      \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_##NAME<FpParams>), grid_, block_, 0, C.stream, __VA_ARGS__);                  \
-        else hipLaunchKernelGGL((k_##NAME<FqParams>), grid_, block_, 0, C.stream, __VA_ARGS__);                                       \
-        KH_HIP(hipGetLastError());                                                                                                    \
-        C.timer.mark(#NAME, C.stream);                                                                                                \
-    } while (0)
-
 // kh_poseidon_gate_witness_dev takes the three-lane kernel up to this many instances (kh_poseidon_set_split_max_n): up to two of its waves per SIMD.
 // A batch takes about ceil(waves / 1024) wave times, 0.18 ms for a three-lane wave of 21 instances and 0.5 ms for a one-lane wave of 64: measured, three
 // lanes win up to 53,760 instances (0.545 against 0.599 ms; 0.380 against 0.532 at 43,008), lose at 2^16 (0.71 against 0.61) and by 2 % at 2^20.
 static std::atomic<size_t> g_split_max_n{(size_t)POSEIDON_SPLIT * 2048};
 
-// (the callers in vector_api.cpp have validated pointers and sizes: n <= POSEIDON_MAX_N keeps the grid inside 31 bits)
+// (the callers in vector_api.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grid inside 31 bits)
 int poseidon_permute(Context& C, int field, uint64_t* states_dev, size_t n) {
-    KH_POSEIDON_DISPATCH(poseidon_permute, POSEIDON_BLOCK, n, C, (u64*)states_dev, n);
+    C.timer.begin(C.stream);
+    KH_FIELD_LAUNCH(field, k_poseidon_permute<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, states_dev, n);
+    C.timer.mark("poseidon_permute", C.stream);
     return KH_OK;
 }
 int poseidon_hash(Context& C, int field, const uint64_t* msgs_dev, size_t msg_len, size_t n, const uint64_t* init, uint64_t* digests_dev) {
     PoseidonInit st; memset(&st, 0, sizeof(st));
     if (init) memcpy(st.s, init, sizeof(st.s));
-    KH_POSEIDON_DISPATCH(poseidon_hash, POSEIDON_BLOCK, n, C, (const u64*)msgs_dev, msg_len, n, st, (u64*)digests_dev);
+    C.timer.begin(C.stream);
+    KH_FIELD_LAUNCH(field, k_poseidon_hash<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, msgs_dev, msg_len, n, st, digests_dev);
+    C.timer.mark("poseidon_hash", C.stream);
     return KH_OK;
 }
-int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const uint32_t* rows_dev, size_t row0, size_t row_stride,
-                       uint64_t* witness_dev, size_t col_stride, uint64_t* out_states_dev) {
-    if (n <= g_split_max_n.load(std::memory_order_relaxed))
-        KH_POSEIDON_DISPATCH(poseidon_gate_rows3, POSEIDON_SPLIT, n, C, (const u64*)states_dev, n, rows_dev, row0, row_stride, (u64*)witness_dev, col_stride,
-                             (u64*)out_states_dev);
-    else
-        KH_POSEIDON_DISPATCH(poseidon_gate_rows, POSEIDON_BLOCK, n, C, (const u64*)states_dev, n, rows_dev, row0, row_stride, (u64*)witness_dev, col_stride,
-                             (u64*)out_states_dev);
+int poseidon_gate_rows(Context& C, int field, const uint64_t* states_dev, size_t n, const WitnessPlace& at, uint64_t* out_states_dev) {
+    const bool split = n <= g_split_max_n.load(std::memory_order_relaxed);
+    C.timer.begin(C.stream);
+    if (split) KH_FIELD_LAUNCH(field, k_poseidon_gate_rows3<F>, blocks_of(n, POSEIDON_SPLIT), dim3(WAVE_BLOCK), 0, C.stream, states_dev, n, at, out_states_dev);
+    else KH_FIELD_LAUNCH(field, k_poseidon_gate_rows<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, states_dev, n, at, out_states_dev);
+    C.timer.mark(split ? "poseidon_gate_rows3" : "poseidon_gate_rows", C.stream);
     return KH_OK;
 }
 void poseidon_set_split_max_n(size_t n) { g_split_max_n.store(n, std::memory_order_relaxed); }

@@ -147,9 +147,7 @@ int srs_generate_device(Context& C, int curve, size_t start, size_t count, void*
     put(P.s, s); put(P.c2, F.inv(three)); put(P.five, five); put(P.root, root);
     memcpy(P.t_m1_d2, &tm1d2, 32);
     dim3 grid((unsigned)((count + 127) / 128));
-    if (fid == KH_FIELD_FQ) hipLaunchKernelGGL((k_srs_generate<FqParams>), grid, dim3(128), 0, C.stream, (u32)start, count, P, (uint8_t*)out_xy_dev);
-    else hipLaunchKernelGGL((k_srs_generate<FpParams>), grid, dim3(128), 0, C.stream, (u32)start, count, P, (uint8_t*)out_xy_dev);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(fid, k_srs_generate<F>, grid, dim3(128), 0, C.stream, (u32)start, count, P, (uint8_t*)out_xy_dev);
     KH_HIP(hipStreamSynchronize(C.stream));
     return KH_OK;
 }

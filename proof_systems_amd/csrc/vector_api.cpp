@@ -8,6 +8,18 @@ using namespace kh;
 
 namespace {
 #include "poseidon_params.inc"      // the round constants kh_poseidon_gate_coefficients hands out (the host sponge and the device kernels have the same table)
+
+// How a vector step is queued on the main stream: under the context's lock, and when run(C) has queued it, the point is marked that a later MSM on
+// another slot's stream waits for.  The entry points check their arguments in front of this.
+template <class Run>
+int queue_step(Run run) {
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = run(C);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
 }
 
 // transfer buffers of the host-pointer transforms (kh_ntt / kh_lde: host_transform below)
@@ -47,7 +59,6 @@ int kh_combine_polys_dev(int field, const uint64_t* const* polys_dev, const size
                          const uint64_t polyscale[4], size_t srs_length, uint64_t* out_dev, size_t* out_len) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(out_dev && polyscale && srs_length > 0 && (m == 0 || (polys_dev && lens && num_chunks)), "kh_combine_polys_dev: bad argument");
-    int rc = ensure_init(); if (rc) return rc;
     khost::Fld F(field);
     khost::fe ps; memcpy(&ps, polyscale, 32);
     khost::fe scale = F.f.one;
@@ -62,39 +73,26 @@ int kh_combine_polys_dev(int field, const uint64_t* const* polys_dev, const size
             offset += srs_length;
         }
     }
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    if ((rc = poly_lincomb(C, field, segs.data(), slen.data(), (const uint64_t*)scales.data(), segs.size(), out_dev, srs_length))) return rc;
-    C.mark_async();
-    if (out_len) *out_len = longest;
-    return KH_OK;
+    const int rc = queue_step([&](Context& C) { return poly_lincomb(C, field, segs.data(), slen.data(), (const uint64_t*)scales.data(), segs.size(), out_dev, srs_length); });
+    if (rc == KH_OK && out_len) *out_len = longest;
+    return rc;
 }
 int kh_poly_lincomb_dev(int field, const uint64_t* const* polys_dev, const size_t* lens, const uint64_t* scalars, size_t m,
                         uint64_t* out_dev, size_t out_len) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE((out_dev || out_len == 0) && (m == 0 || (polys_dev && lens && scalars)), "kh_poly_lincomb_dev: null argument");
     for (size_t i = 0; i < m; i++) KH_REQUIRE(lens[i] <= out_len, "polynomial %zu has %zu coefficients, the output %zu", i, lens[i], out_len);
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_lincomb(C, field, polys_dev, lens, scalars, m, out_dev, out_len);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_lincomb(C, field, polys_dev, lens, scalars, m, out_dev, out_len); });
 }
 int kh_b_init_dev(int field, const uint64_t* elm, size_t k, const uint64_t evalscale[4], size_t padded_len, uint64_t* out_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(out_dev && evalscale && (elm || k == 0), "kh_b_init_dev: null argument");
-    int rc = ensure_init(); if (rc) return rc;
     khost::Fld F(field);
     khost::fe es; memcpy(&es, evalscale, 32);
     std::vector<khost::fe> scales(k);
     khost::fe sc = F.f.one;
     for (size_t i = 0; i < k; i++) { scales[i] = sc; sc = F.mul(sc, es); }
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_b_init(C, field, elm, (const uint64_t*)scales.data(), k, padded_len, out_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_b_init(C, field, elm, (const uint64_t*)scales.data(), k, padded_len, out_dev); });
 }
 int kh_evaluate_chunks_batch_dev(int field, const uint64_t* const* polys_dev, const size_t* lens, const size_t* num_chunks, size_t m,
                                  size_t chunk_size, const uint64_t* points, size_t npts, uint64_t* out) {
@@ -121,33 +119,18 @@ int kh_divide_by_vanishing_poly_dev(int field, const uint64_t* f_dev, size_t len
     KH_REQUIRE(log2_n <= 32 && r_dev && (f_dev || len == 0), "kh_divide_by_vanishing_poly_dev: bad argument");
     const size_t n = (size_t)1 << log2_n;
     KH_REQUIRE(q_dev || len <= n, "null quotient buffer");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_div_vanishing(C, field, f_dev, len, n, q_dev, r_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_div_vanishing(C, field, f_dev, len, n, q_dev, r_dev); });
 }
 
 int kh_field_scan_dev(int field, int op, int reverse, uint64_t* data_dev, size_t n) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE((op == KH_SCAN_ADD || op == KH_SCAN_MUL) && (data_dev || n == 0), "kh_field_scan_dev: bad argument");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_scan(C, field, op, reverse ? 1 : 0, data_dev, n);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_scan(C, field, op, reverse ? 1 : 0, data_dev, n); });
 }
 int kh_batch_inversion_dev(int field, uint64_t* v_dev, size_t n) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(v_dev || n == 0, "null vector");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_batch_inversion(C, field, v_dev, n);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_batch_inversion(C, field, v_dev, n); });
 }
 int kh_divide_by_linear_dev(int field, const uint64_t* f_dev, size_t len, const uint64_t a[4], uint64_t* q_dev, uint64_t rem[4]) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
@@ -160,21 +143,11 @@ int kh_divide_by_linear_dev(int field, const uint64_t* f_dev, size_t len, const 
 int kh_divide_by_linear_async_dev(int field, const uint64_t* f_dev, size_t len, const uint64_t a[4], uint64_t* q_dev, uint64_t* rem_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(a && (f_dev || len == 0) && (q_dev || len <= 1), "kh_divide_by_linear_async_dev: null argument");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_divide_by_linear(C, field, f_dev, len, a, q_dev, nullptr, rem_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_divide_by_linear(C, field, f_dev, len, a, q_dev, nullptr, rem_dev); });
 }
 int kh_check_equal_dev(const uint64_t* v_dev, size_t n, const uint64_t* expect, uint32_t* flags_dev, unsigned bit) {
     KH_REQUIRE((v_dev || n == 0) && flags_dev && bit < 32, "kh_check_equal_dev: bad argument");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_check_equal(C, v_dev, n, expect, flags_dev, bit);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_check_equal(C, v_dev, n, expect, flags_dev, bit); });
 }
 int kh_expr_evaluations_dev(int field, const uint32_t* tokens, size_t ntok, const uint64_t* const* cols_dev, const size_t* col_len, size_t ncols,
                             const uint64_t* constants, size_t nconsts, size_t rows, unsigned stride, unsigned next_shift, int accumulate,
@@ -182,12 +155,7 @@ int kh_expr_evaluations_dev(int field, const uint32_t* tokens, size_t ntok, cons
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(tokens && ntok > 0 && (out_dev || rows == 0) && stride > 0, "kh_expr_evaluations_dev: bad argument");
     KH_REQUIRE((ncols == 0 || (cols_dev && col_len)) && (nconsts == 0 || constants), "kh_expr_evaluations_dev: null table");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = expr_run(C, field, tokens, ntok, cols_dev, col_len, ncols, constants, nconsts, rows, stride, next_shift, accumulate, out_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return expr_run(C, field, tokens, ntok, cols_dev, col_len, ncols, constants, nconsts, rows, stride, next_shift, accumulate, out_dev); });
 }
 
 // The `sorted` step of the lookup argument on the device (kernels in lookup_sorted.hip).  The scratch block comes from the kh_dev_alloc pool (taken before the
@@ -201,17 +169,17 @@ int kh_lookup_sorted_dev(const uint64_t* table_dev, size_t lookup_rows, const ui
                "kh_lookup_sorted_dev: (max_per_row + 1) * lookup_rows = (%zu + 1) * %zu does not fit 31 bits", max_per_row, lookup_rows);
     int rc = ensure_init(); if (rc) return rc;
     if (bad_row) *bad_row = (size_t)-1;
-    struct Scratch { uint32_t* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } scratch;
-    if ((rc = kh_dev_alloc((void**)&scratch.p, lookup_sorted_scratch_words(lookup_rows) * sizeof(uint32_t)))) return rc;
+    PoolBlock scratch;
+    if ((rc = kh_dev_alloc(&scratch.p, lookup_sorted_scratch_words(lookup_rows) * sizeof(uint32_t)))) return rc;
     {
         Context& C = ctx();
         std::lock_guard<std::mutex> lk(C.mu);
-        rc = lookup_sorted_run(C, table_dev, lookup_rows, values_dev, value_stride, max_per_row, out_dev, out_stride, scratch.p);
+        rc = lookup_sorted_run(C, table_dev, lookup_rows, values_dev, value_stride, max_per_row, out_dev, out_stride, scratch.as<uint32_t>());
         C.mark_async();
         if (rc) return rc;
     }
     uint32_t status[2] = {0, 0};
-    if ((rc = kh_dev_download(status, scratch.p + lookup_sorted_status_offset(lookup_rows), sizeof(status)))) return rc;
+    if ((rc = kh_dev_download(status, scratch.as<uint32_t>() + lookup_sorted_status_offset(lookup_rows), sizeof(status)))) return rc;
     if (status[0] != 0xffffffffu) {                         // a looked-up value that is not in the table (constraints.rs:137-141)
         const size_t s = status[0] / lookup_rows, r = status[0] % lookup_rows;
         if (bad_row) *bad_row = r;
@@ -234,12 +202,7 @@ int kh_gate_evaluations_dev(int field, int gate, const uint64_t* const* cols_dev
                             unsigned stride, unsigned next_shift, int accumulate, uint64_t* out_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(cols_dev && constants && (out_dev || rows == 0) && stride > 0, "kh_gate_evaluations_dev: bad argument");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = gate_run(C, field, gate, cols_dev, col_len, constants, nconsts, rows, stride, next_shift, accumulate, out_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return gate_run(C, field, gate, cols_dev, col_len, constants, nconsts, rows, stride, next_shift, accumulate, out_dev); });
 }
 
 // ---------------------------------------------------------------------------------- Poseidon on the device (kernels in poseidon.hip)
@@ -256,173 +219,132 @@ int kh_poseidon_permute_dev(int field, uint64_t* states_dev, size_t n) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(states_dev || n == 0, "kh_poseidon_permute_dev: null states");
     KH_REQUIRE(KH_POSEIDON_ALIGNED(states_dev), "kh_poseidon_permute_dev: states_dev must be 16-byte aligned");
-    KH_REQUIRE(n <= POSEIDON_MAX_N, "kh_poseidon_permute_dev: %zu states are more than the %zu one call takes", n, POSEIDON_MAX_N);
-    int rc = ensure_init(); if (rc) return rc;
-    if (n == 0) return KH_OK;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poseidon_permute(C, field, states_dev, n);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N, "kh_poseidon_permute_dev: %zu states are more than the %zu one call takes", n, WAVE_BLOCK_MAX_N);
+    if (n == 0) return ensure_init();
+    return queue_step([&](Context& C) { return poseidon_permute(C, field, states_dev, n); });
 }
 int kh_poseidon_hash_dev(int field, const uint64_t* msgs_dev, size_t msg_len, size_t n, const uint64_t* init, uint64_t* digests_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(n == 0 || (digests_dev && (msgs_dev || msg_len == 0)), "kh_poseidon_hash_dev: null %s", digests_dev ? "messages" : "digests");
     KH_REQUIRE(KH_POSEIDON_ALIGNED(msgs_dev) && KH_POSEIDON_ALIGNED(digests_dev), "kh_poseidon_hash_dev: msgs_dev and digests_dev must be 16-byte aligned");
-    KH_REQUIRE(n <= POSEIDON_MAX_N && (msg_len == 0 || n <= (SIZE_MAX / 32) / msg_len),
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && (msg_len == 0 || n <= (SIZE_MAX / 32) / msg_len),
                "kh_poseidon_hash_dev: %zu messages of %zu elements overflow the byte count", n, msg_len);
-    int rc = ensure_init(); if (rc) return rc;
-    if (n == 0) return KH_OK;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poseidon_hash(C, field, msgs_dev, msg_len, n, init, digests_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
-}
-int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_states_dev) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
-    KH_REQUIRE(n == 0 || (states_dev && witness_dev), "kh_poseidon_gate_witness_dev: null %s", states_dev ? "witness" : "states");
-    KH_REQUIRE(KH_POSEIDON_ALIGNED(states_dev) && KH_POSEIDON_ALIGNED(witness_dev) && KH_POSEIDON_ALIGNED(out_states_dev),
-               "kh_poseidon_gate_witness_dev: states_dev, witness_dev and out_states_dev must be 16-byte aligned");
-    KH_REQUIRE(col_stride >= col_len, "kh_poseidon_gate_witness_dev: col_stride %zu is less than col_len %zu", col_stride, col_len);
-    KH_REQUIRE(n <= POSEIDON_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "kh_poseidon_gate_witness_dev: %zu instances in columns %zu elements apart overflow the byte count",
-               n, col_stride);
-    if (n > 0 && rows) {
-        for (size_t i = 0; i < n; i++)
-            KH_REQUIRE(col_len >= 12 && rows[i] <= col_len - 12, "kh_poseidon_gate_witness_dev: instance %zu at row %u does not fit %zu rows (12 rows each)", i, rows[i], col_len);
-    } else if (n > 0) {
-        KH_REQUIRE(row_stride >= 12, "kh_poseidon_gate_witness_dev: row_stride %zu is less than the 12 rows of an instance", row_stride);
-        KH_REQUIRE(col_len >= 12 && row0 <= col_len - 12 && (n - 1) <= (col_len - 12 - row0) / row_stride,
-                   "kh_poseidon_gate_witness_dev: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", n, row0, row_stride, col_len);
-    }
-    int rc = ensure_init(); if (rc) return rc;
-    if (n == 0) return KH_OK;
-    // the start rows travel through the pinned staging ring into a block of the kh_dev_alloc pool (taken before the context's lock, like
-    // kh_lookup_sorted_dev's scratch), in pieces that leave the ring its size: the caller's array is not read after this returns
-    struct Scratch { uint32_t* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } rows_dev;
-    if (rows && (rc = kh_dev_alloc((void**)&rows_dev.p, n * sizeof(uint32_t)))) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    const size_t piece = (size_t)1 << 15;
-    for (size_t i = 0; rows && i < n; i += piece)
-        if ((rc = C.stage_upload(rows_dev.p + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}}))) return rc;
-    rc = poseidon_gate_rows(C, field, states_dev, n, rows_dev.p, row0, row_stride, witness_dev, col_stride, out_states_dev);
-    C.mark_async();
-    return rc;
+    if (n == 0) return ensure_init();
+    return queue_step([&](Context& C) { return poseidon_hash(C, field, msgs_dev, msg_len, n, init, digests_dev); });
 }
 #undef KH_POSEIDON_ALIGNED
 int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return KH_OK; }
 
-// ---------------------------------------------------------------------------------- the curve gates' witness on the device (kernels in curve_gadgets.hip)
+// ---------------------------------------------------------------------------------- gadget witnesses on the device (kernels in poseidon.hip, curve_gadgets.hip)
+}  // extern "C"
 namespace {
+// what a placement (WitnessPlace, rows still on the host) is refused for: a null or misaligned witness, columns that overlap or whose byte count
+// overflows, instances of inst_rows rows that do not fit col_len rows
+int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t col_len, size_t inst_rows) {
+    KH_REQUIRE(at.witness || n == 0, "%s: null witness_dev", call);
+    KH_REQUIRE((((uintptr_t)at.witness) & 15) == 0, "%s: witness_dev must be 16-byte aligned", call);
+    KH_REQUIRE(at.col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, at.col_stride, col_len);
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && at.col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
+               at.col_stride);
+    if (n > 0 && at.rows) {
+        for (size_t i = 0; i < n; i++)
+            KH_REQUIRE(col_len >= inst_rows && at.rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
+                       at.rows[i], col_len, inst_rows);
+    } else if (n > 0) {
+        KH_REQUIRE(at.row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, at.row_stride, inst_rows);
+        KH_REQUIRE(col_len >= inst_rows && at.row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - at.row0) / at.row_stride,
+                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, at.row0, at.row_stride, col_len);
+    }
+    return KH_OK;
+}
 struct GadgetPtr { const char* name; const void* p; bool required; };
-// what the four calls refuse alike: the field, null / misaligned device pointers, sizes that overflow, instances of inst_rows rows that do not fit
-int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                    size_t col_stride, size_t col_len, size_t inst_rows) {
+// what the five calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
+int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
     for (const GadgetPtr& a : ptrs) {
         KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
         KH_REQUIRE((((uintptr_t)a.p) & 15) == 0, "%s: %s must be 16-byte aligned", call, a.name);
     }
-    KH_REQUIRE(col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, col_stride, col_len);
-    KH_REQUIRE(n <= GADGET_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
-               col_stride);
-    if (n > 0 && rows) {
-        for (size_t i = 0; i < n; i++)
-            KH_REQUIRE(col_len >= inst_rows && rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
-                       rows[i], col_len, inst_rows);
-    } else if (n > 0) {
-        KH_REQUIRE(row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, row_stride, inst_rows);
-        KH_REQUIRE(col_len >= inst_rows && row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - row0) / row_stride,
-                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, row0, row_stride, col_len);
-    }
-    return KH_OK;
+    return place_validate(call, at, n, col_len, inst_rows);
 }
-// blocks of the kh_dev_alloc pool that go back to it when the call returns (work queued on the main stream before that precedes their next use)
-struct PoolBlock { void* p = nullptr; ~PoolBlock() { if (p) (void)kh_dev_free(p); } };
-// the start rows through the pinned staging ring into rows_dev, in pieces that leave the ring its size (C.mu held)
-int upload_rows(Context& C, const uint32_t* rows, size_t n, uint32_t* rows_dev) {
-    const size_t piece = (size_t)1 << 15;
+// The queueing of a validated call: the start rows travel through the pinned staging ring into a block of the kh_dev_alloc pool (taken before the
+// context's lock, like kh_lookup_sorted_dev's scratch), in pieces that leave the ring its size -- the caller's array is not read after this returns --
+// and launch(C, at) runs with at.rows on the device.
+template <class Launch>
+int gadget_queue(WitnessPlace at, size_t n, Launch launch) {
+    if (n == 0) return ensure_init();
+    const uint32_t* const rows = at.rows;
+    PoolBlock rows_dev;
     int rc;
-    for (size_t i = 0; rows && i < n; i += piece)
-        if ((rc = C.stage_upload(rows_dev + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}}))) return rc;
-    return KH_OK;
+    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    at.rows = rows_dev.as<uint32_t>();
+    return queue_step([&](Context& C) {
+        const size_t piece = (size_t)1 << 15;
+        for (size_t i = 0; rows && i < n; i += piece) {
+            const int up = C.stage_upload(rows_dev.as<uint32_t>() + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}});
+            if (up) return up;
+        }
+        return launch(C, at);
+    });
 }
 }  // namespace
+extern "C" {
 
+int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_states_dev) {
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = gadget_validate("kh_poseidon_gate_witness_dev", field, {{"states_dev", states_dev, true}, {"out_states_dev", out_states_dev, false}}, n, at, col_len, 12);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return poseidon_gate_rows(C, field, states_dev, n, dev, out_states_dev); });
+}
 int kh_complete_add_witness_dev(int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    int rc = gadget_validate("kh_complete_add_witness_dev", field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"witness_dev", witness_dev, true},
-                             {"out_dev", out_dev, false}}, n, rows, row0, row_stride, col_stride, col_len, 1);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = gadget_validate("kh_complete_add_witness_dev", field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
     if (rc) return rc;
-    if ((rc = ensure_init())) return rc;
-    if (n == 0) return KH_OK;
-    PoolBlock rows_dev;
-    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
-    rc = complete_add_rows(C, field, p1_dev, p2_dev, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev, col_stride, out_dev);
-    C.mark_async();
-    return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return complete_add_rows(C, field, p1_dev, p2_dev, n, dev, out_dev); });
 }
 int kh_endomul_scalar_witness_dev(int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                                   uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t* out_dev) {
     KH_REQUIRE(num_bits >= 16 && num_bits <= 128 && num_bits % 16 == 0, "kh_endomul_scalar_witness_dev: num_bits %u is not a multiple of 16 from 16 to 128",
                num_bits);
-    int rc = gadget_validate("kh_endomul_scalar_witness_dev", field, {{"chals_dev", chals_dev, true}, {"witness_dev", witness_dev, true},
-                             {"out_dev", out_dev, false}}, n, rows, row0, row_stride, col_stride, col_len, num_bits / 16);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = gadget_validate("kh_endomul_scalar_witness_dev", field, {{"chals_dev", chals_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, num_bits / 16);
     if (rc) return rc;
     KH_REQUIRE(endo_scalar || !out_dev || n == 0, "kh_endomul_scalar_witness_dev: null endo_scalar with an out_dev");
-    if ((rc = ensure_init())) return rc;
-    if (n == 0) return KH_OK;
-    PoolBlock rows_dev;
-    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
-    rc = endomul_scalar_rows(C, field, chals_dev, num_bits, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev, col_stride, endo_scalar, out_dev);
-    C.mark_async();
-    return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return endomul_scalar_rows(C, field, chals_dev, num_bits, n, dev, endo_scalar, out_dev); });
 }
 // VarBaseMul (endo == nullptr, scalars of 4 limbs) and EndoMul (challenges of 2 limbs) share everything but their row counts
 static int chain_witness(const char* call, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev,
-                         const uint64_t* scalars_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev,
-                         size_t col_stride, size_t col_len, uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
+                         const uint64_t* scalars_dev, unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len, uint64_t* out_acc_dev,
+                         uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
     if (is_endo) KH_REQUIRE(num_bits >= 4 && num_bits <= 128 && num_bits % 4 == 0, "%s: num_bits %u is not a multiple of 4 from 4 to 128", call, num_bits);
     else KH_REQUIRE(num_bits >= 5 && num_bits <= 255 && num_bits % 5 == 0, "%s: num_bits %u is not a multiple of 5 from 5 to 255", call, num_bits);
     int rc = gadget_validate(call, field, {{"base_dev", base_dev, true}, {"acc0_dev", acc0_dev, true}, {is_endo ? "chals_dev" : "scalars_dev", scalars_dev, true},
-                             {"witness_dev", witness_dev, true}, {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
-                             n, rows, row0, row_stride, col_stride, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
+                             {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
+                             n, at, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
     if (rc) return rc;
     KH_REQUIRE(!is_endo || endo || n == 0, "%s: null endo", call);
     KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (void*)flags_dev);
-    if ((rc = ensure_init())) return rc;
-    if (n == 0) return KH_OK;
-    PoolBlock rows_dev, scratch;
-    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
+    PoolBlock scratch;
     const size_t scratch_bytes = chain_scratch_bytes(is_endo, num_bits, n);
-    if ((rc = kh_dev_alloc(&scratch.p, scratch_bytes))) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    if ((rc = upload_rows(C, rows, n, (uint32_t*)rows_dev.p))) return rc;
-    rc = chain_rows(C, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, (const uint32_t*)rows_dev.p, row0, row_stride, witness_dev,
-                    col_stride, out_acc_dev, out_n_dev, flags_dev, bit, (uint64_t*)scratch.p, scratch_bytes);
-    C.mark_async();
-    return rc;
+    if (n > 0 && (rc = kh_dev_alloc(&scratch.p, scratch_bytes))) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
+        return chain_rows(C, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, dev, out_acc_dev, out_n_dev, flags_dev, bit, scratch.as<uint64_t>(),
+                          scratch_bytes);
+    });
 }
 int kh_varbasemul_witness_dev(int field, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev, unsigned num_bits, size_t n,
                               const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
                               uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    return chain_witness("kh_varbasemul_witness_dev", field, false, nullptr, base_dev, acc0_dev, scalars_dev, num_bits, n, rows, row0, row_stride, witness_dev,
-                         col_stride, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
+    return chain_witness("kh_varbasemul_witness_dev", field, false, nullptr, base_dev, acc0_dev, scalars_dev, num_bits, n,
+                         WitnessPlace{rows, row0, row_stride, witness_dev, col_stride}, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
 }
 int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* chals_dev, unsigned num_bits,
                            size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
                            uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    return chain_witness("kh_endomul_witness_dev", field, true, endo, base_dev, acc0_dev, chals_dev, num_bits, n, rows, row0, row_stride, witness_dev,
-                         col_stride, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
+    return chain_witness("kh_endomul_witness_dev", field, true, endo, base_dev, acc0_dev, chals_dev, num_bits, n,
+                         WitnessPlace{rows, row0, row_stride, witness_dev, col_stride}, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
 }
 int kh_curve_witness_set_slice_elements(size_t elements) { chain_set_slice_elements(elements); return KH_OK; }
 
@@ -438,37 +360,22 @@ int kh_ntt_dev(int field, uint64_t* data_dev, unsigned log2_n, int inverse, size
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(log2_n <= 28, "log2_n = %u too large", log2_n);
     KH_REQUIRE(data_dev || batch == 0, "null data");
-    int rc = ensure_init(); if (rc) return rc;
-    if (batch == 0) return KH_OK;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = ntt_run(C, field, data_dev, log2_n, inverse, batch);
-    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;   // a later MSM on another slot waits for this point
-    return rc;
+    if (batch == 0) return ensure_init();
+    return queue_step([&](Context& C) { return ntt_run(C, field, data_dev, log2_n, inverse, batch); });
 }
 int kh_lde_dev(int field, const uint64_t* coeffs_dev, unsigned log2_n, unsigned log2_blowup, uint64_t* out_dev, size_t batch) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(log2_n + log2_blowup <= 28, "log2 size %u too large", log2_n + log2_blowup);
     KH_REQUIRE((coeffs_dev && out_dev) || batch == 0, "null data");
-    int rc = ensure_init(); if (rc) return rc;
-    if (batch == 0) return KH_OK;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = lde_run(C, field, coeffs_dev, log2_n, log2_blowup, out_dev, batch);
-    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;
-    return rc;
+    if (batch == 0) return ensure_init();
+    return queue_step([&](Context& C) { return lde_run(C, field, coeffs_dev, log2_n, log2_blowup, out_dev, batch); });
 }
 int kh_coset_ntt_dev(int field, const uint64_t* coeffs_dev, unsigned log2_n, const uint64_t shift[4], uint64_t* out_dev, size_t batch) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(log2_n <= 28 && shift, "kh_coset_ntt_dev: bad argument");
     KH_REQUIRE((coeffs_dev && out_dev) || batch == 0, "null data");
-    int rc = ensure_init(); if (rc) return rc;
-    if (batch == 0) return KH_OK;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_coset_ntt(C, field, coeffs_dev, log2_n, shift, out_dev, batch);
-    if (rc == KH_OK && hipEventRecord(C.order_ev, C.stream) == hipSuccess) C.main_dirty = true;
-    return rc;
+    if (batch == 0) return ensure_init();
+    return queue_step([&](Context& C) { return poly_coset_ntt(C, field, coeffs_dev, log2_n, shift, out_dev, batch); });
 }
 // Host-pointer transforms (what the ark-poly patch calls: interpolate -> kh_ntt, evaluate_over_domain_by_ref -> kh_lde).  The reference calls them from
 // 15 / 16 rayon workers at once (prover.rs:370-381, constraints.rs:488-494), one column each, and each call moves 2 + 2 (or 2 + 16) MB over PCIe around
@@ -581,49 +488,34 @@ int index_columns_dev(int field, const uint8_t* selcol_dev, const uint32_t* wire
                       size_t zk_rows, const uint64_t* shifts, size_t ncol, uint64_t* d1_dev) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
     KH_REQUIRE(d1_dev && shifts && (n_gates == 0 || (selcol_dev && wires_dev && coeffs_dev)), "index_columns_dev: null argument");
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = poly_index_columns(C, field, selcol_dev, wires_dev, coeffs_dev, n_gates, n, zk_rows, shifts, ncol, d1_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return poly_index_columns(C, field, selcol_dev, wires_dev, coeffs_dev, n_gates, n, zk_rows, shifts, ncol, d1_dev); });
 }
 // the lookup passes of kh_prover_index_create_lookup (kernels in lookup_index.hip), queued on the main stream
-#define KH_LOOKUP_STEP(call)                                                                     \
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);     \
-    int rc = ensure_init(); if (rc) return rc;                                                  \
-    Context& C = ctx();                                                                         \
-    std::lock_guard<std::mutex> lk(C.mu);                                                       \
-    rc = call;                                                                                  \
-    if (rc == KH_OK) C.mark_async();                                                            \
-    return rc
 int lookup_selectors_dev(int field, const uint8_t* code_dev, size_t n_gates, size_t n, const int* patterns, size_t npat, uint64_t* out_dev) {
     KH_REQUIRE(code_dev && patterns && out_dev, "lookup_selectors_dev: null argument");
-    KH_LOOKUP_STEP(lookup_selector_columns(C, field, code_dev, n_gates, n, patterns, npat, out_dev));
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    return queue_step([&](Context& C) { return lookup_selector_columns(C, field, code_dev, n_gates, n, patterns, npat, out_dev); });
 }
 int lookup_tables_dev(int field, const uint64_t* segs_dev, const uint64_t* seg_starts, size_t nseg, const uint64_t* data_dev, size_t n, size_t width, uint64_t* tcols_dev,
                       uint64_t* ids_dev, uint64_t* rtsel_dev, size_t rt_offset, size_t rt_len, size_t zk_rows) {
     KH_REQUIRE(segs_dev && seg_starts && tcols_dev, "lookup_tables_dev: null argument");
-    KH_LOOKUP_STEP(lookup_table_columns(C, field, segs_dev, seg_starts, nseg, data_dev, n, width, tcols_dev, ids_dev, rtsel_dev, rt_offset, rt_len, zk_rows));
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    return queue_step([&](Context& C) { return lookup_table_columns(C, field, segs_dev, seg_starts, nseg, data_dev, n, width, tcols_dev, ids_dev, rtsel_dev, rt_offset, rt_len, zk_rows); });
 }
 int lookup_atom_denominators_dev(int field, const uint64_t* x8_dev, size_t n, size_t zk_rows, const uint64_t a[4], const uint64_t omega[4], uint64_t* atoms_dev) {
     KH_REQUIRE(x8_dev && a && omega && atoms_dev, "lookup_atom_denominators_dev: null argument");
-    KH_LOOKUP_STEP(lookup_atom_denominators(C, field, x8_dev, n, zk_rows, a, omega, atoms_dev));
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    return queue_step([&](Context& C) { return lookup_atom_denominators(C, field, x8_dev, n, zk_rows, a, omega, atoms_dev); });
 }
 int lookup_atom_finish_dev(int field, size_t n, size_t zk_rows, const uint64_t zh8[32], const uint64_t lim0[4], const uint64_t limf[4], uint64_t* atoms_dev) {
     KH_REQUIRE(zh8 && lim0 && limf && atoms_dev, "lookup_atom_finish_dev: null argument");
-    KH_LOOKUP_STEP(lookup_atom_finish(C, field, n, zk_rows, zh8, lim0, limf, atoms_dev));
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "unknown field id %d", field);
+    return queue_step([&](Context& C) { return lookup_atom_finish(C, field, n, zk_rows, zh8, lim0, limf, atoms_dev); });
 }
-#undef KH_LOOKUP_STEP
 // the gate part of the constant term of a batch of proofs (csrc/verifier.cpp; kernels in gates.hip), queued on the main stream
 int verifier_gate_terms_dev(int field, const uint64_t* cols_host, size_t ncols, size_t items, const GateBatchLaunch* launches, size_t nl, uint64_t* out_dev,
                             const uint64_t** cols_dev) {
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = gate_batch_run(C, field, cols_host, ncols, items, launches, nl, out_dev, cols_dev);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
+    return queue_step([&](Context& C) { return gate_batch_run(C, field, cols_host, ncols, items, launches, nl, out_dev, cols_dev); });
 }
 // the kernels of kh_witness_check (csrc/prover.cpp; witness_check.hip).  The scratch block comes from the kh_dev_alloc pool, taken before the context's lock like
 // kh_lookup_sorted_dev's; the read-back of the four status words, outside the lock, is the call's only wait.  lookups: what to check of them, or NULL.
@@ -631,7 +523,7 @@ int witness_check_dev(int field, const uint64_t* witness_dev, const uint64_t* d1
                       const uint64_t endo[4], const uint32_t* wires_dev, size_t n_gates, const WitnessLookups* lookups, uint64_t status[4]) {
     KH_REQUIRE(status, "witness_check_dev: null argument");
     int rc = ensure_init(); if (rc) return rc;
-    struct Scratch { void* p = nullptr; ~Scratch() { if (p) (void)kh_dev_free(p); } } scratch;
+    PoolBlock scratch;
     if ((rc = kh_dev_alloc(&scratch.p, witness_check_scratch_bytes() + (lookups ? witness_check_lookup_scratch_bytes(lookups->L, lookups->W, lookups->rt_len) : 0)))) return rc;
     {
         Context& C = ctx();

@@ -290,15 +290,14 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
     hipStream_t s = C.stream;
     const dim3 grid((unsigned)((n + 127) / 128));
     C.timer.begin(s);
-#define KH_WITNESS_GATE_LAUNCH(ID, NAME)                                                                                          \
+#define KH_WITNESS_GATE_STEP(ID, NAME)                                                                                            \
     if ((size_t)ID < ngate_ids && sel_col[ID] >= 0) {                                                                             \
         a.sel = d1_dev + 4 * (size_t)sel_col[ID] * n; a.consts = status + wc_const_words(ID); a.gate = ID;                      \
-        if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_witness_gate_##NAME<FpParams>), grid, dim3(128), 0, s, a);                \
-        else hipLaunchKernelGGL((k_witness_gate_##NAME<FqParams>), grid, dim3(128), 0, s, a);                                     \
+        KH_FIELD_LAUNCH(field, k_witness_gate_##NAME<F>, grid, dim3(128), 0, s, a);                                               \
         C.timer.mark("check_" #NAME, s);                                                                                          \
     }
-    KH_FOR_EACH_CHECKED_GATE(KH_WITNESS_GATE_LAUNCH)
-#undef KH_WITNESS_GATE_LAUNCH
+    KH_FOR_EACH_CHECKED_GATE(KH_WITNESS_GATE_STEP)
+#undef KH_WITNESS_GATE_STEP
     if (wires_dev && n_gates) {
         const size_t total = 7 * n_gates;                // < 2^32: n_gates <= 2^26
         hipLaunchKernelGGL(k_witness_wires, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, s, witness_dev, wires_dev, (u32)n, (u32)total, status);

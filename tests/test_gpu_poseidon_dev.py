@@ -384,6 +384,8 @@ def test_refusals_leave_everything_untouched(khip):
         assert call() == khip.E_INVALID, what
         text = lib.kh_last_error().decode()
         assert text.strip(), what
+        if what.startswith("gate rows:"):
+            assert "kh_poseidon_gate_witness_dev" in text, (what, text)
         if what == "gate rows: an instance past the end":
             assert "instance 2" in text, text
     for buf, elems in ((states, 3 * n), (dig, n), (msgs, 2 * n), (wit, 15 * COL_LEN), (out, 3 * n)):
