@@ -369,6 +369,83 @@ int kh_curve_witness_set_slice_elements(size_t elements);
 int kh_endomul_scalar_witness_dev(int field, const uint64_t *chals_dev, unsigned num_bits, size_t n, const uint32_t *rows, size_t row0, size_t row_stride,
                                   uint64_t *witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t *out_dev);
 
+/* ---- The optional gates' witness on the device (csrc/limb_gadgets.hip) ----
+ * RangeCheck0 / RangeCheck1 (the multi-range-check), Xor16, Rot64, ForeignFieldAdd and ForeignFieldMul: with the two blocks above, the witness of every
+ * gate of the library, written in place from 8 to 96 bytes of input per instance.  The conventions are those of the Poseidon and curve-gate blocks.
+ * witness_dev: 15 columns, column c at witness_dev + 4 * c * col_stride, col_len rows each.  Instance i starts at row rows[i] (host array, copied
+ * before the call returns), or at row0 + i * row_stride when rows == NULL.  The calls are vector steps: queued on the main stream of the calling
+ * thread's current context and ordered against every other call of the library -- a producer followed by a consumer needs no kh_sync; none of them
+ * waits for the device.  n == 0 is KH_OK with nothing launched.  KH_E_INVALID with a kh_last_error text that names the call, before anything is
+ * launched and with nothing written: an unknown field, a null pointer with n > 0, a misaligned device pointer, byte counts that overflow, an
+ * instance that does not fit col_len (naming it), row_stride smaller than the instance's row count when rows == NULL, col_stride < col_len, a bad
+ * compact, bits, rot, sign or modulus.  Overlapping instances are the caller's responsibility.
+ * Inputs are plain integers, not field elements: an 88-bit limb is two uint64_t, little-endian, 16-byte aligned; a foreign element or a range-check
+ * triple is three limbs (48 bytes, least significant limb first); Rot64 words are one uint64_t each (8-byte aligned); Xor operands are 4 uint64_t,
+ * little-endian (16-byte aligned).  Every cell written is the canonical Montgomery element of the integer the tables below give (a negative one reduced
+ * mod p: carry = -1 is p - 1).  bits(v, lo, hi) is bits lo .. hi - 1 of v, L = 2^88.
+ * flags_dev, bit: as for kh_check_equal_dev and kh_varbasemul_witness_dev -- bit `bit` (< 32) of a caller-zeroed device uint32_t (nullable) is set
+ * when any instance's input is out of range, and is not touched otherwise.  That instance's own cells are unspecified (inside its own rows); every
+ * other instance of the call is exact.
+ * One lane per (instance, row): a wave's store to a column covers consecutive rows when the instances are packed densely. */
+
+/* host only, no device: the coefficients a gate list for kh_prover_index_create* carries on the foreign-field rows of the modulus f (3 limbs of two
+ * uint64_t, not zero, each < 2^88; nf = 2^264 - f in limbs) -- ForeignFieldMul's four (f2, nf0, nf1, nf2), then ForeignFieldAdd's three (f0, f1, f2;
+ * the caller appends the sign); out: 7 x 4 Montgomery limbs */
+int kh_foreign_field_gate_coefficients(int field, const uint64_t modulus[6], uint64_t *out);
+
+/* The multi-range-check (range_check/witness.rs): limbs_dev = n x 3 limbs v0 v1 v2; 4 rows per instance -- RangeCheck0, RangeCheck0, RangeCheck1,
+ * Zero --, all 60 cells written.  The rows carry (x0, x1, x2) = (v0, v1, v2), or (v2, v0, v1) when compact == 1 (the gate list's second row then has
+ * coefficient 0 = 1).
+ *   rows 0, 1 (x = x0, x1):  col 0 = x;  col 1 + k = bits(x, 76 - 12 k, 88 - 12 k), k = 0..5;  col 7 + k = bits(x, 14 - 2 k, 16 - 2 k), k = 0..7
+ *   row 2:  col 0 = x2;  col 1 = 0, or v0 + L v1 when compact;  col 2 = bits(x2, 86, 88);  col 3 + k = bits(x2, 74 - 12 k, 86 - 12 k), k = 0..3;
+ *           col 7 + k = bits(x2, 36 - 2 k, 38 - 2 k), k = 0..7
+ *   row 3:  cols 0, 1, 2 = bits(x2, 20, 22), bits(x2, 18, 20), bits(x2, 16, 18);  cols 3, 4 = row 0's cols 1, 2;  cols 5, 6 = row 1's cols 1, 2;
+ *           col 7 + k = bits(x2, 14 - 2 k, 16 - 2 k), k = 0..7
+ * The flag is set when a limb is >= 2^88. */
+int kh_range_check_witness_dev(int field, const uint64_t *limbs_dev, size_t n, int compact, const uint32_t *rows, size_t row0, size_t row_stride,
+                               uint64_t *witness_dev, size_t col_stride, size_t col_len, uint32_t *flags_dev, unsigned bit);
+
+/* xor.rs create_xor_witness: in1_dev, in2_dev = n x 4 words; bits from 1 to 254; ceil(bits / 16) Xor16 rows + the closing row per instance, all 15
+ * cells of each written, the closing row zero.  Row i: cols 0, 1, 2 = in1 >> 16 i, in2 >> 16 i, (in1 ^ in2) >> 16 i; cols 3..6, 7..10, 11..14 = the
+ * four low nybbles of each of those, lowest first.  out_dev (nullable): n x 4 words, in1 ^ in2.  The flag is set when an operand is >= 2^bits. */
+int kh_xor_witness_dev(int field, const uint64_t *in1_dev, const uint64_t *in2_dev, unsigned bits, size_t n, const uint32_t *rows, size_t row0,
+                       size_t row_stride, uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev, uint32_t *flags_dev, unsigned bit);
+
+/* rot.rs create_witness: words_dev = n words, rotated left by rot (0..63; the gate list's Rot64 row has coefficient 0 = 2^rot); 3 rows per instance,
+ * all 45 cells written.  excess = (w << rot) >> 64, shifted = (w << rot) mod 2^64, rotated = shifted + excess, bound = excess - 2^rot + 2^64.
+ *   row 0 (Rot64):  cols 0, 1, 2 = w, rotated, excess;  col 3 + k = bits(bound, 52 - 12 k, 64 - 12 k), k = 0..3;
+ *                   col 7 + k = bits(bound, 14 - 2 k, 16 - 2 k), k = 0..7
+ *   rows 1, 2:      the RangeCheck0 rows of shifted and of excess, as rows 0, 1 of kh_range_check_witness_dev
+ * out_dev (nullable): n words, rotated. */
+int kh_rot64_witness_dev(int field, const uint64_t *words_dev, unsigned rot, size_t n, const uint32_t *rows, size_t row0, size_t row_stride,
+                         uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev);
+
+/* foreign_field_add/witness.rs, one operation per instance: left_dev, right_dev = n x 3 limbs; sign = +1 or -1.  r = left + sign right - overflow f
+ * with overflow in {0, sign} such that 0 <= r < f; carry = (lo(left) + sign lo(right) - overflow lo(f) - lo(r)) / 2^176 with lo(x) = x0 + L x1, one
+ * of -1, 0, 1.  Written: cells 0..7 of the gate row -- left limbs, right limbs, overflow, carry -- and cells 0..2 of the next row, the limbs of r.
+ * NOTHING else.  An instance counts as 2 rows; a chain whose operations share their result rows is placed through rows[].  out_dev (nullable):
+ * n x 3 limbs, r.  The flag is set when no such r exists: an operand >= f, or a limb >= 2^88.  (The final bound row of the reference's chain gadget
+ * is not written by this call.) */
+int kh_foreign_field_add_witness_dev(int field, const uint64_t modulus[6], const uint64_t *left_dev, const uint64_t *right_dev, int sign, size_t n,
+                                     const uint32_t *rows, size_t row0, size_t row_stride, uint64_t *witness_dev, size_t col_stride, size_t col_len,
+                                     uint64_t *out_dev, uint32_t *flags_dev, unsigned bit);
+
+/* foreign_field_mul/witness.rs: a_dev, b_dev = n x 3 limbs; 2 rows per instance, ForeignFieldMul and Zero.  (q, r) = divmod(a b, f), exact;
+ * nf = 2^264 - f in limbs;  p0 = a0 b0 + q0 nf0,  p1 = a0 b1 + a1 b0 + q0 nf1 + q1 nf0,  p2 = a0 b2 + a2 b0 + a1 b1 + q0 nf2 + q2 nf0 + q1 nf1;
+ * p1_lo = p1 mod L, p1_hi = p1 >> 88, p1_hi0 = p1_hi mod L, p1_hi1 = p1_hi >> 88;  carry0 = (p0 + L p1_lo - r0 - L r1) >> 176;
+ * carry1 = (p2 + p1_hi + carry0 - r2) >> 88.
+ *   gate row, all 15 cells:  cols 0..2 = a;  cols 3..5 = b;  col 6 = p1_lo;  col 7 + k = bits(carry1, 12 k, 12 k + 12), k = 0..3;
+ *                            cols 11, 12, 13 = bits(carry1, 84, 86), (86, 88), (88, 90);  col 14 = bits(carry1, 90, 91)
+ *   next row, cells 0..11:   col 0 = r0 + L r1;  col 1 = r2;  cols 2..4 = q;  col 5 = q2 + L - f2 - 1;  col 6 = p1_hi0;  col 7 = p1_hi1;
+ *                            col 8 + k = bits(carry1, 48 + 12 k, 60 + 12 k), k = 0..2;  col 11 = carry0.  Cells 12..14 are NOT written.
+ * out_checks_dev (nullable): n x 9 limbs -- (q0, q1, q2), (r0, r1, r2), (q2 + L - f2 - 1, p1_lo, p1_hi0) --, three triples in the input format of
+ * kh_range_check_witness_dev: the gate's external range checks are one call of that with 3 n instances and no host round trip.
+ * The flag is set when an input limb is >= 2^88 or a value does not fit its cell: q >= 2^264, carry0 >= 4, p1_hi1 >= 4, carry1 >= 2^91.
+ * The division is Barrett's, with mu = floor(2^528 / f) computed on the host per call and the full product: a fixed trip count, no lane diverges. */
+int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const uint64_t *a_dev, const uint64_t *b_dev, size_t n, const uint32_t *rows,
+                                     size_t row0, size_t row_stride, uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_checks_dev,
+                                     uint32_t *flags_dev, unsigned bit);
+
 /* ---- scans, batch inversion, division by a linear factor: the permutation argument's vector steps ----
  * kh_field_scan_dev: in-place inclusive prefix (reverse = 0) or suffix (reverse = 1) scan under + or *
  *   (the running product z[j+1] = z[j] * ..., kimchi/src/circuits/polynomials/permutation.rs:556-563).

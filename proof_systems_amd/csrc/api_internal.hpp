@@ -125,4 +125,16 @@ int chain_rows(Context& C, int field, bool is_endo, const uint64_t* endo, const 
                unsigned num_bits, size_t n, const WitnessPlace& at, uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit,
                uint64_t* scratch_dev, size_t scratch_bytes);
 void chain_set_slice_elements(size_t elems);
+// limb_gadgets.hip: the launchers of kh_range_check_witness_dev, kh_xor_witness_dev, kh_rot64_witness_dev, kh_foreign_field_add_witness_dev and
+// kh_foreign_field_mul_witness_dev, queued on C.stream (arguments validated by the entry points; n >= 1, n times the instance's rows <= WAVE_BLOCK_MAX_N;
+// modulus: 3 limbs of two u64 on the host, non-zero, each < 2^88).  ff_negated_modulus is host only: the limbs of 2^264 - f.
+int range_check_rows(Context& C, int field, const uint64_t* limbs_dev, size_t n, int compact, const WitnessPlace& at, uint32_t* flags_dev, unsigned bit);
+int xor_rows(Context& C, int field, const uint64_t* in1_dev, const uint64_t* in2_dev, unsigned bits, size_t n, const WitnessPlace& at, uint64_t* out_dev,
+             uint32_t* flags_dev, unsigned bit);
+int rot64_rows(Context& C, int field, const uint64_t* words_dev, unsigned rot, size_t n, const WitnessPlace& at, uint64_t* out_dev);
+int ff_add_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* left_dev, const uint64_t* right_dev, int sign, size_t n, const WitnessPlace& at,
+                uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
+int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
+                uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit);
+void ff_negated_modulus(const uint64_t* modulus, uint64_t* nf_out);
 }  // namespace kh

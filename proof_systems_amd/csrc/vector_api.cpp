@@ -1,4 +1,4 @@
-// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve gates' kh_*_witness_dev, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve and limb gates' kh_*_witness_dev, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
 #include <stdlib.h>
 
 #include "api_internal.hpp"
@@ -257,13 +257,13 @@ int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t co
     }
     return KH_OK;
 }
-struct GadgetPtr { const char* name; const void* p; bool required; };
-// what the five calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
+struct GadgetPtr { const char* name; const void* p; bool required; unsigned align = 16; };
+// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
 int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
     for (const GadgetPtr& a : ptrs) {
         KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
-        KH_REQUIRE((((uintptr_t)a.p) & 15) == 0, "%s: %s must be 16-byte aligned", call, a.name);
+        KH_REQUIRE((((uintptr_t)a.p) & (a.align - 1)) == 0, "%s: %s must be %u-byte aligned", call, a.name, a.align);
     }
     return place_validate(call, at, n, col_len, inst_rows);
 }
@@ -347,6 +347,93 @@ int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t* ba
                          WitnessPlace{rows, row0, row_stride, witness_dev, col_stride}, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
 }
 int kh_curve_witness_set_slice_elements(size_t elements) { chain_set_slice_elements(elements); return KH_OK; }
+
+// ---------------------------------------------------------------------------------- the optional gates' witnesses (kernels in limb_gadgets.hip)
+// what the five limb gadgets refuse alike after their own arguments: gadget_validate's list, more lanes (one per instance and row) than a grid takes, a
+// flag word that is misaligned or a bit that is not one
+static int limb_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows,
+                         const uint32_t* flags_dev = nullptr, unsigned bit = 0) {
+    int rc = gadget_validate(call, field, ptrs, n, at, col_len, inst_rows);
+    if (rc) return rc;
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / inst_rows, "%s: %zu instances of %zu rows overflow the byte count", call, n, inst_rows);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
+    return KH_OK;
+}
+// a foreign modulus: three limbs of two u64 on the host, each < 2^88, not all zero
+static int modulus_validate(const char* call, const uint64_t* modulus, size_t n) {
+    KH_REQUIRE(modulus || n == 0, "%s: null modulus", call);
+    if (!modulus) return KH_OK;
+    KH_REQUIRE((modulus[1] | modulus[3] | modulus[5]) >> 24 == 0, "%s: a modulus limb is 2^88 or more", call);
+    KH_REQUIRE((modulus[0] | modulus[1] | modulus[2] | modulus[3] | modulus[4] | modulus[5]) != 0, "%s: the modulus is zero", call);
+    return KH_OK;
+}
+int kh_foreign_field_gate_coefficients(int field, const uint64_t modulus[6], uint64_t* out) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "kh_foreign_field_gate_coefficients: unknown field id %d", field);
+    KH_REQUIRE(out, "kh_foreign_field_gate_coefficients: null output");
+    int rc = modulus_validate("kh_foreign_field_gate_coefficients", modulus, 1);
+    if (rc) return rc;
+    uint64_t nf[6];
+    ff_negated_modulus(modulus, nf);
+    const khost::Fld F(field);
+    const uint64_t* const src[7] = {modulus + 4, nf, nf + 2, nf + 4, modulus, modulus + 2, modulus + 4};       // f2 nf0 nf1 nf2 | f0 f1 f2
+    for (size_t k = 0; k < 7; k++) {
+        const khost::fe v = F.to_mont(khost::fe{{src[k][0], src[k][1], 0, 0}});
+        memcpy(out + 4 * k, v.l, 32);
+    }
+    return KH_OK;
+}
+int kh_range_check_witness_dev(int field, const uint64_t* limbs_dev, size_t n, int compact, const uint32_t* rows, size_t row0, size_t row_stride,
+                               uint64_t* witness_dev, size_t col_stride, size_t col_len, uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(compact == 0 || compact == 1, "kh_range_check_witness_dev: compact is %d, not 0 or 1", compact);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = limb_validate("kh_range_check_witness_dev", field, {{"limbs_dev", limbs_dev, true}}, n, at, col_len, 4, flags_dev, bit);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return range_check_rows(C, field, limbs_dev, n, compact, dev, flags_dev, bit); });
+}
+int kh_xor_witness_dev(int field, const uint64_t* in1_dev, const uint64_t* in2_dev, unsigned bits, size_t n, const uint32_t* rows, size_t row0,
+                       size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(bits >= 1 && bits <= 254, "kh_xor_witness_dev: bits %u is not from 1 to 254", bits);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = limb_validate("kh_xor_witness_dev", field, {{"in1_dev", in1_dev, true}, {"in2_dev", in2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len,
+                           (bits + 15) / 16 + 1, flags_dev, bit);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return xor_rows(C, field, in1_dev, in2_dev, bits, n, dev, out_dev, flags_dev, bit); });
+}
+int kh_rot64_witness_dev(int field, const uint64_t* words_dev, unsigned rot, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
+                         uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
+    KH_REQUIRE(rot <= 63, "kh_rot64_witness_dev: rot %u is not from 0 to 63", rot);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = limb_validate("kh_rot64_witness_dev", field, {{"words_dev", words_dev, true, 8}, {"out_dev", out_dev, false, 8}}, n, at, col_len, 3);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return rot64_rows(C, field, words_dev, rot, n, dev, out_dev); });
+}
+int kh_foreign_field_add_witness_dev(int field, const uint64_t modulus[6], const uint64_t* left_dev, const uint64_t* right_dev, int sign, size_t n,
+                                     const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
+                                     uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(sign == 1 || sign == -1, "kh_foreign_field_add_witness_dev: sign is %d, not +1 or -1", sign);
+    int rc = modulus_validate("kh_foreign_field_add_witness_dev", modulus, n);
+    if (rc) return rc;
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    rc = limb_validate("kh_foreign_field_add_witness_dev", field, {{"left_dev", left_dev, true}, {"right_dev", right_dev, true}, {"out_dev", out_dev, false}}, n, at,
+                       col_len, 2, flags_dev, bit);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
+        return ff_add_rows(C, field, modulus, left_dev, right_dev, sign, n, dev, out_dev, flags_dev, bit);
+    });
+}
+int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const uint32_t* rows,
+                                     size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_checks_dev,
+                                     uint32_t* flags_dev, unsigned bit) {
+    int rc = modulus_validate("kh_foreign_field_mul_witness_dev", modulus, n);
+    if (rc) return rc;
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    rc = limb_validate("kh_foreign_field_mul_witness_dev", field, {{"a_dev", a_dev, true}, {"b_dev", b_dev, true}, {"out_checks_dev", out_checks_dev, false}}, n, at,
+                       col_len, 2, flags_dev, bit);
+    if (rc) return rc;
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
+        return ff_mul_rows(C, field, modulus, a_dev, b_dev, n, dev, out_checks_dev, flags_dev, bit);
+    });
+}
 
 // ---------------------------------------------------------------------------------- NTT
 int kh_domain_generator(int field, unsigned log2_n, uint64_t out[4]) {

@@ -769,6 +769,63 @@ def endomul_scalar_witness_dev(field: int, chals, num_bits: int, n: int, witness
                                               _ptr(witness), col_stride, col_len, _p64(es) if es is not None else None, _ptr(out)))
 
 
+def _modulus6(modulus: int):
+    """a foreign modulus as the calls take it: three 88-bit limbs of two uint64 each"""
+    L = 1 << 88
+    limbs = [(modulus >> (88 * k)) % L if k < 2 else modulus >> 176 for k in range(3)]
+    if modulus < 0 or limbs[2] >= 1 << 128:
+        raise ValueError("foreign modulus out of range")
+    return np.array([w for v in limbs for w in (v & ((1 << 64) - 1), v >> 64)], dtype=np.uint64)
+
+
+def foreign_field_gate_coefficients(field: int, modulus: int):
+    """kh_foreign_field_gate_coefficients (host only): (7, 4) Montgomery limbs -- ForeignFieldMul's f2, nf0, nf1, nf2, then ForeignFieldAdd's f0, f1, f2."""
+    out = np.zeros((7, 4), dtype=np.uint64)
+    _check(_lib.kh_foreign_field_gate_coefficients(field, _p64(_modulus6(modulus)), _p64(out)))
+    return out
+
+
+def range_check_witness_dev(field: int, limbs, n: int, witness, col_stride: int, col_len: int, compact: bool = False, rows=None, row0: int = 0,
+                            row_stride: int = 4, flags=None, bit: int = 0):
+    """kh_range_check_witness_dev: the 4 multi-range-check rows of n triples of 88-bit limbs (n x 3 x 2 uint64 at `limbs`) into the 15 columns at
+    `witness`, instance i at row rows[i] or row0 + i * row_stride; flags (a DevBuf holding a zeroed uint32) gets bit `bit` set when a limb is >= 2^88."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_range_check_witness_dev(field, _ptr(limbs), n, int(compact), rp, row0, row_stride, _ptr(witness), col_stride, col_len, _ptr(flags), bit))
+
+
+def xor_witness_dev(field: int, in1, in2, bits: int, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0, row_stride: int = None,
+                    out=None, flags=None, bit: int = 0):
+    """kh_xor_witness_dev: the ceil(bits / 16) Xor16 rows + the zero row of n pairs of operands (n x 4 uint64 each); out (nullable): in1 ^ in2; the flag
+    is set when an operand is >= 2^bits."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_xor_witness_dev(field, _ptr(in1), _ptr(in2), bits, n, rp, row0, (bits + 15) // 16 + 1 if row_stride is None else row_stride,
+                                   _ptr(witness), col_stride, col_len, _ptr(out), _ptr(flags), bit))
+
+
+def rot64_witness_dev(field: int, words, rot: int, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0, row_stride: int = 3, out=None):
+    """kh_rot64_witness_dev: the Rot64 row and the two RangeCheck0 rows of n words rotated left by rot; out (nullable): the n rotated words."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_rot64_witness_dev(field, _ptr(words), rot, n, rp, row0, row_stride, _ptr(witness), col_stride, col_len, _ptr(out)))
+
+
+def foreign_field_add_witness_dev(field: int, modulus: int, left, right, sign: int, n: int, witness, col_stride: int, col_len: int, rows=None,
+                                  row0: int = 0, row_stride: int = 2, out=None, flags=None, bit: int = 0):
+    """kh_foreign_field_add_witness_dev: cells 0..7 of the ForeignFieldAdd row and 0..2 of the next of n operations left + sign * right mod `modulus`
+    (operands n x 3 x 2 uint64); out (nullable): the results' limbs; the flag is set when an operand is >= modulus."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_foreign_field_add_witness_dev(field, _p64(_modulus6(modulus)), _ptr(left), _ptr(right), sign, n, rp, row0, row_stride, _ptr(witness),
+                                                 col_stride, col_len, _ptr(out), _ptr(flags), bit))
+
+
+def foreign_field_mul_witness_dev(field: int, modulus: int, a, b, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0,
+                                  row_stride: int = 2, out_checks=None, flags=None, bit: int = 0):
+    """kh_foreign_field_mul_witness_dev: the ForeignFieldMul row and cells 0..11 of the next of n products a * b mod `modulus`; out_checks (nullable,
+    n x 9 limbs): quotient, remainder and (bound, p1_lo, p1_hi0), three range-check triples per instance for range_check_witness_dev."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_foreign_field_mul_witness_dev(field, _p64(_modulus6(modulus)), _ptr(a), _ptr(b), n, rp, row0, row_stride, _ptr(witness), col_stride,
+                                                 col_len, _ptr(out_checks), _ptr(flags), bit))
+
+
 class Comm:
     """kh_comm_*: the in-library RCCL communicator of the one-process-per-GPU deployment (no torch).  Comm.unique_id() on one rank, the bytes to
     the others, Comm(world, rank, id) on every rank."""
