@@ -446,6 +446,53 @@ int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const
                                      size_t row0, size_t row_stride, uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_checks_dev,
                                      uint32_t *flags_dev, unsigned bit);
 
+/* ---- Wires between the gadgets on the device (csrc/wiring.hip) ----
+ * A gadget leaves its result in a witness cell as a Montgomery element; the next one takes its input in a format of its own.  Two cell-level calls
+ * convert between cells and every input format of the three blocks above, and one writes the generic rows between gadgets, so that a circuit's
+ * witness is chained on the device without a download, a host conversion, an upload and a kh_sync per hop.
+ * cells: a host array of n (row, column) pairs, in the order of `wires` in kh_prover_index_create, copied before the call returns.  Any of the 15
+ * columns is allowed; only columns 0..6 carry copy constraints.  witness_dev, col_stride, col_len as above.  The calls are vector steps: queued on the
+ * main stream of the calling thread's current context and ordered against every other call of the library; none of them waits for the device.
+ * n == 0 is KH_OK with nothing launched.  KH_E_INVALID with a kh_last_error text that names the call, before anything is launched and with nothing
+ * written: an unknown field or format, half not 0 or 1, a null pointer with n > 0, a misaligned device pointer (16 bytes; 8 for KH_CELL_U64 data),
+ * byte counts that overflow, col_stride < col_len, a cell with row >= col_len or column >= 15 (naming its index), a generic instance that does not fit.
+ * flags_dev, bit: as for kh_check_equal_dev and the limb gadgets -- bit `bit` (< 32) of a caller-zeroed device uint32_t (nullable) is set when any
+ * value of the call does not fit its format, and is not touched otherwise.  Every other value of the call is exact.
+ * One lane per cell or instance: a cell is one 32-byte access wherever it lies, the dense side is consecutive across the wave. */
+enum { KH_CELL_FIELD = 0,   /* 4 words: the cell as it is, a Montgomery element                          */
+       KH_CELL_INT256 = 1,  /* 4 words: the canonical integer (< p) -- scalars_dev, Xor operands         */
+       KH_CELL_INT128 = 2,  /* 2 words -- chals_dev of EndoMul / EndoMulScalar                           */
+       KH_CELL_LIMB88 = 3,  /* 2 words, value < 2^88 -- the limb of the range-check / foreign-field calls */
+       KH_CELL_U64 = 4 };   /* 1 word -- the Rot64 word                                                  */
+
+/* out_dev[i] = cell i in `format`, packed densely (4, 4, 2, 2 or 1 words each).  KH_CELL_FIELD copies the four limbs: no arithmetic, never a flag.
+ * The other formats deliver v, the canonical integer the cell stands for (one Montgomery product by 1 and the final reduction): KH_CELL_INT256 all of
+ * it; KH_CELL_INT128, KH_CELL_LIMB88 and KH_CELL_U64 its low 128, 88 or 64 bits -- exactly those, also when the flag is set, which it is when
+ * v >= 2^128, 2^88 or 2^64.  Cells may repeat.  The witness is not written; out_dev must not overlap it.  Cells are assumed canonical (< p) and are
+ * not checked. */
+int kh_witness_gather_dev(int field, const uint64_t *witness_dev, size_t col_stride, size_t col_len,
+                          const uint32_t *cells /* host, n x 2: (row, column) */, size_t n, int format,
+                          uint64_t *out_dev, uint32_t *flags_dev, unsigned bit);
+
+/* Cell i becomes the canonical Montgomery element of values_dev[i] (KH_CELL_FIELD: copied as it is).  The flag is set by a KH_CELL_INT256 value >= p
+ * and by a KH_CELL_LIMB88 value >= 2^88; such a cell is unspecified.  NOTHING else is written.  Target cells that repeat are the caller's
+ * responsibility.  A cell-to-cell copy is a KH_CELL_FIELD gather followed by a KH_CELL_FIELD scatter. */
+int kh_witness_scatter_dev(int field, const uint64_t *values_dev, int format,
+                           const uint32_t *cells /* host, n x 2 */, size_t n,
+                           uint64_t *witness_dev, size_t col_stride, size_t col_len,
+                           uint32_t *flags_dev, unsigned bit);
+
+/* generic.rs: one half of a double generic row per instance, an instance being ONE row placed like a gadget's (rows[i], or row0 + i * row_stride).
+ * half 0 writes cells 0, 1, 2, half 1 cells 3, 4, 5: l, r and o = -(c_l l + c_r r + c_m l r + c_c) / c_o, NOTHING else -- two calls with half 0 and 1
+ * may target the same rows.  coeffs: that half's five coefficients in generic.rs order, l r o m c (coefficients 5 * half .. 5 * half + 4 of the gate
+ * row), canonical Montgomery limbs on the host.  1 / c_o is computed once per call on the host: no lane inverts.  c_o = 0 (a constant or a public
+ * input: the row constrains l and defines nothing) writes o = 0, as the reference's generators leave it.  l_dev, r_dev: n x 4 Montgomery limbs
+ * (r_dev nullable: r = 0).  out_dev (nullable): the n values of o, Montgomery. */
+int kh_generic_witness_dev(int field, const uint64_t coeffs[20] /* host: l r o m c, Montgomery */, int half,
+                           const uint64_t *l_dev, const uint64_t *r_dev /* nullable: r = 0 */, size_t n,
+                           const uint32_t *rows, size_t row0, size_t row_stride,
+                           uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev /* nullable */);
+
 /* ---- scans, batch inversion, division by a linear factor: the permutation argument's vector steps ----
  * kh_field_scan_dev: in-place inclusive prefix (reverse = 0) or suffix (reverse = 1) scan under + or *
  *   (the running product z[j+1] = z[j] * ..., kimchi/src/circuits/polynomials/permutation.rs:556-563).

@@ -137,4 +137,13 @@ int ff_add_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* 
 int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
                 uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit);
 void ff_negated_modulus(const uint64_t* modulus, uint64_t* nf_out);
+// wiring.hip: the launchers of kh_witness_gather_dev, kh_witness_scatter_dev and kh_generic_witness_dev, queued on C.stream (arguments validated by the
+// entry points; n >= 1; cells_dev: n (row, column) pairs on the device, every one inside the columns; format: a KH_CELL_* value; coeffs: the half's five
+// coefficients l r o m c on the host, Montgomery -- generic_rows divides by -c_o there, once per call; half: 0 or 1)
+int cell_gather(Context& C, int field, const uint64_t* witness_dev, size_t col_stride, const uint32_t* cells_dev, size_t n, int format, uint64_t* out_dev,
+                uint32_t* flags_dev, unsigned bit);
+int cell_scatter(Context& C, int field, const uint64_t* values_dev, int format, const uint32_t* cells_dev, size_t n, uint64_t* witness_dev, size_t col_stride,
+                 uint32_t* flags_dev, unsigned bit);
+int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
+                 uint64_t* out_dev);
 }  // namespace kh

@@ -1,4 +1,4 @@
-// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve and limb gates' kh_*_witness_dev, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve and limb gates' kh_*_witness_dev and the wiring between them, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
 #include <stdlib.h>
 
 #include "api_internal.hpp"
@@ -238,14 +238,20 @@ int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return 
 // ---------------------------------------------------------------------------------- gadget witnesses on the device (kernels in poseidon.hip, curve_gadgets.hip)
 }  // extern "C"
 namespace {
-// what a placement (WitnessPlace, rows still on the host) is refused for: a null or misaligned witness, columns that overlap or whose byte count
-// overflows, instances of inst_rows rows that do not fit col_len rows
+// what the 15 witness columns of a call that takes n instances (or cells) are refused for: a null or misaligned witness, columns that overlap or whose
+// byte count overflows
+int columns_validate(const char* call, const void* witness, size_t col_stride, size_t col_len, size_t n) {
+    KH_REQUIRE(witness || n == 0, "%s: null witness_dev", call);
+    KH_REQUIRE((((uintptr_t)witness) & 15) == 0, "%s: witness_dev must be 16-byte aligned", call);
+    KH_REQUIRE(col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, col_stride, col_len);
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
+               col_stride);
+    return KH_OK;
+}
+// what a placement (WitnessPlace, rows still on the host) is refused for: its columns, instances of inst_rows rows that do not fit col_len rows
 int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t col_len, size_t inst_rows) {
-    KH_REQUIRE(at.witness || n == 0, "%s: null witness_dev", call);
-    KH_REQUIRE((((uintptr_t)at.witness) & 15) == 0, "%s: witness_dev must be 16-byte aligned", call);
-    KH_REQUIRE(at.col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, at.col_stride, col_len);
-    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && at.col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
-               at.col_stride);
+    int rc = columns_validate(call, at.witness, at.col_stride, col_len, n);
+    if (rc) return rc;
     if (n > 0 && at.rows) {
         for (size_t i = 0; i < n; i++)
             KH_REQUIRE(col_len >= inst_rows && at.rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
@@ -267,25 +273,28 @@ int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr
     }
     return place_validate(call, at, n, col_len, inst_rows);
 }
-// The queueing of a validated call: the start rows travel through the pinned staging ring into a block of the kh_dev_alloc pool (taken before the
-// context's lock, like kh_lookup_sorted_dev's scratch), in pieces that leave the ring its size -- the caller's array is not read after this returns --
-// and launch(C, at) runs with at.rows on the device.
+// The queueing of a validated call with a host table of `words` uint32_t (start rows, cells; nullable): the table travels through the pinned staging
+// ring into a block of the kh_dev_alloc pool (taken before the context's lock, like kh_lookup_sorted_dev's scratch), in pieces that leave the ring its
+// size -- the caller's array is not read after this returns -- and launch(C, table_dev) runs with the table on the device (null without one).
+template <class Launch>
+int table_queue(const uint32_t* table, size_t words, Launch launch) {
+    PoolBlock table_dev;
+    int rc;
+    if (table && (rc = kh_dev_alloc(&table_dev.p, words * sizeof(uint32_t)))) return rc;
+    return queue_step([&](Context& C) {
+        const size_t piece = (size_t)1 << 15;
+        for (size_t i = 0; table && i < words; i += piece) {
+            const int up = C.stage_upload(table_dev.as<uint32_t>() + i, {{table + i, std::min(piece, words - i) * sizeof(uint32_t)}});
+            if (up) return up;
+        }
+        return launch(C, table_dev.as<uint32_t>());
+    });
+}
+// ... of a gadget call: launch(C, at) runs with at.rows on the device
 template <class Launch>
 int gadget_queue(WitnessPlace at, size_t n, Launch launch) {
     if (n == 0) return ensure_init();
-    const uint32_t* const rows = at.rows;
-    PoolBlock rows_dev;
-    int rc;
-    if (rows && (rc = kh_dev_alloc(&rows_dev.p, n * sizeof(uint32_t)))) return rc;
-    at.rows = rows_dev.as<uint32_t>();
-    return queue_step([&](Context& C) {
-        const size_t piece = (size_t)1 << 15;
-        for (size_t i = 0; rows && i < n; i += piece) {
-            const int up = C.stage_upload(rows_dev.as<uint32_t>() + i, {{rows + i, std::min(piece, n - i) * sizeof(uint32_t)}});
-            if (up) return up;
-        }
-        return launch(C, at);
-    });
+    return table_queue(at.rows, n, [&](Context& C, const uint32_t* rows_dev) { at.rows = rows_dev; return launch(C, at); });
 }
 }  // namespace
 extern "C" {
@@ -433,6 +442,52 @@ int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
         return ff_mul_rows(C, field, modulus, a_dev, b_dev, n, dev, out_checks_dev, flags_dev, bit);
     });
+}
+
+// ---------------------------------------------------------------------------------- wires between the gadgets (kernels in wiring.hip)
+// what the two cell calls refuse alike: the field and the format, their columns, the dense buffer (`data`: out_dev / values_dev, aligned to its
+// format's access), the flag word, a cell outside the 15 columns of col_len rows
+static int cells_validate(const char* call, int field, int format, const void* witness, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n,
+                          const char* data_name, const void* data, const uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
+    KH_REQUIRE(format >= KH_CELL_FIELD && format <= KH_CELL_U64, "%s: unknown cell format %d", call, format);
+    int rc = columns_validate(call, witness, col_stride, col_len, n);
+    if (rc) return rc;
+    const unsigned align = format == KH_CELL_U64 ? 8 : 16;
+    KH_REQUIRE((cells && data) || n == 0, "%s: null %s", call, cells ? data_name : "cells");
+    KH_REQUIRE((((uintptr_t)data) & (align - 1)) == 0, "%s: %s must be %u-byte aligned", call, data_name, align);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
+    for (size_t i = 0; i < n; i++)
+        KH_REQUIRE(cells[2 * i] < col_len && cells[2 * i + 1] < 15, "%s: cell %zu at (row %u, column %u) is outside the 15 columns of %zu rows", call, i, cells[2 * i],
+                   cells[2 * i + 1], col_len);
+    return KH_OK;
+}
+int kh_witness_gather_dev(int field, const uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n, int format,
+                          uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
+    int rc = cells_validate("kh_witness_gather_dev", field, format, witness_dev, col_stride, col_len, cells, n, "out_dev", out_dev, flags_dev, bit);
+    if (rc) return rc;
+    if (n == 0) return ensure_init();
+    return table_queue(cells, 2 * n, [&](Context& C, const uint32_t* cells_dev) {
+        return cell_gather(C, field, witness_dev, col_stride, cells_dev, n, format, out_dev, flags_dev, bit);
+    });
+}
+int kh_witness_scatter_dev(int field, const uint64_t* values_dev, int format, const uint32_t* cells, size_t n, uint64_t* witness_dev, size_t col_stride,
+                           size_t col_len, uint32_t* flags_dev, unsigned bit) {
+    int rc = cells_validate("kh_witness_scatter_dev", field, format, witness_dev, col_stride, col_len, cells, n, "values_dev", values_dev, flags_dev, bit);
+    if (rc) return rc;
+    if (n == 0) return ensure_init();
+    return table_queue(cells, 2 * n, [&](Context& C, const uint32_t* cells_dev) {
+        return cell_scatter(C, field, values_dev, format, cells_dev, n, witness_dev, col_stride, flags_dev, bit);
+    });
+}
+int kh_generic_witness_dev(int field, const uint64_t coeffs[20], int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const uint32_t* rows,
+                           size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
+    KH_REQUIRE(half == 0 || half == 1, "kh_generic_witness_dev: half is %d, not 0 or 1", half);
+    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
+    int rc = gadget_validate("kh_generic_witness_dev", field, {{"l_dev", l_dev, true}, {"r_dev", r_dev, false}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
+    if (rc) return rc;
+    KH_REQUIRE(coeffs || n == 0, "kh_generic_witness_dev: null coeffs");
+    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return generic_rows(C, field, coeffs, half, l_dev, r_dev, n, dev, out_dev); });
 }
 
 // ---------------------------------------------------------------------------------- NTT

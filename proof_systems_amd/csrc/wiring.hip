@@ -1,0 +1,139 @@
+// wiring.hip -- what joins two gadgets on the device: single witness cells read into and written from the input formats of the gadget calls, and the
+// generic rows between them (kimchi/src/circuits/polynomials/generic.rs; oracle/circuit.py::generic_spec has the coefficient order), for
+// kh_witness_gather_dev, kh_witness_scatter_dev and kh_generic_witness_dev (csrc/vector_api.cpp).  include/kimchi_hip.h has the formats.
+//
+// Every kernel is ONE LANE PER CELL (or generic instance) in blocks of one wave.  A cell is one 32-byte element at an arbitrary (row, column): two
+// 16-byte accesses per lane that share a 32-byte sector and nothing else with their neighbours', whatever the launch shape -- the witness side moves
+// a sector per cell, the cell list 8 bytes.  The dense side (out_dev, values_dev, l_dev, r_dev) is consecutive across the wave: 32, 16 or 8 bytes per
+// lane.  Spreading a cell over several lanes would split the one Montgomery product its conversion costs; several cells per lane would leave a
+// circuit's worth of wires (a few thousand cells) on a handful of CUs.
+//
+//   k_cell_gather     cell -> value: KH_CELL_FIELD copies; every other format is from_mont (the reduction half of a product), the low words out, the
+//                     high words tested for the flag
+//   k_cell_scatter    value -> cell: KH_CELL_FIELD copies; every other format is one product by R^2; a KH_CELL_INT256 value is compared with p, a
+//                     KH_CELL_LIMB88 value with 2^88, for the flag
+//   k_generic_half    l, r -> l, r, o = l (c_l' + c_m' r) + c_r' r + c_c' with the four coefficients already divided by -c_o on the host (all zero
+//                     when c_o = 0: o = 0): three products, three additions, no inversion on the device
+// The format is a kernel argument: the branches on it are uniform, and a lane diverges from its wave only to raise the flag.
+#include "common.hpp"
+#include "field.cuh"
+#include "api_internal.hpp"
+
+namespace kh {
+
+// cell i of a list of (row, column) pairs in the 15 columns at `witness`
+struct CellList {
+    const u32* cells;
+    size_t col_stride;
+    __device__ __forceinline__ size_t offset(size_t i) const {
+        const uint2 rc = ((const uint2*)cells)[i];
+        return 4 * ((size_t)rc.y * col_stride + rc.x);
+    }
+};
+__device__ __forceinline__ void raise_cell_flag(u32* flags, u32 bit, bool bad) {
+    if (flags && __any(bad) && (threadIdx.x & 63u) == 0) atomicOr(flags, 1u << bit);
+}
+__device__ __forceinline__ u64 word64(const u32* v, int k) { return (u64)v[2 * k] | ((u64)v[2 * k + 1] << 32); }
+
+template <class F>
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_cell_gather(const u64* __restrict__ witness, CellList at, size_t n, int format, u64* __restrict__ out, u32* __restrict__ flags, u32 bit) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        Fe<F> v = Fe<F>::load(witness + at.offset(i));
+        if (format != KH_CELL_FIELD) v = from_mont<F>(v);
+        if (format == KH_CELL_FIELD || format == KH_CELL_INT256) v.store(out + 4 * i);
+        else if (format == KH_CELL_U64) {
+            out[i] = word64(v.v, 0);
+            bad = (word64(v.v, 1) | word64(v.v, 2) | word64(v.v, 3)) != 0;
+        } else {                                                    // two words: 128 bits, or 88
+            const bool limb = format == KH_CELL_LIMB88;
+            const u64 hi = word64(v.v, 1);
+            *(ulonglong2*)(out + 2 * i) = make_ulonglong2(word64(v.v, 0), limb ? hi & 0xffffffu : hi);
+            bad = ((limb ? hi >> 24 : 0) | word64(v.v, 2) | word64(v.v, 3)) != 0;
+        }
+    }
+    raise_cell_flag(flags, bit, bad);
+}
+
+template <class F>
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_cell_scatter(const u64* __restrict__ values, int format, CellList at, size_t n, u64* __restrict__ witness, u32* __restrict__ flags, u32 bit) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
+    bool bad = false;
+    if (i < n) {
+        Fe<F> v = Fe<F>::zero();
+        if (format == KH_CELL_FIELD || format == KH_CELL_INT256) {
+            v = Fe<F>::load(values + 4 * i);
+            if (format == KH_CELL_INT256) {                         // v >= p: v - p does not borrow
+                u32 br = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) br = (u32)(((u64)v.v[k] - Fe<F>::pw(k) - br) >> 63);
+                bad = br == 0;
+            }
+        } else if (format == KH_CELL_U64) {
+            const u64 w = values[i];
+            v.v[0] = (u32)w; v.v[1] = (u32)(w >> 32);
+        } else {
+            const ulonglong2 w = *(const ulonglong2*)(values + 2 * i);
+            bad = format == KH_CELL_LIMB88 && (w.y >> 24) != 0;
+            v.v[0] = (u32)w.x; v.v[1] = (u32)(w.x >> 32); v.v[2] = (u32)w.y; v.v[3] = (u32)(w.y >> 32);
+        }
+        if (format != KH_CELL_FIELD) v = to_mont<F>(v);
+        v.store(witness + at.offset(i));
+    }
+    raise_cell_flag(flags, bit, bad);
+}
+
+struct GenericHalf { u64 l[4][4]; };                                // c_l c_r c_m c_c, each over -c_o
+template <class F>
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_generic_half(const u64* l_in, const u64* r_in, size_t n, GenericHalf co, unsigned col0, WitnessPlace at, u64* out) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const Fe<F> l = Fe<F>::load(l_in + 4 * i), r = r_in ? Fe<F>::load(r_in + 4 * i) : Fe<F>::zero();
+    const Fe<F> cl = Fe<F>::load(co.l[0]), cr = Fe<F>::load(co.l[1]), cm = Fe<F>::load(co.l[2]), cc = Fe<F>::load(co.l[3]);
+    const Fe<F> o = add<F>(add<F>(mul<F>(l, add<F>(cl, mul<F>(cm, r))), mul<F>(cr, r)), cc);
+    const size_t row = at.start_row(i);
+    l.store(at.cell(row, col0)); r.store(at.cell(row, col0 + 1)); o.store(at.cell(row, col0 + 2));
+    if (out) o.store(out + 4 * i);
+}
+
+// (the callers in vector_api.cpp have validated pointers, sizes and every cell; one phase of kh_last_timings per call)
+int cell_gather(Context& C, int field, const uint64_t* witness_dev, size_t col_stride, const uint32_t* cells_dev, size_t n, int format, uint64_t* out_dev,
+                uint32_t* flags_dev, unsigned bit) {
+    C.timer.begin(C.stream);
+    KH_FIELD_LAUNCH(field, k_cell_gather<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)witness_dev, (CellList{cells_dev, col_stride}), n,
+                    format, (u64*)out_dev, flags_dev, (u32)bit);
+    C.timer.mark("cell_gather", C.stream);
+    return KH_OK;
+}
+int cell_scatter(Context& C, int field, const uint64_t* values_dev, int format, const uint32_t* cells_dev, size_t n, uint64_t* witness_dev, size_t col_stride,
+                 uint32_t* flags_dev, unsigned bit) {
+    C.timer.begin(C.stream);
+    KH_FIELD_LAUNCH(field, k_cell_scatter<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)values_dev, format,
+                    (CellList{cells_dev, col_stride}), n, (u64*)witness_dev, flags_dev, (u32)bit);
+    C.timer.mark("cell_scatter", C.stream);
+    return KH_OK;
+}
+int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
+                 uint64_t* out_dev) {
+    const khost::Fld F(field);
+    khost::fe c[5];
+    memcpy(c, coeffs, sizeof(c));                                   // l r o m c
+    GenericHalf co;
+    memset(&co, 0, sizeof(co));
+    if (!khost::is_zero(c[2])) {
+        const khost::fe scale = F.neg(F.inv(c[2]));
+        const khost::fe folded[4] = {F.mul(c[0], scale), F.mul(c[1], scale), F.mul(c[3], scale), F.mul(c[4], scale)};
+        memcpy(co.l, folded, sizeof(co.l));
+    }
+    C.timer.begin(C.stream);
+    KH_FIELD_LAUNCH(field, k_generic_half<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)l_dev, (const u64*)r_dev, n, co,
+                    (unsigned)(3 * half), at, (u64*)out_dev);
+    C.timer.mark("generic", C.stream);
+    return KH_OK;
+}
+
+}  // namespace kh

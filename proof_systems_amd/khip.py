@@ -826,6 +826,38 @@ def foreign_field_mul_witness_dev(field: int, modulus: int, a, b, n: int, witnes
                                                  col_len, _ptr(out_checks), _ptr(flags), bit))
 
 
+CELL_WORDS = {_CONSTANTS["KH_CELL_FIELD"]: 4, _CONSTANTS["KH_CELL_INT256"]: 4, _CONSTANTS["KH_CELL_INT128"]: 2, _CONSTANTS["KH_CELL_LIMB88"]: 2,
+              _CONSTANTS["KH_CELL_U64"]: 1}          # uint64 words per value of each KH_CELL_* format
+
+
+def _cells32(cells):
+    c = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1, 2)
+    return c, c.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def witness_gather_dev(field: int, witness, col_stride: int, col_len: int, cells, fmt: int, out, flags=None, bit: int = 0):
+    """kh_witness_gather_dev: out[i] = the cell cells[i] = (row, column) of the 15 columns at `witness` in the format `fmt` (CELL_FIELD, CELL_INT256,
+    CELL_INT128, CELL_LIMB88, CELL_U64: CELL_WORDS[fmt] uint64 each); the flag is set when a cell does not fit a narrow format."""
+    c, cp = _cells32(cells)
+    _check(_lib.kh_witness_gather_dev(field, _ptr(witness), col_stride, col_len, cp, len(c), fmt, _ptr(out), _ptr(flags), bit))
+
+
+def witness_scatter_dev(field: int, values, fmt: int, cells, witness, col_stride: int, col_len: int, flags=None, bit: int = 0):
+    """kh_witness_scatter_dev: the cell cells[i] = (row, column) becomes the Montgomery element of values[i], read in the format `fmt`; the flag is set
+    by a CELL_INT256 value >= p and by a CELL_LIMB88 value >= 2^88."""
+    c, cp = _cells32(cells)
+    _check(_lib.kh_witness_scatter_dev(field, _ptr(values), fmt, cp, len(c), _ptr(witness), col_stride, col_len, _ptr(flags), bit))
+
+
+def generic_witness_dev(field: int, coeffs, half: int, l, r, n: int, witness, col_stride: int, col_len: int, rows=None, row0: int = 0, row_stride: int = 1,
+                        out=None):
+    """kh_generic_witness_dev: cells 3 * half .. 3 * half + 2 of n generic rows = l, r (n x 4 Montgomery limbs each; r nullable: 0) and
+    o = -(c_l l + c_r r + c_m l r + c_c) / c_o for the half's coefficients `coeffs` = (5, 4) Montgomery limbs l r o m c; out (nullable): the n values o."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_generic_witness_dev(field, _p64(_c64(coeffs, (5, 4))), half, _ptr(l), _ptr(r), n, rp, row0, row_stride, _ptr(witness), col_stride, col_len,
+                                       _ptr(out)))
+
+
 class Comm:
     """kh_comm_*: the in-library RCCL communicator of the one-process-per-GPU deployment (no torch).  Comm.unique_id() on one rank, the bytes to
     the others, Comm(world, rank, id) on every rank."""
