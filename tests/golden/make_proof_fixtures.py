@@ -47,6 +47,10 @@ CASES = {
     # the gate library against BYTES: instances of Poseidon (11 rows = one 55-round permutation), CompleteAdd (incl. doubling, P + (-P)),
     # VarBaseMul, EndoMul, EndoMulScalar (witnesses by the reference's generators restated in oracle/gates.py) on a 2^13 domain (~120 instances each)
     "library_gates_vesta_2_13": (0, 13, 13, bytes([13, 5] + [42] * 30)),
+    # the two above over Fq: a Pallas proof whose circuit computes on Vesta points (the wrap side of the recursion) -- the "fq" Poseidon parameters, Vesta's
+    # endo coefficient in EndoMul / EndoMulScalar, and the whole lookup side of a Pallas proof
+    "library_gates_pallas_2_13": (1, 13, 13, bytes([13, 6] + [42] * 30)),
+    "and_lookup_pallas_2_13": (1, 13, 13, bytes([13, 7] + [42] * 30)),
 }
 PREV_SEED = bytes([11] * 32)           # the previous challenges of *_prev1 are drawn from StdRng::from_seed(PREV_SEED)
 AND_SEED = bytes([12] * 32)            # the AND gadgets' 64-bit inputs
@@ -127,7 +131,7 @@ def library_circuit(F, log2_n: int, rng_seed: int = 55):
     full = False
     while not full:
         for name in ("Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar"):
-            w, co, ngate = tables(name, rnd)
+            w, co, ngate = tables(name, rnd, F)
             if len(gates) + len(w) + 3 + 1 > (1 << log2_n) - 1:
                 full = True
                 break

@@ -22,14 +22,20 @@ F = P.Fp
 CURVE = P.PALLAS                      # coordinates in Fp: the points a Vesta-side circuit computes on
 
 
-def kimchi_params():
-    d = json.load(open(os.path.join(ROOT, "tests", "golden", "poseidon_kimchi_params.json")))["fp"]
+def circuit_curve(F):
+    """the curve whose coordinates lie in F: the points a circuit over F computes on (Fp: Pallas, the Vesta-side proofs; Fq: Vesta, the Pallas-side ones)"""
+    return P.PALLAS if F is P.Fp else P.VESTA
+
+
+def kimchi_params(F=F):
+    d = json.load(open(os.path.join(ROOT, "tests", "golden", "poseidon_kimchi_params.json")))["fp" if F is P.Fp else "fq"]
     return [[int(x) for x in r] for r in d["mds"]], [[int(x) for x in r] for r in d["round_constants"]]
 
 
-def tables(name, rnd):
-    """(witness rows, coefficient rows, number of gate rows, extras) of a satisfied instance."""
-    mds, rc = kimchi_params()
+def tables(name, rnd, F=F):
+    """(witness rows, coefficient rows, number of gate rows, extras) of a satisfied instance over F (the draws from `rnd` are the same code on both fields)."""
+    mds, rc = kimchi_params(F)
+    CURVE = circuit_curve(F)
     endo = P.endos(CURVE)[0]
     if name == "Poseidon":
         st = [rnd.randrange(F.p) for _ in range(3)]
@@ -116,24 +122,37 @@ def tables(name, rnd):
     return w + [[0] * 15], [[0] * 15] * (len(w) + 1), len(w)
 
 
-def program(name, alpha):
-    mds, _ = kimchi_params()
-    return OP.gate_program(name, F.p, alpha, selector_col=30, mds=mds, endo=P.endos(CURVE)[0])
+def program(name, alpha, F=F):
+    mds, _ = kimchi_params(F)
+    return OP.gate_program(name, F.p, alpha, selector_col=30, mds=mds, endo=P.endos(circuit_curve(F))[0])
 
 
 def gate_rows(name, ngate):
     return list(range(0, ngate, 2)) if name == "VarBaseMul" else list(range(ngate))
 
 
-@pytest.mark.parametrize("name", list(OP.GATES))
-def test_gate_program_matches_row_machine(name):
+def on_both_fields(names):
+    """(name, field) cases: the Fp ones keep the ids they had before the Fq ones joined them"""
+    return [pytest.param(n, Fd, id=n + tag) for n in names for Fd, tag in ((P.Fp, ""), (P.Fq, "-fq"))]
+
+
+def test_the_fq_parameters_are_the_other_field_s():
+    """what the Fq cases run on: the "fq" Poseidon parameters (= the MDS literals the generated kernels carry), the endo coefficient of the curve over Fq"""
+    assert kimchi_params(P.Fq) != kimchi_params(P.Fp) and P.endos(P.VESTA)[0] != P.endos(P.PALLAS)[0]
+    for fid, Fd in enumerate((P.Fp, P.Fq)):
+        assert [[v % Fd.p for v in r] for r in OP.POSEIDON_MDS[fid]] == kimchi_params(Fd)[0]
+        assert pow(P.endos(circuit_curve(Fd))[0], 3, Fd.p) == 1 != P.endos(circuit_curve(Fd))[0]
+
+
+@pytest.mark.parametrize("name,F", on_both_fields(OP.GATES))
+def test_gate_program_matches_row_machine(name, F):
     rnd = random.Random(sum(map(ord, name)))
-    mds, _ = kimchi_params()
-    endo = P.endos(CURVE)[0]
-    w, co, ngate = tables(name, rnd)
+    mds, _ = kimchi_params(F)
+    endo = P.endos(circuit_curve(F))[0]
+    w, co, ngate = tables(name, rnd, F)
     nrows = len(w)
     alpha = rnd.randrange(F.p)
-    toks, consts = program(name, alpha)
+    toks, consts = program(name, alpha, F)
     sel = [0] * nrows
     for r in gate_rows(name, ngate):
         sel[r] = 1
@@ -153,12 +172,12 @@ def test_gate_program_matches_row_machine(name):
             assert (nonzero == 0) == (variant == "satisfied"), (name, variant)
 
 
-@pytest.mark.parametrize("name", list(OP.GATES))
-def test_every_constrained_cell_matters(name):
+@pytest.mark.parametrize("name,F", on_both_fields(OP.GATES))
+def test_every_constrained_cell_matters(name, F):
     rnd = random.Random(7)
-    mds, _ = kimchi_params()
-    endo = P.endos(CURVE)[0]
-    w, co, ngate = tables(name, rnd)
+    mds, _ = kimchi_params(F)
+    endo = P.endos(circuit_curve(F))[0]
+    w, co, ngate = tables(name, rnd, F)
     row = gate_rows(name, ngate)[0]
     used = {"Poseidon": range(15), "CompleteAdd": range(11), "VarBaseMul": [0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 14], "EndoMul": [0, 1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14],
             "EndoMulScalar": range(14), "Xor16": range(15), "RangeCheck0": range(15), "RangeCheck1": [0] + list(range(2, 15)), "Rot64": [0, 1, 2] + list(range(3, 15)),

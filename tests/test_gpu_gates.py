@@ -12,7 +12,7 @@ from oracle import gates as G
 from oracle import pasta as P
 from proof_systems_amd import polish as OP
 
-from test_gates import CURVE, F, gate_rows, kimchi_params, program, tables
+from test_gates import circuit_curve, gate_rows, on_both_fields, kimchi_params, program, tables
 
 pytestmark = pytest.mark.gpu
 
@@ -24,25 +24,20 @@ def khip():
     return k
 
 
-def _limbs(vals):
-    return cref.ints_to_limbs([F.to_mont(v) for v in vals])
-
-
-def _ints(limbs):
-    return [F.from_mont(v) for v in cref.limbs_to_ints(limbs)]
-
-
-@pytest.mark.parametrize("name", list(OP.GATES))
-def test_gate_on_device(khip, name):
-    fid = khip.FP
+@pytest.mark.parametrize("name,F", on_both_fields(OP.GATES))
+def test_gate_on_device(khip, name, F):
+    """on Fq: the other instantiation of every k_gate_<Name> (a kernel of its own), the "fq" MDS literals and Vesta's endo coefficient in its constants"""
+    fid = khip.FP if F is P.Fp else khip.FQ
+    _limbs = lambda vals: cref.ints_to_limbs([F.to_mont(v) for v in vals])
+    _ints = lambda limbs: [F.from_mont(v) for v in cref.limbs_to_ints(limbs)]
     rnd = random.Random(1000 + sum(map(ord, name)))
-    mds, _ = kimchi_params()
-    endo = P.endos(CURVE)[0]
-    w, co, ngate = tables(name, rnd)
+    mds, _ = kimchi_params(F)
+    endo = P.endos(circuit_curve(F))[0]
+    w, co, ngate = tables(name, rnd, F)
     logn = 6; n = 1 << logn
     assert len(w) <= n - 3
     alpha = rnd.randrange(F.p)
-    toks, consts = program(name, alpha)
+    toks, consts = program(name, alpha, F)
     for variant in ("satisfied", "violated"):
         wt = [list(r) for r in w] + [[0] * 15 for _ in range(n - len(w))]
         ct = [list(r) for r in co] + [[0] * 15 for _ in range(n - len(co))]

@@ -12,7 +12,7 @@ from oracle import cref
 from oracle import lookup as L
 from oracle import pasta as P
 
-from test_lookup import F, LOGN, N, ZK, circuit, p, user_table
+from test_lookup import LOGN, N, ZK, circuit, user_table
 
 pytestmark = pytest.mark.gpu
 
@@ -26,19 +26,23 @@ def env():
     return khip, LK, OP
 
 
-def _limbs(vals):
-    return cref.ints_to_limbs([F.to_mont(v) for v in vals])
-
-
-def _ints(limbs):
-    return [F.from_mont(v) for v in cref.limbs_to_ints(limbs)]
-
-
 def test_lookup_argument_on_device(env):
+    lookup_argument_on_device(env, P.Fp)
+
+
+def test_lookup_argument_on_device_over_fq(env):
+    """the lookup side of a Pallas proof: the same columns, sorted columns, aggregation, constraint rows and quotient step on the other field's kernels"""
+    lookup_argument_on_device(env, P.Fq)
+
+
+def lookup_argument_on_device(env, F):
     khip, LK, OP = env
-    fid = khip.FP
+    fid = khip.FP if F is P.Fp else khip.FQ
+    p = F.p
+    _limbs = lambda vals: cref.ints_to_limbs([F.to_mont(v) for v in vals])
+    _ints = lambda limbs: [F.from_mont(v) for v in cref.limbs_to_ints(limbs)]
     rnd = random.Random(11)
-    gates, wit = circuit(rnd)
+    gates, wit = circuit(rnd, p=p)
     cs = L.LookupCS(p, gates, [user_table()], N, ZK)
     ix = LK.LookupIndex(fid, gates, [user_table()], LOGN, ZK)
     # ---- index
@@ -128,18 +132,19 @@ def test_lookup_argument_on_device(env):
         assert rem.download((N, 4)).any() == (variant == "violated"), variant
 
 
-@pytest.mark.parametrize("zk", [3, 5])
-def test_atom_columns_on_the_device_equal_the_host_restatement(zk):
+@pytest.mark.parametrize("zk,fid", [pytest.param(3, 0, id="3"), pytest.param(5, 0, id="5"), pytest.param(3, 1, id="3-fq"), pytest.param(5, 1, id="5-fq")])
+def test_atom_columns_on_the_device_equal_the_host_restatement(zk, fid):
     """VanishesOnZeroKnowledgeAndPreviousRows, UnnormalizedLagrangeBasis(0), UnnormalizedLagrangeBasis(-zk_rows - 1) on d8 (expr.rs:883-893): the device
     version (products / one batched inversion per atom / the removable singularity patched) against the host loop over every point."""
     import proof_systems_amd.khip as khip
     from proof_systems_amd import lookup as LK, prover
     khip.init(0)
     logn = 7; n = 1 << logn
-    F = prover.Fld(khip.FP)
+    assert (khip.FP, khip.FQ) == (0, 1)
+    F = prover.Fld(fid)
     tables = [{"id": 0, "data": [list(range(8)), [0] + list(range(11, 18))]}]
     gates = ["Lookup"] * 20 + ["Zero"] * (n - zk - 20)
-    LI = LK.LookupIndex(khip.FP, gates, tables, logn, zk_rows=zk)
+    LI = LK.LookupIndex(fid, gates, tables, logn, zk_rows=zk)
     root = LK.khip_root(F, logn + 3)
     xs = [1] * (8 * n)
     for k in range(1, 8 * n):

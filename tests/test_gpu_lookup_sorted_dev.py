@@ -203,6 +203,15 @@ def test_argument_refusals_launch_nothing(khip):
 
 def test_kh_prove_reproduces_the_committed_lookup_proof_on_the_device_path(khip):
     """the 2^13 AND-gadget fixture (Xor16 rows + 4-bit XOR-table lookups): the same bytes, and the sorted columns came from kh_lookup_sorted_dev -- once"""
+    committed_lookup_proof_on_the_device_path(khip, "and_lookup_vesta_2_13")
+
+
+def test_kh_prove_reproduces_the_committed_pallas_lookup_proof_on_the_device_path(khip):
+    """the same over Fq: the sort, the join and the layout kernels' other instantiation inside a Pallas proof"""
+    committed_lookup_proof_on_the_device_path(khip, "and_lookup_pallas_2_13")
+
+
+def committed_lookup_proof_on_the_device_path(khip, name):
     import os
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
@@ -211,10 +220,12 @@ def test_kh_prove_reproduces_the_committed_lookup_proof_on_the_device_path(khip)
     from proof_systems_amd import prover
     from test_gpu_proof_fixtures import first_difference, load
     from test_gpu_prover_parity import _limbs, device_index
-    rec, want = load("and_lookup_vesta_2_13")
-    Cv = P.VESTA; Fo = Cv.scalar
+    rec, want = load(name)
+    cid = ["vesta", "pallas"].index(rec["curve"])
+    assert (khip.VESTA, khip.PALLAS) == (0, 1)
+    Cv = P.CURVES[cid]; Fo = Cv.scalar
     cs, wrows = M.and_circuit(Fo, rec["log2_n"])
-    ix = device_index(khip, cs, khip.VESTA, khip.Srs.create(khip.VESTA, 1 << rec["log2_srs"]))
+    ix = device_index(khip, cs, cid, khip.Srs.create(cid, 1 << rec["log2_srs"]))
     wit = np.stack([_limbs(Fo, [r[c] for r in wrows]) for c in range(15)])
     before = khip.counter("lookup_sorted_dev")
     nproof = prover.create_proof_native(ix, wit, V.RefRng(P.StdRng(bytes.fromhex(rec["seed_hex"]))))
@@ -282,8 +293,16 @@ def test_native_and_python_provers_agree_on_the_device_path(khip, cid):
 def test_lookup_py_device_path_equals_its_python_path(khip):
     """proof_systems_amd/lookup.py: sorted_columns_dev (values, join and layout on the device) against sorted_columns (Python integers, the
     restatement of lookup/constraints.rs:90-194) on the two-table circuit; and written in place into padded columns"""
+    lookup_py_device_path_equals_its_python_path(khip, 0)
+
+
+def test_lookup_py_device_path_equals_its_python_path_on_pallas(khip):
+    lookup_py_device_path_equals_its_python_path(khip, 1)
+
+
+def lookup_py_device_path_equals_its_python_path(khip, cid):
     from proof_systems_amd import lookup as LK
-    ix, LI, F, wit, ngen = two_table_circuit(khip, 0)
+    ix, LI, F, wit, ngen = two_table_circuit(khip, cid)
     n, zk = LI.n, LI.zk_rows
     jc = 0x1234567890abcdef1234567890abcdef % F.p
     wfull = np.zeros((15, n, 4), dtype=np.uint64)

@@ -80,7 +80,7 @@ def library_circuit(F, rnd, optional=("ForeignFieldAdd",)):
     for r in range(6):
         wrows.append([5] + [0] * 14); crows.append([1, 0, 0, 0, F.p - 5] + [0] * 10); types.append("Generic")
     for name in ("Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar") + tuple(optional):
-        w, co, ngate = tables(name, rnd)
+        w, co, ngate = tables(name, rnd, F)
         live = set(gate_rows(name, ngate))
         for r, (wr, cr) in enumerate(zip(w, co)):
             wrows.append(list(wr)); crows.append([c % F.p for c in cr]); types.append(name if r in live else "Zero")
@@ -271,16 +271,20 @@ def test_a_c_program_proves_and_the_oracle_verifier_accepts(khip, tmp_path):
     ix.free()
 
 
-@pytest.mark.parametrize("seed", range(6))
+@pytest.mark.parametrize("seed", range(12))
 def test_randomised_configurations_native_equals_python_and_verifies(khip, seed):
     """Differential fuzz over what the parity tests fix by hand: a random subset of the library / optional gates (in random order, between random
     numbers of generic rows), a random number of public inputs, the domain 1x / 2x / 4x the SRS or half of it -- kh_prove and the Python loop give the
-    same proof from the same random stream, and the oracle verifier accepts it."""
+    same proof from the same random stream, and the oracle verifier accepts it.  The seed gives the curve too: 0..5 Vesta (the configurations they
+    always were), 6..11 Pallas (gate instances over Fq: points on Vesta, Vesta's endo coefficient, the "fq" Poseidon parameters)."""
     from proof_systems_amd import prover
     from test_gates import gate_rows, tables
     from test_gpu_prover import _verify
     rnd = random.Random(9000 + seed)
-    F = prover.Fld(khip.FP)
+    cid = seed // 6
+    assert (khip.VESTA, khip.PALLAS, khip.FP, khip.FQ) == (0, 1, 0, 1)
+    F = prover.Fld(cid)
+    Fo = P.CURVES[cid].scalar
     names = ["Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar", "ForeignFieldAdd", "Rot64"]
     rnd.shuffle(names)
     names = names[:rnd.randrange(0, len(names) + 1)]
@@ -296,7 +300,7 @@ def test_randomised_configurations_native_equals_python_and_verifies(khip, seed)
     generic_rows(npub, public=True)
     generic_rows(rnd.randrange(1, 6))
     for name in names:
-        w, co, ngate = tables(name, rnd)
+        w, co, ngate = tables(name, rnd, Fo)
         live = set(gate_rows(name, ngate))
         for r, (wr, cr) in enumerate(zip(w, co)):
             wrows.append(list(wr)); crows.append([c % F.p for c in cr]); types.append(name if r in live else "Zero")
@@ -306,8 +310,8 @@ def test_randomised_configurations_native_equals_python_and_verifies(khip, seed)
     log_srs = logn + rnd.choice([-2, -1, 0, 0, 1])
     nch = 1 << max(0, logn - log_srs)
     assert rows + (16 * nch + 5) // 7 <= 1 << logn
-    srs = khip.Srs.create(khip.VESTA, 1 << log_srs)
-    ix = prover.ProverIndex(khip.VESTA, logn, np.stack([F.limbs_many(r) for r in crows]), srs=srs, gate_types=types, public=npub)
+    srs = khip.Srs.create(cid, 1 << log_srs)
+    ix = prover.ProverIndex(cid, logn, np.stack([F.limbs_many(r) for r in crows]), srs=srs, gate_types=types, public=npub)
     assert ix.num_chunks == nch
     wit = np.stack([F.limbs_many([wrows[r][c] for r in range(rows)]) for c in range(15)])
     a = prover.create_proof(ix, wit, np.random.default_rng(seed))

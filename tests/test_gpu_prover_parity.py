@@ -238,6 +238,52 @@ def test_recursive_proof_equals_the_oracle_provers_proof(khip, cid, logn, log_sr
     ix.free()
 
 
+@pytest.mark.parametrize("cid,circuit", [(0, "library"), (1, "library"), (0, "and"), (1, "and")])
+def test_gate_library_and_lookup_proofs_equal_the_oracle_provers_proof(khip, cid, circuit):
+    """What every other oracle-prover parity case lacks on Pallas: live library gates (2^7: Poseidon, CompleteAdd, VarBaseMul, EndoMul, EndoMulScalar) and
+    the lookup argument (2^9: AND gadgets, Xor16 rows with XOR-table lookups), on both curves from the same random stream.  Over Fq the circuit computes on
+    Vesta points: the quotient reads Vesta's endo coefficient and the "fq" MDS, and the lookup side (joint combiner, sorted columns, aggregation, the lookup
+    constraints on d8, the extra commitments and openings) runs the other field's kernels.  kh_prove and the Python loop = the oracle prover, byte for byte."""
+    import sys
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_proof_fixtures as M
+    from proof_systems_amd import prover
+    C = P.CURVES[cid]; F = C.scalar
+    if circuit == "library":
+        cs, wit = M.library_circuit(F, 7)
+        assert {"Poseidon", "CompleteAdd", "VarBaseMul", "EndoMul", "EndoMulScalar"} <= set(cs["gate_types"]) and cs["lookup"] is None
+    else:
+        cs, wrows = M.and_circuit(F, 9)
+        wit = [[r[c] for r in wrows] for c in range(15)]
+        assert cs["lookup"] is not None and "Xor16" in cs["gate_types"]
+    logn = cs["log2_n"]
+    assert logn == (7 if circuit == "library" else 9)
+    seed = bytes([71, logn] + [6] * 30)                           # the same stream on both curves
+    osrs = OPR.Srs(C, 1 << logn)
+    oix = OPR.Index(C, cs, osrs)
+    want = OPR.serialize_proof(C, OPR.create_proof(oix, wit, P.StdRng(seed)))
+    ix = device_index(khip, cs, cid, khip.Srs.create(cid, 1 << logn))
+    assert C.base.from_mont(P.from_limbs(ix.digest)) == oix.digest, "the device-built index is not the oracle's (verifier-index digest)"
+    w = np.stack([_limbs(F, col) for col in wit])
+    nproof = prover.create_proof_native(ix, w, V.RefRng(P.StdRng(seed)))
+    npr = V.device_views(ix, nproof)[2]
+    assert OPR.serialize_proof(C, npr) == want, "kh_prove differs from the oracle prover"
+    assert (npr.get("lookup") is not None) == (circuit == "and")
+    dproof = prover.create_proof(ix, w, V.RefRng(P.StdRng(seed)))
+    assert OPR.serialize_proof(C, V.device_views(ix, dproof)[2]) == want, "create_proof (Python loop) differs from the oracle prover"
+    aproof = prover.create_proof_native(ix, w, V.RefRng(P.StdRng(seed)), all_gates=True)
+    assert OPR.serialize_proof(C, V.device_views(ix, aproof)[2]) == want
+    if circuit == "library":                                      # a spoiled row of the two gates whose constants differ by field: the reference's error
+        for name, col in (("Poseidon", 7), ("EndoMul", 4)):
+            r0 = cs["gate_types"].index(name) + 3
+            assert cs["gate_types"][r0] == name
+            bad = [list(c) for c in wit]
+            bad[col][r0] = (bad[col][r0] + 1) % F.p
+            with pytest.raises(khip.KhError, match="vanishing polynomial"):
+                prover.create_proof_native(ix, np.stack([_limbs(F, c) for c in bad]), V.RefRng(P.StdRng(seed)))
+    ix.free()
+
+
 def test_optional_gate_circuit_proof_equals_the_oracle_provers_proof(khip):
     """A circuit of RangeCheck0 rows (12-bit lookups into the range-check table, the compact form on one of them), a Rot64 row with its
     two range-check rows, and a ForeignFieldAdd row: optional-gate selectors committed non-hiding and evaluated, the RangeCheck lookup

@@ -290,7 +290,7 @@ def circuit_records(khip, F, Fo, cs, wit):
     return types, wires, co, np.stack([F.limbs_many([v % Fo.p for v in col]) for col in wit])
 
 
-def lookup_case():
+def lookup_case(Fo=P.Fp):
     """30 Lookup rows into a caller's table with id 5 (even rows) and a runtime table with id 7 (odd rows): table ids, a synthesised dummy table, runtime rows"""
     ent = 12
     c0 = [7 * j + 1 for j in range(ent)]; c1 = [j * j + 3 for j in range(ent)]
@@ -302,7 +302,7 @@ def lookup_case():
         for k in range(3):
             j = (5 * r + 7 * k) % (ent if r % 2 == 0 else 5)
             wit[1 + 2 * k][r], wit[2 + 2 * k][r] = (c0[j], c1[j]) if r % 2 == 0 else (first[j], data[j])
-    return Case([CC.gate("Lookup", r) for r in range(rows)], wit, [{"id": 5, "data": [c0, c1]}], runtime_cfg=[{"id": 7, "first_column": first}], runtime=data)
+    return Case([CC.gate("Lookup", r) for r in range(rows)], wit, [{"id": 5, "data": [c0, c1]}], runtime_cfg=[{"id": 7, "first_column": first}], runtime=data, Fo=Fo)
 
 
 def xor_case_2_13():
@@ -343,14 +343,28 @@ def made(khip):
     case = xor_case_2_13()
     types, wires, co = case.records(khip, FV)
     out["xor"] = Made(khip, srs13, types, wires, co, case.limbs(FV))
+    # the Pallas twins (circuits over Fq: points on Vesta, Vesta's endo coefficient, the "fq" Poseidon parameters; the lookup side on the other field's
+    # kernels); the xor twin is the 2^9 AND circuit (Xor16 rows with their XOR-table lookups, generic rows) over a 2^9 SRS
+    srs9p = khip.Srs.create(khip.PALLAS, 1 << 9)
+    cs, wit = M.library_circuit(P.Fq, 7)
+    out["library_pallas"] = Made(khip, srs7p, *circuit_records(khip, FP_, P.Fq, cs, wit))
+    case = lookup_case(P.Fq)
+    types, wires, co = case.records(khip, FP_)
+    out["lookup_pallas"] = Made(khip, srs9p, types, wires, co, case.limbs(FP_), tables=case.tables, runtime_cfg=case.runtime_cfg,
+                                runtime=FP_.limbs_many(case.runtime))
+    cs, wrows = M.and_circuit(P.Fq, 9)
+    assert cs["lookup"] is not None and cs["log2_n"] == 9
+    out["xor_pallas"] = Made(khip, srs9p, *circuit_records(khip, FP_, P.Fq, cs, [[r[c] for r in wrows] for c in range(15)]))
+    for name in ("library_pallas", "lookup_pallas", "xor_pallas"):
+        assert out[name].ix.curve == khip.PALLAS and out[name].F.p == P.Fq.p
     yield out
     for m in out.values():
         m.free()
-    for s in (srs7, srs7p, srs9, srs13):
+    for s in (srs7, srs7p, srs9, srs13, srs9p):
         s.close()
 
 
-ROUND_TRIPS = ["bench_vesta", "bench_pallas", "two_chunks", "recursive", "lookup", "xor", "library"]
+ROUND_TRIPS = ["bench_vesta", "bench_pallas", "two_chunks", "recursive", "lookup", "xor", "library", "library_pallas", "lookup_pallas", "xor_pallas"]
 
 
 @pytest.mark.parametrize("name", ROUND_TRIPS)
@@ -360,7 +374,8 @@ def test_native_proof_is_accepted_and_every_changed_section_is_rejected(khip, ma
     assert ok
     changed = [s for s in POINT_SECTIONS + ELEMENT_SECTIONS if s in m.sections and len(m.sections[s][0] if isinstance(m.sections[s], tuple) else m.sections[s])]
     assert {"w_comm", "z_comm", "t_comm", "evals", "public_evals", "ft_eval1", "lr", "delta", "z1_z2", "sg"} <= set(changed)
-    assert ("lookup_sorted_comm" in changed) == (name in ("lookup", "xor")) and ("lookup_runtime_comm" in changed) == (name == "lookup")
+    kind = name[:-len("_pallas")] if name.endswith("_pallas") else name
+    assert ("lookup_sorted_comm" in changed) == (kind in ("lookup", "xor")) and ("lookup_runtime_comm" in changed) == (kind == "lookup")
     for s in changed:
         ok, _trace = m.verify(tampered(khip, m.ix.curve, m.sections, s))
         assert not ok, s
@@ -368,11 +383,21 @@ def test_native_proof_is_accepted_and_every_changed_section_is_rejected(khip, ma
 
 # ---------------------------------------------------------------------------------------------------- 4. batch
 def test_batch_of_eight_over_three_indexes(khip, made):
-    F = made["bench_vesta"].F
-    order = ["bench_vesta", "library", "two_chunks", "bench_vesta", "library", "two_chunks", "library", "bench_vesta"]
-    secs = [made[n].prove(seed=40 + i) for i, n in enumerate(order)]            # eight different proofs: every item has its own alpha
+    batch_over_indexes(khip, made, ["bench_vesta", "library", "two_chunks", "bench_vesta", "library", "two_chunks", "library", "bench_vesta"], 5)
+
+
+def test_pallas_batch_of_four_over_two_indexes(khip, made):
+    """a batch takes one SRS, so one curve: the Pallas library proofs (live EndoMul / EndoMulScalar / Poseidon terms in the constant term, with Vesta's endo
+    coefficient and the "fq" MDS in the per-item constants) in a batch of their own, between generic-only items"""
+    batch_over_indexes(khip, made, ["bench_pallas", "library_pallas", "library_pallas", "bench_pallas"], 2)
+
+
+def batch_over_indexes(khip, made, order, spoil):
+    F = made[order[0]].F
+    curve = made[order[0]].ix.curve
+    secs = [made[n].prove(seed=40 + i) for i, n in enumerate(order)]            # different proofs: every item has its own alpha
     alone = [made[n].verify(s) for n, s in zip(order, secs)]
-    assert all(ok for ok, _t in alone) and len({tuple(t["challenges"][2]) for _ok, t in alone}) == 8
+    assert all(ok for ok, _t in alone) and len({tuple(t["challenges"][2]) for _ok, t in alone}) == len(order)
     rand = F.limbs_many([0x1234567, 0x89abcdef01])
     items = [made[n].item(s) for n, s in zip(order, secs)]
     ok, traces = khip.batch_verify(items, rand)
@@ -383,10 +408,10 @@ def test_batch_of_eight_over_three_indexes(khip, made):
     ok, _t = khip.batch_verify(items, None)                                     # rand_base, sg_rand_base drawn by the library
     assert ok
     bad = list(items)
-    bad[5] = made[order[5]].item(tampered(khip, khip.VESTA, secs[5], "evals"))
+    bad[spoil] = made[order[spoil]].item(tampered(khip, curve, secs[spoil], "evals"))
     ok, traces = khip.batch_verify(bad, rand)
     assert not ok
-    for it in items + [bad[5]]:
+    for it in items + [bad[spoil]]:
         it[1].free()
 
 

@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 sys.path.insert(0, HERE)
 import make_proof_fixtures as M  # noqa: E402
-from test_gates import gate_rows, tables  # noqa: E402
+from test_gates import gate_rows, on_both_fields, tables  # noqa: E402
 
 GATE_NAMES = list(OP.GATES) + ["Generic"]
 NCONSTRAINTS = dict(G.ROW_MACHINES, Generic=2)
@@ -145,7 +145,7 @@ def gate_circuit(name, F=P.Fp):
             gates.append(CC.generic_gadget(p, r, CC.generic_spec(p, "Add"), CC.generic_spec(p, "Mul")))
             rows.append([a, b, (a + b) % p, b, a, a * b % p] + [0] * 9)
     else:
-        w, co, ngate = tables(name, random.Random(7))
+        w, co, ngate = tables(name, random.Random(7), F)
         live = set(gate_rows(name, ngate))
         gates = [CC.gate(name if k in live else "Zero", k, [c % p for c in co[k]] if k in live else []) for k in range(len(w))]
         rows = [list(r) for r in w]
@@ -163,6 +163,11 @@ def khip():
 @pytest.fixture(scope="module")
 def srs13(khip):
     return khip.Srs.create(khip.VESTA, 1 << 13)
+
+
+@pytest.fixture(scope="module")
+def srs13_pallas(khip):
+    return khip.Srs.create(khip.PALLAS, 1 << 13)
 
 
 def created(khip, srs, circ):
@@ -188,10 +193,12 @@ def spoiled(circ, cells, delta=1):
 
 
 # ---- 1. every constraint of every gate
-@pytest.mark.parametrize("name", GATE_NAMES)
-def test_every_constraint_of_every_gate(khip, srs13, name):
-    circ = gate_circuit(name)
-    ix, F = created(khip, srs13, circ)
+@pytest.mark.parametrize("name,Fo", on_both_fields(GATE_NAMES))
+def test_every_constraint_of_every_gate(khip, request, name, Fo):
+    """over Fq (a Pallas SRS): the comparing sink's other instantiation, with the gate_fixed_constants(field = 1, ...) tables -- the "fq" MDS, Vesta's endo coefficient"""
+    circ = gate_circuit(name, Fo)
+    ix, F = created(khip, request.getfixturevalue("srs13" if Fo is P.Fp else "srs13_pallas"), circ)
+    assert F.p == Fo.p
     assert ix.n == circ.n and (name not in LOOKUP_GATES or circ.n == (1 << 9 if name == "Xor16" else 1 << 13)), ix.n     # the gate tables set the lookup gates' domain
     base = circ.limbs(F)
     rep = check(khip, ix, circ, F, limbs=base)
@@ -223,26 +230,38 @@ def test_every_constraint_of_every_gate(khip, srs13, name):
 
 
 # ---- 2. block and wave boundaries, the minimum across blocks
-@pytest.fixture(scope="module")
-def library(khip, srs13):
+def library_indexes(khip, srs, Fo):
     out = {}
     for logn in (7, 8):
-        cs, wit = M.library_circuit(P.Fp, logn)
+        cs, wit = M.library_circuit(Fo, logn)
         circ = Circuit(cs, wit)
-        ix, F = created(khip, srs13, circ)
+        ix, F = created(khip, srs, circ)
         out[logn] = (circ, ix, F)
     yield out
     for _c, ix, _F in out.values():
         ix.free()
 
 
+@pytest.fixture(scope="module")
+def library(khip, srs13):
+    yield from library_indexes(khip, srs13, P.Fp)
+
+
+@pytest.fixture(scope="module")
+def library_pallas(khip, srs13_pallas):
+    """the same circuits over Fq (points on Vesta, the "fq" Poseidon parameters), indexed over a Pallas SRS"""
+    yield from library_indexes(khip, srs13_pallas, P.Fq)
+
+
 def nearest_gate_row(circ, r):
     return min((q for q, t in enumerate(circ.types) if t != "Zero"), key=lambda q: (abs(q - r), q))
 
 
-@pytest.mark.parametrize("logn", [7, 8])
-def test_block_and_wave_boundaries(khip, library, logn):
-    circ, ix, F = library[logn]
+@pytest.mark.parametrize("logn,lib", [pytest.param(7, "library", id="7"), pytest.param(8, "library", id="8"),
+                                      pytest.param(7, "library_pallas", id="7-fq"), pytest.param(8, "library_pallas", id="8-fq")])
+def test_block_and_wave_boundaries(khip, request, logn, lib):
+    circ, ix, F = request.getfixturevalue(lib)[logn]
+    assert ix.srs.curve == (khip.VESTA if lib == "library" else khip.PALLAS) and F.p == circ.F.p
     assert ix.n == 1 << logn and (logn != 8 or circ.rows > 128)
     assert check(khip, ix, circ, F).kind == khip.WITNESS_OK
     last = max(q for q, t in enumerate(circ.types) if t != "Zero")
@@ -367,8 +386,16 @@ def test_index_from_columns_and_refusals(khip, srs13, library):
 
 # ---- 9. agreement with the prover's own check
 def test_agrees_with_the_prover_check(khip, library):
+    agrees_with_the_prover_check(khip, library[7])
+
+
+def test_agrees_with_the_prover_check_on_pallas(khip, library_pallas):
+    agrees_with_the_prover_check(khip, library_pallas[7])
+
+
+def agrees_with_the_prover_check(khip, lib):
     from proof_systems_amd import prover
-    circ, ix, F = library[7]
+    circ, ix, F = lib
     rng = lambda: P.StdRng(bytes([5] * 32))
     from oracle import views as V
     prover.create_proof_native(ix, circ.limbs(F), V.RefRng(rng()), check=True)

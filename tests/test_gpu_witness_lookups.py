@@ -24,15 +24,15 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_proof_fixtures as M  # noqa: E402
 
 PATTERN_IDS = {"Xor": 0, "Lookup": 1, "RangeCheck": 2, "ForeignFieldMul": 3}
-Fo = P.Fp
+Fo = P.Fp                       # the default field of the cases (a Vesta SRS); the `*_on_pallas` tests run the same bodies with the brute force on P.Fq
 
 
 # ---------------------------------------------------------------------------------------------------------------- the brute-force side
 class Case:
     """an oracle constraint system with lookups, its gate records and a witness (15 columns of integers)"""
 
-    def __init__(self, gates, wit, tables=(), runtime_cfg=None, runtime=None):
-        self.gates, self.tables, self.runtime_cfg = gates, list(tables), runtime_cfg
+    def __init__(self, gates, wit, tables=(), runtime_cfg=None, runtime=None, Fo=Fo):
+        self.gates, self.tables, self.runtime_cfg, self.Fo = gates, list(tables), runtime_cfg, Fo
         self.cs = CC.build(Fo, gates, lookup_tables=self.tables, runtime_tables=runtime_cfg)
         self.L = self.cs["lookup"]
         self.n, self.zk = self.cs["n"], self.cs["zk_rows"]
@@ -47,7 +47,7 @@ class Case:
             L, lim = self.L, self.n - self.zk - 1
             cols = [list(c) for c in L.table_cols]
             if runtime is not None:
-                cols[1][L.runtime_offset:L.runtime_offset + len(runtime)] = [v % Fo.p for v in runtime]
+                cols[1][L.runtime_offset:L.runtime_offset + len(runtime)] = [v % self.Fo.p for v in runtime]
             self._sets[key] = {((L.table_ids[t] if L.table_ids is not None else 0),) + tuple(c[t] for c in cols) for t in range(lim)}
         return self._sets[key]
 
@@ -57,7 +57,7 @@ class Case:
         runtime = self.runtime if runtime == "own" else runtime
         table, L = self.table_set(runtime), self.L
         W = len(L.table_cols)
-        cell = lambda c, r: wit[c][r] % Fo.p if r < len(wit[c]) else 0
+        cell = lambda c, r: wit[c][r] % self.Fo.p if r < len(wit[c]) else 0
         out = []
         for r in range(self.n - self.zk - 1):
             for q in L.info.patterns:
@@ -76,17 +76,17 @@ class Case:
         special = {"Zero": khip.GATE_ZERO, "Lookup": khip.GATE_LOOKUP}
         types = [special[g["typ"]] if g["typ"] in special else gids[g["typ"]] for g in self.gates]
         wires = np.array([g["wires"] for g in self.gates], dtype=np.uint32).reshape(self.rows, 7, 2)
-        co = np.stack([F.limbs_many([c % Fo.p for c in (list(g["coeffs"]) + [0] * 15)[:15]]) for g in self.gates])
+        co = np.stack([F.limbs_many([c % self.Fo.p for c in (list(g["coeffs"]) + [0] * 15)[:15]]) for g in self.gates])
         return types, wires, co
 
     def limbs(self, F, wit=None):
-        return np.stack([F.limbs_many([v % Fo.p for v in col]) for col in (self.wit if wit is None else wit)])
+        return np.stack([F.limbs_many([v % self.Fo.p for v in col]) for col in (self.wit if wit is None else wit)])
 
     def spoiled(self, cells):
         """the witness with the cells {(row, column): value} replaced"""
         w = [list(c) for c in self.wit]
         for (r, c), v in cells.items():
-            w[c][r] = v % Fo.p
+            w[c][r] = v % self.Fo.p
         return w
 
 
@@ -107,7 +107,7 @@ def expect(khip, F, case, rep, lk, wit=None, runtime="own"):
 
 
 # ---------------------------------------------------------------------------------------------------------------- circuits
-def fixed_case():
+def fixed_case(Fo=Fo):
     """509 Lookup rows (domain 2^9, L = 508: row 507 is the last checked row, row 508 is not checked) into two tables with the same first two columns:
     id 5 of width 2, id 9 of width 4 whose columns 2 and 3 are non-zero on some rows -- those rows can never be looked up"""
     ent = 40
@@ -127,7 +127,7 @@ def fixed_case():
             if tid == 9:
                 j = [1, 2, 5, 7, 8, 10][(r + k) % 6]                       # rows of table 9 with a zero tail
             wit[1 + 2 * k][r], wit[2 + 2 * k][r] = c0[j], c1[j]
-    case = Case(gates, wit, tables)
+    case = Case(gates, wit, tables, Fo=Fo)
     assert case.n == 512 and case.zk == 3 and len(case.L.table_cols) == 4 and case.L.table_ids is not None
     return case
 
@@ -146,7 +146,7 @@ def no_id_case():
     return case
 
 
-def xor_case():
+def xor_case(Fo=Fo):
     """rows 0..9 Zero, a 64-bit xor from row 10 (four Xor16 rows and its zero row), row 15 a Zero row whose cell 0 is wired to cell (11, 3): 2^9"""
     a, b = 0x0123456789abcdef, 0xfedcba9876543210 ^ 0x1111
     xw = G.xor_witness(Fo, a, b, 64)
@@ -154,12 +154,12 @@ def xor_case():
     CC.connect_cell_pair(gates, (11, 3), (15, 0))
     rows = [[0] * 15 for _ in range(10)] + [list(r) for r in xw] + [[0] * 15]
     rows[15][0] = rows[11][3]
-    case = Case(gates, [[r[c] for r in rows] for c in range(15)])
+    case = Case(gates, [[r[c] for r in rows] for c in range(15)], Fo=Fo)
     assert case.n == 512 and case.L.info.patterns == ["Xor"]
     return case
 
 
-def range_case():
+def range_case(Fo=Fo):
     """RangeCheck0, RangeCheck1, Rot64, ForeignFieldMul, Xor16 and Generic rows at 2^13: the 4096-entry table with id 1, the XOR table, the table-id
     column and thousands of padding rows.  The looked-up cells hold table values; the gates themselves are not satisfied (only the lookups are asked for)."""
     import random
@@ -180,12 +180,12 @@ def range_case():
             for k in range(4):
                 x, y = rnd.randrange(16), rnd.randrange(16)
                 wit[3 + k][r], wit[7 + k][r], wit[11 + k][r] = x, y, x ^ y
-    case = Case(gates, wit)
+    case = Case(gates, wit, Fo=Fo)
     assert case.n == 1 << 13 and case.L.info.patterns == ["Xor", "RangeCheck", "ForeignFieldMul"] and case.L.table_ids is not None
     return case
 
 
-def runtime_case():
+def runtime_case(Fo=Fo):
     """kimchi/src/tests/lookup.rs::test_runtime_table's shape: 20 Lookup rows into five runtime tables, ids 1..5; the second column comes with the call"""
     first, data = [8, 9, 8, 7, 1], [0, 2, 3, 4, 5]
     cfg = [{"id": tid, "first_column": list(first)} for tid in range(1, 6)]
@@ -195,7 +195,7 @@ def runtime_case():
         for k in range(3):
             idx = (r + 2 * k) % 5
             wit[1 + 2 * k][r], wit[2 + 2 * k][r] = first[idx], data[idx]
-    return Case([CC.gate("Lookup", r) for r in range(20)], wit, runtime_cfg=cfg, runtime=data * 5)
+    return Case([CC.gate("Lookup", r) for r in range(20)], wit, runtime_cfg=cfg, runtime=data * 5, Fo=Fo)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the device side
@@ -226,9 +226,47 @@ def created(khip, F, srs, case):
 
 
 def made(khip, F, srs13, build):
-    case = build()
+    case = build() if F.fid == khip.FP else build(P.Fq)
+    assert case.Fo.p == F.p and srs13.curve == (khip.VESTA if F.fid == khip.FP else khip.PALLAS)
     ix = created(khip, F, srs13, case)
     return case, ix, case.limbs(F)
+
+
+@pytest.fixture(scope="module")
+def F_pallas(khip):
+    from proof_systems_amd import prover
+    return prover.Fld(khip.FQ)
+
+
+@pytest.fixture(scope="module")
+def srs13_pallas(khip):
+    return khip.Srs.create(khip.PALLAS, 1 << 13)
+
+
+def index_fixture(khip, F, srs13, build):
+    case, ix, base = made(khip, F, srs13, build)
+    yield case, ix, base
+    ix.free()
+
+
+@pytest.fixture(scope="module")
+def fixed_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, fixed_case)
+
+
+@pytest.fixture(scope="module")
+def ranged_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, range_case)
+
+
+@pytest.fixture(scope="module")
+def xored_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, xor_case)
+
+
+@pytest.fixture(scope="module")
+def runtimed_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, runtime_case)
 
 
 @pytest.fixture(scope="module")
@@ -262,6 +300,15 @@ def runtimed(khip, F, srs13):
 @pytest.fixture(scope="module")
 def library(khip, F, srs13):
     """the library-gate circuits of 2^7 and 2^8 rows (no lookup index), built anew"""
+    yield from library_indexes(khip, F, srs13, Fo)
+
+
+@pytest.fixture(scope="module")
+def library_pallas(khip, F_pallas, srs13_pallas):
+    yield from library_indexes(khip, F_pallas, srs13_pallas, P.Fq)
+
+
+def library_indexes(khip, F, srs13, Fo):
     from proof_systems_amd import prover
     out = {}
     for logn in (7, 8):
@@ -280,7 +327,7 @@ def library(khip, F, srs13):
 def patched(F, base, cells):
     limbs = base.copy()
     for (r, c), v in cells.items():
-        limbs[c, r] = F.limbs(v % Fo.p)
+        limbs[c, r] = F.limbs(v % F.p)
     return limbs
 
 
@@ -288,7 +335,7 @@ def run(khip, F, case, ix, base, cells=None, runtime="own", flags=None):
     """spoil `cells`, call with KH_WITNESS_LOOKUPS alone (or `flags`), compare with the brute force; returns (report, lookup record, misses)"""
     cells = cells or {}
     rt = case.runtime if runtime == "own" else runtime
-    rep, lk = khip.witness_check_full(ix.native, patched(F, base, cells), runtime=F.limbs_many([v % Fo.p for v in rt]) if rt is not None else None,
+    rep, lk = khip.witness_check_full(ix.native, patched(F, base, cells), runtime=F.limbs_many([v % F.p for v in rt]) if rt is not None else None,
                                       flags=khip.WITNESS_LOOKUPS if flags is None else flags)
     ms = expect(khip, F, case, rep, lk, case.spoiled(cells), rt) if flags is None else None
     return rep, lk, ms
@@ -296,7 +343,16 @@ def run(khip, F, case, ix, base, cells=None, runtime="own", flags=None):
 
 # ---- 1. fixed tables, the Lookup pattern: entry, id, tail, several rows, wave boundaries, the last row
 def test_fixed_tables_entries_ids_and_tails(khip, F, fixed):
+    fixed_tables_entries_ids_and_tails_body(khip, F, fixed)
+
+
+def test_fixed_tables_entries_ids_and_tails_on_pallas(khip, F_pallas, fixed_pallas):
+    fixed_tables_entries_ids_and_tails_body(khip, F_pallas, fixed_pallas)
+
+
+def fixed_tables_entries_ids_and_tails_body(khip, F, fixed):
     case, ix, base = fixed
+    Fo = case.Fo
     rep, lk, ms = run(khip, F, case, ix, base)
     assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0 and not ms
     w = case.wit
@@ -329,6 +385,14 @@ def test_fixed_tables_entries_ids_and_tails(khip, F, fixed):
 
 
 def test_fixed_tables_lowest_row_and_slot_counts_and_boundaries(khip, F, fixed):
+    fixed_tables_lowest_row_and_slot_counts_and_boundaries_body(khip, F, fixed)
+
+
+def test_fixed_tables_lowest_row_and_slot_counts_and_boundaries_on_pallas(khip, F_pallas, fixed_pallas):
+    fixed_tables_lowest_row_and_slot_counts_and_boundaries_body(khip, F_pallas, fixed_pallas)
+
+
+def fixed_tables_lowest_row_and_slot_counts_and_boundaries_body(khip, F, fixed):
     case, ix, base = fixed
     w, lim = case.wit, case.n - case.zk - 1
     assert lim == 508 and case.rows == 509
@@ -364,6 +428,14 @@ def test_without_an_id_column_an_unknown_table_id_is_reported(khip, F, srs13):
 
 # ---- 3. the gate tables: Xor16 at 2^9, the range-check patterns at 2^13
 def test_xor_table(khip, F, xored):
+    xor_table_body(khip, F, xored)
+
+
+def test_xor_table_on_pallas(khip, F_pallas, xored_pallas):
+    xor_table_body(khip, F_pallas, xored_pallas)
+
+
+def xor_table_body(khip, F, xored):
     case, ix, base = xored
     rep, lk, ms = run(khip, F, case, ix, base)
     assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0
@@ -377,7 +449,16 @@ def test_xor_table(khip, F, xored):
 
 
 def test_range_check_table_and_next_rows(khip, F, ranged):
+    range_check_table_and_next_rows_body(khip, F, ranged)
+
+
+def test_range_check_table_and_next_rows_on_pallas(khip, F_pallas, ranged_pallas):
+    range_check_table_and_next_rows_body(khip, F_pallas, ranged_pallas)
+
+
+def range_check_table_and_next_rows_body(khip, F, ranged):
     case, ix, base = ranged
+    Fo = case.Fo
     order = [g["typ"] for g in case.gates]
     rep, lk, ms = run(khip, F, case, ix, base)
     assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0
@@ -426,7 +507,16 @@ def test_two_patterns_on_one_row_count_separately(khip, F, srs13):
 
 # ---- 4. runtime tables
 def test_runtime_tables(khip, F, runtimed):
+    runtime_tables_body(khip, F, runtimed)
+
+
+def test_runtime_tables_on_pallas(khip, F_pallas, runtimed_pallas):
+    runtime_tables_body(khip, F_pallas, runtimed_pallas)
+
+
+def runtime_tables_body(khip, F, runtimed):
     case, ix, base = runtimed
+    Fo = case.Fo
     rep, lk, ms = run(khip, F, case, ix, base)
     assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0
     # the same witness against another runtime vector: entry 1 of table 3 changes, the rows that look up (3, 9, 2) miss
@@ -522,6 +612,14 @@ def test_device_witness_and_attached_index(khip, F, srs13, fixed):
 
 # ---- 7. agreement with the prover
 def test_agrees_with_the_prover(khip, F, fixed):
+    agrees_with_the_prover_body(khip, F, fixed)
+
+
+def test_agrees_with_the_prover_on_pallas(khip, F_pallas, fixed_pallas):
+    agrees_with_the_prover_body(khip, F_pallas, fixed_pallas)
+
+
+def agrees_with_the_prover_body(khip, F, fixed):
     from proof_systems_amd import prover
     case, ix, base = fixed
     rng = lambda: V.RefRng(P.StdRng(bytes([5] * 32)))
@@ -597,6 +695,14 @@ def test_messages(khip, F, ranged, fixed):
 
 # ---- 9. gates and wires through the new entry point = kh_witness_check
 def test_gates_and_wires_equal_the_old_entry_point(khip, F, library):
+    gates_and_wires_equal_the_old_entry_point_body(khip, F, library)
+
+
+def test_gates_and_wires_equal_the_old_entry_point_on_pallas(khip, F_pallas, library_pallas):
+    gates_and_wires_equal_the_old_entry_point_body(khip, F_pallas, library_pallas)
+
+
+def gates_and_wires_equal_the_old_entry_point_body(khip, F, library):
     fields = lambda rep: (rep.kind, rep.row, rep.gate, rep.constraints, rep.col, rep.wired_row, rep.wired_col, rep.gate_rows_violated, rep.cells_disconnected)
     for logn in (7, 8):
         ix, w, types = library[logn]

@@ -19,8 +19,8 @@ def user_table():
     return {"id": 2, "data": [[i for i in range(16)], [(7 * i * i + 3) % 1000 for i in range(16)]]}
 
 
-def circuit(rnd, nxor=40, nlookup=30):
-    """gate names per row and a witness whose lookups are all in the tables (other cells random)."""
+def circuit(rnd, nxor=40, nlookup=30, p=p):
+    """gate names per row and a witness whose lookups are all in the tables (other cells random, below the modulus p)."""
     gates = ["Generic"] * (N - ZK)
     rows = rnd.sample(range(0, N - ZK - 2), nxor + nlookup)
     wit = [[rnd.randrange(p) for _ in range(N)] for _ in range(15)]

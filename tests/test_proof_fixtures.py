@@ -16,7 +16,8 @@ from oracle import prover as OPR
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIX = os.path.join(HERE, "golden", "proof_fixtures")
 sys.path.insert(0, os.path.join(HERE, "golden"))
-NAMES = ["bench_vesta_2_10", "bench_vesta_2_16", "bench_pallas_2_16", "bench_vesta_2_17_over_2_16", "bench_vesta_2_16_prev1", "and_lookup_vesta_2_13", "generic_public_vesta_2_16", "library_gates_vesta_2_13"]
+NAMES = ["bench_vesta_2_10", "bench_vesta_2_16", "bench_pallas_2_16", "bench_vesta_2_17_over_2_16", "bench_vesta_2_16_prev1", "and_lookup_vesta_2_13", "generic_public_vesta_2_16", "library_gates_vesta_2_13",
+         "library_gates_pallas_2_13", "and_lookup_pallas_2_13"]
 
 
 def _load(name):
@@ -55,3 +56,19 @@ def test_small_fixture_is_what_the_generator_writes_today():
         finally:
             OPR.FAST_LOG = 8
         assert OPR.serialize_proof(C, proof) == raw
+
+
+@pytest.mark.parametrize("name", ["library_gates_pallas_2_13", "and_lookup_pallas_2_13"])
+def test_pallas_fixtures_are_the_twins_of_the_vesta_ones(name):
+    """the records of the two Pallas fixtures against the generator's table as it is now (curve, sizes, seed) and against their Vesta twins: the same
+    circuit family with the same number of rows, over the other field -- another index, another proof"""
+    import make_proof_fixtures as M
+    rec, raw = _load(name)
+    cid, log2_n, log_srs, seed = M.CASES[name]
+    assert (cid, rec["curve"], rec["log2_n"], rec["log2_srs"], rec["seed_hex"]) == (1, "pallas", log2_n, log_srs, seed.hex())
+    vname = name.replace("pallas", "vesta")
+    twin, vraw = _load(vname)
+    assert M.CASES[vname][:3] == (0, log2_n, log_srs) and twin["seed_hex"] == M.CASES[vname][3].hex() != rec["seed_hex"]
+    assert (rec["gates"], rec["zk_rows"], rec["lookup"], rec["witness"]) == (twin["gates"], twin["zk_rows"], twin["lookup"], twin["witness"])
+    assert rec["lookup"] == name.startswith("and_lookup") and (rec["challenges_hex"]["joint_combiner"] is not None) == rec["lookup"]
+    assert twin["verifier_index_digest_hex"] != rec["verifier_index_digest_hex"] and raw != vraw
