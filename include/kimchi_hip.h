@@ -493,6 +493,82 @@ int kh_generic_witness_dev(int field, const uint64_t coeffs[20] /* host: l r o m
                            const uint32_t *rows, size_t row0, size_t row_stride,
                            uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev /* nullable */);
 
+/* ---- Witness schedule: a circuit's gadget and wire steps compiled once, run per proof (csrc/witness_schedule.cpp, csrc/wiring.hip) ----
+ * The circuit is fixed when its index is created and only the inputs change from proof to proof.  A schedule is the witness-side counterpart of
+ * kh_prover_index_create: the list of direct calls above that writes a circuit's witness, described once.  kh_witness_schedule_create does everything
+ * that depends only on the circuit -- every check of the direct calls, against col_len; the rows[] and cells tables uploaded into ONE resident device
+ * block; the host-side constants (a generic half's coefficients over -c_o, ForeignFieldMul's Barrett constant) -- and kh_witness_schedule_run produces
+ * one proof's witness_dev with one call that uploads nothing and checks nothing per cell.
+ * A step is ONE direct call and means exactly what that call means with these arguments: same cells written, same values, same flag rules, NOTHING
+ * else is written.  n, rows / row0 / row_stride, cells / format, sign are the direct call's; a device pointer of the direct call is a kh_witness_ref_t:
+ * buf >= 0 is bufs_dev[buf] + offset bytes of the run, KH_REF_ARENA the run's own scratch arena + offset, KH_REF_NONE a nullable argument left out.
+ * in[] are the call's device inputs in their order, out[] its nullable device outputs in their order; rows, cells and consts are host arrays copied
+ * at create.
+ *   op                       direct call                          in[0]       in[1]     in[2]        out[0]          out[1]     param     consts
+ *   KH_STEP_GATHER           kh_witness_gather_dev                -           -         -            out_dev (req.)  -          -         -
+ *   KH_STEP_SCATTER          kh_witness_scatter_dev               values_dev  -         -            -               -          -         -
+ *   KH_STEP_GENERIC          kh_generic_witness_dev               l_dev       r_dev *   -            out_dev         -          half      coeffs[20]
+ *   KH_STEP_POSEIDON         kh_poseidon_gate_witness_dev         states_dev  -         -            out_states_dev  -          -         -
+ *   KH_STEP_COMPLETE_ADD     kh_complete_add_witness_dev          p1_dev      p2_dev    -            out_dev         -          -         -
+ *   KH_STEP_VARBASEMUL       kh_varbasemul_witness_dev            base_dev    acc0_dev  scalars_dev  out_acc_dev     out_n_dev  num_bits  -
+ *   KH_STEP_ENDOMUL          kh_endomul_witness_dev               base_dev    acc0_dev  chals_dev    out_acc_dev     out_n_dev  num_bits  endo[4]
+ *   KH_STEP_ENDOMUL_SCALAR   kh_endomul_scalar_witness_dev        chals_dev   -         -            out_dev         -          num_bits  endo_scalar[4] *
+ *   KH_STEP_RANGE_CHECK      kh_range_check_witness_dev           limbs_dev   -         -            -               -          compact   -
+ *   KH_STEP_XOR              kh_xor_witness_dev                   in1_dev     in2_dev   -            out_dev         -          bits      -
+ *   KH_STEP_ROT64            kh_rot64_witness_dev                 words_dev   -         -            out_dev         -          rot       -
+ *   KH_STEP_FF_ADD           kh_foreign_field_add_witness_dev     left_dev    right_dev -            out_dev         -          -         modulus[6]
+ *   KH_STEP_FF_MUL           kh_foreign_field_mul_witness_dev     a_dev       b_dev     -            out_checks_dev  -          -         modulus[6]
+ * (* nullable as in the direct call; every out[] but the gather's is nullable; refs and fields a call does not have are ignored.)  flag_bit: the
+ * direct call's `bit` on the run's flags_dev, or KH_STEP_NO_FLAG for a step that passes flags_dev = NULL; calls without a flag ignore it.
+ * A run is equivalent to the direct calls issued in step order on the calling thread's current context: a vector step like them, queued on that
+ * context's main stream and ordered against every other call -- a consumer (kh_witness_check, kh_prove) needs no kh_sync --, and it waits for the
+ * device only where they do (once per slice in VarBaseMul / EndoMul steps).  The arena (arena_bytes, not zeroed) and the chain steps' scratch come from
+ * the kh_dev_alloc pool for the time of the run, so a schedule is immutable after create and may be run from several threads and contexts of its
+ * device at once.
+ * Wire steps are many and tiny.  Consecutive KH_STEP_GATHER steps whose out[0] is in the arena run as ONE launch (k_cell_moves, one lane per cell, formats
+ * and flag bits mixed inside a wave), and likewise consecutive KH_STEP_SCATTER steps whose in[0] is; a step starts a new group where fusing would
+ * change the result of running the steps one after another: a gather whose output extent overlaps an earlier output of the group, a scatter with a
+ * target cell the group already targets.  A wire step on a caller buffer runs on its own like the direct call.
+ * kh_witness_schedule_create: KH_E_INVALID, *out untouched, with a kh_last_error text that names the step and, for a table entry, its index
+ * ("kh_witness_schedule_create: step 7 (KH_STEP_GATHER): cell 3 at (row 300, column 0) is outside ...") for everything the direct call refuses, and
+ * for a ref: buf >= n_bufs or below KH_REF_NONE, an offset not aligned as the direct call demands of that pointer, an arena extent past arena_bytes, a
+ * required ref that is KH_REF_NONE; an unknown op; flag_bit >= 32 that is not KH_STEP_NO_FLAG.  It waits for its upload: the schedule is ready when
+ * it returns.
+ * kh_witness_schedule_run checks only what changes between runs -- n_bufs is the schedule's, bufs_dev[k] / witness_dev non-null and 16-byte aligned,
+ * flags_dev 4-byte aligned (nullable: no step raises a flag), col_stride >= col_len, byte counts -- and returns KH_E_INVALID before anything is
+ * launched and with nothing written.  Its host work is O(steps); nothing goes through the staging ring (kh_counter("table_staged_words")).
+ * kh_witness_schedule_info: steps; launch_groups = the launcher invocations a run makes (a fused group counts once, a step with n = 0 not at all);
+ * resident_bytes = the device block holding the tables; run_bytes = what a run takes from the pool (arena + chain scratch at the current slice knob).
+ * kh_witness_schedule_free: no run of the schedule may be in progress on another thread; queued device work is waited for. */
+typedef struct kh_witness_schedule kh_witness_schedule_t;
+#define KH_REF_NONE  (-2)   /* a nullable argument that is absent */
+#define KH_REF_ARENA (-1)   /* the run's own scratch arena */
+#define KH_STEP_NO_FLAG 255 /* flag_bit of a step that raises no flag */
+enum { KH_STEP_GATHER = 0, KH_STEP_SCATTER = 1, KH_STEP_GENERIC = 2, KH_STEP_POSEIDON = 3, KH_STEP_COMPLETE_ADD = 4, KH_STEP_VARBASEMUL = 5,
+       KH_STEP_ENDOMUL = 6, KH_STEP_ENDOMUL_SCALAR = 7, KH_STEP_RANGE_CHECK = 8, KH_STEP_XOR = 9, KH_STEP_ROT64 = 10, KH_STEP_FF_ADD = 11,
+       KH_STEP_FF_MUL = 12 };
+typedef struct kh_witness_ref kh_witness_ref_t;
+typedef struct kh_witness_step kh_witness_step_t;
+struct kh_witness_ref { int buf; size_t offset; };   /* buf >= 0: bufs_dev[buf] of the run; offset in bytes */
+struct kh_witness_step {
+    int op;                                   /* KH_STEP_* */
+    size_t n;                                 /* instances; cells for GATHER / SCATTER */
+    const uint32_t *rows; size_t row0, row_stride;   /* placement of a gadget step, exactly as in the direct call */
+    const uint32_t *cells; int format;        /* GATHER / SCATTER: n (row, column) pairs, KH_CELL_* */
+    unsigned param;                           /* num_bits | bits | rot | compact | half, as the direct call names it */
+    int sign;                                 /* ForeignFieldAdd */
+    const uint64_t *consts;                   /* host, copied at create: endo[4] | endo_scalar[4] | modulus[6] | coeffs[20] | Poseidon none */
+    kh_witness_ref_t in[3], out[2];
+    unsigned flag_bit;                        /* < 32, or KH_STEP_NO_FLAG */
+};
+int kh_witness_schedule_create(int field, size_t col_len, const kh_witness_step_t *steps, size_t n_steps,
+                               size_t arena_bytes, size_t n_bufs, kh_witness_schedule_t **out);
+int kh_witness_schedule_run(const kh_witness_schedule_t *s, void *const *bufs_dev, size_t n_bufs,
+                            uint64_t *witness_dev, size_t col_stride, uint32_t *flags_dev);
+int kh_witness_schedule_info(const kh_witness_schedule_t *s, size_t *steps, size_t *launch_groups,
+                             size_t *resident_bytes, size_t *run_bytes);
+void kh_witness_schedule_free(kh_witness_schedule_t *s);
+
 /* ---- scans, batch inversion, division by a linear factor: the permutation argument's vector steps ----
  * kh_field_scan_dev: in-place inclusive prefix (reverse = 0) or suffix (reverse = 1) scan under + or *
  *   (the running product z[j+1] = z[j] * ..., kimchi/src/circuits/polynomials/permutation.rs:556-563).
@@ -697,7 +773,8 @@ int kh_last_timings(const char **names, float *ms, int cap);
  * materialising the folded basis of their late rounds, switched over to it, gave it up), "rebased_rounds" (rounds that ran over a materialised
  * basis), "lookup_sorted_dev" (successful kh_lookup_sorted_dev calls; kh_prove makes one per proof with lookups), "ipa_concurrent" (kh_ipa_begin calls
  * that found another opening live on the same handle and went ahead beside it), "ipa_waited" (kh_ipa_begin calls that found every workspace of the handle
- * claimed; counted before the wait starts).  Unknown names read 0. */
+ * claimed; counted before the wait starts), "table_staged_words" (the uint32_t words of rows[] / cells tables that the gadget and wire calls and
+ * kh_witness_schedule_create sent through the staging ring; kh_witness_schedule_run adds none).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,

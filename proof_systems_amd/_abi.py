@@ -12,7 +12,7 @@ _NAME = r"[A-Za-z_][A-Za-z0-9_]*"
 def parse(path=HEADER):
     """(prototypes, structs, constants), each in the header's order:
     prototypes  {name: (return type, [(C type, parameter name)])}; an array parameter `uint64_t out[4]` has the type `uint64_t *`
-    structs     {name: [(field, C type, [array dimensions])]} of the `typedef struct [tag] { ... } kh_name_t;` records a caller fills in
+    structs     {name: [(field, C type, [array dimensions])]} of the records a caller fills in, under their typedef names
     constants   {name: int} of the `#define KH_*` lines, then of the anonymous enums (token opcodes, scan operators)"""
     src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
     prototypes = {}
@@ -24,7 +24,10 @@ def parse(path=HEADER):
             params.append((m.group(1).strip() + (" *" if m.group(3) else ""), m.group(2)))
         prototypes[name] = (ret.strip(), params)
     structs = {}
-    for body, name in re.findall(r"typedef\s+struct\s*(?:kh_[a-z_0-9]+\s*)?\{([^}]*)\}\s*(kh_[a-z_0-9]+)\s*;", src):
+    # `typedef struct [tag] { ... } kh_name_t;`, or `struct kh_name { ... };` with its `typedef struct kh_name kh_name_t;` elsewhere
+    later = dict(re.findall(r"typedef\s+struct\s+(kh_[a-z_0-9]+)\s+(kh_[a-z_0-9]+)\s*;", src))
+    records = re.findall(r"(?:typedef\s+)?struct\s*(kh_[a-z_0-9]+)?\s*\{([^}]*)\}\s*(kh_[a-z_0-9]+)?\s*;", src)
+    for body, name in [(b, n or later[tag]) for tag, b, n in records]:
         declarator = _NAME + r"(?:\s*\[\d+\])*"                                   # a field, or an array field: entry[3][4]
         fields = []
         for decl in filter(None, (d.strip() for d in body.split(";"))):

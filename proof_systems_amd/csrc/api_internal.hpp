@@ -1,5 +1,5 @@
 // api_internal.hpp -- what crosses a file boundary between the translation units of the extern "C" boundary (context.hip, srs.cpp, msm_api.cpp,
-// opening.cpp, vector_api.cpp, debug_api.cpp).  State stays private to the file that owns it: only types and functions are declared here.
+// opening.cpp, vector_api.cpp, witness_schedule.cpp, debug_api.cpp).  State stays private to the file that owns it: only types and functions are declared here.
 #pragma once
 #include <atomic>
 #include <map>
@@ -92,7 +92,7 @@ struct PoolBlock {
 };
 // Where instance i of a gadget lands in the 15 witness columns (kh_poseidon_gate_witness_dev and the curve gates' kh_*_witness_dev): it starts at row
 // rows[i], or row0 + i row_stride when rows is null; column c of the witness starts at witness + 4 c col_stride.  The entry points validate it against
-// col_len (vector_api.cpp: place_validate) and hand it on with `rows` on the device; the kernels take it by value.
+// col_len (place_validate below) and hand it on with `rows` on the device; the kernels take it by value.
 struct WitnessPlace {
     const uint32_t* rows;
     size_t row0, row_stride;
@@ -146,4 +146,176 @@ int cell_scatter(Context& C, int field, const uint64_t* values_dev, int format, 
                  uint32_t* flags_dev, unsigned bit);
 int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
                  uint64_t* out_dev);
+// What the launchers of kh_generic_witness_dev and kh_foreign_field_mul_witness_dev compute on the host per call, as a step of its own: a witness
+// schedule (witness_schedule.cpp) takes it once, at create, and launches through the *_prepared halves; the per-call launchers above are
+// prepare + *_prepared.  GenericHalf: c_l c_r c_m c_c, each over -c_o (all zero when c_o = 0).  FfMulConst: the modulus with its Barrett constant
+// (limb_gadgets.hip owns the layout).
+struct GenericHalf { uint64_t l[4][4]; };
+GenericHalf generic_fold(int field, const uint64_t* coeffs);
+int generic_rows_prepared(Context& C, int field, const GenericHalf& co, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
+                          uint64_t* out_dev);
+struct FfMulConst;
+std::shared_ptr<const FfMulConst> ff_mul_prepare(const uint64_t* modulus);
+int ff_mul_rows_prepared(Context& C, int field, const FfMulConst& m, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
+                         uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit);
+// A group of wire steps of a witness schedule in one launch (k_cell_moves): one resident 16-byte record per cell.  The dense side of every move is
+// the run's arena, `dense` words of 8 bytes from its start; flag: the step's bit, or CELL_MOVE_NO_FLAG.
+struct CellMove { uint32_t row, meta, dense_lo, dense_hi; };
+static constexpr uint32_t CELL_MOVE_NO_FLAG = 63;
+inline CellMove cell_move(uint32_t row, uint32_t col, int format, uint32_t flag, uint64_t dense) {
+    return CellMove{row, col | ((uint32_t)format << 4) | (flag << 8), (uint32_t)dense, (uint32_t)(dense >> 32)};
+}
+int cell_moves(Context& C, int field, bool scatter, const CellMove* moves_dev, size_t n, uint64_t* witness_dev, size_t col_stride, uint64_t* arena_dev,
+               uint32_t* flags_dev);
+
+// ------------------------------------------------------------------ what the entry points of the gadget and wire calls refuse (vector_api.cpp), shared
+// with kh_witness_schedule_create (witness_schedule.cpp), which validates a step through the function its direct call uses: `call` names the call, or
+// the step.
+// How a vector step is queued on the main stream: under the context's lock, and when run(C) has queued it, the point is marked that a later MSM on
+// another slot's stream waits for.  The entry points check their arguments in front of this.
+template <class Run>
+int queue_step(Run run) {
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    rc = run(C);
+    if (rc == KH_OK) C.mark_async();
+    return rc;
+}
+// what the 15 witness columns of a call that takes n instances (or cells) are refused for: a null or misaligned witness, columns that overlap or whose
+// byte count overflows
+inline int columns_validate(const char* call, const void* witness, size_t col_stride, size_t col_len, size_t n) {
+    KH_REQUIRE(witness || n == 0, "%s: null witness_dev", call);
+    KH_REQUIRE((((uintptr_t)witness) & 15) == 0, "%s: witness_dev must be 16-byte aligned", call);
+    KH_REQUIRE(col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, col_stride, col_len);
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
+               col_stride);
+    return KH_OK;
+}
+// what a placement (WitnessPlace, rows still on the host) is refused for: its columns, instances of inst_rows rows that do not fit col_len rows
+inline int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t col_len, size_t inst_rows) {
+    int rc = columns_validate(call, at.witness, at.col_stride, col_len, n);
+    if (rc) return rc;
+    if (n > 0 && at.rows) {
+        for (size_t i = 0; i < n; i++)
+            KH_REQUIRE(col_len >= inst_rows && at.rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
+                       at.rows[i], col_len, inst_rows);
+    } else if (n > 0) {
+        KH_REQUIRE(at.row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, at.row_stride, inst_rows);
+        KH_REQUIRE(col_len >= inst_rows && at.row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - at.row0) / at.row_stride,
+                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, at.row0, at.row_stride, col_len);
+    }
+    return KH_OK;
+}
+struct GadgetPtr { const char* name; const void* p; bool required; unsigned align = 16; };
+// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
+inline int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
+    for (const GadgetPtr& a : ptrs) {
+        KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
+        KH_REQUIRE((((uintptr_t)a.p) & (a.align - 1)) == 0, "%s: %s must be %u-byte aligned", call, a.name, a.align);
+    }
+    return place_validate(call, at, n, col_len, inst_rows);
+}
+// what the five limb gadgets refuse alike after their own arguments: gadget_validate's list, more lanes (one per instance and row) than a grid takes, a
+// flag word that is misaligned or a bit that is not one
+inline int limb_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows,
+                         const uint32_t* flags_dev = nullptr, unsigned bit = 0) {
+    int rc = gadget_validate(call, field, ptrs, n, at, col_len, inst_rows);
+    if (rc) return rc;
+    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / inst_rows, "%s: %zu instances of %zu rows overflow the byte count", call, n, inst_rows);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
+    return KH_OK;
+}
+// a foreign modulus: three limbs of two u64 on the host, each < 2^88, not all zero
+inline int modulus_validate(const char* call, const uint64_t* modulus, size_t n) {
+    KH_REQUIRE(modulus || n == 0, "%s: null modulus", call);
+    if (!modulus) return KH_OK;
+    KH_REQUIRE((modulus[1] | modulus[3] | modulus[5]) >> 24 == 0, "%s: a modulus limb is 2^88 or more", call);
+    KH_REQUIRE((modulus[0] | modulus[1] | modulus[2] | modulus[3] | modulus[4] | modulus[5]) != 0, "%s: the modulus is zero", call);
+    return KH_OK;
+}
+// what the two cell calls refuse alike: the field and the format, their columns, the dense buffer (`data`: out_dev / values_dev, aligned to its
+// format's access), the flag word, a cell outside the 15 columns of col_len rows
+inline int cells_validate(const char* call, int field, int format, const void* witness, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n,
+                          const char* data_name, const void* data, const uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
+    KH_REQUIRE(format >= KH_CELL_FIELD && format <= KH_CELL_U64, "%s: unknown cell format %d", call, format);
+    int rc = columns_validate(call, witness, col_stride, col_len, n);
+    if (rc) return rc;
+    const unsigned align = format == KH_CELL_U64 ? 8 : 16;
+    KH_REQUIRE((cells && data) || n == 0, "%s: null %s", call, cells ? data_name : "cells");
+    KH_REQUIRE((((uintptr_t)data) & (align - 1)) == 0, "%s: %s must be %u-byte aligned", call, data_name, align);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
+    for (size_t i = 0; i < n; i++)
+        KH_REQUIRE(cells[2 * i] < col_len && cells[2 * i + 1] < 15, "%s: cell %zu at (row %u, column %u) is outside the 15 columns of %zu rows", call, i, cells[2 * i],
+                   cells[2 * i + 1], col_len);
+    return KH_OK;
+}
+// ... and each gadget call's own list, in the order the call has always checked it
+inline int poseidon_gate_validate(const char* call, int field, const void* states_dev, size_t n, const WitnessPlace& at, size_t col_len, const void* out_states_dev) {
+    return gadget_validate(call, field, {{"states_dev", states_dev, true}, {"out_states_dev", out_states_dev, false}}, n, at, col_len, 12);
+}
+inline int complete_add_validate(const char* call, int field, const void* p1_dev, const void* p2_dev, size_t n, const WitnessPlace& at, size_t col_len,
+                                 const void* out_dev) {
+    return gadget_validate(call, field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
+}
+inline int endomul_scalar_validate(const char* call, int field, const void* chals_dev, unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len,
+                                   const uint64_t* endo_scalar, const void* out_dev) {
+    KH_REQUIRE(num_bits >= 16 && num_bits <= 128 && num_bits % 16 == 0, "%s: num_bits %u is not a multiple of 16 from 16 to 128", call, num_bits);
+    int rc = gadget_validate(call, field, {{"chals_dev", chals_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, num_bits / 16);
+    if (rc) return rc;
+    KH_REQUIRE(endo_scalar || !out_dev || n == 0, "%s: null endo_scalar with an out_dev", call);
+    return KH_OK;
+}
+// VarBaseMul (endo == nullptr, scalars of 4 limbs) and EndoMul (challenges of 2 limbs) share everything but their row counts
+inline int chain_validate(const char* call, int field, bool is_endo, const uint64_t* endo, const void* base_dev, const void* acc0_dev, const void* scalars_dev,
+                          unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len, const void* out_acc_dev, const void* out_n_dev,
+                          const uint32_t* flags_dev, unsigned bit) {
+    if (is_endo) KH_REQUIRE(num_bits >= 4 && num_bits <= 128 && num_bits % 4 == 0, "%s: num_bits %u is not a multiple of 4 from 4 to 128", call, num_bits);
+    else KH_REQUIRE(num_bits >= 5 && num_bits <= 255 && num_bits % 5 == 0, "%s: num_bits %u is not a multiple of 5 from 5 to 255", call, num_bits);
+    int rc = gadget_validate(call, field, {{"base_dev", base_dev, true}, {"acc0_dev", acc0_dev, true}, {is_endo ? "chals_dev" : "scalars_dev", scalars_dev, true},
+                             {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
+                             n, at, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
+    if (rc) return rc;
+    KH_REQUIRE(!is_endo || endo || n == 0, "%s: null endo", call);
+    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (void*)flags_dev);
+    return KH_OK;
+}
+inline int range_check_validate(const char* call, int field, const void* limbs_dev, size_t n, int compact, const WitnessPlace& at, size_t col_len,
+                                const uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(compact == 0 || compact == 1, "%s: compact is %d, not 0 or 1", call, compact);
+    return limb_validate(call, field, {{"limbs_dev", limbs_dev, true}}, n, at, col_len, 4, flags_dev, bit);
+}
+inline int xor_validate(const char* call, int field, const void* in1_dev, const void* in2_dev, unsigned bits, size_t n, const WitnessPlace& at, size_t col_len,
+                        const void* out_dev, const uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(bits >= 1 && bits <= 254, "%s: bits %u is not from 1 to 254", call, bits);
+    return limb_validate(call, field, {{"in1_dev", in1_dev, true}, {"in2_dev", in2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, (bits + 15) / 16 + 1,
+                         flags_dev, bit);
+}
+inline int rot64_validate(const char* call, int field, const void* words_dev, unsigned rot, size_t n, const WitnessPlace& at, size_t col_len, const void* out_dev) {
+    KH_REQUIRE(rot <= 63, "%s: rot %u is not from 0 to 63", call, rot);
+    return limb_validate(call, field, {{"words_dev", words_dev, true, 8}, {"out_dev", out_dev, false, 8}}, n, at, col_len, 3);
+}
+inline int ff_add_validate(const char* call, int field, const uint64_t* modulus, const void* left_dev, const void* right_dev, int sign, size_t n,
+                           const WitnessPlace& at, size_t col_len, const void* out_dev, const uint32_t* flags_dev, unsigned bit) {
+    KH_REQUIRE(sign == 1 || sign == -1, "%s: sign is %d, not +1 or -1", call, sign);
+    int rc = modulus_validate(call, modulus, n);
+    if (rc) return rc;
+    return limb_validate(call, field, {{"left_dev", left_dev, true}, {"right_dev", right_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 2, flags_dev, bit);
+}
+inline int ff_mul_validate(const char* call, int field, const uint64_t* modulus, const void* a_dev, const void* b_dev, size_t n, const WitnessPlace& at,
+                           size_t col_len, const void* out_checks_dev, const uint32_t* flags_dev, unsigned bit) {
+    int rc = modulus_validate(call, modulus, n);
+    if (rc) return rc;
+    return limb_validate(call, field, {{"a_dev", a_dev, true}, {"b_dev", b_dev, true}, {"out_checks_dev", out_checks_dev, false}}, n, at, col_len, 2, flags_dev, bit);
+}
+inline int generic_validate(const char* call, int field, const uint64_t* coeffs, int half, const void* l_dev, const void* r_dev, size_t n, const WitnessPlace& at,
+                            size_t col_len, const void* out_dev) {
+    KH_REQUIRE(half == 0 || half == 1, "%s: half is %d, not 0 or 1", call, half);
+    int rc = gadget_validate(call, field, {{"l_dev", l_dev, true}, {"r_dev", r_dev, false}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
+    if (rc) return rc;
+    KH_REQUIRE(coeffs || n == 0, "%s: null coeffs", call);
+    return KH_OK;
+}
 }  // namespace kh

@@ -324,14 +324,22 @@ int ff_add_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* 
     C.timer.mark("foreign_field_add", C.stream);
     return KH_OK;
 }
-int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
-                uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit) {
-    const limb::FfModulus m = limb::ff_modulus(host_limbs(modulus));
+struct FfMulConst { limb::FfModulus m; };
+std::shared_ptr<const FfMulConst> ff_mul_prepare(const uint64_t* modulus) {
+    return std::make_shared<const FfMulConst>(FfMulConst{limb::ff_modulus(host_limbs(modulus))});
+}
+int ff_mul_rows_prepared(Context& C, int field, const FfMulConst& m, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
+                         uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit) {
     C.timer.begin(C.stream);
-    KH_FIELD_LAUNCH(field, k_ff_mul<F>, blocks_of(2 * n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)a_dev, (const u64*)b_dev, n, m, at,
+    KH_FIELD_LAUNCH(field, k_ff_mul<F>, blocks_of(2 * n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)a_dev, (const u64*)b_dev, n, m.m, at,
                     (u64*)out_checks_dev, flags_dev, (u32)bit);
     C.timer.mark("foreign_field_mul", C.stream);
     return KH_OK;
+}
+int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
+                uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit) {
+    const FfMulConst m{limb::ff_modulus(host_limbs(modulus))};
+    return ff_mul_rows_prepared(C, field, m, a_dev, b_dev, n, at, out_checks_dev, flags_dev, bit);
 }
 // the limbs of f and of 2^264 - f, two u64 each (kh_foreign_field_gate_coefficients reduces them into the field)
 void ff_negated_modulus(const uint64_t* modulus, uint64_t* nf_out) {

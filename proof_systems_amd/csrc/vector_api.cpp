@@ -8,18 +8,6 @@ using namespace kh;
 
 namespace {
 #include "poseidon_params.inc"      // the round constants kh_poseidon_gate_coefficients hands out (the host sponge and the device kernels have the same table)
-
-// How a vector step is queued on the main stream: under the context's lock, and when run(C) has queued it, the point is marked that a later MSM on
-// another slot's stream waits for.  The entry points check their arguments in front of this.
-template <class Run>
-int queue_step(Run run) {
-    int rc = ensure_init(); if (rc) return rc;
-    Context& C = ctx();
-    std::lock_guard<std::mutex> lk(C.mu);
-    rc = run(C);
-    if (rc == KH_OK) C.mark_async();
-    return rc;
-}
 }
 
 // transfer buffers of the host-pointer transforms (kh_ntt / kh_lde: host_transform below)
@@ -238,41 +226,6 @@ int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return 
 // ---------------------------------------------------------------------------------- gadget witnesses on the device (kernels in poseidon.hip, curve_gadgets.hip)
 }  // extern "C"
 namespace {
-// what the 15 witness columns of a call that takes n instances (or cells) are refused for: a null or misaligned witness, columns that overlap or whose
-// byte count overflows
-int columns_validate(const char* call, const void* witness, size_t col_stride, size_t col_len, size_t n) {
-    KH_REQUIRE(witness || n == 0, "%s: null witness_dev", call);
-    KH_REQUIRE((((uintptr_t)witness) & 15) == 0, "%s: witness_dev must be 16-byte aligned", call);
-    KH_REQUIRE(col_stride >= col_len, "%s: col_stride %zu is less than col_len %zu", call, col_stride, col_len);
-    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N && col_stride <= SIZE_MAX / (32 * 15), "%s: %zu instances in columns %zu elements apart overflow the byte count", call, n,
-               col_stride);
-    return KH_OK;
-}
-// what a placement (WitnessPlace, rows still on the host) is refused for: its columns, instances of inst_rows rows that do not fit col_len rows
-int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t col_len, size_t inst_rows) {
-    int rc = columns_validate(call, at.witness, at.col_stride, col_len, n);
-    if (rc) return rc;
-    if (n > 0 && at.rows) {
-        for (size_t i = 0; i < n; i++)
-            KH_REQUIRE(col_len >= inst_rows && at.rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
-                       at.rows[i], col_len, inst_rows);
-    } else if (n > 0) {
-        KH_REQUIRE(at.row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, at.row_stride, inst_rows);
-        KH_REQUIRE(col_len >= inst_rows && at.row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - at.row0) / at.row_stride,
-                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, at.row0, at.row_stride, col_len);
-    }
-    return KH_OK;
-}
-struct GadgetPtr { const char* name; const void* p; bool required; unsigned align = 16; };
-// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
-int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
-    for (const GadgetPtr& a : ptrs) {
-        KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
-        KH_REQUIRE((((uintptr_t)a.p) & (a.align - 1)) == 0, "%s: %s must be %u-byte aligned", call, a.name, a.align);
-    }
-    return place_validate(call, at, n, col_len, inst_rows);
-}
 // The queueing of a validated call with a host table of `words` uint32_t (start rows, cells; nullable): the table travels through the pinned staging
 // ring into a block of the kh_dev_alloc pool (taken before the context's lock, like kh_lookup_sorted_dev's scratch), in pieces that leave the ring its
 // size -- the caller's array is not read after this returns -- and launch(C, table_dev) runs with the table on the device (null without one).
@@ -283,6 +236,7 @@ int table_queue(const uint32_t* table, size_t words, Launch launch) {
     if (table && (rc = kh_dev_alloc(&table_dev.p, words * sizeof(uint32_t)))) return rc;
     return queue_step([&](Context& C) {
         const size_t piece = (size_t)1 << 15;
+        if (table) counter(CNT_TABLE_STAGED_WORDS) += words;
         for (size_t i = 0; table && i < words; i += piece) {
             const int up = C.stage_upload(table_dev.as<uint32_t>() + i, {{table + i, std::min(piece, words - i) * sizeof(uint32_t)}});
             if (up) return up;
@@ -302,39 +256,29 @@ extern "C" {
 int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                                  uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_states_dev) {
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = gadget_validate("kh_poseidon_gate_witness_dev", field, {{"states_dev", states_dev, true}, {"out_states_dev", out_states_dev, false}}, n, at, col_len, 12);
+    int rc = poseidon_gate_validate("kh_poseidon_gate_witness_dev", field, states_dev, n, at, col_len, out_states_dev);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return poseidon_gate_rows(C, field, states_dev, n, dev, out_states_dev); });
 }
 int kh_complete_add_witness_dev(int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = gadget_validate("kh_complete_add_witness_dev", field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
+    int rc = complete_add_validate("kh_complete_add_witness_dev", field, p1_dev, p2_dev, n, at, col_len, out_dev);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return complete_add_rows(C, field, p1_dev, p2_dev, n, dev, out_dev); });
 }
 int kh_endomul_scalar_witness_dev(int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                                   uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t* out_dev) {
-    KH_REQUIRE(num_bits >= 16 && num_bits <= 128 && num_bits % 16 == 0, "kh_endomul_scalar_witness_dev: num_bits %u is not a multiple of 16 from 16 to 128",
-               num_bits);
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = gadget_validate("kh_endomul_scalar_witness_dev", field, {{"chals_dev", chals_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, num_bits / 16);
+    int rc = endomul_scalar_validate("kh_endomul_scalar_witness_dev", field, chals_dev, num_bits, n, at, col_len, endo_scalar, out_dev);
     if (rc) return rc;
-    KH_REQUIRE(endo_scalar || !out_dev || n == 0, "kh_endomul_scalar_witness_dev: null endo_scalar with an out_dev");
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return endomul_scalar_rows(C, field, chals_dev, num_bits, n, dev, endo_scalar, out_dev); });
 }
-// VarBaseMul (endo == nullptr, scalars of 4 limbs) and EndoMul (challenges of 2 limbs) share everything but their row counts
 static int chain_witness(const char* call, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev,
                          const uint64_t* scalars_dev, unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len, uint64_t* out_acc_dev,
                          uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    if (is_endo) KH_REQUIRE(num_bits >= 4 && num_bits <= 128 && num_bits % 4 == 0, "%s: num_bits %u is not a multiple of 4 from 4 to 128", call, num_bits);
-    else KH_REQUIRE(num_bits >= 5 && num_bits <= 255 && num_bits % 5 == 0, "%s: num_bits %u is not a multiple of 5 from 5 to 255", call, num_bits);
-    int rc = gadget_validate(call, field, {{"base_dev", base_dev, true}, {"acc0_dev", acc0_dev, true}, {is_endo ? "chals_dev" : "scalars_dev", scalars_dev, true},
-                             {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
-                             n, at, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
+    int rc = chain_validate(call, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, at, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
     if (rc) return rc;
-    KH_REQUIRE(!is_endo || endo || n == 0, "%s: null endo", call);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (void*)flags_dev);
     PoolBlock scratch;
     const size_t scratch_bytes = chain_scratch_bytes(is_endo, num_bits, n);
     if (n > 0 && (rc = kh_dev_alloc(&scratch.p, scratch_bytes))) return rc;
@@ -358,24 +302,6 @@ int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t* ba
 int kh_curve_witness_set_slice_elements(size_t elements) { chain_set_slice_elements(elements); return KH_OK; }
 
 // ---------------------------------------------------------------------------------- the optional gates' witnesses (kernels in limb_gadgets.hip)
-// what the five limb gadgets refuse alike after their own arguments: gadget_validate's list, more lanes (one per instance and row) than a grid takes, a
-// flag word that is misaligned or a bit that is not one
-static int limb_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows,
-                         const uint32_t* flags_dev = nullptr, unsigned bit = 0) {
-    int rc = gadget_validate(call, field, ptrs, n, at, col_len, inst_rows);
-    if (rc) return rc;
-    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / inst_rows, "%s: %zu instances of %zu rows overflow the byte count", call, n, inst_rows);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
-    return KH_OK;
-}
-// a foreign modulus: three limbs of two u64 on the host, each < 2^88, not all zero
-static int modulus_validate(const char* call, const uint64_t* modulus, size_t n) {
-    KH_REQUIRE(modulus || n == 0, "%s: null modulus", call);
-    if (!modulus) return KH_OK;
-    KH_REQUIRE((modulus[1] | modulus[3] | modulus[5]) >> 24 == 0, "%s: a modulus limb is 2^88 or more", call);
-    KH_REQUIRE((modulus[0] | modulus[1] | modulus[2] | modulus[3] | modulus[4] | modulus[5]) != 0, "%s: the modulus is zero", call);
-    return KH_OK;
-}
 int kh_foreign_field_gate_coefficients(int field, const uint64_t modulus[6], uint64_t* out) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "kh_foreign_field_gate_coefficients: unknown field id %d", field);
     KH_REQUIRE(out, "kh_foreign_field_gate_coefficients: null output");
@@ -393,38 +319,30 @@ int kh_foreign_field_gate_coefficients(int field, const uint64_t modulus[6], uin
 }
 int kh_range_check_witness_dev(int field, const uint64_t* limbs_dev, size_t n, int compact, const uint32_t* rows, size_t row0, size_t row_stride,
                                uint64_t* witness_dev, size_t col_stride, size_t col_len, uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(compact == 0 || compact == 1, "kh_range_check_witness_dev: compact is %d, not 0 or 1", compact);
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = limb_validate("kh_range_check_witness_dev", field, {{"limbs_dev", limbs_dev, true}}, n, at, col_len, 4, flags_dev, bit);
+    int rc = range_check_validate("kh_range_check_witness_dev", field, limbs_dev, n, compact, at, col_len, flags_dev, bit);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return range_check_rows(C, field, limbs_dev, n, compact, dev, flags_dev, bit); });
 }
 int kh_xor_witness_dev(int field, const uint64_t* in1_dev, const uint64_t* in2_dev, unsigned bits, size_t n, const uint32_t* rows, size_t row0,
                        size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(bits >= 1 && bits <= 254, "kh_xor_witness_dev: bits %u is not from 1 to 254", bits);
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = limb_validate("kh_xor_witness_dev", field, {{"in1_dev", in1_dev, true}, {"in2_dev", in2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len,
-                           (bits + 15) / 16 + 1, flags_dev, bit);
+    int rc = xor_validate("kh_xor_witness_dev", field, in1_dev, in2_dev, bits, n, at, col_len, out_dev, flags_dev, bit);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return xor_rows(C, field, in1_dev, in2_dev, bits, n, dev, out_dev, flags_dev, bit); });
 }
 int kh_rot64_witness_dev(int field, const uint64_t* words_dev, unsigned rot, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
                          uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    KH_REQUIRE(rot <= 63, "kh_rot64_witness_dev: rot %u is not from 0 to 63", rot);
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = limb_validate("kh_rot64_witness_dev", field, {{"words_dev", words_dev, true, 8}, {"out_dev", out_dev, false, 8}}, n, at, col_len, 3);
+    int rc = rot64_validate("kh_rot64_witness_dev", field, words_dev, rot, n, at, col_len, out_dev);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return rot64_rows(C, field, words_dev, rot, n, dev, out_dev); });
 }
 int kh_foreign_field_add_witness_dev(int field, const uint64_t modulus[6], const uint64_t* left_dev, const uint64_t* right_dev, int sign, size_t n,
                                      const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
                                      uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(sign == 1 || sign == -1, "kh_foreign_field_add_witness_dev: sign is %d, not +1 or -1", sign);
-    int rc = modulus_validate("kh_foreign_field_add_witness_dev", modulus, n);
-    if (rc) return rc;
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    rc = limb_validate("kh_foreign_field_add_witness_dev", field, {{"left_dev", left_dev, true}, {"right_dev", right_dev, true}, {"out_dev", out_dev, false}}, n, at,
-                       col_len, 2, flags_dev, bit);
+    int rc = ff_add_validate("kh_foreign_field_add_witness_dev", field, modulus, left_dev, right_dev, sign, n, at, col_len, out_dev, flags_dev, bit);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
         return ff_add_rows(C, field, modulus, left_dev, right_dev, sign, n, dev, out_dev, flags_dev, bit);
@@ -433,11 +351,8 @@ int kh_foreign_field_add_witness_dev(int field, const uint64_t modulus[6], const
 int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const uint32_t* rows,
                                      size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_checks_dev,
                                      uint32_t* flags_dev, unsigned bit) {
-    int rc = modulus_validate("kh_foreign_field_mul_witness_dev", modulus, n);
-    if (rc) return rc;
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    rc = limb_validate("kh_foreign_field_mul_witness_dev", field, {{"a_dev", a_dev, true}, {"b_dev", b_dev, true}, {"out_checks_dev", out_checks_dev, false}}, n, at,
-                       col_len, 2, flags_dev, bit);
+    int rc = ff_mul_validate("kh_foreign_field_mul_witness_dev", field, modulus, a_dev, b_dev, n, at, col_len, out_checks_dev, flags_dev, bit);
     if (rc) return rc;
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
         return ff_mul_rows(C, field, modulus, a_dev, b_dev, n, dev, out_checks_dev, flags_dev, bit);
@@ -445,23 +360,6 @@ int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const
 }
 
 // ---------------------------------------------------------------------------------- wires between the gadgets (kernels in wiring.hip)
-// what the two cell calls refuse alike: the field and the format, their columns, the dense buffer (`data`: out_dev / values_dev, aligned to its
-// format's access), the flag word, a cell outside the 15 columns of col_len rows
-static int cells_validate(const char* call, int field, int format, const void* witness, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n,
-                          const char* data_name, const void* data, const uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
-    KH_REQUIRE(format >= KH_CELL_FIELD && format <= KH_CELL_U64, "%s: unknown cell format %d", call, format);
-    int rc = columns_validate(call, witness, col_stride, col_len, n);
-    if (rc) return rc;
-    const unsigned align = format == KH_CELL_U64 ? 8 : 16;
-    KH_REQUIRE((cells && data) || n == 0, "%s: null %s", call, cells ? data_name : "cells");
-    KH_REQUIRE((((uintptr_t)data) & (align - 1)) == 0, "%s: %s must be %u-byte aligned", call, data_name, align);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
-    for (size_t i = 0; i < n; i++)
-        KH_REQUIRE(cells[2 * i] < col_len && cells[2 * i + 1] < 15, "%s: cell %zu at (row %u, column %u) is outside the 15 columns of %zu rows", call, i, cells[2 * i],
-                   cells[2 * i + 1], col_len);
-    return KH_OK;
-}
 int kh_witness_gather_dev(int field, const uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n, int format,
                           uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
     int rc = cells_validate("kh_witness_gather_dev", field, format, witness_dev, col_stride, col_len, cells, n, "out_dev", out_dev, flags_dev, bit);
@@ -482,11 +380,9 @@ int kh_witness_scatter_dev(int field, const uint64_t* values_dev, int format, co
 }
 int kh_generic_witness_dev(int field, const uint64_t coeffs[20], int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const uint32_t* rows,
                            size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    KH_REQUIRE(half == 0 || half == 1, "kh_generic_witness_dev: half is %d, not 0 or 1", half);
     const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = gadget_validate("kh_generic_witness_dev", field, {{"l_dev", l_dev, true}, {"r_dev", r_dev, false}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
+    int rc = generic_validate("kh_generic_witness_dev", field, coeffs, half, l_dev, r_dev, n, at, col_len, out_dev);
     if (rc) return rc;
-    KH_REQUIRE(coeffs || n == 0, "kh_generic_witness_dev: null coeffs");
     return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return generic_rows(C, field, coeffs, half, l_dev, r_dev, n, dev, out_dev); });
 }
 

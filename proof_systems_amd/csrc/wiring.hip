@@ -12,9 +12,11 @@
 //                     high words tested for the flag
 //   k_cell_scatter    value -> cell: KH_CELL_FIELD copies; every other format is one product by R^2; a KH_CELL_INT256 value is compared with p, a
 //                     KH_CELL_LIMB88 value with 2^88, for the flag
+//   k_cell_moves      a witness schedule's group of consecutive gathers (or scatters) over its arena in ONE launch: a 16-byte record per lane carries
+//                     the cell, the format, the step's flag bit and the value's place in the arena; the conversions are the two above
 //   k_generic_half    l, r -> l, r, o = l (c_l' + c_m' r) + c_r' r + c_c' with the four coefficients already divided by -c_o on the host (all zero
 //                     when c_o = 0: o = 0): three products, three additions, no inversion on the device
-// The format is a kernel argument: the branches on it are uniform, and a lane diverges from its wave only to raise the flag.
+// In the direct kernels the format is a kernel argument: the branches on it are uniform, and a lane diverges from its wave only to raise the flag.
 #include "common.hpp"
 #include "field.cuh"
 #include "api_internal.hpp"
@@ -35,25 +37,54 @@ __device__ __forceinline__ void raise_cell_flag(u32* flags, u32 bit, bool bad) {
 }
 __device__ __forceinline__ u64 word64(const u32* v, int k) { return (u64)v[2 * k] | ((u64)v[2 * k + 1] << 32); }
 
+// The conversion of ONE cell, the same code for the direct kernels (format uniform across the launch) and for a schedule's fused moves (format per
+// lane).  `dense` is the value's own place on the dense side: cell_words(format) words.  Both return whether the value does not fit its format.
+__device__ __forceinline__ size_t cell_words(int format) { return format == KH_CELL_FIELD || format == KH_CELL_INT256 ? 4 : format == KH_CELL_U64 ? 1 : 2; }
+template <class F>
+__device__ __forceinline__ bool cell_to_value(const u64* __restrict__ cell, int format, u64* __restrict__ dense) {
+    Fe<F> v = Fe<F>::load(cell);
+    if (format != KH_CELL_FIELD) v = from_mont<F>(v);
+    if (format == KH_CELL_FIELD || format == KH_CELL_INT256) { v.store(dense); return false; }
+    if (format == KH_CELL_U64) {
+        dense[0] = word64(v.v, 0);
+        return (word64(v.v, 1) | word64(v.v, 2) | word64(v.v, 3)) != 0;
+    }
+    const bool limb = format == KH_CELL_LIMB88;                     // two words: 128 bits, or 88
+    const u64 hi = word64(v.v, 1);
+    *(ulonglong2*)dense = make_ulonglong2(word64(v.v, 0), limb ? hi & 0xffffffu : hi);
+    return ((limb ? hi >> 24 : 0) | word64(v.v, 2) | word64(v.v, 3)) != 0;
+}
+template <class F>
+__device__ __forceinline__ bool value_to_cell(const u64* __restrict__ dense, int format, u64* __restrict__ cell) {
+    Fe<F> v = Fe<F>::zero();
+    bool bad = false;
+    if (format == KH_CELL_FIELD || format == KH_CELL_INT256) {
+        v = Fe<F>::load(dense);
+        if (format == KH_CELL_INT256) {                             // v >= p: v - p does not borrow
+            u32 br = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) br = (u32)(((u64)v.v[k] - Fe<F>::pw(k) - br) >> 63);
+            bad = br == 0;
+        }
+    } else if (format == KH_CELL_U64) {
+        const u64 w = dense[0];
+        v.v[0] = (u32)w; v.v[1] = (u32)(w >> 32);
+    } else {
+        const ulonglong2 w = *(const ulonglong2*)dense;
+        bad = format == KH_CELL_LIMB88 && (w.y >> 24) != 0;
+        v.v[0] = (u32)w.x; v.v[1] = (u32)(w.x >> 32); v.v[2] = (u32)w.y; v.v[3] = (u32)(w.y >> 32);
+    }
+    if (format != KH_CELL_FIELD) v = to_mont<F>(v);
+    v.store(cell);
+    return bad;
+}
+
 template <class F>
 __global__ void __launch_bounds__(WAVE_BLOCK)
 k_cell_gather(const u64* __restrict__ witness, CellList at, size_t n, int format, u64* __restrict__ out, u32* __restrict__ flags, u32 bit) {
     const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     bool bad = false;
-    if (i < n) {
-        Fe<F> v = Fe<F>::load(witness + at.offset(i));
-        if (format != KH_CELL_FIELD) v = from_mont<F>(v);
-        if (format == KH_CELL_FIELD || format == KH_CELL_INT256) v.store(out + 4 * i);
-        else if (format == KH_CELL_U64) {
-            out[i] = word64(v.v, 0);
-            bad = (word64(v.v, 1) | word64(v.v, 2) | word64(v.v, 3)) != 0;
-        } else {                                                    // two words: 128 bits, or 88
-            const bool limb = format == KH_CELL_LIMB88;
-            const u64 hi = word64(v.v, 1);
-            *(ulonglong2*)(out + 2 * i) = make_ulonglong2(word64(v.v, 0), limb ? hi & 0xffffffu : hi);
-            bad = ((limb ? hi >> 24 : 0) | word64(v.v, 2) | word64(v.v, 3)) != 0;
-        }
-    }
+    if (i < n) bad = cell_to_value<F>(witness + at.offset(i), format, out + cell_words(format) * i);
     raise_cell_flag(flags, bit, bad);
 }
 
@@ -62,31 +93,34 @@ __global__ void __launch_bounds__(WAVE_BLOCK)
 k_cell_scatter(const u64* __restrict__ values, int format, CellList at, size_t n, u64* __restrict__ witness, u32* __restrict__ flags, u32 bit) {
     const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
     bool bad = false;
-    if (i < n) {
-        Fe<F> v = Fe<F>::zero();
-        if (format == KH_CELL_FIELD || format == KH_CELL_INT256) {
-            v = Fe<F>::load(values + 4 * i);
-            if (format == KH_CELL_INT256) {                         // v >= p: v - p does not borrow
-                u32 br = 0;
-#pragma unroll
-                for (int k = 0; k < 8; k++) br = (u32)(((u64)v.v[k] - Fe<F>::pw(k) - br) >> 63);
-                bad = br == 0;
-            }
-        } else if (format == KH_CELL_U64) {
-            const u64 w = values[i];
-            v.v[0] = (u32)w; v.v[1] = (u32)(w >> 32);
-        } else {
-            const ulonglong2 w = *(const ulonglong2*)(values + 2 * i);
-            bad = format == KH_CELL_LIMB88 && (w.y >> 24) != 0;
-            v.v[0] = (u32)w.x; v.v[1] = (u32)(w.x >> 32); v.v[2] = (u32)w.y; v.v[3] = (u32)(w.y >> 32);
-        }
-        if (format != KH_CELL_FIELD) v = to_mont<F>(v);
-        v.store(witness + at.offset(i));
-    }
+    if (i < n) bad = value_to_cell<F>(values + cell_words(format) * i, format, witness + at.offset(i));
     raise_cell_flag(flags, bit, bad);
 }
 
-struct GenericHalf { u64 l[4][4]; };                                // c_l c_r c_m c_c, each over -c_o
+// A group of a witness schedule's wire steps in one launch: lane i carries move i, whatever step it came from.  One 16-byte record per lane, one
+// load: row | column, format, flag bit | the dense side's word offset in the arena.  Format and flag bit are per lane: the lanes of a wave branch on
+// the format where a group changes it, and their flag masks are ORed across the wave into at most one atomicOr.
+template <class F, bool SCATTER>
+__global__ void __launch_bounds__(WAVE_BLOCK)
+k_cell_moves(const CellMove* __restrict__ moves, size_t n, u64* witness, size_t col_stride, u64* arena, u32* __restrict__ flags) {
+    const size_t i = (size_t)blockIdx.x * WAVE_BLOCK + threadIdx.x;
+    u32 mask = 0;
+    if (i < n) {
+        const uint4 m = ((const uint4*)moves)[i];
+        const int format = (int)((m.y >> 4) & 7u);
+        const u32 flag = (m.y >> 8) & 63u;
+        u64* const cell = witness + 4 * ((size_t)(m.y & 15u) * col_stride + m.x);
+        u64* const dense = arena + ((u64)m.z | ((u64)m.w << 32));
+        const bool bad = SCATTER ? value_to_cell<F>(dense, format, cell) : cell_to_value<F>(cell, format, dense);
+        if (bad && flag < 32) mask = 1u << flag;
+    }
+    if (flags && __any(mask != 0)) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mask |= (u32)__shfl_xor((int)mask, off);
+        if ((threadIdx.x & 63u) == 0) atomicOr(flags, mask);
+    }
+}
+
 template <class F>
 __global__ void __launch_bounds__(WAVE_BLOCK)
 k_generic_half(const u64* l_in, const u64* r_in, size_t n, GenericHalf co, unsigned col0, WitnessPlace at, u64* out) {
@@ -117,8 +151,17 @@ int cell_scatter(Context& C, int field, const uint64_t* values_dev, int format, 
     C.timer.mark("cell_scatter", C.stream);
     return KH_OK;
 }
-int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
-                 uint64_t* out_dev) {
+int cell_moves(Context& C, int field, bool scatter, const CellMove* moves_dev, size_t n, uint64_t* witness_dev, size_t col_stride, uint64_t* arena_dev,
+               uint32_t* flags_dev) {
+    C.timer.begin(C.stream);
+    if (scatter) KH_FIELD_LAUNCH(field, (k_cell_moves<F, true>), blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, moves_dev, n, (u64*)witness_dev, col_stride,
+                                 (u64*)arena_dev, flags_dev);
+    else KH_FIELD_LAUNCH(field, (k_cell_moves<F, false>), blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, moves_dev, n, (u64*)witness_dev, col_stride,
+                         (u64*)arena_dev, flags_dev);
+    C.timer.mark(scatter ? "cell_moves_scatter" : "cell_moves_gather", C.stream);
+    return KH_OK;
+}
+GenericHalf generic_fold(int field, const uint64_t* coeffs) {
     const khost::Fld F(field);
     khost::fe c[5];
     memcpy(c, coeffs, sizeof(c));                                   // l r o m c
@@ -129,11 +172,19 @@ int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const 
         const khost::fe folded[4] = {F.mul(c[0], scale), F.mul(c[1], scale), F.mul(c[3], scale), F.mul(c[4], scale)};
         memcpy(co.l, folded, sizeof(co.l));
     }
+    return co;
+}
+int generic_rows_prepared(Context& C, int field, const GenericHalf& co, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
+                          uint64_t* out_dev) {
     C.timer.begin(C.stream);
     KH_FIELD_LAUNCH(field, k_generic_half<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)l_dev, (const u64*)r_dev, n, co,
                     (unsigned)(3 * half), at, (u64*)out_dev);
     C.timer.mark("generic", C.stream);
     return KH_OK;
+}
+int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
+                 uint64_t* out_dev) {
+    return generic_rows_prepared(C, field, generic_fold(field, coeffs), half, l_dev, r_dev, n, at, out_dev);
 }
 
 }  // namespace kh

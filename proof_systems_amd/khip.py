@@ -858,6 +858,88 @@ def generic_witness_dev(field: int, coeffs, half: int, l, r, n: int, witness, co
                                        _ptr(out)))
 
 
+WitnessRefC, WitnessStepC = _STRUCTURES["kh_witness_ref_t"], _STRUCTURES["kh_witness_step_t"]
+REF_NONE, REF_ARENA, STEP_NO_FLAG = _CONSTANTS["KH_REF_NONE"], _CONSTANTS["KH_REF_ARENA"], _CONSTANTS["KH_STEP_NO_FLAG"]
+(STEP_GATHER, STEP_SCATTER, STEP_GENERIC, STEP_POSEIDON, STEP_COMPLETE_ADD, STEP_VARBASEMUL, STEP_ENDOMUL, STEP_ENDOMUL_SCALAR, STEP_RANGE_CHECK, STEP_XOR,
+ STEP_ROT64, STEP_FF_ADD, STEP_FF_MUL) = (_CONSTANTS["KH_STEP_" + _n] for _n in (
+     "GATHER", "SCATTER", "GENERIC", "POSEIDON", "COMPLETE_ADD", "VARBASEMUL", "ENDOMUL", "ENDOMUL_SCALAR", "RANGE_CHECK", "XOR", "ROT64", "FF_ADD", "FF_MUL"))
+_STEP_FIELDS = ("op", "n", "rows", "row0", "row_stride", "cells", "format", "param", "sign", "consts", "in", "out", "flag_bit")     # kh_witness_step_t's order
+
+
+def _witness_ref(ref):
+    """None -> absent; (buf, offset) with buf = REF_ARENA or the index of a bound buffer; a bare int is (buf, 0)"""
+    if ref is None:
+        return WitnessRefC(REF_NONE, 0)
+    return WitnessRefC(int(ref), 0) if isinstance(ref, (int, np.integer)) else WitnessRefC(int(ref[0]), int(ref[1]))
+
+
+class WitnessSchedule:
+    """kh_witness_schedule_*: a circuit's gadget and wire steps, validated and uploaded once (`create`), run per proof (`run`).  A step is a dict with
+    the fields of kh_witness_step_t (or a tuple in their order: op, n, rows, row0, row_stride, cells, format, param, sign, consts, in, out, flag_bit);
+    what a dict leaves out is 0 / None, n defaults to the number of cells, flag_bit to STEP_NO_FLAG.  in / out: lists of refs -- None, (REF_ARENA,
+    offset), (index of a bound buffer, offset).  consts: uint64 limbs as the direct call takes them, or the modulus as an int for the foreign-field steps."""
+
+    def __init__(self, handle, n_bufs: int, col_len: int):
+        self.handle, self.n_bufs, self.col_len = handle, n_bufs, col_len
+
+    @staticmethod
+    def pack(steps):
+        """(a kh_witness_step_t array of the steps, the host arrays it points to: to be kept until create has returned)"""
+        arr = (WitnessStepC * max(1, len(steps)))()
+        keep = []                                                  # the host arrays the structs point to, until create has copied them
+        for st, src in zip(arr, steps):
+            d = dict(zip(_STEP_FIELDS, src)) if isinstance(src, (tuple, list)) else dict(src)
+            unknown = set(d) - set(_STEP_FIELDS)
+            if unknown:
+                raise ValueError(f"step fields {sorted(unknown)} are not kh_witness_step_t's")
+            st.op = d["op"]
+            if d.get("cells") is not None:
+                c, st.cells = _cells32(d["cells"]); keep.append(c)
+                st.n = len(c)
+            if d.get("rows") is not None:
+                r, st.rows = _rows32(d["rows"]); keep.append(r)
+            if d.get("n") is not None:
+                st.n = d["n"]
+            st.row0, st.row_stride = d.get("row0") or 0, d.get("row_stride") or 0
+            st.format, st.param, st.sign = d.get("format") or 0, d.get("param") or 0, d.get("sign") or 0
+            consts = d.get("consts")
+            if consts is not None:
+                k = _modulus6(consts) if isinstance(consts, int) else _c64(consts).reshape(-1)
+                keep.append(k)
+                st.consts = _p64(k)
+            for name, count in (("in", 3), ("out", 2)):
+                refs = list(d.get(name) or ())
+                if len(refs) > count:
+                    raise ValueError(f"a step has {count} `{name}` refs at most")
+                setattr(st, name, (WitnessRefC * count)(*[_witness_ref(r) for r in refs + [None] * (count - len(refs))]))
+            st.flag_bit = STEP_NO_FLAG if d.get("flag_bit") is None else d["flag_bit"]
+        return arr, keep
+
+    @classmethod
+    def create(cls, field: int, col_len: int, steps, arena_bytes: int = 0, n_bufs: int = 0):
+        arr, _keep = cls.pack(steps)
+        h = C.c_void_p()
+        _check(_lib.kh_witness_schedule_create(field, col_len, arr, len(steps), arena_bytes, n_bufs, C.byref(h)))
+        return cls(h, n_bufs, col_len)
+
+    def run(self, bufs, witness, col_stride: int = None, flags=None):
+        """one proof's witness into the 15 columns at `witness` (col_stride: col_len unless given) from the bound buffers `bufs` (DevBufs, views or
+        addresses, as many as the schedule binds); flags: a DevBuf holding the run's flag word"""
+        ptrs = (C.c_void_p * max(1, len(bufs)))(*[b if isinstance(b, int) else b.ptr for b in bufs])
+        _check(_lib.kh_witness_schedule_run(self.handle, ptrs, len(bufs), _ptr(witness), self.col_len if col_stride is None else col_stride, _ptr(flags)))
+
+    def info(self):
+        """{"steps", "launch_groups", "resident_bytes", "run_bytes"}"""
+        v = [C.c_size_t() for _ in range(4)]
+        _check(_lib.kh_witness_schedule_info(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("steps", "launch_groups", "resident_bytes", "run_bytes"), (x.value for x in v)))
+
+    def free(self):
+        if self.handle:
+            _lib.kh_witness_schedule_free(self.handle)
+            self.handle = None
+
+
 class Comm:
     """kh_comm_*: the in-library RCCL communicator of the one-process-per-GPU deployment (no torch).  Comm.unique_id() on one rank, the bytes to
     the others, Comm(world, rank, id) on every rank."""
