@@ -193,6 +193,64 @@ __device__ __forceinline__ bool madd29(Acc29<F>& a, const Fe29<F>& px, const Fe2
     return true;
 }
 
+// v (limbs 0..7 normalised, v < 2^261) -> v - (h - 1) p with h = v >> 254: the same residue in (0, 2 p), normalised.  p = 2^254 + t
+// with t on five limbs, so the result is (v mod 2^254) + 2^254 + (1 - h) t: five signed 64-bit MADs (|1 - h| < 2^7 against 29-bit
+// limbs) and one signed carry sweep whose last borrow the 2^254 takes.  Limb model: tools/gen_field29_asm.py (Madd29Model.fold).
+template <class F>
+__device__ __forceinline__ Fe29<F> fold29(const Fe29<F>& a) {
+    typedef typename C29<F>::T K;
+    const int pl[5] = {1, (int)K::P1, (int)K::P2, (int)K::P3, (int)K::P4};
+    const int nh = 1 - (int)(a.v[8] >> 22);
+    Fe29<F> r;
+    long long c = 0;
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const long long t = (long long)nh * pl[i] + (long long)a.v[i] + c;
+        r.v[i] = (u32)t & MASK29; c = t >> 29;
+    }
+    int c32 = (int)c;
+#pragma unroll
+    for (int i = 5; i < 8; i++) {
+        const int t = (int)a.v[i] + c32;
+        r.v[i] = (u32)t & MASK29; c32 = t >> 29;
+    }
+    r.v[8] = (a.v[8] & 0x3fffffu) + (1u << 22) + (u32)c32;
+    return r;
+}
+
+// out = (x1, y1) + (x2, y2), the FIRST addition of a bucket: both points affine, both as 32 X, 32 Y (pack29<F, 5> of the canonical
+// coordinates, signs applied), so neither needs a to29 and ZZ3 = PP, ZZZ3 = PPP: 2 squarings + 2 products + one fused pair where
+// to29 x 2 + madd29 spends 2 + 6 products more.  P and R are differences of two values < 32 p (< 65 p with the 33 p that keeps them
+// positive) and are folded below 2 p before they are squared or multiplied; X1 and Y1 stay as they come, they only meet PP, PPP < 1.1 p
+// (32 * 1.1 p^2 < R' p).  Returns false -- out untouched -- when P = 0 (mod p) cannot be excluded (equal or opposite points): a folded
+// P lies in (0, 2 p), so that is P = p alone.  Result within the Acc29 bounds (x < 5.1 p, y < 1.4 p, zz, zzz < 1.1 p), so a madd29
+// behind it never meets zz in {0, p}.  Limb model and bounds: tools/gen_field29_asm.py (Madd29Model.aadd, check_aadd).
+template <class F>
+__device__ __forceinline__ bool aadd29(Acc29<F>& out, const Fe29<F>& x1, const Fe29<F>& y1, const Fe29<F>& x2, const Fe29<F>& y2) {
+    typedef typename C29<F>::T K;
+    Fe29<F> P, R;
+    KH29_SUBN(P, x2, x1, K::s331)
+    P = fold29<F>(P);
+    if (__builtin_expect(P.v[0] == 1u, 0) && is_kp29<F>(P, 1u)) return false;                      // P = p: same x
+    KH29_SUBN(R, y2, y1, K::s331)
+    R = fold29<F>(R);
+    const Fe29<F> PP = sqr29<F>(P);
+    const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(x1, PP), RR = sqr29<F>(R);
+    Fe29<F> sub, rx, t, yn;
+#pragma unroll
+    for (int i = 0; i < 9; i++) sub.v[i] = PPP.v[i] + 2u * Q.v[i];
+    KH29_SUBN(rx, RR, sub, K::s44)
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.v[i] = Q.v[i] + K::s61(i) - rx.v[i];          // not normalised: limbs < 2^29 + 2^30
+#pragma unroll
+    for (int i = 0; i < 9; i++) yn.v[i] = K::s331(i) - y1.v[i];                   // 33 p - 32 Y1, not normalised: limbs < 2^30
+    out.y = muladd29<F>(R, t, yn, PPP);                                         // R (Q - X3) - Y1 PPP, one reduction, < 1.4 p
+    out.x = rx;
+    out.zz = PP;
+    out.zzz = PPP;
+    return true;
+}
+
 // a += b, both lazy XYZZ points with the bounds of Acc29 (the full addition add-2008-s, 12M + 2S as 10 products + 2 squarings + one fused
 // product pair; limb model: tools/gen_field29_asm.py Madd29Model.add).  Neither operand may be the identity (the callers skip all-zero
 // records; a lazy point that went through madd29 / add29 never is one).  Returns false -- a untouched -- when P = U2 - U1 = 0 (mod p)

@@ -1037,13 +1037,23 @@ k_accumulate29(const u32* __restrict__ entries, const u32* __restrict__ off, con
     if (e >> 31) p.y = neg<BF>(p.y);
     typedef typename C29<BF>::T K29;
     Acc29<BF> acc;
-    acc.x = to29<BF>(p.x); acc.y = to29<BF>(p.y);
-#pragma unroll
-    for (int i = 0; i < 9; i++) { acc.zz.v[i] = K29::one(i); acc.zzz.v[i] = K29::one(i); }
     bool ok = true;
+    u32 k = start + 1;
+    if (k < end) {          // two entries or more: open with the affine + affine addition (aadd29); refused, the task is redone exactly below
+        const Fe29<BF> x1 = pack29<BF, 5>(p.x), y1 = pack29<BF, 5>(p.y);
+        e = entries[k];
+        p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
+        if (e >> 31) p.y = neg<BF>(p.y);
+        ok = aadd29<BF>(acc, x1, y1, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));
+        k = ok ? k + 1 : end;
+    } else {
+        acc.x = to29<BF>(p.x); acc.y = to29<BF>(p.y);
+#pragma unroll
+        for (int i = 0; i < 9; i++) { acc.zz.v[i] = K29::one(i); acc.zzz.v[i] = K29::one(i); }
+    }
     // (issuing the next point's gather before the current addition -- 109 VGPRs -- and sizing the tasks for 5 waves per SIMD
     //  were both measured: no gain, four waves already hide the gather)
-    for (u32 k = start + 1; k < end; k++) {
+    for (; k < end; k++) {
         e = entries[k];
         p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
         if (e >> 31) p.y = neg<BF>(p.y);
@@ -1089,17 +1099,31 @@ __device__ __forceinline__ bool wide_task29(u32 key, u32 jt, const u32* __restri
     const u32 o0 = off[key], cnt = off[key + 1] - o0;
     if (cnt == 0) return true;
     const u32 t0 = toff[key], nt = toff[key + 1] - t0;
-    const u32 start = o0 + (u32)(((u64)jt * cnt) / nt), end = o0 + (u32)(((u64)(jt + 1) * cnt) / nt);
+    // (an unsplit bucket -- every bucket of unskewed scalars -- is its own only task: no divisions by the task count)
+    u32 start = o0, end = o0 + cnt;
+    if (nt != 1) { start = o0 + (u32)(((u64)jt * cnt) / nt); end = o0 + (u32)(((u64)(jt + 1) * cnt) / nt); }
     u32 e = entries[start];
     Aff<BF> p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
     if (e >> 31) p.y = neg<BF>(p.y);
     typedef typename C29<BF>::T K29;
     Acc29<BF> acc;
-    acc.x = to29<BF>(p.x); acc.y = to29<BF>(p.y);
-#pragma unroll
-    for (int i = 0; i < 9; i++) { acc.zz.v[i] = K29::one(i); acc.zzz.v[i] = K29::one(i); }
     bool ok = true;
-    for (u32 k = start + 1; k < end; k++) {
+    u32 k = start + 1;
+    if (k < end) {
+        // two entries or more: the first addition is affine + affine (aadd29: 6 products fewer than to29 x 2 + madd29); refused, the
+        // task goes the way of a refused madd29
+        const Fe29<BF> x1 = pack29<BF, 5>(p.x), y1 = pack29<BF, 5>(p.y);
+        e = entries[k];
+        p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
+        if (e >> 31) p.y = neg<BF>(p.y);
+        ok = aadd29<BF>(acc, x1, y1, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));
+        k = ok ? k + 1 : end;
+    } else {
+        acc.x = to29<BF>(p.x); acc.y = to29<BF>(p.y);
+#pragma unroll
+        for (int i = 0; i < 9; i++) { acc.zz.v[i] = K29::one(i); acc.zzz.v[i] = K29::one(i); }
+    }
+    for (; k < end; k++) {
         e = entries[k];
         p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
         if (e >> 31) p.y = neg<BF>(p.y);

@@ -239,7 +239,8 @@ def check(p, name, trials=300):
 # Subtraction a - b + K p on limbs without borrows: add the limbs of K p "spread" so that every limb dominates the
 # subtrahend's: C_0 = d_0 + J 2^29, C_i = d_i + J 2^29 - J (0 < i < 8), C_8 = d_8 - J  (d = limbs of K p; sum C_i 2^(29 i) = K p).
 # Valid when b_i <= J MASK for i < 8 and b_8 <= d_8 - J.
-SPREADS = [(7, 1), (5, 1), (4, 4), (6, 1)]        # (K, J) pairs used by madd29 (field29.cuh)
+SPREADS = [(7, 1), (5, 1), (4, 4), (6, 1),        # (K, J) pairs used by madd29 (field29.cuh)
+           (33, 1)]                                  # aadd29: both operands are 32 X < 32 p, top limb <= (32 p)_8 = (33 p)_8 - 2^22
 
 
 def spread(p, K, J):
@@ -326,6 +327,42 @@ class Madd29Model:
         yn = [self.u32(c["S51"][i] - y[i]) for i in range(9)]                            # 5p - y, not normalised
         ry = self.muladd(R, t, yn, PPP)                                                  # R (Q - rx) - y PPP with ONE reduction
         return (rx, ry, self.mul(zz, PP), self.mul(zzz, PPP))
+
+    def fold(self, v):
+        """fold29: v (limbs 0..7 normalised, v < 2^261) -> v - (h - 1) p with h = v >> 254, the same residue in (0, 2 p), normalised.
+        p = 2^254 + t with t on five limbs, so v - (h - 1) p = (v mod 2^254) + 2^254 + (1 - h) t: five signed 64-bit MADs and one
+        (signed) carry sweep; the 2^254 takes the last borrow."""
+        pl = self.pl
+        assert all(0 <= x <= MASK for x in v[:8]) and 0 <= v[8] < (1 << 29)
+        nh = 1 - (v[8] >> 22)
+        r, c = [], 0
+        for i in range(5):
+            t = nh * pl[i] + v[i] + c
+            assert -(1 << 63) <= t < (1 << 63)
+            r.append(t & MASK); c = t >> 29
+        assert -(1 << 31) <= c < (1 << 31)
+        for i in range(5, 8):
+            t = v[i] + c
+            assert -(1 << 31) <= t < (1 << 31)
+            r.append(t & MASK); c = t >> 29
+        r.append(self.u32((v[8] & ((1 << 22) - 1)) + (1 << 22) + c))
+        return r
+
+    def aadd(self, px1, py1, px2, py2):
+        """aadd29: the first addition of a bucket, affine + affine, both points as 32 X, 32 Y (normalised, < 32 p).  None when
+        P = X2 - X1 = 0 (mod p) cannot be excluded: after the fold P lies in (0, 2 p), so P = p is the only such value."""
+        c = self.c
+        P = self.fold(self.subn(px2, px1, c["S331"]))
+        if P[0] == 1 and P == self.pl:
+            return None
+        R = self.fold(self.subn(py2, py1, c["S331"]))
+        PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(px1, PP); RR = self.sqr(R)
+        sub = [self.u32(PPP[i] + 2 * Q[i]) for i in range(9)]
+        rx = self.subn(RR, sub, c["S44"])
+        t = [self.u32(self.u32(Q[i] + c["S61"][i]) - rx[i]) for i in range(9)]          # not normalised: limbs < 2^29 + 2^30
+        yn = [self.u32(c["S331"][i] - py1[i]) for i in range(9)]                         # 33 p - 32 Y1, not normalised: limbs < 2^30
+        ry = self.muladd(R, t, yn, PPP)                                                  # R (Q - rx) - Y1 PPP with ONE reduction
+        return (rx, ry, PP, PPP)
 
     def add(self, A, B):
         """Full XYZZ addition of two lazy points (add29, field29.cuh): both operands as madd leaves an accumulator (x < 6p, y < 4p, zz, zzz < 2p,
@@ -474,6 +511,68 @@ def check_add(p, name, trees=6, leaves=24):
     print(f"{name}: add29 limb model OK over {trees} trees of {leaves} leaves; max value / p = " + ", ".join(f"{m:.2f}" for m in maxv))
 
 
+def check_aadd(p, name, trials=60, length=6):
+    """aadd29 through the limb model: random openings (all four sign combinations) against affine big-integer arithmetic, each carried
+    on through a short madd chain; the fold over its whole input range (0, 65 p); the refusal of equal x.
+    Spread constant of the two differences and of 33 p - 32 Y1: (K, J) = (33, 1); of X3: (4, 4); of Q - X3: (6, 1)."""
+    rnd = random.Random(13)
+    M = Madd29Model(p)
+    R, R29inv = 1 << 256, pow(1 << 261, -1, p)
+
+    def sqrt(a):
+        q, s = p - 1, 0
+        while q % 2 == 0: q //= 2; s += 1
+        z = 5
+        while pow(z, (p - 1) // 2, p) != p - 1: z += 1
+        m_, c_, t_, r_ = s, pow(z, q, p), pow(a, q, p), pow(a, (q + 1) // 2, p)
+        while t_ != 1:
+            i, tt = 0, t_
+            while tt != 1: tt = tt * tt % p; i += 1
+            bb = pow(c_, 1 << (m_ - i - 1), p); m_, c_ = i, bb * bb % p; t_, r_ = t_ * c_ % p, r_ * bb % p
+        return r_
+
+    def rand_point():
+        while True:
+            x = rnd.randrange(p); y2 = (x * x * x + 5) % p
+            if pow(y2, (p - 1) // 2, p) == 1:
+                y = sqrt(y2)
+                return x, (p - y if rnd.random() < 0.5 else y)
+
+    def aff_add(A, B):
+        (x1, y1), (x2, y2) = A, B
+        lam = (y2 - y1) * pow(x2 - x1, -1, p) % p
+        x3 = (lam * lam - x1 - x2) % p
+        return x3, (lam * (x1 - x3) - y1) % p
+
+    wire = lambda A: (limbs29((A[0] * R % p) << 5), limbs29((A[1] * R % p) << 5))
+    # the fold: every residue class at both ends of its input range, and every k p it can meet
+    for k in range(1, 66):
+        assert M.fold(limbs29(k * p)) == M.pl, "fold29: k p must come out as p"
+    for v in [1, p - 1, p + 1, (1 << 254) - 1, 1 << 254, 65 * p - 1, 64 * p + 1] + [rnd.randrange(1, 65 * p) for _ in range(200)]:
+        f = val29(M.fold(limbs29(v)))
+        assert 0 < f < 2 * p and f % p == v % p and all(x <= MASK for x in M.fold(limbs29(v))[:8])
+    maxv = [0, 0, 0, 0]
+    for _ in range(trials):
+        A, B = rand_point(), rand_point()
+        acc = M.aadd(*wire(A), *wire(B))
+        assert acc is not None, "filter fired on random points"
+        A = aff_add(A, B)
+        for step in range(length + 1):
+            vals = [val29(v) for v in acc]
+            maxv = [max(m, v / p) for m, v in zip(maxv, vals)]
+            assert vals[0] < 6 * p and vals[1] < 4 * p and vals[2] < 2 * p and vals[3] < 2 * p
+            assert all(l <= MASK for v in acc for l in v[:8])
+            xs, ys, zzs, zzzs = [v * R29inv % p for v in vals]
+            assert xs * pow(zzs, -1, p) % p == A[0] and ys * pow(zzzs, -1, p) % p == A[1], f"{name}: aadd29 model mismatch"
+            if step < length:
+                B = rand_point()
+                acc = M.madd(acc, *wire(B)); A = aff_add(A, B)
+                assert acc is not None
+    A = rand_point()
+    assert M.aadd(*wire(A), *wire(A)) is None and M.aadd(*wire(A), *wire((A[0], p - A[1]))) is None
+    print(f"{name}: aadd29 limb model OK over {trials} openings + {length} additions each; max value / p = " + ", ".join(f"{m:.2f}" for m in maxv))
+
+
 # ------------------------------------------------------------------------------------------- directed operands
 # The 29-bit streams have no carry chain: a v_mad_u64_u32 is their only VCC writer and nothing reads VCC, so every carry site is
 # unreachable by the accumulator bound that simulate() asserts (A + B <= 60.7, see the header).  What a uniform operand meets with
@@ -617,6 +716,7 @@ def main():
         check(P_FP, "Fp"); check(P_FQ, "Fq")
         check_madd(P_FP, "Fp"); check_madd(P_FQ, "Fq")
         check_add(P_FP, "Fp"); check_add(P_FQ, "Fq")
+        check_aadd(P_FP, "Fp"); check_aadd(P_FQ, "Fq")
     text = render()
     if not os.path.exists(INC_PATH) or open(INC_PATH).read() != text:      # leave the mtime alone when nothing changed
         open(INC_PATH, "w").write(text)
