@@ -1,5 +1,5 @@
 // api_internal.hpp -- what crosses a file boundary between the translation units of the extern "C" boundary (context.hip, srs.cpp, msm_api.cpp,
-// opening.cpp, vector_api.cpp, witness_schedule.cpp, debug_api.cpp).  State stays private to the file that owns it: only types and functions are declared here.
+// opening.cpp, vector_api.cpp, witness_steps.cpp, witness_schedule.cpp, debug_api.cpp).  State stays private to the file that owns it: only types and functions are declared here.
 #pragma once
 #include <atomic>
 #include <map>
@@ -92,7 +92,7 @@ struct PoolBlock {
 };
 // Where instance i of a gadget lands in the 15 witness columns (kh_poseidon_gate_witness_dev and the curve gates' kh_*_witness_dev): it starts at row
 // rows[i], or row0 + i row_stride when rows is null; column c of the witness starts at witness + 4 c col_stride.  The entry points validate it against
-// col_len (place_validate below) and hand it on with `rows` on the device; the kernels take it by value.
+// col_len (place_validate in witness_steps.cpp) and hand it on with `rows` on the device; the kernels take it by value.
 struct WitnessPlace {
     const uint32_t* rows;
     size_t row0, row_stride;
@@ -134,22 +134,17 @@ int xor_rows(Context& C, int field, const uint64_t* in1_dev, const uint64_t* in2
 int rot64_rows(Context& C, int field, const uint64_t* words_dev, unsigned rot, size_t n, const WitnessPlace& at, uint64_t* out_dev);
 int ff_add_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* left_dev, const uint64_t* right_dev, int sign, size_t n, const WitnessPlace& at,
                 uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
-int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
-                uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit);
 void ff_negated_modulus(const uint64_t* modulus, uint64_t* nf_out);
 // wiring.hip: the launchers of kh_witness_gather_dev, kh_witness_scatter_dev and kh_generic_witness_dev, queued on C.stream (arguments validated by the
 // entry points; n >= 1; cells_dev: n (row, column) pairs on the device, every one inside the columns; format: a KH_CELL_* value; coeffs: the half's five
-// coefficients l r o m c on the host, Montgomery -- generic_rows divides by -c_o there, once per call; half: 0 or 1)
+// coefficients l r o m c on the host, Montgomery -- generic_fold divides by -c_o there; half: 0 or 1)
 int cell_gather(Context& C, int field, const uint64_t* witness_dev, size_t col_stride, const uint32_t* cells_dev, size_t n, int format, uint64_t* out_dev,
                 uint32_t* flags_dev, unsigned bit);
 int cell_scatter(Context& C, int field, const uint64_t* values_dev, int format, const uint32_t* cells_dev, size_t n, uint64_t* witness_dev, size_t col_stride,
                  uint32_t* flags_dev, unsigned bit);
-int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
-                 uint64_t* out_dev);
-// What the launchers of kh_generic_witness_dev and kh_foreign_field_mul_witness_dev compute on the host per call, as a step of its own: a witness
-// schedule (witness_schedule.cpp) takes it once, at create, and launches through the *_prepared halves; the per-call launchers above are
-// prepare + *_prepared.  GenericHalf: c_l c_r c_m c_c, each over -c_o (all zero when c_o = 0).  FfMulConst: the modulus with its Barrett constant
-// (limb_gadgets.hip owns the layout).
+// What kh_generic_witness_dev and kh_foreign_field_mul_witness_dev compute on the host, as a step of its own in front of the launch (StepPrepared
+// below).  GenericHalf: c_l c_r c_m c_c, each over -c_o (all zero when c_o = 0).  FfMulConst: the modulus with its Barrett constant (limb_gadgets.hip
+// owns the layout).
 struct GenericHalf { uint64_t l[4][4]; };
 GenericHalf generic_fold(int field, const uint64_t* coeffs);
 int generic_rows_prepared(Context& C, int field, const GenericHalf& co, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
@@ -168,9 +163,6 @@ inline CellMove cell_move(uint32_t row, uint32_t col, int format, uint32_t flag,
 int cell_moves(Context& C, int field, bool scatter, const CellMove* moves_dev, size_t n, uint64_t* witness_dev, size_t col_stride, uint64_t* arena_dev,
                uint32_t* flags_dev);
 
-// ------------------------------------------------------------------ what the entry points of the gadget and wire calls refuse (vector_api.cpp), shared
-// with kh_witness_schedule_create (witness_schedule.cpp), which validates a step through the function its direct call uses: `call` names the call, or
-// the step.
 // How a vector step is queued on the main stream: under the context's lock, and when run(C) has queued it, the point is marked that a later MSM on
 // another slot's stream waits for.  The entry points check their arguments in front of this.
 template <class Run>
@@ -182,6 +174,17 @@ int queue_step(Run run) {
     if (rc == KH_OK) C.mark_async();
     return rc;
 }
+// `words` uint32_t of a host table (start rows, cells, a schedule's resident block) into dst_dev, through the pinned staging ring in pieces that leave
+// the ring its size: the caller's array is not read after this returns
+inline int stage_words(Context& C, uint32_t* dst_dev, const uint32_t* src, size_t words) {
+    const size_t piece = (size_t)1 << 15;
+    counter(CNT_TABLE_STAGED_WORDS) += words;
+    for (size_t i = 0; i < words; i += piece) {
+        const int up = C.stage_upload(dst_dev + i, {{src + i, std::min(piece, words - i) * sizeof(uint32_t)}});
+        if (up) return up;
+    }
+    return KH_OK;
+}
 // what the 15 witness columns of a call that takes n instances (or cells) are refused for: a null or misaligned witness, columns that overlap or whose
 // byte count overflows
 inline int columns_validate(const char* call, const void* witness, size_t col_stride, size_t col_len, size_t n) {
@@ -192,130 +195,39 @@ inline int columns_validate(const char* call, const void* witness, size_t col_st
                col_stride);
     return KH_OK;
 }
-// what a placement (WitnessPlace, rows still on the host) is refused for: its columns, instances of inst_rows rows that do not fit col_len rows
-inline int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t col_len, size_t inst_rows) {
-    int rc = columns_validate(call, at.witness, at.col_stride, col_len, n);
-    if (rc) return rc;
-    if (n > 0 && at.rows) {
-        for (size_t i = 0; i < n; i++)
-            KH_REQUIRE(col_len >= inst_rows && at.rows[i] <= col_len - inst_rows, "%s: instance %zu at row %u does not fit %zu rows (%zu rows each)", call, i,
-                       at.rows[i], col_len, inst_rows);
-    } else if (n > 0) {
-        KH_REQUIRE(at.row_stride >= inst_rows, "%s: row_stride %zu is less than the %zu rows of an instance", call, at.row_stride, inst_rows);
-        KH_REQUIRE(col_len >= inst_rows && at.row0 <= col_len - inst_rows && (n - 1) <= (col_len - inst_rows - at.row0) / at.row_stride,
-                   "%s: %zu instances from row %zu, %zu rows apart, do not fit %zu rows", call, n, at.row0, at.row_stride, col_len);
-    }
-    return KH_OK;
-}
-struct GadgetPtr { const char* name; const void* p; bool required; unsigned align = 16; };
-// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
-inline int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
-    for (const GadgetPtr& a : ptrs) {
-        KH_REQUIRE(a.p || !a.required || n == 0, "%s: null %s", call, a.name);
-        KH_REQUIRE((((uintptr_t)a.p) & (a.align - 1)) == 0, "%s: %s must be %u-byte aligned", call, a.name, a.align);
-    }
-    return place_validate(call, at, n, col_len, inst_rows);
-}
-// what the five limb gadgets refuse alike after their own arguments: gadget_validate's list, more lanes (one per instance and row) than a grid takes, a
-// flag word that is misaligned or a bit that is not one
-inline int limb_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n, const WitnessPlace& at, size_t col_len, size_t inst_rows,
-                         const uint32_t* flags_dev = nullptr, unsigned bit = 0) {
-    int rc = gadget_validate(call, field, ptrs, n, at, col_len, inst_rows);
-    if (rc) return rc;
-    KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / inst_rows, "%s: %zu instances of %zu rows overflow the byte count", call, n, inst_rows);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
-    return KH_OK;
-}
-// a foreign modulus: three limbs of two u64 on the host, each < 2^88, not all zero
-inline int modulus_validate(const char* call, const uint64_t* modulus, size_t n) {
-    KH_REQUIRE(modulus || n == 0, "%s: null modulus", call);
-    if (!modulus) return KH_OK;
-    KH_REQUIRE((modulus[1] | modulus[3] | modulus[5]) >> 24 == 0, "%s: a modulus limb is 2^88 or more", call);
-    KH_REQUIRE((modulus[0] | modulus[1] | modulus[2] | modulus[3] | modulus[4] | modulus[5]) != 0, "%s: the modulus is zero", call);
-    return KH_OK;
-}
-// what the two cell calls refuse alike: the field and the format, their columns, the dense buffer (`data`: out_dev / values_dev, aligned to its
-// format's access), the flag word, a cell outside the 15 columns of col_len rows
-inline int cells_validate(const char* call, int field, int format, const void* witness, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n,
-                          const char* data_name, const void* data, const uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
-    KH_REQUIRE(format >= KH_CELL_FIELD && format <= KH_CELL_U64, "%s: unknown cell format %d", call, format);
-    int rc = columns_validate(call, witness, col_stride, col_len, n);
-    if (rc) return rc;
-    const unsigned align = format == KH_CELL_U64 ? 8 : 16;
-    KH_REQUIRE((cells && data) || n == 0, "%s: null %s", call, cells ? data_name : "cells");
-    KH_REQUIRE((((uintptr_t)data) & (align - 1)) == 0, "%s: %s must be %u-byte aligned", call, data_name, align);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (const void*)flags_dev);
-    for (size_t i = 0; i < n; i++)
-        KH_REQUIRE(cells[2 * i] < col_len && cells[2 * i + 1] < 15, "%s: cell %zu at (row %u, column %u) is outside the 15 columns of %zu rows", call, i, cells[2 * i],
-                   cells[2 * i + 1], col_len);
-    return KH_OK;
-}
-// ... and each gadget call's own list, in the order the call has always checked it
-inline int poseidon_gate_validate(const char* call, int field, const void* states_dev, size_t n, const WitnessPlace& at, size_t col_len, const void* out_states_dev) {
-    return gadget_validate(call, field, {{"states_dev", states_dev, true}, {"out_states_dev", out_states_dev, false}}, n, at, col_len, 12);
-}
-inline int complete_add_validate(const char* call, int field, const void* p1_dev, const void* p2_dev, size_t n, const WitnessPlace& at, size_t col_len,
-                                 const void* out_dev) {
-    return gadget_validate(call, field, {{"p1_dev", p1_dev, true}, {"p2_dev", p2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
-}
-inline int endomul_scalar_validate(const char* call, int field, const void* chals_dev, unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len,
-                                   const uint64_t* endo_scalar, const void* out_dev) {
-    KH_REQUIRE(num_bits >= 16 && num_bits <= 128 && num_bits % 16 == 0, "%s: num_bits %u is not a multiple of 16 from 16 to 128", call, num_bits);
-    int rc = gadget_validate(call, field, {{"chals_dev", chals_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, num_bits / 16);
-    if (rc) return rc;
-    KH_REQUIRE(endo_scalar || !out_dev || n == 0, "%s: null endo_scalar with an out_dev", call);
-    return KH_OK;
-}
-// VarBaseMul (endo == nullptr, scalars of 4 limbs) and EndoMul (challenges of 2 limbs) share everything but their row counts
-inline int chain_validate(const char* call, int field, bool is_endo, const uint64_t* endo, const void* base_dev, const void* acc0_dev, const void* scalars_dev,
-                          unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len, const void* out_acc_dev, const void* out_n_dev,
-                          const uint32_t* flags_dev, unsigned bit) {
-    if (is_endo) KH_REQUIRE(num_bits >= 4 && num_bits <= 128 && num_bits % 4 == 0, "%s: num_bits %u is not a multiple of 4 from 4 to 128", call, num_bits);
-    else KH_REQUIRE(num_bits >= 5 && num_bits <= 255 && num_bits % 5 == 0, "%s: num_bits %u is not a multiple of 5 from 5 to 255", call, num_bits);
-    int rc = gadget_validate(call, field, {{"base_dev", base_dev, true}, {"acc0_dev", acc0_dev, true}, {is_endo ? "chals_dev" : "scalars_dev", scalars_dev, true},
-                             {"out_acc_dev", out_acc_dev, false}, {"out_n_dev", out_n_dev, false}},
-                             n, at, col_len, is_endo ? num_bits / 4 + 1 : 2 * num_bits / 5);
-    if (rc) return rc;
-    KH_REQUIRE(!is_endo || endo || n == 0, "%s: null endo", call);
-    KH_REQUIRE(bit < 32 && (((uintptr_t)flags_dev) & 3) == 0, "%s: flag bit %u of a word at %p", call, bit, (void*)flags_dev);
-    return KH_OK;
-}
-inline int range_check_validate(const char* call, int field, const void* limbs_dev, size_t n, int compact, const WitnessPlace& at, size_t col_len,
-                                const uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(compact == 0 || compact == 1, "%s: compact is %d, not 0 or 1", call, compact);
-    return limb_validate(call, field, {{"limbs_dev", limbs_dev, true}}, n, at, col_len, 4, flags_dev, bit);
-}
-inline int xor_validate(const char* call, int field, const void* in1_dev, const void* in2_dev, unsigned bits, size_t n, const WitnessPlace& at, size_t col_len,
-                        const void* out_dev, const uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(bits >= 1 && bits <= 254, "%s: bits %u is not from 1 to 254", call, bits);
-    return limb_validate(call, field, {{"in1_dev", in1_dev, true}, {"in2_dev", in2_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, (bits + 15) / 16 + 1,
-                         flags_dev, bit);
-}
-inline int rot64_validate(const char* call, int field, const void* words_dev, unsigned rot, size_t n, const WitnessPlace& at, size_t col_len, const void* out_dev) {
-    KH_REQUIRE(rot <= 63, "%s: rot %u is not from 0 to 63", call, rot);
-    return limb_validate(call, field, {{"words_dev", words_dev, true, 8}, {"out_dev", out_dev, false, 8}}, n, at, col_len, 3);
-}
-inline int ff_add_validate(const char* call, int field, const uint64_t* modulus, const void* left_dev, const void* right_dev, int sign, size_t n,
-                           const WitnessPlace& at, size_t col_len, const void* out_dev, const uint32_t* flags_dev, unsigned bit) {
-    KH_REQUIRE(sign == 1 || sign == -1, "%s: sign is %d, not +1 or -1", call, sign);
-    int rc = modulus_validate(call, modulus, n);
-    if (rc) return rc;
-    return limb_validate(call, field, {{"left_dev", left_dev, true}, {"right_dev", right_dev, true}, {"out_dev", out_dev, false}}, n, at, col_len, 2, flags_dev, bit);
-}
-inline int ff_mul_validate(const char* call, int field, const uint64_t* modulus, const void* a_dev, const void* b_dev, size_t n, const WitnessPlace& at,
-                           size_t col_len, const void* out_checks_dev, const uint32_t* flags_dev, unsigned bit) {
-    int rc = modulus_validate(call, modulus, n);
-    if (rc) return rc;
-    return limb_validate(call, field, {{"a_dev", a_dev, true}, {"b_dev", b_dev, true}, {"out_checks_dev", out_checks_dev, false}}, n, at, col_len, 2, flags_dev, bit);
-}
-inline int generic_validate(const char* call, int field, const uint64_t* coeffs, int half, const void* l_dev, const void* r_dev, size_t n, const WitnessPlace& at,
-                            size_t col_len, const void* out_dev) {
-    KH_REQUIRE(half == 0 || half == 1, "%s: half is %d, not 0 or 1", call, half);
-    int rc = gadget_validate(call, field, {{"l_dev", l_dev, true}, {"r_dev", r_dev, false}, {"out_dev", out_dev, false}}, n, at, col_len, 1);
-    if (rc) return rc;
-    KH_REQUIRE(coeffs || n == 0, "%s: null coeffs", call);
-    return KH_OK;
-}
+
+// ------------------------------------------------------------------ one gadget or wire step with its arguments resolved (witness_steps.cpp): what a
+// direct call (kh_*_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev) builds from its arguments and a witness schedule
+// (witness_schedule.cpp) from a kh_witness_step_t.  Which argument of which call sits in in[] / out[] / param / consts is the table above KH_STEP_* in
+// include/kimchi_hip.h.  at.rows and cells are on the host while validating and on the device when launching; consts stays on the host.
+struct StepArgs {
+    int op;                                   // KH_STEP_*
+    size_t n;
+    WitnessPlace at;                          // the wire steps use its witness and col_stride alone
+    const void* in[3];
+    void* out[2];
+    unsigned param;
+    const uint64_t* consts;
+    uint32_t* flags; unsigned bit;            // (calls without a flag leave them 0)
+    int sign;
+    const uint32_t* cells; int format;
+};
+struct OpInfo {
+    const char* name;
+    int n_in, n_out;
+    unsigned in_bytes[3], out_bytes[2];       // per instance; 0: the cell format decides (GATHER / SCATTER)
+    bool tabled_cells;                        // the table is `cells` (2 n words), not `at.rows` (n words)
+    int n_consts;                             // uint64_t words behind `consts`
+};
+const OpInfo* step_op(int op);                // null: no such op
+// What a step computes on the host before it can be launched: a generic half's c_l c_r c_m c_c over -c_o (all zero when c_o = 0), ForeignFieldMul's
+// modulus with its Barrett constant.  A direct call takes it per call, a schedule once, at create.
+struct StepPrepared { GenericHalf generic; std::shared_ptr<const FfMulConst> ff_mul; };
+// step_validate: everything the step's direct call refuses, in that call's order and words; `call` names the call, or the schedule's step.
+// step_prepare: for n >= 1 (at n = 0 coeffs / modulus may be null).  step_scratch_bytes: what VarBaseMul / EndoMul need from the kh_dev_alloc pool
+// at the current slice knob, 0 for every other step and at n = 0.  step_launch: queued on C.stream, n >= 1.
+int step_validate(const char* call, int field, size_t col_len, const StepArgs& a);
+StepPrepared step_prepare(int field, const StepArgs& a);
+size_t step_scratch_bytes(const StepArgs& a);
+int step_launch(Context& C, int field, const StepArgs& a, const StepPrepared& prepared, uint64_t* scratch_dev, size_t scratch_bytes);
 }  // namespace kh

@@ -1,6 +1,6 @@
 // curve_gadgets.hip -- the witness rows of the curve gates on the device: CompleteAdd, VarBaseMul, EndoMul, EndoMulScalar
 // (kimchi/src/circuits/polynomials/{complete_add,varbasemul,endosclmul,endomul_scalar}.rs; oracle/gates.py restates their generators), for
-// kh_complete_add_witness_dev, kh_varbasemul_witness_dev, kh_endomul_witness_dev and kh_endomul_scalar_witness_dev (csrc/vector_api.cpp).
+// kh_complete_add_witness_dev, kh_varbasemul_witness_dev, kh_endomul_witness_dev and kh_endomul_scalar_witness_dev (csrc/witness_steps.cpp).
 //
 //   k_complete_add        one lane per instance, ONE Fermat inversion: the two denominators a row may need are inverted as their product
 //   k_endomul_scalar      one lane per instance, additions only
@@ -305,7 +305,7 @@ k_endomul_cells(ChainScratch S, const u64* __restrict__ base, const u64* __restr
     if (flags && __any(degenerate) && (threadIdx.x & 63u) == 0) atomicOr(flags, 1u << bit);
 }
 
-// (the callers in vector_api.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grids inside 31 bits; the phases of kh_last_timings
+// (the callers in witness_steps.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grids inside 31 bits; the phases of kh_last_timings
 // are complete_add, endomul_scalar and, per slice, chain, denominators, cells)
 int complete_add_rows(Context& C, int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const WitnessPlace& at, uint64_t* out_dev) {
     C.timer.begin(C.stream);

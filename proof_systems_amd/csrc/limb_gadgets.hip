@@ -1,7 +1,7 @@
 // limb_gadgets.hip -- the witness rows of the optional gates on the device: RangeCheck0 / RangeCheck1 (the multi-range-check), Xor16, Rot64,
 // ForeignFieldAdd and ForeignFieldMul (kimchi/src/circuits/polynomials/{range_check,xor,rot,foreign_field_add,foreign_field_mul}; oracle/gates.py restates
 // their constraints), for kh_range_check_witness_dev, kh_xor_witness_dev, kh_rot64_witness_dev, kh_foreign_field_add_witness_dev and
-// kh_foreign_field_mul_witness_dev (csrc/vector_api.cpp).  include/kimchi_hip.h has the cell tables.
+// kh_foreign_field_mul_witness_dev (csrc/witness_steps.cpp).  include/kimchi_hip.h has the cell tables.
 //
 // Every kernel is ONE LANE PER (instance, row) in blocks of one wave: the witness is column-major, so with instances packed densely the 64 lanes of a
 // wave store 64 consecutive rows of a column, 2 KiB in a row, fifteen times.  (One lane per instance would store four rows of each column 128 bytes
@@ -286,7 +286,7 @@ k_ff_mul(const u64* __restrict__ a_in, const u64* __restrict__ b_in, size_t n, l
     raise_flag(flags, bit, bad);
 }
 
-// (the callers in vector_api.cpp have validated pointers and sizes: at most WAVE_BLOCK_MAX_N lanes per call keeps the grids inside 31 bits; one phase
+// (the callers in witness_steps.cpp have validated pointers and sizes: at most WAVE_BLOCK_MAX_N lanes per call keeps the grids inside 31 bits; one phase
 // of kh_last_timings per call, under the gate's name)
 int range_check_rows(Context& C, int field, const uint64_t* limbs_dev, size_t n, int compact, const WitnessPlace& at, uint32_t* flags_dev, unsigned bit) {
     C.timer.begin(C.stream);
@@ -335,11 +335,6 @@ int ff_mul_rows_prepared(Context& C, int field, const FfMulConst& m, const uint6
                     (u64*)out_checks_dev, flags_dev, (u32)bit);
     C.timer.mark("foreign_field_mul", C.stream);
     return KH_OK;
-}
-int ff_mul_rows(Context& C, int field, const uint64_t* modulus, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
-                uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit) {
-    const FfMulConst m{limb::ff_modulus(host_limbs(modulus))};
-    return ff_mul_rows_prepared(C, field, m, a_dev, b_dev, n, at, out_checks_dev, flags_dev, bit);
 }
 // the limbs of f and of 2^264 - f, two u64 each (kh_foreign_field_gate_coefficients reduces them into the field)
 void ff_negated_modulus(const uint64_t* modulus, uint64_t* nf_out) {

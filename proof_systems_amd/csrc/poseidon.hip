@@ -1,6 +1,6 @@
 // poseidon.hip -- Kimchi Poseidon on the device (PlonkSpongeConstantsKimchi, poseidon/src/constants.rs:29-41: width 3, rate 2, 55 full rounds of
 // x^7, the 3 x 3 MDS, + round constants, no initial round-constant addition; poseidon/src/permutation.rs full_round), for kh_poseidon_permute_dev,
-// kh_poseidon_hash_dev and kh_poseidon_gate_witness_dev (csrc/vector_api.cpp).
+// kh_poseidon_hash_dev and kh_poseidon_gate_witness_dev (csrc/vector_api.cpp, csrc/witness_steps.cpp).
 //
 //   k_poseidon_permute     n states of 3 elements, in place
 //   k_poseidon_hash        ArithmeticSponge (poseidon.rs:60-175): state = init, absorb msg_len elements at rate 2, squeeze once; one message per lane
@@ -168,7 +168,7 @@ k_poseidon_gate_rows3(const u64* states, size_t n, WitnessPlace at, u64* out_sta
 // lanes win up to 53,760 instances (0.545 against 0.599 ms; 0.380 against 0.532 at 43,008), lose at 2^16 (0.71 against 0.61) and by 2 % at 2^20.
 static std::atomic<size_t> g_split_max_n{(size_t)POSEIDON_SPLIT * 2048};
 
-// (the callers in vector_api.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grid inside 31 bits)
+// (the callers in vector_api.cpp and witness_steps.cpp have validated pointers and sizes: n <= WAVE_BLOCK_MAX_N keeps the grid inside 31 bits)
 int poseidon_permute(Context& C, int field, uint64_t* states_dev, size_t n) {
     C.timer.begin(C.stream);
     KH_FIELD_LAUNCH(field, k_poseidon_permute<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, states_dev, n);

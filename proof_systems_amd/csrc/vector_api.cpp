@@ -1,4 +1,4 @@
-// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, the curve and limb gates' kh_*_witness_dev and the wiring between them, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.
+// vector_api.cpp -- vector steps (kh_poly_*, kh_expr_*, kh_gate_*, kh_poseidon_*, scans, divisions), kh_ntt* / kh_lde* / kh_coset_ntt_dev and the host-pointer transforms.  (The gadget and wire steps, kh_*_witness_dev, are in witness_steps.cpp.)
 #include <stdlib.h>
 
 #include "api_internal.hpp"
@@ -222,169 +222,6 @@ int kh_poseidon_hash_dev(int field, const uint64_t* msgs_dev, size_t msg_len, si
 }
 #undef KH_POSEIDON_ALIGNED
 int kh_poseidon_set_split_max_n(size_t n) { poseidon_set_split_max_n(n); return KH_OK; }
-
-// ---------------------------------------------------------------------------------- gadget witnesses on the device (kernels in poseidon.hip, curve_gadgets.hip)
-}  // extern "C"
-namespace {
-// The queueing of a validated call with a host table of `words` uint32_t (start rows, cells; nullable): the table travels through the pinned staging
-// ring into a block of the kh_dev_alloc pool (taken before the context's lock, like kh_lookup_sorted_dev's scratch), in pieces that leave the ring its
-// size -- the caller's array is not read after this returns -- and launch(C, table_dev) runs with the table on the device (null without one).
-template <class Launch>
-int table_queue(const uint32_t* table, size_t words, Launch launch) {
-    PoolBlock table_dev;
-    int rc;
-    if (table && (rc = kh_dev_alloc(&table_dev.p, words * sizeof(uint32_t)))) return rc;
-    return queue_step([&](Context& C) {
-        const size_t piece = (size_t)1 << 15;
-        if (table) counter(CNT_TABLE_STAGED_WORDS) += words;
-        for (size_t i = 0; table && i < words; i += piece) {
-            const int up = C.stage_upload(table_dev.as<uint32_t>() + i, {{table + i, std::min(piece, words - i) * sizeof(uint32_t)}});
-            if (up) return up;
-        }
-        return launch(C, table_dev.as<uint32_t>());
-    });
-}
-// ... of a gadget call: launch(C, at) runs with at.rows on the device
-template <class Launch>
-int gadget_queue(WitnessPlace at, size_t n, Launch launch) {
-    if (n == 0) return ensure_init();
-    return table_queue(at.rows, n, [&](Context& C, const uint32_t* rows_dev) { at.rows = rows_dev; return launch(C, at); });
-}
-}  // namespace
-extern "C" {
-
-int kh_poseidon_gate_witness_dev(int field, const uint64_t* states_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                                 uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_states_dev) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = poseidon_gate_validate("kh_poseidon_gate_witness_dev", field, states_dev, n, at, col_len, out_states_dev);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return poseidon_gate_rows(C, field, states_dev, n, dev, out_states_dev); });
-}
-int kh_complete_add_witness_dev(int field, const uint64_t* p1_dev, const uint64_t* p2_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                                uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = complete_add_validate("kh_complete_add_witness_dev", field, p1_dev, p2_dev, n, at, col_len, out_dev);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return complete_add_rows(C, field, p1_dev, p2_dev, n, dev, out_dev); });
-}
-int kh_endomul_scalar_witness_dev(int field, const uint64_t* chals_dev, unsigned num_bits, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                                  uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint64_t endo_scalar[4], uint64_t* out_dev) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = endomul_scalar_validate("kh_endomul_scalar_witness_dev", field, chals_dev, num_bits, n, at, col_len, endo_scalar, out_dev);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return endomul_scalar_rows(C, field, chals_dev, num_bits, n, dev, endo_scalar, out_dev); });
-}
-static int chain_witness(const char* call, int field, bool is_endo, const uint64_t* endo, const uint64_t* base_dev, const uint64_t* acc0_dev,
-                         const uint64_t* scalars_dev, unsigned num_bits, size_t n, const WitnessPlace& at, size_t col_len, uint64_t* out_acc_dev,
-                         uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    int rc = chain_validate(call, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, at, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
-    if (rc) return rc;
-    PoolBlock scratch;
-    const size_t scratch_bytes = chain_scratch_bytes(is_endo, num_bits, n);
-    if (n > 0 && (rc = kh_dev_alloc(&scratch.p, scratch_bytes))) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
-        return chain_rows(C, field, is_endo, endo, base_dev, acc0_dev, scalars_dev, num_bits, n, dev, out_acc_dev, out_n_dev, flags_dev, bit, scratch.as<uint64_t>(),
-                          scratch_bytes);
-    });
-}
-int kh_varbasemul_witness_dev(int field, const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* scalars_dev, unsigned num_bits, size_t n,
-                              const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
-                              uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    return chain_witness("kh_varbasemul_witness_dev", field, false, nullptr, base_dev, acc0_dev, scalars_dev, num_bits, n,
-                         WitnessPlace{rows, row0, row_stride, witness_dev, col_stride}, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
-}
-int kh_endomul_witness_dev(int field, const uint64_t endo[4], const uint64_t* base_dev, const uint64_t* acc0_dev, const uint64_t* chals_dev, unsigned num_bits,
-                           size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
-                           uint64_t* out_acc_dev, uint64_t* out_n_dev, uint32_t* flags_dev, unsigned bit) {
-    return chain_witness("kh_endomul_witness_dev", field, true, endo, base_dev, acc0_dev, chals_dev, num_bits, n,
-                         WitnessPlace{rows, row0, row_stride, witness_dev, col_stride}, col_len, out_acc_dev, out_n_dev, flags_dev, bit);
-}
-int kh_curve_witness_set_slice_elements(size_t elements) { chain_set_slice_elements(elements); return KH_OK; }
-
-// ---------------------------------------------------------------------------------- the optional gates' witnesses (kernels in limb_gadgets.hip)
-int kh_foreign_field_gate_coefficients(int field, const uint64_t modulus[6], uint64_t* out) {
-    KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "kh_foreign_field_gate_coefficients: unknown field id %d", field);
-    KH_REQUIRE(out, "kh_foreign_field_gate_coefficients: null output");
-    int rc = modulus_validate("kh_foreign_field_gate_coefficients", modulus, 1);
-    if (rc) return rc;
-    uint64_t nf[6];
-    ff_negated_modulus(modulus, nf);
-    const khost::Fld F(field);
-    const uint64_t* const src[7] = {modulus + 4, nf, nf + 2, nf + 4, modulus, modulus + 2, modulus + 4};       // f2 nf0 nf1 nf2 | f0 f1 f2
-    for (size_t k = 0; k < 7; k++) {
-        const khost::fe v = F.to_mont(khost::fe{{src[k][0], src[k][1], 0, 0}});
-        memcpy(out + 4 * k, v.l, 32);
-    }
-    return KH_OK;
-}
-int kh_range_check_witness_dev(int field, const uint64_t* limbs_dev, size_t n, int compact, const uint32_t* rows, size_t row0, size_t row_stride,
-                               uint64_t* witness_dev, size_t col_stride, size_t col_len, uint32_t* flags_dev, unsigned bit) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = range_check_validate("kh_range_check_witness_dev", field, limbs_dev, n, compact, at, col_len, flags_dev, bit);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return range_check_rows(C, field, limbs_dev, n, compact, dev, flags_dev, bit); });
-}
-int kh_xor_witness_dev(int field, const uint64_t* in1_dev, const uint64_t* in2_dev, unsigned bits, size_t n, const uint32_t* rows, size_t row0,
-                       size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = xor_validate("kh_xor_witness_dev", field, in1_dev, in2_dev, bits, n, at, col_len, out_dev, flags_dev, bit);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return xor_rows(C, field, in1_dev, in2_dev, bits, n, dev, out_dev, flags_dev, bit); });
-}
-int kh_rot64_witness_dev(int field, const uint64_t* words_dev, unsigned rot, size_t n, const uint32_t* rows, size_t row0, size_t row_stride,
-                         uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = rot64_validate("kh_rot64_witness_dev", field, words_dev, rot, n, at, col_len, out_dev);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return rot64_rows(C, field, words_dev, rot, n, dev, out_dev); });
-}
-int kh_foreign_field_add_witness_dev(int field, const uint64_t modulus[6], const uint64_t* left_dev, const uint64_t* right_dev, int sign, size_t n,
-                                     const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len,
-                                     uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = ff_add_validate("kh_foreign_field_add_witness_dev", field, modulus, left_dev, right_dev, sign, n, at, col_len, out_dev, flags_dev, bit);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
-        return ff_add_rows(C, field, modulus, left_dev, right_dev, sign, n, dev, out_dev, flags_dev, bit);
-    });
-}
-int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const uint32_t* rows,
-                                     size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_checks_dev,
-                                     uint32_t* flags_dev, unsigned bit) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = ff_mul_validate("kh_foreign_field_mul_witness_dev", field, modulus, a_dev, b_dev, n, at, col_len, out_checks_dev, flags_dev, bit);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) {
-        return ff_mul_rows(C, field, modulus, a_dev, b_dev, n, dev, out_checks_dev, flags_dev, bit);
-    });
-}
-
-// ---------------------------------------------------------------------------------- wires between the gadgets (kernels in wiring.hip)
-int kh_witness_gather_dev(int field, const uint64_t* witness_dev, size_t col_stride, size_t col_len, const uint32_t* cells, size_t n, int format,
-                          uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
-    int rc = cells_validate("kh_witness_gather_dev", field, format, witness_dev, col_stride, col_len, cells, n, "out_dev", out_dev, flags_dev, bit);
-    if (rc) return rc;
-    if (n == 0) return ensure_init();
-    return table_queue(cells, 2 * n, [&](Context& C, const uint32_t* cells_dev) {
-        return cell_gather(C, field, witness_dev, col_stride, cells_dev, n, format, out_dev, flags_dev, bit);
-    });
-}
-int kh_witness_scatter_dev(int field, const uint64_t* values_dev, int format, const uint32_t* cells, size_t n, uint64_t* witness_dev, size_t col_stride,
-                           size_t col_len, uint32_t* flags_dev, unsigned bit) {
-    int rc = cells_validate("kh_witness_scatter_dev", field, format, witness_dev, col_stride, col_len, cells, n, "values_dev", values_dev, flags_dev, bit);
-    if (rc) return rc;
-    if (n == 0) return ensure_init();
-    return table_queue(cells, 2 * n, [&](Context& C, const uint32_t* cells_dev) {
-        return cell_scatter(C, field, values_dev, format, cells_dev, n, witness_dev, col_stride, flags_dev, bit);
-    });
-}
-int kh_generic_witness_dev(int field, const uint64_t coeffs[20], int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const uint32_t* rows,
-                           size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride, size_t col_len, uint64_t* out_dev) {
-    const WitnessPlace at{rows, row0, row_stride, witness_dev, col_stride};
-    int rc = generic_validate("kh_generic_witness_dev", field, coeffs, half, l_dev, r_dev, n, at, col_len, out_dev);
-    if (rc) return rc;
-    return gadget_queue(at, n, [&](Context& C, const WitnessPlace& dev) { return generic_rows(C, field, coeffs, half, l_dev, r_dev, n, dev, out_dev); });
-}
 
 // ---------------------------------------------------------------------------------- NTT
 int kh_domain_generator(int field, unsigned log2_n, uint64_t out[4]) {

@@ -1,6 +1,6 @@
 // wiring.hip -- what joins two gadgets on the device: single witness cells read into and written from the input formats of the gadget calls, and the
 // generic rows between them (kimchi/src/circuits/polynomials/generic.rs; oracle/circuit.py::generic_spec has the coefficient order), for
-// kh_witness_gather_dev, kh_witness_scatter_dev and kh_generic_witness_dev (csrc/vector_api.cpp).  include/kimchi_hip.h has the formats.
+// kh_witness_gather_dev, kh_witness_scatter_dev and kh_generic_witness_dev (csrc/witness_steps.cpp).  include/kimchi_hip.h has the formats.
 //
 // Every kernel is ONE LANE PER CELL (or generic instance) in blocks of one wave.  A cell is one 32-byte element at an arbitrary (row, column): two
 // 16-byte accesses per lane that share a 32-byte sector and nothing else with their neighbours', whatever the launch shape -- the witness side moves
@@ -134,7 +134,7 @@ k_generic_half(const u64* l_in, const u64* r_in, size_t n, GenericHalf co, unsig
     if (out) o.store(out + 4 * i);
 }
 
-// (the callers in vector_api.cpp have validated pointers, sizes and every cell; one phase of kh_last_timings per call)
+// (the callers in witness_steps.cpp have validated pointers, sizes and every cell; one phase of kh_last_timings per call)
 int cell_gather(Context& C, int field, const uint64_t* witness_dev, size_t col_stride, const uint32_t* cells_dev, size_t n, int format, uint64_t* out_dev,
                 uint32_t* flags_dev, unsigned bit) {
     C.timer.begin(C.stream);
@@ -181,10 +181,6 @@ int generic_rows_prepared(Context& C, int field, const GenericHalf& co, int half
                     (unsigned)(3 * half), at, (u64*)out_dev);
     C.timer.mark("generic", C.stream);
     return KH_OK;
-}
-int generic_rows(Context& C, int field, const uint64_t* coeffs, int half, const uint64_t* l_dev, const uint64_t* r_dev, size_t n, const WitnessPlace& at,
-                 uint64_t* out_dev) {
-    return generic_rows_prepared(C, field, generic_fold(field, coeffs), half, l_dev, r_dev, n, at, out_dev);
 }
 
 }  // namespace kh
