@@ -493,6 +493,34 @@ int kh_generic_witness_dev(int field, const uint64_t coeffs[20] /* host: l r o m
                            const uint32_t *rows, size_t row0, size_t row_stride,
                            uint64_t *witness_dev, size_t col_stride, size_t col_len, uint64_t *out_dev /* nullable */);
 
+/* ---- GateType::Lookup rows on the device: the values a circuit reads from a ROM / RAM table (csrc/lookup_rows.hip) ----
+ * A Lookup row holds (table id, key, value, key, value, key, value).  The circuit knows the keys; the values are what the table holds at them, and
+ * in a runtime table they arrive with each proof.  An instance is ONE row, placed like every gadget's (rows[i], or row0 + i * row_stride with
+ * row_stride >= 1).  table_keys_dev, table_values_dev: table_len elements each, two columns of a table's rows -- typically column 0 and column 1 of
+ * the combined table at that table's rows (kh_prover_index_lookup_table), or a runtime table's first column and the caller's own runtime values.
+ * keys_dev: n x 3 elements.  For instance i and slot k = 0, 1, 2: t = the LOWEST index with table_keys_dev[t] == keys_dev[3 i + k] (elements are
+ * compared as 32-byte strings: canonical Montgomery limbs are unique; inputs are assumed canonical and are not checked), the value is
+ * table_values_dev[t].  Written per instance: cell 0 = table_id, cell 2 k + 1 = the key, cell 2 k + 2 = the value, NOTHING else -- cells 7..14 stay
+ * as they are.  out_values_dev (nullable): n x 3 elements, the values.  The Lookup pattern always makes three lookups per row: a row that needs
+ * fewer repeats a key.
+ * A key that is in no row of the table sets bit `bit` of *flags_dev (the rules of the limb gadgets: a caller-zeroed device uint32_t, nullable, not
+ * touched otherwise) and gets the zero element as its value, in the cell and in out_values_dev; every other slot and instance is exact.
+ * The call reads only the two columns it is given.  On a table wider than two columns the row satisfies the pattern only where the further columns
+ * are zero at row t, and table_id must be that table's id: both are the caller's responsibility, no flag is raised for them, and
+ * kh_witness_check_full (KH_WITNESS_LOOKUPS) names a row that gets either wrong.
+ * A vector step like the gadget calls: queued on the main stream of the calling thread's current context, ordered against every other call, and it
+ * does not wait for the device; n == 0 is KH_OK with nothing launched.  The hash set over the table's keys is built per call in a block of the
+ * kh_dev_alloc pool (a power of two of at least 2 table_len 32-bit slots).  KH_E_INVALID with a kh_last_error text that names the call, before
+ * anything is launched and with nothing written: what the gadget calls refuse (field, null / misaligned device pointers, col_stride < col_len, byte
+ * counts, an instance outside col_len rows), a null table_id or one >= p, table_len == 0 or >= 2^31, null or misaligned (16 bytes) table columns,
+ * 3 n lanes that overflow a grid, a misaligned flag word or bit >= 32. */
+int kh_lookup_witness_dev(int field, const uint64_t table_id[4] /* host, Montgomery, < p */,
+                          const uint64_t *table_keys_dev, const uint64_t *table_values_dev, size_t table_len,
+                          const uint64_t *keys_dev /* n x 3 x 4 limbs */, size_t n,
+                          const uint32_t *rows, size_t row0, size_t row_stride,
+                          uint64_t *witness_dev, size_t col_stride, size_t col_len,
+                          uint64_t *out_values_dev /* nullable, n x 3 x 4 */, uint32_t *flags_dev, unsigned bit);
+
 /* ---- Witness schedule: a circuit's gadget and wire steps compiled once, run per proof (csrc/witness_schedule.cpp, csrc/wiring.hip) ----
  * The circuit is fixed when its index is created and only the inputs change from proof to proof.  A schedule is the witness-side counterpart of
  * kh_prover_index_create: the list of direct calls above that writes a circuit's witness, described once.  kh_witness_schedule_create does everything
@@ -518,12 +546,15 @@ int kh_generic_witness_dev(int field, const uint64_t coeffs[20] /* host: l r o m
  *   KH_STEP_ROT64            kh_rot64_witness_dev                 words_dev   -         -            out_dev         -          rot       -
  *   KH_STEP_FF_ADD           kh_foreign_field_add_witness_dev     left_dev    right_dev -            out_dev         -          -         modulus[6]
  *   KH_STEP_FF_MUL           kh_foreign_field_mul_witness_dev     a_dev       b_dev     -            out_checks_dev  -          -         modulus[6]
+ *   KH_STEP_LOOKUP           kh_lookup_witness_dev                keys_dev    table_keys_dev  table_values_dev  out_values_dev  -  table_len  table_id[4]
  * (* nullable as in the direct call; every out[] but the gather's is nullable; refs and fields a call does not have are ignored.)  flag_bit: the
  * direct call's `bit` on the run's flags_dev, or KH_STEP_NO_FLAG for a step that passes flags_dev = NULL; calls without a flag ignore it.
+ * An arena extent is n instances of the argument's size, except the Lookup step's in[1] and in[2], which are its table: table_len x 32 bytes
+ * whatever n is (normally bound buffers: the pointers of kh_prover_index_lookup_table, the run's runtime values).
  * A run is equivalent to the direct calls issued in step order on the calling thread's current context: a vector step like them, queued on that
  * context's main stream and ordered against every other call -- a consumer (kh_witness_check, kh_prove) needs no kh_sync --, and it waits for the
- * device only where they do (once per slice in VarBaseMul / EndoMul steps).  The arena (arena_bytes, not zeroed) and the chain steps' scratch come from
- * the kh_dev_alloc pool for the time of the run, so a schedule is immutable after create and may be run from several threads and contexts of its
+ * device only where they do (once per slice in VarBaseMul / EndoMul steps).  The arena (arena_bytes, not zeroed), the chain steps' scratch and the
+ * Lookup steps' slots come from the kh_dev_alloc pool for the time of the run, so a schedule is immutable after create and may be run from several threads and contexts of its
  * device at once.
  * Wire steps are many and tiny.  Consecutive KH_STEP_GATHER steps whose out[0] is in the arena run as ONE launch (k_cell_moves, one lane per cell, formats
  * and flag bits mixed inside a wave), and likewise consecutive KH_STEP_SCATTER steps whose in[0] is; a step starts a new group where fusing would
@@ -538,7 +569,8 @@ int kh_generic_witness_dev(int field, const uint64_t coeffs[20] /* host: l r o m
  * flags_dev 4-byte aligned (nullable: no step raises a flag), col_stride >= col_len, byte counts -- and returns KH_E_INVALID before anything is
  * launched and with nothing written.  Its host work is O(steps); nothing goes through the staging ring (kh_counter("table_staged_words")).
  * kh_witness_schedule_info: steps; launch_groups = the launcher invocations a run makes (a fused group counts once, a step with n = 0 not at all);
- * resident_bytes = the device block holding the tables; run_bytes = what a run takes from the pool (arena + chain scratch at the current slice knob).
+ * resident_bytes = the device block holding the tables; run_bytes = what a run takes from the pool (arena + chain scratch at the current slice knob
+ * + the Lookup steps' slots).
  * kh_witness_schedule_free: no run of the schedule may be in progress on another thread; queued device work is waited for. */
 typedef struct kh_witness_schedule kh_witness_schedule_t;
 #define KH_REF_NONE  (-2)   /* a nullable argument that is absent */
@@ -546,7 +578,9 @@ typedef struct kh_witness_schedule kh_witness_schedule_t;
 #define KH_STEP_NO_FLAG 255 /* flag_bit of a step that raises no flag */
 enum { KH_STEP_GATHER = 0, KH_STEP_SCATTER = 1, KH_STEP_GENERIC = 2, KH_STEP_POSEIDON = 3, KH_STEP_COMPLETE_ADD = 4, KH_STEP_VARBASEMUL = 5,
        KH_STEP_ENDOMUL = 6, KH_STEP_ENDOMUL_SCALAR = 7, KH_STEP_RANGE_CHECK = 8, KH_STEP_XOR = 9, KH_STEP_ROT64 = 10, KH_STEP_FF_ADD = 11,
-       KH_STEP_FF_MUL = 12 };
+       KH_STEP_FF_MUL = 12,
+       /* 13 stays unassigned: it is refused as an unknown op (the tests of the schedule use it as the op that does not exist) */
+       KH_STEP_LOOKUP = 14 };
 typedef struct kh_witness_ref kh_witness_ref_t;
 typedef struct kh_witness_step kh_witness_step_t;
 struct kh_witness_ref { int buf; size_t offset; };   /* buf >= 0: bufs_dev[buf] of the run; offset in bytes */
@@ -555,9 +589,9 @@ struct kh_witness_step {
     size_t n;                                 /* instances; cells for GATHER / SCATTER */
     const uint32_t *rows; size_t row0, row_stride;   /* placement of a gadget step, exactly as in the direct call */
     const uint32_t *cells; int format;        /* GATHER / SCATTER: n (row, column) pairs, KH_CELL_* */
-    unsigned param;                           /* num_bits | bits | rot | compact | half, as the direct call names it */
+    unsigned param;                           /* num_bits | bits | rot | compact | half | table_len, as the direct call names it */
     int sign;                                 /* ForeignFieldAdd */
-    const uint64_t *consts;                   /* host, copied at create: endo[4] | endo_scalar[4] | modulus[6] | coeffs[20] | Poseidon none */
+    const uint64_t *consts;                   /* host, copied at create: endo[4] | endo_scalar[4] | modulus[6] | coeffs[20] | table_id[4] | Poseidon none */
     kh_witness_ref_t in[3], out[2];
     unsigned flag_bit;                        /* < 32, or KH_STEP_NO_FLAG */
 };
@@ -994,6 +1028,16 @@ int kh_prover_index_create_lookup(kh_srs_t *srs, size_t n_gates, const int *gate
 #define KH_LOOKUP_COL_ATOM_D8 5            /* k = 0 VanishesOnZeroKnowledgeAndPreviousRows, 1 UnnormalizedLagrangeBasis(0), 2 UnnormalizedLagrangeBasis(-zk_rows - 1) */
 #define KH_LOOKUP_COL_RUNTIME_SELECTOR 6   /* the runtime-table selector: k = 0 evaluations, 1 coefficient form, 2 d8 */
 int kh_debug_lookup_column(const kh_prover_index_t *index, int block, size_t k, const uint64_t **dev, size_t *elems);
+/* Where a lookup table sits in an index from kh_prover_index_create_lookup: the rows [first_row, first_row + len) of the combined table that hold
+ * table `table_id` -- one of the caller's fixed tables, a gate table (range check: id 1, XOR: id 0) or a runtime table, each under the id it was
+ * created with.  keys_dev = column 0 of the combined table at first_row, values_dev = column 1 at first_row (NULL when the combined table has one
+ * column): the two columns kh_lookup_witness_dev / KH_STEP_LOOKUP read.  For a runtime table column 1 is the index's fixed zero column: is_runtime
+ * is 1 (else 0), runtime_first is the table's first element inside the concatenated runtime values (else 0), and the caller passes
+ * its_runtime_values_dev + 4 * runtime_first as the value column.  NULL outputs are skipped; the memory belongs to the index.
+ * KH_E_NOTFOUND: an id the index does not have, an index without a lookup index, an index from kh_prover_index_new / _attach_lookup (whose tables
+ * are the caller's own). */
+int kh_prover_index_lookup_table(const kh_prover_index_t *index, int table_id, size_t *first_row, size_t *len, int *is_runtime,
+                                 size_t *runtime_first, const uint64_t **keys_dev, const uint64_t **values_dev);
 int kh_prover_index_shape(const kh_prover_index_t *index, unsigned *log2_n, unsigned *zk_rows, size_t *num_chunks);
 int kh_verifier_index_section(const kh_prover_index_t *index, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
 /* wall-clock seconds of kh_prover_index_create(_lookup)'s phases (the lookup columns count under the first, their transforms and atoms under the second), each ended by a device synchronisation: validation + upload + column kernel, transforms
@@ -1013,6 +1057,14 @@ int kh_prove_recursive(kh_prover_index_t *index, const uint64_t *witness, size_t
 int kh_prove_full(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, const uint64_t *randomness, size_t n_random,
                   unsigned flags, const uint64_t *prev_chals, const unsigned *prev_rounds, const uint64_t *prev_comm_xy, const uint8_t *prev_comm_inf,
                   const size_t *prev_comm_chunks, size_t n_prev, const uint64_t *runtime_values, size_t n_runtime, kh_proof_t **out);
+/* kh_prove_full with the runtime tables' second column in DEVICE memory (16-byte aligned; n_runtime elements): same meaning and same refusals, but the
+ * values are read in stream order -- a producer on this thread's context needs no kh_sync -- and, like witness_dev, are not checked against p.  The
+ * runtime column is assembled on the device (zeros, a device copy at the runtime rows, the drawn zero-knowledge rows) and the randomness is drawn in
+ * kh_prove_full's order: with the same index, witness, randomness and values every proof section is byte-identical. */
+int kh_prove_full_runtime_dev(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev, const uint64_t *randomness,
+                              size_t n_random, unsigned flags, const uint64_t *prev_chals, const unsigned *prev_rounds, const uint64_t *prev_comm_xy,
+                              const uint8_t *prev_comm_inf, const size_t *prev_comm_chunks, size_t n_prev, const uint64_t *runtime_values_dev,
+                              size_t n_runtime, kh_proof_t **out);
 /* ---- the witness against the circuit, row by row: ProverIndex::verify / ConstraintSystem::verify (kimchi/src/circuits/constraints.rs) ----
  * kh_prove with KH_PROVE_CHECK runs the whole proof before it says that the witness does not satisfy the constraints, and names no row.
  * kh_witness_check says which row and why, in tens of microseconds of kernels (csrc/witness_check.hip) over what is resident already: the index's d1
@@ -1093,6 +1145,11 @@ typedef struct {
 int kh_witness_check_full(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev,
                           const uint64_t *runtime_values, size_t n_runtime, unsigned flags, kh_witness_report_t *out,
                           kh_witness_lookup_t *lookup_out);
+/* kh_witness_check_full with the runtime values in DEVICE memory (16-byte aligned): same meaning and refusals, read in stream order and not checked
+ * against p (a value >= p equals no canonical cell). */
+int kh_witness_check_full_runtime_dev(kh_prover_index_t *index, const uint64_t *witness, size_t rows, const uint64_t *witness_dev,
+                                      const uint64_t *runtime_values_dev, size_t n_runtime, unsigned flags, kh_witness_report_t *out,
+                                      kh_witness_lookup_t *lookup_out);
 int kh_witness_lookup_message(const kh_witness_report_t *r, const kh_witness_lookup_t *l, char *buf, size_t cap);
 int kh_proof_section(const kh_proof_t *proof, int section, const uint64_t **limbs, const uint8_t **flags, size_t *count);
 int kh_proof_phase_seconds(const kh_proof_t *proof, double *seconds, size_t cap);   /* witness_upload, witness_commit, z, quotient, evaluations, opening */

@@ -153,6 +153,13 @@ struct FfMulConst;
 std::shared_ptr<const FfMulConst> ff_mul_prepare(const uint64_t* modulus);
 int ff_mul_rows_prepared(Context& C, int field, const FfMulConst& m, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, const WitnessPlace& at,
                          uint64_t* out_checks_dev, uint32_t* flags_dev, unsigned bit);
+// lookup_rows.hip: the launcher of kh_lookup_witness_dev, queued on C.stream (arguments validated by the entry point; n >= 1, 3 n <= WAVE_BLOCK_MAX_N,
+// 1 <= table_len < 2^31; table_id: 4 Montgomery limbs on the host).  The hash set over the table's keys is built per call in slots_dev, a block of
+// lookup_rows_slot_bytes(table_len) that the entry point takes from the kh_dev_alloc pool.
+size_t lookup_rows_slot_bytes(size_t table_len);
+int lookup_rows(Context& C, const uint64_t* table_id, const uint64_t* table_keys_dev, const uint64_t* table_values_dev, size_t table_len,
+                const uint64_t* keys_dev, size_t n, const WitnessPlace& at, uint64_t* out_values_dev, uint32_t* flags_dev, unsigned bit, uint32_t* slots_dev,
+                size_t scratch_bytes);
 // A group of wire steps of a witness schedule in one launch (k_cell_moves): one resident 16-byte record per cell.  The dense side of every move is
 // the run's arena, `dense` words of 8 bytes from its start; flag: the step's bit, or CELL_MOVE_NO_FLAG.
 struct CellMove { uint32_t row, meta, dense_lo, dense_hi; };
@@ -218,14 +225,16 @@ struct OpInfo {
     unsigned in_bytes[3], out_bytes[2];       // per instance; 0: the cell format decides (GATHER / SCATTER)
     bool tabled_cells;                        // the table is `cells` (2 n words), not `at.rows` (n words)
     int n_consts;                             // uint64_t words behind `consts`
+    unsigned table_in = 0;                    // bit k: in[k] is a table of `param` elements of in_bytes[k], not one of them per instance (LOOKUP)
 };
 const OpInfo* step_op(int op);                // null: no such op
 // What a step computes on the host before it can be launched: a generic half's c_l c_r c_m c_c over -c_o (all zero when c_o = 0), ForeignFieldMul's
 // modulus with its Barrett constant.  A direct call takes it per call, a schedule once, at create.
 struct StepPrepared { GenericHalf generic; std::shared_ptr<const FfMulConst> ff_mul; };
 // step_validate: everything the step's direct call refuses, in that call's order and words; `call` names the call, or the schedule's step.
-// step_prepare: for n >= 1 (at n = 0 coeffs / modulus may be null).  step_scratch_bytes: what VarBaseMul / EndoMul need from the kh_dev_alloc pool
-// at the current slice knob, 0 for every other step and at n = 0.  step_launch: queued on C.stream, n >= 1.
+// step_prepare: for n >= 1 (at n = 0 coeffs / modulus may be null).  step_scratch_bytes: what VarBaseMul / EndoMul (at the current slice knob) and
+// Lookup (the slots of its table's hash set) need from the kh_dev_alloc pool, 0 for every other step and at n = 0.  step_launch: queued on
+// C.stream, n >= 1.
 int step_validate(const char* call, int field, size_t col_len, const StepArgs& a);
 StepPrepared step_prepare(int field, const StepArgs& a);
 size_t step_scratch_bytes(const StepArgs& a);

@@ -18,6 +18,7 @@
 // All memory-bound, 256-thread blocks.  Every index is below 2^31 (the caller refuses (max_per_row + 1) L >= 2^31).
 #include "common.hpp"
 #include "msm.hpp"
+#include "lookup_key.cuh"                                    // Key, load_key, same, hash (shared with lookup_rows.hip)
 
 namespace kh {
 
@@ -25,20 +26,6 @@ namespace {
 typedef uint32_t u32;
 typedef uint64_t u64;
 constexpr u32 SORTED_EMPTY = 0xffffffffu;
-
-struct Key { u64 l[4]; };
-__device__ __forceinline__ Key load_key(const u64* __restrict__ p) {
-    const ulonglong2 a = ((const ulonglong2*)p)[0], b = ((const ulonglong2*)p)[1];
-    Key k; k.l[0] = a.x; k.l[1] = a.y; k.l[2] = b.x; k.l[3] = b.y;
-    return k;
-}
-__device__ __forceinline__ bool same(const Key& a, const Key& b) { return ((a.l[0] ^ b.l[0]) | (a.l[1] ^ b.l[1]) | (a.l[2] ^ b.l[2]) | (a.l[3] ^ b.l[3])) == 0; }
-__device__ __forceinline__ u64 hash(const Key& k) {          // as host_lookup.cpp
-    u64 h = k.l[0] * 0x9e3779b97f4a7c15ULL ^ k.l[1];
-    h = (h ^ (h >> 29)) * 0xbf58476d1ce4e5b9ULL ^ k.l[2];
-    h = (h ^ (h >> 32)) * 0x94d049bb133111ebULL ^ k.l[3];
-    return h ^ (h >> 31);
-}
 }  // namespace
 
 __global__ void __launch_bounds__(256)

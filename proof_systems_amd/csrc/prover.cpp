@@ -55,6 +55,9 @@ struct kh_lookup_index {
     // runtime tables (lookup/runtime_tables.rs): the rows of the combined table whose second column arrives with each proof
     const uint64_t *rtsel1 = nullptr, *rtselc = nullptr, *rtsel8 = nullptr;
     size_t rt_offset = 0, rt_len = 0;
+    // kh_prover_index_create_lookup: where each table sits in the combined table (kh_prover_index_lookup_table); empty for an attached lookup index
+    struct TableAt { int id; size_t first_row, len; bool runtime; size_t runtime_first; };
+    std::vector<TableAt> tables;
 };
 
 struct kh_prover_index {
@@ -525,6 +528,12 @@ int index_build(const char* who, kh_srs_t* srs, size_t n_gates, const int* gate_
         if (has_ids) lk->tids = l1.at((nsel + width) * n);
         for (int k = 0; k < 3; k++) lk->atoms8[k] = l8.at((nsel + (size_t)k) * 8 * n);
         if (has_rt) { lk->rtsel1 = l1.at(npat * n); lk->rtselc = lc.at(npat * n); lk->rtsel8 = l8.at(npat * 8 * n); lk->rt_offset = rt_offset; lk->rt_len = rt_len; }
+        size_t first_row = 0;
+        for (size_t k = 0; k < tabs.size(); k++) {       // the combined table's order: fixed, gate, runtime tables
+            const bool runtime = k >= tabs.size() - lin->n_runtime;
+            lk->tables.push_back({tabs[k].id, first_row, tabs[k].len, runtime, runtime ? first_row - rt_offset : 0});
+            first_row += tabs[k].len;
+        }
         ix->lk = lk;
         ix->own_l1 = l1.p; ix->own_lc = lc.p; ix->own_l8 = l8.p;
         l1.p = lc.p = l8.p = nullptr;
@@ -604,6 +613,25 @@ int kh_debug_lookup_column(const kh_prover_index_t* ix, int block, size_t k, con
     *dev = p; *elems = len;
     return KH_OK;
 }
+int kh_prover_index_lookup_table(const kh_prover_index_t* ix, int table_id, size_t* first_row, size_t* len, int* is_runtime, size_t* runtime_first,
+                                 const uint64_t** keys_dev, const uint64_t** values_dev) {
+    if (!ix) { kh::set_error("kh_prover_index_lookup_table: null index"); return KH_E_INVALID; }
+    const kh_lookup_index* lk = ix->lk;
+    if (!lk) { kh::set_error("kh_prover_index_lookup_table: the index has no lookup index"); return KH_E_NOTFOUND; }
+    if (!ix->created) { kh::set_error("kh_prover_index_lookup_table: the index comes from kh_prover_index_new, whose tables are the caller's own"); return KH_E_NOTFOUND; }
+    for (const kh_lookup_index::TableAt& t : lk->tables) {
+        if (t.id != table_id) continue;
+        if (first_row) *first_row = t.first_row;
+        if (len) *len = t.len;
+        if (is_runtime) *is_runtime = t.runtime ? 1 : 0;
+        if (runtime_first) *runtime_first = t.runtime_first;
+        if (keys_dev) *keys_dev = lk->tcols[0] + 4 * t.first_row;
+        if (values_dev) *values_dev = lk->tcols.size() > 1 ? lk->tcols[1] + 4 * t.first_row : nullptr;
+        return KH_OK;
+    }
+    kh::set_error("kh_prover_index_lookup_table: the index has no lookup table with id %d", table_id);
+    return KH_E_NOTFOUND;
+}
 int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, size_t cap) {
     if (!ix || !seconds) { kh::set_error("kh_prover_index_phase_seconds: null argument"); return KH_E_INVALID; }
     for (size_t i = 0; i < cap && i < 4; i++) seconds[i] = ix->phase[i];
@@ -612,8 +640,10 @@ int kh_prover_index_phase_seconds(const kh_prover_index_t* ix, double* seconds, 
 
 // ProverIndex::verify (constraints.rs): the first row of the witness that violates its gate or a copy constraint -- or, kh_witness_check_full with
 // KH_WITNESS_LOOKUPS, looks up a tuple that is in no table.  Kernels in witness_check.hip.  `allowed`: the flags the entry point `who` takes.
+// runtime_on_device: runtime_values is device memory, read in stream order and not compared with p.
 static int witness_check_impl(const char* who, unsigned allowed, kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev,
-                              const uint64_t* runtime_values, size_t n_runtime, unsigned flags, kh_witness_report_t* out, kh_witness_lookup_t* lookup_out) {
+                              const uint64_t* runtime_values, bool runtime_on_device, size_t n_runtime, unsigned flags, kh_witness_report_t* out,
+                              kh_witness_lookup_t* lookup_out) {
     if (!ix || !out) { kh::set_error("%s: null argument", who); return KH_E_INVALID; }
     if (!witness == !witness_dev) { kh::set_error("%s: give the witness either on the host or on the device", who); return KH_E_INVALID; }
     if (!flags || (flags & ~allowed)) {
@@ -639,7 +669,8 @@ static int witness_check_impl(const char* who, unsigned allowed, kh_prover_index
             kh::set_error("%s: RuntimeTablesInconsistent: the index has %zu runtime table rows, the call brings %zu", who, rt_len, runtime_values ? n_runtime : (size_t)0);
             return KH_E_INVALID;
         }
-        for (size_t i = 0; i < rt_len; i++)
+        if (runtime_on_device && (((uintptr_t)runtime_values) & 15)) { kh::set_error("%s: runtime_values_dev must be 16-byte aligned", who); return KH_E_INVALID; }
+        for (size_t i = 0; !runtime_on_device && i < rt_len; i++)
             if (khost::geq(load(runtime_values + 4 * i), F.f.p)) { kh::set_error("%s: runtime value %zu is not below the field's modulus", who, i); return KH_E_INVALID; }
         if (n <= ix->zk + 1 || lk->tcols.empty() || lk->pats.empty()) { kh::set_error("%s: the lookup index is empty", who); return KH_E_INVALID; }
         wl.npat = lk->pats.size();
@@ -656,7 +687,8 @@ static int witness_check_impl(const char* who, unsigned allowed, kh_prover_index
             }
         }
         wl.L = n - ix->zk - 1; wl.W = lk->tcols.size(); wl.tcols = lk->tcols.data(); wl.tids = lk->tids;
-        wl.rt_offset = rt_len ? lk->rt_offset : 0; wl.rt_len = rt_len; wl.runtime = rt_len ? runtime_values : nullptr;
+        wl.rt_offset = rt_len ? lk->rt_offset : 0; wl.rt_len = rt_len;
+        wl.runtime = rt_len && !runtime_on_device ? runtime_values : nullptr; wl.runtime_dev = rt_len && runtime_on_device ? runtime_values : nullptr;
     }
     struct DeviceRestore { int prev; ~DeviceRestore() { if (prev >= 0) (void)kh_set_device(prev); } } device_restore{kh_get_device()};
     KP(kh_set_device(kh_srs_device(ix->srs)));
@@ -709,12 +741,17 @@ static int witness_check_impl(const char* who, unsigned allowed, kh_prover_index
     return KH_OK;
 }
 int kh_witness_check(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, unsigned flags, kh_witness_report_t* out) {
-    return witness_check_impl("kh_witness_check", KH_WITNESS_GATES | KH_WITNESS_WIRES, ix, witness, rows, witness_dev, nullptr, 0, flags, out, nullptr);
+    return witness_check_impl("kh_witness_check", KH_WITNESS_GATES | KH_WITNESS_WIRES, ix, witness, rows, witness_dev, nullptr, false, 0, flags, out, nullptr);
 }
 int kh_witness_check_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* runtime_values, size_t n_runtime,
                           unsigned flags, kh_witness_report_t* out, kh_witness_lookup_t* lookup_out) {
-    return witness_check_impl("kh_witness_check_full", KH_WITNESS_GATES | KH_WITNESS_WIRES | KH_WITNESS_LOOKUPS, ix, witness, rows, witness_dev, runtime_values, n_runtime,
-                              flags, out, lookup_out);
+    return witness_check_impl("kh_witness_check_full", KH_WITNESS_GATES | KH_WITNESS_WIRES | KH_WITNESS_LOOKUPS, ix, witness, rows, witness_dev, runtime_values, false,
+                              n_runtime, flags, out, lookup_out);
+}
+int kh_witness_check_full_runtime_dev(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* runtime_values_dev,
+                                      size_t n_runtime, unsigned flags, kh_witness_report_t* out, kh_witness_lookup_t* lookup_out) {
+    return witness_check_impl("kh_witness_check_full_runtime_dev", KH_WITNESS_GATES | KH_WITNESS_WIRES | KH_WITNESS_LOOKUPS, ix, witness, rows, witness_dev,
+                              runtime_values_dev, true, n_runtime, flags, out, lookup_out);
 }
 int kh_witness_report_message(const kh_witness_report_t* r, char* buf, size_t cap) {
     if (!r || (!buf && cap)) { kh::set_error("kh_witness_report_message: null argument"); return KH_E_INVALID; }
@@ -780,9 +817,26 @@ int kh_prove_recursive(kh_prover_index_t* ix, const uint64_t* witness, size_t ro
                          nullptr, 0, out);
 }
 
+// the body of kh_prove_full and kh_prove_full_runtime_dev: runtime_values is host memory, or (runtime_on_device) device memory read in stream order
+static int prove_full_impl(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* randomness, size_t n_random,
+                           unsigned flags, const uint64_t* prev_chals, const unsigned* prev_rounds, const uint64_t* prev_comm_xy, const uint8_t* prev_comm_inf,
+                           const size_t* prev_comm_chunks, size_t n_prev, const uint64_t* runtime_values, bool runtime_on_device, size_t n_runtime, kh_proof_t** out);
 int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* randomness, size_t n_random,
                   unsigned flags, const uint64_t* prev_chals, const unsigned* prev_rounds, const uint64_t* prev_comm_xy, const uint8_t* prev_comm_inf,
                   const size_t* prev_comm_chunks, size_t n_prev, const uint64_t* runtime_values, size_t n_runtime, kh_proof_t** out) {
+    return prove_full_impl(ix, witness, rows, witness_dev, randomness, n_random, flags, prev_chals, prev_rounds, prev_comm_xy, prev_comm_inf, prev_comm_chunks, n_prev,
+                           runtime_values, false, n_runtime, out);
+}
+int kh_prove_full_runtime_dev(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* randomness, size_t n_random,
+                              unsigned flags, const uint64_t* prev_chals, const unsigned* prev_rounds, const uint64_t* prev_comm_xy, const uint8_t* prev_comm_inf,
+                              const size_t* prev_comm_chunks, size_t n_prev, const uint64_t* runtime_values_dev, size_t n_runtime, kh_proof_t** out) {
+    if (((uintptr_t)runtime_values_dev) & 15) { kh::set_error("kh_prove_full_runtime_dev: runtime_values_dev must be 16-byte aligned"); return KH_E_INVALID; }
+    return prove_full_impl(ix, witness, rows, witness_dev, randomness, n_random, flags, prev_chals, prev_rounds, prev_comm_xy, prev_comm_inf, prev_comm_chunks, n_prev,
+                           runtime_values_dev, true, n_runtime, out);
+}
+static int prove_full_impl(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, const uint64_t* witness_dev, const uint64_t* randomness, size_t n_random,
+                           unsigned flags, const uint64_t* prev_chals, const unsigned* prev_rounds, const uint64_t* prev_comm_xy, const uint8_t* prev_comm_inf,
+                           const size_t* prev_comm_chunks, size_t n_prev, const uint64_t* runtime_values, bool runtime_on_device, size_t n_runtime, kh_proof_t** out) {
     if (ix && ((ix->lk && ix->lk->rtsel1) ? (!runtime_values || n_runtime != ix->lk->rt_len) : n_runtime != 0)) {
         kh::set_error("RuntimeTablesInconsistent: the index has %zu runtime table rows, the proof brings %zu", (ix->lk && ix->lk->rtsel1) ? ix->lk->rt_len : (size_t)0, n_runtime);
         return KH_E_INVALID;
@@ -979,12 +1033,18 @@ int kh_prove_full(kh_prover_index_t* ix, const uint64_t* witness, size_t rows, c
     const fe* rt_blind = nullptr;
     const bool has_rt = lk && lk->rtsel1;
     if (has_rt) {                                     // prover.rs:397-470: placed at the runtime rows, zero-knowledge rows drawn from the last row backwards, committed hiding
-        std::vector<fe> rte(n, zero);
-        memcpy(&rte[lk->rt_offset], runtime_values, n_runtime * 32);
         const fe* z = draw(zk);
-        for (size_t j = 0; j < zk; j++) rte[n - zk + j] = z[zk - 1 - j];
         KP(d_rt.alloc(NB)); KP(d_rtc.alloc(NB));
-        KP(kh_dev_upload(d_rt.p, rte.data(), NB * 32));
+        if (runtime_on_device) {                      // the same column assembled on the device, in stream order: nothing waits for the values' producer
+            KP(kh_dev_memset_zero(d_rt.p, NB * 32));
+            KP(kh_dev_copy(d_rt.at(lk->rt_offset), runtime_values, n_runtime * 32));
+            for (size_t j = 0; j < zk; j++) KP(set_const(d_rt.at(n - zk + j), z[zk - 1 - j]));
+        } else {
+            std::vector<fe> rte(n, zero);
+            memcpy(&rte[lk->rt_offset], runtime_values, n_runtime * 32);
+            for (size_t j = 0; j < zk; j++) rte[n - zk + j] = z[zk - 1 - j];
+            KP(kh_dev_upload(d_rt.p, rte.data(), NB * 32));
+        }
         KP(kh_dev_copy(d_rtc.p, d_rt.p, NB * 32));
         KP(kh_ntt_dev(fid, d_rtc.p, logn, 1, 1));
         std::vector<uint64_t> rxy, rcx; std::vector<uint8_t> rinf, rci;

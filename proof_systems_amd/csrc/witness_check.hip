@@ -305,7 +305,8 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
     }
     if (lk) {
         const size_t L = lk->L, W = lk->W;
-        KH_REQUIRE(L >= 1 && L < n && W >= 1 && lk->tcols && lk->npat >= 1 && lk->npat <= 4 && lk->rt_offset + lk->rt_len <= L && (!lk->rt_len || (lk->runtime && W >= 2)),
+        KH_REQUIRE(L >= 1 && L < n && W >= 1 && lk->tcols && lk->npat >= 1 && lk->npat <= 4 && lk->rt_offset + lk->rt_len <= L &&
+                   (!lk->rt_len || ((!lk->runtime != !lk->runtime_dev) && W >= 2)) && (((uintptr_t)lk->runtime_dev) & 15) == 0,
                    "witness_check_run: bad lookup shape");
         for (size_t k = 0; k < lk->npat; k++) {
             const WitnessLookupPattern& P = lk->pat[k];
@@ -321,11 +322,12 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
         u32* const slots = (u32*)(runtime_dev + 4 * lk->rt_len);
         const size_t cap = wc_lookup_slots(L);
         static const u64 pad = 0;
-        if ((rc = C.stage_upload(cols_dev, {{lk->tcols, W * 8}, {&pad, (wc_lookup_col_words(W) - W) * 8}, {lk->runtime, lk->rt_len * 32}}))) return rc;
+        // (runtime values that are on the device already are read where they are: their room in the scratch block stays unused)
+        if ((rc = C.stage_upload(cols_dev, {{lk->tcols, W * 8}, {&pad, (wc_lookup_col_words(W) - W) * 8}, {lk->runtime, lk->runtime ? lk->rt_len * 32 : 0}}))) return rc;
         KH_HIP(hipMemsetAsync(slots, 0xff, cap * sizeof(u32), s));
         LookupTable T{};
         for (size_t k = 0; k < 3 && k < W; k++) { KH_REQUIRE(lk->tcols[k], "witness_check_run: null table column"); T.col[k] = lk->tcols[k]; }
-        T.tids = lk->tids; T.runtime = runtime_dev; T.rt_offset = (u32)lk->rt_offset; T.rt_len = (u32)lk->rt_len;
+        T.tids = lk->tids; T.runtime = lk->runtime_dev ? lk->runtime_dev : runtime_dev; T.rt_offset = (u32)lk->rt_offset; T.rt_len = (u32)lk->rt_len;
         hipLaunchKernelGGL(k_witness_lookup_build, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, s, T, (const u64* const*)cols_dev, (u32)W, (u32)L, slots, (u32)(cap - 1));
         C.timer.mark("check_lookup_build", s);
         LookupProbeArgs p{};

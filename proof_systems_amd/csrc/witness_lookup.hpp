@@ -17,7 +17,8 @@ struct WitnessLookups {
     const uint64_t* const* tcols;                        // host array of W device columns (d1)
     const uint64_t* tids;                                // the table-id column (d1, device), or NULL: every id is 0
     size_t rt_offset, rt_len;                            // the runtime rows of the table
-    const uint64_t* runtime;                             // HOST: rt_len elements, column 1 of the runtime rows (NULL iff rt_len == 0)
+    const uint64_t* runtime;                             // HOST: rt_len elements, column 1 of the runtime rows, or ...
+    const uint64_t* runtime_dev;                         // ... the same in DEVICE memory (16-byte aligned), read in stream order; both NULL iff rt_len == 0
 };
 
 }  // namespace kh

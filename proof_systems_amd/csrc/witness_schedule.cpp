@@ -21,7 +21,7 @@ struct Step {
     bool flagged = false;                     // the run's flags_dev is the step's
     size_t table = 0;                         // word offset of the step's rows[] / cells in the resident block
     bool has_table = false, has_consts = false;
-    int scratch = -1;                         // which of the run's scratch blocks is the step's (VarBaseMul / EndoMul), or none
+    int scratch = -1;                         // which of the run's scratch blocks is the step's (VarBaseMul / EndoMul / Lookup), or none
     uint64_t consts[20];
     StepPrepared prepared;
 };
@@ -51,12 +51,14 @@ int ref_validate(const char* call, const char* what, int k, const kh_witness_ref
     return KH_OK;
 }
 
-// the refs of step `call` that its op has, against the arena (after the call's own list: n is known to be small enough for the extents, the format to be one)
+// the refs of step `call` that its op has, against the arena (after the call's own list: n is known to be small enough for the extents, the format to be one).
+// An input that is a table (OpInfo::table_in: the Lookup step's two columns) extends over `param` elements, whatever n is.
 int refs_validate(const char* call, const OpInfo& op, const kh_witness_step_t& s, size_t arena_bytes, size_t n_bufs) {
     const size_t cell_bytes = op.tabled_cells ? format_bytes(s.format) : 0;
     int rc;
     for (int k = 0; k < op.n_in; k++)
-        if ((rc = ref_validate(call, "in", k, s.in[k], op.in_bytes[k] ? op.in_bytes[k] : cell_bytes, s.n, arena_bytes, n_bufs))) return rc;
+        if ((rc = ref_validate(call, "in", k, s.in[k], op.in_bytes[k] ? op.in_bytes[k] : cell_bytes, (op.table_in >> k & 1) ? (size_t)s.param : s.n, arena_bytes, n_bufs)))
+            return rc;
     for (int k = 0; k < op.n_out; k++)
         if ((rc = ref_validate(call, "out", k, s.out[k], op.out_bytes[k] ? op.out_bytes[k] : cell_bytes, s.n, arena_bytes, n_bufs))) return rc;
     return KH_OK;
@@ -180,7 +182,7 @@ int kh_witness_schedule_run(const kh_witness_schedule_t* s, void* const* bufs_de
     KH_REQUIRE((((uintptr_t)flags_dev) & 3) == 0, "kh_witness_schedule_run: the flag word at %p is misaligned", (void*)flags_dev);
     DeviceScope on_device(s->device);
     if ((rc = ensure_init())) return rc;
-    // what the run owns: the arena and the chain steps' scratch, from the pool (before the context's lock, like kh_lookup_sorted_dev's scratch)
+    // what the run owns: the arena, the chain steps' scratch and the Lookup steps' slots, from the pool (before the context's lock, like kh_lookup_sorted_dev's scratch)
     PoolBlock arena;
     if (s->arena_bytes && (rc = kh_dev_alloc(&arena.p, s->arena_bytes))) return rc;
     std::vector<PoolBlock> scratch(s->n_scratch);

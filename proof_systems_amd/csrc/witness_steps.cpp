@@ -1,4 +1,4 @@
-// witness_steps.cpp -- the gadget and wire steps (kh_*_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev): the one list of them.  A step is a
+// witness_steps.cpp -- the gadget and wire steps (kh_*_witness_dev, kh_lookup_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev): the one list of them.  A step is a
 // StepArgs record (api_internal.hpp); OPS[] says what each op takes, step_validate what it refuses, step_prepare what it computes on the host,
 // step_launch which launcher it runs.  A direct call fills the record from its arguments and goes through direct_step; a witness schedule
 // (witness_schedule.cpp) fills it from a kh_witness_step_t and goes through the same three functions, so the two cannot differ.
@@ -23,6 +23,8 @@ constexpr OpInfo OPS[] = {
     {"KH_STEP_ROT64", 1, 1, {8, 0, 0}, {8, 0}, false, 0},
     {"KH_STEP_FF_ADD", 2, 1, {48, 48, 0}, {48, 0}, false, 6},
     {"KH_STEP_FF_MUL", 2, 1, {48, 48, 0}, {144, 0}, false, 6},
+    {nullptr, 0, 0, {0, 0, 0}, {0, 0}, false, 0},                   // 13: unassigned (include/kimchi_hip.h), refused as an unknown op
+    {"KH_STEP_LOOKUP", 3, 1, {96, 32, 32}, {96, 0}, false, 4, 6},    // in[1], in[2]: the table's two columns, `param` elements each
 };
 constexpr int N_OPS = sizeof(OPS) / sizeof(OPS[0]);
 
@@ -75,7 +77,7 @@ int modulus_validate(const char* call, const uint64_t* modulus, size_t n) {
 }  // namespace
 
 namespace kh {
-const OpInfo* step_op(int op) { return op >= 0 && op < N_OPS ? &OPS[op] : nullptr; }
+const OpInfo* step_op(int op) { return op >= 0 && op < N_OPS && OPS[op].name ? &OPS[op] : nullptr; }
 
 // each call's own list, in the order the call has always checked it
 int step_validate(const char* call, int field, size_t col_len, const StepArgs& a) {
@@ -145,6 +147,21 @@ int step_validate(const char* call, int field, size_t col_len, const StepArgs& a
     case KH_STEP_FF_MUL:
         if ((rc = modulus_validate(call, a.consts, n))) return rc;
         return limb_validate(call, field, {{"a_dev", in[0], true}, {"b_dev", in[1], true}, {"out_checks_dev", out[0], false}}, a, col_len, 2);
+    case KH_STEP_LOOKUP: {
+        // gadget_validate's list for an instance of ONE row; the table id; the table's length and columns; one lane per (slot, instance); the flag
+        if ((rc = gadget_validate(call, field, {{"keys_dev", in[0], true}, {"out_values_dev", out[0], false}}, a, col_len, 1))) return rc;
+        KH_REQUIRE(a.consts || n == 0, "%s: null table_id", call);
+        khost::fe id{{0, 0, 0, 0}};
+        if (a.consts) memcpy(id.l, a.consts, sizeof(id.l));
+        KH_REQUIRE(!khost::geq(id, khost::Fld(field).f.p), "%s: table_id is not a canonical field element (>= p)", call);
+        KH_REQUIRE(a.param >= 1 && a.param < (1u << 31), "%s: table_len %u is not from 1 to 2^31 - 1", call, a.param);
+        for (const GadgetPtr& p : {GadgetPtr{"table_keys_dev", in[1], true}, GadgetPtr{"table_values_dev", in[2], true}}) {
+            KH_REQUIRE(p.p || n == 0, "%s: null %s", call, p.name);
+            KH_REQUIRE((((uintptr_t)p.p) & 15) == 0, "%s: %s must be 16-byte aligned", call, p.name);
+        }
+        KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / 3, "%s: %zu instances of 3 lookups overflow the grid", call, n);
+        return flag_validate(call, a);
+    }
     }
     set_error("%s: unknown op %d", call, a.op);
     return KH_E_INVALID;
@@ -158,6 +175,7 @@ StepPrepared step_prepare(int field, const StepArgs& a) {
 }
 
 size_t step_scratch_bytes(const StepArgs& a) {
+    if (a.op == KH_STEP_LOOKUP) return a.n > 0 ? lookup_rows_slot_bytes(a.param) : 0;
     return (a.op == KH_STEP_VARBASEMUL || a.op == KH_STEP_ENDOMUL) && a.n > 0 ? chain_scratch_bytes(a.op == KH_STEP_ENDOMUL, a.param, a.n) : 0;
 }
 
@@ -182,6 +200,7 @@ int step_launch(Context& C, int field, const StepArgs& a, const StepPrepared& pr
     case KH_STEP_ROT64: return rot64_rows(C, field, in0, a.param, a.n, a.at, out0);
     case KH_STEP_FF_ADD: return ff_add_rows(C, field, a.consts, in0, in1, a.sign, a.n, a.at, out0, a.flags, a.bit);
     case KH_STEP_FF_MUL: return ff_mul_rows_prepared(C, field, *prepared.ff_mul, in0, in1, a.n, a.at, out0, a.flags, a.bit);
+    case KH_STEP_LOOKUP: return lookup_rows(C, a.consts, in1, in2, a.param, in0, a.n, a.at, out0, a.flags, a.bit, (uint32_t*)scratch_dev, scratch_bytes);
     }
     set_error("step_launch: unknown op %d", a.op);
     return KH_E_INVALID;
@@ -191,7 +210,7 @@ int step_launch(Context& C, int field, const StepArgs& a, const StepPrepared& pr
 namespace {
 // A direct call.  Arguments first, before anything touches the device; the host-side constants; then what the call takes from the kh_dev_alloc pool
 // (before the context's lock, like kh_lookup_sorted_dev's scratch: the pool may order this context behind a block's previous owner) -- the chain
-// steps' scratch, and a block for the host table (start rows, or cells; nullable) --; then, under one hold of the lock, the table through the staging
+// steps' scratch or the Lookup step's slots, and a block for the host table (start rows, or cells; nullable) --; then, under one hold of the lock, the table through the staging
 // ring and the launch with the table on the device.  The caller's arrays are not read after this returns, and nothing waits for the device.
 int direct_step(const char* call, int field, size_t col_len, StepArgs a) {
     int rc = step_validate(call, field, col_len, a);
@@ -290,6 +309,16 @@ int kh_foreign_field_mul_witness_dev(int field, const uint64_t modulus[6], const
                                      uint32_t* flags_dev, unsigned bit) {
     return direct_step("kh_foreign_field_mul_witness_dev", field, col_len,
                        {KH_STEP_FF_MUL, n, {rows, row0, row_stride, witness_dev, col_stride}, {a_dev, b_dev}, {out_checks_dev}, 0, modulus, flags_dev, bit});
+}
+
+// ---------------------------------------------------------------------------------- GateType::Lookup rows (kernels in lookup_rows.hip)
+int kh_lookup_witness_dev(int field, const uint64_t table_id[4], const uint64_t* table_keys_dev, const uint64_t* table_values_dev, size_t table_len,
+                          const uint64_t* keys_dev, size_t n, const uint32_t* rows, size_t row0, size_t row_stride, uint64_t* witness_dev, size_t col_stride,
+                          size_t col_len, uint64_t* out_values_dev, uint32_t* flags_dev, unsigned bit) {
+    const unsigned len = table_len < ((size_t)1 << 31) ? (unsigned)table_len : 1u << 31;        // (a step's param is 32 bits: every refused length as one refused value)
+    return direct_step("kh_lookup_witness_dev", field, col_len,
+                       {KH_STEP_LOOKUP, n, {rows, row0, row_stride, witness_dev, col_stride}, {keys_dev, table_keys_dev, table_values_dev}, {out_values_dev}, len,
+                        table_id, flags_dev, bit});
 }
 
 // ---------------------------------------------------------------------------------- wires between the gadgets (kernels in wiring.hip)

@@ -858,11 +858,23 @@ def generic_witness_dev(field: int, coeffs, half: int, l, r, n: int, witness, co
                                        _ptr(out)))
 
 
+def lookup_witness_dev(field: int, table_id, table_keys, table_values, table_len: int, keys, n: int, witness, col_stride: int, col_len: int, rows=None,
+                       row0: int = 0, row_stride: int = 1, out_values=None, flags=None, bit: int = 0):
+    """kh_lookup_witness_dev: cells 0..6 of n Lookup rows = (table_id, key, value, key, value, key, value) for the n x 3 keys at `keys`, each value
+    read from `table_values` at the lowest row of `table_keys` that holds the key (two device columns of table_len elements: DevBufs, views or what
+    NativeProverIndex.lookup_table returns).  table_id: 4 Montgomery limbs.  out_values (nullable): the n x 3 values; the flag is set by a key that
+    is in no row of the table, whose value is then zero."""
+    _r, rp = _rows32(rows)
+    _check(_lib.kh_lookup_witness_dev(field, _p64(_c64(table_id, (4,))), _ptr(table_keys), _ptr(table_values), table_len, _ptr(keys), n, rp, row0, row_stride,
+                                      _ptr(witness), col_stride, col_len, _ptr(out_values), _ptr(flags), bit))
+
+
 WitnessRefC, WitnessStepC = _STRUCTURES["kh_witness_ref_t"], _STRUCTURES["kh_witness_step_t"]
 REF_NONE, REF_ARENA, STEP_NO_FLAG = _CONSTANTS["KH_REF_NONE"], _CONSTANTS["KH_REF_ARENA"], _CONSTANTS["KH_STEP_NO_FLAG"]
 (STEP_GATHER, STEP_SCATTER, STEP_GENERIC, STEP_POSEIDON, STEP_COMPLETE_ADD, STEP_VARBASEMUL, STEP_ENDOMUL, STEP_ENDOMUL_SCALAR, STEP_RANGE_CHECK, STEP_XOR,
- STEP_ROT64, STEP_FF_ADD, STEP_FF_MUL) = (_CONSTANTS["KH_STEP_" + _n] for _n in (
-     "GATHER", "SCATTER", "GENERIC", "POSEIDON", "COMPLETE_ADD", "VARBASEMUL", "ENDOMUL", "ENDOMUL_SCALAR", "RANGE_CHECK", "XOR", "ROT64", "FF_ADD", "FF_MUL"))
+ STEP_ROT64, STEP_FF_ADD, STEP_FF_MUL, STEP_LOOKUP) = (_CONSTANTS["KH_STEP_" + _n] for _n in (
+     "GATHER", "SCATTER", "GENERIC", "POSEIDON", "COMPLETE_ADD", "VARBASEMUL", "ENDOMUL", "ENDOMUL_SCALAR", "RANGE_CHECK", "XOR", "ROT64", "FF_ADD", "FF_MUL",
+     "LOOKUP"))
 _STEP_FIELDS = ("op", "n", "rows", "row0", "row_stride", "cells", "format", "param", "sign", "consts", "in", "out", "flag_bit")     # kh_witness_step_t's order
 
 
@@ -877,7 +889,8 @@ class WitnessSchedule:
     """kh_witness_schedule_*: a circuit's gadget and wire steps, validated and uploaded once (`create`), run per proof (`run`).  A step is a dict with
     the fields of kh_witness_step_t (or a tuple in their order: op, n, rows, row0, row_stride, cells, format, param, sign, consts, in, out, flag_bit);
     what a dict leaves out is 0 / None, n defaults to the number of cells, flag_bit to STEP_NO_FLAG.  in / out: lists of refs -- None, (REF_ARENA,
-    offset), (index of a bound buffer, offset).  consts: uint64 limbs as the direct call takes them, or the modulus as an int for the foreign-field steps."""
+    offset), (index of a bound buffer, offset).  consts: uint64 limbs as the direct call takes them (STEP_LOOKUP: the table id's 4 Montgomery limbs, with
+    param = table_len and in = [keys, table keys, table values]), or the modulus as an int for the foreign-field steps."""
 
     def __init__(self, handle, n_bufs: int, col_len: int):
         self.handle, self.n_bufs, self.col_len = handle, n_bufs, col_len
@@ -1002,12 +1015,20 @@ def witness_check(index, witness=None, witness_dev=None, flags: int = WITNESS_GA
     return rep
 
 
-def witness_check_full(index, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS):
+def witness_check_full(index, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS, runtime_dev=None):
     """kh_witness_check_full on a NativeProverIndex: as witness_check, + the lookups (WITNESS_LOOKUPS; runtime: (k, 4) limbs, the runtime tables' second
-    column, as for prove).  Returns (kh_witness_report_t, kh_witness_lookup_t), both filled; bad arguments raise KhError."""
+    column, as for prove -- or runtime_dev = (a DevBuf or view holding them, k): kh_witness_check_full_runtime_dev).  Returns (kh_witness_report_t,
+    kh_witness_lookup_t), both filled; bad arguments raise KhError."""
     w = _c64(witness, (15, -1, 4)) if witness is not None else None
     rtv = _c64(runtime, (-1, 4)) if runtime is not None else None
     rep, lk = WitnessReportC(), WitnessLookupC()
+    if runtime_dev is not None:
+        if runtime is not None:
+            raise ValueError("runtime values either on the host or on the device")
+        _check(_lib.kh_witness_check_full_runtime_dev(index._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
+                                                      C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _ptr(runtime_dev[0]), runtime_dev[1],
+                                                      flags, C.byref(rep), C.byref(lk)))
+        return rep, lk
     _check(_lib.kh_witness_check_full(index._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
                                       C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rtv) if rtv is not None else None,
                                       rtv.shape[0] if rtv is not None else 0, flags, C.byref(rep), C.byref(lk)))
@@ -1094,6 +1115,19 @@ class NativeProverIndex:
                 out[name] = (np.zeros((0, 8), np.uint64), np.zeros(0, np.uint8))
         return out
 
+    def lookup_table(self, table_id: int):
+        """kh_prover_index_lookup_table: {"first_row", "len", "is_runtime", "runtime_first", "keys", "values"} of the table with this id in an index
+        from create_lookup -- keys / values: DevViews of columns 0 and 1 of the combined table at first_row (values None for a one-column table), the
+        index's memory --, or None where the index has no such table (KH_E_NOTFOUND)."""
+        fr, ln, rf, rt = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        kd, vd = C.c_void_p(), C.c_void_p()
+        rc = _lib.kh_prover_index_lookup_table(self._h, table_id, C.byref(fr), C.byref(ln), C.byref(rt), C.byref(rf), C.byref(kd), C.byref(vd))
+        if rc == _CONSTANTS["KH_E_NOTFOUND"]:
+            return None
+        _check(rc)
+        return {"first_row": fr.value, "len": ln.value, "is_runtime": bool(rt.value), "runtime_first": rf.value, "keys": DevView(kd.value),
+                "values": DevView(vd.value) if vd.value else None}
+
     def lookup_column(self, block: str, k: int = 0):
         """kh_debug_lookup_column, downloaded: (elems, 4) limbs of column k of a block of LOOKUP_COLUMN_BLOCKS, or None where the index has none."""
         dev = U64P(); cnt = C.c_size_t(0)
@@ -1127,15 +1161,16 @@ class NativeProverIndex:
         """kh_witness_check (see witness_check)"""
         return witness_check(self, witness, witness_dev, flags)
 
-    def witness_check_full(self, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS):
-        """kh_witness_check_full (see witness_check_full)"""
-        return witness_check_full(self, witness, witness_dev, runtime, flags)
+    def witness_check_full(self, witness=None, witness_dev=None, runtime=None, flags: int = WITNESS_GATES | WITNESS_WIRES | WITNESS_LOOKUPS, runtime_dev=None):
+        """kh_witness_check_full / kh_witness_check_full_runtime_dev (see witness_check_full)"""
+        return witness_check_full(self, witness, witness_dev, runtime, flags, runtime_dev)
 
     def randomness_count(self, witness_on_host: bool) -> int:
         return _lib.kh_prove_randomness_count(self._h, int(witness_on_host))
 
-    def prove(self, witness=None, witness_dev=None, randomness=None, flags: int = PROVE_CHECK, prev=(), runtime=None):
-        """kh_prove_full (runtime: (k, 4) limbs, the runtime tables' second column).  witness: (15, rows, 4) limbs on the host, or witness_dev: DevBuf with the padded columns.  randomness:
+    def prove(self, witness=None, witness_dev=None, randomness=None, flags: int = PROVE_CHECK, prev=(), runtime=None, runtime_dev=None):
+        """kh_prove_full (runtime: (k, 4) limbs, the runtime tables' second column; or runtime_dev = (a DevBuf or view holding them, k):
+        kh_prove_full_runtime_dev, read in stream order).  witness: (15, rows, 4) limbs on the host, or witness_dev: DevBuf with the padded columns.  randomness:
         (k, 4) limbs in the reference's draw order, or None (the library draws from the OS).  prev: [(chals (k, 4) limbs, (xy (chunks, 8), inf
         (chunks,)))].  Returns ({section: limbs[, flags]}, {phase: seconds})."""
         pr = C.c_void_p()
@@ -1148,11 +1183,14 @@ class NativeProverIndex:
         cinf = np.ascontiguousarray(np.concatenate([np.asarray(cm[1], dtype=np.uint8).reshape(-1) for _, cm in prev])) if m else None
         cch = (C.c_size_t * max(m, 1))(*[np.asarray(cm[1]).reshape(-1).shape[0] for _, cm in prev])
         rtv = _c64(runtime, (-1, 4)) if runtime is not None else None
-        _check(_lib.kh_prove_full(self._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
-                                       C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rnd) if rnd is not None else None,
-                                       rnd.shape[0] if rnd is not None else 0, flags, _p64(chals) if m else None, rounds,
-                                       _p64(cxy) if m else None, _p8(cinf) if m else None, cch, m, _p64(rtv) if rtv is not None else None,
-                                       rtv.shape[0] if rtv is not None else 0, C.byref(pr)))
+        if runtime_dev is not None and runtime is not None:
+            raise ValueError("runtime values either on the host or on the device")
+        fn = _lib.kh_prove_full if runtime_dev is None else _lib.kh_prove_full_runtime_dev
+        rt_args = (_p64(rtv) if rtv is not None else None, rtv.shape[0] if rtv is not None else 0) if runtime_dev is None else (_ptr(runtime_dev[0]), runtime_dev[1])
+        _check(fn(self._h, _p64(w) if w is not None else None, w.shape[1] if w is not None else 0,
+                  C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rnd) if rnd is not None else None,
+                  rnd.shape[0] if rnd is not None else 0, flags, _p64(chals) if m else None, rounds,
+                  _p64(cxy) if m else None, _p8(cinf) if m else None, cch, m, *rt_args, C.byref(pr)))
         try:
             out = {}
             for name, sid in PROOF_SECTIONS.items():
