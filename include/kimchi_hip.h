@@ -521,6 +521,39 @@ int kh_lookup_witness_dev(int field, const uint64_t table_id[4] /* host, Montgom
                           uint64_t *witness_dev, size_t col_stride, size_t col_len,
                           uint64_t *out_values_dev /* nullable, n x 3 x 4 */, uint32_t *flags_dev, unsigned bit);
 
+/* ---- Witness advice on the device: the inverse of a value, a square root, the bits of a value (csrc/value_steps.hip) ----
+ * The witness values that no gate computes and the prover supplies: the inverse behind every is_zero / equals / division, the square root of a point
+ * decompression or an is_square, the bits behind range and comparison logic.  A VALUE step reads a dense device array and writes a dense device
+ * array: it writes no witness cell and has no placement; a KH_CELL_FIELD scatter, a generic row (l_dev / r_dev) or a gadget call consumes the result.
+ * Elements are 4 x u64 Montgomery limbs.  Inputs are assumed canonical (< p) and are not compared with p, like witness_dev: a non-canonical input
+ * gives an unspecified value for that element only, and every kernel ends whatever it is given (every loop has a constant trip bound).
+ * flags_dev, bit: the rules of the gadget calls -- bit `bit` (< 32) of a caller-zeroed device uint32_t (nullable) is set with one atomicOr per wave,
+ * and only by a wave in which some lane raises it; it is not touched otherwise.
+ * Vector steps: queued on the main stream of the calling thread's current context and ordered against every other call; NONE of them waits for the
+ * device (kh_batch_inversion_dev does, for its host turn).  n == 0 is KH_OK with nothing launched.  KH_E_INVALID with a kh_last_error text that names
+ * the call, before anything is launched and with nothing written: an unknown field, a null in_dev / out_dev with n > 0, a misaligned device pointer
+ * (16 bytes; 8 for KH_CELL_U64 data), an unknown format, num_bits outside 1..255 or above 64 x the format's words, n > 2^36 (the grid), a flag bit
+ * >= 32 or a misaligned flag word.  No pool scratch, no LDS, no per-lane scratch memory.
+ *
+ * kh_field_inverse_dev: out[i] = in[i]^-1.  A zero input gives zero AND raises the bit: that is the "inverse or zero" advice of is_zero, whose caller
+ * passes flags_dev = NULL (KH_STEP_NO_FLAG in a schedule).  out_dev == in_dev is allowed; any other overlap is the caller's responsibility.  Each
+ * lane inverts a run of 4 elements with Montgomery's trick and ONE Fermat chain: about 85 products per element instead of 330.
+ *
+ * kh_field_sqrt_dev: out[i] = the root ark-ff's Tonelli-Shanks returns for in[i] (SqrtPrecomputation::TonelliShanks; no sign normalisation -- the
+ * function the SRS generator uses).  Zero gives zero, a success that raises nothing.  A non-residue gives zero and raises the bit.
+ * out_is_square_dev (nullable): n elements, the Montgomery 1 or 0; zero counts as a square.  out_dev == in_dev is allowed.
+ *
+ * kh_field_bits_dev: in_dev holds n values in `format`, exactly as kh_witness_gather_dev delivers them: KH_CELL_FIELD a Montgomery element, whose
+ * canonical integer is taken; the other formats plain integers of 4, 2, 2 or 1 words.  out_dev receives num_bits x n elements, BIT-MAJOR: bit k
+ * (least significant first) of value i is element k n + i, the Montgomery 0 or 1 -- "bit k of every value" is a contiguous n-array that a generic
+ * row takes as l_dev / r_dev and a scatter puts into one column of cells.  A value >= 2^num_bits raises the bit; its low num_bits bits are written
+ * regardless.  out_dev must not overlap in_dev. */
+int kh_field_inverse_dev(int field, const uint64_t *in_dev, size_t n, uint64_t *out_dev, uint32_t *flags_dev, unsigned bit);
+int kh_field_sqrt_dev(int field, const uint64_t *in_dev, size_t n, uint64_t *out_dev,
+                      uint64_t *out_is_square_dev /* nullable */, uint32_t *flags_dev, unsigned bit);
+int kh_field_bits_dev(int field, const uint64_t *in_dev, int format, unsigned num_bits, size_t n,
+                      uint64_t *out_dev /* num_bits x n x 4 limbs */, uint32_t *flags_dev, unsigned bit);
+
 /* ---- Witness schedule: a circuit's gadget and wire steps compiled once, run per proof (csrc/witness_schedule.cpp, csrc/wiring.hip) ----
  * The circuit is fixed when its index is created and only the inputs change from proof to proof.  A schedule is the witness-side counterpart of
  * kh_prover_index_create: the list of direct calls above that writes a circuit's witness, described once.  kh_witness_schedule_create does everything
@@ -547,10 +580,15 @@ int kh_lookup_witness_dev(int field, const uint64_t table_id[4] /* host, Montgom
  *   KH_STEP_FF_ADD           kh_foreign_field_add_witness_dev     left_dev    right_dev -            out_dev         -          -         modulus[6]
  *   KH_STEP_FF_MUL           kh_foreign_field_mul_witness_dev     a_dev       b_dev     -            out_checks_dev  -          -         modulus[6]
  *   KH_STEP_LOOKUP           kh_lookup_witness_dev                keys_dev    table_keys_dev  table_values_dev  out_values_dev  -  table_len  table_id[4]
- * (* nullable as in the direct call; every out[] but the gather's is nullable; refs and fields a call does not have are ignored.)  flag_bit: the
+ *   KH_STEP_INVERSE          kh_field_inverse_dev                 in_dev      -         -            out_dev (req.)  -          -         -
+ *   KH_STEP_SQRT             kh_field_sqrt_dev                    in_dev      -         -            out_dev (req.)  out_is_square_dev  -  -
+ *   KH_STEP_BITS             kh_field_bits_dev                    in_dev      -         -            out_dev (req.)  -          num_bits  -          (format: the input's)
+ * (* nullable as in the direct call; every out[] but the gather's and the value steps' out[0] is nullable; refs and fields a call does not have are ignored.)  flag_bit: the
  * direct call's `bit` on the run's flags_dev, or KH_STEP_NO_FLAG for a step that passes flags_dev = NULL; calls without a flag ignore it.
  * An arena extent is n instances of the argument's size, except the Lookup step's in[1] and in[2], which are its table: table_len x 32 bytes
- * whatever n is (normally bound buffers: the pointers of kh_prover_index_lookup_table, the run's runtime values).
+ * whatever n is (normally bound buffers: the pointers of kh_prover_index_lookup_table, the run's runtime values), and the BITS step's out[0]:
+ * n x num_bits x 32 bytes.  The three value steps (kh_field_*_dev) write no witness cell and have no placement: rows, row0, row_stride and cells are
+ * ignored.  Each is one launch group and, like every step that is not a wire step, ends a fused group.
  * A run is equivalent to the direct calls issued in step order on the calling thread's current context: a vector step like them, queued on that
  * context's main stream and ordered against every other call -- a consumer (kh_witness_check, kh_prove) needs no kh_sync --, and it waits for the
  * device only where they do (once per slice in VarBaseMul / EndoMul steps).  The arena (arena_bytes, not zeroed), the chain steps' scratch and the
@@ -580,7 +618,8 @@ enum { KH_STEP_GATHER = 0, KH_STEP_SCATTER = 1, KH_STEP_GENERIC = 2, KH_STEP_POS
        KH_STEP_ENDOMUL = 6, KH_STEP_ENDOMUL_SCALAR = 7, KH_STEP_RANGE_CHECK = 8, KH_STEP_XOR = 9, KH_STEP_ROT64 = 10, KH_STEP_FF_ADD = 11,
        KH_STEP_FF_MUL = 12,
        /* 13 stays unassigned: it is refused as an unknown op (the tests of the schedule use it as the op that does not exist) */
-       KH_STEP_LOOKUP = 14 };
+       KH_STEP_LOOKUP = 14,
+       KH_STEP_INVERSE = 15, KH_STEP_SQRT = 16, KH_STEP_BITS = 17 };   /* the value steps: rows, row0, row_stride and cells are ignored */
 typedef struct kh_witness_ref kh_witness_ref_t;
 typedef struct kh_witness_step kh_witness_step_t;
 struct kh_witness_ref { int buf; size_t offset; };   /* buf >= 0: bufs_dev[buf] of the run; offset in bytes */
@@ -588,7 +627,7 @@ struct kh_witness_step {
     int op;                                   /* KH_STEP_* */
     size_t n;                                 /* instances; cells for GATHER / SCATTER */
     const uint32_t *rows; size_t row0, row_stride;   /* placement of a gadget step, exactly as in the direct call */
-    const uint32_t *cells; int format;        /* GATHER / SCATTER: n (row, column) pairs, KH_CELL_* */
+    const uint32_t *cells; int format;        /* GATHER / SCATTER: n (row, column) pairs, KH_CELL_*; BITS: the format of in[0] */
     unsigned param;                           /* num_bits | bits | rot | compact | half | table_len, as the direct call names it */
     int sign;                                 /* ForeignFieldAdd */
     const uint64_t *consts;                   /* host, copied at create: endo[4] | endo_scalar[4] | modulus[6] | coeffs[20] | table_id[4] | Poseidon none */

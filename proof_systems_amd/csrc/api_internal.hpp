@@ -160,6 +160,15 @@ size_t lookup_rows_slot_bytes(size_t table_len);
 int lookup_rows(Context& C, const uint64_t* table_id, const uint64_t* table_keys_dev, const uint64_t* table_values_dev, size_t table_len,
                 const uint64_t* keys_dev, size_t n, const WitnessPlace& at, uint64_t* out_values_dev, uint32_t* flags_dev, unsigned bit, uint32_t* slots_dev,
                 size_t scratch_bytes);
+// value_steps.hip: the launchers of kh_field_inverse_dev, kh_field_sqrt_dev and kh_field_bits_dev, queued on C.stream (arguments validated by the entry
+// points; n >= 1, n <= WAVE_BLOCK_MAX_N; format: a KH_CELL_* value; 1 <= num_bits <= 255).  The inverse's division of the work: a lane inverts a
+// run of INV_RUN elements with ONE Fermat chain (3 (INV_RUN - 1) products beside it), a launch has at most INV_MAX_BLOCKS blocks of one wave -- four
+// waves for each of the chip's 1024 SIMDs --, and from INV_MAX_BLOCKS * WAVE_BLOCK * INV_RUN elements on every lane works through several runs.
+static constexpr int INV_RUN = 4;
+static constexpr size_t INV_MAX_BLOCKS = 4096;
+int field_inverse(Context& C, int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
+int field_sqrt(Context& C, int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint64_t* out_is_square_dev, uint32_t* flags_dev, unsigned bit);
+int field_bits(Context& C, int field, const uint64_t* in_dev, int format, unsigned num_bits, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
 // A group of wire steps of a witness schedule in one launch (k_cell_moves): one resident 16-byte record per cell.  The dense side of every move is
 // the run's arena, `dense` words of 8 bytes from its start; flag: the step's bit, or CELL_MOVE_NO_FLAG.
 struct CellMove { uint32_t row, meta, dense_lo, dense_hi; };
@@ -203,8 +212,8 @@ inline int columns_validate(const char* call, const void* witness, size_t col_st
     return KH_OK;
 }
 
-// ------------------------------------------------------------------ one gadget or wire step with its arguments resolved (witness_steps.cpp): what a
-// direct call (kh_*_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev) builds from its arguments and a witness schedule
+// ------------------------------------------------------------------ one gadget, wire or value step with its arguments resolved (witness_steps.cpp): what a
+// direct call (kh_*_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev, kh_field_*_dev) builds from its arguments and a witness schedule
 // (witness_schedule.cpp) from a kh_witness_step_t.  Which argument of which call sits in in[] / out[] / param / consts is the table above KH_STEP_* in
 // include/kimchi_hip.h.  at.rows and cells are on the host while validating and on the device when launching; consts stays on the host.
 struct StepArgs {
@@ -226,6 +235,8 @@ struct OpInfo {
     bool tabled_cells;                        // the table is `cells` (2 n words), not `at.rows` (n words)
     int n_consts;                             // uint64_t words behind `consts`
     unsigned table_in = 0;                    // bit k: in[k] is a table of `param` elements of in_bytes[k], not one of them per instance (LOOKUP)
+    unsigned param_out = 0;                   // bit k: out[k] holds `param` elements of out_bytes[k] per instance (BITS)
+    bool value = false;                       // a value step: dense arrays in and out, no placement -- rows, row0, row_stride and cells are ignored
 };
 const OpInfo* step_op(int op);                // null: no such op
 // What a step computes on the host before it can be launched: a generic half's c_l c_r c_m c_c over -c_o (all zero when c_o = 0), ForeignFieldMul's

@@ -59,20 +59,6 @@ __device__ __forceinline__ Fe<F> scalar_prefix(const u64* s, unsigned num_bits, 
     return to_mont<F>(cond_sub_p<F>(t));
 }
 
-// inv<F> of field.cuh (a^(p-2), the same square-and-multiply ladder) inlined: the call of the __noinline__ one costs the kernel a stack frame in scratch memory
-template <class F>
-__device__ __forceinline__ Fe<F> inv_inlined(const Fe<F>& a) {
-    Fe<F> acc = a;
-#pragma unroll 1
-    for (int i = 253; i >= 0; i--) {
-        const int wd = i >> 5;
-        const u32 e = wd == 0 ? 0xffffffffu : wd == 1 ? F::P1 - 1u : wd == 2 ? F::P2 : wd == 3 ? F::P3 : wd == 7 ? P7W : 0u;
-        acc = sqr<F>(acc);
-        if ((e >> (i & 31)) & 1u) acc = mul<F>(acc, a);
-    }
-    return acc;
-}
-
 // ---------------------------------------------------------------------------------------------------------- CompleteAdd
 // complete_add_witness: cells 0..10 = x1 y1 x2 y2 x3 y3 inf same_x s inf_z x21_inv.  The denominators: x2 - x1 (generic), 2 y1 (same x), and
 // y2 - y1 as well for P + (-P) -- inverted together, 1 / (d1 d2) times the other one.

@@ -203,4 +203,20 @@ __device__ __noinline__ Fe<F> inv(const Fe<F>& a) {
     return acc;
 }
 
+// The same ladder inlined, for the kernels with one inversion on every lane's chain (k_complete_add of curve_gadgets.hip, k_field_inverse of
+// value_steps.hip): the call of the __noinline__ one costs the kernel a stack frame in scratch memory.  254 squarings and one multiplication per set bit below
+// bit 254 of p - 2: 330 products in Fp, 327 in Fq.
+template <class F>
+__device__ __forceinline__ Fe<F> inv_inlined(const Fe<F>& a) {
+    Fe<F> acc = a;
+#pragma unroll 1
+    for (int i = 253; i >= 0; i--) {
+        const int wd = i >> 5;
+        const u32 e = wd == 0 ? 0xffffffffu : wd == 1 ? F::P1 - 1u : wd == 2 ? F::P2 : wd == 3 ? F::P3 : wd == 7 ? P7W : 0u;
+        acc = sqr<F>(acc);
+        if ((e >> (i & 31)) & 1u) acc = mul<F>(acc, a);
+    }
+    return acc;
+}
+
 }  // namespace kh

@@ -5,14 +5,15 @@
 // products per point: 2^20 points in ~15 ms instead of seconds of host threads.
 #include "common.hpp"
 #include "field.cuh"
+#include "field_sqrt.cuh"
 #include "host_ec.hpp"
 #include "msm.hpp"
 
 namespace kh {
 
 struct SvdwParams {            // Montgomery limbs (8 x u32 each), base field of the curve
-    u32 fu[8], c1[8], s[8], c2[8], five[8], root[8];      // root = 5^T (2-adic root of unity)
-    u32 t_m1_d2[8];                                        // (T-1)/2, plain integer, T = (p-1) >> 32
+    u32 fu[8], c1[8], s[8], c2[8], five[8];
+    SqrtParams sqrt;                                       // what fe_sqrt needs (field_sqrt.cuh)
 };
 
 __device__ __forceinline__ u64 rotr64(u64 x, int n) { return (x >> n) | (x << (64 - n)); }
@@ -51,42 +52,6 @@ __device__ void blake2b_be32(u32 idx, uint8_t out[64]) {
 template <class F>
 __device__ __forceinline__ Fe<F> fe_from(const u32 w[8]) { Fe<F> r; for (int i = 0; i < 8; i++) r.v[i] = w[i]; return r; }
 
-// Tonelli-Shanks exactly as ark-ff / the oracle.  Returns false for a non-residue.
-template <class F>
-__device__ bool fe_sqrt(const Fe<F>& a, const SvdwParams& P, Fe<F>& out) {
-    if (a.is_zero()) { out = a; return true; }
-    const Fe<F> one = Fe<F>::one();
-    // w = a^((T-1)/2)
-    Fe<F> w = one;
-    int top = 255;
-    while (top > 0 && !((P.t_m1_d2[top >> 5] >> (top & 31)) & 1u)) top--;
-    for (int i = top; i >= 0; i--) {
-        w = sqr<F>(w);
-        if ((P.t_m1_d2[i >> 5] >> (i & 31)) & 1u) w = mul<F>(w, a);
-    }
-    Fe<F> x = mul<F>(a, w);
-    Fe<F> b = mul<F>(x, w);              // a^T
-    {                                    // residue test: b^(2^31) == 1
-        Fe<F> t = b;
-        for (int i = 0; i < 31; i++) t = sqr<F>(t);
-        if (!(t == one)) return false;
-    }
-    Fe<F> z = fe_from<F>(P.root);
-    int v = 32;
-    while (!(b == one)) {
-        int k = 0; Fe<F> t = b;
-        while (!(t == one)) { t = sqr<F>(t); k++; }
-        w = z;
-        for (int i = 0; i < v - k - 1; i++) w = sqr<F>(w);
-        z = sqr<F>(w);
-        b = mul<F>(b, z);
-        x = mul<F>(x, w);
-        v = k;
-    }
-    out = x;
-    return true;
-}
-
 template <class F>
 __global__ void __launch_bounds__(128)
 k_srs_generate(u32 start, size_t count, SvdwParams P, uint8_t* __restrict__ out_xy) {
@@ -110,7 +75,7 @@ k_srs_generate(u32 start, size_t count, SvdwParams P, uint8_t* __restrict__ out_
     Fe<F> x = Fe<F>::zero(), y = Fe<F>::zero();
     for (int k = 0; k < 3; k++) {
         Fe<F> rhs = add<F>(mul<F>(sqr<F>(xs[k]), xs[k]), five);
-        if (fe_sqrt<F>(rhs, P, y)) { x = xs[k]; break; }
+        if (fe_sqrt<F>(rhs, P.sqrt, y)) { x = xs[k]; break; }
     }
     x.store(out_xy + i * 64); y.store(out_xy + i * 64 + 32);
 }
@@ -122,13 +87,10 @@ int srs_generate_device(Context& C, int curve, size_t start, size_t count, void*
     auto put = [](u32 dst[8], const khost::fe& v) { memcpy(dst, &v, 32); };
     khost::fe five = {{5, 0, 0, 0}}; five = F.to_mont(five);
     khost::fe two = F.add(F.f.one, F.f.one), three = F.add(two, F.f.one);
-    khost::fe pm1 = F.f.p; pm1.l[0] -= 1;
-    khost::fe T, Tm1, tm1d2;
-    for (int i = 0; i < 4; i++) T.l[i] = (pm1.l[i] >> 32) | (i < 3 ? pm1.l[i + 1] << 32 : 0);
-    Tm1 = T; Tm1.l[0] -= 1;
-    for (int i = 0; i < 4; i++) tm1d2.l[i] = (Tm1.l[i] >> 1) | (i < 3 ? Tm1.l[i + 1] << 63 : 0);
+    P.sqrt = sqrt_params(F);
+    khost::fe root, tm1d2;
+    memcpy(&root, P.sqrt.root, 32); memcpy(&tm1d2, P.sqrt.t_m1_d2, 32);
     auto hpow = [&](const khost::fe& a, const khost::fe& e) { khost::fe acc = F.f.one, b = a; for (int i = 0; i < 256; i++) { if ((e.l[i >> 6] >> (i & 63)) & 1) acc = F.mul(acc, b); b = F.sqr(b); } return acc; };
-    khost::fe root = hpow(five, T);
     // host Tonelli-Shanks for the one constant sqrt(-3)
     auto hsqrt = [&](const khost::fe& a) {
         khost::fe z = root, w = hpow(a, tm1d2), x = F.mul(a, w), b = F.mul(x, w);
@@ -144,8 +106,7 @@ int srs_generate_device(Context& C, int curve, size_t start, size_t count, void*
     khost::fe s = hsqrt(F.neg(three));
     put(P.fu, F.add(F.f.one, five));                        // u^3 + 5 with u = 1
     put(P.c1, F.mul(F.sub(s, F.f.one), F.inv(two)));
-    put(P.s, s); put(P.c2, F.inv(three)); put(P.five, five); put(P.root, root);
-    memcpy(P.t_m1_d2, &tm1d2, 32);
+    put(P.s, s); put(P.c2, F.inv(three)); put(P.five, five);
     dim3 grid((unsigned)((count + 127) / 128));
     KH_FIELD_LAUNCH(fid, k_srs_generate<F>, grid, dim3(128), 0, C.stream, (u32)start, count, P, (uint8_t*)out_xy_dev);
     KH_HIP(hipStreamSynchronize(C.stream));

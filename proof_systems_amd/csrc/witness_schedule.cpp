@@ -52,15 +52,18 @@ int ref_validate(const char* call, const char* what, int k, const kh_witness_ref
 }
 
 // the refs of step `call` that its op has, against the arena (after the call's own list: n is known to be small enough for the extents, the format to be one).
-// An input that is a table (OpInfo::table_in: the Lookup step's two columns) extends over `param` elements, whatever n is.
+// An input that is a table (OpInfo::table_in: the Lookup step's two columns) extends over `param` elements, whatever n is; an output of `param`
+// elements per instance (OpInfo::param_out: the bits of BITS) over n * param of them.
 int refs_validate(const char* call, const OpInfo& op, const kh_witness_step_t& s, size_t arena_bytes, size_t n_bufs) {
-    const size_t cell_bytes = op.tabled_cells ? format_bytes(s.format) : 0;
+    const size_t cell_bytes = format_bytes(s.format);                // (for the refs whose size the format decides: GATHER / SCATTER, the input of BITS)
     int rc;
     for (int k = 0; k < op.n_in; k++)
         if ((rc = ref_validate(call, "in", k, s.in[k], op.in_bytes[k] ? op.in_bytes[k] : cell_bytes, (op.table_in >> k & 1) ? (size_t)s.param : s.n, arena_bytes, n_bufs)))
             return rc;
     for (int k = 0; k < op.n_out; k++)
-        if ((rc = ref_validate(call, "out", k, s.out[k], op.out_bytes[k] ? op.out_bytes[k] : cell_bytes, s.n, arena_bytes, n_bufs))) return rc;
+        if ((rc = ref_validate(call, "out", k, s.out[k], (op.out_bytes[k] ? op.out_bytes[k] : cell_bytes) * ((op.param_out >> k & 1) ? (size_t)s.param : 1), s.n, arena_bytes,
+                               n_bufs)))
+            return rc;
     return KH_OK;
 }
 
@@ -145,7 +148,7 @@ int kh_witness_schedule_create(int field, size_t col_len, const kh_witness_step_
             continue;
         }
         group.close();
-        const uint32_t* const src = wire ? s.cells : s.rows;
+        const uint32_t* const src = op.value ? nullptr : wire ? s.cells : s.rows;        // (a value step has no placement: its rows are ignored)
         if (src) {
             st.has_table = true; st.table = table.size();
             table.insert(table.end(), src, src + (wire ? 2 : 1) * s.n);

@@ -1,4 +1,4 @@
-// witness_steps.cpp -- the gadget and wire steps (kh_*_witness_dev, kh_lookup_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev): the one list of them.  A step is a
+// witness_steps.cpp -- the gadget, wire and value steps (kh_*_witness_dev, kh_lookup_witness_dev, kh_witness_gather_dev, kh_witness_scatter_dev, kh_field_*_dev): the one list of them.  A step is a
 // StepArgs record (api_internal.hpp); OPS[] says what each op takes, step_validate what it refuses, step_prepare what it computes on the host,
 // step_launch which launcher it runs.  A direct call fills the record from its arguments and goes through direct_step; a witness schedule
 // (witness_schedule.cpp) fills it from a kh_witness_step_t and goes through the same three functions, so the two cannot differ.
@@ -25,6 +25,9 @@ constexpr OpInfo OPS[] = {
     {"KH_STEP_FF_MUL", 2, 1, {48, 48, 0}, {144, 0}, false, 6},
     {nullptr, 0, 0, {0, 0, 0}, {0, 0}, false, 0},                   // 13: unassigned (include/kimchi_hip.h), refused as an unknown op
     {"KH_STEP_LOOKUP", 3, 1, {96, 32, 32}, {96, 0}, false, 4, 6},    // in[1], in[2]: the table's two columns, `param` elements each
+    {"KH_STEP_INVERSE", 1, 1, {32, 0, 0}, {32, 0}, false, 0, 0, 0, true},
+    {"KH_STEP_SQRT", 1, 2, {32, 0, 0}, {32, 32}, false, 0, 0, 0, true},
+    {"KH_STEP_BITS", 1, 1, {0, 0, 0}, {32, 0}, false, 0, 0, 1, true},    // in[0]: the format decides; out[0]: `param` = num_bits elements per instance
 };
 constexpr int N_OPS = sizeof(OPS) / sizeof(OPS[0]);
 
@@ -44,19 +47,32 @@ int place_validate(const char* call, const WitnessPlace& at, size_t n, size_t co
     return KH_OK;
 }
 struct GadgetPtr { const char* name; const void* p; bool required; unsigned align = 16; };
-// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
-int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, const StepArgs& a, size_t col_len, size_t inst_rows) {
+// the field, null / misaligned device pointers
+int pointers_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, size_t n) {
     KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
     for (const GadgetPtr& p : ptrs) {
-        KH_REQUIRE(p.p || !p.required || a.n == 0, "%s: null %s", call, p.name);
+        KH_REQUIRE(p.p || !p.required || n == 0, "%s: null %s", call, p.name);
         KH_REQUIRE((((uintptr_t)p.p) & (p.align - 1)) == 0, "%s: %s must be %u-byte aligned", call, p.name, p.align);
     }
+    return KH_OK;
+}
+// what the gadget calls refuse alike: the field, null / misaligned device pointers, a placement that does not hold
+int gadget_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, const StepArgs& a, size_t col_len, size_t inst_rows) {
+    int rc = pointers_validate(call, field, ptrs, a.n);
+    if (rc) return rc;
     return place_validate(call, a.at, a.n, col_len, inst_rows);
 }
 // a flag word that is misaligned or a bit that is not one
 int flag_validate(const char* call, const StepArgs& a) {
     KH_REQUIRE(a.bit < 32 && (((uintptr_t)a.flags) & 3) == 0, "%s: flag bit %u of a word at %p", call, a.bit, (const void*)a.flags);
     return KH_OK;
+}
+// what the value calls refuse alike: the same pointer checks with no placement, more elements than a grid of one lane each takes, the flag
+int value_validate(const char* call, int field, std::initializer_list<GadgetPtr> ptrs, const StepArgs& a) {
+    int rc = pointers_validate(call, field, ptrs, a.n);
+    if (rc) return rc;
+    KH_REQUIRE(a.n <= WAVE_BLOCK_MAX_N, "%s: %zu elements overflow the grid", call, a.n);
+    return flag_validate(call, a);
 }
 // what the five limb gadgets refuse alike after their own arguments: gadget_validate's list, more lanes (one per instance and row) than a grid takes, the
 // flag
@@ -162,6 +178,19 @@ int step_validate(const char* call, int field, size_t col_len, const StepArgs& a
         KH_REQUIRE(n <= WAVE_BLOCK_MAX_N / 3, "%s: %zu instances of 3 lookups overflow the grid", call, n);
         return flag_validate(call, a);
     }
+    case KH_STEP_INVERSE:
+        return value_validate(call, field, {{"in_dev", in[0], true}, {"out_dev", out[0], true}}, a);
+    case KH_STEP_SQRT:
+        return value_validate(call, field, {{"in_dev", in[0], true}, {"out_dev", out[0], true}, {"out_is_square_dev", out[1], false}}, a);
+    case KH_STEP_BITS: {
+        // the field and the format first: the format decides the input's alignment and how many bits it has
+        KH_REQUIRE(field == KH_FIELD_FP || field == KH_FIELD_FQ, "%s: unknown field id %d", call, field);
+        KH_REQUIRE(a.format >= KH_CELL_FIELD && a.format <= KH_CELL_U64, "%s: unknown cell format %d", call, a.format);
+        const unsigned words = a.format == KH_CELL_FIELD || a.format == KH_CELL_INT256 ? 4 : a.format == KH_CELL_U64 ? 1 : 2;
+        KH_REQUIRE(a.param >= 1 && a.param <= 255, "%s: num_bits %u is not from 1 to 255", call, a.param);
+        KH_REQUIRE(a.param <= 64 * words, "%s: num_bits %u is more than the %u bits of cell format %d", call, a.param, 64 * words, a.format);
+        return value_validate(call, field, {{"in_dev", in[0], true, a.format == KH_CELL_U64 ? 8u : 16u}, {"out_dev", out[0], true}}, a);
+    }
     }
     set_error("%s: unknown op %d", call, a.op);
     return KH_E_INVALID;
@@ -201,6 +230,9 @@ int step_launch(Context& C, int field, const StepArgs& a, const StepPrepared& pr
     case KH_STEP_FF_ADD: return ff_add_rows(C, field, a.consts, in0, in1, a.sign, a.n, a.at, out0, a.flags, a.bit);
     case KH_STEP_FF_MUL: return ff_mul_rows_prepared(C, field, *prepared.ff_mul, in0, in1, a.n, a.at, out0, a.flags, a.bit);
     case KH_STEP_LOOKUP: return lookup_rows(C, a.consts, in1, in2, a.param, in0, a.n, a.at, out0, a.flags, a.bit, (uint32_t*)scratch_dev, scratch_bytes);
+    case KH_STEP_INVERSE: return field_inverse(C, field, in0, a.n, out0, a.flags, a.bit);
+    case KH_STEP_SQRT: return field_sqrt(C, field, in0, a.n, out0, out1, a.flags, a.bit);
+    case KH_STEP_BITS: return field_bits(C, field, in0, a.format, a.param, a.n, out0, a.flags, a.bit);
     }
     set_error("step_launch: unknown op %d", a.op);
     return KH_E_INVALID;
@@ -319,6 +351,17 @@ int kh_lookup_witness_dev(int field, const uint64_t table_id[4], const uint64_t*
     return direct_step("kh_lookup_witness_dev", field, col_len,
                        {KH_STEP_LOOKUP, n, {rows, row0, row_stride, witness_dev, col_stride}, {keys_dev, table_keys_dev, table_values_dev}, {out_values_dev}, len,
                         table_id, flags_dev, bit});
+}
+
+// ---------------------------------------------------------------------------------- advice values (kernels in value_steps.hip): no witness, no placement
+int kh_field_inverse_dev(int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
+    return direct_step("kh_field_inverse_dev", field, 0, {KH_STEP_INVERSE, n, {}, {in_dev}, {out_dev}, 0, nullptr, flags_dev, bit});
+}
+int kh_field_sqrt_dev(int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint64_t* out_is_square_dev, uint32_t* flags_dev, unsigned bit) {
+    return direct_step("kh_field_sqrt_dev", field, 0, {KH_STEP_SQRT, n, {}, {in_dev}, {out_dev, out_is_square_dev}, 0, nullptr, flags_dev, bit});
+}
+int kh_field_bits_dev(int field, const uint64_t* in_dev, int format, unsigned num_bits, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit) {
+    return direct_step("kh_field_bits_dev", field, 0, {KH_STEP_BITS, n, {}, {in_dev}, {out_dev}, num_bits, nullptr, flags_dev, bit, 0, nullptr, format});
 }
 
 // ---------------------------------------------------------------------------------- wires between the gadgets (kernels in wiring.hip)

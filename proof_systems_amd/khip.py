@@ -869,12 +869,30 @@ def lookup_witness_dev(field: int, table_id, table_keys, table_values, table_len
                                       _ptr(witness), col_stride, col_len, _ptr(out_values), _ptr(flags), bit))
 
 
+def field_inverse_dev(field: int, values, n: int, out, flags=None, bit: int = 0):
+    """kh_field_inverse_dev: out[i] = values[i]^-1 for n Montgomery elements (DevBufs or views; out may be `values`); a zero gives zero and sets the flag
+    -- the "inverse or zero" advice of is_zero, whose caller passes no flags."""
+    _check(_lib.kh_field_inverse_dev(field, _ptr(values), n, _ptr(out), _ptr(flags), bit))
+
+
+def field_sqrt_dev(field: int, values, n: int, out, out_is_square=None, flags=None, bit: int = 0):
+    """kh_field_sqrt_dev: out[i] = the square root ark-ff's Tonelli-Shanks returns for values[i] (out may be `values`); zero gives zero; a non-residue
+    gives zero and sets the flag.  out_is_square (nullable): n elements, the Montgomery 1 or 0."""
+    _check(_lib.kh_field_sqrt_dev(field, _ptr(values), n, _ptr(out), _ptr(out_is_square), _ptr(flags), bit))
+
+
+def field_bits_dev(field: int, values, fmt: int, num_bits: int, n: int, out, flags=None, bit: int = 0):
+    """kh_field_bits_dev: the low num_bits bits of n values in the format `fmt` (CELL_WORDS[fmt] uint64 each, as witness_gather_dev delivers them) as
+    Montgomery 0 / 1, bit-major: bit k of value i is element k * n + i of out (num_bits x n elements); the flag is set by a value >= 2^num_bits."""
+    _check(_lib.kh_field_bits_dev(field, _ptr(values), fmt, num_bits, n, _ptr(out), _ptr(flags), bit))
+
+
 WitnessRefC, WitnessStepC = _STRUCTURES["kh_witness_ref_t"], _STRUCTURES["kh_witness_step_t"]
 REF_NONE, REF_ARENA, STEP_NO_FLAG = _CONSTANTS["KH_REF_NONE"], _CONSTANTS["KH_REF_ARENA"], _CONSTANTS["KH_STEP_NO_FLAG"]
 (STEP_GATHER, STEP_SCATTER, STEP_GENERIC, STEP_POSEIDON, STEP_COMPLETE_ADD, STEP_VARBASEMUL, STEP_ENDOMUL, STEP_ENDOMUL_SCALAR, STEP_RANGE_CHECK, STEP_XOR,
- STEP_ROT64, STEP_FF_ADD, STEP_FF_MUL, STEP_LOOKUP) = (_CONSTANTS["KH_STEP_" + _n] for _n in (
+ STEP_ROT64, STEP_FF_ADD, STEP_FF_MUL, STEP_LOOKUP, STEP_INVERSE, STEP_SQRT, STEP_BITS) = (_CONSTANTS["KH_STEP_" + _n] for _n in (
      "GATHER", "SCATTER", "GENERIC", "POSEIDON", "COMPLETE_ADD", "VARBASEMUL", "ENDOMUL", "ENDOMUL_SCALAR", "RANGE_CHECK", "XOR", "ROT64", "FF_ADD", "FF_MUL",
-     "LOOKUP"))
+     "LOOKUP", "INVERSE", "SQRT", "BITS"))
 _STEP_FIELDS = ("op", "n", "rows", "row0", "row_stride", "cells", "format", "param", "sign", "consts", "in", "out", "flag_bit")     # kh_witness_step_t's order
 
 
@@ -890,7 +908,8 @@ class WitnessSchedule:
     the fields of kh_witness_step_t (or a tuple in their order: op, n, rows, row0, row_stride, cells, format, param, sign, consts, in, out, flag_bit);
     what a dict leaves out is 0 / None, n defaults to the number of cells, flag_bit to STEP_NO_FLAG.  in / out: lists of refs -- None, (REF_ARENA,
     offset), (index of a bound buffer, offset).  consts: uint64 limbs as the direct call takes them (STEP_LOOKUP: the table id's 4 Montgomery limbs, with
-    param = table_len and in = [keys, table keys, table values]), or the modulus as an int for the foreign-field steps."""
+    param = table_len and in = [keys, table keys, table values]), or the modulus as an int for the foreign-field steps.  The value steps (STEP_INVERSE,
+    STEP_SQRT, STEP_BITS) take n, in = [values], out = [result] (STEP_SQRT: [root, is_square or None]) and, for STEP_BITS, format and param = num_bits."""
 
     def __init__(self, handle, n_bufs: int, col_len: int):
         self.handle, self.n_bufs, self.col_len = handle, n_bufs, col_len
