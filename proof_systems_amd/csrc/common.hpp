@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/kimchi_hip.h"
+#include "msm_plan.hpp"
 
 namespace kh {
 
@@ -108,12 +109,9 @@ struct MsmJob {
     const uint64_t* scalars = nullptr;
     size_t n = 0, k = 0;
     int mont = 0, curve = 0;
-    // what msm_finish folds and how the job ends
-    int W = 0, c = 0, precomp = 0, planes = 0, plane_shift[2] = {0, 0};
-    int wide_lo = 0;                   // wide windows: bits of the low bucket digit (0: the narrow path); msm_finish folds two marginal groups per MSM
-    size_t ngroups = 0;                // 0: nothing was launched (n == 0 or k == 0), the results are k identities
+    // every decision of msm_enqueue (msm_plan.hpp): msm_finish folds by it.  plan.ngroups == 0: nothing was launched (n == 0 or k == 0), the results are k identities
+    MsmPlan plan;
     bool done_by_flag = false;         // the last kernel stores the slot's launch count into done_flag (MsmSlot)
-    bool fused = false, spread = false;    // ran the one-launch sort / under MSM_SPREAD_SCALARS
     bool spread_rerun = false;         // set by msm_finish: the spread hint did not hold and the job was re-run without it
 };
 
@@ -217,13 +215,21 @@ int exclusive_scan_u32(const uint32_t* in, uint32_t* out, size_t n, DevBuf& tmp,
 
 }  // namespace kh
 
-// How a field id selects a kernel instantiation, for every launch that is keyed by the FIELD (the MSM side is keyed by the curve: msm.hip, rebase.hip,
-// lagrange.hip).  KERNEL names the instantiation with F for the field's parameters, in parentheses when it holds a comma:
+// How a field id selects a kernel instantiation, for every launch that is keyed by the FIELD.  KERNEL names the instantiation with F for the field's
+// parameters, in parentheses when it holds a comma:
 //     KH_FIELD_LAUNCH(field, k_lincomb<F>, grid, block, 0, s, args...);      KH_FIELD_LAUNCH(field, (k_chain<F, true>), ...);
 // The arguments are written once; a launch that fails returns KH_E_DEVICE from the calling function, like KH_HIP.
 #define KH_FIELD_LAUNCH(field, KERNEL, grid, block, lds, stream, ...)                                                        \
     do {                                                                                                                     \
         if ((field) == KH_FIELD_FP) { using F = kh::FpParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); } \
         else { using F = kh::FqParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); }               \
+        KH_HIP(hipGetLastError());                                                                                           \
+    } while (0)
+// The same for a launch keyed by the CURVE (the MSM side): F is the curve's BASE field, Fq for Vesta and Fp for Pallas (msm.hip: VestaCfg / PallasCfg).
+// (rebase.hip and lagrange.hip dispatch whole functions templated on both fields instead.)
+#define KH_CURVE_LAUNCH(curve, KERNEL, grid, block, lds, stream, ...)                                                        \
+    do {                                                                                                                     \
+        if ((curve) == KH_CURVE_VESTA) { using F = kh::FqParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); } \
+        else { using F = kh::FpParams; hipLaunchKernelGGL((KERNEL), grid, block, lds, stream, __VA_ARGS__); }               \
         KH_HIP(hipGetLastError());                                                                                           \
     } while (0)

@@ -283,7 +283,7 @@ __device__ __forceinline__ bool add29(Acc29<F>& a, const Acc29<F>& b) {
 
 // A lazy XYZZ point in memory ("B29 record"): 36 words x | y | zz | zzz of nine limbs each, 144 bytes, 16-byte aligned.  The identity is the
 // record whose zz limbs are all zero (what to29 makes of the canonical identity; a lazy sum is never congruent to it, see add29).
-static constexpr size_t B29_BYTES = 144;
+// (B29_BYTES: msm_plan.hpp, with the sizes the MSM driver reserves by it)
 template <class F>
 __device__ __forceinline__ Acc29<F> load_b29(const uint8_t* rec) {
     const uint4* q = (const uint4*)rec;

@@ -446,9 +446,7 @@ int ipa_fold_points(Context& C, int curve, const uint64_t* g_lo, const uint64_t*
     KH_HIP(hipMemcpyAsync(du, &uu, 32, hipMemcpyHostToDevice, s));
     KH_HIP(hipStreamSynchronize(s));                       // uu is a stack buffer
     dim3 grid((unsigned)((n + 127) / 128));
-    if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_fold_points<FqParams>), grid, dim3(128), 0, s, dlo, dhi, du, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
-    else hipLaunchKernelGGL((k_fold_points<FpParams>), grid, dim3(128), 0, s, dlo, dhi, du, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
-    KH_HIP(hipGetLastError());
+    KH_CURVE_LAUNCH(curve, k_fold_points<F>, grid, dim3(128), 0, s, dlo, dhi, du, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
     KH_HIP(hipMemcpyAsync(out_xy, g_ipa_b.p, n * 64, hipMemcpyDeviceToHost, s));
     KH_HIP(hipMemcpyAsync(out_inf, g_ipa_c.p, n, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));
@@ -469,9 +467,7 @@ int ipa_fold_points_endo(Context& C, int curve, const uint64_t* g_lo, const uint
     KH_HIP(hipMemcpyAsync(deq, &eq, 32, hipMemcpyHostToDevice, s));
     KH_HIP(hipStreamSynchronize(s));
     dim3 grid((unsigned)((n + 127) / 128));
-    if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_fold_points_endo<FqParams>), grid, dim3(128), 0, s, dlo, dhi, chal[0], chal[1], deq, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
-    else hipLaunchKernelGGL((k_fold_points_endo<FpParams>), grid, dim3(128), 0, s, dlo, dhi, chal[0], chal[1], deq, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
-    KH_HIP(hipGetLastError());
+    KH_CURVE_LAUNCH(curve, k_fold_points_endo<F>, grid, dim3(128), 0, s, dlo, dhi, chal[0], chal[1], deq, n, g_ipa_b.as<uint8_t>(), g_ipa_c.as<uint8_t>());
     KH_HIP(hipMemcpyAsync(out_xy, g_ipa_b.p, n * 64, hipMemcpyDeviceToHost, s));
     KH_HIP(hipMemcpyAsync(out_inf, g_ipa_c.p, n, hipMemcpyDeviceToHost, s));
     KH_HIP(hipStreamSynchronize(s));

@@ -35,6 +35,7 @@
 #include "field29.cuh"
 #include "host_ec.hpp"
 #include "msm.hpp"
+#include "msm_plan.hpp"          // the constants and geometry structs the kernels share with the plan; msm_plan()
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -290,16 +291,6 @@ __global__ void k_digits(const u64* __restrict__ scalars, const uint8_t* __restr
 }
 
 // ------------------------------------------------------------------------------------ 2 histogram
-struct SortGeom {
-    size_t n;       // scalars per MSM
-    u32 nb;         // buckets per group = 2^(c-1)
-    int S;          // slices per (window, msm)
-    int W;          // windows
-    int precomp;    // 1: all windows of an MSM share one bucket group
-    size_t pt_stride;   // precomp: points per window table
-    size_t pt_offset;   // first basis point used
-    size_t pt_batch;    // index step between the bases of consecutive MSMs of a batch (0: shared basis)
-};
 __device__ __forceinline__ void geom_ids(const SortGeom& g, int s, int w, int j, size_t& q, int& Sq, int& sigma) {
     if (g.precomp) { q = (size_t)j; Sq = g.W * g.S; sigma = w * g.S + s; }
     else { q = (size_t)j * g.W + w; Sq = g.S; sigma = s; }
@@ -366,7 +357,6 @@ __global__ void k_scatter(const int32_t* __restrict__ digits, SortGeom g, const 
 //   pass B  one block per partition (~64 K records, read twice from the L2): histogram of its 128 buckets, off[], then the
 //           final entries through 128 LDS cursors into a 256 KB window.
 // No per-slice histogram matrix, no key-total pass, no global scan over the keys.  Needs n <= 2^20 and W <= 16 for the record.
-static constexpr int PART_T = 1024, PART_P = 256, PART_LOW = 7;
 // LDS counter increment with wave aggregation for the skewed case: when every active lane of the wave targets the SAME counter (the
 // reference's benchmark witness puts n - 10 of n scalars into one bucket: 65,526 same-address LDS atomics serialise, 228 us in
 // k_part_sort for 15 such columns) ONE lane adds the lane count and the others take consecutive positions; a mixed wave pays one
@@ -473,7 +463,6 @@ k_part_sort(const u32* __restrict__ mid, const u32* __restrict__ PO, u32 nblk, u
     }
 }
 // ------------------------------------------------------------------------------------ tasks
-static constexpr u32 MAX_K = 256;           // upper bound of the task length (length bins of the task ordering)
 // K (entries per task) is chosen HERE from the actual number of entries off[nkeys]: zero digits
 // produce no entry, and the reference's own benchmark witness is almost all ones (one non-zero
 // digit per scalar) -- sizing K from the n*W upper bound left the chip 5 % occupied on it.
@@ -483,7 +472,6 @@ static constexpr u32 MAX_K = 256;           // upper bound of the task length (l
 //     cost(K) = ceil(blocks(K) / CUs) * min(K, m + 2.3 sqrt(m)) + 2 * tasks-per-bucket(K),   bucket sizes ~ Poisson(m), m = entries / buckets
 // (the second term: every further task of a bucket is one more partial for the bucket sums).  The host tabulates argmin_K over m in quarter octaves
 // for the launch's bucket count (KTab, 0 = no opinion: a big job, where only the total matters); the device looks m up from the ACTUAL entry count.
-struct KTab { uint8_t k[48]; };
 __device__ __forceinline__ u32 pick_K(u32 total, u32 room, u32 kmin, const KTab& tab, u32 nkeys) {
     u32 K = (total + room - 1) / room;
     u32 lo = kmin;
@@ -571,13 +559,6 @@ k_len_rank(const u32* __restrict__ off, const u32* __restrict__ nt, size_t nkeys
 // contiguous chunk of group j's digit matrix [w][i]; its LDS histogram is one "slice" of the deterministic counting sort, the
 // keys are scanned with one (thread-contiguous keys, block scan, block totals) pass per barrier, and the same block scatters its
 // chunk.  Outputs are exactly those of the multi-launch path (off / toff / entries, empty hand-over and big-bucket lists).
-struct FusedGeom {
-    u32 n, nb, W, k, bpg, split, sub, kpt, nkeys, room, kmin;     // sub = nb / split buckets per block
-    KTab ktab;
-    size_t pt_stride, pt_offset, pt_batch;
-};
-static constexpr int FUSED_T = 1024, FUSED_KPT = 2, FUSED_G = 16, FUSED_B = 64;      // chunks per job <= FUSED_G, blocks <= FUSED_B
-static constexpr int FUSED_V = 17, FUSED_C = 16;        // int4's of digits / cursors per thread (registers)
 // Bounded: the barrier assumes every block of the launch is resident.  Inside one process that holds (64 blocks of 64 KB LDS, two per
 // CU, even with all four pipeline slots in flight); with several PROCESSES on one GPU it need not, and resident blocks would spin on
 // peers that cannot be scheduled.  After `limit` ticks of the 100 MHz wall clock (or when another block has given up) the barrier
@@ -808,7 +789,6 @@ k_sort_fused(const int32_t* __restrict__ digits, FusedGeom g, u32* __restrict__ 
 // BLOCK instead (16 bits: a block reads a contiguous run of <= 65,536 digits of the [w][i] matrix): pass B knows from the scanned block matrix PO
 // which block wrote the record it is looking at (the partition's run is the concatenation of the blocks' runs, in block order) and rebuilds
 // (window, point) from block start + local position.
-static constexpr u32 PART2_MAXLOW = 11, PART2_MAXPASS = 8;  // (array bound; the launch's max_pass decides: 2 by default)
 __global__ void __launch_bounds__(PART_T)
 k_part2_scatter(const int32_t* __restrict__ digits, u32 tot_e, u32 nblk, u32 low, const u32* __restrict__ PO, u32* __restrict__ mid, u32* __restrict__ xlist, u32* __restrict__ big) {
     KH_HIGH_PRIO();
@@ -839,7 +819,6 @@ k_part2_scatter(const int32_t* __restrict__ digits, u32 tot_e, u32 nblk, u32 low
 // consecutive ranks of a partition side by side (measured: og = 1 / 4 / 16 / 64 / 2048 -> 923 / 843 / 795 / 819 / 1710 us of accumulation).  The extra
 // chunks of split buckets go to xlist as (key, chunk) pairs ([0] = their number), the split buckets themselves to slist ([1] = their number);
 // empty buckets get their identity record here.
-struct WideTasks { u32 room, kmin, nkeys; KTab ktab; };
 __global__ void __launch_bounds__(PART_T)
 k_part2_sort(const u32* __restrict__ mid, const u32* __restrict__ PO, u32 nblk, u32 low, u32 nb, u32 tot_e, u32 n, size_t pt_stride, size_t pt_offset,
              size_t pt_batch, u32 last_group, size_t total_idx, WideTasks ta, u32* __restrict__ off, u32* __restrict__ entries,
@@ -1162,7 +1141,6 @@ __device__ __forceinline__ void wide_task_exact(u32 key, u32 jt, const u32* __re
 }
 // Thread per bucket.  Launched with enough dynamic LDS to hold the kernel to THREE blocks per CU (it is VALU-bound from
 // three waves per SIMD on; the fourth only keeps the neighbouring jobs' sort and reduction kernels off the CU: 886-930 -> 940-1000 Mscalar/s pipelined).
-static constexpr u32 WIDE_XB = 32, WIDE_HOT_NT = 16;       // (a split bucket with more partials than WIDE_HOT_NT is summed by many waves)
 template <class BF>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(112), amdgpu_waves_per_eu(4, 4)))
 k_acc_wide29(const u32* __restrict__ entries, const u32* __restrict__ off, const u32* __restrict__ toff, const u32* __restrict__ order, u32 nkeys,
@@ -1195,7 +1173,6 @@ k_acc_wide_rest(const u32* __restrict__ entries, const u32* __restrict__ off, co
 // kernel argument: 16 for large problems (throughput), 4 for small ones (shorter dependent chain)
 // hot-bucket bookkeeping in `big`: [0] = #big buckets, [1] = #chunk items, then four arrays of `cap` words:
 // bigkey[], bigcbase[] (first chunk item of that bucket), itemkey[], itemj[]
-static constexpr u32 CHUNK = 128;            // partials per chunk item = 8 per quad of a wave (cooperative additions)
 template <class BF>
 __global__ void __launch_bounds__(256)
 k_bucket_sum(const u32* __restrict__ toff, size_t nkeys, const uint8_t* __restrict__ partial,
@@ -1315,7 +1292,6 @@ k_reduce_seg(const uint8_t* __restrict__ buckets, u32 nb, u32 m, size_t ngroups,
 }
 // sum of `count` XYZZ records per group, two launches: level 1 = blocks of 256 threads x SUM_PER_T
 // records (coalesced strided loads, shuffle tree, LDS across the 4 waves), level 2 = one block per group.
-static constexpr u32 SUM_PER_T = 2, SUM_BLK = 256 * SUM_PER_T;
 template <class BF>
 __device__ __forceinline__ Xyzz<BF> block_sum(Xyzz<BF> acc, u32* sh) {
     for (int d = 32; d >= 1; d >>= 1) { Xyzz<BF> o = shfl_down<BF>(acc, d); acc = add<BF>(acc, o); }
@@ -1372,7 +1348,6 @@ k_sum_final(const uint8_t* __restrict__ in, u32 count, uint8_t* __restrict__ out
 // sums of nb / 32 buckets each (k_marginals: 4 sequential additions + the block tree), the digit weights then need
 // 5-bit ladders on 3 x 32 points only (k_marginal_fin), and the host folds the three results with f0 + f1 doublings.
 // Chain ~380 field products instead of ~630 (15-bit ladder per bucket + two tree levels), and a tenth of the work.
-struct MargGeom { u32 nb; u32 sh[3]; u32 wd[3]; };
 template <class BF>
 __global__ void __launch_bounds__(256)
 k_marginals(const uint8_t* __restrict__ buckets, MargGeom g, uint8_t* __restrict__ out) {
@@ -1603,7 +1578,6 @@ k_marginal_fin_q(const uint8_t* __restrict__ marg, MargGeom g, uint8_t* __restri
 //                      per lane, then 4 or 3 lane-cooperative additions (coop.cuh).  Output: 2 x 2^lo wire records per MSM laid out as TWO bucket groups of 2^lo
 //                      buckets for k_marginals_q / k_marginal_fin_q -- group 0 holds H_a at slot a - 1 (weight a; H_0 has weight 0 and is
 //                      dropped, slots >= 2^hi - 1 are the identity), group 1 holds L_b at slot b.
-struct WideGeom { u32 nb, lo, hi, rlog, flog; };      // buckets, the two digit widths, log2 of the chunk (level one) and of the run of chunks (level two)
 // split buckets only (slist: pass B's list of buckets with more than one task; count in xlist[1]), ONE launch (round 6; until then this kernel listed the hot
 // buckets for k_bucket_chunk / k_bucket_big and k_big_to29 converted their sums: three more empty dependent launches for unskewed scalars).
 //   (1) a thread sums a bucket of up to SMALL_NT partials by itself (2^22 uniform scalars: 16 K buckets of two partials);
@@ -1832,94 +1806,15 @@ static std::atomic<u32>& sort_staging_cell(int i) {
 void msm_set_sort_staging(unsigned entries, unsigned max_passes) { sort_staging_cell(0).store(entries); sort_staging_cell(1).store(max_passes); }
 size_t msm_wide_min_n() { const size_t v = wide_min_n_cell().load(); return v ? v : ~(size_t)0; }
 void msm_set_wide_min_n(size_t n) { wide_min_n_cell().store(n); }
-int msm_pick_window(size_t n) {
-    int lg = 0; while (((size_t)1 << (lg + 1)) <= n) lg++;
-    int c = lg - 3;
-    if (c < 4) c = 4;
-    if (c > 16) c = 16;
-    return c;
-}
-
-// the task-length table of pick_K for a launch with `nkeys` buckets on `cus` compute units (cached per bucket count)
-static KTab task_length_table(size_t nkeys, u32 cus) {
-    static std::mutex mu;
-    static std::map<std::pair<size_t, u32>, KTab> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find({nkeys, cus});
-    if (it != cache.end()) return it->second;
-    KTab t{};
-    for (int idx = 0; idx < 48; idx++) {
-        const double m = pow(2.0, (idx - 8) / 4.0);
-        std::vector<double> p(1, exp(-m));                                   // Poisson(m), up to the far tail
-        for (int c = 1; c < (int)(m + 12 * sqrt(m) + 24); c++) p.push_back(p.back() * m / c);
-        auto tasks_per_bucket = [&](int K) { double s = 0; for (size_t c = 1; c < p.size(); c++) s += p[c] * (double)((c + K - 1) / K); return s; };
-        if (ceil(ceil((double)nkeys * tasks_per_bucket(8) / 256.0) / cus) > 6) { t.k[idx] = 0; continue; }     // a big job: the total decides
-        double best = 1e300; int bk = 8;
-        for (int K = 4; K <= 32; K++) {
-            const double tpb = tasks_per_bucket(K);
-            const double blocks = ceil((double)nkeys * tpb / 256.0);
-            const double len = std::min<double>(K, m + 2.3 * sqrt(m));
-            const double cost = ceil(blocks / cus) * len + 2.0 * tpb;
-            if (cost < best - 1e-9) { best = cost; bk = K; }
-        }
-        t.k[idx] = (uint8_t)bk;
-    }
-    cache[{nkeys, cus}] = t;
-    return t;
-}
-
-template <class CFG>
-static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t offset, const u64* scalars_dev, size_t n, size_t k,
-                         int mont, int curve, int flags) {
-    typedef typename CFG::Base BF; typedef typename CFG::Scalar SF;
+// Everything a job of plan P needs on slot C before its first launch, sized from the plan: the workspaces, the pinned staging, the fused sort's barrier
+// words, the host-visible abort words and the one-time kernel attributes.  flag_on: completion by flag is on for this job (the plan wants it AND the slot
+// could allocate its coherent words).
+static int msm_reserve(Context& Ctx, MsmSlot& C, const MsmPlan& P, bool& flag_on) {
     hipStream_t s = C.stream;
-    // wide windows (a second table set, c = 20: msm.hpp) for big single MSMs: 13 instead of 16 additions per scalar.  Needs the wide sort's
-    // record (<= 65,536 digits per pass-A block, <= 1024 blocks).
-    const bool wide = basis.wide_pts && basis.wide_c > 16 && basis.wide_c - 9 <= (int)PART2_MAXLOW && n >= msm_wide_min_n() && k <= 4 &&
-                      (size_t)windows_of(basis.wide_c) * n <= ((size_t)1 << 26);
-    // MSM_SPREAD_SCALARS: the caller vouches that the scalars are spread like random ones (the opening rounds: products with Fiat-Shamir challenges), so
-    // no bucket collects a large share of the entries: the two-phase hot-bucket kernels are not launched (two empty dependent launches per MSM, ~20 us of
-    // the ~340 us of an opening round) and a bucket's quad sums however many task partials it finds -- correct for any input, slow for a skewed one.
-    // The promise is checked, not trusted: a bucket with more than SPREAD_MAX_NT task partials (a constant or sparse polynomial from a
-    // degenerate or adversarial witness puts n / K of them into one bucket per window) is left empty and reported through a pinned word; msm_finish re-runs
-    // the job with the hot-bucket kernels and reports it (MsmJob::spread_rerun): the opening passes the hint no more.
-    static constexpr u32 SPREAD_MAX_NT = 256;
-    const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
-    const int c = wide ? basis.wide_c : (basis.precomp_c ? basis.precomp_c : msm_pick_window(n));
-    const bool glv = basis.glv && !wide && basis.precomp_c != 0;      // rows 0 .. W/2-1: 2^(c w) P, rows W/2 .. W-1: phi of them (csrc/rebase.hip)
-    const int W = glv ? 2 * ((128 + c - 1) / c) : windows_of(c);
-    const u32 nb = 1u << (c - 1);
-    const int precomp = (wide || basis.precomp_c) ? 1 : 0;
-    // slices per (window, msm): enough blocks to fill the chip (~512), no more -- the per-slice histograms
-    // cost nkeys x W x S words of traffic in k_key_totals, which dominates the sort of a batch
-    int S = (int)(n / 32768); if (S < 1) S = 1; if (S > 16) S = 16;
-    { int want = (int)(512 / ((size_t)W * k)); if (want < 1) want = 1; if (S > want) S = want; }
-    const size_t tab_stride = basis.stride ? basis.stride : basis.n;
-    SortGeom g{n, nb, S, W, precomp, tab_stride, offset, basis.batch_stride};
-    const size_t ngroups = precomp ? k : k * (size_t)W;
-    // few groups: the latency path of the bucket sums and marginals, lane-cooperative additions (coop.cuh)
-    const bool few_groups = ngroups <= 8;                   // 5 / 7 / 8 MSMs of 2^16: 0.94 / 1.09 / 1.14 -> 0.85 / 1.05 / 1.09 ms against 4
-    const bool quad_sum = !wide && precomp && few_groups;   // k_bucket_sum_q, the only bucket-sum kernel that takes the spread hint
-    const bool spread = quad_sum && (flags & MSM_SPREAD_SCALARS) != 0;
-    const int Sq = precomp ? W * S : S;
-    const size_t nkeys = ngroups * nb;
-    const size_t M = n * (size_t)W * k;                 // upper bound on entries
-    // Task size: the accumulation is one long dependent chain per thread, so a launch that needs
-    // 1.1 "rounds" of resident threads pays a whole extra chain at 10 % occupancy (measured: 1.80 ms
-    // instead of 1.72 ms at 2^20).  Size K so that all tasks are resident at once (4 waves/SIMD =
-    // 1024 threads per CU) whenever the bucket count allows it.
-    const size_t cap = (size_t)Ctx.num_cus * 256 * 4;
-    size_t room_sz = cap / 4;                              // many buckets: about one task per bucket anyway
-    if (nkeys < cap / 2) room_sz = cap - cap / 16 - nkeys / 2;   // ~ half of the buckets add a remainder task
-    const u32 room = (u32)room_sz;                          // K = clamp(ceil(entries / room), 8, MAX_K), on the device
-    const u32 kmin = 8;
-    const KTab ktab = precomp ? task_length_table(nkeys, (u32)Ctx.num_cus) : KTab{};
-    const size_t max_tasks = M / 4 + nkeys + 1;          // bound for the smallest K (the table's entries are >= 4)
-    KH_REQUIRE(M < ((size_t)1 << 31) && (tab_stride * (size_t)(precomp ? W : 1) + basis.batch_stride * k) < ((size_t)1 << 31), "MSM too large for 31-bit entry indices (n=%zu k=%zu)", n, k);
-
+    const size_t nkeys = P.nkeys, M = P.M, max_tasks = P.max_tasks, ngroups = P.ngroups;
     int rc;
     if ((rc = C.ws_digits.reserve(M * sizeof(int32_t)))) return rc;
-    if ((rc = C.ws_hist.reserve(nkeys * Sq * sizeof(u32)))) return rc;
+    if ((rc = C.ws_hist.reserve(nkeys * P.Sq * sizeof(u32)))) return rc;
     if ((rc = C.ws_cnt.reserve((nkeys + 2) * sizeof(u32)))) return rc;
     if ((rc = C.ws_off.reserve((nkeys + 2) * sizeof(u32)))) return rc;
     if ((rc = C.ws_ntask.reserve((nkeys + 2) * sizeof(u32)))) return rc;
@@ -1928,96 +1823,39 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     if ((rc = C.ws_partial.reserve(max_tasks * 128))) return rc;
     if ((rc = C.ws_handed.reserve((max_tasks + 2) * sizeof(u32)))) return rc;
     if ((rc = C.ws_buckets.reserve(nkeys * 128))) return rc;
-    const size_t bigcap = nkeys + max_tasks / CHUNK + 2;      // big buckets <= nkeys; chunk items <= tasks/512 + nkeys
-    if ((rc = C.ws_biglist.reserve((2 + 4 * bigcap) * sizeof(u32)))) return rc;
-    if ((rc = C.ws_chunks.reserve(bigcap * 128))) return rc;
-    if ((rc = C.ws_order.reserve((2 * (MAX_K + 1) + 3 * (nkeys + 2)) * sizeof(u32)))) return rc;
-    WideGeom wg{};
-    // wide-path constants (measured best, tools/wide_sweep.py): ranks of one partition side by side in the accumulation order; blocks of the
-    // accumulation per CU (held down with dynamic LDS); log2 of the chunk length of the first reduction level
-    static constexpr u32 wide_og = 16, wide_acc_blocks = 3, wide_rlog = 4;
-    // k_part2_sort interleaves `og` consecutive ranks of a partition: og must divide the 2^(c - 9) buckets of a partition; k_wide_a1 cuts both digit
-    // planes into chunks of 2^rlog buckets and k_wide_l2 the chunks of a marginal into runs of 2^flog, flog = max(lo - rlog - 4, 1), which leaves a marginal at most 16 runs -- for every wide c (> 16)
-    static_assert((wide_og & (wide_og - 1)) == 0 && wide_og <= (1u << (17 - 9)) && wide_rlog >= 1 && wide_rlog + 2 <= 17 / 2, "wide-path constants");
-    // dynamic LDS that leaves room for exactly wide_acc_blocks blocks on a CU, from the device's own LDS size (160 KB on gfx950), never more than one block
-    // may ask for: where the request cannot hold the count down the kernel simply runs at its register-limited occupancy
-    size_t wide_acc_lds = (Ctx.lds_per_cu / (wide_acc_blocks + 1) + 1024) & ~(size_t)1023;
-    if (wide_acc_lds > Ctx.lds_per_block) wide_acc_lds = Ctx.lds_per_block & ~(size_t)1023;
-    if (wide) {                                                                         // bucket = (hi digit, lo digit)
+    if ((rc = C.ws_biglist.reserve((2 + 4 * P.bigcap) * sizeof(u32)))) return rc;
+    if ((rc = C.ws_chunks.reserve(P.bigcap * 128))) return rc;
+    if ((rc = C.ws_order.reserve((2 * (MAX_K + 1) + 3 * (nkeys + 2)) * sizeof(u32)))) return rc;      // [MAX_K+1] histogram, [MAX_K+1] cursors, then order / rnt / roff
+    if (P.wide) {
         if ((rc = C.ws_xlist.reserve((3 * max_tasks + 8) * sizeof(u32)))) return rc;       // (key, chunk) pairs of the extra chunks, then the split buckets' keys
         if ((rc = C.ws_handed.reserve((2 * max_tasks + 4) * sizeof(u32)))) return rc;
-        wg.nb = nb; wg.lo = (u32)c / 2; wg.hi = (u32)(c - 1) - wg.lo; wg.rlog = wide_rlog;
-        // level two leaves k_wide_a2 sixteen run records per hi-digit marginal (c = 20: runs of 4 chunks, 16 + 8 records).  Runs of 8 halve k_wide_a2's work again,
-        // but their seven additions in sequence made the synchronous MSM 8 us longer than it was with one level; runs of 4 leave it as it was (NOTES 7)
-        wg.flog = wg.lo > wg.rlog + 5 ? wg.lo - wg.rlog - 4 : 1;
         if ((rc = C.ws_b29.reserve(nkeys * B29_BYTES))) return rc;
-        if ((rc = C.ws_a1.reserve(ngroups * 2 * (size_t)(nb >> wg.rlog) * B29_BYTES))) return rc;
-        if ((rc = C.ws_l2.reserve(ngroups * 2 * (size_t)(nb >> (wg.rlog + wg.flog)) * B29_BYTES))) return rc;
-        if ((rc = C.ws_a2.reserve(ngroups * 2 * ((size_t)1 << wg.lo) * 128))) return rc;
+        if ((rc = C.ws_a1.reserve(ngroups * 2 * (size_t)(P.nb >> P.wg.rlog) * B29_BYTES))) return rc;
+        if ((rc = C.ws_l2.reserve(ngroups * 2 * (size_t)(P.nb >> (P.wg.rlog + P.wg.flog)) * B29_BYTES))) return rc;
+        if ((rc = C.ws_a2.reserve(ngroups * 2 * ((size_t)1 << P.wg.lo) * 128))) return rc;
     }
-    // segment length of the weighted reduction: one bucket per thread (a 15-bit double-and-add each)
-    // is the shortest chain, but its work grows with the bucket count -- for batches use running
-    // sums over m buckets (2 additions per bucket + one double-and-add per segment), keeping about
-    // one wave per SIMD busy
-    u32 m = 1;
-    while (m < 16 && (ngroups * (size_t)nb) / m > 65536) m <<= 1;
-    if (!precomp && m < 4) m = 4;
-    if (nb < m) m = nb;
-    const u32 nseg = nb / m;
-    const u32 nblk1 = (nseg + SUM_BLK - 1) / SUM_BLK;
-    // one to four MSMs over the tables: digit marginals instead (k_marginals), three fields of <= 5 bits
-    const u32 planes = wide ? 3u : ((precomp && ngroups <= 4096 && c >= 7 && c <= 16) ? 3u : 0u);
-    MargGeom mg{};
-    if (planes) {                                          // (wide: the tail runs over the two marginal groups of 2^lo slots each, k_wide_a2)
-        const u32 bits = wide ? wg.lo : (u32)c - 1, f0 = (bits + 2) / 3, f1 = (bits - f0 + 1) / 2, f2 = bits - f0 - f1;
-        mg.nb = wide ? 1u << wg.lo : nb; mg.sh[0] = 0; mg.wd[0] = f0; mg.sh[1] = f0; mg.wd[1] = f1; mg.sh[2] = f0 + f1; mg.wd[2] = f2;
-    }
-    const size_t tail_groups = wide ? 2 * ngroups : ngroups;
-    const size_t nout = planes ? tail_groups * planes : ngroups;
-    if ((rc = C.ws_seg.reserve(std::max(ngroups * (size_t)(nseg + nblk1), nout * (size_t)32) * 128))) return rc;
-    if ((rc = C.ws_out.reserve(nout * 128))) return rc;
-    if (C.pinned_cap < nout * 128) {                     // host staging of the group sums; the host part runs in msm_finish
+    if ((rc = C.ws_seg.reserve(std::max(ngroups * (size_t)(P.nseg + P.nblk1), P.nout * (size_t)32) * 128))) return rc;
+    if ((rc = C.ws_out.reserve(P.nout * 128))) return rc;
+    if (C.pinned_cap < P.nout * 128) {                   // host staging of the group sums; the host part runs in msm_finish
         if (C.pinned) (void)hipHostFree(C.pinned);
         C.pinned = nullptr; C.pinned_cap = 0;
         // coherent + mapped, explicitly: the completion-by-flag path reads these lines with no runtime synchronisation in between
-        C.pinned_coherent = hipHostMalloc(&C.pinned, nout * 128 + 4096, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
-        if (!C.pinned_coherent) { (void)hipGetLastError(); C.pinned = nullptr; KH_HIP(hipHostMalloc(&C.pinned, nout * 128 + 4096, hipHostMallocDefault)); }
-        C.pinned_cap = nout * 128 + 4096;
+        C.pinned_coherent = hipHostMalloc(&C.pinned, P.nout * 128 + 4096, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess;
+        if (!C.pinned_coherent) { (void)hipGetLastError(); C.pinned = nullptr; KH_HIP(hipHostMalloc(&C.pinned, P.nout * 128 + 4096, hipHostMallocDefault)); }
+        C.pinned_cap = P.nout * 128 + 4096;
     }
     if (Ctx.once("msm_attr")) {
         KH_HIP(hipFuncSetAttribute((const void*)k_hist, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
         KH_HIP(hipFuncSetAttribute((const void*)k_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
         KH_HIP(hipFuncSetAttribute((const void*)k_sort_fused, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
     }
-    // small jobs over the tables: the whole sort in one launch (k_sort_fused)
-    static const bool fused_off = env_flag("KH_NO_FUSED_SORT", false);
-    // bounded spin of its grid barriers: 20 ms of the 100 MHz wall clock by default (a barrier normally waits < 50 us)
-    static const unsigned long long fused_spin_ticks = 100ull * (unsigned long long)env_int("KH_FUSED_SPIN_US", 20000);
-    FusedGeom fg{};
-    // (co-residency of the spinning blocks is what makes the grid barriers safe: 64 blocks x 4 jobs in flight need 128 CUs -- not in a partitioned mode)
-    bool fused = precomp && !wide && !fused_off && !Ctx.fused_disabled && k <= 4 && M < ((size_t)1 << 22) && nb >= 2048 && Ctx.num_cus >= 128;
-    if (fused) {
-        fg.n = (u32)n; fg.nb = nb; fg.W = (u32)W; fg.k = (u32)k; fg.bpg = (u32)std::min<size_t>(FUSED_G, FUSED_B / (2 * k)); fg.nkeys = (u32)nkeys;
-        fg.split = 2; fg.sub = nb / fg.split;              // 64 blocks of 64 KB LDS: two per CU, so four (even eight) jobs in flight stay co-resident
-        fg.room = room; fg.kmin = kmin; fg.ktab = ktab; fg.pt_stride = tab_stride; fg.pt_offset = offset; fg.pt_batch = basis.batch_stride;
-        const size_t threads = (size_t)fg.bpg * k * fg.split * FUSED_T;
-        fg.kpt = (u32)((nkeys + 1 + threads - 1) / threads);
-        const size_t tot4 = (size_t)W * n / 4, chunk4 = (tot4 + fg.bpg - 1) / fg.bpg + 1;
-        if (fg.kpt > (u32)FUSED_KPT || n < 4 || ((size_t)W * n) % 4 || chunk4 > (size_t)FUSED_V * FUSED_T || fg.sub > (u32)FUSED_C * FUSED_T) fused = false;
-    }
-    // large jobs over the tables: the two-pass partitioned sort (k_part_*)
-    const bool part = wide || (precomp && !fused && nb == ((u32)PART_P << PART_LOW) && n <= ((size_t)1 << 20) && W <= 16 && M >= ((size_t)1 << 21));
-    const u32 part_low = wide ? (u32)c - 9 : (u32)PART_LOW;
-    const u32 part_nblk = wide ? (u32)std::max<size_t>(std::max<size_t>(1, std::min<size_t>(256, 512 / k)), ((size_t)W * n + 65535) / 65536)
-                               : (part ? (u32)std::max<size_t>(1, std::min<size_t>(256, 512 / k)) : 0);
-    const size_t part_size = (size_t)k * PART_P * part_nblk;
-    if (part) {
-        if ((rc = C.ws_hist.reserve((part_size + 1) * sizeof(u32)))) return rc;
-        if ((rc = C.ws_cnt.reserve((part_size + 1) * sizeof(u32)))) return rc;
+    if (P.sort == SORT_PARTITIONED) {
+        if ((rc = C.ws_hist.reserve((P.part_size + 1) * sizeof(u32)))) return rc;
+        if ((rc = C.ws_cnt.reserve((P.part_size + 1) * sizeof(u32)))) return rc;
         if ((rc = C.ws_mid.reserve(M * sizeof(u32)))) return rc;
     }
-    if (fused) {
-        if ((rc = C.ws_hist.reserve((size_t)k * fg.bpg * nb * sizeof(u32)))) return rc;
+    if (P.sort == SORT_FUSED) {
+        if ((rc = C.ws_hist.reserve((size_t)P.fg.k * P.fg.bpg * P.nb * sizeof(u32)))) return rc;
         if (!C.ws_sync.p) {
             if ((rc = C.ws_sync.reserve((2 + 2 * FUSED_B + 32 + 2) * sizeof(u32)))) return rc;
             KH_HIP(hipMemsetAsync(C.ws_sync.p, 0, (2 + 2 * FUSED_B + 32 + 2) * sizeof(u32), s));
@@ -2028,14 +1866,13 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
             C.host_abort = (volatile uint32_t*)hp; *C.host_abort = 0;
         }
     }
-    if (spread && !C.spread_abort) {
+    if (P.spread && !C.spread_abort) {
         void* hp = nullptr;
         KH_HIP(hipHostMalloc(&hp, 64, hipHostMallocCoherent | hipHostMallocMapped));
         C.spread_abort = (volatile uint32_t*)hp; *C.spread_abort = 0;
     }
     // completion by flag (MsmSlot::done_flag): pinned word + two device words, once per slot
-    static const bool flag_off = env_flag("KH_NO_DONE_FLAG", false);
-    bool flag_on = !flag_off && (wide || planes) && !C.flag_unavailable && C.pinned_coherent;
+    flag_on = P.want_flag && !C.flag_unavailable && C.pinned_coherent;
     if (flag_on && !C.done_flag) {
         void* hp = nullptr;
         if (hipHostMalloc(&hp, 64, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {      // no coherent word: completion by event on this slot
@@ -2046,72 +1883,89 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
             KH_HIP(hipMemsetAsync(C.ws_done.p, 0, 64, s));           // ordered in front of the slot's first launch that counts in it
         }
     }
+    if (P.wide && Ctx.once("part2_attr")) KH_HIP(hipFuncSetAttribute((const void*)k_part2_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
+    return KH_OK;
+}
+
+// one launch, between the timer's own start / stop events when the phase timers are on: the dominant kernel's duration (bench.py roofline)
+template <class K, class... A>
+static void launch_timed(PhaseTimer& t, const char* name, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    if (t.enabled && t.created) {
+        hipExtLaunchKernelGGL(kern, grid, block, lds, s, t.k0, t.k1, 0, args...);
+        t.kname = name;
+    } else
+        hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+}
+
+// the launches of plan P (of shape sh) on slot C, whose workspaces msm_reserve has sized
+template <class CFG>
+static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev, int mont, const MsmShape& sh, const MsmPlan& P, bool flag_on) {
+    typedef typename CFG::Base BF; typedef typename CFG::Scalar SF;
+    hipStream_t s = C.stream;
+    const size_t n = sh.n, k = sh.k, nkeys = P.nkeys, ngroups = P.ngroups;
+    const bool wide = P.wide, fused = P.sort == SORT_FUSED;
+    const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
+    int rc;
     C.timer.begin(s);
     // 1 digits
-    if (glv)
+    if (P.glv)
     hipLaunchKernelGGL((k_digits_glv<SF>), dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                       scalars_dev, basis.inf, offset, basis.batch_stride, n, mont, c, W, C.ws_digits.as<int32_t>());
+                       scalars_dev, basis.inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>());
     else
     hipLaunchKernelGGL((k_digits<SF>), dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                       scalars_dev, basis.inf, offset, basis.batch_stride, n, mont, c, W, C.ws_digits.as<int32_t>(), (size_t)0, n);
+                       scalars_dev, basis.inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>(), (size_t)0, n);
     C.timer.mark("digits", s);
     u32* len_hist = C.ws_order.as<u32>();                       // [MAX_K+1] histogram, [MAX_K+1] cursors, then order / rnt / roff
     u32* cursor = len_hist + (MAX_K + 1);
     u32* order = cursor + (MAX_K + 1);
     u32* rnt = order + (nkeys + 2);
     u32* roff = rnt + (nkeys + 2);
+    u32* const slist = C.ws_xlist.as<u32>() + P.slist_off;      // (wide) the split buckets' keys, behind the extra chunks' pairs
     if (fused) {
+        // bounded spin of its grid barriers: 20 ms of the 100 MHz wall clock by default (a barrier normally waits < 50 us)
+        static const unsigned long long fused_spin_ticks = 100ull * (unsigned long long)env_int("KH_FUSED_SPIN_US", 20000);
         order = nullptr; roff = C.ws_toff.as<u32>();
         u32* sy = C.ws_sync.as<u32>();
-        hipLaunchKernelGGL(k_sort_fused, dim3(fg.bpg * fg.k * fg.split), dim3(FUSED_T), (size_t)fg.sub * sizeof(u32), s, C.ws_digits.as<int32_t>(), fg,
+        hipLaunchKernelGGL(k_sort_fused, dim3(P.fg.bpg * P.fg.k * P.fg.split), dim3(FUSED_T), (size_t)P.fg.sub * sizeof(u32), s, C.ws_digits.as<int32_t>(), P.fg,
                            C.ws_hist.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), C.ws_entries.as<u32>(), C.ws_handed.as<u32>(),
                            C.ws_biglist.as<u32>(), sy, sy + 2, C.host_abort, fused_spin_ticks);
         C.timer.mark("sort", s);
-    } else if (part) {
-        const u32 tot_e = (u32)((size_t)W * n);
+    } else if (P.sort == SORT_PARTITIONED) {
+        const u32 tot_e = (u32)P.tot_e, part_nblk = P.part_nblk, part_low = P.part_low;
         const dim3 pgrid(part_nblk, (unsigned)k);
         hipLaunchKernelGGL(k_part_hist, pgrid, dim3(PART_T), 0, s, C.ws_digits.as<int32_t>(), tot_e, part_nblk, wide ? 0u : part_low, C.ws_hist.as<u32>());
         C.timer.mark("histogram", s);
-        if ((rc = exclusive_scan_u32(C.ws_hist.as<u32>(), C.ws_cnt.as<u32>(), part_size + 1, C.ws_scan_tmp, s))) return rc;
+        if ((rc = exclusive_scan_u32(C.ws_hist.as<u32>(), C.ws_cnt.as<u32>(), P.part_size + 1, C.ws_scan_tmp, s))) return rc;
         C.timer.mark("scan", s);
         if (wide) {
             hipLaunchKernelGGL(k_part2_scatter, pgrid, dim3(PART_T), 0, s, C.ws_digits.as<int32_t>(), tot_e, part_nblk, part_low, C.ws_cnt.as<u32>(), C.ws_mid.as<u32>(), C.ws_xlist.as<u32>(), C.ws_biglist.as<u32>());
             // ... and the task plan (toff, the length-ranked order, roff): partition-local in pass B, made global by k_wide_fixup
-            const WideTasks wt{room, kmin, (u32)nkeys, ktab};
-            u32* const slist = C.ws_xlist.as<u32>() + 2 + 2 * max_tasks;
+            const WideTasks wt{P.room, P.kmin, (u32)nkeys, P.ktab};
             u32* const ptot = C.ws_ntask.as<u32>();        // k * 256 partition task totals (the narrow path's per-key task counts: unused here)
-            // staged scatter (round 6): KH_PART2_STAGE = entries per pass in LDS (0: the direct scatter); the dynamic LDS also holds the planning phase's lists
-            const u32 part2_stage = sort_staging_cell(0).load(), part2_maxpass = std::min<u32>(PART2_MAXPASS, sort_staging_cell(1).load());
-            // (clamped to the 128 KB the attribute below asks for; an MSM whose partitions cannot make it in max_pass passes does not ask for the LDS at all)
-            u32 stage_now = std::min<u32>(part2_stage, (131072u - (1u << PART2_MAXLOW)) / 4u);
-            if (stage_now <= 2048u || (size_t)W * n / PART_P > (size_t)part2_maxpass * (stage_now - 1024u)) stage_now = 0;
-            const u32 stage_words = std::max<u32>(stage_now, 3u << PART2_MAXLOW);
-            const size_t part2_lds = (size_t)stage_words * 4 + (stage_now ? ((size_t)1 << PART2_MAXLOW) : 0);
-            if (Ctx.once("part2_attr")) KH_HIP(hipFuncSetAttribute((const void*)k_part2_sort, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
-            hipLaunchKernelGGL(k_part2_sort, dim3(PART_P, (unsigned)k), dim3(PART_T), part2_lds, s, C.ws_mid.as<u32>(), C.ws_cnt.as<u32>(), part_nblk, part_low, nb, tot_e, (u32)n,
-                               tab_stride, offset, basis.batch_stride, (u32)(k - 1), part_size, wt, C.ws_off.as<u32>(), C.ws_entries.as<u32>(),
-                               C.ws_toff.as<u32>(), order, ptot, C.ws_xlist.as<u32>(), slist, C.ws_b29.as<uint8_t>(), wide_og, stage_now, part2_maxpass, C.ws_biglist.as<u32>(), (u32)bigcap, WIDE_HOT_NT);
+            hipLaunchKernelGGL(k_part2_sort, dim3(PART_P, (unsigned)k), dim3(PART_T), P.part2_lds, s, C.ws_mid.as<u32>(), C.ws_cnt.as<u32>(), part_nblk, part_low, P.nb, tot_e, (u32)n,
+                               P.g.pt_stride, sh.offset, sh.batch_stride, (u32)(k - 1), P.part_size, wt, C.ws_off.as<u32>(), C.ws_entries.as<u32>(),
+                               C.ws_toff.as<u32>(), order, ptot, C.ws_xlist.as<u32>(), slist, C.ws_b29.as<uint8_t>(), wide_og, P.stage_now, P.part2_maxpass, C.ws_biglist.as<u32>(), (u32)P.bigcap, WIDE_HOT_NT);
             hipLaunchKernelGGL(k_wide_fixup, dim3((unsigned)(nkeys / 256 + 1)), dim3(256), 0, s, C.ws_toff.as<u32>(), ptot, (u32)(k * PART_P), part_low, (u32)nkeys,
                                C.ws_handed.as<u32>(), C.ws_biglist.as<u32>());
         } else {
         hipLaunchKernelGGL(k_part_scatter, pgrid, dim3(PART_T), 0, s, C.ws_digits.as<int32_t>(), tot_e, (u32)n, part_nblk, C.ws_cnt.as<u32>(), C.ws_mid.as<u32>());
-        hipLaunchKernelGGL(k_part_sort, dim3(PART_P, (unsigned)k), dim3(PART_T), 0, s, C.ws_mid.as<u32>(), C.ws_cnt.as<u32>(), part_nblk, nb,
-                           tab_stride, offset, basis.batch_stride, (u32)(k - 1), C.ws_off.as<u32>(), C.ws_entries.as<u32>());
+        hipLaunchKernelGGL(k_part_sort, dim3(PART_P, (unsigned)k), dim3(PART_T), 0, s, C.ws_mid.as<u32>(), C.ws_cnt.as<u32>(), part_nblk, P.nb,
+                           P.g.pt_stride, sh.offset, sh.batch_stride, (u32)(k - 1), C.ws_off.as<u32>(), C.ws_entries.as<u32>());
         }
         C.timer.mark("scatter", s);
     } else {
         // 2 histogram
-        size_t lds = (size_t)nb * sizeof(u32);
-        dim3 sgrid((unsigned)S, (unsigned)W, (unsigned)k);
-        hipLaunchKernelGGL(k_hist, sgrid, dim3(1024), lds, s, C.ws_digits.as<int32_t>(), g, C.ws_hist.as<u32>());
+        size_t lds = (size_t)P.nb * sizeof(u32);
+        dim3 sgrid((unsigned)P.S, (unsigned)P.W, (unsigned)k);
+        hipLaunchKernelGGL(k_hist, sgrid, dim3(1024), lds, s, C.ws_digits.as<int32_t>(), P.g, C.ws_hist.as<u32>());
         hipLaunchKernelGGL(k_key_totals, dim3((unsigned)((nkeys + 1 + 255) / 256)), dim3(256), 0, s,
-                           C.ws_hist.as<u32>(), nb, Sq, nkeys, C.ws_cnt.as<u32>());
+                           C.ws_hist.as<u32>(), P.nb, P.Sq, nkeys, C.ws_cnt.as<u32>());
         C.timer.mark("histogram", s);
         // 3 scan
         if ((rc = exclusive_scan_u32(C.ws_cnt.as<u32>(), C.ws_off.as<u32>(), nkeys + 1, C.ws_scan_tmp, s))) return rc;
         C.timer.mark("scan", s);
         // 4 scatter
-        hipLaunchKernelGGL(k_scatter, sgrid, dim3(1024), lds, s, C.ws_digits.as<int32_t>(), g, C.ws_hist.as<u32>(),
+        hipLaunchKernelGGL(k_scatter, sgrid, dim3(1024), lds, s, C.ws_digits.as<int32_t>(), P.g, C.ws_hist.as<u32>(),
                            C.ws_off.as<u32>(), C.ws_entries.as<u32>());
         C.timer.mark("scatter", s);
     }
@@ -2119,9 +1973,9 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
         // tasks
         hipLaunchKernelGGL(k_task_reset, dim3(1), dim3(320), 0, s, len_hist, C.ws_biglist.as<u32>());      // (two memset nodes cost the host ~10 us each to queue)
         // (1024-thread blocks: the per-(block, length) global atomics of k_ntask / k_len_rank serialise on ~40 hot addresses -- 25 us each at 256 threads per block)
-        hipLaunchKernelGGL(k_ntask, dim3((unsigned)((nkeys + 1 + 1023) / 1024)), dim3(1024), 0, s, C.ws_off.as<u32>(), nkeys, room, kmin, ktab, C.ws_ntask.as<u32>(), len_hist, C.ws_handed.as<u32>());
+        hipLaunchKernelGGL(k_ntask, dim3((unsigned)((nkeys + 1 + 1023) / 1024)), dim3(1024), 0, s, C.ws_off.as<u32>(), nkeys, P.room, P.kmin, P.ktab, C.ws_ntask.as<u32>(), len_hist, C.ws_handed.as<u32>());
         if ((rc = exclusive_scan_u32(C.ws_ntask.as<u32>(), C.ws_toff.as<u32>(), nkeys + 1, C.ws_scan_tmp, s))) return rc;
-        if (M >= ((size_t)1 << 22)) {      // below ~4M entries the three extra launches cost more than the ordering saves
+        if (P.M >= ((size_t)1 << 22)) {      // below ~4M entries the three extra launches cost more than the ordering saves
             hipLaunchKernelGGL(k_len_starts, dim3(1), dim3(320), 0, s, len_hist, cursor);
             hipLaunchKernelGGL(k_len_rank, dim3((unsigned)((nkeys + 1 + 1023) / 1024)), dim3(1024), 0, s, C.ws_off.as<u32>(), C.ws_ntask.as<u32>(), nkeys, cursor, order, rnt);
             if ((rc = exclusive_scan_u32(rnt, roff, nkeys + 1, C.ws_scan_tmp, s))) return rc;
@@ -2132,54 +1986,36 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     }
     // 5 accumulate: the lazy 29-bit-limb kernel, then the exact kernel over the (almost always zero) tasks it handed over
     const u32* abort_dev = fused ? C.ws_sync.as<u32>() + 2 + 2 * FUSED_B + 32 : nullptr;     // the fused sort's give-up word (sort_gave_up)
-    const dim3 agrid((unsigned)((max_tasks + 255) / 256));
-    const u32 acc_prio = (flags & MSM_LATENCY) ? 1u : 0u;
     uint8_t* const b29 = wide ? C.ws_b29.as<uint8_t>() : nullptr;
     if (wide) {                                            // thread per bucket in pass B's interleaved length order (+ the listed extra chunks), then the exact redos
-        const dim3 wgrid((unsigned)(nkeys / 256));
-        auto kern = k_acc_wide29<BF>;
-        if (C.timer.enabled && C.timer.created) {
-            hipExtLaunchKernelGGL(kern, wgrid, dim3(256), wide_acc_lds, s, C.timer.k0, C.timer.k1, 0, C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), order, (u32)nkeys,
-                                  (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, part_low, C.ws_handed.as<u32>());
-            C.timer.kname = "k_acc_wide29";
-        } else
-        hipLaunchKernelGGL(kern, wgrid, dim3(256), wide_acc_lds, s, C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), order, (u32)nkeys,
-                           (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, part_low, C.ws_handed.as<u32>());
+        launch_timed(C.timer, "k_acc_wide29", k_acc_wide29<BF>, dim3(P.acc_blocks), dim3(256), P.wide_acc_lds, s, C.ws_entries.as<u32>(), C.ws_off.as<u32>(),
+                     C.ws_toff.as<u32>(), order, (u32)nkeys, (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, P.part_low, C.ws_handed.as<u32>());
         // (the extra chunks: none for 2^19..2^21 uniform scalars; at 2^22 the 2^14 top-window buckets hold ~360 entries against K = 256 and split in two --
         //  16 K extra chunks, for which 32 blocks took 2 ms)
-        const unsigned xgrid = M / nkeys >= 64 ? 2048u : WIDE_XB;
+        const unsigned xgrid = P.M / nkeys >= 64 ? 2048u : WIDE_XB;
         hipLaunchKernelGGL((k_acc_wide_rest<BF>), dim3(xgrid), dim3(256), 0, s, C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(),
-                           C.ws_handed.as<u32>(), (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, part_low);
-    } else {
-        auto kern = k_accumulate29<BF>;
-        if (C.timer.enabled && C.timer.created) {     // the dominant kernel's own start / stop timestamps (bench.py roofline)
-            hipExtLaunchKernelGGL(kern, agrid, dim3(256), 0, s, C.timer.k0, C.timer.k1, 0,
-                                  C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
-                                  (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), C.ws_handed.as<u32>(), abort_dev, acc_prio);
-            C.timer.kname = "k_accumulate29";
-        } else
-        hipLaunchKernelGGL(kern, agrid, dim3(256), 0, s,
-                           C.ws_entries.as<u32>(), C.ws_off.as<u32>(), C.ws_toff.as<u32>(), roff, order, nkeys,
-                           (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), C.ws_handed.as<u32>(), abort_dev, acc_prio);
-    }
+                           C.ws_handed.as<u32>(), (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), b29, P.part_low);
+    } else
+        launch_timed(C.timer, "k_accumulate29", k_accumulate29<BF>, dim3(P.acc_blocks), dim3(256), 0, s, C.ws_entries.as<u32>(), C.ws_off.as<u32>(),
+                     C.ws_toff.as<u32>(), roff, order, nkeys, (const uint8_t*)tab_pts, C.ws_partial.as<uint8_t>(), C.ws_handed.as<u32>(), abort_dev, P.acc_prio);
     C.timer.mark("accumulate", s);
     // 6 bucket sums
     if (wide)                                              // (the split buckets' sums, hot ones included: one launch; 2^22: 16 K split buckets of two partials)
-        hipLaunchKernelGGL((k_bucket_sum_wide<BF>), dim3(256), dim3(256), 0, s, C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(), C.ws_xlist.as<u32>() + 2 + 2 * max_tasks,
-                           C.ws_partial.as<uint8_t>(), b29, part_low, WIDE_HOT_NT, C.ws_biglist.as<u32>(), (u32)bigcap, C.ws_chunks.as<uint8_t>());
-    else if (quad_sum)
+        hipLaunchKernelGGL((k_bucket_sum_wide<BF>), dim3(256), dim3(256), 0, s, C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(), slist,
+                           C.ws_partial.as<uint8_t>(), b29, P.part_low, WIDE_HOT_NT, C.ws_biglist.as<u32>(), (u32)P.bigcap, C.ws_chunks.as<uint8_t>());
+    else if (P.quad_sum)
         hipLaunchKernelGGL((k_bucket_sum_q<BF>), dim3((unsigned)((4 * nkeys + 255) / 256)), dim3(256), 0, s,
                            C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
-                           bigcap, spread ? SPREAD_MAX_NT : 16u, abort_dev, spread ? (u32*)C.spread_abort : nullptr);
+                           P.bigcap, P.spread ? SPREAD_MAX_NT : 16u, abort_dev, P.spread ? (u32*)C.spread_abort : nullptr);
     else
     hipLaunchKernelGGL((k_bucket_sum<BF>), dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s,
                        C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
-                       bigcap, nkeys <= 16384 ? 4u : 16u, abort_dev);
-    if (!wide && !spread) {     // (the quad kernel took every bucket: nothing was listed; the wide path's kernel sums its hot buckets itself)
+                       P.bigcap, nkeys <= 16384 ? 4u : 16u, abort_dev);
+    if (!wide && !P.spread) {     // (the quad kernel took every bucket: nothing was listed; the wide path's kernel sums its hot buckets itself)
     hipLaunchKernelGGL((k_bucket_chunk<BF>), dim3(2048), dim3(64), 0, s,
-                       C.ws_toff.as<u32>(), C.ws_partial.as<uint8_t>(), C.ws_biglist.as<u32>(), bigcap, C.ws_chunks.as<uint8_t>(), abort_dev);
+                       C.ws_toff.as<u32>(), C.ws_partial.as<uint8_t>(), C.ws_biglist.as<u32>(), P.bigcap, C.ws_chunks.as<uint8_t>(), abort_dev);
     hipLaunchKernelGGL((k_bucket_big<BF>), dim3(1024), dim3(256), 0, s,
-                       C.ws_toff.as<u32>(), C.ws_chunks.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(), bigcap, abort_dev);
+                       C.ws_toff.as<u32>(), C.ws_chunks.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(), P.bigcap, abort_dev);
     }
     C.timer.mark("bucket_sum", s);
     // 7 reduce
@@ -2187,67 +2023,75 @@ static int msm_enqueue_t(Context& Ctx, MsmSlot& C, const MsmBasis& basis, size_t
     // (the host's launch count moves BEFORE the launch that will move the device's: whatever fails in between, the host is never behind -- a stale
     // equality would end a later wait early -- and a host that is ahead only falls back to the event, then resyncs)
     if (flag_on) C.done_expect++;                        // every flag_on job ends in k_marginal_fin_q
-    bool direct_out = false;                              // latency path: the last kernel writes the (768-byte) result to host memory itself -- no copy node
+    const MargGeom& mg = P.mg;
     if (wide) {
-        const u32 items = 2u * (nb >> wg.rlog) * (u32)ngroups;
-        hipLaunchKernelGGL((k_wide_a1<BF>), dim3((items + 255) / 256), dim3(256), 0, s, b29, wg, (u32)ngroups, C.ws_a1.as<uint8_t>());
+        hipLaunchKernelGGL((k_wide_a1<BF>), dim3((P.wide_items + 255) / 256), dim3(256), 0, s, b29, P.wg, (u32)ngroups, C.ws_a1.as<uint8_t>());
         C.timer.mark("reduce_a1", s);
-        // (one-wave blocks: the 256 waves per MSM each carry a chain of 2^flog - 1 additions, and a wave alone on its SIMD runs it fastest)
-        const u32 runs = 2u * (nb >> (wg.rlog + wg.flog)) * (u32)ngroups;
-        hipLaunchKernelGGL((k_wide_l2<BF>), dim3((runs + 63) / 64), dim3(64), 0, s, C.ws_a1.as<uint8_t>(), wg.flog, runs, C.ws_l2.as<uint8_t>());
-        hipLaunchKernelGGL((k_wide_a2<BF>), dim3(runs / (u32)ngroups / 16u, (unsigned)ngroups), dim3(64), 0, s, C.ws_l2.as<uint8_t>(), C.ws_a1.as<uint8_t>(), b29, wg,
+        hipLaunchKernelGGL((k_wide_l2<BF>), dim3((P.wide_runs + 63) / 64), dim3(64), 0, s, C.ws_a1.as<uint8_t>(), P.wg.flog, P.wide_runs, C.ws_l2.as<uint8_t>());
+        hipLaunchKernelGGL((k_wide_a2<BF>), dim3(P.wide_runs / (u32)ngroups / 16u, (unsigned)ngroups), dim3(64), 0, s, C.ws_l2.as<uint8_t>(), C.ws_a1.as<uint8_t>(), b29, P.wg,
                            C.ws_a2.as<uint8_t>());
-        hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)tail_groups), dim3(256), 0, s, C.ws_a2.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)tail_groups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
-        direct_out = true;
-    } else if (planes) {
+        hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)P.tail_groups), dim3(256), 0, s, C.ws_a2.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
+        hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)P.tail_groups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
+    } else if (P.planes) {
         // few groups: 256 threads per marginal (4 sequential additions + the tree: shortest chain); batches: one wave per marginal (16 + 6 additions
         // deep, but 2.2x less issue work -- batches are throughput-bound).  Either way, where every lane has its own buckets, k_marginals_h: one lane
         // per addition, the 6-level lane tree replaced by the quads' 4 + 4 steps
         if ((mg.nb >> mg.wd[0]) >= 256)
             hipLaunchKernelGGL((k_marginals_h<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        else if (few_groups)
+        else if (P.few_groups)
             hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         else
             hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, (unsigned)ngroups), dim3(64), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        // the weighted tail is 3 x ngroups blocks however many MSMs there are: a pure latency chain (10 additions deep), so it takes the
-        // lane-cooperative kernel for batches too (15 witness columns: 96 -> 35 us); the records have the same 128-byte layout
-        static const bool fin_quad = !env_flag("KH_NO_FIN_QUAD", false);
-        if (few_groups || fin_quad) {                      // straight into the pinned host staging
+        if (P.direct_out)                                  // straight into the pinned host staging (the lane-cooperative tail: msm_plan.hpp)
             hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
-            direct_out = true;
-        } else
+        else
             hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, (unsigned)ngroups), dim3(64), 0, s, C.ws_seg.as<uint8_t>(), mg, C.ws_out.as<uint8_t>());
     } else {
-    hipLaunchKernelGGL((k_reduce_seg<BF>), dim3((unsigned)((ngroups * nseg + 127) / 128)), dim3(128), 0, s,
-                       C.ws_buckets.as<uint8_t>(), nb, m, ngroups, C.ws_seg.as<uint8_t>());
-    {
-        uint8_t* lvl1 = C.ws_seg.as<uint8_t>() + ngroups * (size_t)nseg * 128;
-        hipLaunchKernelGGL((k_sum_level<BF>), dim3(nblk1, (unsigned)ngroups), dim3(256), 0, s, C.ws_seg.as<uint8_t>(), nseg, nblk1, lvl1);
-        hipLaunchKernelGGL((k_sum_final<BF>), dim3((unsigned)ngroups), dim3(nblk1 > 64 ? 256 : 64), 0, s, lvl1, nblk1, C.ws_out.as<uint8_t>());
-    }
+        hipLaunchKernelGGL((k_reduce_seg<BF>), dim3((unsigned)((ngroups * P.nseg + 127) / 128)), dim3(128), 0, s,
+                           C.ws_buckets.as<uint8_t>(), P.nb, P.m, ngroups, C.ws_seg.as<uint8_t>());
+        uint8_t* lvl1 = C.ws_seg.as<uint8_t>() + ngroups * (size_t)P.nseg * 128;
+        hipLaunchKernelGGL((k_sum_level<BF>), dim3(P.nblk1, (unsigned)ngroups), dim3(256), 0, s, C.ws_seg.as<uint8_t>(), P.nseg, P.nblk1, lvl1);
+        hipLaunchKernelGGL((k_sum_final<BF>), dim3((unsigned)ngroups), dim3(P.nblk1 > 64 ? 256 : 64), 0, s, lvl1, P.nblk1, C.ws_out.as<uint8_t>());
     }
     C.timer.mark("reduce", s);
     KH_HIP(hipGetLastError());
-    // group sums -> pinned host staging
-    if (!direct_out) KH_HIP(hipMemcpyAsync(C.pinned, C.ws_out.p, nout * 128, hipMemcpyDeviceToHost, s));
+    // group sums -> pinned host staging (the latency path's last kernel wrote the 768-byte result to host memory itself: no copy node)
+    if (!P.direct_out) KH_HIP(hipMemcpyAsync(C.pinned, C.ws_out.p, P.nout * 128, hipMemcpyDeviceToHost, s));
     KH_HIP(hipEventRecord(C.done, s));
-    C.busy = true; C.owner = std::this_thread::get_id(); C.ticket = Ctx.next_ticket++;
-    C.job = {basis, offset, scalars_dev, n, k, mont, curve, W, c, precomp, (int)planes, {(int)mg.wd[0], (int)mg.wd[1]}, wide ? (int)wg.lo : 0, ngroups,
-             direct_out && flag_on, fused, spread};
     return KH_OK;
 }
 
+// plan, reserve, launch
 int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t offset, const uint64_t* scalars_dev, size_t n, size_t k, int mont,
                 int flags) {
-    if (n == 0 || k == 0) {          // nothing to launch (MsmJob::ngroups = 0): finish() emits k identities
+    MsmJob job;
+    job.basis = basis; job.offset = offset; job.scalars = scalars_dev; job.n = n; job.k = k; job.mont = mont; job.curve = curve;
+    if (n == 0 || k == 0) {          // nothing to launch (plan.ngroups = 0): finish() emits k identities
         S.busy = true; S.owner = std::this_thread::get_id(); S.ticket = C.next_ticket++;
-        S.job = {basis, offset, scalars_dev, n, k, mont, curve};
+        S.job = job;
         KH_HIP(hipEventRecord(S.done, S.stream));
         return KH_OK;
     }
-    if (curve == KH_CURVE_VESTA) return msm_enqueue_t<VestaCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags);
-    return msm_enqueue_t<PallasCfg>(C, S, basis, offset, scalars_dev, n, k, mont, curve, flags);
+    static const bool fused_off = env_flag("KH_NO_FUSED_SORT", false), flag_off = env_flag("KH_NO_DONE_FLAG", false), fin_quad = !env_flag("KH_NO_FIN_QUAD", false);
+    MsmShape sh;
+    sh.n = n; sh.k = k; sh.offset = offset; sh.flags = flags;
+    sh.precomp_c = basis.precomp_c; sh.has_wide = basis.wide_pts != nullptr; sh.wide_c = basis.wide_c; sh.glv = basis.glv;
+    sh.stride = basis.stride; sh.basis_n = basis.n; sh.batch_stride = basis.batch_stride;
+    sh.num_cus = C.num_cus; sh.lds_per_cu = C.lds_per_cu; sh.lds_per_block = C.lds_per_block;
+    sh.wide_min_n = msm_wide_min_n(); sh.stage_entries = sort_staging_cell(0).load(); sh.stage_maxpass = sort_staging_cell(1).load();
+    sh.fused_off = fused_off || C.fused_disabled; sh.flag_off = flag_off; sh.fin_quad = fin_quad;
+    const char* why = nullptr;
+    KH_REQUIRE(msm_plan(sh, job.plan, &why) == 0, "%s (n=%zu k=%zu)", why, n, k);
+    bool flag_on = false;
+    int rc = msm_reserve(C, S, job.plan, flag_on);
+    if (rc) return rc;
+    rc = curve == KH_CURVE_VESTA ? msm_launch<VestaCfg>(S, basis, scalars_dev, mont, sh, job.plan, flag_on)
+                                 : msm_launch<PallasCfg>(S, basis, scalars_dev, mont, sh, job.plan, flag_on);
+    if (rc) return rc;
+    job.done_by_flag = job.plan.direct_out && flag_on;
+    S.busy = true; S.owner = std::this_thread::get_id(); S.ticket = C.next_ticket++;
+    S.job = job;
+    return KH_OK;
 }
 
 // an aborted job again, from its inputs and without the caller's flags, under the same ticket; waits for it
@@ -2265,7 +2109,7 @@ static int msm_rerun(Context& C, MsmSlot& S) {
 int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool flag_seen) {
     // (the per-phase events of a job -- tools only -- are read below: they need the event wait)
     if (!(flag_seen && S.job.done_by_flag && S.timer.n == 0)) KH_HIP(hipEventSynchronize(S.done));
-    if (S.job.fused && S.host_abort && *S.host_abort) {
+    if (S.job.plan.sort == SORT_FUSED && S.host_abort && *S.host_abort) {
         // the one-launch sort gave up at a grid barrier (its blocks were not all resident: the GPU is shared with another process):
         // everything behind it ran on garbage.  Re-run this job with the multi-launch sort and stay on it.
         *S.host_abort = 0;
@@ -2275,7 +2119,7 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
         KH_HIP(hipMemsetAsync(S.ws_sync.p, 0, (2 + 2 * FUSED_B + 32 + 2) * sizeof(u32), S.stream));
         if (int rc = msm_rerun(C, S)) return rc;
     }
-    if (S.job.spread && S.spread_abort && *S.spread_abort) {
+    if (S.job.plan.spread && S.spread_abort && *S.spread_abort) {
         // MSM_SPREAD_SCALARS did not hold (a bucket with more task partials than a quad may sum in sequence): the buckets that said so were left empty.
         // Re-run this job with the hot-bucket kernels, and say so: the caller's opening passes the hint no more.
         *S.spread_abort = 0;
@@ -2292,45 +2136,46 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
     }
     collect_timings(C, S.timer);
     const MsmJob& J = S.job;
-    if (J.ngroups == 0) {
+    const MsmPlan& P = J.plan;
+    if (P.ngroups == 0) {
         for (size_t j = 0; j < J.k; j++) { memset(out_xy + 8 * j, 0, 64); out_inf[j] = 1; }
         return KH_OK;
     }
     const khost::xyzz* res = (const khost::xyzz*)S.pinned;
-    const MsmJob* Sp = &J;
     static thread_local std::vector<khost::xyzz> totals;
     totals.resize(J.k);
     khost::xyzz* tot = totals.data();
-    auto finish_one = [res, Sp, tot](size_t j) {
-        khost::Crv crv(Sp->curve);
+    const MsmPlan* Pp = &P; const int curve = J.curve;
+    auto finish_one = [res, Pp, curve, tot](size_t j) {
+        khost::Crv crv(curve);
         khost::xyzz& total = tot[j];
-        if (Sp->wide_lo) {                            // two marginal groups per MSM (k_wide_a2): 2^lo * fold(H) + fold(L)
+        if (Pp->wide) {                            // two marginal groups per MSM (k_wide_a2): 2^lo * fold(H) + fold(L)
             for (int g2 = 0; g2 < 2; g2++) {
                 const khost::xyzz* r3 = res + (j * 2 + g2) * 3;
                 khost::xyzz f = r3[2];
-                for (int t = 0; t < Sp->plane_shift[1]; t++) f = crv.dbl(f);
+                for (int t = 0; t < (int)Pp->mg.wd[1]; t++) f = crv.dbl(f);
                 f = crv.add(f, r3[1]);
-                for (int t = 0; t < Sp->plane_shift[0]; t++) f = crv.dbl(f);
+                for (int t = 0; t < (int)Pp->mg.wd[0]; t++) f = crv.dbl(f);
                 f = crv.add(f, r3[0]);
-                if (g2 == 0) { for (int t = 0; t < Sp->wide_lo; t++) f = crv.dbl(f); total = f; }
+                if (g2 == 0) { for (int t = 0; t < (int)Pp->wg.lo; t++) f = crv.dbl(f); total = f; }
                 else total = crv.add(total, f);
             }
-        } else if (Sp->precomp && Sp->planes) {       // (M2 2^f1 + M1) 2^f0 + M0 over the three digit marginals
+        } else if (Pp->precomp && Pp->planes) {       // (M2 2^f1 + M1) 2^f0 + M0 over the three digit marginals
             total = res[j * 3 + 2];
-            for (int t = 0; t < Sp->plane_shift[1]; t++) total = crv.dbl(total);
+            for (int t = 0; t < (int)Pp->mg.wd[1]; t++) total = crv.dbl(total);
             total = crv.add(total, res[j * 3 + 1]);
-            for (int t = 0; t < Sp->plane_shift[0]; t++) total = crv.dbl(total);
+            for (int t = 0; t < (int)Pp->mg.wd[0]; t++) total = crv.dbl(total);
             total = crv.add(total, res[j * 3]);
-        } else if (Sp->precomp) total = res[j];
+        } else if (Pp->precomp) total = res[j];
         else {                                        // Horner over the window sums: ~256 doublings (~70 us)
             total = crv.identity();
-            for (int w = Sp->W - 1; w >= 0; w--) {
-                for (int t = 0; t < Sp->c; t++) total = crv.dbl(total);
-                total = crv.add(total, res[j * Sp->W + w]);
+            for (int w = Pp->W - 1; w >= 0; w--) {
+                for (int t = 0; t < Pp->c; t++) total = crv.dbl(total);
+                total = crv.add(total, res[j * Pp->W + w]);
             }
         }
     };
-    if ((!J.precomp && J.k >= 2) || (J.planes && J.k >= 16)) {      // split the Horner folds with the helper thread (a hand-over costs ~10 us: not for a few doublings)
+    if ((!P.precomp && J.k >= 2) || (P.planes && J.k >= 16)) {      // split the Horner folds with the helper thread (a hand-over costs ~10 us: not for a few doublings)
         const size_t half = J.k / 2, kk = J.k;
         HostHelper& hh = host_helper(&C);
         hh.run([finish_one, half, kk] { for (size_t j = half; j < kk; j++) finish_one(j); });
@@ -2363,9 +2208,7 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
 int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, void* scratch) {
     const int W = windows_of(c);
     dim3 grid((unsigned)((n + 63) / 64));                  // small blocks: the chain of 255 doublings per point is pure latency, one wave per SIMD is the fastest
-    if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_precompute<FqParams>), grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
-    else hipLaunchKernelGGL((k_precompute<FpParams>), grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
-    KH_HIP(hipGetLastError());
+    KH_CURVE_LAUNCH(curve, k_precompute<F>, grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
     return KH_OK;
 }
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c) {
@@ -2373,9 +2216,7 @@ int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size
     DevBuf& scratch = C.scratch("precompute");
     int rc = scratch.reserve((size_t)(W - 1) * n * 128); if (rc) return rc;
     dim3 grid((unsigned)((n + 255) / 256));
-    if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_precompute<FqParams>), grid, dim3(256), 0, C.stream, (uint8_t*)tables, inf, n, c, W, scratch.as<uint8_t>());
-    else hipLaunchKernelGGL((k_precompute<FpParams>), grid, dim3(256), 0, C.stream, (uint8_t*)tables, inf, n, c, W, scratch.as<uint8_t>());
-    KH_HIP(hipGetLastError());
+    KH_CURVE_LAUNCH(curve, k_precompute<F>, grid, dim3(256), 0, C.stream, (uint8_t*)tables, inf, n, c, W, scratch.as<uint8_t>());
     KH_HIP(hipStreamSynchronize(C.stream));
     if (scratch.cap > ((size_t)1 << 30)) scratch.release();     // do not pin GBs of scratch
     return KH_OK;
@@ -2405,9 +2246,7 @@ __global__ void k_debug_field(int op, const u64* a, const u64* b, u64* out, size
 }
 int debug_field_op(Context& C, int field, int op, const u64* a, const u64* b, u64* out, size_t n) {
     dim3 grid((unsigned)((n + 255) / 256));
-    if (field == KH_FIELD_FP) hipLaunchKernelGGL((k_debug_field<FpParams>), grid, dim3(256), 0, C.stream, op, a, b, out, n);
-    else hipLaunchKernelGGL((k_debug_field<FqParams>), grid, dim3(256), 0, C.stream, op, a, b, out, n);
-    KH_HIP(hipGetLastError());
+    KH_FIELD_LAUNCH(field, k_debug_field<F>, grid, dim3(256), 0, C.stream, op, a, b, out, n);
     return KH_OK;
 }
 // out = XYZZ (128 B) so the host can normalise
@@ -2452,15 +2291,11 @@ __global__ void k_debug_quad(int op, const u64* p, const uint8_t* pinf, const u6
 int debug_point_op(Context& C, int curve, int op, const u64* p, const uint8_t* pinf, const u64* q, const uint8_t* qinf, uint8_t* out, size_t n) {
     if (op == 4 || op == 5) {
         dim3 qgrid((unsigned)((4 * n + 255) / 256));
-        if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_debug_quad<FqParams>), qgrid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
-        else hipLaunchKernelGGL((k_debug_quad<FpParams>), qgrid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
-        KH_HIP(hipGetLastError());
+        KH_CURVE_LAUNCH(curve, k_debug_quad<F>, qgrid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
         return KH_OK;
     }
     dim3 grid((unsigned)((n + 255) / 256));
-    if (curve == KH_CURVE_VESTA) hipLaunchKernelGGL((k_debug_point<FqParams>), grid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
-    else hipLaunchKernelGGL((k_debug_point<FpParams>), grid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
-    KH_HIP(hipGetLastError());
+    KH_CURVE_LAUNCH(curve, k_debug_point<F>, grid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
     return KH_OK;
 }
 

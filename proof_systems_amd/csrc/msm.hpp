@@ -7,7 +7,6 @@
 
 namespace kh {
 
-int msm_pick_window(size_t n);
 // builds the window tables 2^(c*w) * P_i in place: `tables` holds W x n x 64 B with table 0 = the basis
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c);
 int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, void* scratch);      // asynchronous, scratch = (W - 1) x n x 128 bytes
@@ -23,7 +22,7 @@ size_t rebase_bucket_bytes(size_t N);
 size_t rebase_part_bytes(size_t N);
 size_t rebase_list_bytes(size_t Q);
 static constexpr int MSM_PRECOMP_C = 16;          // window width of the precomputed tables
-constexpr int windows_of(int c) { return (256 + c - 1) / c; }      // windows of c bits that cover a 256-bit scalar = tables of a set
+// (windows_of(c): the windows of c bits that cover a 256-bit scalar = tables of a set -- msm_plan.hpp)
 static constexpr int MSM_WIDE_C = 20;             // ... of the second table set big bases get: 13 windows, 2^19 buckets (msm.hip, "wide windows")
 void msm_set_wide_min_n(size_t n);
 void msm_set_sort_staging(unsigned entries, unsigned max_passes);   // k_part2_sort's staged scatter (kh_msm_set_sort_staging)
@@ -32,9 +31,7 @@ size_t msm_wide_min_n();                          // MSMs of at least this many 
                                                   // 2^20 896 -> 960..1000, 2^21 770 -> 976, 2^22 861 -> 992
 static constexpr size_t MSM_PRECOMP_MIN_N = 1024; // smaller bases keep the plain per-window path
 // enqueue all device work of k MSMs on slot S (returns immediately); msm_finish waits for it and does the host part
-// flags: MSM_SPREAD_SCALARS (msm.hip, "the caller vouches ..."), MSM_LATENCY
-static constexpr int MSM_SPREAD_SCALARS = 2;
-static constexpr int MSM_LATENCY = 4;                              // the caller's critical path: the accumulation runs above the default wave priority too
+// flags: MSM_SPREAD_SCALARS, MSM_LATENCY (msm_plan.hpp)
 int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t offset, const uint64_t* scalars_dev, size_t n, size_t k, int mont,
                 int flags = 0);
 // flag_seen: the caller has read the job's launch count from S.done_flag (the result is in S.pinned): no wait on the event

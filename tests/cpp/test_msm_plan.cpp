@@ -1,0 +1,225 @@
+// The MSM launch plan (csrc/msm_plan.hpp) on the host: a sweep of shapes held to what the kernels of msm.hip rely on, and five shapes pinned to the
+// values the driver computed before the plan was a function of its own.  Stand-alone: msm_plan.hpp alone, no library, no GPU (tests/test_msm_plan.py builds
+// it under AddressSanitizer and UBSan).  Prints the number of plans checked; exits non-zero at the first property that does not hold.
+#include "../../proof_systems_amd/csrc/msm_plan.hpp"
+#include <stdio.h>
+#include <stdlib.h>
+
+using namespace kh;
+
+static const MsmShape* g_shape = nullptr;
+#define CHECK(cond)                                                                                                                                   \
+    do {                                                                                                                                              \
+        if (!(cond)) {                                                                                                                                \
+            const MsmShape& s_ = *g_shape;                                                                                                            \
+            fprintf(stderr, "%s:%d: %s\n  n=%zu k=%zu flags=%d precomp_c=%d wide=%d wide_c=%d glv=%d stride=%zu cus=%d wide_min_n=%zu stage=%u/%u\n", \
+                    __FILE__, __LINE__, #cond, s_.n, s_.k, s_.flags, s_.precomp_c, (int)s_.has_wide, s_.wide_c, (int)s_.glv, s_.stride, s_.num_cus,   \
+                    s_.wide_min_n, s_.stage_entries, s_.stage_maxpass);                                                                               \
+            exit(1);                                                                                                                                  \
+        }                                                                                                                                             \
+    } while (0)
+
+// a grid dimension: at least one block; x fits 31 bits, y and z the 16 bits HIP gives them
+static bool grid_x(size_t v) { return v >= 1 && v < ((size_t)1 << 31); }
+static bool grid_yz(size_t v) { return v >= 1 && v <= 65535; }
+
+enum Kind { PLAIN = 0, TAB16, TAB16_WIDE20, TAB16_WIDE17, TAB16_GLV, NKINDS };
+static MsmShape shape(size_t n, size_t k, int kind, int cus, int flags = 0) {
+    MsmShape s;
+    s.n = n; s.k = k; s.flags = flags; s.num_cus = cus;
+    s.basis_n = n;
+    if (kind != PLAIN) s.precomp_c = 16;
+    if (kind == TAB16_WIDE20 || kind == TAB16_WIDE17) { s.has_wide = true; s.wide_c = kind == TAB16_WIDE20 ? 20 : 17; }
+    if (kind == TAB16_GLV) s.glv = true;
+    s.wide_min_n = (size_t)1 << 19; s.stage_entries = 28672; s.stage_maxpass = 2;       // the defaults (KH_WIDE_MIN_N, KH_PART2_STAGE, KH_PART2_MAXPASS)
+    return s;
+}
+
+static size_t n_refused = 0, n_fused = 0, n_part = 0, n_plain = 0, n_wide = 0, n_staged = 0;
+
+static void check(const MsmShape& sh) {
+    g_shape = &sh;
+    MsmPlan P; const char* why = nullptr;
+    const int rc = msm_plan(sh, P, &why);
+    const size_t n = sh.n, k = sh.k, two31 = (size_t)1 << 31;
+    const size_t tab_stride = sh.stride ? sh.stride : sh.basis_n;
+    // the entries are 31-bit table indices + the sign bit (k_scatter, k_part_sort, k_part2_sort, k_sort_fused: pt_offset-free index | sign << 31), and the
+    // sort's offsets are u32 counts of at most M entries: refused exactly when either does not fit
+    const bool must_refuse = n * (size_t)P.W * k >= two31 || tab_stride * (size_t)(P.precomp ? P.W : 1) + sh.batch_stride * k >= two31;
+    CHECK((rc != 0) == must_refuse);
+    if (rc) { CHECK(why != nullptr); n_refused++; return; }
+    CHECK(P.M == n * (size_t)P.W * k && P.tot_e == (size_t)P.W * n && P.nkeys == P.ngroups * P.nb && P.nb == 1u << (P.c - 1));
+    CHECK(P.ngroups == (P.precomp ? k : k * (size_t)P.W));
+    // exactly one sort path (the enum); wide has only the partitioned kernels (k_part2_*)
+    CHECK(P.sort == SORT_PLAIN || P.sort == SORT_FUSED || P.sort == SORT_PARTITIONED);
+    if (P.wide) CHECK(P.sort == SORT_PARTITIONED);
+    CHECK(grid_x((n + 255) / 256) && grid_yz(k));                                      // k_digits: grid (ceil(n / 256), k)
+    if (P.glv) CHECK(P.W % 2 == 0 && (P.W / 2) * P.c >= 128);                          // k_digits_glv: W / 2 windows for each 128-bit half
+    else CHECK(P.W * P.c >= 256);                                                      // k_digits: the windows cover a 256-bit scalar
+    if (P.sort == SORT_FUSED) {
+        n_fused++;
+        const FusedGeom& fg = P.fg;
+        // k_sort_fused spins on grid barriers: its blocks (and those of three more jobs in flight) must all be resident, two per CU
+        CHECK(sh.num_cus >= 128 && k <= 4);
+        CHECK(fg.kpt >= 1 && fg.kpt <= (u32)FUSED_KPT);                                // keys per thread live in registers: u32 [FUSED_KPT]
+        const size_t blocks = (size_t)fg.bpg * fg.k * fg.split;
+        CHECK(blocks >= 1 && blocks <= (size_t)FUSED_B);                               // the barrier words in ws_sync: 2 * FUSED_B block totals
+        CHECK((size_t)fg.bpg * fg.k * fg.split * FUSED_T * fg.kpt >= P.nkeys + 1);     // the block scans cover every key and the total
+        const size_t chunk4 = (P.tot_e / 4 + fg.bpg - 1) / fg.bpg + 1;
+        CHECK(P.tot_e % 4 == 0 && chunk4 <= (size_t)FUSED_V * FUSED_T);                // a block's chunk of digits, as int4's in registers: [FUSED_V] per thread
+        CHECK(fg.sub * fg.split == P.nb && fg.sub <= (u32)FUSED_C * FUSED_T);          // a block's cursors: [FUSED_C] per thread
+        CHECK((size_t)fg.sub * 4 <= 131072);                                           // dynamic LDS, within what the attribute asks for
+        CHECK(fg.n == n && fg.nb == P.nb && fg.W == (u32)P.W && fg.k == k && fg.nkeys == P.nkeys && fg.room == P.room && fg.kmin == P.kmin);
+    } else if (P.sort == SORT_PARTITIONED) {
+        n_part++;
+        CHECK(grid_x(P.part_nblk) && grid_yz(k));                                      // k_part_hist / k_part(2)_scatter: grid (part_nblk, k); pass B: (PART_P, k)
+        CHECK(P.part_size == k * (size_t)PART_P * P.part_nblk && P.part_size + 1 < two31);      // the scanned (partition, block) matrix, u32 offsets
+        CHECK(P.tot_e < two31);                                                        // tot_e is a u32 kernel argument
+        if (!P.wide) {
+            // k_part_scatter's record: 7 low bucket bits | sign | 4 window bits | 20 point bits
+            CHECK(P.nb == ((u32)PART_P << PART_LOW) && P.part_low == (u32)PART_LOW && P.W <= 16 && n <= ((size_t)1 << 20));
+        }
+    } else {
+        n_plain++;
+        CHECK((size_t)P.nb * 4 <= 131072);                                             // k_hist / k_scatter: one LDS counter per bucket
+        CHECK(grid_x((size_t)P.S) && grid_yz((size_t)P.W) && grid_yz(k));              // grid (S, W, k)
+        CHECK(P.g.n == n && P.g.nb == P.nb && P.g.S == P.S && P.g.W == P.W && P.g.precomp == P.precomp && P.g.pt_stride == tab_stride);
+        CHECK(P.Sq == (P.precomp ? P.W * P.S : P.S));                                  // k_key_totals sums Sq slice histograms per key
+        CHECK(grid_x((P.nkeys + 1 + 255) / 256));
+    }
+    if (P.wide) {
+        n_wide++;
+        const WideGeom& wg = P.wg;
+        CHECK(P.tot_e <= ((size_t)1 << 26) && k <= 4);
+        CHECK(P.part_nblk <= 1024);                                                    // pass B finds a record's pass-A block in the scanned matrix: <= 1024 blocks
+        CHECK((P.tot_e + P.part_nblk - 1) / P.part_nblk <= 65536);                     // pass A's record carries a 16-bit position inside its block's run of digits
+        CHECK(P.part_low == (u32)P.c - 9 && P.part_low <= PART2_MAXLOW);               // pass B: 2^low LDS cursors (array bound)
+        CHECK(((1u << P.part_low) % wide_og) == 0);                                    // k_part2_sort interleaves og consecutive ranks of a partition
+        CHECK(wg.nb == P.nb && wg.lo + wg.hi == (u32)P.c - 1 && wg.rlog == wide_rlog); // bucket = (hi digit, lo digit)
+        CHECK(wg.flog >= 1 && wg.rlog + wg.flog <= wg.hi);                             // a run of chunks stays inside one marginal of either plane
+        CHECK(P.wide_items == 2u * (P.nb >> wg.rlog) * (u32)P.ngroups && grid_x((P.wide_items + 255) / 256));     // k_wide_a1: thread per chunk of both planes
+        CHECK(P.wide_runs == P.wide_items >> wg.flog && grid_x((P.wide_runs + 63) / 64));                         // k_wide_l2: thread per run
+        CHECK(P.wide_runs / (u32)P.ngroups / 16u >= 1 && P.wide_runs % (16u * (u32)P.ngroups) == 0 && grid_yz(P.ngroups));   // k_wide_a2: wave per 16 run records
+        CHECK(P.part2_lds <= 131072 && P.part2_lds >= ((size_t)3 << PART2_MAXLOW) * 4);     // the planning phase's three lists of 2^MAXLOW words; the attribute's 128 KB
+        CHECK(P.part2_maxpass <= PART2_MAXPASS);
+        if (P.stage_now) {                                                             // staged scatter: the staging area shares the lists' words, + 2^MAXLOW bytes
+            n_staged++;
+            CHECK(P.stage_now > 2048 && P.part2_lds >= (size_t)P.stage_now * 4 + ((size_t)1 << PART2_MAXLOW));
+            CHECK(P.tot_e / PART_P <= (size_t)P.part2_maxpass * (P.stage_now - 1024u)); // a partition's share fits max_pass passes, each with the 1024-entry margin
+        }
+        CHECK(grid_x(P.nkeys / 256 + 1));                                              // k_wide_fixup
+        CHECK(P.nkeys % 256 == 0 && (size_t)P.acc_blocks * 256 == P.nkeys);            // k_acc_wide29: thread per bucket, no bound check on the key
+        CHECK(P.wide_acc_lds <= sh.lds_per_block && P.wide_acc_lds % 1024 == 0);
+        CHECK(P.slist_off + P.nkeys <= 3 * P.max_tasks + 8);                           // ws_xlist: [2] counts, (key, chunk) pairs of the extra chunks, the split buckets' keys
+        CHECK(P.nb >> (wg.rlog + wg.flog) >= 1 && ((size_t)1 << wg.lo) >= 1);          // ws_a1 / ws_l2 / ws_a2 are not empty
+        CHECK(!P.quad_sum && !P.spread && !P.glv);
+    } else {
+        // k_accumulate29: thread per task; tasks <= entries / K + one remainder per bucket, K >= 4 (KTab's entries; kmin = 8 otherwise)
+        CHECK(P.max_tasks >= P.M / 4 + P.nkeys + 1 && (size_t)P.acc_blocks * 256 >= P.max_tasks);
+        CHECK(grid_x((4 * P.nkeys + 255) / 256));                                      // k_bucket_sum_q: four lanes per bucket
+        if (P.sort != SORT_FUSED) CHECK(grid_x((P.nkeys + 1 + 1023) / 1024));          // k_ntask / k_len_rank
+    }
+    CHECK(grid_x(P.acc_blocks) && P.max_tasks < two31);
+    CHECK(P.kmin >= 4 && P.kmin <= MAX_K && P.room >= 1);                               // pick_K: K = clamp(ceil(entries / room), kmin, MAX_K)
+    for (int i = 0; i < 48; i++) CHECK(P.ktab.k[i] == 0 || (P.ktab.k[i] >= 4 && P.ktab.k[i] <= MAX_K));
+    CHECK(P.bigcap >= P.nkeys + P.max_tasks / CHUNK && 2 + 4 * P.bigcap < two31);       // big buckets <= nkeys, chunk items <= tasks / CHUNK + nkeys; (u32)bigcap
+    CHECK(P.spread ? P.quad_sum && (sh.flags & MSM_SPREAD_SCALARS) : true);
+    CHECK(P.quad_sum == (!P.wide && P.precomp && P.ngroups <= 8));                      // k_bucket_sum_q takes every bucket: few groups over the tables
+    CHECK(P.acc_prio == ((sh.flags & MSM_LATENCY) ? 1u : 0u));
+    // the tail
+    CHECK(P.m >= 1 && P.nb % P.m == 0 && P.nseg * P.m == P.nb);                         // k_reduce_seg: nseg running sums of m buckets
+    CHECK(P.nblk1 >= 1 && (size_t)P.nblk1 * SUM_BLK >= P.nseg);                         // k_sum_level: blocks of SUM_BLK records cover the segments
+    if (P.planes) {
+        const MargGeom& mg = P.mg;
+        const u32 bits = P.wide ? P.wg.lo : (u32)P.c - 1;
+        CHECK(P.planes == 3 && mg.nb == 1u << bits);
+        CHECK(mg.wd[0] + mg.wd[1] + mg.wd[2] == bits && mg.sh[0] == 0 && mg.sh[1] == mg.wd[0] && mg.sh[2] == mg.wd[0] + mg.wd[1]);
+        CHECK(mg.wd[0] <= 5 && mg.wd[1] <= 5 && mg.wd[2] <= 5);                        // k_marginals: 32 blocks in x, one per value of a field (wide: the fields split lo)
+        CHECK(grid_yz(P.tail_groups) && P.tail_groups == (P.wide ? 2 * P.ngroups : P.ngroups));      // grid (32, 3, groups) and (3, groups)
+        CHECK(P.nout == 3 * P.tail_groups);                                            // k_marginal_fin(_q): block (plane, group) writes one 128-byte record
+    } else {
+        CHECK(!P.wide && !P.direct_out && P.nout == P.ngroups);                        // k_sum_final: one record per group
+        CHECK(grid_x((P.ngroups * P.nseg + 127) / 128) && grid_x(P.nblk1) && grid_yz(P.ngroups));
+    }
+    CHECK(P.nout >= 1 && P.nout * 128 < two31);
+    if (P.direct_out) CHECK(P.planes == 3);                                             // only k_marginal_fin_q writes to host memory
+    if (P.want_flag) CHECK(P.planes == 3);
+    // workspaces: what msm_reserve computes from the plan is not empty where a launch takes the buffer
+    CHECK(P.M >= 1 && P.nkeys >= 1 && P.Sq >= 1 && P.max_tasks >= 1 && P.bigcap >= 1);
+    CHECK(std::max(P.ngroups * (size_t)(P.nseg + P.nblk1), P.nout * (size_t)32) >= 1);
+    if (P.sort == SORT_FUSED) CHECK((size_t)P.fg.k * P.fg.bpg * P.nb >= 1);
+}
+
+#define PIN(cond) do { if (!(cond)) { fprintf(stderr, "%s:%d: pinned shape: %s\n", __FILE__, __LINE__, #cond); exit(1); } } while (0)
+static MsmPlan plan_of(const MsmShape& sh) {
+    MsmPlan P; const char* why = nullptr;
+    if (msm_plan(sh, P, &why)) { fprintf(stderr, "pinned shape refused: %s\n", why); exit(1); }
+    return P;
+}
+static void pinned() {
+    {   // 2^20 scalars, one MSM, 16-bit + wide 20-bit tables, 256 CUs: the benchmark's MSM
+        const MsmPlan P = plan_of(shape((size_t)1 << 20, 1, TAB16_WIDE20, 256));
+        PIN(P.wide && P.c == 20 && P.W == 13 && P.sort == SORT_PARTITIONED && P.precomp == 1 && !P.glv);
+        PIN(P.nb == 1u << 19 && P.ngroups == 1 && P.nkeys == (size_t)1 << 19 && P.M == (size_t)13 << 20);
+        PIN(P.part_low == 11 && P.part_nblk == 256 && P.wg.lo == 10 && P.wg.hi == 9 && P.wg.rlog == 4 && P.wg.flog == 2);
+        PIN(P.planes == 3 && P.mg.wd[0] == 4 && P.mg.wd[1] == 3 && P.mg.wd[2] == 3 && P.tail_groups == 2 && P.nout == 6 && P.direct_out && P.want_flag);
+    }
+    {   // fifteen witness columns of 2^16 over the 16-bit tables
+        const MsmPlan P = plan_of(shape((size_t)1 << 16, 15, TAB16, 256));
+        PIN(!P.wide && P.c == 16 && P.W == 16 && P.sort == SORT_PARTITIONED && !P.quad_sum);
+        PIN(P.nb == 1u << 15 && P.ngroups == 15 && P.S == 2 && P.part_nblk == 34);
+        PIN(P.planes == 3 && P.mg.wd[0] == 5 && P.mg.wd[1] == 5 && P.mg.wd[2] == 5);
+    }
+    {   // a lone 2^12 commitment over the tables: the one-launch sort on a whole chip ...
+        const MsmPlan P = plan_of(shape((size_t)1 << 12, 1, TAB16, 256));
+        PIN(P.sort == SORT_FUSED && P.fg.bpg == 16 && P.fg.split == 2 && P.fg.sub == 1u << 14 && P.fg.kpt == 2);
+    }
+    {   // ... and the multi-launch sort in a partitioned mode (64 CUs)
+        const MsmPlan P = plan_of(shape((size_t)1 << 12, 1, TAB16, 64));
+        PIN(P.sort == SORT_PLAIN);
+    }
+    {   // 512 scalars over a plain basis: per-window buckets, Horner on the host
+        const MsmPlan P = plan_of(shape(512, 1, PLAIN, 256));
+        PIN(P.c == 6 && P.W == 43 && P.precomp == 0 && P.ngroups == 43 && P.nb == 32);
+        PIN(P.planes == 0 && P.m == 4 && P.nseg == 8 && P.sort == SORT_PLAIN && !P.direct_out && !P.want_flag);
+    }
+    {   // the table-index bound alone: 16 tables of 2^27 points
+        MsmShape sh = shape(1024, 1, TAB16, 256); sh.stride = (size_t)1 << 27;
+        MsmPlan P; const char* why = nullptr;
+        PIN(msm_plan(sh, P, &why) != 0 && why);
+        sh.stride = ((size_t)1 << 27) - 1;
+        PIN(msm_plan(sh, P, &why) == 0);
+    }
+}
+
+int main() {
+    static const size_t NS[] = {1, 2, 3, 4, 511, 512, 1023, 1024, 4095, 4096, (size_t)1 << 13, (size_t)1 << 16, ((size_t)1 << 16) + 1, (size_t)1 << 17,
+                                ((size_t)1 << 19) - 1, (size_t)1 << 19, (size_t)1 << 20, (size_t)1 << 21, (size_t)1 << 22};
+    static const size_t KS[] = {1, 2, 4, 5, 8, 15, 16, 23, 64};
+    static const int CUS[] = {64, 128, 256};
+    static const int FLAGS[] = {0, MSM_SPREAD_SCALARS, MSM_LATENCY};
+    static const u32 STAGING[][2] = {{0, 2}, {2560, 8}, {4096, 3}, {3000, 1}, {28672, 2}};     // the pairs of tests/test_gpu_wide_msm.py
+    static const size_t WIDE_MIN[] = {(size_t)1 << 19, (size_t)1 << 12};                        // the default, and the tests' way to the wide path at small n
+    size_t plans = 0;
+    for (size_t n : NS) for (size_t k : KS) for (int kind = 0; kind < NKINDS; kind++) for (int cus : CUS) for (int flags : FLAGS)
+        for (const auto& st : STAGING) for (size_t wmin : WIDE_MIN) {
+            MsmShape sh = shape(n, k, kind, cus, flags);
+            sh.stage_entries = st[0]; sh.stage_maxpass = st[1]; sh.wide_min_n = wmin;
+            check(sh); plans++;
+        }
+    // the switches: no fused sort, no done flag, the plain tail kernel for batches
+    for (size_t n : NS) for (size_t k : KS) for (int kind = 0; kind < NKINDS; kind++) for (int sw = 0; sw < 3; sw++) {
+        MsmShape sh = shape(n, k, kind, 256);
+        if (sw == 0) sh.fused_off = true; else if (sw == 1) sh.flag_off = true; else sh.fin_quad = false;
+        check(sh); plans++;
+        MsmPlan P; const char* why = nullptr;
+        if (msm_plan(sh, P, &why) == 0) {
+            if (sw == 0 && P.sort == SORT_FUSED) { fprintf(stderr, "fused_off ignored\n"); return 1; }
+            if (sw == 1 && P.want_flag) { fprintf(stderr, "flag_off ignored\n"); return 1; }
+        }
+    }
+    pinned();
+    if (!n_refused || !n_fused || !n_part || !n_plain || !n_wide || !n_staged) { fprintf(stderr, "a path was never taken\n"); return 1; }
+    printf("plans %zu refused %zu fused %zu partitioned %zu plain %zu wide %zu staged %zu\n", plans, n_refused, n_fused, n_part, n_plain, n_wide, n_staged);
+    return 0;
+}
