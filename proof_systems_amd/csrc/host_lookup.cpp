@@ -6,33 +6,25 @@
 // vectors out, one thread (the Python loop it replaced cost 0.36 s of a 0.38 s proof at 2^16 rows).  kh_prove and the Python prover no longer come
 // through here: their values and table are device-resident and csrc/lookup_sorted.hip (kh_lookup_sorted_dev) runs the same join there, without the
 // two transfers.  This function stays for callers with host-side columns and as the reference the device path is tested against, position for
-// position (tests/test_gpu_lookup_sorted_dev.py); the hash and the first-occurrence rule below are the ones the kernels use.
+// position (tests/test_gpu_lookup_sorted_dev.py); the hash (lookup_hash.hpp) and the first-occurrence rule below are the ones the kernels use.
 // Nothing here does field arithmetic: values are compared as 32-byte strings (canonical Montgomery limbs are unique).
 #include <stdint.h>
 #include <string.h>
 #include <vector>
 
 #include "../../include/kimchi_hip.h"
+#include "lookup_hash.hpp"
 
 namespace kh { void set_error(const char* fmt, ...); }
 
-namespace {
-struct Key { uint64_t l[4]; };
-inline bool same(const Key& a, const Key& b) { return ((a.l[0] ^ b.l[0]) | (a.l[1] ^ b.l[1]) | (a.l[2] ^ b.l[2]) | (a.l[3] ^ b.l[3])) == 0; }
-inline uint64_t hash(const Key& k) {
-    uint64_t h = k.l[0] * 0x9e3779b97f4a7c15ULL ^ k.l[1];
-    h = (h ^ (h >> 29)) * 0xbf58476d1ce4e5b9ULL ^ k.l[2];
-    h = (h ^ (h >> 32)) * 0x94d049bb133111ebULL ^ k.l[3];
-    return h ^ (h >> 31);
-}
-}  // namespace
+using namespace kh;                                     // Key, same, hash, lookup_slots
 
 extern "C" int kh_lookup_sorted(const uint64_t* table, size_t lookup_rows, const uint64_t* values, size_t value_stride, size_t max_per_row, uint64_t* out,
                                 size_t* bad_row) {
     if (!table || !values || !out || lookup_rows == 0 || max_per_row == 0 || value_stride < lookup_rows) { kh::set_error("kh_lookup_sorted: bad argument"); return KH_E_INVALID; }
     if (bad_row) *bad_row = (size_t)-1;
     const Key* T = (const Key*)table;
-    size_t cap = 16; while (cap < 2 * lookup_rows) cap <<= 1;
+    const size_t cap = lookup_slots(lookup_rows);
     const size_t mask = cap - 1;
     std::vector<uint32_t> slot(cap, 0xffffffffu);      // open addressing: table index of the FIRST occurrence of a value
     std::vector<uint32_t> cnt(lookup_rows, 1);         // counts live on first occurrences; a repeated table entry keeps its 1

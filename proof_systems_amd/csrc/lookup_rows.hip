@@ -1,7 +1,7 @@
 // lookup_rows.hip -- the rows of GateType::Lookup on the device, for kh_lookup_witness_dev and KH_STEP_LOOKUP (csrc/witness_steps.cpp): a row holds
 // (table id, key, value, key, value, key, value); the circuit knows the keys, the values are what the table holds at them.  The table is two device
 // columns of table_len elements -- keys and values --, the keys of the call n x 3 elements; a hash set over the table's keys is built per call in
-// scratch and probed once per (slot, instance).  No field arithmetic: elements are compared as 32-byte strings (lookup_key.cuh), with the scheme of
+// scratch and probed once per (slot, instance).  No field arithmetic: elements are compared as 32-byte strings (lookup_hash.hpp), with the scheme of
 // lookup_sorted.hip.
 //
 //   (memset)          slots = EMPTY (0xff bytes)
@@ -82,16 +82,15 @@ k_lookup_rows(const u64* __restrict__ table_keys, const u64* __restrict__ table_
     if (flags && __any(miss) && (threadIdx.x & 63u) == 0) atomicOr(flags, 1u << bit);
 }
 
-// the slots of a table of L entries: a power of two of at least 2 L u32
-static size_t lookup_rows_capacity(size_t L) { size_t cap = 16; while (cap < 2 * L) cap <<= 1; return cap; }
-size_t lookup_rows_slot_bytes(size_t table_len) { return lookup_rows_capacity(table_len) * sizeof(u32); }
+// the slots of a table of L entries: lookup_slots(L) u32 (lookup_hash.hpp)
+size_t lookup_rows_slot_bytes(size_t table_len) { return lookup_slots(table_len) * sizeof(u32); }
 
 // (the callers in witness_steps.cpp have validated pointers, sizes and the placement: 1 <= table_len < 2^31, n >= 1, 3 n lanes fit a grid; slots_dev
 // holds scratch_bytes, which the caller asked lookup_rows_slot_bytes for)
 int lookup_rows(Context& C, const uint64_t* table_id, const uint64_t* table_keys_dev, const uint64_t* table_values_dev, size_t table_len,
                 const uint64_t* keys_dev, size_t n, const WitnessPlace& at, uint64_t* out_values_dev, uint32_t* flags_dev, unsigned bit, uint32_t* slots_dev,
                 size_t scratch_bytes) {
-    const size_t cap = lookup_rows_capacity(table_len);
+    const size_t cap = lookup_slots(table_len);
     KH_REQUIRE(slots_dev && scratch_bytes >= cap * sizeof(u32) && table_len >= 1 && table_len < ((size_t)1 << 31) && n >= 1 && n <= WAVE_BLOCK_MAX_N / 3,
                "lookup_rows: bad shape");
     TableId id;

@@ -18,7 +18,7 @@
 // All memory-bound, 256-thread blocks.  Every index is below 2^31 (the caller refuses (max_per_row + 1) L >= 2^31).
 #include "common.hpp"
 #include "msm.hpp"
-#include "lookup_key.cuh"                                    // Key, load_key, same, hash (shared with lookup_rows.hip)
+#include "lookup_key.cuh"                                    // load_key; Key, same, hash, lookup_slots (lookup_hash.hpp)
 
 namespace kh {
 
@@ -118,14 +118,13 @@ k_sorted_expand(const u64* __restrict__ table, const u32* __restrict__ off, u32 
 }
 
 // scratch: words for sorted_scratch_words(L) u32; status_dev = 2 words inside it (see sorted_status_offset).  Queues everything on C.stream.
-size_t lookup_sorted_capacity(size_t L) { size_t cap = 16; while (cap < 2 * L) cap <<= 1; return cap; }
-size_t lookup_sorted_scratch_words(size_t L) { return lookup_sorted_capacity(L) + 2 * (L + 1) + 2; }
-size_t lookup_sorted_status_offset(size_t L) { return lookup_sorted_capacity(L) + 2 * (L + 1); }
+size_t lookup_sorted_scratch_words(size_t L) { return lookup_slots(L) + 2 * (L + 1) + 2; }
+size_t lookup_sorted_status_offset(size_t L) { return lookup_slots(L) + 2 * (L + 1); }
 
 int lookup_sorted_run(Context& C, const uint64_t* table_dev, size_t L, const uint64_t* values_dev, size_t value_stride, size_t mpr, uint64_t* out_dev,
                       size_t out_stride, uint32_t* scratch_dev) {
     KH_REQUIRE(L >= 1 && mpr >= 1 && (mpr + 1) * L < ((size_t)1 << 31), "lookup_sorted_run: bad shape");
-    const size_t cap = lookup_sorted_capacity(L);
+    const size_t cap = lookup_slots(L);
     u32* const slots = scratch_dev;
     u32* const cnt = slots + cap;
     u32* const off = cnt + (L + 1);

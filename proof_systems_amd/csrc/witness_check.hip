@@ -37,6 +37,7 @@
 #include "common.hpp"
 #include "field.cuh"
 #include "msm.hpp"
+#include "lookup_key.cuh"
 
 namespace kh {
 
@@ -128,33 +129,13 @@ k_witness_wires(const u64* __restrict__ w, const u32* __restrict__ wires, u32 n,
     report(status, bad, word, ST_CELLS);
 }
 
-// ---- lookups: the hash join.  Keys are compared as bytes, hashed as in lookup_sorted.hip / host_lookup.cpp
+// ---- lookups: the hash join.  Keys are compared as bytes, hashed as in lookup_sorted.hip / host_lookup.cpp (lookup_hash.hpp)
 constexpr u32 LOOKUP_EMPTY = 0xffffffffu;
 constexpr u32 SUB_LOOKUP0 = 8;
 
-struct Key { u64 l[4]; };
-struct Tuple { Key k[4]; };                              // table id, entry 0..2
-__device__ __forceinline__ Key load_key(const u64* __restrict__ p) {
-    const ulonglong2 a = ((const ulonglong2*)p)[0], b = ((const ulonglong2*)p)[1];
-    Key k; k.l[0] = a.x; k.l[1] = a.y; k.l[2] = b.x; k.l[3] = b.y;
-    return k;
-}
+// (Key, Tuple = (table id, entry 0..2), same, hash: lookup_hash.hpp; load_key: lookup_key.cuh)
 __device__ __forceinline__ Key zero_key() { Key k; k.l[0] = k.l[1] = k.l[2] = k.l[3] = 0; return k; }
 __device__ __forceinline__ bool is_zero(const Key& a) { return (a.l[0] | a.l[1] | a.l[2] | a.l[3]) == 0; }
-__device__ __forceinline__ bool same(const Key& a, const Key& b) { return ((a.l[0] ^ b.l[0]) | (a.l[1] ^ b.l[1]) | (a.l[2] ^ b.l[2]) | (a.l[3] ^ b.l[3])) == 0; }
-__device__ __forceinline__ bool same(const Tuple& a, const Tuple& b) { return same(a.k[0], b.k[0]) && same(a.k[1], b.k[1]) && same(a.k[2], b.k[2]) && same(a.k[3], b.k[3]); }
-__device__ __forceinline__ u64 hash(const Key& k) {
-    u64 h = k.l[0] * 0x9e3779b97f4a7c15ULL ^ k.l[1];
-    h = (h ^ (h >> 29)) * 0xbf58476d1ce4e5b9ULL ^ k.l[2];
-    h = (h ^ (h >> 32)) * 0x94d049bb133111ebULL ^ k.l[3];
-    return h ^ (h >> 31);
-}
-__device__ __forceinline__ u32 hash(const Tuple& t) {
-    u64 h = hash(t.k[0]);
-#pragma unroll
-    for (int i = 1; i < 4; i++) h = (h ^ (h >> 27)) * 0x9e3779b97f4a7c15ULL + hash(t.k[i]);
-    return (u32)(h ^ (h >> 32));
-}
 
 // the combined table as a set of tuples: columns 0..2 (absent columns are zero), the id column (absent: every id is 0), the runtime rows' column 1
 struct LookupTable {
@@ -263,9 +244,8 @@ __global__ void __launch_bounds__(256) k_witness_lookup_probe(LookupProbeArgs a)
 static constexpr size_t WC_STATUS_WORDS = 4;
 static constexpr size_t wc_const_words(int gate) { size_t n = WC_STATUS_WORDS; for (int k = 0; k < gate; k++) n += 4 * (size_t)GATE_NCONST[k]; return n; }
 size_t witness_check_scratch_bytes() { return 8 * wc_const_words(GATE_CHECKED_COUNT); }
-static size_t wc_lookup_slots(size_t L) { size_t cap = 16; while (cap < 2 * L) cap <<= 1; return cap; }
 static size_t wc_lookup_col_words(size_t W) { return (W + 1) & ~(size_t)1; }
-size_t witness_check_lookup_scratch_bytes(size_t L, size_t W, size_t rt_len) { return 8 * (wc_lookup_col_words(W) + 4 * rt_len) + 4 * wc_lookup_slots(L); }
+size_t witness_check_lookup_scratch_bytes(size_t L, size_t W, size_t rt_len) { return 8 * (wc_lookup_col_words(W) + 4 * rt_len) + 4 * lookup_slots(L); }
 
 int witness_check_num_constraints(int gate) { return gate >= 0 && gate < GATE_CHECKED_COUNT ? GATE_NCONSTRAINTS[gate] : 0; }
 
@@ -320,7 +300,7 @@ int witness_check_run(Context& C, int field, const uint64_t* witness_dev, const 
         u64* const cols_dev = status + wc_const_words(GATE_CHECKED_COUNT);
         u64* const runtime_dev = cols_dev + wc_lookup_col_words(W);
         u32* const slots = (u32*)(runtime_dev + 4 * lk->rt_len);
-        const size_t cap = wc_lookup_slots(L);
+        const size_t cap = lookup_slots(L);
         static const u64 pad = 0;
         // (runtime values that are on the device already are read where they are: their room in the scratch block stays unused)
         if ((rc = C.stage_upload(cols_dev, {{lk->tcols, W * 8}, {&pad, (wc_lookup_col_words(W) - W) * 8}, {lk->runtime, lk->runtime ? lk->rt_len * 32 : 0}}))) return rc;

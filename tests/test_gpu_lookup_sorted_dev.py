@@ -2,12 +2,23 @@
 device hash join + expansion over device-resident columns -- against the host entry point kh_lookup_sorted (csrc/host_lookup.cpp, itself pinned to
 the reference algorithm by tests/test_lookup_sorted.py): EXACT equality of every limb, the layout contract (only elements 0 .. lookup_rows of each
 output column are written, rows from lookup_rows on are not read), the missing-value report, scratch reuse, the argument refusals; and kh_prove /
-the Python prover on the device path (proof bytes, proofs equal to each other, the error of a spoiled witness, the call counter)."""
+the Python prover on the device path (proof bytes, proofs equal to each other, the error of a spoiled witness, the call counter).
+
+The host function shares the hash and the probing scheme with the kernels, so the cases with forced collisions (collision_case of
+tests/test_lookup_sorted.py: the whole table one probe chain across the end of the slot array) are held to the pure-Python reference_sorted as well."""
 import ctypes as C
+import os
 import random
+import sys
 
 import numpy as np
 import pytest
+
+from oracle import pasta as P
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lookup_collisions as LC  # noqa: E402
+from test_lookup_sorted import COLLISION_CASES, collision_case, miss_rows, reference_sorted  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -197,6 +208,76 @@ def test_argument_refusals_launch_nothing(khip):
     assert np.array_equal(d_o.download((mpr + 1, stride, 4)), khip.lookup_sorted(table, lookup_rows, values, mpr))
     for b in (d_t, d_v, d_o):
         b.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------- forced collisions
+def raw_call(khip, table, values, lookup_rows, mpr):
+    """(return code, bad_row, whether the sentinel-filled output is untouched) of the C entry point"""
+    d_t = khip.DevBuf(table.nbytes).upload(table); d_v = khip.DevBuf(values.nbytes).upload(values)
+    stride = lookup_rows + 1
+    fill = np.tile(SENTINEL, ((mpr + 1) * stride, 1))
+    d_o = khip.DevBuf((mpr + 1) * stride * 32).upload(fill)
+    bad = C.c_size_t(0)
+    try:
+        rc = khip.raw().kh_lookup_sorted_dev(d_t.ptr, lookup_rows, d_v.ptr, values.shape[1], mpr, d_o.ptr, stride, C.byref(bad))
+        untouched = np.array_equal(d_o.download(((mpr + 1) * stride, 4)), fill)
+    finally:
+        for b in (d_t, d_v, d_o):
+            b.free()
+    return rc, bad.value, untouched
+
+
+@pytest.mark.parametrize("mpr", (1, 3))
+@pytest.mark.parametrize("lookup_rows,merge", COLLISION_CASES)
+def test_colliding_tables_equal_the_reference_algorithm(khip, lookup_rows, merge, mpr):
+    """k_sorted_build / k_sorted_count on a table that is one probe chain across the end of the slot array (the preconditions are asserted in
+    collision_case): 600 and 1024 entries span several blocks of k_sorted_build, whose threads then contend for the slots of ONE chain; 8 and 1024 are
+    at exactly half load; in the 48 and 600 cases the hot key sits at entries 9, 23 and L - 1 of the chain.  Three runs each: the atomics arrive in
+    another order every time, the columns may not change.  An absent value whose home is the head of the chain, or its middle behind the wrap, is
+    reported only after the walk: the row, KH_E_INVALID, nothing written."""
+    case = collision_case(P.Fp, lookup_rows, mpr, merge)
+    table, values = np.array(case.table, dtype=np.uint64), np.array(case.values, dtype=np.uint64)
+    want = np.array(reference_sorted(list(case.table), case.values, lookup_rows, mpr), dtype=np.uint64)
+    assert want.shape == (mpr + 1, lookup_rows + 1, 4)
+    host = khip.lookup_sorted(table, lookup_rows, values, mpr)
+    for attempt in range(3):
+        got = run_dev(khip, table, values, lookup_rows, mpr)
+        assert np.array_equal(got, want), "run %d: first difference from the reference at (column, index, limb) %s" % (attempt, tuple(np.argwhere(got != want)[0]))
+        assert np.array_equal(got, host)
+    for name, absent in case.misses:
+        row = miss_rows(lookup_rows)[name]
+        bad = values.copy()
+        bad[mpr - 1, row] = absent
+        with pytest.raises(ValueError) as ref:
+            reference_sorted(list(case.table), [[tuple(int(x) for x in v) for v in col] for col in bad], lookup_rows, mpr)
+        assert ref.value.args[0] == row
+        with pytest.raises(ValueError) as dev:
+            run_dev(khip, table, bad, lookup_rows, mpr)
+        assert dev.value.args[0] == row, name
+        for attempt in range(3):
+            assert raw_call(khip, table, bad, lookup_rows, mpr) == (KH_E_INVALID, row, True), (name, attempt)
+    assert np.array_equal(run_dev(khip, table, values, lookup_rows, mpr), want)      # status and slots are cleared per call
+
+
+def test_tiny_random_tables_at_sixteen_slots(khip):
+    """64 tables of 1 .. 8 entries (16 slots, up to half load) of random canonical elements with repeats: the collisions that happen by themselves at
+    the smallest capacity, against the reference and the host"""
+    rnd = random.Random(64)
+    collided = repeats = 0
+    for _ in range(64):
+        lookup_rows, mpr = rnd.randrange(1, 9), rnd.randrange(1, 4)
+        pool = [LC.mont_limbs(P.Fp, rnd.randrange(P.Fp.p)) for _ in range(rnd.randrange((lookup_rows + 1) // 2, lookup_rows + 1))]
+        keys = pool + [rnd.choice(pool) for _ in range(lookup_rows - len(pool))]
+        rnd.shuffle(keys)
+        vals = [[rnd.choice(keys) for _ in range(lookup_rows)] for _ in range(mpr)]
+        assert LC.slots(lookup_rows) == 16
+        repeats += len(set(keys)) < lookup_rows
+        collided += LC.longest_run([LC.home(k, lookup_rows) for k in dict.fromkeys(keys)], 16).displacement > 0
+        table, values = np.array(keys, dtype=np.uint64), np.array(vals, dtype=np.uint64)
+        want = np.array(reference_sorted(keys, vals, lookup_rows, mpr), dtype=np.uint64)
+        got = run_dev(khip, table, values, lookup_rows, mpr)
+        assert np.array_equal(got, want) and np.array_equal(got, khip.lookup_sorted(table, lookup_rows, values, mpr)), (lookup_rows, mpr, keys)
+    assert collided >= 16 and repeats >= 16, (collided, repeats)    # (fixed by the seed: 19 of the 64 tables have a displaced key, 34 a repeated one)
 
 
 # ---------------------------------------------------------------------------------------------------------------- prover level

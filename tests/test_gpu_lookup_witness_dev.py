@@ -1,7 +1,10 @@
 """kh_lookup_witness_dev (csrc/lookup_rows.hip): the rows of GateType::Lookup written on the device from a table's two columns and the keys.
 
 The expected values are a Python dict over the integers this file puts into the table, first occurrence wins; every comparison is exact: the whole
-15 x COL_LEN witness against a sentinel-filled array with the expected cells replaced, so a cell the call must not write is checked too."""
+15 x COL_LEN witness against a sentinel-filled array with the expected cells replaced, so a cell the call must not write is checked too.
+
+Random keys at half load give probe chains of one or two slots; section 5 runs tables whose keys are made to collide (collision_case of
+tests/test_lookup_sorted.py, on the hash mirror tests/test_lookup_hash.py pins): the whole table is one chain across the end of the slot array."""
 import ctypes as C
 import os
 import random
@@ -14,7 +17,9 @@ from oracle import pasta as P
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import lookup_collisions as LC  # noqa: E402
 from test_gpu_limb_gadgets_dev import SENTINEL, SIZES, flag_word, mont, sentinel_buf  # noqa: E402
+from test_lookup_sorted import collision_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FIELDS = (P.Fp, P.Fq)
@@ -116,7 +121,7 @@ def test_rows_and_values(khip, F, n):
     tab.free()
 
 
-# ---- 2. table sizes: one entry, two, and 4096 entries in 8192 slots (probe chains longer than one)
+# ---- 2. table sizes: one entry, two, and 4096 entries in 8192 slots (probe chains longer than one, where random keys happen to make them: section 5 makes them)
 @pytest.mark.parametrize("F", FIELDS, ids=("fp", "fq"))
 @pytest.mark.parametrize("table_len", (1, 2, 4096))
 def test_table_sizes(khip, F, table_len):
@@ -227,3 +232,98 @@ def test_refusals_leave_everything_untouched(khip):
     assert lib.kh_lookup_witness_dev(0, None, None, None, 1, None, 0, None, 0, 0, None, 0, 0, None, None, 0) == 0
     for b in (tk, tv, keys, wit, out, flags):
         b.free()
+
+
+# ---- 5. forced collisions: the table is one probe chain that wraps from the last slot to slot 0
+COLLIDING = (1, 2, 8, 48, 600, 1024)                              # blocks are one wave: 600 and 1024 entries are 10 and 16 blocks of k_lookup_build on ONE chain
+PRESET = 0x00500003
+
+
+def colliding_table(khip, F, table_len):
+    """the keys of collision_case (its preconditions are asserted there: homes in the last two slots, one chain across the wrap, displacement; 8 and 1024
+    at exactly half load; 48 and 600 with ONE key at entries 9, 23 and L - 1) with distinct non-zero values -- so the three entries of the repeated key
+    differ in their values, and every probe of it must read entry 9's"""
+    case = collision_case(F, table_len, 1)
+    keys = list(case.keys)
+    rnd = random.Random(31 * table_len)
+    values = [rnd.randrange(1, F.p) for _ in keys]
+    assert len(set(values)) == table_len and len(set(keys)) == case.distinct
+    tab = Table(khip, F, keys, values)
+    if case.distinct < table_len:
+        assert keys[9] == keys[23] == keys[-1] and tab.at[keys[23]] == tab.at[keys[-1]] == values[9] and values[9] not in (values[23], values[-1])
+    return case, tab
+
+
+def preset_word(khip):
+    return khip.DevBuf(4).upload(np.array([PRESET], dtype=np.uint32))
+
+
+@pytest.mark.parametrize("F", FIELDS, ids=("fp", "fq"))
+@pytest.mark.parametrize("table_len", COLLIDING)
+def test_colliding_tables(khip, F, table_len):
+    """every entry of the table probed at least once (130 instances = 390 probes a call, so up to three calls), through both placements, three runs
+    each: the build's atomics arrive in another order every time, the witness may not change.  Then absent keys -- home = the head of the chain, home =
+    its middle behind the wrap -- in lanes 0, 64 and 129: zero values, exactly the caller's bit over a preset word."""
+    case, tab = colliding_table(khip, F, table_len)
+    n = 130
+    rnd = random.Random(500 + table_len)
+    keys3 = None
+    for first in range(0, table_len, 3 * n):
+        picks = list(range(first, min(first + 3 * n, table_len)))
+        picks += [rnd.randrange(table_len) for _ in range(3 * n - len(picks))]
+        rnd.shuffle(picks)
+        keys3 = [[tab.keys[picks[3 * i + k]] for k in range(3)] for i in range(n)]
+        for what, kw, rows in placements(n):
+            want_w, want_o = expected(F, rows, keys3, tab.at)
+            for attempt in range(3):
+                flags = preset_word(khip)
+                w, o = call(khip, F, tab, kw, keys3, flags=flags, bit=17)
+                assert flag_word(flags) == PRESET, (what, attempt)                # no miss: the word stays as it was
+                assert np.array_equal(o, want_o), (what, attempt)
+                assert np.array_equal(w, want_w), (what, attempt)
+                flags.free()
+    head, mid = case.absent["head"], case.absent.get("mid", case.absent["head"])        # (one entry: nothing of the chain lies behind the wrap)
+    assert head not in tab.at and mid not in tab.at
+    keys3[0][1], keys3[64][0], keys3[129][2] = head, mid, head
+    zero = np.zeros(4, dtype=np.uint64)
+    for what, kw, rows in placements(n):
+        want_w, want_o = expected(F, rows, keys3, tab.at)
+        for i, k in ((0, 1), (64, 0), (129, 2)):
+            assert np.array_equal(want_o[i, k], zero) and np.array_equal(want_w[2 * k + 2, rows[i]], zero)
+        for attempt in range(3):
+            flags = preset_word(khip)
+            w, o = call(khip, F, tab, kw, keys3, flags=flags, bit=17)
+            assert flag_word(flags) == PRESET | (1 << 17), (what, attempt)
+            assert np.array_equal(o, want_o) and np.array_equal(w, want_w), (what, attempt)
+            flags.free()
+    tab.free()
+
+
+def test_a_colliding_table_as_a_schedule_step(khip):
+    """the 600-entry table (a repeated key inside the chain) and keys with both kinds of misses as a KH_STEP_LOOKUP step: the witness and the flag word of
+    the direct call, which equal the expectation"""
+    F, table_len, n, bit = P.Fp, 600, 130, 4
+    case, tab = colliding_table(khip, F, table_len)
+    rnd = random.Random(77)
+    picks = [9, 23, table_len - 1] + [rnd.randrange(table_len) for _ in range(3 * n - 3)]
+    keys3 = [[tab.keys[picks[3 * i + k]] for k in range(3)] for i in range(n)]
+    keys3[5][2], keys3[64][0] = case.absent["head"], case.absent["mid"]
+    what, kw, rows = placements(n)[0]
+    want_w, want_o = expected(F, rows, keys3, tab.at)
+    flags = preset_word(khip)
+    direct, o = call(khip, F, tab, kw, keys3, flags=flags, bit=bit)
+    assert flag_word(flags) == PRESET | (1 << bit) and np.array_equal(o, want_o) and np.array_equal(direct, want_w)
+    flags.free()
+    step = dict(op=khip.STEP_LOOKUP, n=n, rows=rows, param=table_len, consts=mont(F, [TABLE_ID])[0], flag_bit=bit,
+                **{"in": [(2, 0), (0, 0), (1, 0)]}, out=[(khip.REF_ARENA, 0)])
+    sched = khip.WitnessSchedule.create(fid(khip, F), COL_LEN, [step], arena_bytes=96 * n, n_bufs=3)
+    slots = (sched.info()["run_bytes"] - 96 * n) // 4
+    assert slots >= LC.slots(table_len) and slots & (slots - 1) == 0
+    kd = khip.DevBuf(96 * n).upload(mont(F, [k for ks in keys3 for k in ks]))
+    for attempt in range(3):
+        wit, flags = sentinel_buf(khip, 15 * COL_LEN), preset_word(khip)
+        sched.run([tab.k_dev, tab.v_dev, kd], wit, flags=flags)
+        assert np.array_equal(wit.download((15, COL_LEN, 4)), direct), attempt
+        assert flag_word(flags) == PRESET | (1 << bit), attempt
+        wit.free(); flags.free()
+    sched.free(); kd.free(); tab.free()

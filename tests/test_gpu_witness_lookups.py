@@ -4,7 +4,11 @@
 The expected result is computed here from the oracle's lookup constraint system (oracle.lookup.LookupCS: table_cols, table_ids, selectors, info,
 PATTERNS): the set of table tuples (id, c_0, .., c_{W-1}) of the rows t < L = n - zk_rows - 1 (column 1 of the runtime rows = the call's runtime
 values), then the rows r < L in order, every joint lookup of every pattern whose selector is 1 on the row.  It gives the first (row, joint lookup),
-the number of misses and the looked-up tuple; kind, row, pattern, joint lookup, columns, limbs and count must be equal exactly."""
+the number of misses and the looked-up tuple; kind, row, pattern, joint lookup, columns, limbs and count must be equal exactly.
+
+Section 10 runs tables whose tuples are made to collide under the tuple hash (tests/lookup_collisions.py, pinned to csrc/lookup_hash.hpp by
+tests/test_lookup_hash.py): every table row's home slot is one of the last two of the 1024 slots, so the index's table is one probe chain across the end of
+the slot array -- with random entries at a load of 0.2 a chain has one or two slots."""
 import ctypes as C
 import os
 import sys
@@ -22,6 +26,8 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_proof_fixtures as M  # noqa: E402
+sys.path.insert(0, HERE)
+import lookup_collisions as LC  # noqa: E402
 
 PATTERN_IDS = {"Xor": 0, "Lookup": 1, "RangeCheck": 2, "ForeignFieldMul": 3}
 Fo = P.Fp                       # the default field of the cases (a Vesta SRS); the `*_on_pallas` tests run the same bodies with the brute force on P.Fq
@@ -719,3 +725,212 @@ def gates_and_wires_equal_the_old_entry_point_body(khip, F, library):
                 assert (lk.pattern, lk.slot, lk.ncells, lk.lookups_missing) == (-1, -1, 0, 0)
                 kinds.add(old.kind)
         assert {khip.WITNESS_OK, khip.WITNESS_GATE} <= kinds, kinds
+
+
+# ---- 10. forced collisions: every table tuple's home slot is 1022 or 1023 of 1024 (domain 2^9, L = 508)
+LIM, CAP = 508, 1024
+LAST_TWO = (CAP - 2, CAP - 1)
+TAIL_THEN_PLAIN, PLAIN_THEN_TAIL = 40, 70                         # entries of table 9 that stand next to a copy of themselves with a non-zero tail
+RT_POOL = (17, 4242, 99)                                          # the runtime table's values: three values, each many times
+
+
+def entry(x):
+    return (x, x * x + 3)
+
+
+def colliding_case(Fo=Fo):
+    """509 Lookup rows into two fixed tables, id 5 of width 2 and id 9 of width 4, 100 + 103 entries: x = 1, 2, .. kept when (id, x, x^2 + 3, 0) has its
+    home slot in the last two.  Table 9 also holds, for the predecessor rule of k_witness_lookup_build (a row equal to its predecessor in id and columns
+    0..2 is skipped -- unless that predecessor has a non-zero tail and was never inserted):
+      entry 40 preceded by a copy with tail 11   the copy is not inserted, so entry 40 must insert itself
+      entry 70 followed by a copy with tail 12   the copy is not inserted, entry 70 is
+      one more colliding entry with tail 5 alone: never in the set
+    Every entry with a zero tail is looked up by a checked row of the sound witness."""
+    x5 = LC.tuple_colliders(Fo, 5, LIM, LAST_TWO, 100)
+    x9 = LC.tuple_colliders(Fo, 9, LIM, LAST_TWO, 101)
+    x9, lone = x9[:100], x9[100]
+    rows9 = []
+    for j, x in enumerate(x9):
+        if j == TAIL_THEN_PLAIN:
+            rows9.append(entry(x) + (0, 11))
+        rows9.append(entry(x) + (0, 0))
+        if j == PLAIN_THEN_TAIL:
+            rows9.append(entry(x) + (0, 12))
+    rows9.append(entry(lone) + (0, 5))
+    tables = [{"id": 5, "data": [list(x5), [entry(x)[1] for x in x5]]}, {"id": 9, "data": [list(c) for c in zip(*rows9)]}]
+    rows = 509
+    wit = [[0] * rows for _ in range(15)]
+    for r in range(rows):
+        tid, xs = (9, x9) if r % 3 == 0 else (5, x5)
+        wit[0][r] = tid
+        for k in range(3):
+            wit[1 + 2 * k][r], wit[2 + 2 * k][r] = entry(xs[(3 * (r // 3 if tid == 9 else r) + k) % 100])
+    case = Case([CC.gate("Lookup", r) for r in range(rows)], wit, tables, Fo=Fo)
+    assert case.n == 512 and case.zk == 3 and len(case.L.table_cols) == 4 and case.L.table_ids is not None
+    looked = {(wit[0][r], wit[1 + 2 * k][r]) for r in range(LIM) for k in range(3)}
+    assert looked == {(5, x) for x in x5} | {(9, x) for x in x9}
+    case.x5, case.x9, case.lone = x5, x9, lone
+    return case
+
+
+def colliding_runtime_case(Fo=Fo):
+    """300 Lookup rows: even rows into a fixed table id 5 (80 colliding entries), odd rows into a runtime table id 7 of 120 entries whose second column --
+    the call's runtime values -- holds three values only; its first column is x = 1, 2, .. kept when (7, x, RT_POOL[x % 3], 0) collides"""
+    x5 = LC.tuple_colliders(Fo, 5, LIM, LAST_TWO, 80)
+    first = LC.tuple_colliders(Fo, 7, LIM, LAST_TWO, 120, entry=lambda x: (x, RT_POOL[x % 3], 0))
+    runtime = [RT_POOL[x % 3] for x in first]
+    assert all(runtime.count(v) >= 20 for v in RT_POOL)
+    rows = 300
+    wit = [[0] * rows for _ in range(15)]
+    for r in range(rows):
+        wit[0][r] = 7 if r % 2 else 5
+        for k in range(3):
+            j = 3 * (r // 2) + k
+            wit[1 + 2 * k][r], wit[2 + 2 * k][r] = (first[j % 120], runtime[j % 120]) if r % 2 else entry(x5[j % 80])
+    case = Case([CC.gate("Lookup", r) for r in range(rows)], wit, [{"id": 5, "data": [list(x5), [entry(x)[1] for x in x5]]}],
+                runtime_cfg=[{"id": 7, "first_column": list(first)}], runtime=runtime, Fo=Fo)
+    assert case.n == 512 and case.zk == 3
+    case.x5, case.first = x5, first
+    return case
+
+
+def chain_of(case):
+    """the preconditions, on the table the index really has: the oracle's table_cols / table_ids over all L rows (column 1 of the runtime rows = the
+    call's values), the rows k_witness_lookup_build inserts (a zero tail), their distinct (id, c0, c1, c2), the mirror's home slots.  Every home is one
+    of the last two slots -- but the all-zero tuple of the padding rows, whose hash is 0: slot 0, inside the chain --; the occupied slots are ONE run across
+    the end of the array; the key in its last slot is displaced by tuples - 3 at least (three home slots).  Returns the run."""
+    L, Fo = case.L, case.Fo
+    assert case.n - case.zk - 1 == LIM and LC.slots(LIM) == CAP
+    cols = [list(c) for c in L.table_cols]
+    if case.runtime is not None:
+        cols[1][L.runtime_offset:L.runtime_offset + len(case.runtime)] = [v % Fo.p for v in case.runtime]
+    tuples = {}
+    for t in range(LIM):
+        if not any(c[t] for c in cols[3:]):
+            tuples.setdefault((L.table_ids[t], cols[0][t], cols[1][t], cols[2][t] if len(cols) > 2 else 0))
+    assert (0, 0, 0, 0) in tuples and L.entries < LIM
+    homes = {tup: LC.tuple_home(*(LC.mont_limbs(Fo, v) for v in tup), LIM) for tup in tuples}
+    assert homes.pop((0, 0, 0, 0)) == 0 and set(homes.values()) == set(LAST_TWO)
+    run = LC.longest_run(list(homes.values()) + [0], CAP)
+    assert len(tuples) >= 200 and len(run.slots) == len(tuples) and run.occupied == set(run.slots) and run.slots[0] == CAP - 2
+    assert run.wraps and 0 in run.occupied and run.displacement >= len(tuples) - 3
+    return run
+
+
+def absent_cell(case, tid, x, second, slot):
+    """v such that (tid, x, v, 0) is no table tuple and has its home in `slot`: the tuple of a row that looks (tid, x, second) up, ONE cell replaced"""
+    v = LC.tuple_colliders(case.Fo, tid, LIM, {slot}, 1, exclude={second}, entry=lambda v: (x, v, 0))[0]
+    assert (tid, x, v) + (0,) * (len(case.L.table_cols) - 2) not in case.table_set(case.runtime)
+    return v
+
+
+def thrice(khip, F, case, ix, base, cells=None, runtime="own"):
+    """three runs of one call (the build's atomics arrive in another order each time), each against the brute force; returns the last"""
+    for _ in range(3):
+        out = run(khip, F, case, ix, base, cells, runtime)
+    return out
+
+
+@pytest.fixture(scope="module")
+def colliding(khip, F, srs13):
+    yield from index_fixture(khip, F, srs13, colliding_case)
+
+
+@pytest.fixture(scope="module")
+def colliding_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, colliding_case)
+
+
+@pytest.fixture(scope="module")
+def colliding_rt(khip, F, srs13):
+    yield from index_fixture(khip, F, srs13, colliding_runtime_case)
+
+
+@pytest.fixture(scope="module")
+def colliding_rt_pallas(khip, F_pallas, srs13_pallas):
+    yield from index_fixture(khip, F_pallas, srs13_pallas, colliding_runtime_case)
+
+
+def test_colliding_tables(khip, F, colliding):
+    colliding_tables_body(khip, F, colliding)
+
+
+def test_colliding_tables_on_pallas(khip, F_pallas, colliding_pallas):
+    colliding_tables_body(khip, F_pallas, colliding_pallas)
+
+
+def colliding_tables_body(khip, F, fixture):
+    case, ix, base = fixture
+    chain = chain_of(case)
+    head = chain.slots[0]
+    behind = chain.slots[chain.slots.index(CAP - 1) + 1:]
+    mid = behind[len(behind) // 2]
+    assert head == CAP - 2 and len(behind) >= 198 and 0 < mid < 250
+    w = case.wit
+    # the sound witness: every zero-tail entry of both tables is looked up, entry 40 and entry 70 of table 9 (the predecessor rule, both orders) among them
+    rep, lk, ms = thrice(khip, F, case, ix, base)
+    assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0 and not ms
+    for j in (TAIL_THEN_PLAIN, PLAIN_THEN_TAIL):
+        assert any(w[0][r] == 9 and w[1 + 2 * k][r] == case.x9[j] for r in range(LIM) for k in range(3))
+    t9 = list(zip(*case.tables[1]["data"]))
+    a, b = t9.index(entry(case.x9[TAIL_THEN_PLAIN]) + (0, 0)), t9.index(entry(case.x9[PLAIN_THEN_TAIL]) + (0, 0))
+    assert t9[a - 1] == t9[a][:3] + (11,) and t9[b + 1] == t9[b][:3] + (12,)
+    # the entry that exists with a non-zero tail only is in no lookup's reach
+    r9 = next(r for r in range(20, 500) if w[0][r] == 9)
+    rep, lk, ms = thrice(khip, F, case, ix, base, {(r9, 1): case.lone, (r9, 2): entry(case.lone)[1]})
+    assert [m[:2] for m in ms] == [(r9, 0)]
+    # one cell replaced, the tuple absent: home = the head of the chain (the probe walks all of it, the wrap included) / the middle behind the wrap
+    r5 = next(r for r in range(200, 500) if w[0][r] == 5)
+    for slot in (head, mid):
+        v = absent_cell(case, 5, w[3][r5], w[4][r5], slot)
+        rep, lk, ms = thrice(khip, F, case, ix, base, {(r5, 4): v})
+        assert ms == [(r5, 1, 1, 5, [w[3][r5], v], [3, 4])], slot
+        v = absent_cell(case, 9, w[5][r9], w[6][r9], slot)
+        rep, lk, ms = thrice(khip, F, case, ix, base, {(r9, 6): v})
+        assert ms == [(r9, 2, 1, 9, [w[5][r9], v], [5, 6])], slot
+    # several misses in one wave (rows 64 .. 127), of both kinds: the lowest row and joint lookup, the exact count
+    cells = {}
+    for r, k, slot in ((100, 2, head), (71, 1, mid), (71, 2, head), (126, 0, mid), (64, 0, head)):
+        cells[(r, 2 + 2 * k)] = absent_cell(case, w[0][r], w[1 + 2 * k][r], w[2 + 2 * k][r], slot)
+    rep, lk, ms = thrice(khip, F, case, ix, base, cells)
+    assert (rep.row, lk.slot, lk.lookups_missing) == (64, 0, 5) and [m[:2] for m in ms] == [(64, 0), (71, 1), (71, 2), (100, 2), (126, 0)]
+
+
+def test_colliding_runtime_table(khip, F, colliding_rt):
+    colliding_runtime_table_body(khip, F, colliding_rt)
+
+
+def test_colliding_runtime_table_on_pallas(khip, F_pallas, colliding_rt_pallas):
+    colliding_runtime_table_body(khip, F_pallas, colliding_rt_pallas)
+
+
+def colliding_runtime_table_body(khip, F, fixture):
+    case, ix, base = fixture
+    chain = chain_of(case)
+    head = chain.slots[0]
+    behind = chain.slots[chain.slots.index(CAP - 1) + 1:]
+    mid = behind[len(behind) // 2]
+    w = case.wit
+    rep, lk, ms = thrice(khip, F, case, ix, base)
+    assert rep.kind == khip.WITNESS_OK and lk.lookups_missing == 0 and not ms
+    # a runtime row's value replaced by an absent one whose tuple starts at the head of the chain / in its middle; a fixed row likewise
+    r7, r5 = 151, 150
+    assert w[0][r7] == 7 and w[0][r5] == 5
+    for slot in (head, mid):
+        v = absent_cell(case, 7, w[1][r7], w[2][r7], slot)
+        assert v not in RT_POOL
+        rep, lk, ms = thrice(khip, F, case, ix, base, {(r7, 2): v})
+        assert ms == [(r7, 0, 1, 7, [w[1][r7], v], [1, 2])], slot
+        v = absent_cell(case, 5, w[3][r5], w[4][r5], slot)
+        rep, lk, ms = thrice(khip, F, case, ix, base, {(r5, 4): v})
+        assert ms == [(r5, 1, 1, 5, [w[3][r5], v], [3, 4])], slot
+    # another of the three values for one entry: the tuple the witness looks up is gone (the new one need not collide: it takes any slot)
+    other = list(case.runtime)
+    j = 50
+    other[j] = RT_POOL[(RT_POOL.index(other[j]) + 1) % 3]
+    hits = [(r, k) for r in range(300) for k in range(3) if w[0][r] == 7 and w[1 + 2 * k][r] == case.first[j]]
+    rep, lk, ms = thrice(khip, F, case, ix, base, runtime=other)
+    assert hits and [m[:2] for m in ms] == hits and rep.row == hits[0][0]
+    r, k = hits[0]
+    rep, lk, ms = thrice(khip, F, case, ix, base, {(r, 2 + 2 * k): other[j]}, runtime=other)
+    assert [m[:2] for m in ms] == hits[1:]
