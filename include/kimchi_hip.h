@@ -853,6 +853,11 @@ uint64_t kh_counter(const char *name);
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,
  * 5 sqr, 6 neg).  Used by the parity tests to pin the device arithmetic itself. */
 int kh_debug_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
+/* Test hook of the two product scans that subtract (csrc/field29.cuh: the accumulation's 29-bit-limb arithmetic), on the caller's limbs as they are:
+ * every element is nine uint32_t limbs, nothing is converted.  op 0 (mulsub29): out = a b / 2^261 - c + K p; op 1 (sqrsub29, b unused, may be NULL):
+ * out = a a / 2^261 - c + K p; both in normalised limbs.  spread picks K p as the additions spread it over the limbs: 0 = (K, J) = (7, 1), 1 = (5, 1),
+ * 2 = (4, 4); the caller keeps c_i <= J (2^29 - 1), c_8 <= (K p)_8 - J and the limb magnitudes of a, b within the scan's column bound. */
+int kh_debug_field29_op(int field, int op, int spread, const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *out, size_t n);
 /* Test hook of the opening's rebase (csrc/rebase.hip; the folded basis of poly-commitment/src/ipa.rs:985-1003 after several rounds at once):
  * out[i] = sum_{q < Q} coef[q] * g[q N + i] for i < N = n / Q (N a multiple of 64), from the handle's c = 16 window tables; coef Montgomery, out affine.
  * *out_fail != 0: an output was the point at infinity (the rebase is then abandoned; out is incomplete). */

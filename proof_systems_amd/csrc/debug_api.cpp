@@ -58,6 +58,23 @@ int kh_debug_field_op(int field, int op, const uint64_t* a, const uint64_t* b, u
     (void)hipFree(da); (void)hipFree(dout); if (db) (void)hipFree(db);
     return rc;
 }
+int kh_debug_field29_op(int field, int op, int spread, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, size_t n) {
+    KH_REQUIRE(a && c && out && (op == 1 || b), "null argument");
+    KH_REQUIRE((op == 0 || op == 1) && spread >= 0 && spread <= 2, "kh_debug_field29_op: op %d / spread %d unknown", op, spread);
+    int rc = ensure_init(); if (rc) return rc;
+    if (n == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    DevBuf da, db, dc, dout;
+    if ((rc = da.reserve(n * 36)) || (rc = db.reserve(n * 36)) || (rc = dc.reserve(n * 36)) || (rc = dout.reserve(n * 36))) return rc;
+    KH_HIP(hipMemcpyAsync(da.p, a, n * 36, hipMemcpyHostToDevice, C.stream));
+    if (op == 0) KH_HIP(hipMemcpyAsync(db.p, b, n * 36, hipMemcpyHostToDevice, C.stream));
+    KH_HIP(hipMemcpyAsync(dc.p, c, n * 36, hipMemcpyHostToDevice, C.stream));
+    if ((rc = debug_field29_op(C, field, op, spread, da.as<uint32_t>(), db.as<uint32_t>(), dc.as<uint32_t>(), dout.as<uint32_t>(), n))) return rc;
+    KH_HIP(hipMemcpyAsync(out, dout.p, n * 36, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipStreamSynchronize(C.stream));
+    return KH_OK;
+}
 int kh_debug_point_op(int curve, int op, const uint64_t* p_xy, const uint8_t* p_inf, const uint64_t* q_xy, const uint8_t* q_inf,
                       uint64_t* out_xy, uint8_t* out_inf, size_t n) {
     KH_REQUIRE(p_xy && q_xy && out_xy && out_inf, "null argument");

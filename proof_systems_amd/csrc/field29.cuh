@@ -11,6 +11,9 @@
 //   several p large.  Additions and subtractions are limb-wise without carry chains (a - b is a + (K p spread over
 //   the limbs) - b), followed by ONE carry sweep where the next use needs normalised limbs (< 2^29).
 //   Accumulator bound of a product: limbs a_i < 2^A, b_j < 2^B with A + B <= 60.7 (one operand may be un-normalised).
+//   Where the minuend of such a subtraction is itself a product, the product's scan takes the subtraction along (mulsub29 /
+//   sqrsub29: the nine limb differences K p - c enter the upper nine columns, 174 / 146 instructions) and its normalisation
+//   is the only one: P, R and X3 of madd29, X3 of aadd29, R of add29.
 //
 // Values here are NOT canonical, so nothing in this file decides equality: madd29 only applies cheap NECESSARY
 // conditions for the exceptional cases of the group law (p = 1 mod 2^29, so k p has low limb k) and reports them; the
@@ -120,6 +123,53 @@ __device__ __forceinline__ Fe29<F> sqr29(const Fe29<F>& a) {
         }                                                                            \
     }
 
+// The same a - b + K p where a is a product: the product scan does the subtraction.  d_i = SPREAD(i) - c_i (one v_sub_u32 per limb; same
+// validity condition as KH29_SUBN) is added to column 9 + i of the scan, whose v_and / shift normalise the sum as they normalise the
+// product: the result is the integer mul29(a, b) - c + K p in the same unique normalised limbs as KH29_SUBN(r, mul29(a, b), c, SPREAD)
+// leaves, without the second sweep (2 instructions per limb instead of 4; Madd29Model.mulsub asserts the equality limb for limb).
+template <class F>
+__device__ __forceinline__ Fe29<F> mulsub29_d(const Fe29<F>& a, const Fe29<F>& b, const Fe29<F>& d) {
+    Fe29<F> r;
+    KH29_CONSTS;
+    asm(KH29_MULSUB_ASM
+        : "=&v"(r.v[0]), "=&v"(r.v[1]), "=&v"(r.v[2]), "=&v"(r.v[3]), "=&v"(r.v[4]), "=&v"(r.v[5]), "=&v"(r.v[6]), "=&v"(r.v[7]), "=&v"(r.v[8])
+        : "v"(a.v[0]), "v"(a.v[1]), "v"(a.v[2]), "v"(a.v[3]), "v"(a.v[4]), "v"(a.v[5]), "v"(a.v[6]), "v"(a.v[7]), "v"(a.v[8]),
+          "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7]), "v"(b.v[8]),
+          "v"(d.v[0]), "v"(d.v[1]), "v"(d.v[2]), "v"(d.v[3]), "v"(d.v[4]), "v"(d.v[5]), "v"(d.v[6]), "v"(d.v[7]), "v"(d.v[8]),
+          "s"(p1), "s"(p2), "s"(p3), "s"(p4), "s"(c22), "s"(msk), "v"(pairk)
+        : "vcc", "v2", "v3");
+    return r;
+}
+template <class F>
+__device__ __forceinline__ Fe29<F> sqrsub29_d(const Fe29<F>& a, const Fe29<F>& d) {
+    Fe29<F> r;
+    KH29_CONSTS;
+    u32 d1, d2, d3, d4, d5, d6, d7, d8;                    // 2 a_1 .. 2 a_8 (scratch)
+    asm(KH29_SQRSUB_ASM
+        : "=&v"(r.v[0]), "=&v"(r.v[1]), "=&v"(r.v[2]), "=&v"(r.v[3]), "=&v"(r.v[4]), "=&v"(r.v[5]), "=&v"(r.v[6]), "=&v"(r.v[7]), "=&v"(r.v[8]),
+          "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(d4), "=&v"(d5), "=&v"(d6), "=&v"(d7), "=&v"(d8)
+        : "v"(a.v[0]), "v"(a.v[1]), "v"(a.v[2]), "v"(a.v[3]), "v"(a.v[4]), "v"(a.v[5]), "v"(a.v[6]), "v"(a.v[7]), "v"(a.v[8]),
+          "v"(d.v[0]), "v"(d.v[1]), "v"(d.v[2]), "v"(d.v[3]), "v"(d.v[4]), "v"(d.v[5]), "v"(d.v[6]), "v"(d.v[7]), "v"(d.v[8]),
+          "s"(p1), "s"(p2), "s"(p3), "s"(p4), "s"(c22), "s"(msk), "v"(pairk)
+        : "vcc", "v2", "v3");
+    return r;
+}
+// mul29(a, b) - c + K p and sqr29(a) - c + K p, normalised; SPREAD is one of K::s71 ... as for KH29_SUBN
+template <class F, u32 (*SPREAD)(int)>
+__device__ __forceinline__ Fe29<F> mulsub29(const Fe29<F>& a, const Fe29<F>& b, const Fe29<F>& c) {
+    Fe29<F> d;
+#pragma unroll
+    for (int i = 0; i < 9; i++) d.v[i] = SPREAD(i) - c.v[i];
+    return mulsub29_d<F>(a, b, d);
+}
+template <class F, u32 (*SPREAD)(int)>
+__device__ __forceinline__ Fe29<F> sqrsub29(const Fe29<F>& a, const Fe29<F>& c) {
+    Fe29<F> d;
+#pragma unroll
+    for (int i = 0; i < 9; i++) d.v[i] = SPREAD(i) - c.v[i];
+    return sqrsub29_d<F>(a, d);
+}
+
 // wire form (canonical, Montgomery radix 2^256) <-> lazy R'-form
 template <class F>
 __device__ __forceinline__ Fe29<F> to29(const Fe<F>& a) {          // result < 1.01 p, normalised
@@ -167,28 +217,28 @@ __device__ __forceinline__ bool is_kp29(const Fe29<F>& x, u32 k) {
 // acc += (px, py) with px = 32 X, py = 32 Y (pack29<F, 5> of the canonical affine coordinates; the sign already applied).
 // Returns false -- acc untouched -- when an exceptional case of the group law cannot be excluded (acc possibly the
 // identity, the points possibly equal or opposite); see the header.  Bounds: tools/gen_field29_asm.py (Madd29Model).
-template <class F>
+// ZZ_TEST = false leaves the identity test out: for an accumulator that an aadd29 opened (zz = PP < 1.1 p with P != 0 mod p) and that
+// only madd29 touched since (zz <- zz PP / R', never 0 mod p as long as no P is: the second filter), the test cannot fire.
+template <class F, bool ZZ_TEST = true>
 __device__ __forceinline__ bool madd29(Acc29<F>& a, const Fe29<F>& px, const Fe29<F>& py) {
     typedef typename C29<F>::T K;
-    if (__builtin_expect(a.zz.v[0] <= 1u, 0) && is_kp29<F>(a.zz, a.zz.v[0])) return false;        // zz in {0, p}: the identity
-    const Fe29<F> U2 = mul29<F>(px, a.zz), S2 = mul29<F>(py, a.zzz);
-    Fe29<F> P, R;
-    KH29_SUBN(P, U2, a.x, K::s71)
+    if (ZZ_TEST && __builtin_expect(a.zz.v[0] <= 1u, 0) && is_kp29<F>(a.zz, a.zz.v[0])) return false;        // zz in {0, p}: the identity
+    const Fe29<F> P = mulsub29<F, K::s71>(px, a.zz, a.x);                                          // U2 - X1 + 7 p
     if (__builtin_expect(P.v[0] <= 8u, 0) && is_kp29<F>(P, P.v[0])) return false;                  // P = k p, k <= 8: same x
-    KH29_SUBN(R, S2, a.y, K::s51)
+    const Fe29<F> R = mulsub29<F, K::s51>(py, a.zzz, a.y);                                         // S2 - Y1 + 5 p
     const Fe29<F> PP = sqr29<F>(P);
-    const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(a.x, PP), RR = sqr29<F>(R);
-    Fe29<F> sub, rx, t, yn;
+    const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(a.x, PP);
+    a.zz = mul29<F>(a.zz, PP);                                                  // (before the X3 scan: PP is dead while its nine addends are live)
+    a.zzz = mul29<F>(a.zzz, PPP);
+    Fe29<F> sub, t, yn;
 #pragma unroll
     for (int i = 0; i < 9; i++) sub.v[i] = PPP.v[i] + 2u * Q.v[i];
-    KH29_SUBN(rx, RR, sub, K::s44)
+    const Fe29<F> rx = sqrsub29<F, K::s44>(R, sub);                                                // RR - (PPP + 2 Q) + 4 p
 #pragma unroll
     for (int i = 0; i < 9; i++) t.v[i] = Q.v[i] + K::s61(i) - rx.v[i];          // not normalised: limbs < 2^29 + 2^30
 #pragma unroll
     for (int i = 0; i < 9; i++) yn.v[i] = K::s51(i) - a.y.v[i];                   // 5 p - y, not normalised
     a.y = muladd29<F>(R, t, yn, PPP);                                           // R (Q - X3) - Y1 PPP, one reduction, < 1.4 p
-    a.zz = mul29<F>(a.zz, PP);
-    a.zzz = mul29<F>(a.zzz, PPP);
     a.x = rx;
     return true;
 }
@@ -235,11 +285,11 @@ __device__ __forceinline__ bool aadd29(Acc29<F>& out, const Fe29<F>& x1, const F
     KH29_SUBN(R, y2, y1, K::s331)
     R = fold29<F>(R);
     const Fe29<F> PP = sqr29<F>(P);
-    const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(x1, PP), RR = sqr29<F>(R);
-    Fe29<F> sub, rx, t, yn;
+    const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(x1, PP);
+    Fe29<F> sub, t, yn;
 #pragma unroll
     for (int i = 0; i < 9; i++) sub.v[i] = PPP.v[i] + 2u * Q.v[i];
-    KH29_SUBN(rx, RR, sub, K::s44)
+    const Fe29<F> rx = sqrsub29<F, K::s44>(R, sub);                                                // RR - (PPP + 2 Q) + 4 p
 #pragma unroll
     for (int i = 0; i < 9; i++) t.v[i] = Q.v[i] + K::s61(i) - rx.v[i];          // not normalised: limbs < 2^29 + 2^30
 #pragma unroll
@@ -255,15 +305,17 @@ __device__ __forceinline__ bool aadd29(Acc29<F>& out, const Fe29<F>& x1, const F
 // product pair; limb model: tools/gen_field29_asm.py Madd29Model.add).  Neither operand may be the identity (the callers skip all-zero
 // records; a lazy point that went through madd29 / add29 never is one).  Returns false -- a untouched -- when P = U2 - U1 = 0 (mod p)
 // cannot be excluded, i.e. the points may be equal or opposite: the caller hands its work item to the exact 32-bit path.
+// Of the three subtractions only R = S2 - S1 rides its product's scan: P before the filter (both points whole, U1 and its nine addends live
+// at once) takes k_wide_a1 / k_wide_l2 from 117 / 114 VGPRs to 128 / 125, X3 to 119 / 116; those two keep the sweep.
 template <class F>
 __device__ __forceinline__ bool add29(Acc29<F>& a, const Acc29<F>& b) {
     typedef typename C29<F>::T K;
     const Fe29<F> U1 = mul29<F>(a.x, b.zz), U2 = mul29<F>(b.x, a.zz);
-    Fe29<F> P, R;
+    Fe29<F> P;
     KH29_SUBN(P, U2, U1, K::s51)
     if (__builtin_expect(P.v[0] <= 8u, 0) && is_kp29<F>(P, P.v[0])) return false;                  // P = k p: same x
-    const Fe29<F> S1 = mul29<F>(a.y, b.zzz), S2 = mul29<F>(b.y, a.zzz);
-    KH29_SUBN(R, S2, S1, K::s51)
+    const Fe29<F> S1 = mul29<F>(a.y, b.zzz);
+    const Fe29<F> R = mulsub29<F, K::s51>(b.y, a.zzz, S1);                                         // S2 - S1 + 5 p
     const Fe29<F> PP = sqr29<F>(P);
     const Fe29<F> PPP = mul29<F>(P, PP), Q = mul29<F>(U1, PP), RR = sqr29<F>(R);
     Fe29<F> sub, rx, t, yn;

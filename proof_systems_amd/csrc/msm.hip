@@ -1036,7 +1036,7 @@ k_accumulate29(const u32* __restrict__ entries, const u32* __restrict__ off, con
         e = entries[k];
         p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
         if (e >> 31) p.y = neg<BF>(p.y);
-        ok = madd29<BF>(acc, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));
+        ok = madd29<BF, false>(acc, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));      // (behind a successful aadd29 only: no identity test)
         if (!ok) break;
     }
     Xyzz<BF> r;
@@ -1106,7 +1106,7 @@ __device__ __forceinline__ bool wide_task29(u32 key, u32 jt, const u32* __restri
         e = entries[k];
         p = Aff<BF>::load(pts + (size_t)(e & 0x7fffffffu) * 64);
         if (e >> 31) p.y = neg<BF>(p.y);
-        ok = madd29<BF>(acc, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));
+        ok = madd29<BF, false>(acc, pack29<BF, 5>(p.x), pack29<BF, 5>(p.y));      // (behind a successful aadd29 only: no identity test)
         if (!ok) break;
     }
     // (the exact redo stays a separate kernel here: inlined as in k_accumulate29 it raised this kernel from 92 to 127 VGPRs, and the sort kernels of the
@@ -2243,6 +2243,26 @@ __global__ void k_debug_field(int op, const u64* a, const u64* b, u64* out, size
         default: r = neg<F>(x); break;
     }
     r.store(out + 4 * i);
+}
+// mulsub29 (op 0) / sqrsub29 (op 1) on caller-supplied limbs (nine u32 per element, no conversion): out = a b / R' - c + spread, normalised;
+// spread 0 = (7, 1), 1 = (5, 1), 2 = (4, 4) -- the three (K, J) the additions subtract with
+template <class F>
+__global__ void k_debug_field29(int op, int spread, const u32* a, const u32* b, const u32* c, u32* out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    typedef typename C29<F>::T K;
+    Fe29<F> x, y, z, r;
+#pragma unroll
+    for (int k = 0; k < 9; k++) { x.v[k] = a[9 * i + k]; y.v[k] = op == 0 ? b[9 * i + k] : 0u; z.v[k] = c[9 * i + k]; }
+    if (op == 0) r = spread == 0 ? mulsub29<F, K::s71>(x, y, z) : (spread == 1 ? mulsub29<F, K::s51>(x, y, z) : mulsub29<F, K::s44>(x, y, z));
+    else r = spread == 0 ? sqrsub29<F, K::s71>(x, z) : (spread == 1 ? sqrsub29<F, K::s51>(x, z) : sqrsub29<F, K::s44>(x, z));
+#pragma unroll
+    for (int k = 0; k < 9; k++) out[9 * i + k] = r.v[k];
+}
+int debug_field29_op(Context& C, int field, int op, int spread, const u32* a, const u32* b, const u32* c, u32* out, size_t n) {
+    dim3 grid((unsigned)((n + 255) / 256));
+    KH_FIELD_LAUNCH(field, k_debug_field29<F>, grid, dim3(256), 0, C.stream, op, spread, a, b, c, out, n);
+    return KH_OK;
 }
 int debug_field_op(Context& C, int field, int op, const u64* a, const u64* b, u64* out, size_t n) {
     dim3 grid((unsigned)((n + 255) / 256));

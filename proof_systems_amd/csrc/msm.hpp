@@ -37,6 +37,7 @@ int msm_enqueue(Context& C, MsmSlot& S, int curve, const MsmBasis& basis, size_t
 // flag_seen: the caller has read the job's launch count from S.done_flag (the result is in S.pinned): no wait on the event
 int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool flag_seen = false);
 int debug_field_op(Context& C, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+int debug_field29_op(Context& C, int field, int op, int spread, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, size_t n);
 int debug_point_op(Context& C, int curve, int op, const uint64_t* p, const uint8_t* pinf, const uint64_t* q, const uint8_t* qinf, uint8_t* out, size_t n);
 
 // ntt.hip

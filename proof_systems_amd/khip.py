@@ -1636,6 +1636,17 @@ def debug_field_op(field: int, op: str, a, b=None):
     return out
 
 
+def debug_field29_op(field: int, op: str, spread: str, a, b, c):
+    """mulsub29 / sqrsub29 (field29.cuh) on limbs as given: (n, 9) uint32 each, b None for sqrsub29; spread "s71", "s51" or "s44"."""
+    U32P = C.POINTER(C.c_uint32)
+    a, c = (np.ascontiguousarray(v, dtype=np.uint32).reshape(-1, 9) for v in (a, c))
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, 9)
+    out = np.zeros_like(a)
+    _check(_lib.kh_debug_field29_op(field, {"mulsub29": 0, "sqrsub29": 1}[op], {"s71": 0, "s51": 1, "s44": 2}[spread], a.ctypes.data_as(U32P),
+                                    None if b is None else b.ctypes.data_as(U32P), c.ctypes.data_as(U32P), out.ctypes.data_as(U32P), a.shape[0]))
+    return out
+
+
 def debug_point_op(curve: int, op: int, p, q, p_inf=None, q_inf=None):
     p = _c64(p, (-1, 8)); q = _c64(q, (-1, 8))
     n = p.shape[0]

@@ -22,6 +22,12 @@ field_mulasm.inc needs 104 MADs + 104 v_addc (254 instructions); this one needs 
 Operands (mul):  %0-%8 r (early clobber; r_k holds m_k until column k+8), %9-%17 a, %18-%26 b,
                  %27-%30 P1..P4, %31 2^22, %32 MASK (SGPRs).  Clobbers vcc, v2, v3 (the 64-bit accumulator).
 Operands (sqr):  %0-%8 r, %9-%16 2*a_1..2*a_8 (scratch outputs), %17-%25 a, %26-%29 P1..P4, %30 2^22, %31 MASK.
+
+The scans that subtract (KH29_MULSUB_ASM / KH29_SQRSUB_ASM): nine more VGPR operands d_0..d_8, d_i added to column 9 + i (one
+v_mad_u64_u32 acc, d_i, 1, acc before that column's v_and; d_8 by the v_add_u32 that takes the place of the last v_mov).  The
+result is the integer (a b + m p) / R' + sum d_i 2^(29 i) in normalised limbs: with d_i = C_i - c_i (C a spread multiple of p,
+below) exactly what the sweep subn(mul(a, b), c, C) leaves, limb for limb, without normalising twice.  Column bound: the old one
+plus d_i < 2^32.
 """
 import os
 import random
@@ -41,6 +47,8 @@ def limbs29(x, n=9):
 #   mul    : %9-%17 a, %18-%26 b, %27-%30 P1..P4, %31 2^22, %32 MASK (SGPRs), %33 2^29+1 (VGPR)
 #   sqr    : %9-%16 2*a_1..2*a_8 (scratch outputs), %17-%25 a, %26-%29 P1..P4, %30 2^22, %31 MASK, %32 2^29+1
 #   muladd : r = (a b + c d) / R':  %9-%17 a, %18-%26 b, %27-%35 c, %36-%44 d, %45-%48 P1..P4, %49 2^22, %50 MASK, %51 2^29+1
+#   mulsub : r = a b / R' + d:      %9-%17 a, %18-%26 b, %27-%35 d, %36-%39 P1..P4, %40 2^22, %41 MASK, %42 2^29+1
+#   sqrsub : r = a a / R' + d:      %9-%16 2*a_1..2*a_8 (scratch outputs), %17-%25 a, %26-%34 d, %35-%38 P1..P4, %39 2^22, %40 MASK, %41 2^29+1
 def gen_mul(shift64=True):
     r = lambda i: f"%{i}"
     a = lambda i: f"%{9 + i}"
@@ -71,11 +79,33 @@ def gen_muladd(shift64=True):
     return _gen(r, prods, P, "%50", "%51", [], shift64)
 
 
+def gen_mulsub():
+    r = lambda i: f"%{i}"
+    a = lambda i: f"%{9 + i}"
+    b = lambda i: f"%{18 + i}"
+    d = lambda i: f"%{27 + i}"
+    P = {1: "%36", 2: "%37", 3: "%38", 4: "%39", 8: "%40"}
+    prods = [(i + j, a(i), b(j)) for i in range(9) for j in range(9)]
+    return _gen(r, prods, P, "%41", "%42", [], True, d)
+
+
+def gen_sqrsub():
+    r = lambda i: f"%{i}"
+    dbl = lambda j: f"%{8 + j}"          # 2 * a_j, j = 1..8 -> %9..%16 (scratch OUTPUT operands)
+    a = lambda i: f"%{17 + i}"
+    d = lambda i: f"%{26 + i}"
+    P = {1: "%35", 2: "%36", 3: "%37", 4: "%38", 8: "%39"}
+    pre = [f"v_lshlrev_b32 {dbl(j)}, 1, {a(j)}" for j in range(1, 9)]
+    prods = [(i + j, a(i), a(j) if i == j else dbl(j)) for i in range(9) for j in range(i, 9)]
+    return _gen(r, prods, P, "%40", "%41", pre, True, d)
+
+
 ACC, LO, HI = "v[2:3]", "v2", "v3"            # the 64-bit column accumulator: a fixed aligned pair (clobbered)
 
 
-def _gen(r, prods, P, mask, pairk, pre, shift64):
-    """prods: (column, x, y) limb products.  The MASK offsets of two neighbouring reduction columns are added by ONE MAD:
+def _gen(r, prods, P, mask, pairk, pre, shift64, addend=None):
+    """addend: None, or i -> the operand added to column 9 + i (the scans that subtract, see the header).
+    prods: (column, x, y) limb products.  The MASK offsets of two neighbouring reduction columns are added by ONE MAD:
     column k (even) receives MASK + MASK 2^29 = (2^29 - 1)(2^29 + 1) -- the second term is column k+1's offset, 29 bits
     up, invisible to m_k and delivered by the shift; column 8 adds its own MASK alone."""
     L = list(pre)
@@ -98,6 +128,8 @@ def _gen(r, prods, P, mask, pairk, pre, shift64):
                 L.append(f"v_mad_u64_u32 {acc}, vcc, {mask}, {pairk}, {acc}")
             L.append(f"v_bfi_b32 {r(k)}, {lo}, 0, {mask}")            # m_k = ~lo & MASK
         else:
+            if addend:
+                L.append(f"v_mad_u64_u32 {acc}, vcc, {addend(k - 9)}, 1, {acc}")
             L.append(f"v_and_b32 {r(k - 9)}, {mask}, {lo}")
         if shift64:
             L.append(f"v_lshrrev_b64 {acc}, 29, {acc}")
@@ -105,7 +137,7 @@ def _gen(r, prods, P, mask, pairk, pre, shift64):
             L.append(f"v_alignbit_b32 {lo}, {hi}, {lo}, 29")
             if k < 16:
                 L.append(f"v_lshrrev_b32 {hi}, 29, {hi}")
-    L.append(f"v_mov_b32 {r(8)}, {lo}")
+    L.append(f"v_add_u32 {r(8)}, {lo}, {addend(8)}" if addend else f"v_mov_b32 {r(8)}, {lo}")
     return L
 
 
@@ -166,6 +198,10 @@ def simulate(lines, regs, trace=None):
         elif op == "v_mov_b32":
             d, x = args
             regs[d] = val(x)
+        elif op == "v_add_u32":
+            d, x, y = args
+            regs[d] = val(x) + val(y)
+            assert regs[d] < (1 << 32), "32-bit overflow in: " + ln
         else:
             raise ValueError(op)
     return regs
@@ -176,6 +212,7 @@ def check(p, name, trials=300):
     pl = limbs29(p)
     assert pl[0] == 1 and pl[5] == pl[6] == pl[7] == 0 and pl[8] == 1 << 22
     Rinv = pow(1 << 261, -1, p)
+    M = Madd29Model(p)
     for shift64 in (False, True):
         mul, sqr, mad = gen_mul(shift64), gen_sqr(shift64), gen_muladd(shift64)
         for t in range(trials):
@@ -200,6 +237,15 @@ def check(p, name, trials=300):
             assert all(x <= MASK for x in out[:8]), "limbs not normalised"
             assert ov % p == av * bv * Rinv % p, f"{name} mul mismatch"
             assert ov < av * bv // (1 << 261) + p + 1, "bound"
+            # the scans that subtract (64-bit shifts only): the same product with nine addends in columns 9..17, every one at its ceiling in kind 1
+            # (d_8 lower: the top limb is not masked, limb 8 of the product + d_8 stays a u32)
+            dl = [(1 << 32) - 1] * 8 + [(1 << 30) - 1] if kind == 1 else [rnd.randrange(0, 1 << 32) for _ in range(8)] + [rnd.randrange(0, 1 << 30)]
+            dv = sum(x << (29 * i) for i, x in enumerate(dl))
+            if shift64:
+                regs = M.regs_mulsub(al, bl, dl)
+                simulate(M.mulsub_l, regs)
+                out = [regs[f"%{i}"] for i in range(9)]
+                assert all(x <= MASK for x in out[:8]) and sum(x << (29 * i) for i, x in enumerate(out)) == ov + dv, f"{name} mulsub mismatch"
             # squaring: limbs < 2^30 (doubled operand < 2^31)
             if kind in (0, 3):
                 sl = limbs29(av % (16 * p))
@@ -215,6 +261,11 @@ def check(p, name, trials=300):
             ov = sum(x << (29 * i) for i, x in enumerate(out))
             assert ov % p == sv * sv * Rinv % p, f"{name} sqr mismatch"
             assert all(x <= MASK for x in out[:8])
+            if shift64:
+                regs = M.regs_sqrsub(sl, dl)
+                simulate(M.sqrsub_l, regs)
+                out = [regs[f"%{i}"] for i in range(9)]
+                assert all(x <= MASK for x in out[:8]) and sum(x << (29 * i) for i, x in enumerate(out)) == ov + dv, f"{name} sqrsub mismatch"
             # fused a b + c d: one normalised and one un-normalised operand per product (the r.y step of madd29);
             # worst-case magnitudes in kind 1: limbs 2^29 - 1 against 1.5 * 2^30 and 1.25 * 2^30
             if kind == 1:
@@ -232,7 +283,8 @@ def check(p, name, trials=300):
             v4 = [sum(x << (29 * i) for i, x in enumerate(v)) for v in (al2, bl2, cl, dl)]
             assert ov % p == (v4[0] * v4[1] + v4[2] * v4[3]) * Rinv % p, f"{name} muladd mismatch"
             assert all(x <= MASK for x in out[:8]) and ov < (v4[0] * v4[1] + v4[2] * v4[3]) // (1 << 261) + p + 1
-    print(f"{name}: mul {len(gen_mul())} instr ({len(gen_mul(False))} with v_alignbit/v_lshrrev_b32 shifts), sqr {len(gen_sqr())}, muladd {len(gen_muladd())} -- {trials} x 2 trials OK")
+    print(f"{name}: mul {len(gen_mul())} instr ({len(gen_mul(False))} with v_alignbit/v_lshrrev_b32 shifts), sqr {len(gen_sqr())}, muladd {len(gen_muladd())}, "
+          f"mulsub {len(gen_mulsub())}, sqrsub {len(gen_sqrsub())} -- {trials} x 2 trials OK")
 
 
 # ------------------------------------------------------------------------------------------- constants + madd model
@@ -264,9 +316,54 @@ class Madd29Model:
     the generated instruction stream.  Returns None when an exception filter fires (the kernel then hands the task to the
     exact 32-bit path)."""
 
-    def __init__(self, p):
+    def __init__(self, p, scan_sub=True):
         self.p = p; self.c = field_consts(p); self.mul_l, self.sqr_l, self.mad_l = gen_mul(), gen_sqr(), gen_muladd()
+        self.mulsub_l, self.sqrsub_l = gen_mulsub(), gen_sqrsub()
         self.pl = limbs29(p)
+        self.scan_sub = scan_sub
+
+    def regs_mulsub(self, a, b, d):
+        regs = {f"%{i}": 0 for i in range(9)}
+        for base, vec in ((9, a), (18, b), (27, d)):
+            regs.update({f"%{base + i}": vec[i] for i in range(9)})
+        pl = self.pl
+        regs.update({"%36": pl[1], "%37": pl[2], "%38": pl[3], "%39": pl[4], "%40": 1 << 22, "%41": MASK, "%42": (1 << 29) + 1, LO: 0, HI: 0})
+        return regs
+
+    def regs_sqrsub(self, a, d):
+        regs = {f"%{i}": 0 for i in range(17)}
+        for base, vec in ((17, a), (26, d)):
+            regs.update({f"%{base + i}": vec[i] for i in range(9)})
+        pl = self.pl
+        regs.update({"%35": pl[1], "%36": pl[2], "%37": pl[3], "%38": pl[4], "%39": 1 << 22, "%40": MASK, "%41": (1 << 29) + 1, LO: 0, HI: 0})
+        return regs
+
+    def mulsub(self, a, b, c, C):
+        """mulsub29: the normalised mul(a, b) - c + C from ONE scan, d_i = C_i - c_i added to column 9 + i.  Valid under the condition
+        of subn (c_i <= J MASK, c_8 <= (K p)_8 - J: every d_i is a u32); asserted equal to the sweep limb for limb."""
+        d = [self.u32(C[i] - c[i]) for i in range(9)]
+        assert 9 * max(a) * max(b) + 4 * (1 << 58) + (1 << 51) + (1 << 36) + max(d) < (1 << 64), "column bound with the addend"
+        regs = self.regs_mulsub(a, b, d)
+        simulate(self.mulsub_l, regs)
+        r = [regs[f"%{i}"] for i in range(9)]
+        assert r == self.subn(self.mul(a, b), c, C), "mulsub29 differs from subn(mul29)"
+        return r
+
+    def sqrsub(self, a, c, C):
+        """sqrsub29: the normalised sqr(a) - c + C from one scan (see mulsub)."""
+        d = [self.u32(C[i] - c[i]) for i in range(9)]
+        assert 9 * max(a) * max(a) + 4 * (1 << 58) + (1 << 51) + (1 << 36) + max(d) < (1 << 64), "column bound with the addend"
+        regs = self.regs_sqrsub(a, d)
+        simulate(self.sqrsub_l, regs)
+        r = [regs[f"%{i}"] for i in range(9)]
+        assert r == self.subn(self.sqr(a), c, C), "sqrsub29 differs from subn(sqr29)"
+        return r
+
+    def _mulsub(self, a, b, c, C):               # as the device code has it, or (scan_sub = False) the composition it replaced
+        return self.mulsub(a, b, c, C) if self.scan_sub else self.subn(self.mul(a, b), c, C)
+
+    def _sqrsub(self, a, c, C):
+        return self.sqrsub(a, c, C) if self.scan_sub else self.subn(self.sqr(a), c, C)
 
     def mul(self, a, b):
         assert max(a) * max(b) < (1 << 61) * 1.6, "limb magnitudes beyond the accumulator bound"
@@ -316,13 +413,12 @@ class Madd29Model:
         x, y, zz, zzz = acc
         if zz[0] <= 1:
             return None                            # possibly the identity
-        U2 = self.mul(px, zz); S2 = self.mul(py, zzz)
-        P = self.subn(U2, x, c["S71"]); R = self.subn(S2, y, c["S51"])
+        P = self._mulsub(px, zz, x, c["S71"]); R = self._mulsub(py, zzz, y, c["S51"])        # U2 - X1, S2 - Y1
         if P[0] <= 8:
             return None                            # possibly P == 0 (mod p): equal or opposite points
-        PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(x, PP); RR = self.sqr(R)
+        PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(x, PP)
         sub = [self.u32(PPP[i] + 2 * Q[i]) for i in range(9)]
-        rx = self.subn(RR, sub, c["S44"])
+        rx = self._sqrsub(R, sub, c["S44"])                                              # RR - (PPP + 2 Q)
         t = [self.u32(self.u32(Q[i] + c["S61"][i]) - rx[i]) for i in range(9)]          # not normalised: limbs < 2^29 + 2^30
         yn = [self.u32(c["S51"][i] - y[i]) for i in range(9)]                            # 5p - y, not normalised
         ry = self.muladd(R, t, yn, PPP)                                                  # R (Q - rx) - y PPP with ONE reduction
@@ -356,9 +452,9 @@ class Madd29Model:
         if P[0] == 1 and P == self.pl:
             return None
         R = self.fold(self.subn(py2, py1, c["S331"]))
-        PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(px1, PP); RR = self.sqr(R)
+        PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(px1, PP)
         sub = [self.u32(PPP[i] + 2 * Q[i]) for i in range(9)]
-        rx = self.subn(RR, sub, c["S44"])
+        rx = self._sqrsub(R, sub, c["S44"])
         t = [self.u32(self.u32(Q[i] + c["S61"][i]) - rx[i]) for i in range(9)]          # not normalised: limbs < 2^29 + 2^30
         yn = [self.u32(c["S331"][i] - py1[i]) for i in range(9)]                         # 33 p - 32 Y1, not normalised: limbs < 2^30
         ry = self.muladd(R, t, yn, PPP)                                                  # R (Q - rx) - Y1 PPP with ONE reduction
@@ -370,8 +466,9 @@ class Madd29Model:
         c = self.c
         x1, y1, zz1, zzz1 = A
         x2, y2, zz2, zzz2 = B
-        U1 = self.mul(x1, zz2); U2 = self.mul(x2, zz1); S1 = self.mul(y1, zzz2); S2 = self.mul(y2, zzz1)
-        P = self.subn(U2, U1, c["S51"]); R = self.subn(S2, S1, c["S51"])
+        U1 = self.mul(x1, zz2); S1 = self.mul(y1, zzz2)
+        # (the device's add29 folds R alone: with P or X3 folded as well the tail kernels need more registers than they have had)
+        P = self.subn(self.mul(x2, zz1), U1, c["S51"]); R = self._mulsub(y2, zzz1, S1, c["S51"])  # U2 - U1, S2 - S1
         if P[0] <= 8:
             return None
         PP = self.sqr(P); PPP = self.mul(P, PP); Q = self.mul(U1, PP); RR = self.sqr(R)
@@ -585,20 +682,28 @@ def m_sites(lines):
 
 
 def directed29(p, kind):
-    """kind 'mul', 'sqr', 'mul32x'.  Returns [(x, y, k, target)]: canonical wire-form operands (integers < p; y = x for sqr) for
-    which the middle product has m_k = target (every k = 0..8 and target 0, MASK; not m_0 = MASK for mul32x).  Deterministic."""
+    """kind 'mul', 'sqr', 'mul32x', 'mulsub', 'sqrsub'.  Returns [(x, y, k, target)]: canonical wire-form operands (integers < p; y = x for
+    sqr / sqrsub) for which the middle product has m_k = target (every k = 0..8 and target 0, MASK; not m_0 = MASK for mul32x).  Deterministic.
+    'mulsub' / 'sqrsub': the scans that subtract.  Their reduction digits do not see the addends (columns 9..17), so the operands are found
+    as for 'mul' / 'sqr' -- through the NEW streams, with every addend at its ceiling, which is what shows that they do not."""
     rnd = random.Random(f"directed29/{kind}/{p & 0xffff}")
     M = Madd29Model(p)
     R, R29 = 1 << 256, 1 << 261
     to_wire = R * pow(R29, -1, p) % p                    # to29(x) = x R' / R (mod p)
-    lines = M.sqr_l if kind == "sqr" else M.mul_l
+    scan_sub = kind in ("mulsub", "sqrsub")
+    if scan_sub:
+        kind = kind[:3]
+    lines = (M.sqrsub_l if kind == "sqr" else M.mulsub_l) if scan_sub else (M.sqr_l if kind == "sqr" else M.mul_l)
     sites = m_sites(lines)
+    dmax = [(1 << 32) - 1] * 8 + [(1 << 30) - 1]
 
     def middle(al, bl):
         tr = {}
         regs = {f"%{i}": 0 for i in range(9)}
         pl = M.pl
-        if kind == "sqr":
+        if scan_sub:
+            regs = M.regs_sqrsub(al, dmax) if kind == "sqr" else M.regs_mulsub(al, bl, dmax)
+        elif kind == "sqr":
             regs.update({f"%{17 + i}": al[i] for i in range(9)})
             regs.update({"%26": pl[1], "%27": pl[2], "%28": pl[3], "%29": pl[4], "%30": 1 << 22, "%31": MASK, "%32": (1 << 29) + 1, LO: 0, HI: 0})
             regs.update({f"%{8 + j}": 0 for j in range(1, 9)})
@@ -697,6 +802,7 @@ INC_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "proof
 
 def render():
     mul, sqr, mad = gen_mul(), gen_sqr(), gen_muladd()
+    mulsub, sqrsub = gen_mulsub(), gen_sqrsub()
     mul32 = gen_mul(False)
     nm = lambda l: sum('v_mad' in x for x in l)
     out = ["// GENERATED by tools/gen_field29_asm.py -- do not edit.  See that file for the schedule and the bounds.",
@@ -706,6 +812,10 @@ def render():
            emit("KH29_SQR_ASM", sqr),
            f"// (a b + c d) / R' with one reduction: {len(mad)} instructions, {nm(mad)} v_mad_u64_u32.",
            emit("KH29_MULADD_ASM", mad),
+           f"// a b / R' + d, d_i added to column 9 + i (the product that subtracts: d = K p spread - c): {len(mulsub)} instructions, {nm(mulsub)} v_mad_u64_u32.",
+           emit("KH29_MULSUB_ASM", mulsub),
+           f"// a a / R' + d: {len(sqrsub)} instructions, {nm(sqrsub)} v_mad_u64_u32.",
+           emit("KH29_SQRSUB_ASM", sqrsub),
            f"// the product with v_alignbit_b32 + v_lshrrev_b32 column shifts ({len(mul32)} instructions): slower (tools/microbench.hip measures both)",
            emit("KH29_MUL_ASM_B32", mul32), emit_consts()]
     return "\n".join(out)

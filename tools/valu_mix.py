@@ -72,6 +72,16 @@ def main():
     if not spans:
         raise SystemExit("no loop around the dominant block of " + kern)
     lo, hi = min(spans, key=lambda sp: sp[1] - sp[0])
+    # A rare path laid out behind the loop (the exact comparison behind a one-limb filter) jumps back INTO the body: a backward branch that is no
+    # back edge.  Its span crosses the loop's instead of nesting with it, and the smallest span may be that detour (k_acc_wide29 with the subtracting
+    # scans: 29..33 against the loop's 25..29, four blocks each).  Spans that cross are one loop: take their union; an enclosing loop is left alone.
+    every = [(index[t], i) for i, ts in targets.items() for t in ts if t in index and index[t] <= i]
+    grown = True
+    while grown:
+        grown = False
+        for a, b in every:
+            if a <= hi and b >= lo and not (lo <= a and b <= hi) and not (a <= lo and hi <= b):
+                lo, hi, grown = min(lo, a), max(hi, b), True
     body = [op for b in blocks[lo:hi + 1] for op in b[1]]
     hist = Counter(op for op in body if op.startswith("v_"))
     res = {"source_sha256": source_hash(), "kernel": ("k_accumulate29" if narrow else "k_acc_wide29") + "<FqParams>",
