@@ -847,7 +847,8 @@ int kh_last_timings(const char **names, float *ms, int cap);
  * basis), "lookup_sorted_dev" (successful kh_lookup_sorted_dev calls; kh_prove makes one per proof with lookups), "ipa_concurrent" (kh_ipa_begin calls
  * that found another opening live on the same handle and went ahead beside it), "ipa_waited" (kh_ipa_begin calls that found every workspace of the handle
  * claimed; counted before the wait starts), "table_staged_words" (the uint32_t words of rows[] / cells tables that the gadget and wire calls and
- * kh_witness_schedule_create sent through the staging ring; kh_witness_schedule_run adds none).  Unknown names read 0. */
+ * kh_witness_schedule_create sent through the staging ring; kh_witness_schedule_run adds none), "point_codec_launches" (launches of the point
+ * decompression kernel: one per kh_points_decompress(_dev), kh_srs_create_compressed and kh_proofs_from_wire call that got past its checks).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,
@@ -1256,6 +1257,67 @@ typedef struct kh_verify_trace {                     /* what the verifier derive
 int kh_batch_verify(const kh_verify_item_t *items, size_t k, const uint64_t *rand, int *ok, kh_verify_trace_t *trace /* k records, nullable */);
 int kh_verify(const kh_verify_item_t *item, int *ok, kh_verify_trace_t *trace);
 int kh_verify_last_phase_seconds(double *seconds, size_t cap);
+
+/* ---- Compressed points: the 33-byte record the reference stores and sends (csrc/point_codec.hip, csrc/srs_file.hpp) ----
+ * A record is x as 32 little-endian bytes of the CANONICAL integer plus one flag byte: 0x80 when y > (p - 1) / 2, 0x40 for the point at infinity (x = 0),
+ * 0x00 otherwise (ark-serialize's compressed short-Weierstrass form; p = the curve's base field).  The srs/ files, the stored proofs and every commitment of a
+ * serialised ProverProof / VerifierIndex hold it.  Decoding is one square root per point (Tonelli-Shanks, the function of kh_field_sqrt_dev), one lane
+ * per record; encoding is two conversions out of Montgomery form.  No LDS, no pool scratch, no per-lane scratch memory.
+ *
+ * Statuses of a decoded record (one byte each).  The first two are valid records; a record with any other status gives xy = 0 and inf = 0, and every other
+ * record of the call is exact.  For valid records the result is the reference's; the classification of malformed ones is this library's own contract:
+ *   KH_POINT_OK             a point: x || y in Montgomery limbs, inf = 0
+ *   KH_POINT_INFINITY       flag exactly 0x40 and x = 0: xy = 0, inf = 1
+ *   KH_POINT_BAD_FLAGS      0x80 and 0x40 both set, one of the low six bits set, or 0x40 with x != 0 (checked first)
+ *   KH_POINT_NOT_CANONICAL  x >= p
+ *   KH_POINT_NOT_ON_CURVE   x^3 + 5 is not a square
+ *
+ * kh_points_compress / kh_points_decompress: arrays in host memory; staged through the context, the same kernels, and the call waits.  inf = NULL: no point
+ *   at infinity; a set infinity byte gives 32 zero bytes and 0x40 whatever xy holds.  kh_points_decompress returns KH_OK when every record is valid;
+ *   otherwise KH_E_INVALID with a kh_last_error text naming the lowest bad index and its status and *first_bad set to it -- out_xy, out_inf and status are
+ *   written for all n records all the same.
+ * kh_points_compress_dev / kh_points_decompress_dev: vector steps like kh_field_sqrt_dev -- queued on the main stream of the calling thread's current
+ *   context, ordered against every other call, not waiting for the device; n == 0 is KH_OK with nothing launched.  flags_dev, bit: the rule of the gadget
+ *   calls (nullable word, one atomicOr per wave that has something to raise); the bit is raised by any status other than OK and INFINITY.
+ * Every one of the four refuses with KH_E_INVALID, before anything is launched and with nothing written: an unknown curve, a null pointer with n > 0 (other
+ *   than the nullable ones), an xy pointer that is not 16-byte aligned, bit >= 32 or a misaligned flag word, n >= 2^32 (the record index is 32 bits in the
+ *   SRS file; no byte count overflows below it).
+ *
+ * kh_srs_create_compressed: kh_srs_create from n records in host memory: the bytes are uploaded and decoded straight into the handle's tables, no affine
+ *   copy exists on the host.  A basis point must be a point: a record that is not KH_POINT_OK (an infinity record too) is KH_E_INVALID naming its index, and
+ *   no handle is made.  h_bytes (nullable): the blinding base as one record through the same launch, set as kh_srs_set_blinding_base does.
+ * kh_srs_get_g_compressed: g[offset .. offset + count) as records (the product writes the bytes the golden SRS digests are defined on).
+ * The SRS file: 0x92, 0xdd + the count as a big-endian u32, count x (0xc4 0x21 + record), 0xc4 0x21 + the record of h: kh_srs_file_bytes(n) =
+ *   6 + 35 (n + 1) bytes (0 if that overflows).  kh_srs_write_file writes the handle's g and blinding base (KH_E_INVALID when cap is too small);
+ *   kh_srs_create_from_file reads one: limit (0 = all) keeps the first `limit` points, h is always the file's last record.  A short buffer, a wrong marker
+ *   or a count that disagrees with len is KH_E_INVALID with the byte offset in the message; every length is checked before a read.
+ *
+ * kh_proofs_from_wire: k proofs from the byte strings of k serialised ProverProofs: sections[p * n_sections + s] is section s (KH_PROOF_*) of proof p.  A
+ *   point section is count x 33 records, an element section count x 32 little-endian canonical integers (converted to Montgomery limbs on the host;
+ *   KH_E_INVALID when >= p); KH_PROOF_PUBLIC_COMM and KH_PROOF_CHALLENGES are ignored as by kh_proof_from_sections.  The points of ALL k proofs are decoded
+ *   in ONE launch and handed to kh_proof_from_sections: the proofs are the ones affine sections would have given.  A bad record is KH_E_INVALID naming
+ *   proof, section, index and status; no proof is made and out is left untouched.  The caller's serde still walks the msgpack structure.
+ */
+#define KH_POINT_BYTES 33
+#define KH_POINT_OK 0
+#define KH_POINT_INFINITY 1
+#define KH_POINT_BAD_FLAGS 2
+#define KH_POINT_NOT_CANONICAL 3
+#define KH_POINT_NOT_ON_CURVE 4
+int kh_points_compress(int curve, const uint64_t *xy, const uint8_t *inf /* nullable */, size_t n, uint8_t *out /* n x 33 */);
+int kh_points_decompress(int curve, const uint8_t *bytes, size_t n, uint64_t *out_xy, uint8_t *out_inf,
+                         uint8_t *status /* nullable */, size_t *first_bad /* nullable */);
+int kh_points_compress_dev(int curve, const uint64_t *xy_dev, const uint8_t *inf_dev /* nullable */, size_t n, uint8_t *out_dev);
+int kh_points_decompress_dev(int curve, const uint8_t *bytes_dev, size_t n, uint64_t *out_xy_dev, uint8_t *out_inf_dev,
+                             uint8_t *status_dev /* nullable */, uint32_t *flags_dev, unsigned bit);
+int kh_srs_create_compressed(int curve, const uint8_t *g_bytes /* n x 33, host */, size_t n, const uint8_t *h_bytes /* 33, nullable */, kh_srs_t **out);
+int kh_srs_get_g_compressed(kh_srs_t *srs, size_t offset, size_t count, uint8_t *out /* host, count x 33 */);
+size_t kh_srs_file_bytes(size_t n);
+int kh_srs_write_file(kh_srs_t *srs, uint8_t *out, size_t cap);
+int kh_srs_create_from_file(int curve, const uint8_t *file, size_t len, size_t limit /* 0 = all */, kh_srs_t **out);
+typedef struct kh_wire_section kh_wire_section_t;
+struct kh_wire_section { const uint8_t *bytes; size_t count; };   /* count records of 33 bytes, or count elements of 32 */
+int kh_proofs_from_wire(int curve, const kh_wire_section_t *sections /* k x n_sections */, size_t n_sections, size_t k, kh_proof_t **out /* k */);
 
 /* ---- Fiat-Shamir sponges (host side) --------------------------------------
  * The transcript of kimchi's prover / verifier: Kimchi Poseidon (width 3, rate 2, 55 full rounds, x^7) under

@@ -88,6 +88,7 @@ class SRS {                                  // trait SRS<G> (lib.rs:61-241) bac
         for (size_t j = 0; j < cnt; j++) { pc.chunks[j].infinity = inf[j] != 0; if (!inf[j]) { std::copy(&xy[8 * j], &xy[8 * j + 4], pc.chunks[j].x.begin()); std::copy(&xy[8 * j + 4], &xy[8 * j + 8], pc.chunks[j].y.begin()); } }
         return pc;
     }
+    SRS(Curve c, kh_srs_t* made) : h_(made), curve_(c), n_(kh_srs_size(made)) {}          // adopts a handle
   public:
     SRS(Curve c, const std::vector<std::array<uint64_t, 8>>& g) : curve_(c), n_(g.size()) { check(kh_srs_create(int(c), g[0].data(), g.size(), &h_)); }
     // SRS::create(depth) (ipa.rs:751-778)
@@ -95,6 +96,18 @@ class SRS {                                  // trait SRS<G> (lib.rs:61-241) bac
         std::vector<std::array<uint64_t, 8>> g(depth);
         check(kh_srs_generate(int(c), 0, depth, g[0].data(), 0));
         return SRS(c, g);
+    }
+    // from the serialised form: n compressed records of 33 bytes (h: the blinding base as one record, or null), or the contents of an srs/*.srs file
+    // (limit: keep the first `limit` points, 0 = all); decoded on the device, no affine copy on the host
+    static SRS from_compressed(Curve c, const uint8_t* g_bytes, size_t n, const uint8_t* h_bytes = nullptr) {
+        kh_srs_t* h = nullptr;
+        check(kh_srs_create_compressed(int(c), g_bytes, n, h_bytes, &h));
+        return SRS(c, h);
+    }
+    static SRS from_file(Curve c, const std::vector<uint8_t>& file, size_t limit = 0) {
+        kh_srs_t* h = nullptr;
+        check(kh_srs_create_from_file(int(c), file.data(), file.size(), limit, &h));
+        return SRS(c, h);
     }
     SRS(const SRS&) = delete; SRS& operator=(const SRS&) = delete;
     SRS(SRS&& o) noexcept : h_(o.h_), curve_(o.curve_), n_(o.n_) { o.h_ = nullptr; }

@@ -169,6 +169,16 @@ static constexpr size_t INV_MAX_BLOCKS = 4096;
 int field_inverse(Context& C, int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
 int field_sqrt(Context& C, int field, const uint64_t* in_dev, size_t n, uint64_t* out_dev, uint64_t* out_is_square_dev, uint32_t* flags_dev, unsigned bit);
 int field_bits(Context& C, int field, const uint64_t* in_dev, int format, unsigned num_bits, size_t n, uint64_t* out_dev, uint32_t* flags_dev, unsigned bit);
+// point_codec.hip: the 33-byte compressed record (include/kimchi_hip.h).  The launchers are queued on C.stream (arguments validated by the entry points;
+// 1 <= n < 2^32; inf_dev, status_dev and flags_dev nullable) and the decoder counts its launch (CNT_POINT_CODEC_LAUNCHES).  points_decompress_staged is
+// the host-memory route of kh_points_decompress and kh_proofs_from_wire: it takes the context's lock, stages the records through the context's
+// scratch, launches once and waits; out_xy (n x 8), out_inf and status (n each) are host arrays.  (kh_srs_create_compressed in srs.cpp launches into
+// the handle's table 0 itself, under the lock srs_create holds.)
+int points_compress_launch(Context& C, int curve, const uint64_t* xy_dev, const uint8_t* inf_dev, size_t n, uint8_t* out_dev);
+int points_decompress_launch(Context& C, int curve, const uint8_t* bytes_dev, size_t n, uint64_t* out_xy_dev, uint8_t* out_inf_dev, uint8_t* status_dev,
+                             uint32_t* flags_dev, unsigned bit);
+int points_decompress_staged(int curve, const uint8_t* bytes, size_t n, uint64_t* out_xy, uint8_t* out_inf, uint8_t* status);
+const char* point_status_name(unsigned status);
 // A group of wire steps of a witness schedule in one launch (k_cell_moves): one resident 16-byte record per cell.  The dense side of every move is
 // the run's arena, `dense` words of 8 bytes from its start; flag: the step's bit, or CELL_MOVE_NO_FLAG.
 struct CellMove { uint32_t row, meta, dense_lo, dense_hi; };

@@ -2,6 +2,7 @@
 #include <stdlib.h>
 
 #include "api_internal.hpp"
+#include "srs_file.hpp"
 
 using namespace kh;
 
@@ -145,6 +146,83 @@ int kh_srs_create_device_range(int curve, size_t start, size_t depth, kh_srs_t**
     KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "unknown curve id %d", curve);
     KH_REQUIRE(start + depth <= ((size_t)1 << 32), "SRS index must fit u32 (ipa.rs:758)");
     return srs_create(curve, depth, out, [&](Context& C, void* g) { return srs_generate_device(C, curve, start, depth, g); });
+}
+// n records of g and (nullable) the record of h, decoded by ONE launch straight into table 0: h lands in the slot behind the basis, which is H's own
+// and holds a placeholder until the first opening, and is read back from there
+int kh_srs_create_compressed(int curve, const uint8_t* g_bytes, size_t n, const uint8_t* h_bytes, kh_srs_t** out) {
+    KH_REQUIRE(out && g_bytes && n > 0, "kh_srs_create_compressed: null argument or n == 0");
+    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "unknown curve id %d", curve);
+    KH_REQUIRE(n < ((size_t)1 << 32), "kh_srs_create_compressed: %zu records, the limit is 2^32 - 1", n);
+    const size_t m = n + (h_bytes ? 1 : 0);
+    uint64_t h_xy[8];
+    kh_srs_t* srs = nullptr;
+    int rc = srs_create(curve, n, &srs, [&](Context& C, void* g) -> int {
+        DevBuf &rec = C.scratch("point_codec_bytes"), &inf = C.scratch("point_codec_inf"), &st = C.scratch("point_codec_status");
+        int r;
+        if ((r = rec.reserve(m * KH_POINT_BYTES)) || (r = inf.reserve(m)) || (r = st.reserve(m))) return r;
+        KH_HIP(hipMemcpyAsync(rec.p, g_bytes, n * KH_POINT_BYTES, hipMemcpyHostToDevice, C.stream));
+        if (h_bytes) KH_HIP(hipMemcpyAsync(rec.as<uint8_t>() + n * KH_POINT_BYTES, h_bytes, KH_POINT_BYTES, hipMemcpyHostToDevice, C.stream));
+        if ((r = points_decompress_launch(C, curve, rec.as<uint8_t>(), m, (uint64_t*)g, inf.as<uint8_t>(), st.as<uint8_t>(), nullptr, 0))) return r;
+        std::vector<uint8_t> status(m);
+        KH_HIP(hipMemcpyAsync(status.data(), st.p, m, hipMemcpyDeviceToHost, C.stream));
+        if (h_bytes) KH_HIP(hipMemcpyAsync(h_xy, (const char*)g + n * 64, 64, hipMemcpyDeviceToHost, C.stream));
+        KH_HIP(hipStreamSynchronize(C.stream));
+        for (size_t i = 0; i < m; i++) {
+            if (status[i] == KH_POINT_OK) continue;
+            if (i < n) set_error("kh_srs_create_compressed: record %zu is %s: a basis point must be a point", i, point_status_name(status[i]));
+            else set_error("kh_srs_create_compressed: the record of the blinding base is %s", point_status_name(status[i]));
+            return KH_E_INVALID;
+        }
+        return KH_OK;
+    });
+    if (rc) return rc;
+    if (h_bytes && (rc = kh_srs_set_blinding_base(srs, h_xy))) { kh_srs_free(srs); return rc; }
+    *out = srs;
+    return KH_OK;
+}
+int kh_srs_get_g_compressed(kh_srs_t* srs, size_t offset, size_t count, uint8_t* out) {
+    KH_ON_DEVICE_OF(srs);
+    KH_REQUIRE(srs && (out || count == 0), "kh_srs_get_g_compressed: null argument");
+    KH_REQUIRE(offset <= srs->n && count <= srs->n - offset, "range [%zu, %zu) beyond the SRS size %zu", offset, offset + count, srs->n);
+    if (count == 0) return KH_OK;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    DevBuf& rec = C.scratch("point_codec_bytes");
+    int rc = rec.reserve(count * KH_POINT_BYTES); if (rc) return rc;
+    if ((rc = points_compress_launch(C, srs->curve, (const uint64_t*)((const char*)srs->g.p + offset * 64), nullptr, count, rec.as<uint8_t>()))) return rc;
+    KH_HIP(hipMemcpyAsync(out, rec.p, count * KH_POINT_BYTES, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipStreamSynchronize(C.stream));
+    return KH_OK;
+}
+size_t kh_srs_file_bytes(size_t n) { return kh_srs_file::file_bytes(n); }
+int kh_srs_write_file(kh_srs_t* srs, uint8_t* out, size_t cap) {
+    KH_REQUIRE(srs && out, "kh_srs_write_file: null argument");
+    const size_t want = kh_srs_file::file_bytes(srs->n);
+    KH_REQUIRE(want && cap >= want, "kh_srs_write_file: %zu points need %zu bytes, the buffer has %zu", srs->n, want, cap);
+    std::vector<uint8_t> records(srs->n * KH_POINT_BYTES);
+    uint8_t h_record[KH_POINT_BYTES];
+    uint64_t h_xy[8] __attribute__((aligned(16)));
+    int rc = kh_srs_get_g_compressed(srs, 0, srs->n, records.data()); if (rc) return rc;
+    if ((rc = kh_srs_get_blinding_base(srs, h_xy))) return rc;
+    {
+        KH_ON_DEVICE_OF(srs);
+        if ((rc = kh_points_compress(srs->curve, h_xy, nullptr, 1, h_record))) return rc;
+    }
+    char err[192];
+    if (kh_srs_file::write(records.data(), srs->n, h_record, out, cap, err, sizeof err)) { set_error("kh_srs_write_file: %s", err); return KH_E_INVALID; }
+    return KH_OK;
+}
+int kh_srs_create_from_file(int curve, const uint8_t* file, size_t len, size_t limit, kh_srs_t** out) {
+    KH_REQUIRE(out && file, "kh_srs_create_from_file: null argument");
+    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "unknown curve id %d", curve);
+    kh_srs_file::View v;
+    char err[192];
+    if (kh_srs_file::parse(file, len, &v, err, sizeof err)) { set_error("kh_srs_create_from_file: %s", err); return KH_E_INVALID; }
+    const size_t n = limit && limit < v.count ? limit : v.count;
+    KH_REQUIRE(n > 0, "kh_srs_create_from_file: the file holds no point");
+    std::vector<uint8_t> records(n * KH_POINT_BYTES);                        // the items without their markers
+    for (size_t i = 0; i < n; i++) memcpy(records.data() + i * KH_POINT_BYTES, v.record(i), KH_POINT_BYTES);
+    return kh_srs_create_compressed(curve, records.data(), n, v.record(v.count), out);
 }
 int kh_srs_get_g(kh_srs_t* srs, size_t offset, size_t count, uint64_t* out_xy) {
     KH_ON_DEVICE_OF(srs);

@@ -186,6 +186,58 @@ def set_wide_min_n(n: int):
     _check(_lib.kh_msm_set_wide_min_n(n))
 
 
+POINT_BYTES = _CONSTANTS["KH_POINT_BYTES"]
+POINT_OK, POINT_INFINITY, POINT_BAD_FLAGS, POINT_NOT_CANONICAL, POINT_NOT_ON_CURVE = (_CONSTANTS["KH_POINT_" + _n] for _n in (
+    "OK", "INFINITY", "BAD_FLAGS", "NOT_CANONICAL", "NOT_ON_CURVE"))
+
+
+def _records(b):
+    """compressed points as a C-contiguous (n, 33) uint8 array: from bytes, a list of 33-byte strings or an array"""
+    if isinstance(b, (bytes, bytearray, memoryview)):
+        b = np.frombuffer(bytes(b), dtype=np.uint8)
+    elif isinstance(b, (list, tuple)):
+        b = np.frombuffer(b"".join(bytes(r) for r in b), dtype=np.uint8)
+    return np.ascontiguousarray(b, dtype=np.uint8).reshape(-1, POINT_BYTES)
+
+
+def points_compress(curve: int, xy, inf=None):
+    """kh_points_compress: (n, 8) affine Montgomery limbs (+ infinity bytes) -> (n, 33) compressed records, encoded on the device"""
+    xy = _c64(xy, (-1, 8))
+    if inf is not None:
+        inf = np.ascontiguousarray(inf, dtype=np.uint8).reshape(-1)
+    out = np.zeros((xy.shape[0], POINT_BYTES), dtype=np.uint8)
+    _check(_lib.kh_points_compress(curve, _p64(xy), _p8(inf), xy.shape[0], _p8(out)))
+    return out
+
+
+def points_decompress_raw(curve: int, records):
+    """kh_points_decompress without raising: (return code, xy (n, 8), inf (n,), status (n,), first bad index or None)"""
+    rec = _records(records)
+    n = rec.shape[0]
+    xy = np.zeros((n, 8), dtype=np.uint64); inf = np.zeros(n, dtype=np.uint8); status = np.zeros(n, dtype=np.uint8)
+    first = C.c_size_t(n)
+    rc = _lib.kh_points_decompress(curve, _p8(rec), n, _p64(xy), _p8(inf), _p8(status), C.byref(first))
+    return rc, xy, inf, status, (first.value if first.value < n else None)
+
+
+def points_decompress(curve: int, records):
+    """kh_points_decompress: (n, 33) records -> (xy (n, 8), inf (n,)); a malformed record raises KhError naming the first one"""
+    rc, xy, inf, _status, _first = points_decompress_raw(curve, records)
+    _check(rc)
+    return xy, inf
+
+
+def points_compress_dev(curve: int, xy, inf, n: int, out):
+    """kh_points_compress_dev: n points in a DevBuf (64 bytes each; inf: a DevBuf of n bytes or None) -> n x 33 bytes in `out`; a queued vector step"""
+    _check(_lib.kh_points_compress_dev(curve, _ptr(xy), _ptr(inf), n, _ptr(out)))
+
+
+def points_decompress_dev(curve: int, records, n: int, out_xy, out_inf, status=None, flags=None, bit: int = 0):
+    """kh_points_decompress_dev: n x 33 bytes in a DevBuf -> out_xy (n x 64 bytes), out_inf and (nullable) status (n bytes each); the flag bit is raised
+    by any record that is neither a point nor the point at infinity; a queued vector step"""
+    _check(_lib.kh_points_decompress_dev(curve, _ptr(records), n, _ptr(out_xy), _ptr(out_inf), _ptr(status), _ptr(flags), bit))
+
+
 class Srs:
     """Device-resident SRS bases (the g half of ipa::SRS<G>, poly-commitment/src/ipa.rs:53-75)."""
 
@@ -206,10 +258,47 @@ class Srs:
         """SRS::create(depth) (ipa.rs:751-778) on the device; start > 0 gives the slice g[start, start+depth)."""
         return cls(curve, None, depth, start)
 
+    @classmethod
+    def _adopt(cls, curve: int, handle):
+        self = cls.__new__(cls)
+        self.curve, self._h, self.n = curve, handle, int(_lib.kh_srs_size(handle))
+        return self
+
+    @classmethod
+    def from_compressed(cls, curve: int, g_bytes, h_bytes=None):
+        """kh_srs_create_compressed: the bases from (n, 33) compressed records, decoded on the device straight into the handle's tables; h_bytes: the
+        blinding base as one record.  A record that is not a point (an infinity record too) raises KhError naming its index."""
+        g = _records(g_bytes)
+        h = _records(h_bytes) if h_bytes is not None else None
+        handle = C.c_void_p()
+        _check(_lib.kh_srs_create_compressed(curve, _p8(g), g.shape[0], _p8(h), C.byref(handle)))
+        return cls._adopt(curve, handle)
+
+    @classmethod
+    def from_file_bytes(cls, curve: int, data: bytes, limit: int = 0):
+        """kh_srs_create_from_file: the contents of an srs/*.srs file; limit (0 = all) keeps the first `limit` points, h is the file's last record."""
+        buf = np.frombuffer(bytes(data) + b"\0", dtype=np.uint8)               # (never a null pointer, whatever the length)
+        handle = C.c_void_p()
+        _check(_lib.kh_srs_create_from_file(curve, buf.ctypes.data_as(U8P), buf.size - 1, limit, C.byref(handle)))
+        return cls._adopt(curve, handle)
+
+    def to_file_bytes(self) -> bytes:
+        """kh_srs_write_file: the handle's bases and blinding base in the layout of the srs/*.srs files"""
+        out = np.zeros(int(_lib.kh_srs_file_bytes(self.n)), dtype=np.uint8)
+        _check(_lib.kh_srs_write_file(self._h, _p8(out), out.size))
+        return out.tobytes()
+
     def get_g(self, offset: int = 0, count: int = None):
         count = self.n - offset if count is None else count
         out = np.zeros((count, 8), dtype=np.uint64)
         _check(_lib.kh_srs_get_g(self._h, offset, count, _p64(out)))
+        return out
+
+    def get_g_compressed(self, offset: int = 0, count: int = None):
+        """kh_srs_get_g_compressed: g[offset, offset + count) as (count, 33) compressed records, encoded on the device"""
+        count = self.n - offset if count is None else count
+        out = np.zeros((count, POINT_BYTES), dtype=np.uint8)
+        _check(_lib.kh_srs_get_g_compressed(self._h, offset, count, _p8(out)))
         return out
 
     def debug_rebase_points(self, coef):
@@ -409,7 +498,8 @@ def msm_points_batch(curve: int, xy, scalars, inf=None, mont: bool = True):
 
 
 def counter(name: str) -> int:
-    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds, lookup_sorted_dev."""
+    """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds, lookup_sorted_dev,
+    ipa_concurrent, ipa_waited, table_staged_words, point_codec_launches."""
     return int(_lib.kh_counter(name.encode()))
 
 
@@ -1063,6 +1153,21 @@ def witness_lookup_message(report: "WitnessReportC", lookup: "WitnessLookupC", c
     return buf.value.decode()
 
 
+def _proof_sections(pr):
+    """{section name: (xy (k, 8), inf (k,)) | (k, 4) limbs} of a proof handle: copies of what kh_proof_section shows"""
+    out = {}
+    for name, sid in PROOF_SECTIONS.items():
+        lp = C.POINTER(C.c_uint64)(); fp = C.POINTER(C.c_uint8)(); cnt = C.c_size_t(0)
+        _check(_lib.kh_proof_section(pr, sid, C.byref(lp), C.byref(fp), C.byref(cnt)))
+        k = cnt.value
+        if fp:                                    # points
+            out[name] = (np.ctypeslib.as_array(lp, shape=(k, 8)).copy() if k else np.zeros((0, 8), np.uint64),
+                         np.ctypeslib.as_array(fp, shape=(k,)).copy() if k else np.zeros(0, np.uint8))
+        else:
+            out[name] = np.ctypeslib.as_array(lp, shape=(k, 4)).copy() if k else np.zeros((0, 4), np.uint64)
+    return out
+
+
 class NativeProverIndex:
     """kh_prover_index_new: the C++ prover's view of device-resident index columns (they must outlive the handle); or, NativeProverIndex.create,
     kh_prover_index_create: an index built from gate records that owns its columns."""
@@ -1211,16 +1316,7 @@ class NativeProverIndex:
                   rnd.shape[0] if rnd is not None else 0, flags, _p64(chals) if m else None, rounds,
                   _p64(cxy) if m else None, _p8(cinf) if m else None, cch, m, *rt_args, C.byref(pr)))
         try:
-            out = {}
-            for name, sid in PROOF_SECTIONS.items():
-                lp = C.POINTER(C.c_uint64)(); fp = C.POINTER(C.c_uint8)(); cnt = C.c_size_t(0)
-                _check(_lib.kh_proof_section(pr, sid, C.byref(lp), C.byref(fp), C.byref(cnt)))
-                k = cnt.value
-                if fp:                                    # points
-                    out[name] = (np.ctypeslib.as_array(lp, shape=(k, 8)).copy() if k else np.zeros((0, 8), np.uint64),
-                                 np.ctypeslib.as_array(fp, shape=(k,)).copy() if k else np.zeros(0, np.uint8))
-                else:
-                    out[name] = np.ctypeslib.as_array(lp, shape=(k, 4)).copy() if k else np.zeros((0, 4), np.uint64)
+            out = _proof_sections(pr)
             ph = (C.c_double * 6)()
             _lib.kh_proof_phase_seconds(pr, ph, 6)
             return out, dict(zip(PROOF_PHASES, list(ph)))
@@ -1298,6 +1394,10 @@ class Proof:
         arr, _keep = _section_array(sections, PROOF_SECTIONS)
         _check(_lib.kh_proof_from_sections(arr, len(arr), C.byref(self._h)))
 
+    def sections(self):
+        """the proof's sections as NativeProverIndex.prove returns them (kh_proof_section)"""
+        return _proof_sections(self._h)
+
     def free(self):
         if self._h:
             _lib.kh_proof_free(self._h); self._h = C.c_void_p()
@@ -1307,6 +1407,45 @@ class Proof:
             self.free()
         except Exception:
             pass
+
+
+WireSectionC = _STRUCTURES["kh_wire_section_t"]
+_ELEMENT_SECTIONS = ("evals", "public_evals", "ft_eval1", "z1_z2", "challenges")      # count x 32 bytes; every other section is points
+
+
+def proofs_from_wire_raw(curve: int, proofs, out_before: int = 0):
+    """kh_proofs_from_wire without raising: (return code, the k entries of `out` afterwards -- out_before where the call left them alone)"""
+    k, ns = len(proofs), len(PROOF_SECTIONS)
+    arr = (WireSectionC * max(k * ns, 1))()
+    keep = []
+    for p, sections in enumerate(proofs):
+        for name, sid in PROOF_SECTIONS.items():
+            v = sections.get(name)
+            if v is None:
+                continue
+            b = np.ascontiguousarray(np.frombuffer(bytes(v), dtype=np.uint8) if isinstance(v, (bytes, bytearray, memoryview)) else v, dtype=np.uint8).reshape(-1)
+            width = 32 if name in _ELEMENT_SECTIONS else POINT_BYTES
+            assert b.size % width == 0, f"section {name}: {b.size} bytes are no multiple of {width}"
+            keep.append(b)
+            if b.size:
+                arr[p * ns + sid] = WireSectionC(b.ctypes.data_as(U8P), b.size // width)
+    out = (C.c_void_p * max(k, 1))(*([out_before] * max(k, 1)))
+    rc = _lib.kh_proofs_from_wire(curve, arr, ns, k, out)
+    return rc, [out[p] or 0 for p in range(k)]
+
+
+def proofs_from_wire(curve: int, proofs):
+    """kh_proofs_from_wire: [Proof] from a list of {section name: bytes-like} in the serialised form -- point sections count x 33 compressed records, element
+    sections count x 32 little-endian canonical integers; every point of every proof is decoded in one launch.  A bad record or element raises KhError
+    naming proof, section and index, and no proof is made."""
+    rc, handles = proofs_from_wire_raw(curve, proofs)
+    _check(rc)
+    made = []
+    for h in handles:
+        pr = Proof.__new__(Proof)
+        pr._h = C.c_void_p(h)
+        made.append(pr)
+    return made
 
 
 def _trace(t: "VerifyTraceC"):
