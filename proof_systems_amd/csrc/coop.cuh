@@ -134,4 +134,42 @@ __device__ __forceinline__ Fe<BF> quad_shfl_down(const Fe<BF>& v, int quads) {
 template <class F>
 __device__ __forceinline__ Fe<F> quad_identity() { return Fe<F>::zero(); }     // all-zero record = identity (ZZ = 0)
 
+// ---- folds: every sum of points over the quads of a wave or of a block is one of these three
+// the sum of the points held by the 16 quads of a wave: 4 tree levels, valid in quad 0 (lanes 0..3)
+template <class F>
+__device__ __forceinline__ Fe<F> quad_wave_sum(Fe<F> acc) {
+    for (int d = 8; d >= 1; d >>= 1) acc = quad_add<F>(acc, quad_shfl_down<F>(acc, d));
+    return acc;
+}
+// the sum of the records first, first + stride, ... below `end` of `rec` (128 bytes each) over the 16 quads of a wave, `first` = this quad's own: each quad adds
+// its share in sequence, then the wave's tree.  Valid in quad 0.
+template <class F>
+__device__ __forceinline__ Fe<F> quad_chunk_sum(const uint8_t* rec, u32 first, u32 end, u32 stride) {
+    Fe<F> acc = quad_identity<F>();
+    for (u32 k = first; k < end; k += stride) acc = quad_add<F>(acc, quad_load<F>(rec + (size_t)k * 128));
+    return acc = quad_wave_sum<F>(acc);
+}
+// the sum of the wave sums (quad_wave_sum) of a block of nw <= 16 waves: lanes 0..3 of every wave park their coordinate in sh (32 nw words), quad w of wave 0
+// takes wave w's sum, and the tree over those quads has as many levels as nw needs (a literal nw folds to exactly those).  Valid in threads 0..3.  Every
+// thread of the block calls it; a second call needs a barrier of the caller's in front, which is what keeps the parked words until they are read.
+template <class F>
+__device__ __forceinline__ Fe<F> quad_block_sum(Fe<F> acc, u32* sh, u32 nw) {
+    const u32 role = threadIdx.x & 3u, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quad = lane >> 2;
+    if (lane < 4) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) sh[(wave * 4 + role) * 8 + k] = acc.v[k];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        Fe<F> o = Fe<F>::zero();
+        if (quad < nw) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) o.v[k] = sh[(quad * 4 + role) * 8 + k];
+        }
+        acc = o;
+        for (int d = nw > 1 ? 1 << (31 - __clz((int)(nw - 1))) : 0; d >= 1; d >>= 1) acc = quad_add<F>(acc, quad_shfl_down<F>(acc, d));      // from the largest power of two below nw
+    }
+    return acc;
+}
+
 }  // namespace kh

@@ -133,4 +133,19 @@ __device__ __forceinline__ Xyzz<F> scalar_mul(const Xyzz<F>& p, const u32 k[8]) 
 template <class F>
 __device__ __forceinline__ Xyzz<F> negate(const Xyzz<F>& a) { Xyzz<F> r = a; r.y = neg<F>(a.y); return r; }
 
+// v normalised to affine: x | y as 64 bytes at xy and the infinity flag at inf; the identity as zeros + flag 1 (one inversion: the __noinline__ inv)
+template <class F>
+__device__ __forceinline__ void store_affine(const Xyzz<F>& v, uint8_t* xy, uint8_t* inf) {
+    Fe<F> x = Fe<F>::zero(), y = Fe<F>::zero();
+    uint8_t flag = 1;
+    if (!v.is_identity()) {
+        Fe<F> izzz = inv<F>(v.zzz);
+        Fe<F> izz = sqr<F>(mul<F>(izzz, v.zz));
+        x = mul<F>(v.x, izz); y = mul<F>(v.y, izzz);
+        flag = 0;
+    }
+    x.store(xy); y.store(xy + 32);
+    *inf = flag;
+}
+
 }  // namespace kh

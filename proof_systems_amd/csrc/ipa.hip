@@ -3,12 +3,12 @@
 //   fold_scalars : a' = a_lo + u^-1 * a_hi  /  b' = b_lo + u * b_hi          (ipa.rs:980-1003)
 //   fold_points  : g' = g_lo + [u] g_hi  = CommitmentCurve::combine_one       (ipa.rs:1006, commitment.rs:576-579)
 //   fold_points_endo : the same by the endo ladder of combine_one_endo       (combine.rs:292-340)
-//   round_prepare / round_fold : the device-resident opening loop (no basis folding, see below)
+//   round_step / round_fold : the device-resident opening loop (no basis folding, see below)
 //   inner_product: <a, b>                                                      (utils/src/field_helpers.rs:273-279)
 // Element-wise and embarrassingly parallel; the basis fold is one 255-bit double-and-add per point
 // (a ~380-operation dependent chain: ~4 ms whatever the length below ~60k points).
 #include "common.hpp"
-#include "curve.cuh"
+#include "block_sum.cuh"
 #include "host_ec.hpp"
 #include "msm.hpp"
 
@@ -29,20 +29,7 @@ k_inner_product(const u64* __restrict__ a, const u64* __restrict__ b, size_t n, 
     Fe<F> acc = Fe<F>::zero();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         acc = add<F>(acc, mul<F>(Fe<F>::load(a + 4 * i), Fe<F>::load(b + 4 * i)));
-#pragma unroll
-    for (int k = 0; k < 8; k++) sh[k * 256 + threadIdx.x] = acc.v[k];
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            Fe<F> o;
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[k * 256 + threadIdx.x + s];
-            acc = add<F>(acc, o);
-#pragma unroll
-            for (int k = 0; k < 8; k++) sh[k * 256 + threadIdx.x] = acc.v[k];
-        }
-        __syncthreads();
-    }
+    acc = block_tree_sum<F, 256>(acc, sh);
     if (threadIdx.x == 0) acc.store(partial + 4 * blockIdx.x);
 }
 template <class BF>
@@ -51,21 +38,12 @@ k_fold_points(const uint8_t* __restrict__ g_lo, const uint8_t* __restrict__ g_hi
               uint8_t* __restrict__ out_xy, uint8_t* __restrict__ out_inf) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    u32 kw[8];
+    u32 kw[8];                                              // (filled here, not by a helper: behind a call the compiler moves the array from registers to LDS)
 #pragma unroll
     for (int w = 0; w < 4; w++) { u64 l = u_plain[w]; kw[2 * w] = (u32)l; kw[2 * w + 1] = (u32)(l >> 32); }
     Xyzz<BF> v = scalar_mul<BF>(Xyzz<BF>::from_affine(Aff<BF>::load(g_hi + i * 64)), kw);
     v = madd<BF>(v, Aff<BF>::load(g_lo + i * 64), false);
-    Fe<BF> x = Fe<BF>::zero(), y = Fe<BF>::zero();
-    uint8_t inf = 1;
-    if (!v.is_identity()) {
-        Fe<BF> izzz = inv<BF>(v.zzz);
-        Fe<BF> izz = sqr<BF>(mul<BF>(izzz, v.zz));
-        x = mul<BF>(v.x, izz); y = mul<BF>(v.y, izzz);
-        inf = 0;
-    }
-    x.store(out_xy + i * 64); y.store(out_xy + i * 64 + 32);
-    out_inf[i] = inf;
+    store_affine<BF>(v, out_xy + 64 * i, out_inf + i);
 }
 
 // The endo ladder of CommitmentCurve::combine_one_endo (commitment.rs:581-589 -> combine.rs:292-340,
@@ -91,16 +69,7 @@ k_fold_points_endo(const uint8_t* __restrict__ g_lo, const uint8_t* __restrict__
         acc = madd<BF>(dbl<BF>(acc), S, !b0);              // (acc + s) + acc = 2 acc + s
     }
     acc = madd<BF>(acc, Aff<BF>::load(g_lo + i * 64), false);
-    Fe<BF> x = Fe<BF>::zero(), y = Fe<BF>::zero();
-    uint8_t inf = 1;
-    if (!acc.is_identity()) {
-        Fe<BF> izzz = inv<BF>(acc.zzz);
-        Fe<BF> izz = sqr<BF>(mul<BF>(izzz, acc.zz));
-        x = mul<BF>(acc.x, izz); y = mul<BF>(acc.y, izzz);
-        inf = 0;
-    }
-    x.store(out_xy + i * 64); y.store(out_xy + i * 64 + 32);
-    out_inf[i] = inf;
+    store_affine<BF>(acc, out_xy + 64 * i, out_inf + i);
 }
 
 // ---------------------------------------------------------------- device-resident opening rounds
@@ -115,75 +84,6 @@ k_fold_points_endo(const uint8_t* __restrict__ g_lo, const uint8_t* __restrict__
 // bit-identical after normalisation.
 struct Fe4 { u64 l[4]; };
 
-// side 0 (L): <a[m..2m), b[0..m)>; side 1 (R): <a[0..m), b[m..2m)>; per-block partial sums
-template <class F>
-__global__ void __launch_bounds__(256)
-k_ipa_ip(const u64* __restrict__ a, const u64* __restrict__ b, size_t m, u64* __restrict__ partial) {
-    __shared__ u32 sh[256 * 8];
-    const int side = blockIdx.y;
-    const u64* pa = side == 0 ? a + 4 * m : a;
-    const u64* pb = side == 0 ? b : b + 4 * m;
-    Fe<F> acc = Fe<F>::zero();
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (size_t)gridDim.x * blockDim.x)
-        acc = add<F>(acc, mul<F>(Fe<F>::load(pa + 4 * i), Fe<F>::load(pb + 4 * i)));
-#pragma unroll
-    for (int k = 0; k < 8; k++) sh[k * 256 + threadIdx.x] = acc.v[k];
-    __syncthreads();
-    for (int s = 128; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            Fe<F> o;
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[k * 256 + threadIdx.x + s];
-            acc = add<F>(acc, o);
-#pragma unroll
-            for (int k = 0; k < 8; k++) sh[k * 256 + threadIdx.x] = acc.v[k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) acc.store(partial + 4 * ((size_t)side * gridDim.x + blockIdx.x));
-}
-// block = side: sums the <= 64 partials and fills the two extra scalar slots of that side's MSM:
-// sc[side][n] = rand (the H term), sc[side][n + 1] = the inner product (the U term)
-template <class F>
-__global__ void __launch_bounds__(64)
-k_ipa_ip_fin(const u64* __restrict__ partial, unsigned nblk, Fe4 rand_l, Fe4 rand_r, size_t n, u64* __restrict__ sc) {
-    __shared__ u32 sh[64 * 8];
-    const int side = blockIdx.x;
-    Fe<F> acc = Fe<F>::zero();
-    if (threadIdx.x < nblk) acc = Fe<F>::load(partial + 4 * ((size_t)side * nblk + threadIdx.x));
-#pragma unroll
-    for (int k = 0; k < 8; k++) sh[k * 64 + threadIdx.x] = acc.v[k];
-    __syncthreads();
-    for (int s = 32; s >= 1; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            Fe<F> o;
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[k * 64 + threadIdx.x + s];
-            acc = add<F>(acc, o);
-#pragma unroll
-            for (int k = 0; k < 8; k++) sh[k * 64 + threadIdx.x] = acc.v[k];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        u64* dst = sc + 4 * ((size_t)side * (n + 2) + n);
-        const Fe4& r = side == 0 ? rand_l : rand_r;
-        dst[0] = r.l[0]; dst[1] = r.l[1]; dst[2] = r.l[2]; dst[3] = r.l[3];
-        acc.store(dst + 4);
-    }
-}
-// the two expanded scalar vectors over the original basis (N_j = 2m = 2^logN)
-template <class F>
-__global__ void k_ipa_expand(const u64* __restrict__ a, const u64* __restrict__ coef, size_t n, size_t m, unsigned logN, u64* __restrict__ sc) {
-    size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const size_t r = t & (2 * m - 1), q = t >> logN;
-    const bool lo = r < m;
-    Fe<F> v = mul<F>(Fe<F>::load(a + 4 * (lo ? r + m : r - m)), Fe<F>::load(coef + 4 * q));
-    const Fe<F> z = Fe<F>::zero();
-    (lo ? v : z).store(sc + 4 * t);
-    (lo ? z : v).store(sc + 4 * ((n + 2) + t));
-}
 // a' = a_lo + u^-1 a_hi, b' = b_lo + u b_hi (ipa.rs:980-1003); coef' = coef (x) (1, u)  (combine_one_endo's scalar, ipa.rs:1006)
 template <class F>
 __global__ void k_ipa_fold(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __restrict__ coef, size_t m, size_t ncoef,
@@ -210,7 +110,7 @@ __global__ void k_ipa_fold(const u64* __restrict__ a, const u64* __restrict__ b,
 // `extra`: the slots behind the n points of the table set the round's MSM runs over (1 + KH_IPA_OPENINGS on the handle's tables, 2 on rebased ones) --
 // each side's scalar vector has n + extra entries: the points, H, then the U slots; `uslot`: which of those is this opening's.  The other openings'
 // entries are left alone (zeroed by kh_ipa_begin: a zero digit makes no entry, their points are never fetched).
-// Replaces k_ipa_fold + k_ipa_ip + k_ipa_ip_fin + k_ipa_expand: four dependent launches (~25 us of an opening round) -> one.
+// One launch where a round had four dependent ones (k_ipa_fold, two for the inner products, one for the expansion: ~25 us of an opening round).
 template <class F>
 __global__ void __launch_bounds__(256)
 k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __restrict__ coef, size_t n, size_t cur2, unsigned logN2, unsigned extra, size_t ncoef,
@@ -245,19 +145,9 @@ k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __re
         if (has_fold) { alo.store(a2 + 4 * t); ahi.store(a2 + 4 * (t + m)); blo.store(b2 + 4 * t); bhi.store(b2 + 4 * (t + m)); }
         accL = mul<F>(ahi, blo); accR = mul<F>(alo, bhi);
     }
-    auto wave_sum = [](Fe<F> v) {                          // sum over the 64 lanes of a wave (valid in lane 0)
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            Fe<F> o;
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = __shfl_down(v.v[k], d, 64);
-            v = add<F>(v, o);
-        }
-        return v;
-    };
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     if (blockIdx.x < nblk_ip) {                            // block sums of the two inner products: wave shuffles, then four values through LDS
-        accL = wave_sum(accL); accR = wave_sum(accR);
+        accL = wave_sum<F>(accL); accR = wave_sum<F>(accR);
         if (lane == 0) {
 #pragma unroll
             for (int k = 0; k < 8; k++) { sh[(wave * 2) * 8 + k] = accL.v[k]; sh[(wave * 2 + 1) * 8 + k] = accR.v[k]; }
@@ -292,7 +182,7 @@ k_ipa_step(const u64* __restrict__ a, const u64* __restrict__ b, const u64* __re
             for (int w = 0; w < 4; w++) l[w] = __hip_atomic_load(src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // written by other blocks
             acc = add<F>(acc, Fe<F>::load(l));
         }
-        acc = wave_sum(acc);
+        acc = wave_sum<F>(acc);
         __syncthreads();
         if (lane == 0) {
 #pragma unroll
@@ -323,18 +213,6 @@ int ipa_round_step(hipStream_t s, int field, int has_fold, const uint64_t* a, co
     return KH_OK;
 }
 
-int ipa_round_prepare(hipStream_t s, int field, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t n, size_t Nj,
-                      const uint64_t rand_l[4], const uint64_t rand_r[4], uint64_t* sc, uint64_t* partial) {
-    const size_t m = Nj / 2;
-    unsigned logN = 0; while (((size_t)1 << logN) < Nj) logN++;
-    const unsigned nblk = (unsigned)std::min<size_t>(64, (m + 255) / 256);
-    Fe4 rl, rr; memcpy(rl.l, rand_l, 32); memcpy(rr.l, rand_r, 32);
-    dim3 eg((unsigned)((n + 255) / 256));
-    KH_FIELD_LAUNCH(field, k_ipa_ip<F>, dim3(nblk, 2), dim3(256), 0, s, a, b, m, partial);
-    KH_FIELD_LAUNCH(field, k_ipa_ip_fin<F>, dim3(2), dim3(64), 0, s, partial, nblk, rl, rr, n, sc);
-    KH_FIELD_LAUNCH(field, k_ipa_expand<F>, eg, dim3(256), 0, s, a, coef, n, m, logN, sc);
-    return KH_OK;
-}
 int ipa_round_fold(hipStream_t s, int field, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t Nj, size_t ncoef,
                    const uint64_t u[4], const uint64_t uinv[4], uint64_t* a2, uint64_t* b2, uint64_t* coef2) {
     const size_t m = Nj / 2, thr = std::max(m, ncoef);

@@ -90,22 +90,13 @@ k_lag_finish(const uint8_t* __restrict__ A, size_t n, const u64* __restrict__ ni
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Xyzz<BF> v = Xyzz<BF>::load(A + i * 128);
-    Fe<BF> x = Fe<BF>::zero(), y = Fe<BF>::zero();
-    uint8_t inf = 1;
     if (!v.is_identity()) {
         u32 kw[8];
 #pragma unroll
         for (int w = 0; w < 4; w++) { u64 l = ninv_plain[w]; kw[2 * w] = (u32)l; kw[2 * w + 1] = (u32)(l >> 32); }
         v = scalar_mul<BF>(v, kw);
-        if (!v.is_identity()) {
-            Fe<BF> izzz = inv<BF>(v.zzz);
-            Fe<BF> izz = sqr<BF>(mul<BF>(izzz, v.zz));
-            x = mul<BF>(v.x, izz); y = mul<BF>(v.y, izzz);
-            inf = 0;
-        }
     }
-    x.store(out_xy + i * 64); y.store(out_xy + i * 64 + 32);
-    out_inf[i] = inf;
+    store_affine<BF>(v, out_xy + 64 * i, out_inf + i);
 }
 
 template <class BF, class SF>

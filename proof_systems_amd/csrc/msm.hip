@@ -30,7 +30,7 @@
 #include <math.h>
 #include "common.hpp"
 #include "env.hpp"
-#include "curve.cuh"
+#include "block_sum.cuh"
 #include "coop.cuh"
 #include "field29.cuh"
 #include "host_ec.hpp"
@@ -1171,8 +1171,20 @@ k_acc_wide_rest(const u32* __restrict__ entries, const u32* __restrict__ off, co
 // ------------------------------------------------------------------------------------ 6 bucket sums
 // buckets with more partials than this go to the wave-per-bucket tree (k_bucket_big); the threshold is a
 // kernel argument: 16 for large problems (throughput), 4 for small ones (shorter dependent chain)
-// hot-bucket bookkeeping in `big`: [0] = #big buckets, [1] = #chunk items, then four arrays of `cap` words:
-// bigkey[], bigcbase[] (first chunk item of that bucket), itemkey[], itemj[]
+// hot-bucket bookkeeping in `big`: [0] = #big buckets, [1] = #chunk items, then four arrays of `cap` words, at these word offsets:
+// the key of big bucket `slot` and its first chunk item; the key of chunk item `it` and which chunk of that bucket it is
+__device__ __forceinline__ size_t hot_key(u32 slot) { return 2 + (size_t)slot; }
+__device__ __forceinline__ size_t hot_cbase(size_t cap, u32 slot) { return 2 + cap + slot; }
+__device__ __forceinline__ size_t item_key(size_t cap, u32 it) { return 2 + 2 * cap + it; }
+__device__ __forceinline__ size_t item_chunk(size_t cap, u32 it) { return 2 + 3 * cap + it; }
+// one thread lists bucket `key` of nt partials: a slot among the big buckets (k_bucket_big) and a chunk item per CHUNK partials (k_bucket_chunk)
+__device__ __forceinline__ void list_hot_bucket(u32* __restrict__ big, size_t cap, u32 key, u32 nt) {
+    u32 nch = (nt + CHUNK - 1) / CHUNK;
+    u32 slot = atomicAdd(&big[0], 1u);
+    u32 cbase = atomicAdd(&big[1], nch);
+    big[hot_key(slot)] = key; big[hot_cbase(cap, slot)] = cbase;
+    for (u32 j = 0; j < nch; j++) { big[item_key(cap, cbase + j)] = key; big[item_chunk(cap, cbase + j)] = j; }
+}
 template <class BF>
 __global__ void __launch_bounds__(256)
 k_bucket_sum(const u32* __restrict__ toff, size_t nkeys, const uint8_t* __restrict__ partial,
@@ -1184,30 +1196,16 @@ k_bucket_sum(const u32* __restrict__ toff, size_t nkeys, const uint8_t* __restri
     u32 t0 = toff[key], nt = toff[key + 1] - t0;
     Xyzz<BF> acc = Xyzz<BF>::identity();
     if (nt > SMALL_NT) {
-        u32 nch = (nt + CHUNK - 1) / CHUNK;
-        u32 slot = atomicAdd(&big[0], 1u);
-        u32 cbase = atomicAdd(&big[1], nch);
-        big[2 + slot] = (u32)key; big[2 + cap + slot] = cbase;
-        for (u32 j = 0; j < nch; j++) { big[2 + 2 * cap + cbase + j] = (u32)key; big[2 + 3 * cap + cbase + j] = j; }
+        list_hot_bucket(big, cap, (u32)key, nt);
     } else if (nt > 0) {
         acc = Xyzz<BF>::load(partial + (size_t)t0 * 128);
         for (u32 k = 1; k < nt; k++) acc = add<BF>(acc, Xyzz<BF>::load(partial + (size_t)(t0 + k) * 128));
     }
     acc.store(buckets + key * 128);
 }
-template <class F>
-__device__ __forceinline__ Xyzz<F> shfl_down(const Xyzz<F>& a, int delta) {
-    Xyzz<F> r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        r.x.v[i] = __shfl_down(a.x.v[i], delta, 64); r.y.v[i] = __shfl_down(a.y.v[i], delta, 64);
-        r.zz.v[i] = __shfl_down(a.zz.v[i], delta, 64); r.zzz.v[i] = __shfl_down(a.zzz.v[i], delta, 64);
-    }
-    return r;
-}
 // Hot buckets in two phases, so that one bucket holding most of the entries (the all-ones witness) is
-// summed by many waves: phase A = one wave per chunk of <= 512 partials (8 per lane + shuffle tree),
-// phase B = one wave per hot bucket over its chunk sums.
+// summed by many waves: phase A = one wave per chunk of <= 128 partials (8 per quad + the wave's tree),
+// phase B = one block per hot bucket over its chunk sums.
 template <class BF>
 __global__ void __launch_bounds__(64)
 k_bucket_chunk(const u32* __restrict__ toff, const uint8_t* __restrict__ partial, const u32* __restrict__ big, size_t cap,
@@ -1218,12 +1216,10 @@ k_bucket_chunk(const u32* __restrict__ toff, const uint8_t* __restrict__ partial
     u32 nitems = big[1];
     const u32 quad = threadIdx.x >> 2;
     for (u32 it = blockIdx.x; it < nitems; it += gridDim.x) {
-        u32 key = big[2 + 2 * cap + it], j = big[2 + 3 * cap + it];
+        u32 key = big[item_key(cap, it)], j = big[item_chunk(cap, it)];
         u32 t0 = toff[key], nt = toff[key + 1] - t0;
         u32 lo = j * CHUNK, hi = lo + CHUNK < nt ? lo + CHUNK : nt;
-        Fe<BF> acc = Fe<BF>::zero();
-        for (u32 k = lo + quad; k < hi; k += 16) acc = quad_add<BF>(acc, quad_load<BF>(partial + (size_t)(t0 + k) * 128));
-        for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
+        const Fe<BF> acc = quad_chunk_sum<BF>(partial + (size_t)t0 * 128, lo + quad, hi, 16);
         if (threadIdx.x < 4) quad_store<BF>(chunk_out + (size_t)it * 128, acc);
     }
 }
@@ -1236,30 +1232,15 @@ k_bucket_big(const u32* __restrict__ toff, const uint8_t* __restrict__ chunk_out
     // one 256-thread block = 64 quads per hot bucket: a bucket holding 2^20 entries has ~1000 chunk sums
     __shared__ u32 sh[4 * 32];
     u32 nbig = big[0];
-    const u32 quad = threadIdx.x >> 2, role = threadIdx.x & 3u, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const u32 quad = threadIdx.x >> 2;
     for (u32 bi = blockIdx.x; bi < nbig; bi += gridDim.x) {
-        u32 key = big[2 + bi], cbase = big[2 + cap + bi];
+        u32 key = big[hot_key(bi)], cbase = big[hot_cbase(cap, bi)];
         u32 nt = toff[key + 1] - toff[key];
         u32 nch = (nt + CHUNK - 1) / CHUNK;
-        Fe<BF> acc = Fe<BF>::zero();
-        for (u32 k = quad; k < nch; k += 64) acc = quad_add<BF>(acc, quad_load<BF>(chunk_out + (size_t)(cbase + k) * 128));
-        for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
+        Fe<BF> acc = quad_chunk_sum<BF>(chunk_out + (size_t)cbase * 128, quad, nch, 64);
         __syncthreads();                                    // sh is reused across iterations
-        if (lane < 4) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) sh[(wave * 4 + role) * 8 + k] = acc.v[k];
-        }
-        __syncthreads();
-        if (wave == 0) {
-            Fe<BF> o = Fe<BF>::zero();
-            if (quad < 4) {
-#pragma unroll
-                for (int k = 0; k < 8; k++) o.v[k] = sh[(quad * 4 + role) * 8 + k];
-            }
-            acc = o;
-            for (int d = 2; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
-            if (threadIdx.x < 4) quad_store<BF>(buckets + (size_t)key * 128, acc);
-        }
+        acc = quad_block_sum<BF>(acc, sh, 4);
+        if (threadIdx.x < 4) quad_store<BF>(buckets + (size_t)key * 128, acc);
     }
 }
 // ------------------------------------------------------------------------------------ 7 reduce
@@ -1292,29 +1273,6 @@ k_reduce_seg(const uint8_t* __restrict__ buckets, u32 nb, u32 m, size_t ngroups,
 }
 // sum of `count` XYZZ records per group, two launches: level 1 = blocks of 256 threads x SUM_PER_T
 // records (coalesced strided loads, shuffle tree, LDS across the 4 waves), level 2 = one block per group.
-template <class BF>
-__device__ __forceinline__ Xyzz<BF> block_sum(Xyzz<BF> acc, u32* sh) {
-    for (int d = 32; d >= 1; d >>= 1) { Xyzz<BF> o = shfl_down<BF>(acc, d); acc = add<BF>(acc, o); }
-    int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    u32* mine = sh + wave * 32;
-    if (lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) { mine[i] = acc.x.v[i]; mine[8 + i] = acc.y.v[i]; mine[16 + i] = acc.zz.v[i]; mine[24 + i] = acc.zzz.v[i]; }
-    }
-    __syncthreads();
-    int nw = blockDim.x >> 6;
-    if (threadIdx.x < 64) {              // wave 0 folds the (<= 4) wave results
-        Xyzz<BF> o = Xyzz<BF>::identity();
-        if (lane < nw) {
-            const u32* p = sh + lane * 32;
-#pragma unroll
-            for (int i = 0; i < 8; i++) { o.x.v[i] = p[i]; o.y.v[i] = p[8 + i]; o.zz.v[i] = p[16 + i]; o.zzz.v[i] = p[24 + i]; }
-        }
-        for (int d = 2; d >= 1; d >>= 1) { Xyzz<BF> q = shfl_down<BF>(o, d); o = add<BF>(o, q); }
-        acc = o;
-    }
-    return acc;                          // valid in thread 0
-}
 template <class BF>
 __global__ void __launch_bounds__(256)
 k_sum_level(const uint8_t* __restrict__ in, u32 count, u32 out_stride, uint8_t* __restrict__ out) {
@@ -1354,15 +1312,11 @@ k_marginals(const uint8_t* __restrict__ buckets, MargGeom g, uint8_t* __restrict
     KH_HIGH_PRIO();
     __shared__ u32 sh[4 * 32];
     const u32 v = blockIdx.x, j = blockIdx.y; const size_t q = blockIdx.z;
-    const u32 s = g.sh[j], f = g.wd[j];
-    if (v >= (1u << f)) return;
+    if (v >= (1u << g.wd[j])) return;
     const uint8_t* B = buckets + q * (size_t)g.nb * 128;
-    const u32 cnt = g.nb >> f, lowmask = (1u << s) - 1u;
+    const u32 cnt = g.nb >> g.wd[j];
     Xyzz<BF> acc = Xyzz<BF>::identity();
-    for (u32 e = threadIdx.x; e < cnt; e += blockDim.x) {
-        const u32 t = ((e >> s) << (s + f)) | (v << s) | (e & lowmask);
-        acc = add<BF>(acc, Xyzz<BF>::load(B + (size_t)t * 128));
-    }
+    for (u32 e = threadIdx.x; e < cnt; e += blockDim.x) acc = add<BF>(acc, Xyzz<BF>::load(B + (size_t)marginal_bucket(g, j, v, e) * 128));
     acc = block_sum<BF>(acc, sh);
     if (threadIdx.x == 0) acc.store(out + ((q * 3 + j) * 32 + v) * 128);
 }
@@ -1405,13 +1359,7 @@ k_bucket_sum_q(const u32* __restrict__ toff, size_t nkeys, const uint8_t* __rest
         if (spread_abort) {                                // no hot-bucket kernels behind this launch (MSM_SPREAD_SCALARS): tell the host, which re-runs the job with them
             if (live && role == 0) __hip_atomic_store(spread_abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         } else
-        if (live && role == 0) {
-            u32 nch = (nt + CHUNK - 1) / CHUNK;
-            u32 slot = atomicAdd(&big[0], 1u);
-            u32 cbase = atomicAdd(&big[1], nch);
-            big[2 + slot] = (u32)key; big[2 + cap + slot] = cbase;
-            for (u32 j = 0; j < nch; j++) { big[2 + 2 * cap + cbase + j] = (u32)key; big[2 + 3 * cap + cbase + j] = j; }
-        }
+        if (live && role == 0) list_hot_bucket(big, cap, (u32)key, nt);
         nt = 0;
     }
     // the trip count may differ between the quads of a wave: quad_add's shuffles stay inside the quad, its ballot is only a hint
@@ -1428,33 +1376,14 @@ k_marginals_q(const uint8_t* __restrict__ buckets, MargGeom g, uint8_t* __restri
     KH_HIGH_PRIO();
     __shared__ u32 sh[16 * 32];
     const u32 v = blockIdx.x, j = blockIdx.y; const size_t q = blockIdx.z;
-    const u32 s = g.sh[j], f = g.wd[j];
-    if (v >= (1u << f)) return;
+    if (v >= (1u << g.wd[j])) return;
     const uint8_t* B = buckets + q * (size_t)g.nb * 128;
-    const u32 cnt = g.nb >> f, lowmask = (1u << s) - 1u;
-    const u32 quad = threadIdx.x >> 2, nquads = blockDim.x >> 2, role = threadIdx.x & 3u;
+    const u32 cnt = g.nb >> g.wd[j];
+    const u32 quad = threadIdx.x >> 2, nquads = blockDim.x >> 2;
     Fe<BF> acc = Fe<BF>::zero();
-    for (u32 e = quad; e < cnt; e += nquads) {
-        const u32 t = ((e >> s) << (s + f)) | (v << s) | (e & lowmask);
-        acc = quad_add<BF>(acc, quad_load<BF>(B + (size_t)t * 128));
-    }
-    for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));       // 16 quads of the wave
-    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, nw = blockDim.x >> 6;
-    if (lane < 4) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) sh[(wave * 4 + role) * 8 + k] = acc.v[k];
-    }
-    __syncthreads();
-    if (wave == 0) {                                        // quad w of wave 0 takes wave w's sum
-        Fe<BF> o = Fe<BF>::zero();
-        if (quad < nw) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[(quad * 4 + role) * 8 + k];
-        }
-        acc = o;
-        for (int d = 8; d >= 1; d >>= 1) if ((u32)d < nw) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
-        if (threadIdx.x < 4) quad_store<BF>(out + ((q * 3 + j) * 32 + v) * 128, acc);
-    }
+    for (u32 e = quad; e < cnt; e += nquads) acc = quad_add<BF>(acc, quad_load<BF>(B + (size_t)marginal_bucket(g, j, v, e) * 128));
+    acc = quad_block_sum<BF>(quad_wave_sum<BF>(acc), sh, blockDim.x >> 6);
+    if (threadIdx.x < 4) quad_store<BF>(out + ((q * 3 + j) * 32 + v) * 128, acc);
 }
 // Hybrid of the two: the sequential part with ONE LANE per addition, the tree with quads.  These tails are bound by VALU ISSUE, not only by the
 // dependent chain (a cooperative addition is 5 product rounds x 4 lanes = 20 lane-products, the ordinary one 14 in one lane: per addition 78 against 55
@@ -1468,16 +1397,14 @@ k_marginals_h(const uint8_t* __restrict__ buckets, MargGeom g, uint8_t* __restri
     __shared__ u32 stage[4][32][64];                    // [wave][word of the XYZZ record][lane]
     __shared__ u32 sh[16 * 32];
     const u32 v = blockIdx.x, j = blockIdx.y; const size_t q = blockIdx.z;
-    const u32 s = g.sh[j], f = g.wd[j];
-    if (v >= (1u << f)) return;
+    if (v >= (1u << g.wd[j])) return;
     const uint8_t* B = buckets + q * (size_t)g.nb * 128;
-    const u32 cnt = g.nb >> f, lowmask = (1u << s) - 1u;
-    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, role = threadIdx.x & 3u, quad = lane >> 2, nw = blockDim.x >> 6;
+    const u32 cnt = g.nb >> g.wd[j];
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, role = threadIdx.x & 3u, quad = lane >> 2;
     Xyzz<BF> a = Xyzz<BF>::identity();
     bool have = false;
     for (u32 e = threadIdx.x; e < cnt; e += blockDim.x) {
-        const u32 t = ((e >> s) << (s + f)) | (v << s) | (e & lowmask);
-        const Xyzz<BF> b = Xyzz<BF>::load(B + (size_t)t * 128);
+        const Xyzz<BF> b = Xyzz<BF>::load(B + (size_t)marginal_bucket(g, j, v, e) * 128);
         a = have ? add<BF>(a, b) : b;
         have = true;
     }
@@ -1492,22 +1419,8 @@ k_marginals_h(const uint8_t* __restrict__ buckets, MargGeom g, uint8_t* __restri
     };
     Fe<BF> acc = parked(quad);
     for (u32 k = 1; k < 4; k++) acc = quad_add<BF>(acc, parked(quad + 16 * k));
-    for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));       // 16 quads of the wave
-    if (lane < 4) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) sh[(wave * 4 + role) * 8 + k] = acc.v[k];
-    }
-    __syncthreads();
-    if (wave == 0) {                                        // quad w of wave 0 takes wave w's sum
-        Fe<BF> o = Fe<BF>::zero();
-        if (quad < nw) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[(quad * 4 + role) * 8 + k];
-        }
-        acc = o;
-        for (int d = 8; d >= 1; d >>= 1) if ((u32)d < nw) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
-        if (threadIdx.x < 4) quad_store<BF>(out + ((q * 3 + j) * 32 + v) * 128, acc);
-    }
+    acc = quad_block_sum<BF>(quad_wave_sum<BF>(acc), sh, blockDim.x >> 6);
+    if (threadIdx.x < 4) quad_store<BF>(out + ((q * 3 + j) * 32 + v) * 128, acc);
 }
 // block (j, q), 128 threads = 32 quads, one per marginal: suffix scan + sum as in k_marginal_fin, exchanges through LDS
 template <class BF>
@@ -1611,9 +1524,7 @@ k_bucket_sum_wide(const u32* __restrict__ toff, const u32* __restrict__ xlist, c
         const u32 t0 = toff[key], nt = toff[key + 1] - t0, nch = (nt + CHUNK - 1) / CHUNK;
         for (u32 c = (gw + GW - cbase % GW) % GW; c < nch; c += GW) {      // (chunk slot cbase + c belongs to wave (cbase + c) mod GW: thirteen buckets of 256 chunks spread over all waves, not over the first 256 thirteen times)
             const u32 lo = c * CHUNK, hi = lo + CHUNK < nt ? lo + CHUNK : nt;
-            Fe<BF> acc = quad_identity<BF>();
-            for (u32 k = lo + quad; k < hi; k += 16) acc = quad_add<BF>(acc, quad_load<BF>(partial + (size_t)(t0 + k) * 128));
-            for (int d = 8; d >= 1; d >>= 1) acc = quad_add<BF>(acc, quad_shfl_down<BF>(acc, d));
+            const Fe<BF> acc = quad_chunk_sum<BF>(partial + (size_t)t0 * 128, lo + quad, hi, 16);
             if (lane < 4) quad_store<BF>(chunk_out + (size_t)(cbase + c) * 128, acc);
             __threadfence();                               // the chunk sum is visible device-wide before the arrival is counted
             u32 arrived = 0;
@@ -1621,9 +1532,7 @@ k_bucket_sum_wide(const u32* __restrict__ toff, const u32* __restrict__ xlist, c
             arrived = __shfl(arrived, 0, 64);
             if (arrived == nch) {                          // (wave-uniform) last one in: add up the chunk sums
                 __threadfence();
-                Fe<BF> o = quad_identity<BF>();
-                for (u32 k = quad; k < nch; k += 16) o = quad_add<BF>(o, quad_load<BF>(chunk_out + (size_t)(cbase + k) * 128));
-                for (int d = 8; d >= 1; d >>= 1) o = quad_add<BF>(o, quad_shfl_down<BF>(o, d));
+                const Fe<BF> o = quad_chunk_sum<BF>(chunk_out + (size_t)cbase * 128, quad, nch, 16);
                 if (lane < 4) quad_store<BF>(total + 128 * wave, o);
                 __builtin_amdgcn_wave_barrier();
                 if (lane == 0) {
@@ -1636,13 +1545,6 @@ k_bucket_sum_wide(const u32* __restrict__ toff, const u32* __restrict__ xlist, c
         }
         cbase += nch;
     }
-}
-// work item `out` of a group (the index of its output record): first bucket and bucket stride of its chunk
-__device__ __forceinline__ void wide_a1_item(const WideGeom& g, u32 out, u32& t0, u32& tstride) {
-    const u32 per = g.nb >> g.rlog;                        // items per plane
-    if (out < per) { t0 = out << g.rlog; tstride = 1u; return; }
-    const u32 cpm = (1u << g.hi) >> g.rlog, v = out - per, b = v / cpm, s = v - b * cpm;      // chunks per lo-digit marginal
-    t0 = ((s << g.rlog) << g.lo) + b; tstride = 1u << g.lo;
 }
 // a record whose zz limb 0 is all ones (no normalised limb is): "this lazy sum met a possible exceptional case" -- k_wide_a2 redoes it exactly, from the
 // records one level down
@@ -2204,13 +2106,6 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
     return KH_OK;
 }
 
-// the same on a caller's stream, with a caller's scratch buffer ((W - 1) x n x 128 bytes), no synchronisation: the opening's rebased tables (rebase.hip)
-int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, void* scratch) {
-    const int W = windows_of(c);
-    dim3 grid((unsigned)((n + 63) / 64));                  // small blocks: the chain of 255 doublings per point is pure latency, one wave per SIMD is the fastest
-    KH_CURVE_LAUNCH(curve, k_precompute<F>, grid, dim3(64), 0, s, (uint8_t*)tables, (const uint8_t*)nullptr, n, c, W, (uint8_t*)scratch);
-    return KH_OK;
-}
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c) {
     const int W = windows_of(c);
     DevBuf& scratch = C.scratch("precompute");

@@ -9,11 +9,9 @@ namespace kh {
 
 // builds the window tables 2^(c*w) * P_i in place: `tables` holds W x n x 64 B with table 0 = the basis
 int msm_precompute(Context& C, int curve, void* tables, const uint8_t* inf, size_t n, int c);
-int msm_precompute_on(hipStream_t s, int curve, void* tables, size_t n, int c, void* scratch);      // asynchronous, scratch = (W - 1) x n x 128 bytes
 // rebase.hip: the folded basis of the opening's late rounds, materialised from the c = 16 tables (see there)
 int rebase_points(hipStream_t s, int curve, const uint64_t* coef, size_t Q, const void* tables, size_t stride, size_t N, void* B, void* part, void* lists,
                   hipEvent_t after_plan = nullptr);
-const void* rebase_outputs(const void* part, size_t N);          // the N materialised points (XYZZ, 128 bytes each) inside `part`
 int rebase_tables(hipStream_t s, int curve, const void* part, size_t N, const void* extra_affine_host, size_t extra, int c, void* scratch, void* tables, uint32_t* fail,
                   const uint64_t* glv_beta = nullptr);      // glv_beta (Montgomery, base field): build W/2 levels and phi of them
 int msm_debug_glv_split(hipStream_t s, int field, const uint64_t* scalars_dev, size_t n, uint32_t* out_dev);
@@ -51,8 +49,6 @@ int ipa_round_step(hipStream_t s, int field, int has_fold, const uint64_t* a, co
                    const uint64_t u[4], const uint64_t uinv[4], uint64_t* a2, uint64_t* b2, uint64_t* coef2,
                    const uint64_t rand_l[4], const uint64_t rand_r[4], uint64_t* sc, uint64_t* partial, unsigned* counter, unsigned extra, unsigned uslot);
 // (extra: scalar entries behind the n points of each side = slots behind the points of the table set; uslot: which U slot is the opening's -- ipa.hip, k_ipa_step)
-int ipa_round_prepare(hipStream_t s, int field, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t n, size_t Nj,
-                      const uint64_t rand_l[4], const uint64_t rand_r[4], uint64_t* sc, uint64_t* partial);
 int ipa_round_fold(hipStream_t s, int field, const uint64_t* a, const uint64_t* b, const uint64_t* coef, size_t Nj, size_t ncoef,
                    const uint64_t u[4], const uint64_t uinv[4], uint64_t* a2, uint64_t* b2, uint64_t* coef2);
 int ipa_sg_split(hipStream_t s, int field, const uint64_t* coef, size_t n, int has_fold, const uint64_t u[4], uint64_t* out);
@@ -118,7 +114,6 @@ int srs_generate_device(Context& C, int curve, size_t start, size_t count, void*
 // lagrange.hip
 int lagrange_run(Context& C, int curve, const void* g_dev, size_t srs_size, unsigned log_n, unsigned chunk, void* out_xy_dev, uint8_t* out_inf_dev);
 khost::fe ntt_host_root(int field, unsigned logn, int inverse);   // omega_{2^logn} (or its inverse), Montgomery
-unsigned ntt_max_logr();
 int ntt_set_max_logr(unsigned v);            // 4..10, 0 = default (kh_ntt_set_max_logr)
 int ntt_run(Context& C, int field, uint64_t* data_dev, unsigned log2_n, int inverse, size_t batch);
 int lde_run(Context& C, int field, const uint64_t* coeffs_dev, unsigned log2_n, unsigned log2_blowup, uint64_t* out_dev, size_t batch);

@@ -66,6 +66,25 @@ struct WideTasks { u32 room, kmin, nkeys; KTab ktab; };
 struct MargGeom { u32 nb; u32 sh[3]; u32 wd[3]; };
 struct WideGeom { u32 nb, lo, hi, rlog, flog; };      // buckets, the two digit widths, log2 of the chunk (level one) and of the run of chunks (level two)
 
+// ------------------------------------------------------------------------------------ which bucket a lane reads: the kernels' index formulas, testable on the host
+#if defined(__HIPCC__)                                       // (__forceinline__ spelled out, as in lookup_hash.hpp: not every file that gets here includes a HIP header)
+#define KH_PLAN_FN __host__ __device__ inline __attribute__((always_inline))
+#else
+#define KH_PLAN_FN inline
+#endif
+// the bucket whose digit j (field g.sh[j], g.wd[j] bits wide) is v and whose other bits are e, e < g.nb >> g.wd[j]: bucket e with the digit spliced in
+KH_PLAN_FN u32 marginal_bucket(const MargGeom& g, u32 j, u32 v, u32 e) {
+    const u32 s = g.sh[j], f = g.wd[j];
+    return ((e >> s) << (s + f)) | (v << s) | (e & ((1u << s) - 1u));
+}
+// work item `out` of a group of k_wide_a1 (the index of its output record): first bucket and bucket stride of its chunk of 2^rlog buckets
+KH_PLAN_FN void wide_a1_item(const WideGeom& g, u32 out, u32& t0, u32& tstride) {
+    const u32 per = g.nb >> g.rlog;                        // items per plane
+    if (out < per) { t0 = out << g.rlog; tstride = 1u; return; }
+    const u32 cpm = (1u << g.hi) >> g.rlog, v = out - per, b = v / cpm, s = v - b * cpm;      // chunks per lo-digit marginal
+    t0 = ((s << g.rlog) << g.lo) + b; tstride = 1u << g.lo;
+}
+
 // ------------------------------------------------------------------------------------ the plan
 struct MsmShape {
     size_t n = 0, k = 0, offset = 0;       // scalars per MSM, MSMs, first basis point used

@@ -374,7 +374,7 @@ static std::atomic<unsigned>& max_logr_cell() {
     static std::atomic<unsigned> v((unsigned)std::min(10ll, std::max(4ll, env_int("KH_NTT_MAX_LOGR", NTT_MAX_LOGR))));
     return v;
 }
-unsigned ntt_max_logr() { return max_logr_cell().load(std::memory_order_relaxed); }
+static unsigned ntt_max_logr() { return max_logr_cell().load(std::memory_order_relaxed); }
 int ntt_set_max_logr(unsigned v) {
     if (v == 0) v = NTT_MAX_LOGR;
     if (v < 4 || v > 10) { set_error("kh_ntt_set_max_logr: %u is outside 4..10", v); return KH_E_INVALID; }

@@ -7,7 +7,7 @@
 // All four are element-wise or short reductions over 32-byte Montgomery elements; none is a bottleneck
 // (a few field products per element), the point is that their inputs and outputs never leave HBM.
 #include "common.hpp"
-#include "field.cuh"
+#include "block_sum.cuh"
 #include "msm.hpp"
 #include "host_ec.hpp"
 
@@ -71,20 +71,7 @@ k_eval_chunks(const ChunkDesc* __restrict__ tab, const u64* __restrict__ pw, siz
         for (int k = 0; e; k++, e >>= 1)
             if (e & 1) acc = mul<F>(acc, Fe<F>::load(xp + 4 * k));
     }
-#pragma unroll
-    for (int k = 0; k < 8; k++) sh[k * EVAL_T + t] = acc.v[k];
-    __syncthreads();
-    for (int s = EVAL_T / 2; s >= 1; s >>= 1) {
-        if ((int)t < s) {
-            Fe<F> o;
-#pragma unroll
-            for (int k = 0; k < 8; k++) o.v[k] = sh[k * EVAL_T + t + s];
-            acc = add<F>(acc, o);
-#pragma unroll
-            for (int k = 0; k < 8; k++) sh[k * EVAL_T + t] = acc.v[k];
-        }
-        __syncthreads();
-    }
+    acc = block_tree_sum<F, EVAL_T>(acc, sh);
     if (t == 0) acc.store(out + 4 * (d.out + p * nseg));
 }
 // f = q (x^n - 1) + r:  q[i] = sum_{k >= 1} f[i + k n],  r[i] = sum_{k >= 0} f[i + k n] (i < n).

@@ -261,7 +261,8 @@ int rebase_points(hipStream_t s, int curve, const uint64_t* coef, size_t Q, cons
     if (curve == KH_CURVE_VESTA) return rebase_t<FqParams, FpParams>(s, coef, Q, tables, stride, N, (uint8_t*)B, (uint8_t*)part, (u32*)lists, after_plan);
     return rebase_t<FpParams, FqParams>(s, coef, Q, tables, stride, N, (uint8_t*)B, (uint8_t*)part, (u32*)lists, after_plan);
 }
-const void* rebase_outputs(const void* part, size_t N) { return (const uint8_t*)part + (size_t)RB_CHUNKS * 2 * N * 128; }
+// the N materialised points (XYZZ, 128 bytes each) inside `part`
+static const void* rebase_outputs(const void* part, size_t N) { return (const uint8_t*)part + (size_t)RB_CHUNKS * 2 * N * 128; }
 // The window tables (width c) of the N materialised points and of the `extra` (<= 2) affine points `extra_affine_host` (HOST memory, 64 bytes each: H and U) behind
 // them: tables[w][i] = 2^(c w) P_i, affine, W x (N + extra) entries; scratch = W x (N + extra) x 128 bytes.  *fail != 0 afterwards: some point was the
 // identity (no affine form).

@@ -35,7 +35,51 @@ static MsmShape shape(size_t n, size_t k, int kind, int cus, int flags = 0) {
     return s;
 }
 
-static size_t n_refused = 0, n_fused = 0, n_part = 0, n_plain = 0, n_wide = 0, n_staged = 0;
+static size_t n_refused = 0, n_fused = 0, n_part = 0, n_plain = 0, n_wide = 0, n_staged = 0, n_marginal = 0, n_a1 = 0;
+
+// The kernels' index formulas (marginal_bucket, wide_a1_item), for every plan of the sweep that uses them.  The maps depend on the geometry alone and the
+// sweep has only a handful of those, so a geometry is walked once and every further plan with it is counted as checked.
+static bool seen_before(std::vector<std::vector<u32>>& seen, const std::vector<u32>& key) {
+    if (std::find(seen.begin(), seen.end(), key) != seen.end()) return true;
+    seen.push_back(key);
+    return false;
+}
+// k_marginals(_q, _h): block (v, j) reads the buckets marginal_bucket(g, j, v, e), e < nb >> wd[j] -- over all v every bucket exactly once, digit j of each = v
+static void check_marginal_buckets(const MargGeom& mg) {
+    static std::vector<std::vector<u32>> seen;
+    n_marginal++;
+    if (seen_before(seen, {mg.nb, mg.sh[0], mg.sh[1], mg.sh[2], mg.wd[0], mg.wd[1], mg.wd[2]})) return;
+    for (u32 j = 0; j < 3; j++) {
+        std::vector<uint8_t> hits(mg.nb, 0);
+        for (u32 v = 0; v < (1u << mg.wd[j]); v++) for (u32 e = 0; e < (mg.nb >> mg.wd[j]); e++) {
+            const u32 t = marginal_bucket(mg, j, v, e);
+            CHECK(t < mg.nb && hits[t] == 0 && ((t >> mg.sh[j]) & ((1u << mg.wd[j]) - 1u)) == v);
+            hits[t] = 1;
+        }
+        CHECK(std::count(hits.begin(), hits.end(), 1) == (long)mg.nb);
+    }
+}
+// k_wide_a1: the items out < wide_items / ngroups of a group are chunks of 2^rlog buckets, t0 + i tstride; the first half covers [0, nb) once (plane 0, the
+// hi-digit marginals), the second half once more (plane 1, the lo-digit marginals)
+static void check_wide_items(const WideGeom& wg, u32 items) {
+    static std::vector<std::vector<u32>> seen;
+    n_a1++;
+    CHECK(items == 2u * (wg.nb >> wg.rlog));
+    if (seen_before(seen, {wg.nb, wg.lo, wg.hi, wg.rlog, items})) return;
+    for (u32 plane = 0; plane < 2; plane++) {
+        std::vector<uint8_t> hits(wg.nb, 0);
+        for (u32 out = plane * (items / 2); out < (plane + 1) * (items / 2); out++) {
+            u32 t0 = 0, ts = 0;
+            wide_a1_item(wg, out, t0, ts);
+            for (u32 i = 0; i < (1u << wg.rlog); i++) {
+                const size_t t = (size_t)t0 + (size_t)i * ts;
+                CHECK(t < wg.nb && hits[t] == 0);
+                hits[t] = 1;
+            }
+        }
+        CHECK(std::count(hits.begin(), hits.end(), 1) == (long)wg.nb);
+    }
+}
 
 static void check(const MsmShape& sh) {
     g_shape = &sh;
@@ -98,6 +142,7 @@ static void check(const MsmShape& sh) {
         CHECK(wg.nb == P.nb && wg.lo + wg.hi == (u32)P.c - 1 && wg.rlog == wide_rlog); // bucket = (hi digit, lo digit)
         CHECK(wg.flog >= 1 && wg.rlog + wg.flog <= wg.hi);                             // a run of chunks stays inside one marginal of either plane
         CHECK(P.wide_items == 2u * (P.nb >> wg.rlog) * (u32)P.ngroups && grid_x((P.wide_items + 255) / 256));     // k_wide_a1: thread per chunk of both planes
+        check_wide_items(wg, P.wide_items / (u32)P.ngroups);
         CHECK(P.wide_runs == P.wide_items >> wg.flog && grid_x((P.wide_runs + 63) / 64));                         // k_wide_l2: thread per run
         CHECK(P.wide_runs / (u32)P.ngroups / 16u >= 1 && P.wide_runs % (16u * (u32)P.ngroups) == 0 && grid_yz(P.ngroups));   // k_wide_a2: wave per 16 run records
         CHECK(P.part2_lds <= 131072 && P.part2_lds >= ((size_t)3 << PART2_MAXLOW) * 4);     // the planning phase's three lists of 2^MAXLOW words; the attribute's 128 KB
@@ -135,6 +180,7 @@ static void check(const MsmShape& sh) {
         CHECK(P.planes == 3 && mg.nb == 1u << bits);
         CHECK(mg.wd[0] + mg.wd[1] + mg.wd[2] == bits && mg.sh[0] == 0 && mg.sh[1] == mg.wd[0] && mg.sh[2] == mg.wd[0] + mg.wd[1]);
         CHECK(mg.wd[0] <= 5 && mg.wd[1] <= 5 && mg.wd[2] <= 5);                        // k_marginals: 32 blocks in x, one per value of a field (wide: the fields split lo)
+        check_marginal_buckets(mg);
         CHECK(grid_yz(P.tail_groups) && P.tail_groups == (P.wide ? 2 * P.ngroups : P.ngroups));      // grid (32, 3, groups) and (3, groups)
         CHECK(P.nout == 3 * P.tail_groups);                                            // k_marginal_fin(_q): block (plane, group) writes one 128-byte record
     } else {
@@ -219,7 +265,8 @@ int main() {
         }
     }
     pinned();
-    if (!n_refused || !n_fused || !n_part || !n_plain || !n_wide || !n_staged) { fprintf(stderr, "a path was never taken\n"); return 1; }
-    printf("plans %zu refused %zu fused %zu partitioned %zu plain %zu wide %zu staged %zu\n", plans, n_refused, n_fused, n_part, n_plain, n_wide, n_staged);
+    if (!n_refused || !n_fused || !n_part || !n_plain || !n_wide || !n_staged || !n_marginal || !n_a1) { fprintf(stderr, "a path was never taken\n"); return 1; }
+    printf("plans %zu refused %zu fused %zu partitioned %zu plain %zu wide %zu staged %zu marginal_maps %zu wide_item_maps %zu\n", plans, n_refused, n_fused, n_part,
+           n_plain, n_wide, n_staged, n_marginal, n_a1);
     return 0;
 }

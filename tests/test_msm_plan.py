@@ -16,3 +16,5 @@ def test_plan_holds_the_kernels_conditions_over_the_sweep_and_the_pinned_shapes(
     assert run.returncode == 0, run.stderr[-2000:]
     counts = dict(zip(run.stdout.split()[::2], map(int, run.stdout.split()[1::2])))
     assert counts["plans"] >= 19 * 9 * 5 * 3 * 3 * 5 and all(counts[p] > 0 for p in ("refused", "fused", "partitioned", "plain", "wide", "staged")), run.stdout
+    # the kernels' index formulas (marginal_bucket, wide_a1_item): plans whose bucket maps were walked
+    assert counts["marginal_maps"] > 0 and counts["wide_item_maps"] > 0, run.stdout
