@@ -872,6 +872,21 @@ int kh_debug_glv_split(int scalar_field, const uint64_t *scalars, size_t n, uint
 int kh_debug_point_op(int curve, int op, const uint64_t *p_xy, const uint8_t *p_inf,
                       const uint64_t *q_xy, const uint8_t *q_inf,
                       uint64_t *out_xy, uint8_t *out_inf, size_t n);
+/* Test hooks of the MSM's last two stages over narrow windows (csrc/msm.hip, "6 bucket sums" and "7 reduce"), on the caller's records and through the
+ * launches an MSM makes.  A record is 128 bytes, x | y | zz | zzz in Montgomery limbs (the point (x / zz, y / zzz)); sixteen zero limbs are the identity.
+ * Results are affine with an infinity byte, as kh_debug_point_op gives them.  Neither call takes an MSM slot; each returns when its result has arrived.
+ *
+ * kh_debug_bucket_tail: sum_t (t + 1) B_t over each of `groups` arrays of nb buckets.  tail 0 / 1 / 2 = the marginal sums by k_marginals (one wave per
+ * marginal) / k_marginals_q / k_marginals_h, then k_marginal_fin (fin 0) or k_marginal_fin_q (fin 1): c_or_nb is the window width c, 7 .. 16, nb = 2^(c-1),
+ * a bucket index is three digit fields as the plan cuts them (bits = c - 1, f0 = (bits + 2) / 3, f1 = (bits - f0 + 1) / 2, f2 = the rest; m is unused), and
+ * out holds three points per group, plane j = sum_t (digit_j(t) + [j == 0]) B_t; the weighted sum is 2^(f0+f1) out[2] + 2^f0 out[1] + out[0].  tail 2 needs
+ * nb >> f0 >= 256, as the plan does.  tail 3 = k_reduce_seg, k_sum_level, k_sum_final: c_or_nb is nb itself, a power of two up to 2^15, m the segment
+ * length (a power of two up to 16 that divides nb, or nb), fin is unused, and out holds one point per group.
+ *
+ * kh_debug_bucket_sums: bucket i = the sum of the records partial[toff[i]] .. partial[toff[i + 1] - 1], i < nkeys (toff: nkeys + 1 ascending offsets from 0).
+ * kind 0 / 1 = k_bucket_sum, lists of more than 4 / 16 records through k_bucket_chunk and k_bucket_big; kind 2 = k_bucket_sum_q, more than 16. */
+int kh_debug_bucket_tail(int curve, int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, const uint64_t *buckets, uint64_t *out_xy, uint8_t *out_inf);
+int kh_debug_bucket_sums(int curve, int kind, size_t nkeys, const uint32_t *toff, const uint64_t *partial, uint64_t *out_xy, uint8_t *out_inf);
 
 /* ---- one process per GPU: the path's only collective, over RCCL / xGMI ----
  * A point-range-sharded MSM (BASELINE config 4) exchanges ONE partial point per rank: RCCL has no elliptic-curve reduction, so the "all-reduce" is an

@@ -105,5 +105,52 @@ int kh_debug_point_op(int curve, int op, const uint64_t* p_xy, const uint8_t* p_
     (void)hipFree(dp); (void)hipFree(dq); (void)hipFree(dout); if (dpi) (void)hipFree(dpi); if (dqi) (void)hipFree(dqi);
     return rc;
 }
+// n XYZZ records of the device -> affine points and infinity bytes, after everything queued on the context stream
+static int download_points(Context& C, int curve, const DevBuf& dev, size_t n, uint64_t* out_xy, uint8_t* out_inf) {
+    std::vector<khost::xyzz> res(n);
+    KH_HIP(hipMemcpyAsync(res.data(), dev.p, n * 128, hipMemcpyDeviceToHost, C.stream));
+    KH_HIP(hipStreamSynchronize(C.stream));
+    khost::Crv crv(curve);
+    for (size_t i = 0; i < n; i++) {
+        khost::aff a; const bool inf = crv.to_affine(res[i], a);
+        memcpy(out_xy + 8 * i, &a, 64); out_inf[i] = inf ? 1 : 0;
+    }
+    return KH_OK;
+}
+int kh_debug_bucket_tail(int curve, int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, const uint64_t* buckets, uint64_t* out_xy, uint8_t* out_inf) {
+    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "unknown curve id %d", curve);
+    KH_REQUIRE(buckets && out_xy && out_inf, "kh_debug_bucket_tail: null argument");
+    size_t nin = 0, nseg = 0, nout = 0;
+    int rc = debug_bucket_tail_sizes(tail, fin, c_or_nb, m, groups, &nin, &nseg, &nout); if (rc) return rc;
+    if ((rc = ensure_init())) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    DevBuf din, dseg, dout;
+    if ((rc = din.reserve(nin * 128)) || (rc = dseg.reserve(nseg * 128)) || (rc = dout.reserve(nout * 128))) return rc;
+    KH_HIP(hipMemcpyAsync(din.p, buckets, nin * 128, hipMemcpyHostToDevice, C.stream));
+    if ((rc = debug_bucket_tail(C, curve, tail, fin, c_or_nb, m, groups, din.as<uint8_t>(), dseg.as<uint8_t>(), dout.as<uint8_t>()))) return rc;
+    return download_points(C, curve, dout, nout, out_xy, out_inf);
+}
+int kh_debug_bucket_sums(int curve, int kind, size_t nkeys, const uint32_t* toff, const uint64_t* partial, uint64_t* out_xy, uint8_t* out_inf) {
+    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "unknown curve id %d", curve);
+    KH_REQUIRE(toff && out_xy && out_inf, "kh_debug_bucket_sums: null argument");
+    KH_REQUIRE(kind >= 0 && kind <= 2, "kh_debug_bucket_sums: kind %d unknown", kind);
+    KH_REQUIRE(nkeys >= 1 && nkeys <= ((size_t)1 << 24), "kh_debug_bucket_sums: %zu buckets (1 .. 2^24)", nkeys);
+    KH_REQUIRE(toff[0] == 0, "kh_debug_bucket_sums: toff[0] = %u, the first list starts at 0", toff[0]);
+    for (size_t i = 0; i < nkeys; i++) KH_REQUIRE(toff[i] <= toff[i + 1], "kh_debug_bucket_sums: toff[%zu] = %u > toff[%zu] = %u", i, toff[i], i + 1, toff[i + 1]);
+    const size_t ntasks = toff[nkeys];
+    KH_REQUIRE(ntasks < ((size_t)1 << 24) && (ntasks == 0 || partial), "kh_debug_bucket_sums: %zu partials (below 2^24, and not NULL)", ntasks);
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    const size_t cap = debug_bucket_sums_cap(nkeys, ntasks);
+    DevBuf dtoff, dpart, dbuckets, dbig, dchunks;
+    if ((rc = dtoff.reserve((nkeys + 1) * 4)) || (rc = dpart.reserve(std::max<size_t>(ntasks, 1) * 128)) || (rc = dbuckets.reserve(nkeys * 128)) ||
+        (rc = dbig.reserve((2 + 4 * cap) * 4)) || (rc = dchunks.reserve(cap * 128))) return rc;
+    KH_HIP(hipMemcpyAsync(dtoff.p, toff, (nkeys + 1) * 4, hipMemcpyHostToDevice, C.stream));
+    if (ntasks) KH_HIP(hipMemcpyAsync(dpart.p, partial, ntasks * 128, hipMemcpyHostToDevice, C.stream));
+    if ((rc = debug_bucket_sums(C, curve, kind, nkeys, dtoff.as<uint32_t>(), dpart.as<uint8_t>(), dbuckets.as<uint8_t>(), dbig.as<uint32_t>(), cap, dchunks.as<uint8_t>()))) return rc;
+    return download_points(C, curve, dbuckets, nkeys, out_xy, out_inf);
+}
 
 }  // extern "C"

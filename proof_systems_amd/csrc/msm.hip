@@ -1799,6 +1799,56 @@ static void launch_timed(PhaseTimer& t, const char* name, K kern, dim3 grid, dim
         hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
 }
 
+// Stages 6 and 7 of a job over narrow windows, each as one function: msm_launch calls them with the plan's values and the slot's workspaces, the test
+// hooks at the end of this file (debug_bucket_sums, debug_bucket_tail) with a caller's buckets -- the grids and block sizes are written here and nowhere else.
+//
+// 6 bucket sums: bucket `key` = the sum of the partials toff[key] .. toff[key + 1].  quad: k_bucket_sum_q (a quad per bucket), else k_bucket_sum (a thread per
+// bucket); buckets of more than small_nt partials go through the lists in `big` (2 + 4 bigcap words, [0] and [1] zeroed by the caller; `chunks`: bigcap
+// records) to k_bucket_chunk and k_bucket_big.  spread_abort != NULL (MSM_SPREAD_SCALARS, quad only): such a bucket is reported there instead, and the two
+// hot-bucket kernels are not launched.
+template <class BF>
+static void launch_bucket_sums(hipStream_t s, bool quad, u32 small_nt, u32* spread_abort, const u32* toff, size_t nkeys, const uint8_t* partial, uint8_t* buckets,
+                               u32* big, size_t bigcap, uint8_t* chunks, const u32* abort_dev) {
+    if (quad)
+        hipLaunchKernelGGL((k_bucket_sum_q<BF>), dim3((unsigned)((4 * nkeys + 255) / 256)), dim3(256), 0, s, toff, nkeys, partial, buckets, big, bigcap, small_nt, abort_dev, spread_abort);
+    else
+        hipLaunchKernelGGL((k_bucket_sum<BF>), dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s, toff, nkeys, partial, buckets, big, bigcap, small_nt, abort_dev);
+    if (spread_abort) return;     // (the quad kernel took every bucket: nothing was listed)
+    hipLaunchKernelGGL((k_bucket_chunk<BF>), dim3(2048), dim3(64), 0, s, toff, partial, big, bigcap, chunks, abort_dev);
+    hipLaunchKernelGGL((k_bucket_big<BF>), dim3(1024), dim3(256), 0, s, toff, chunks, buckets, big, bigcap, abort_dev);
+}
+// 7 reduce: sum_t (t + 1) B_t of every group.  The marginal kinds leave the three plane sums of a group (3 ngroups records in `out`; the host folds them
+// with f0 + f1 doublings), TAIL_SEGMENTS one record per group.  seg: 96 ngroups records for the marginals, ngroups (nseg + nblk1) for the segments.
+enum TailKind { TAIL_MARGINALS = 0, TAIL_MARGINALS_Q = 1, TAIL_MARGINALS_H = 2, TAIL_SEGMENTS = 3 };      // (the values are the `tail` of kh_debug_bucket_tail)
+struct NarrowTail {
+    TailKind kind = TAIL_SEGMENTS;
+    bool fin_quad = false;                 // marginals: k_marginal_fin_q, else k_marginal_fin
+    MargGeom mg{};                         // marginals
+    u32 nb = 0, m = 0, nseg = 0, nblk1 = 0;      // segments
+    size_t ngroups = 0;
+};
+template <class BF>
+static void launch_narrow_tail(hipStream_t s, const NarrowTail& T, const uint8_t* buckets, uint8_t* seg, uint8_t* out, u32* done_ws, u32* done_flag) {
+    const unsigned ngroups = (unsigned)T.ngroups;
+    if (T.kind == TAIL_SEGMENTS) {
+        hipLaunchKernelGGL((k_reduce_seg<BF>), dim3((unsigned)((T.ngroups * T.nseg + 127) / 128)), dim3(128), 0, s, buckets, T.nb, T.m, T.ngroups, seg);
+        uint8_t* lvl1 = seg + T.ngroups * (size_t)T.nseg * 128;
+        hipLaunchKernelGGL((k_sum_level<BF>), dim3(T.nblk1, ngroups), dim3(256), 0, s, seg, T.nseg, T.nblk1, lvl1);
+        hipLaunchKernelGGL((k_sum_final<BF>), dim3(ngroups), dim3(T.nblk1 > 64 ? 256 : 64), 0, s, lvl1, T.nblk1, out);
+        return;
+    }
+    if (T.kind == TAIL_MARGINALS_H)
+        hipLaunchKernelGGL((k_marginals_h<BF>), dim3(32, 3, ngroups), dim3(256), 0, s, buckets, T.mg, seg);
+    else if (T.kind == TAIL_MARGINALS_Q)
+        hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, ngroups), dim3(256), 0, s, buckets, T.mg, seg);
+    else
+        hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, ngroups), dim3(64), 0, s, buckets, T.mg, seg);
+    if (T.fin_quad)
+        hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, ngroups), dim3(128), 0, s, seg, T.mg, out, done_ws, done_flag);
+    else
+        hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, ngroups), dim3(64), 0, s, seg, T.mg, out);
+}
+
 // the launches of plan P (of shape sh) on slot C, whose workspaces msm_reserve has sized
 template <class CFG>
 static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev, int mont, const MsmShape& sh, const MsmPlan& P, bool flag_on) {
@@ -1905,20 +1955,10 @@ static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev,
     if (wide)                                              // (the split buckets' sums, hot ones included: one launch; 2^22: 16 K split buckets of two partials)
         hipLaunchKernelGGL((k_bucket_sum_wide<BF>), dim3(256), dim3(256), 0, s, C.ws_toff.as<u32>(), C.ws_xlist.as<u32>(), slist,
                            C.ws_partial.as<uint8_t>(), b29, P.part_low, WIDE_HOT_NT, C.ws_biglist.as<u32>(), (u32)P.bigcap, C.ws_chunks.as<uint8_t>());
-    else if (P.quad_sum)
-        hipLaunchKernelGGL((k_bucket_sum_q<BF>), dim3((unsigned)((4 * nkeys + 255) / 256)), dim3(256), 0, s,
-                           C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
-                           P.bigcap, P.spread ? SPREAD_MAX_NT : 16u, abort_dev, P.spread ? (u32*)C.spread_abort : nullptr);
     else
-    hipLaunchKernelGGL((k_bucket_sum<BF>), dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, s,
-                       C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(),
-                       P.bigcap, nkeys <= 16384 ? 4u : 16u, abort_dev);
-    if (!wide && !P.spread) {     // (the quad kernel took every bucket: nothing was listed; the wide path's kernel sums its hot buckets itself)
-    hipLaunchKernelGGL((k_bucket_chunk<BF>), dim3(2048), dim3(64), 0, s,
-                       C.ws_toff.as<u32>(), C.ws_partial.as<uint8_t>(), C.ws_biglist.as<u32>(), P.bigcap, C.ws_chunks.as<uint8_t>(), abort_dev);
-    hipLaunchKernelGGL((k_bucket_big<BF>), dim3(1024), dim3(256), 0, s,
-                       C.ws_toff.as<u32>(), C.ws_chunks.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(), P.bigcap, abort_dev);
-    }
+        launch_bucket_sums<BF>(s, P.quad_sum, P.quad_sum ? (P.spread ? SPREAD_MAX_NT : 16u) : (nkeys <= 16384 ? 4u : 16u), P.spread ? (u32*)C.spread_abort : nullptr,
+                               C.ws_toff.as<u32>(), nkeys, C.ws_partial.as<uint8_t>(), C.ws_buckets.as<uint8_t>(), C.ws_biglist.as<u32>(), P.bigcap,
+                               C.ws_chunks.as<uint8_t>(), abort_dev);
     C.timer.mark("bucket_sum", s);
     // 7 reduce
     u32* const done_ws = flag_on ? C.ws_done.as<u32>() : nullptr; u32* const done_flag = flag_on ? (u32*)C.done_flag : nullptr;
@@ -1934,26 +1974,15 @@ static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev,
                            C.ws_a2.as<uint8_t>());
         hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)P.tail_groups), dim3(256), 0, s, C.ws_a2.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
         hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)P.tail_groups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
-    } else if (P.planes) {
-        // few groups: 256 threads per marginal (4 sequential additions + the tree: shortest chain); batches: one wave per marginal (16 + 6 additions
-        // deep, but 2.2x less issue work -- batches are throughput-bound).  Either way, where every lane has its own buckets, k_marginals_h: one lane
-        // per addition, the 6-level lane tree replaced by the quads' 4 + 4 steps
-        if ((mg.nb >> mg.wd[0]) >= 256)
-            hipLaunchKernelGGL((k_marginals_h<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        else if (P.few_groups)
-            hipLaunchKernelGGL((k_marginals_q<BF>), dim3(32, 3, (unsigned)ngroups), dim3(256), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        else
-            hipLaunchKernelGGL((k_marginals<BF>), dim3(32, 3, (unsigned)ngroups), dim3(64), 0, s, C.ws_buckets.as<uint8_t>(), mg, C.ws_seg.as<uint8_t>());
-        if (P.direct_out)                                  // straight into the pinned host staging (the lane-cooperative tail: msm_plan.hpp)
-            hipLaunchKernelGGL((k_marginal_fin_q<BF>), dim3(3, (unsigned)ngroups), dim3(128), 0, s, C.ws_seg.as<uint8_t>(), mg, (uint8_t*)C.pinned, done_ws, done_flag);
-        else
-            hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, (unsigned)ngroups), dim3(64), 0, s, C.ws_seg.as<uint8_t>(), mg, C.ws_out.as<uint8_t>());
     } else {
-        hipLaunchKernelGGL((k_reduce_seg<BF>), dim3((unsigned)((ngroups * P.nseg + 127) / 128)), dim3(128), 0, s,
-                           C.ws_buckets.as<uint8_t>(), P.nb, P.m, ngroups, C.ws_seg.as<uint8_t>());
-        uint8_t* lvl1 = C.ws_seg.as<uint8_t>() + ngroups * (size_t)P.nseg * 128;
-        hipLaunchKernelGGL((k_sum_level<BF>), dim3(P.nblk1, (unsigned)ngroups), dim3(256), 0, s, C.ws_seg.as<uint8_t>(), P.nseg, P.nblk1, lvl1);
-        hipLaunchKernelGGL((k_sum_final<BF>), dim3((unsigned)ngroups), dim3(P.nblk1 > 64 ? 256 : 64), 0, s, lvl1, P.nblk1, C.ws_out.as<uint8_t>());
+        // marginals -- few groups: 256 threads per marginal (4 sequential additions + the tree: shortest chain); batches: one wave per marginal (16 + 6
+        // additions deep, but 2.2x less issue work -- batches are throughput-bound).  Either way, where every lane has its own buckets, k_marginals_h: one
+        // lane per addition, the 6-level lane tree replaced by the quads' 4 + 4 steps.  k_marginal_fin_q writes straight into the pinned host staging (the
+        // lane-cooperative tail: msm_plan.hpp)
+        NarrowTail T;
+        T.kind = !P.planes ? TAIL_SEGMENTS : ((mg.nb >> mg.wd[0]) >= 256 ? TAIL_MARGINALS_H : (P.few_groups ? TAIL_MARGINALS_Q : TAIL_MARGINALS));
+        T.fin_quad = P.direct_out; T.mg = mg; T.nb = P.nb; T.m = P.m; T.nseg = P.nseg; T.nblk1 = P.nblk1; T.ngroups = ngroups;
+        launch_narrow_tail<BF>(s, T, C.ws_buckets.as<uint8_t>(), C.ws_seg.as<uint8_t>(), P.direct_out ? (uint8_t*)C.pinned : C.ws_out.as<uint8_t>(), done_ws, done_flag);
     }
     C.timer.mark("reduce", s);
     KH_HIP(hipGetLastError());
@@ -2211,6 +2240,51 @@ int debug_point_op(Context& C, int curve, int op, const u64* p, const uint8_t* p
     }
     dim3 grid((unsigned)((n + 255) / 256));
     KH_CURVE_LAUNCH(curve, k_debug_point<F>, grid, dim3(256), 0, C.stream, op, p, pinf, q, qinf, out, n);
+    return KH_OK;
+}
+// kh_debug_bucket_tail: one reduction tail over a caller's buckets, through launch_narrow_tail as msm_launch calls it.  Only shapes a plan produces.
+static int debug_tail_of(int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, NarrowTail& T) {
+    KH_REQUIRE(tail >= TAIL_MARGINALS && tail <= TAIL_SEGMENTS && (fin == 0 || fin == 1), "kh_debug_bucket_tail: tail %d / fin %d unknown", tail, fin);
+    KH_REQUIRE(groups >= 1 && groups <= 4096, "kh_debug_bucket_tail: %zu groups (1 .. 4096)", groups);
+    T = NarrowTail{};
+    T.kind = (TailKind)tail; T.ngroups = groups;
+    if (tail == TAIL_SEGMENTS) {
+        const u32 nb = c_or_nb;
+        KH_REQUIRE(nb >= 1 && nb <= (1u << 15) && (nb & (nb - 1)) == 0, "kh_debug_bucket_tail: nb = %u is no power of two up to 2^15", nb);
+        KH_REQUIRE(m >= 1 && (m & (m - 1)) == 0 && (m <= 16 || m == nb) && nb % m == 0, "kh_debug_bucket_tail: segments of m = %u do not divide nb = %u as a plan's do", m, nb);
+        T.nb = nb; T.m = m; T.nseg = nb / m; T.nblk1 = (T.nseg + SUM_BLK - 1) / SUM_BLK;
+        return KH_OK;
+    }
+    KH_REQUIRE(c_or_nb >= 7 && c_or_nb <= 16, "kh_debug_bucket_tail: c = %u has no marginal tail (7 .. 16)", c_or_nb);
+    T.mg = marginal_geometry(c_or_nb - 1); T.fin_quad = fin != 0; T.nb = T.mg.nb;
+    KH_REQUIRE(tail != TAIL_MARGINALS_H || (T.mg.nb >> T.mg.wd[0]) >= 256, "kh_debug_bucket_tail: no plan sends c = %u to k_marginals_h (fewer than 256 buckets per marginal)", c_or_nb);
+    return KH_OK;
+}
+int debug_bucket_tail_sizes(int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, size_t* in_records, size_t* seg_records, size_t* out_records) {
+    NarrowTail T;
+    int rc = debug_tail_of(tail, fin, c_or_nb, m, groups, T); if (rc) return rc;
+    *in_records = groups * T.nb;
+    *seg_records = T.kind == TAIL_SEGMENTS ? groups * ((size_t)T.nseg + T.nblk1) : groups * 96;
+    *out_records = T.kind == TAIL_SEGMENTS ? groups : 3 * groups;
+    return KH_OK;
+}
+int debug_bucket_tail(Context& C, int curve, int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, const uint8_t* buckets, uint8_t* seg, uint8_t* out) {
+    NarrowTail T;
+    int rc = debug_tail_of(tail, fin, c_or_nb, m, groups, T); if (rc) return rc;
+    if (curve == KH_CURVE_VESTA) launch_narrow_tail<VestaCfg::Base>(C.stream, T, buckets, seg, out, nullptr, nullptr);
+    else launch_narrow_tail<PallasCfg::Base>(C.stream, T, buckets, seg, out, nullptr, nullptr);
+    KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+// kh_debug_bucket_sums: the bucket-sum stage over a caller's task lists, through launch_bucket_sums as msm_launch calls it (no fused sort in front: abort_dev
+// NULL; no MSM_SPREAD_SCALARS).  kind 0 / 1: k_bucket_sum with SMALL_NT 4 / 16 (up to / beyond 16384 buckets in a job), 2: k_bucket_sum_q with 16.
+size_t debug_bucket_sums_cap(size_t nkeys, size_t ntasks) { return hot_list_cap(nkeys, ntasks); }
+int debug_bucket_sums(Context& C, int curve, int kind, size_t nkeys, const u32* toff, const uint8_t* partial, uint8_t* buckets, u32* big, size_t bigcap, uint8_t* chunks) {
+    KH_REQUIRE(kind >= 0 && kind <= 2, "kh_debug_bucket_sums: kind %d unknown", kind);
+    KH_HIP(hipMemsetAsync(big, 0, (2 + 4 * bigcap) * sizeof(u32), C.stream));
+    if (curve == KH_CURVE_VESTA) launch_bucket_sums<VestaCfg::Base>(C.stream, kind == 2, kind == 0 ? 4u : 16u, nullptr, toff, nkeys, partial, buckets, big, bigcap, chunks, nullptr);
+    else launch_bucket_sums<PallasCfg::Base>(C.stream, kind == 2, kind == 0 ? 4u : 16u, nullptr, toff, nkeys, partial, buckets, big, bigcap, chunks, nullptr);
+    KH_HIP(hipGetLastError());
     return KH_OK;
 }
 

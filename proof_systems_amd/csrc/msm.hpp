@@ -37,6 +37,13 @@ int msm_finish(Context& C, MsmSlot& S, uint64_t* out_xy, uint8_t* out_inf, bool 
 int debug_field_op(Context& C, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int debug_field29_op(Context& C, int field, int op, int spread, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out, size_t n);
 int debug_point_op(Context& C, int curve, int op, const uint64_t* p, const uint8_t* pinf, const uint64_t* q, const uint8_t* qinf, uint8_t* out, size_t n);
+// kh_debug_bucket_tail: the records (128 B) of its input, scratch and output, or why no plan has such a tail; then the launches, on C.stream, nothing waits
+int debug_bucket_tail_sizes(int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, size_t* in_records, size_t* seg_records, size_t* out_records);
+int debug_bucket_tail(Context& C, int curve, int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, const uint8_t* buckets, uint8_t* seg, uint8_t* out);
+// kh_debug_bucket_sums: room of the hot-bucket lists (big: 2 + 4 cap words, zeroed by the call; chunks: cap records); then the launches, as above
+size_t debug_bucket_sums_cap(size_t nkeys, size_t ntasks);
+int debug_bucket_sums(Context& C, int curve, int kind, size_t nkeys, const uint32_t* toff, const uint8_t* partial, uint8_t* buckets, uint32_t* big, size_t bigcap,
+                      uint8_t* chunks);
 
 // ntt.hip
 int ntt_build_twiddles(Context& C, int field, unsigned logn, int inverse, uint64_t* tab);

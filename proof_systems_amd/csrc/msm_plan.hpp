@@ -77,6 +77,15 @@ KH_PLAN_FN u32 marginal_bucket(const MargGeom& g, u32 j, u32 v, u32 e) {
     const u32 s = g.sh[j], f = g.wd[j];
     return ((e >> s) << (s + f)) | (v << s) | (e & ((1u << s) - 1u));
 }
+// the three digit fields of a `bits`-bit bucket index, low to high, each at most 5 bits wide for bits <= 15 (k_marginals*: 32 blocks in x)
+inline MargGeom marginal_geometry(u32 bits) {
+    const u32 f0 = (bits + 2) / 3, f1 = (bits - f0 + 1) / 2, f2 = bits - f0 - f1;
+    MargGeom mg;
+    mg.nb = 1u << bits; mg.sh[0] = 0; mg.wd[0] = f0; mg.sh[1] = f0; mg.wd[1] = f1; mg.sh[2] = f0 + f1; mg.wd[2] = f2;
+    return mg;
+}
+// room of the hot-bucket lists (msm.hip, list_hot_bucket) for nkeys buckets of at most max_tasks partials: big buckets <= nkeys; chunk items <= tasks / CHUNK + nkeys
+inline size_t hot_list_cap(size_t nkeys, size_t max_tasks) { return nkeys + max_tasks / CHUNK + 2; }
 // work item `out` of a group of k_wide_a1 (the index of its output record): first bucket and bucket stride of its chunk of 2^rlog buckets
 KH_PLAN_FN void wide_a1_item(const WideGeom& g, u32 out, u32& t0, u32& tstride) {
     const u32 per = g.nb >> g.rlog;                        // items per plane
@@ -214,7 +223,7 @@ inline int msm_plan(const MsmShape& sh, MsmPlan& P, const char** why) {
         *why = "MSM too large for 31-bit entry indices";
         return 1;
     }
-    P.bigcap = nkeys + max_tasks / CHUNK + 2;               // big buckets <= nkeys; chunk items <= tasks/512 + nkeys
+    P.bigcap = hot_list_cap(nkeys, max_tasks);
     P.slist_off = 2 + 2 * max_tasks;                        // (key, chunk) pairs of the extra chunks, then the split buckets' keys
     P.acc_blocks = wide ? (u32)(nkeys / 256) : (u32)((max_tasks + 255) / 256);      // wide: thread per bucket; else thread per task
     // dynamic LDS that leaves room for exactly wide_acc_blocks blocks on a CU, from the device's own LDS size (160 KB on gfx950), never more than one block
@@ -244,11 +253,7 @@ inline int msm_plan(const MsmShape& sh, MsmPlan& P, const char** why) {
     P.nblk1 = (P.nseg + SUM_BLK - 1) / SUM_BLK;
     // one to four MSMs over the tables: digit marginals instead (k_marginals), three fields of <= 5 bits
     P.planes = wide ? 3u : ((precomp && ngroups <= 4096 && c >= 7 && c <= 16) ? 3u : 0u);
-    if (P.planes) {                                        // (wide: the tail runs over the two marginal groups of 2^lo slots each, k_wide_a2)
-        MargGeom& mg = P.mg;
-        const u32 bits = wide ? P.wg.lo : (u32)c - 1, f0 = (bits + 2) / 3, f1 = (bits - f0 + 1) / 2, f2 = bits - f0 - f1;
-        mg.nb = wide ? 1u << P.wg.lo : nb; mg.sh[0] = 0; mg.wd[0] = f0; mg.sh[1] = f0; mg.wd[1] = f1; mg.sh[2] = f0 + f1; mg.wd[2] = f2;
-    }
+    if (P.planes) P.mg = marginal_geometry(wide ? P.wg.lo : (u32)c - 1);      // (wide: the tail runs over the two marginal groups of 2^lo slots each, k_wide_a2)
     P.tail_groups = wide ? 2 * ngroups : ngroups;
     P.nout = P.planes ? P.tail_groups * P.planes : ngroups;
     // small jobs over the tables: the whole sort in one launch (k_sort_fused)

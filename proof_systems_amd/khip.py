@@ -1795,3 +1795,32 @@ def debug_point_op(curve: int, op: int, p, q, p_inf=None, q_inf=None):
     oinf = np.zeros(n, dtype=np.uint8)
     _check(_lib.kh_debug_point_op(curve, op, _p64(p), _p8(pi), _p64(q), _p8(qi), _p64(out), _p8(oinf), n))
     return out, oinf
+
+
+def debug_bucket_tail(curve: int, tail: int, fin: int, c_or_nb: int, m: int, groups: int, buckets):
+    """kh_debug_bucket_tail: one reduction tail of the MSM over `groups` arrays of XYZZ records, (groups * nb, 16) uint64.  tail 0 / 1 / 2: k_marginals /
+    _q / _h and k_marginal_fin (fin 0) or _fin_q (fin 1) at window width c_or_nb -> (groups, 3, 8) affine plane sums and (groups, 3) infinity bytes;
+    tail 3: the segment kernels over nb = c_or_nb buckets in segments of m -> (groups, 8) and (groups,)."""
+    b = _c64(buckets, (-1, 16))
+    shape = (groups,) if tail == 3 else (groups, 3)
+    out = np.zeros(shape + (8,), dtype=np.uint64)
+    oinf = np.zeros(shape, dtype=np.uint8)
+    nb = c_or_nb if tail == 3 else 1 << max(c_or_nb - 1, 0)
+    if b.shape[0] != groups * nb:
+        raise ValueError(f"{b.shape[0]} records for {groups} groups of {nb} buckets")
+    _check(_lib.kh_debug_bucket_tail(curve, tail, fin, c_or_nb, m, groups, _p64(b), _p64(out), _p8(oinf)))
+    return out, oinf
+
+
+def debug_bucket_sums(curve: int, kind: int, toff, partial):
+    """kh_debug_bucket_sums: bucket i = the sum of the XYZZ records partial[toff[i]:toff[i + 1]] ((n, 16) uint64) by k_bucket_sum with SMALL_NT 4 (kind 0) or 16
+    (kind 1) or by k_bucket_sum_q (kind 2), each with k_bucket_chunk and k_bucket_big behind it -> (nkeys, 8) affine and (nkeys,) infinity bytes."""
+    t = np.ascontiguousarray(toff, dtype=np.uint32)
+    nkeys = t.shape[0] - 1
+    p = _c64(partial, (-1, 16))
+    if nkeys < 1 or p.shape[0] != int(t[-1]):
+        raise ValueError(f"{p.shape[0]} records for offsets that end at {int(t[-1]) if t.size else None}")
+    out = np.zeros((nkeys, 8), dtype=np.uint64)
+    oinf = np.zeros(nkeys, dtype=np.uint8)
+    _check(_lib.kh_debug_bucket_sums(curve, kind, nkeys, t.ctypes.data_as(C.POINTER(C.c_uint32)), _p64(p), _p64(out), _p8(oinf)))
+    return out, oinf
