@@ -887,6 +887,54 @@ int kh_debug_point_op(int curve, int op, const uint64_t *p_xy, const uint8_t *p_
  * kind 0 / 1 = k_bucket_sum, lists of more than 4 / 16 records through k_bucket_chunk and k_bucket_big; kind 2 = k_bucket_sum_q, more than 16. */
 int kh_debug_bucket_tail(int curve, int tail, int fin, unsigned c_or_nb, unsigned m, size_t groups, const uint64_t *buckets, uint64_t *out_xy, uint8_t *out_inf);
 int kh_debug_bucket_sums(int curve, int kind, size_t nkeys, const uint32_t *toff, const uint64_t *partial, uint64_t *out_xy, uint8_t *out_inf);
+/* Test hook of the MSM's front half (csrc/msm.hip, steps 1 - 4 and "tasks"): the digits, the sort and the task plan of one job, through the function an MSM
+ * launches them with (msm_launch_sort), and nothing behind it: no accumulation, no tail.  The caller gives scalars and the facts of a basis; every geometry
+ * value a kernel gets comes from the library's plan for that shape and every workspace from its reservation, as for a real job.  No SRS handle and no tables:
+ * the sort does index arithmetic on point numbers only.
+ *
+ * args (host memory): k n scalars of the curve's scalar field, Montgomery (mont != 0) or canonical with at most one excess p.  inf (nullable): infinity bytes
+ * indexed as a basis' are, inf[offset + j batch_stride + i] for scalar i of MSM j, inf_len >= offset + (k - 1) batch_stride + n of them.  offset, stride (0 =
+ * offset + n; else at least that), batch_stride: first point used, points between window tables, points between the bases of a batch.  precomp_c: 0 = a plain
+ * basis, 7 .. 16 = window tables of that width; glv: they hold phi(2^(c w) P) too; wide: a second table set of 20-bit windows that every size takes.
+ * fused_off: no one-launch sort.  stage_entries, stage_maxpass: the values of kh_msm_set_sort_staging.  num_cus: 0 = the device's own.
+ * Refused with KH_E_INVALID before anything is reserved: an unknown curve, n = 0, k outside 1 .. 8, precomp_c outside {0, 7 .. 16}, glv without precomp_c, wide
+ * with glv, num_cus above 1024, an infinity mask that is too short, a stride below offset + n, n W k above 2^26, and whatever the plan itself refuses.
+ *
+ * echo: what the plan decided.  sort: 0 = k_hist .. k_scatter, 1 = k_sort_fused, 2 = the partitioned sort (wide != 0: its wide form); ranked: 0 = the tasks
+ * keep the key order, 1 = all keys are ranked by task length (order / rnt / roff), 2 = the wide path's per-partition ranking, interleaved in `order`.
+ * out = NULL: the echo alone, nothing is launched; the caller sizes the outputs from it --
+ *   digits [k][W][n] (int32 in two's complement), off and toff nkeys + 1, entries max_entries, order nkeys, rnt and roff nkeys + 1 (ranked 1; order also for
+ *   ranked 2), counts 8 words; wide only: ptot 256 k, xpairs 2 max_tasks, slist, big_keys and big_arrivals nkeys each, b29_zero nkeys bytes.
+ * counts: [0] handed[0], [1] [2] the hot-bucket list's two counters, [3] the extra chunks of split buckets, [4] the split buckets, [5] off[nkeys] = entries,
+ * [6] toff[nkeys] = tasks.  xpairs: (key, chunk) per extra chunk; b29_zero[g nb + t] = 1 when the lazy bucket record of true bucket t of MSM g is all zero
+ * (the records are set to 0x01 bytes before the launch).  Keys are the sort's own: permuted per MSM on the wide path, (t & 255) << part_low | t >> 8.
+ * Before the launch every array the sort hands on -- digits, off, toff, the task counts, entries, order / rnt / roff, the pairs and keys of the split list -- is
+ * set to 0xff bytes, so a word of the result that still reads 0xffffffff was not written by this job.  Takes a free MSM slot for the duration of the call.
+ * KH_E_SORT_GAVE_UP: k_sort_fused gave up at a grid barrier (its blocks were not co-resident); nothing is retried on another path. */
+#define KH_E_SORT_GAVE_UP (-6)
+struct kh_msm_sort_args {
+    int curve, mont;
+    size_t n, k;
+    const uint64_t *scalars;
+    const uint8_t *inf; size_t inf_len;
+    size_t offset, stride, batch_stride;
+    int precomp_c, glv, wide, fused_off;
+    unsigned stage_entries, stage_maxpass, num_cus;
+};
+struct kh_msm_sort_echo {
+    uint32_t c, W, nb, precomp, glv, wide, sort, S, ngroups, nkeys, part_low, part_nblk, room, kmin, wide_og, bigcap, hot_nt, stage_now, part2_maxpass, ranked;
+    uint32_t max_tasks, max_entries;
+    uint8_t ktab[48];
+};
+struct kh_msm_sort_out {
+    uint32_t *digits; uint32_t *off; uint32_t *entries; uint32_t *toff; uint32_t *order; uint32_t *rnt; uint32_t *roff; uint32_t *counts;
+    uint32_t *ptot; uint32_t *xpairs; uint32_t *slist; uint32_t *big_keys; uint32_t *big_arrivals;
+    uint8_t *b29_zero;
+};
+typedef struct kh_msm_sort_args kh_msm_sort_args_t;
+typedef struct kh_msm_sort_echo kh_msm_sort_echo_t;
+typedef struct kh_msm_sort_out kh_msm_sort_out_t;
+int kh_debug_msm_sort(const kh_msm_sort_args_t *args, kh_msm_sort_echo_t *echo, const kh_msm_sort_out_t *out);
 
 /* ---- one process per GPU: the path's only collective, over RCCL / xGMI ----
  * A point-range-sharded MSM (BASELINE config 4) exchanges ONE partial point per rank: RCCL has no elliptic-curve reduction, so the "all-reduce" is an

@@ -152,5 +152,29 @@ int kh_debug_bucket_sums(int curve, int kind, size_t nkeys, const uint32_t* toff
     if ((rc = debug_bucket_sums(C, curve, kind, nkeys, dtoff.as<uint32_t>(), dpart.as<uint8_t>(), dbuckets.as<uint8_t>(), dbig.as<uint32_t>(), cap, dchunks.as<uint8_t>()))) return rc;
     return download_points(C, curve, dbuckets, nkeys, out_xy, out_inf);
 }
+int kh_debug_msm_sort(const kh_msm_sort_args_t* args, kh_msm_sort_echo_t* echo, const kh_msm_sort_out_t* out) {
+    KH_REQUIRE(args && echo && args->scalars, "kh_debug_msm_sort: null argument");
+    const kh_msm_sort_args_t& a = *args;
+    const size_t lim = (size_t)1 << 26;
+    KH_REQUIRE(a.curve == KH_CURVE_VESTA || a.curve == KH_CURVE_PALLAS, "unknown curve id %d", a.curve);
+    KH_REQUIRE(a.n >= 1 && a.n <= lim && a.k >= 1 && a.k <= 8, "kh_debug_msm_sort: n = %zu (1 .. 2^26), k = %zu (1 .. 8)", (size_t)a.n, (size_t)a.k);
+    KH_REQUIRE(a.precomp_c == 0 || (a.precomp_c >= 7 && a.precomp_c <= 16), "kh_debug_msm_sort: precomp_c = %d (0 or 7 .. 16)", a.precomp_c);
+    KH_REQUIRE(!a.glv || a.precomp_c, "kh_debug_msm_sort: glv needs window tables (precomp_c)");
+    KH_REQUIRE(!(a.wide && a.glv), "kh_debug_msm_sort: no wide table set over a glv basis");
+    KH_REQUIRE(a.num_cus <= 1024, "kh_debug_msm_sort: num_cus = %u (at most 1024)", a.num_cus);
+    KH_REQUIRE(a.offset <= lim && a.batch_stride <= lim && a.stride <= ((size_t)1 << 30), "kh_debug_msm_sort: offset, stride or batch_stride beyond any basis");
+    KH_REQUIRE(a.stride == 0 || a.stride >= a.offset + a.n, "kh_debug_msm_sort: stride %zu below offset + n = %zu", (size_t)a.stride, (size_t)(a.offset + a.n));
+    KH_REQUIRE(!a.inf || a.inf_len >= a.offset + (a.k - 1) * a.batch_stride + a.n, "kh_debug_msm_sort: %zu infinity bytes, the digits read %zu", (size_t)a.inf_len,
+               (size_t)(a.offset + (a.k - 1) * a.batch_stride + a.n));
+    int rc = ensure_init(); if (rc) return rc;
+    Context& C = ctx();
+    std::lock_guard<std::mutex> lk(C.mu);
+    MsmShape sh; MsmPlan P;
+    if ((rc = debug_msm_sort_plan(C, a, sh, P, echo))) return rc;
+    if (!out) return KH_OK;
+    const int si = acquire_slot(nullptr, C);               // (no waiting: a test hook, called with nothing in flight)
+    KH_REQUIRE(si >= 0, "kh_debug_msm_sort: no free MSM pipeline slot");
+    return debug_msm_sort_run(C, C.slot[si], a, sh, P, *echo, *out);
+}
 
 }  // extern "C"

@@ -558,7 +558,10 @@ k_len_rank(const u32* __restrict__ off, const u32* __restrict__ nt, size_t nkeys
 // flight fill at most half of the CUs, so every block is resident and the spin cannot deadlock).  Block (j, r) owns the r-th
 // contiguous chunk of group j's digit matrix [w][i]; its LDS histogram is one "slice" of the deterministic counting sort, the
 // keys are scanned with one (thread-contiguous keys, block scan, block totals) pass per barrier, and the same block scatters its
-// chunk.  Outputs are exactly those of the multi-launch path (off / toff / entries, empty hand-over and big-bucket lists).
+// chunk.  Outputs are those of the multi-launch path: off and toff word for word, per key the same set of entries (their order inside a bucket is
+// that of the LDS atomics on either path), empty hand-over and big-bucket lists; no length ranking, as on the multi-launch path below 2^22 digits
+// (tests/test_gpu_msm_sort.py runs both on the same scalars).  "Four" holds up to c = 15: at c = 16 four MSMs have 2^17 + 1 keys for 2^16 threads, one key
+// per thread more than FUSED_KPT, and the plan sends them to the multi-launch sort.
 // Bounded: the barrier assumes every block of the launch is resident.  Inside one process that holds (64 blocks of 64 KB LDS, two per
 // CU, even with all four pipeline slots in flight); with several PROCESSES on one GPU it need not, and resident blocks would spin on
 // peers that cannot be scheduled.  After `limit` ticks of the 100 MHz wall clock (or when another block has given up) the barrier
@@ -1849,30 +1852,39 @@ static void launch_narrow_tail(hipStream_t s, const NarrowTail& T, const uint8_t
         hipLaunchKernelGGL((k_marginal_fin<BF>), dim3(3, ngroups), dim3(64), 0, s, seg, T.mg, out);
 }
 
-// the launches of plan P (of shape sh) on slot C, whose workspaces msm_reserve has sized
+// where the task plan of a job's sort is: order == NULL (the fused sort, small jobs) = the key order, with roff = toff
+struct SortViews { u32 *len_hist, *cursor, *order, *rnt, *roff, *slist; };
+static SortViews sort_views(const MsmSlot& C, const MsmPlan& P) {
+    SortViews v;
+    v.len_hist = C.ws_order.as<u32>();                          // [MAX_K+1] histogram, [MAX_K+1] cursors, then order / rnt / roff
+    v.cursor = v.len_hist + (MAX_K + 1);
+    v.order = v.cursor + (MAX_K + 1);
+    v.rnt = v.order + (P.nkeys + 2);
+    v.roff = v.rnt + (P.nkeys + 2);
+    v.slist = C.ws_xlist.as<u32>() + P.slist_off;               // (wide) the split buckets' keys, behind the extra chunks' pairs
+    return v;
+}
+// Steps 1 - 4 and the task plan of plan P (of shape sh) on slot C: digits, the sort the plan names, task counts and their ranking.  msm_launch runs the
+// accumulation behind it; the test hook debug_msm_sort (end of this file) stops here and downloads what it wrote.  inf: the basis' infinity bytes (nullable).
+// order / roff: what the accumulation takes (sort_views' arrays, or NULL / toff where the key order is kept).
 template <class CFG>
-static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev, int mont, const MsmShape& sh, const MsmPlan& P, bool flag_on) {
-    typedef typename CFG::Base BF; typedef typename CFG::Scalar SF;
+static int msm_launch_sort(MsmSlot& C, const uint8_t* inf, const u64* scalars_dev, int mont, const MsmShape& sh, const MsmPlan& P, u32*& order, u32*& roff) {
+    typedef typename CFG::Scalar SF;
     hipStream_t s = C.stream;
-    const size_t n = sh.n, k = sh.k, nkeys = P.nkeys, ngroups = P.ngroups;
+    const size_t n = sh.n, k = sh.k, nkeys = P.nkeys;
     const bool wide = P.wide, fused = P.sort == SORT_FUSED;
-    const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
     int rc;
-    C.timer.begin(s);
     // 1 digits
     if (P.glv)
     hipLaunchKernelGGL((k_digits_glv<SF>), dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                       scalars_dev, basis.inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>());
+                       scalars_dev, inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>());
     else
     hipLaunchKernelGGL((k_digits<SF>), dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                       scalars_dev, basis.inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>(), (size_t)0, n);
+                       scalars_dev, inf, sh.offset, sh.batch_stride, n, mont, P.c, P.W, C.ws_digits.as<int32_t>(), (size_t)0, n);
     C.timer.mark("digits", s);
-    u32* len_hist = C.ws_order.as<u32>();                       // [MAX_K+1] histogram, [MAX_K+1] cursors, then order / rnt / roff
-    u32* cursor = len_hist + (MAX_K + 1);
-    u32* order = cursor + (MAX_K + 1);
-    u32* rnt = order + (nkeys + 2);
-    u32* roff = rnt + (nkeys + 2);
-    u32* const slist = C.ws_xlist.as<u32>() + P.slist_off;      // (wide) the split buckets' keys, behind the extra chunks' pairs
+    const SortViews v = sort_views(C, P);
+    u32 *const len_hist = v.len_hist, *const cursor = v.cursor, *const rnt = v.rnt, *const slist = v.slist;
+    order = v.order; roff = v.roff;
     if (fused) {
         // bounded spin of its grid barriers: 20 ms of the 100 MHz wall clock by default (a barrier normally waits < 50 us)
         static const unsigned long long fused_spin_ticks = 100ull * (unsigned long long)env_int("KH_FUSED_SPIN_US", 20000);
@@ -1936,6 +1948,23 @@ static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev,
         }
         C.timer.mark("tasks", s);
     }
+    return KH_OK;
+}
+
+// the launches of plan P (of shape sh) on slot C, whose workspaces msm_reserve has sized
+template <class CFG>
+static int msm_launch(MsmSlot& C, const MsmBasis& basis, const u64* scalars_dev, int mont, const MsmShape& sh, const MsmPlan& P, bool flag_on) {
+    typedef typename CFG::Base BF;
+    hipStream_t s = C.stream;
+    const size_t nkeys = P.nkeys, ngroups = P.ngroups;
+    const bool wide = P.wide, fused = P.sort == SORT_FUSED;
+    const void* const tab_pts = wide ? basis.wide_pts : basis.pts;
+    int rc;
+    C.timer.begin(s);
+    // 1 - 4 digits, sort, tasks
+    u32 *order = nullptr, *roff = nullptr;
+    if ((rc = msm_launch_sort<CFG>(C, basis.inf, scalars_dev, mont, sh, P, order, roff))) return rc;
+    u32* const slist = sort_views(C, P).slist;
     // 5 accumulate: the lazy 29-bit-limb kernel, then the exact kernel over the (almost always zero) tasks it handed over
     const u32* abort_dev = fused ? C.ws_sync.as<u32>() + 2 + 2 * FUSED_B + 32 : nullptr;     // the fused sort's give-up word (sort_gave_up)
     uint8_t* const b29 = wide ? C.ws_b29.as<uint8_t>() : nullptr;
@@ -2285,6 +2314,110 @@ int debug_bucket_sums(Context& C, int curve, int kind, size_t nkeys, const u32* 
     if (curve == KH_CURVE_VESTA) launch_bucket_sums<VestaCfg::Base>(C.stream, kind == 2, kind == 0 ? 4u : 16u, nullptr, toff, nkeys, partial, buckets, big, bigcap, chunks, nullptr);
     else launch_bucket_sums<PallasCfg::Base>(C.stream, kind == 2, kind == 0 ? 4u : 16u, nullptr, toff, nkeys, partial, buckets, big, bigcap, chunks, nullptr);
     KH_HIP(hipGetLastError());
+    return KH_OK;
+}
+// kh_debug_msm_sort: digits, sort and task plan of a job, through msm_launch_sort as msm_launch calls it, and nothing behind it.  The caller gives scalars and a
+// shape; every geometry value the kernels get is msm_plan()'s and every buffer msm_reserve()'s, as in msm_enqueue.
+// debug_msm_sort_plan: the shape msm_enqueue would fill for a basis with these facts, its plan, the echo.  Refuses what msm_plan refuses and jobs beyond 2^26 digits.
+int debug_msm_sort_plan(Context& C, const kh_msm_sort_args_t& a, MsmShape& sh, MsmPlan& P, kh_msm_sort_echo_t* echo) {
+    sh = MsmShape{};
+    sh.n = a.n; sh.k = a.k; sh.offset = a.offset; sh.flags = 0;
+    sh.precomp_c = a.precomp_c; sh.has_wide = a.wide != 0; sh.wide_c = a.wide ? MSM_WIDE_C : 0; sh.glv = a.glv != 0;
+    sh.stride = a.stride; sh.basis_n = a.offset + a.n; sh.batch_stride = a.batch_stride;
+    sh.num_cus = a.num_cus ? (int)a.num_cus : C.num_cus; sh.lds_per_cu = C.lds_per_cu; sh.lds_per_block = C.lds_per_block;
+    sh.wide_min_n = a.wide ? 0 : msm_wide_min_n(); sh.stage_entries = a.stage_entries; sh.stage_maxpass = a.stage_maxpass;
+    sh.fused_off = a.fused_off != 0 || C.fused_disabled;
+    const char* why = nullptr;
+    KH_REQUIRE(msm_plan(sh, P, &why) == 0, "kh_debug_msm_sort: %s (n=%zu k=%zu)", why, (size_t)a.n, (size_t)a.k);
+    KH_REQUIRE(P.M <= ((size_t)1 << 26), "kh_debug_msm_sort: %zu digits (n W k), at most 2^26", P.M);
+    memset(echo, 0, sizeof(*echo));
+    echo->c = (u32)P.c; echo->W = (u32)P.W; echo->nb = P.nb; echo->precomp = (u32)P.precomp; echo->glv = P.glv; echo->wide = P.wide; echo->sort = (u32)P.sort;
+    echo->S = (u32)P.S; echo->ngroups = (u32)P.ngroups; echo->nkeys = (u32)P.nkeys; echo->part_low = P.part_low; echo->part_nblk = P.part_nblk;
+    echo->room = P.room; echo->kmin = P.kmin; echo->wide_og = wide_og; echo->bigcap = (u32)P.bigcap; echo->hot_nt = WIDE_HOT_NT;
+    echo->stage_now = P.stage_now; echo->part2_maxpass = P.part2_maxpass; echo->max_tasks = (u32)P.max_tasks; echo->max_entries = (u32)P.M;
+    // the length ranking: 0 = the key order is kept, 1 = all keys ranked (order / rnt / roff), 2 = the wide path's interleaved per-partition order
+    echo->ranked = P.wide ? 2u : ((P.sort != SORT_FUSED && P.M >= ((size_t)1 << 22)) ? 1u : 0u);
+    memcpy(echo->ktab, P.ktab.k, 48);
+    return KH_OK;
+}
+int debug_msm_sort_run(Context& C, MsmSlot& S, const kh_msm_sort_args_t& a, const MsmShape& sh, const MsmPlan& P, const kh_msm_sort_echo_t& echo, const kh_msm_sort_out_t& o) {
+    hipStream_t s = S.stream;
+    const size_t nkeys = P.nkeys, M = P.M, n = a.n, k = a.k;
+    const bool wide = P.wide;
+    KH_REQUIRE(o.digits && o.off && o.entries && o.toff && o.counts, "kh_debug_msm_sort: null output");
+    KH_REQUIRE(echo.ranked != 1 || (o.order && o.rnt && o.roff), "kh_debug_msm_sort: this plan ranks the keys: order, rnt and roff are outputs");
+    KH_REQUIRE(!wide || (o.order && o.ptot && o.xpairs && o.slist && o.big_keys && o.big_arrivals && o.b29_zero), "kh_debug_msm_sort: null output of the wide path");
+    bool flag_on = false;
+    int rc = msm_reserve(C, S, P, flag_on); if (rc) return rc;
+    DevBuf dinf;
+    if ((rc = S.ws_scalars.reserve(k * n * 32))) return rc;
+    KH_HIP(hipMemcpyAsync(S.ws_scalars.p, a.scalars, k * n * 32, hipMemcpyHostToDevice, s));
+    if (a.inf) {
+        if ((rc = dinf.reserve(a.inf_len))) return rc;
+        KH_HIP(hipMemcpyAsync(dinf.p, a.inf, a.inf_len, hipMemcpyHostToDevice, s));
+    }
+    // every array the sort hands on starts as 0xff bytes: a word of a result that is still 0xffffffff was not written by this job.  (Not ws_sync, ws_handed and the
+    // lists' counters, which a job inherits in a defined state; ws_b29 gets 0x01 bytes, so that an identity record -- zeros -- is one pass B wrote.)
+    const SortViews v = sort_views(S, P);
+    KH_HIP(hipMemsetAsync(S.ws_digits.p, 0xff, M * sizeof(int32_t), s));
+    KH_HIP(hipMemsetAsync(S.ws_off.p, 0xff, (nkeys + 2) * sizeof(u32), s));
+    KH_HIP(hipMemsetAsync(S.ws_toff.p, 0xff, (nkeys + 2) * sizeof(u32), s));
+    KH_HIP(hipMemsetAsync(S.ws_ntask.p, 0xff, (nkeys + 2) * sizeof(u32), s));
+    KH_HIP(hipMemsetAsync(S.ws_entries.p, 0xff, (M + 1) * sizeof(u32), s));
+    KH_HIP(hipMemsetAsync(v.order, 0xff, 3 * (nkeys + 2) * sizeof(u32), s));
+    if (wide) {
+        KH_HIP(hipMemsetAsync(S.ws_xlist.as<u32>() + 2, 0xff, (3 * P.max_tasks + 6) * sizeof(u32), s));
+        KH_HIP(hipMemsetAsync(S.ws_b29.p, 0x01, nkeys * B29_BYTES, s));
+    }
+    S.timer.begin(s);
+    u32 *order = nullptr, *roff = nullptr;
+    rc = a.curve == KH_CURVE_VESTA ? msm_launch_sort<VestaCfg>(S, a.inf ? dinf.as<uint8_t>() : nullptr, S.ws_scalars.as<u64>(), a.mont, sh, P, order, roff)
+                                   : msm_launch_sort<PallasCfg>(S, a.inf ? dinf.as<uint8_t>() : nullptr, S.ws_scalars.as<u64>(), a.mont, sh, P, order, roff);
+    if (rc) return rc;
+    KH_HIP(hipGetLastError());
+    KH_HIP(hipStreamSynchronize(s));
+    if (P.sort == SORT_FUSED && S.host_abort && *S.host_abort) {       // reported, not retried on another path: the caller asked for THIS sort
+        *S.host_abort = 0;
+        KH_HIP(hipMemsetAsync(S.ws_sync.p, 0, (2 + 2 * FUSED_B + 32 + 2) * sizeof(u32), s));
+        KH_HIP(hipStreamSynchronize(s));
+        set_error("kh_debug_msm_sort: k_sort_fused gave up at a grid barrier (its blocks were not co-resident)");
+        return KH_E_SORT_GAVE_UP;
+    }
+    KH_REQUIRE((echo.ranked == 1) == (!wide && order != nullptr), "kh_debug_msm_sort: the echoed ranking is not what ran");
+    u32 cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    KH_HIP(hipMemcpy(o.digits, S.ws_digits.p, M * sizeof(int32_t), hipMemcpyDeviceToHost));
+    KH_HIP(hipMemcpy(o.off, S.ws_off.p, (nkeys + 1) * sizeof(u32), hipMemcpyDeviceToHost));
+    KH_HIP(hipMemcpy(o.toff, S.ws_toff.p, (nkeys + 1) * sizeof(u32), hipMemcpyDeviceToHost));
+    cnt[5] = o.off[nkeys]; cnt[6] = o.toff[nkeys];
+    const size_t ne = std::min<size_t>(cnt[5], M);          // (a count the sort got wrong is the caller's finding; it never sizes a copy)
+    if (ne) KH_HIP(hipMemcpy(o.entries, S.ws_entries.p, ne * sizeof(u32), hipMemcpyDeviceToHost));
+    KH_HIP(hipMemcpy(&cnt[0], S.ws_handed.p, sizeof(u32), hipMemcpyDeviceToHost));
+    KH_HIP(hipMemcpy(&cnt[1], S.ws_biglist.p, 2 * sizeof(u32), hipMemcpyDeviceToHost));
+    if (echo.ranked == 1) {
+        KH_HIP(hipMemcpy(o.order, v.order, nkeys * sizeof(u32), hipMemcpyDeviceToHost));
+        KH_HIP(hipMemcpy(o.rnt, v.rnt, (nkeys + 1) * sizeof(u32), hipMemcpyDeviceToHost));
+        KH_HIP(hipMemcpy(o.roff, v.roff, (nkeys + 1) * sizeof(u32), hipMemcpyDeviceToHost));
+    }
+    if (wide) {
+        KH_HIP(hipMemcpy(o.order, v.order, nkeys * sizeof(u32), hipMemcpyDeviceToHost));
+        KH_HIP(hipMemcpy(o.ptot, S.ws_ntask.p, k * PART_P * sizeof(u32), hipMemcpyDeviceToHost));
+        KH_HIP(hipMemcpy(&cnt[3], S.ws_xlist.p, 2 * sizeof(u32), hipMemcpyDeviceToHost));
+        const size_t nx = std::min<size_t>(cnt[3], P.max_tasks), ns = std::min<size_t>(cnt[4], nkeys), nbig = std::min<size_t>(cnt[1], nkeys);
+        if (nx) KH_HIP(hipMemcpy(o.xpairs, S.ws_xlist.as<u32>() + 2, 2 * nx * sizeof(u32), hipMemcpyDeviceToHost));
+        if (ns) KH_HIP(hipMemcpy(o.slist, v.slist, ns * sizeof(u32), hipMemcpyDeviceToHost));
+        if (nbig) {
+            KH_HIP(hipMemcpy(o.big_keys, S.ws_biglist.as<u32>() + 2, nbig * sizeof(u32), hipMemcpyDeviceToHost));
+            KH_HIP(hipMemcpy(o.big_arrivals, S.ws_biglist.as<u32>() + 2 + P.bigcap, nbig * sizeof(u32), hipMemcpyDeviceToHost));
+        }
+        std::vector<uint8_t> rec(nkeys * B29_BYTES);
+        KH_HIP(hipMemcpy(rec.data(), S.ws_b29.p, rec.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nkeys; i++) {
+            uint8_t any = 0;
+            for (size_t t = 0; t < B29_BYTES; t++) any |= rec[i * B29_BYTES + t];
+            o.b29_zero[i] = any == 0;
+        }
+    }
+    memcpy(o.counts, cnt, sizeof(cnt));
     return KH_OK;
 }
 

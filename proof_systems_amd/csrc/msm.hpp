@@ -44,6 +44,10 @@ int debug_bucket_tail(Context& C, int curve, int tail, int fin, unsigned c_or_nb
 size_t debug_bucket_sums_cap(size_t nkeys, size_t ntasks);
 int debug_bucket_sums(Context& C, int curve, int kind, size_t nkeys, const uint32_t* toff, const uint8_t* partial, uint8_t* buckets, uint32_t* big, size_t bigcap,
                       uint8_t* chunks);
+// kh_debug_msm_sort: the shape and plan of the caller's job with the echo (pure: nothing is reserved); then reservation, poison, the launches of
+// msm_launch_sort on slot S, the wait and the downloads
+int debug_msm_sort_plan(Context& C, const kh_msm_sort_args_t& a, MsmShape& sh, MsmPlan& P, kh_msm_sort_echo_t* echo);
+int debug_msm_sort_run(Context& C, MsmSlot& S, const kh_msm_sort_args_t& a, const MsmShape& sh, const MsmPlan& P, const kh_msm_sort_echo_t& echo, const kh_msm_sort_out_t& out);
 
 // ntt.hip
 int ntt_build_twiddles(Context& C, int field, unsigned logn, int inverse, uint64_t* tab);

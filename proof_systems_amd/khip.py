@@ -1824,3 +1824,56 @@ def debug_bucket_sums(curve: int, kind: int, toff, partial):
     oinf = np.zeros(nkeys, dtype=np.uint8)
     _check(_lib.kh_debug_bucket_sums(curve, kind, nkeys, t.ctypes.data_as(C.POINTER(C.c_uint32)), _p64(p), _p64(out), _p8(oinf)))
     return out, oinf
+
+
+MsmSortArgsC, MsmSortEchoC, MsmSortOutC = _STRUCTURES["kh_msm_sort_args_t"], _STRUCTURES["kh_msm_sort_echo_t"], _STRUCTURES["kh_msm_sort_out_t"]
+
+
+def debug_msm_sort(curve: int, scalars, k: int = 1, mont: bool = False, inf=None, offset: int = 0, stride: int = 0, batch_stride: int = 0, precomp_c: int = 0,
+                   glv: bool = False, wide: bool = False, fused_off: bool = False, stage_entries: int = 28672, stage_maxpass: int = 2, num_cus: int = 0,
+                   echo_only: bool = False):
+    """kh_debug_msm_sort: digits, sort and task plan of one job over `scalars` ((k * n, 4) uint64), nothing behind them.  Two calls: the first returns the
+    plan's echo, which sizes the outputs of the second.  -> dict: the echo's fields (ktab as a uint8 array), and unless echo_only: digits (k, W, n) int32,
+    off, toff, entries[:off[nkeys]], counts (8,), order / rnt / roff where ranked == 1, and for wide plans order, ptot, xpairs (counts[3], 2), slist,
+    big_keys, big_arrivals, b29_zero."""
+    sc = _c64(scalars, (-1, 4))
+    n = sc.shape[0] // k if k > 0 else 0                   # (k = 0 goes through: the library refuses it)
+    if k > 0 and n * k != sc.shape[0]:
+        raise ValueError(f"{sc.shape[0]} scalars for {k} MSMs")
+    a = MsmSortArgsC(curve=curve, mont=int(bool(mont)), n=n, k=k, scalars=_p64(sc), offset=offset, stride=stride, batch_stride=batch_stride, precomp_c=precomp_c,
+                     glv=int(bool(glv)), wide=int(bool(wide)), fused_off=int(bool(fused_off)), stage_entries=stage_entries, stage_maxpass=stage_maxpass, num_cus=num_cus)
+    if inf is not None:
+        inf = np.ascontiguousarray(inf, dtype=np.uint8)
+        a.inf, a.inf_len = _p8(inf), inf.size
+    e = MsmSortEchoC()
+    _check(_lib.kh_debug_msm_sort(C.byref(a), C.byref(e), None))
+    res = {f: getattr(e, f) for f, _t in MsmSortEchoC._fields_ if f != "ktab"}
+    res["ktab"] = np.array(list(e.ktab), np.uint8)
+    if echo_only:
+        return res
+    U32P = C.POINTER(C.c_uint32)
+    nkeys, W = e.nkeys, e.W
+    sizes = {"digits": k * W * n, "off": nkeys + 1, "entries": e.max_entries, "toff": nkeys + 1, "counts": 8}
+    if e.ranked == 1:
+        sizes.update(order=nkeys, rnt=nkeys + 1, roff=nkeys + 1)
+    if e.wide:
+        sizes.update(order=nkeys, ptot=256 * k, xpairs=2 * e.max_tasks, slist=nkeys, big_keys=nkeys, big_arrivals=nkeys)
+    bufs = {name: np.zeros(size, np.uint32) for name, size in sizes.items()}
+    o = MsmSortOutC(**{name: b.ctypes.data_as(U32P) for name, b in bufs.items()})
+    if e.wide:
+        bufs["b29_zero"] = np.zeros(nkeys, np.uint8)
+        o.b29_zero = _p8(bufs["b29_zero"])
+    e2 = MsmSortEchoC()
+    _check(_lib.kh_debug_msm_sort(C.byref(a), C.byref(e2), C.byref(o)))
+    if bytes(e2) != bytes(e):
+        raise KhError("kh_debug_msm_sort: the plan changed between the sizing call and the run")
+    cnt = bufs["counts"]
+    res.update(bufs)
+    res["digits"] = bufs["digits"].view(np.int32).reshape(k, W, n)
+    res["entries"] = bufs["entries"][:min(int(cnt[5]), e.max_entries)]
+    if e.wide:
+        res["xpairs"] = bufs["xpairs"][:2 * min(int(cnt[3]), e.max_tasks)].reshape(-1, 2)
+        res["slist"] = bufs["slist"][:min(int(cnt[4]), nkeys)]
+        res["big_keys"] = bufs["big_keys"][:min(int(cnt[1]), nkeys)]
+        res["big_arrivals"] = bufs["big_arrivals"][:min(int(cnt[1]), nkeys)]
+    return res
