@@ -848,7 +848,9 @@ int kh_last_timings(const char **names, float *ms, int cap);
  * that found another opening live on the same handle and went ahead beside it), "ipa_waited" (kh_ipa_begin calls that found every workspace of the handle
  * claimed; counted before the wait starts), "table_staged_words" (the uint32_t words of rows[] / cells tables that the gadget and wire calls and
  * kh_witness_schedule_create sent through the staging ring; kh_witness_schedule_run adds none), "point_codec_launches" (launches of the point
- * decompression kernel: one per kh_points_decompress(_dev), kh_srs_create_compressed and kh_proofs_from_wire call that got past its checks).  Unknown names read 0. */
+ * decompression kernel: one per kh_points_decompress(_dev), kh_srs_create_compressed, kh_proofs_from_wire, kh_proofs_from_msgpack and kh_verifier_index_from_msgpack call that got past its checks),
+ * "point_codec_encode_launches" (launches of the point compression kernel: one per kh_points_compress(_dev), kh_srs_get_g_compressed / kh_srs_write_file and
+ * per kh_proof_to_wire / kh_proof_to_msgpack / kh_verifier_index_to_msgpack call that writes).  Unknown names read 0. */
 uint64_t kh_counter(const char *name);
 
 /* Test hooks (field ops on the device; op: 0 mul, 1 add, 2 sub, 3 to_mont, 4 from_mont,
@@ -1381,6 +1383,42 @@ int kh_srs_create_from_file(int curve, const uint8_t *file, size_t len, size_t l
 typedef struct kh_wire_section kh_wire_section_t;
 struct kh_wire_section { const uint8_t *bytes; size_t count; };   /* count records of 33 bytes, or count elements of 32 */
 int kh_proofs_from_wire(int curve, const kh_wire_section_t *sections /* k x n_sections */, size_t n_sections, size_t k, kh_proof_t **out /* k */);
+
+/* ---- Serialised proofs and verifier indexes (rmp-serde msgpack) -----------------
+ * The bytes the reference sends and stores: `rmp_serde::to_vec` of a ProverProof (kimchi/src/proof.rs:134-195) and of a VerifierIndex
+ * (kimchi/src/verifier_index.rs:59-158) -- structs as arrays in declaration order, Option::None as nil, a point as a 33-byte bin (the record above), a
+ * field element as a 32-byte little-endian bin, the domain as one 236-byte bin.  The framing (csrc/msgpack_wire.hpp) reads nil, bool, positive fixint,
+ * uint8/16/32/64, bin8/16/32, fixarray and array16/32 and refuses every other type byte; it writes the shortest encoding, which is what rmp-serde writes:
+ * a file of the reference is reproduced byte for byte.  The RawFixture container of the reference's test files is not read here.
+ *
+ * Reading.  The structure is walked on the host first (csrc/proof_wire.hpp) and everything malformed is KH_E_INVALID before any device work, with *out (every
+ *   out[p]) set to NULL, the byte offset in the message ("offset 17: expected an array, found type byte 0xc4") and no launch counted: a short or overlong
+ *   buffer, a foreign type byte, a length beyond the bytes that remain, nesting deeper than 8, a wrong arity (15 w, 6 s, 15 coefficients, 5 lookup_sorted
+ *   slots, (L, R) pairs, ...), a bin that is not 32 / 33 bytes, evaluations whose zeta and zeta-omega lengths differ or differ from the proof's first
+ *   evaluation, witness commitments of unequal chunk counts, lookup evaluations that do not match the lookup commitments; for an index also size != 2^log_size,
+ *   a domain element that is not the library's own (n, 1/n, kh_domain_generator, its inverse, 1, 1, 1), max_poly_size != kh_srs_size(srs), joint_lookup_used
+ *   stated twice with different values, a lookup selector commitment present / absent against its feature bit, a runtime selector against uses_runtime_tables.
+ *   Then the points of the WHOLE call -- all k proofs with their previous-challenge commitments; all commitments of an index -- are decoded in ONE launch
+ *   (kh_counter("point_codec_launches") moves by exactly one per successful call); a bad record is KH_E_INVALID naming section, index and status, an element
+ *   >= p is KH_E_INVALID, and no handle is made.  What needs the other file (chunk counts and lookups against the index, rounds against the SRS) stays with
+ *   kh_verify.  kh_verifier_index_from_msgpack keeps the file's shifts and computes the digest, as kh_verifier_index_new does without one.
+ * The shape of a proof: ProofEvaluations is full of Options, so writing needs to know which are there (optional gates, lookup patterns, runtime tables,
+ *   lookups per row).  kh_prove* and kh_proofs_from_msgpack record it in the handle, and kh_prove_recursive / kh_prove_full(_runtime_dev) keep a copy of the
+ *   previous challenges there too (kh_proof_prev_challenges: the arrays kh_verify_item_t and kh_prove_recursive take, valid until kh_proof_free; n_prev = 0
+ *   when none).  A handle from kh_proof_from_sections or kh_proofs_from_wire has neither: give `shape`, an index of the proof's circuit.  Neither known, or
+ *   both and they disagree: KH_E_INVALID.
+ * Writing.  *len always receives the size needed; out == NULL is a size query (KH_OK, nothing launched); cap too small is KH_E_INVALID with nothing written.
+ *   Every point of the handle goes through ONE launch of the encoder: kh_counter("point_codec_encode_launches") (launches of the compression kernel, from
+ *   any caller) moves by one per call that writes.  kh_proof_to_wire: the proof's sections as kh_proofs_from_wire takes them, back to back in `out`,
+ *   sections[s] pointing into it (KH_PROOF_PUBLIC_COMM and KH_PROOF_CHALLENGES included when the handle has them).  kh_verifier_index_to_msgpack: an index
+ *   from kh_verifier_index_of carries no number of previous challenges, so the argument is written; any other index requires the argument to equal its own. */
+int kh_proofs_from_msgpack(int curve, const uint8_t *const *bytes, const size_t *lens, size_t k, kh_proof_t **out /* k */);
+int kh_proof_prev_challenges(const kh_proof_t *proof, const uint64_t **chals, const unsigned **rounds, const uint64_t **comm_xy, const uint8_t **comm_inf,
+                             const size_t **comm_chunks, size_t *n_prev);
+int kh_proof_to_wire(int curve, const kh_proof_t *proof, uint8_t *out, size_t cap, size_t *len, kh_wire_section_t *sections /* KH_PROOF_LOOKUP_RUNTIME_COMM + 1 */);
+int kh_proof_to_msgpack(int curve, const kh_proof_t *proof, const kh_verifier_index_t *shape /* nullable */, uint8_t *out, size_t cap, size_t *len);
+int kh_verifier_index_from_msgpack(kh_srs_t *srs, const uint8_t *bytes, size_t len, kh_verifier_index_t **out);
+int kh_verifier_index_to_msgpack(const kh_verifier_index_t *vix, unsigned prev_challenges, uint8_t *out, size_t cap, size_t *len);
 
 /* ---- Fiat-Shamir sponges (host side) --------------------------------------
  * The transcript of kimchi's prover / verifier: Kimchi Poseidon (width 3, rate 2, 55 full rounds, x^7) under

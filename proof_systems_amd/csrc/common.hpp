@@ -206,8 +206,8 @@ struct DeviceScope {               // run the rest of this scope on `device` (no
 };
 void collect_timings(Context& c, PhaseTimer& t);
 // process-wide event counters behind kh_counter (tests and tools read them: how often a rare path ran).  `name` must be one of COUNTER_NAMES.
-enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_LOOKUP_SORTED_DEV, CNT_IPA_CONCURRENT, CNT_IPA_WAITED, CNT_TABLE_STAGED_WORDS, CNT_POINT_CODEC_LAUNCHES, CNT_COUNT };
-static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds", "lookup_sorted_dev", "ipa_concurrent", "ipa_waited", "table_staged_words", "point_codec_launches"};
+enum CounterId { CNT_SPREAD_RETRY = 0, CNT_FUSED_RETRY, CNT_REBASE_LAUNCH, CNT_REBASE_SWITCH, CNT_REBASE_ABANDON, CNT_REBASED_ROUNDS, CNT_LOOKUP_SORTED_DEV, CNT_IPA_CONCURRENT, CNT_IPA_WAITED, CNT_TABLE_STAGED_WORDS, CNT_POINT_CODEC_LAUNCHES, CNT_POINT_CODEC_ENCODE_LAUNCHES, CNT_COUNT };
+static constexpr const char* COUNTER_NAMES[CNT_COUNT] = {"spread_retry", "fused_retry", "rebase_launch", "rebase_switch", "rebase_abandon", "rebased_rounds", "lookup_sorted_dev", "ipa_concurrent", "ipa_waited", "table_staged_words", "point_codec_launches", "point_codec_encode_launches"};
 std::atomic<uint64_t>& counter(CounterId id);
 
 // device exclusive scan of n u32 values (in may alias out); tmp is workspace

@@ -14,6 +14,7 @@
 #include "field.cuh"
 #include "field_sqrt.cuh"
 #include "api_internal.hpp"
+#include "wire_handles.hpp"
 
 namespace kh {
 
@@ -105,6 +106,7 @@ int points_compress_launch(Context& C, int curve, const uint64_t* xy_dev, const 
     C.timer.begin(C.stream);
     KH_CURVE_LAUNCH(curve, k_points_compress<F>, blocks_of(n, WAVE_BLOCK), dim3(WAVE_BLOCK), 0, C.stream, (const u64*)xy_dev, inf_dev, n, out_dev);
     C.timer.mark("points_compress", C.stream);
+    counter(CNT_POINT_CODEC_ENCODE_LAUNCHES)++;
     return KH_OK;
 }
 int points_decompress_launch(Context& C, int curve, const uint8_t* bytes_dev, size_t n, uint64_t* out_xy_dev, uint8_t* out_inf_dev, uint8_t* status_dev,
@@ -155,6 +157,93 @@ bool point_section(size_t s) {             // kh_proof_from_sections' rule
     return s <= KH_PROOF_PUBLIC_COMM || s == KH_PROOF_LR || s == KH_PROOF_DELTA || s == KH_PROOF_SG || s >= KH_PROOF_LOOKUP_SORTED_COMM;
 }
 }  // namespace
+
+namespace kh {
+// kh_proofs_from_wire.  extra (nullable): one more list of point records per proof -- the previous-challenge commitments of a serialised proof --, slot
+// n_sections of the proof: decoded in the same launch, handed back in extra_xy[p] / extra_inf[p] and not to kh_proof_from_sections.
+int proofs_from_wire(const char* call, int curve, const kh_wire_section_t* sections, size_t n_sections, size_t k, const kh_wire_section_t* extra,
+                     std::vector<uint64_t>* extra_xy, std::vector<uint8_t>* extra_inf, kh_proof_t** out) {
+    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "%s: unknown curve id %d", call, curve);
+    KH_REQUIRE(sections && out && k > 0 && n_sections > 0 && n_sections <= KH_PROOF_LOOKUP_RUNTIME_COMM + 1, "%s: null argument, no proof or more than %d sections",
+               call, KH_PROOF_LOOKUP_RUNTIME_COMM + 1);
+    KH_REQUIRE(!extra || (extra_xy && extra_inf), "%s: null argument", call);
+    const size_t slots = n_sections + 1;                                    // per proof: its sections, then the extra list
+    KH_REQUIRE(k < ((size_t)1 << 32) / slots, "%s: %zu proofs", call, k);
+    auto ignored = [&](size_t s) { return s == KH_PROOF_PUBLIC_COMM || s == KH_PROOF_CHALLENGES; };
+    auto is_points = [&](size_t s) { return s == n_sections || point_section(s); };
+    auto slot = [&](size_t j) -> kh_wire_section_t {
+        const size_t p = j / slots, s = j % slots;
+        if (s == n_sections) return extra ? extra[p] : kh_wire_section_t{nullptr, 0};
+        return sections[p * n_sections + s];
+    };
+    // every point of every proof, in (proof, section) order: first[j] = where the records of slot j begin
+    std::vector<size_t> first(k * slots + 1, 0);
+    size_t n_elems = 0;
+    for (size_t j = 0; j < k * slots; j++) {
+        const kh_wire_section_t in = slot(j);
+        const size_t s = j % slots;
+        KH_REQUIRE(in.bytes || !in.count || ignored(s), "%s: proof %zu section %zu has %zu entries and no bytes", call, j / slots, s, in.count);
+        KH_REQUIRE(in.count < ((size_t)1 << 32), "%s: proof %zu section %zu has %zu entries", call, j / slots, s, in.count);
+        const size_t cnt = ignored(s) ? 0 : in.count;
+        first[j + 1] = first[j] + (is_points(s) ? cnt : 0);
+        if (!is_points(s)) n_elems += cnt;
+    }
+    const size_t n_points = first.back();
+    KH_REQUIRE(n_points < ((size_t)1 << 32), "%s: %zu points, the limit is 2^32 - 1", call, n_points);
+    // the elements: little-endian canonical integers -> Montgomery limbs
+    const khost::Fld SF(khost::scalar_field_id(curve));
+    std::vector<uint64_t> elems(4 * n_elems);
+    std::vector<size_t> elem_first(k * slots, 0);
+    size_t e = 0;
+    for (size_t j = 0; j < k * slots; j++) {
+        const size_t s = j % slots;
+        elem_first[j] = e;
+        if (is_points(s) || ignored(s)) continue;
+        const kh_wire_section_t in = slot(j);
+        for (size_t i = 0; i < in.count; i++, e++) {
+            khost::fe v;
+            memcpy(v.l, in.bytes + 32 * i, 32);
+            KH_REQUIRE(!khost::geq(v, SF.f.p), "%s: proof %zu section %zu element %zu is not a canonical field element (>= p)", call, j / slots, s, i);
+            v = SF.to_mont(v);
+            memcpy(elems.data() + 4 * e, v.l, 32);
+        }
+    }
+    // the points: gathered, decoded in one launch
+    std::vector<uint8_t> records(n_points * KH_POINT_BYTES), inf(n_points), status(n_points);
+    std::vector<uint64_t> xy(8 * n_points);
+    for (size_t j = 0; j < k * slots; j++)
+        if (first[j + 1] > first[j]) memcpy(records.data() + first[j] * KH_POINT_BYTES, slot(j).bytes, (first[j + 1] - first[j]) * KH_POINT_BYTES);
+    int rc = ensure_init(); if (rc) return rc;
+    if (n_points && (rc = points_decompress_staged(curve, records.data(), n_points, xy.data(), inf.data(), status.data()))) return rc;
+    for (size_t j = 0; j < k * slots; j++)
+        for (size_t i = first[j]; i < first[j + 1]; i++) {
+            if (status[i] == KH_POINT_OK || status[i] == KH_POINT_INFINITY) continue;
+            if (j % slots == n_sections) set_error("%s: proof %zu previous-challenge commitment point %zu is %s", call, j / slots, i - first[j], point_status_name(status[i]));
+            else set_error("%s: proof %zu section %zu point %zu is %s", call, j / slots, j % slots, i - first[j], point_status_name(status[i]));
+            return KH_E_INVALID;
+        }
+    std::vector<kh_proof_t*> made(k, nullptr);
+    for (size_t p = 0; p < k && !rc; p++) {
+        kh_section_t secs[KH_PROOF_LOOKUP_RUNTIME_COMM + 1] = {};
+        for (size_t s = 0; s < n_sections; s++) {
+            const size_t j = p * slots + s;
+            const size_t cnt = sections[p * n_sections + s].count;
+            if (ignored(s) || !cnt) continue;
+            if (point_section(s)) secs[s] = kh_section_t{xy.data() + 8 * first[j], inf.data() + first[j], cnt};
+            else secs[s] = kh_section_t{elems.data() + 4 * elem_first[j], nullptr, cnt};
+        }
+        rc = kh_proof_from_sections(secs, n_sections, &made[p]);
+    }
+    if (rc) { for (kh_proof_t* p : made) kh_proof_free(p); return rc; }
+    for (size_t p = 0; p < k && extra; p++) {
+        const size_t j = p * slots + n_sections;
+        extra_xy[p].assign(xy.begin() + 8 * first[j], xy.begin() + 8 * first[j + 1]);
+        extra_inf[p].assign(inf.begin() + first[j], inf.begin() + first[j + 1]);
+    }
+    for (size_t p = 0; p < k; p++) out[p] = made[p];
+    return KH_OK;
+}
+}  // namespace kh
 
 extern "C" {
 
@@ -207,68 +296,7 @@ int kh_points_decompress_dev(int curve, const uint8_t* bytes_dev, size_t n, uint
 }
 
 int kh_proofs_from_wire(int curve, const kh_wire_section_t* sections, size_t n_sections, size_t k, kh_proof_t** out) {
-    const char* const call = "kh_proofs_from_wire";
-    KH_REQUIRE(curve == KH_CURVE_VESTA || curve == KH_CURVE_PALLAS, "%s: unknown curve id %d", call, curve);
-    KH_REQUIRE(sections && out && k > 0 && n_sections > 0 && n_sections <= KH_PROOF_LOOKUP_RUNTIME_COMM + 1, "%s: null argument, no proof or more than %d sections",
-               call, KH_PROOF_LOOKUP_RUNTIME_COMM + 1);
-    KH_REQUIRE(k < ((size_t)1 << 32) / n_sections, "%s: %zu proofs", call, k);
-    auto ignored = [](size_t s) { return s == KH_PROOF_PUBLIC_COMM || s == KH_PROOF_CHALLENGES; };
-    // every point of every proof, in (proof, section) order: first[j] = where the records of sections[j] begin
-    std::vector<size_t> first(k * n_sections + 1, 0);
-    size_t n_elems = 0;
-    for (size_t j = 0; j < k * n_sections; j++) {
-        const kh_wire_section_t& in = sections[j];
-        const size_t s = j % n_sections;
-        KH_REQUIRE(in.bytes || !in.count || ignored(s), "%s: proof %zu section %zu has %zu entries and no bytes", call, j / n_sections, s, in.count);
-        KH_REQUIRE(in.count < ((size_t)1 << 32), "%s: proof %zu section %zu has %zu entries", call, j / n_sections, s, in.count);
-        const size_t cnt = ignored(s) ? 0 : in.count;
-        first[j + 1] = first[j] + (point_section(s) ? cnt : 0);
-        if (!point_section(s)) n_elems += cnt;
-    }
-    const size_t n_points = first.back();
-    KH_REQUIRE(n_points < ((size_t)1 << 32), "%s: %zu points, the limit is 2^32 - 1", call, n_points);
-    // the elements: little-endian canonical integers -> Montgomery limbs
-    const khost::Fld SF(khost::scalar_field_id(curve));
-    std::vector<uint64_t> elems(4 * n_elems);
-    std::vector<size_t> elem_first(k * n_sections, 0);
-    size_t e = 0;
-    for (size_t j = 0; j < k * n_sections; j++) {
-        const size_t s = j % n_sections;
-        elem_first[j] = e;
-        if (point_section(s) || ignored(s)) continue;
-        for (size_t i = 0; i < sections[j].count; i++, e++) {
-            khost::fe v;
-            memcpy(v.l, sections[j].bytes + 32 * i, 32);
-            KH_REQUIRE(!khost::geq(v, SF.f.p), "%s: proof %zu section %zu element %zu is not a canonical field element (>= p)", call, j / n_sections, s, i);
-            v = SF.to_mont(v);
-            memcpy(elems.data() + 4 * e, v.l, 32);
-        }
-    }
-    // the points: gathered, decoded in one launch
-    std::vector<uint8_t> records(n_points * KH_POINT_BYTES), inf(n_points), status(n_points);
-    std::vector<uint64_t> xy(8 * n_points);
-    for (size_t j = 0; j < k * n_sections; j++)
-        if (first[j + 1] > first[j]) memcpy(records.data() + first[j] * KH_POINT_BYTES, sections[j].bytes, (first[j + 1] - first[j]) * KH_POINT_BYTES);
-    int rc = ensure_init(); if (rc) return rc;
-    if (n_points && (rc = points_decompress_staged(curve, records.data(), n_points, xy.data(), inf.data(), status.data()))) return rc;
-    for (size_t j = 0; j < k * n_sections; j++)
-        for (size_t i = first[j]; i < first[j + 1]; i++)
-            KH_REQUIRE(status[i] == KH_POINT_OK || status[i] == KH_POINT_INFINITY, "%s: proof %zu section %zu point %zu is %s", call, j / n_sections, j % n_sections,
-                       i - first[j], point_status_name(status[i]));
-    std::vector<kh_proof_t*> made(k, nullptr);
-    for (size_t p = 0; p < k && !rc; p++) {
-        kh_section_t secs[KH_PROOF_LOOKUP_RUNTIME_COMM + 1] = {};
-        for (size_t s = 0; s < n_sections; s++) {
-            const size_t j = p * n_sections + s;
-            if (ignored(s) || !sections[j].count) continue;
-            if (point_section(s)) secs[s] = kh_section_t{xy.data() + 8 * first[j], inf.data() + first[j], sections[j].count};
-            else secs[s] = kh_section_t{elems.data() + 4 * elem_first[j], nullptr, sections[j].count};
-        }
-        rc = kh_proof_from_sections(secs, n_sections, &made[p]);
-    }
-    if (rc) { for (kh_proof_t* p : made) kh_proof_free(p); return rc; }
-    for (size_t p = 0; p < k; p++) out[p] = made[p];
-    return KH_OK;
+    return proofs_from_wire("kh_proofs_from_wire", curve, sections, n_sections, k, nullptr, nullptr, nullptr, out);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include "env.hpp"
 #include "host_ec.hpp"
 #include "protocol_host.hpp"
+#include "wire_handles.hpp"
 #include "witness_lookup.hpp"
 
 namespace kh {
@@ -89,6 +90,10 @@ struct kh_proof {
     struct Sec { std::vector<uint64_t> limbs; std::vector<uint8_t> flags; size_t count = 0; bool points = false; };
     Sec sec[15];
     double phase[6] = {0, 0, 0, 0, 0, 0};
+    // for kh_proof_to_msgpack: which Options the serialised proof has (known to kh_prove* and kh_proofs_from_msgpack) and the previous challenges it was made
+    // with or read with.  Nothing of the proving or verifying path reads them.
+    kh_proof_wire::Shape shape;
+    kh::ProofPrev prev;
     void set_points(int s, const uint64_t* xy, const uint8_t* inf, size_t cnt) {
         sec[s].limbs.assign(xy, xy + 8 * cnt); sec[s].flags.assign(inf, inf + cnt); sec[s].count = cnt; sec[s].points = true;
     }
@@ -96,6 +101,13 @@ struct kh_proof {
         sec[s].limbs.resize(4 * cnt); if (cnt) memcpy(sec[s].limbs.data(), v, 32 * cnt); sec[s].flags.clear(); sec[s].count = cnt; sec[s].points = false;
     }
 };
+
+namespace kh {
+const kh_proof_wire::Shape& proof_shape(const kh_proof_t* proof) { return proof->shape; }
+void proof_set_shape(kh_proof_t* proof, const kh_proof_wire::Shape& shape) { proof->shape = shape; }
+const ProofPrev& proof_prev(const kh_proof_t* proof) { return proof->prev; }
+void proof_set_prev(kh_proof_t* proof, ProofPrev&& prev) { proof->prev = std::move(prev); }
+}  // namespace kh
 
 extern "C" {
 
@@ -1502,6 +1514,24 @@ static int prove_full_impl(kh_prover_index_t* ix, const uint64_t* witness, size_
     pr->set_elems(KH_PROOF_CHALLENGES, ch, lk ? 7 : 6);
     KP(kh_sync());                                   // every queued user of the buffers released below has finished
     mark();
+    {                                                // the shape of the serialised proof, and a copy of the previous challenges
+        static const char* const OPTIONAL_GATE_NAMES[6] = {"RangeCheck0", "RangeCheck1", "ForeignFieldAdd", "ForeignFieldMul", "Xor16", "Rot64"};
+        kh_proof_wire::Shape& sh = pr->shape;
+        for (int g : ix->optional)
+            for (int k = 0; k < 6; k++) if (!strcmp(kh_gate_name(g), OPTIONAL_GATE_NAMES[k])) sh.optional |= (uint8_t)(1u << k);
+        if (lk) {
+            sh.lookup = true; sh.runtime = has_rt; sh.max_per_row = (unsigned)lk->mpr;
+            for (int q : lk->pats) sh.patterns |= (uint8_t)(1u << q);
+        }
+        sh.known = true;
+        size_t nchal = 0, nchunk = 0;
+        for (size_t j = 0; j < n_prev; j++) { nchal += prev_rounds[j]; nchunk += prev_comm_chunks[j]; }
+        if (n_prev) {
+            pr->prev.chals.assign(prev_chals, prev_chals + 4 * nchal); pr->prev.rounds.assign(prev_rounds, prev_rounds + n_prev);
+            pr->prev.comm_xy.assign(prev_comm_xy, prev_comm_xy + 8 * nchunk); pr->prev.comm_inf.assign(prev_comm_inf, prev_comm_inf + nchunk);
+            pr->prev.comm_chunks.assign(prev_comm_chunks, prev_comm_chunks + n_prev);
+        }
+    }
     guard.p = nullptr;
     *out = pr;
     return KH_OK;
@@ -1538,6 +1568,14 @@ int kh_proof_phase_seconds(const kh_proof_t* proof, double* seconds, size_t cap)
     if (!proof || !seconds) { kh::set_error("kh_proof_phase_seconds: null argument"); return KH_E_INVALID; }
     for (size_t i = 0; i < cap && i < 6; i++) seconds[i] = proof->phase[i];
     return 6;
+}
+int kh_proof_prev_challenges(const kh_proof_t* proof, const uint64_t** chals, const unsigned** rounds, const uint64_t** comm_xy, const uint8_t** comm_inf,
+                             const size_t** comm_chunks, size_t* n_prev) {
+    if (!proof || !chals || !rounds || !comm_xy || !comm_inf || !comm_chunks || !n_prev) { kh::set_error("kh_proof_prev_challenges: null argument"); return KH_E_INVALID; }
+    const kh::ProofPrev& p = proof->prev;
+    *n_prev = p.rounds.size();
+    *chals = p.chals.data(); *rounds = p.rounds.data(); *comm_xy = p.comm_xy.data(); *comm_inf = p.comm_inf.data(); *comm_chunks = p.comm_chunks.data();
+    return KH_OK;
 }
 void kh_proof_free(kh_proof_t* proof) { delete proof; }
 

@@ -24,6 +24,7 @@
 #include "gate_batch.hpp"
 #include "host_ec.hpp"
 #include "protocol_host.hpp"
+#include "wire_handles.hpp"
 
 namespace kh {
 void prover_index_facts(const kh_prover_index_t* ix, kh_srs_t** srs, unsigned* public_inputs, const int** optional_gates, size_t* n_optional);   // prover.cpp
@@ -72,6 +73,27 @@ struct kh_verifier_index {
     size_t mpr = 0, mjs = 0, width = 0;
     std::vector<int> pats;
 };
+
+namespace kh {
+// what kh_verifier_index_to_msgpack and kh_proof_to_msgpack's `shape` argument read of an index (wire_handles.hpp)
+void vindex_view(const kh_verifier_index_t* vx, VindexView* out) {
+    VindexView& v = *out;
+    v = VindexView{};
+    v.srs = vx->srs; v.curve = vx->curve; v.log2_n = vx->logn;
+    v.zk_rows = vx->zk; v.public_inputs = vx->pub; v.prev_challenges = vx->nprev; v.chunks = vx->nch; v.any_prev = vx->any_prev;
+    for (int slot : vx->optional_slot) v.optional |= (uint8_t)(1u << slot);
+    for (int q : vx->pats) v.patterns |= (uint8_t)(1u << q);
+    v.lookup = vx->lookup; v.joint_lookup_used = vx->joint_used; v.runtime = vx->has_rt; v.max_per_row = vx->mpr; v.max_joint_size = vx->mjs;
+    v.shifts = vx->shifts[0].l;
+    for (int s = 0; s <= KH_VINDEX_LOOKUP_INFO; s++)
+        if (s != KH_VINDEX_SHIFTS && s != KH_VINDEX_DIGEST && s != KH_VINDEX_LOOKUP_INFO) v.sec[s] = kh_section_t{vx->sec[s].xy.data(), vx->sec[s].inf.data(), vx->sec[s].count};
+}
+kh_proof_wire::Shape vindex_shape(const VindexView& v) {
+    kh_proof_wire::Shape sh;
+    sh.known = true; sh.optional = v.optional; sh.patterns = v.patterns; sh.lookup = v.lookup; sh.runtime = v.runtime; sh.max_per_row = (unsigned)v.max_per_row;
+    return sh;
+}
+}  // namespace kh
 
 namespace {
 int vindex_build(const char* who, kh_srs_t* srs, unsigned log2_n, unsigned zk_rows, unsigned public_inputs, unsigned prev_challenges, bool any_prev,

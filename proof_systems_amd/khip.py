@@ -499,7 +499,7 @@ def msm_points_batch(curve: int, xy, scalars, inf=None, mont: bool = True):
 
 def counter(name: str) -> int:
     """Process-wide event counter of the library (kh_counter): spread_retry, fused_retry, rebase_launch, rebase_switch, rebase_abandon, rebased_rounds, lookup_sorted_dev,
-    ipa_concurrent, ipa_waited, table_staged_words, point_codec_launches."""
+    ipa_concurrent, ipa_waited, table_staged_words, point_codec_launches, point_codec_encode_launches."""
     return int(_lib.kh_counter(name.encode()))
 
 
@@ -1297,6 +1297,22 @@ class NativeProverIndex:
         kh_prove_full_runtime_dev, read in stream order).  witness: (15, rows, 4) limbs on the host, or witness_dev: DevBuf with the padded columns.  randomness:
         (k, 4) limbs in the reference's draw order, or None (the library draws from the OS).  prev: [(chals (k, 4) limbs, (xy (chunks, 8), inf
         (chunks,)))].  Returns ({section: limbs[, flags]}, {phase: seconds})."""
+        pr = self._prove(witness, witness_dev, randomness, flags, prev, runtime, runtime_dev)
+        try:
+            out = _proof_sections(pr)
+            ph = (C.c_double * 6)()
+            _lib.kh_proof_phase_seconds(pr, ph, 6)
+            return out, dict(zip(PROOF_PHASES, list(ph)))
+        finally:
+            _lib.kh_proof_free(pr)
+
+    def prove_handle(self, witness=None, witness_dev=None, randomness=None, flags: int = PROVE_CHECK, prev=(), runtime=None, runtime_dev=None):
+        """`prove`, returning the proof as a Proof handle: it carries its shape and previous challenges, so Proof.to_msgpack needs nothing else"""
+        pr = Proof.__new__(Proof)
+        pr._h = self._prove(witness, witness_dev, randomness, flags, prev, runtime, runtime_dev)
+        return pr
+
+    def _prove(self, witness, witness_dev, randomness, flags, prev, runtime, runtime_dev):
         pr = C.c_void_p()
         w = _c64(witness, (15, -1, 4)) if witness is not None else None
         rnd = _c64(randomness, (-1, 4)) if randomness is not None else None
@@ -1315,13 +1331,7 @@ class NativeProverIndex:
                   C.c_void_p(witness_dev.ptr) if witness_dev is not None else None, _p64(rnd) if rnd is not None else None,
                   rnd.shape[0] if rnd is not None else 0, flags, _p64(chals) if m else None, rounds,
                   _p64(cxy) if m else None, _p8(cinf) if m else None, cch, m, *rt_args, C.byref(pr)))
-        try:
-            out = _proof_sections(pr)
-            ph = (C.c_double * 6)()
-            _lib.kh_proof_phase_seconds(pr, ph, 6)
-            return out, dict(zip(PROOF_PHASES, list(ph)))
-        finally:
-            _lib.kh_proof_free(pr)
+        return pr
 
     def free(self):
         if self._h:
@@ -1357,6 +1367,26 @@ def _section_array(sections: dict, names: dict):
     return arr, keep
 
 
+def _sized(call, as_array: bool = False):
+    """the calling convention of the writers (out, cap, len): a size query (out = NULL), then the call that writes into exactly that many bytes"""
+    ln = C.c_size_t(0)
+    _check(call(None, 0, C.byref(ln)))
+    buf = np.zeros(max(ln.value, 1), dtype=np.uint8)
+    _check(call(buf.ctypes.data_as(U8P), ln.value, C.byref(ln)))
+    return buf[:ln.value] if as_array else buf[:ln.value].tobytes()
+
+
+def proofs_from_msgpack_raw(curve: int, blobs, out_before: int = 0):
+    """kh_proofs_from_msgpack without raising: (return code, the k entries of `out` afterwards)"""
+    k = len(blobs)
+    arrs = [np.frombuffer(bytes(b), dtype=np.uint8) if len(b) else np.zeros(1, np.uint8) for b in blobs]
+    ptrs = (U8P * max(k, 1))(*[a.ctypes.data_as(U8P) for a in arrs])
+    lens = (C.c_size_t * max(k, 1))(*[len(b) for b in blobs])
+    out = (C.c_void_p * max(k, 1))(*([out_before] * max(k, 1)))
+    rc = _lib.kh_proofs_from_msgpack(curve, ptrs, lens, k, out)
+    return rc, [out[p] or 0 for p in range(k)]
+
+
 class VerifierIndex:
     """kh_verifier_index_new: a verifier index from sections in the layout NativeProverIndex.verifier_index() returns (absent / None = not there; shifts and
     digest are computed when absent); VerifierIndex.of(native_index): kh_verifier_index_of."""
@@ -1375,6 +1405,20 @@ class VerifierIndex:
         _check(_lib.kh_verifier_index_of(index._h, C.byref(self._h)))
         self._keep = index._keep[:1]
         return self
+
+    @classmethod
+    def from_msgpack(cls, srs, data: bytes):
+        """kh_verifier_index_from_msgpack: the index a serialised VerifierIndex (rmp-serde) describes, over `srs`; its commitments decoded in one launch"""
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        b = np.frombuffer(bytes(data), dtype=np.uint8)
+        _check(_lib.kh_verifier_index_from_msgpack(srs._h, b.ctypes.data_as(U8P), b.size, C.byref(self._h)))
+        self._keep = (srs,)
+        return self
+
+    def to_msgpack(self, prev_challenges: int = 0) -> bytes:
+        """kh_verifier_index_to_msgpack: the bytes the reference writes for this index (a size query, then the call that writes)"""
+        return _sized(lambda out, cap, ln: _lib.kh_verifier_index_to_msgpack(self._h, prev_challenges, out, cap, ln))
 
     def digest(self):
         out = np.zeros(4, dtype=np.uint64)
@@ -1397,6 +1441,51 @@ class Proof:
     def sections(self):
         """the proof's sections as NativeProverIndex.prove returns them (kh_proof_section)"""
         return _proof_sections(self._h)
+
+    @classmethod
+    def from_msgpack(cls, curve: int, data):
+        """kh_proofs_from_msgpack: a Proof from the bytes of one serialised ProverProof, or [Proof] from a list of them -- then the points of all of them are
+        decoded in one launch.  Malformed bytes raise KhError naming the byte offset, or section, index and status; no proof is made."""
+        many = isinstance(data, (list, tuple))
+        rc, handles = proofs_from_msgpack_raw(curve, list(data) if many else [data])
+        _check(rc)
+        made = []
+        for h in handles:
+            pr = cls.__new__(cls)
+            pr._h = C.c_void_p(h)
+            made.append(pr)
+        return made if many else made[0]
+
+    def to_msgpack(self, curve: int, shape: "VerifierIndex" = None) -> bytes:
+        """kh_proof_to_msgpack: the bytes the reference writes for this proof.  shape: an index of the proof's circuit, needed by a handle that does not know
+        which optional evaluations it has (one from sections or from wire bytes)."""
+        return _sized(lambda out, cap, ln: _lib.kh_proof_to_msgpack(curve, self._h, shape._h if shape is not None else None, out, cap, ln))
+
+    def to_wire(self, curve: int):
+        """kh_proof_to_wire: {section name: bytes} in the form proofs_from_wire takes (count x 33 compressed records / count x 32 little-endian integers)"""
+        secs = (WireSectionC * len(PROOF_SECTIONS))()
+        buf = _sized(lambda out, cap, ln: _lib.kh_proof_to_wire(curve, self._h, out, cap, ln, secs), as_array=True)
+        base = buf.ctypes.data
+        out = {}
+        for name, sid in PROOF_SECTIONS.items():
+            width = 32 if name in _ELEMENT_SECTIONS else POINT_BYTES
+            off = C.cast(secs[sid].bytes, C.c_void_p).value
+            out[name] = bytes(buf[off - base: off - base + width * secs[sid].count]) if secs[sid].count else b""
+        return out
+
+    def prev_challenges(self):
+        """kh_proof_prev_challenges: [(chals (rounds, 4) limbs, (xy (chunks, 8), inf (chunks,)))] as `prove` and `verify` take them"""
+        ch, xy = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        rounds, inf, chunks, n = C.POINTER(C.c_uint)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_size_t)(), C.c_size_t(0)
+        _check(_lib.kh_proof_prev_challenges(self._h, C.byref(ch), C.byref(rounds), C.byref(xy), C.byref(inf), C.byref(chunks), C.byref(n)))
+        out, cpos, ppos = [], 0, 0
+        for j in range(n.value):
+            r, c = rounds[j], chunks[j]
+            out.append((np.array([[ch[4 * (cpos + i) + l] for l in range(4)] for i in range(r)], dtype=np.uint64).reshape(r, 4),
+                        (np.array([[xy[8 * (ppos + i) + l] for l in range(8)] for i in range(c)], dtype=np.uint64).reshape(c, 8),
+                         np.array([inf[ppos + i] for i in range(c)], dtype=np.uint8))))
+            cpos += r; ppos += c
+        return out
 
     def free(self):
         if self._h:
